@@ -1,25 +1,30 @@
 #!/usr/bin/env python3
 """CSS real-time-factor benchmark (BASELINE.json metric) on 1..8 MI355X of one node.
 
-    python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times exactly K steps, and prints the headline (`value`, `ms_per_step`, `dtype`).  `--full` adds
+everything else listed below (repeated timed regions, the other arithmetic mode and workloads, rooflines, parity checks, the CPU
+baseline).  `--dump-outputs DIR` writes what the last timed step returned to its caller as DIR/<name>.npy (float32; a larger
+result is reduced to a fixed, seeded sample of at most 64 MB), so that two builds can be compared output for output.
 
 One "step" = one pass of the CSS hot path (css/css.py::separate_and_stitch equivalent: STFT -> Conformer mask
 estimator -> WTA/SCM/MVDR -> PIT stitch -> activity gate -> iSTFT) over one synthetic 7-channel 16 kHz meeting,
 timed from the PCM in (page-locked) HOST memory to the separated waveforms in host memory: both PCIe legs are
 inside the timed region (SURVEY.md 8(d) "Metric").  `value` = audio seconds separated per wall second.  At N = 1 the K
 steps are K sessions in a queue (css_run_enqueue ... css_wait: a session's PCIe legs run under its neighbours' kernels);
-the same K sessions as K synchronous css_run calls are the `synchronous_call` key of the line.
+with --full, the same K sessions as K synchronous css_run calls are the `synchronous_call` key of the line.
 
-  N = 1   BASELINE.json configs[1]: the 60 s meeting (40 segments).  The same line also carries the 30-min meeting of
+  N = 1   BASELINE.json configs[1]: the 60 s meeting (40 segments).  With --full the line also carries the 30-min meeting of
           configs[3] on this one GPU (`meeting_1800s`), the device-resident figure, the exact-float32 arithmetic mode,
           the roofline of the dominant kernel, the memory-bound kernels' GB/s, and the CPU baseline.
   N > 1   BASELINE.json configs[3]: ONE fixed 1800 s meeting (1209 segments), strong-scaled: sharded by sliding-window
           segment across the N ranks with the three small RCCL all-gathers of notsofar1-challenge_amd/parallel.py (PIT
           costs, activity bits, one 256-sample seam block per stream).  Every rank uploads only the samples of its own
           segments, piece by piece under the stages, and finishes and downloads only its own range of the result.
-          Rank 0 also times the same meeting alone on its GPU after the timed region (`single_gpu_same_workload`), so
+          With --full, rank 0 also times the same meeting alone on its GPU after the timed region (`single_gpu_same_workload`), so
           that every line compares like with like.
 
 Weights: v1.0-MC architecture (D=512, H=8, 18 blocks, 1799 inputs), seeded portable random init with the
@@ -65,6 +70,23 @@ def emit_record(obj):
     line = (json.dumps(obj) + "\n").encode()
     sys.stdout.flush()
     os.write(_REAL_STDOUT if _REAL_STDOUT is not None else 1, line)
+
+
+DUMP_BYTES = 64_000_000   # --dump-outputs, all files together
+
+
+def dump_outputs(path, arrays, seed=0):
+    """--dump-outputs: each [rows, samples] array as <path>/<name>.npy in float32.  An array over its share of DUMP_BYTES keeps
+    a seeded sample of its sample positions (sorted; the same positions for the same shape on every run)."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // len(arrays) - 4096   # (room for the .npy header)
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float32)
+        if a.nbytes > share:
+            keep = share // (a.itemsize * a.shape[0])
+            a = a[:, np.sort(np.random.default_rng(seed).choice(a.shape[1], keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+        log(f"--dump-outputs: {name}.npy {a.shape} float32")
 
 
 def pkg(name):
@@ -271,17 +293,25 @@ def main():
     ap.add_argument("--max-batch", type=int, default=256,
                     help="segments per batched mask-estimator pass (the split-f16 mode keeps its batches to 128 segments of 3 s "
                          "by itself: css_set_tuning split_batch_rows)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: repeated timed regions, the split-f16 mode, other call forms and workloads, rooflines, "
+                         "parity checks, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the waveforms of the last timed step as DIR/<name>.npy (float32, at most 64 MB)")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=60.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-long", action="store_true", help="N = 1: skip the 30-min meeting")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-long", action="store_true", help="--full, N = 1: skip the 30-min meeting")
     ap.add_argument("--lanes", type=int, default=0, help="kernel chains per mask-estimator batch (0 = the library's default)")
     ap.add_argument("--queue-group", type=int, default=0,
                     help="queued sessions merged into one mask-estimator batch (css_set_queue_group; 0 = the library's default, 1 = none)")
-    ap.add_argument("--min-seconds", type=float, default=5.0,
-                    help="N = 1: the timed regions (exactly K steps each) are repeated until this much has been timed in total")
+    ap.add_argument("--min-seconds", type=float, default=None,
+                    help="N = 1: the timed regions (exactly K steps each) are repeated until this much has been timed in total "
+                         "(default: 5 with --full, else one region)")
     ap.add_argument("--tune", action="append", default=[], metavar="NAME=VALUE",
                     help="css_set_tuning options of the handle (A/B runs), e.g. --tune tail_pieces=2")
     args = ap.parse_args()
+    if args.min_seconds is None:
+        args.min_seconds = 5.0 if args.full else 0.0
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N` (how the driver starts a bench): this process becomes the launcher of N ranks
@@ -461,17 +491,49 @@ def main():
         def rec_n(el, steps, note):
             return {"ms_per_step": round(1e3 * el / steps, 3), "value": round(seconds * steps / el, 2), "note": note}
 
-        # the headline is the library's default arithmetic = the reference's own (float32 operands), as at N = 1; the opt-in
-        # split-f16 mode is timed first and reported beside it (`split_f16`, `value_split_f16`)
-        h.set_linear_mode("split_f16")
-        step("all"); barrier()   # initialisation, not a step: device buffers, communicator channels, index maps
-        el_split = timed_steps("all", args.steps, args.warmup)
-        assert torch.isfinite(out_host).all()
-        h.sync(); barrier()
+        # the headline is the library's default arithmetic = the reference's own (float32 operands), as at N = 1; with --full the
+        # opt-in split-f16 mode is timed first and reported beside it (`split_f16`, `value_split_f16`)
+        if args.full:
+            h.set_linear_mode("split_f16")
+            step("all"); barrier()   # initialisation, not a step: device buffers, communicator channels, index maps
+            el_split = timed_steps("all", args.steps, args.warmup)
+            assert torch.isfinite(out_host).all()
+            h.sync(); barrier()
         h.set_linear_mode("exact_f32")
         step("all"); barrier()
         el_all = timed_steps("all", args.steps, args.warmup)
         assert torch.isfinite(out_host).all()
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {"waveforms": full_dev.cpu().numpy()})   # the complete streams every rank holds
+        ms_all = 1e3 * el_all / args.steps
+        result.update({
+            "value": round(seconds * args.steps / el_all, 2), "ms_per_step": round(ms_all, 3),
+            "scaling": "strong", "dtype": dtype_of[h.linear_mode()],
+            "config": {"workload": f"synthetic 7-ch 16 kHz {seconds:g} s meeting ({nseg} segments of 3 s / 1.5 s hop), "
+                                   f"Conformer-CSS v1.0-MC (18 blocks, D=512) + MVDR, host PCM -> host waveforms",
+                       "segments": nseg, "segments_per_rank": me.seg_hi - me.seg_lo,
+                       "sharding": f"{world} ranks x segment ranges (one halo segment per seam), each rank uploads its own "
+                                   f"samples; all-gathers over {'RCCL' if backend == 'nccl' else backend}: PIT costs (72 B / "
+                                   f"boundary), activity bits (3 B / frame), then the separated waveform shards (12 B / sample: "
+                                   f"every GPU ends with the complete streams in HBM); each rank writes its own range of the "
+                                   f"result to page-locked host memory",
+                       "gather": "all"},
+            "value_is": "gather_all (waveform shards all-gathered over the process group and joined on every GPU; the ranks' "
+                        "host buffers together hold the result)",
+            "collective": evidence,
+        })
+
+        def finish():
+            dist.barrier()
+            if rank == 0:
+                emit_record(result)
+            be.close()
+            sep.close()
+            dist.destroy_process_group()
+
+        if not args.full:
+            finish()
+            return
         el_range = timed_steps("range", args.steps, max(args.warmup, 1))
         assert torch.isfinite(out_host).all()
         el_r0 = timed_steps("all_rank0", max(args.steps // 2, 3), 1)
@@ -511,8 +573,8 @@ def main():
         roof = gemm_roofline(t_prof, h.linear_mode(), ks_prof)
         roof["measured_on"] = f"rank 0's shard ({me.seg_hi - me.seg_lo} segments) during one sharded step"
 
-        # the sharded result equals the fused single-GPU run, bit for bit -- checked by EVERY N > 1 run after its timed regions
-        # (CSS_BENCH_CHECK=0 skips it): the first real multi-GPU run is also a correctness run
+        # the sharded result equals the fused single-GPU run, bit for bit -- checked by EVERY N > 1 --full run after its timed
+        # regions (CSS_BENCH_CHECK=0 skips it): the first real multi-GPU run is also a correctness run
         if os.environ.get("CSS_BENCH_CHECK", "1") != "0":
             ref = h.run(np.ascontiguousarray(mix[0]), run_cfg)
             step("range"); barrier()
@@ -529,21 +591,7 @@ def main():
             result["parity_checked"] = bool(ok.item() == 1.0)
             result["parity"] = {"sharded_equals_fused_single_gpu_bit_for_bit_on_every_rank": result["parity_checked"],
                                 "compared": "each rank's own range via the seam exchange, via the waveform all-gather, and the all-gathered whole"}
-        ms_all = 1e3 * el_all / args.steps
         result.update({
-            "value": round(seconds * args.steps / el_all, 2), "ms_per_step": round(ms_all, 3),
-            "scaling": "strong", "dtype": dtype_of[h.linear_mode()],
-            "config": {"workload": f"synthetic 7-ch 16 kHz {seconds:g} s meeting ({nseg} segments of 3 s / 1.5 s hop), "
-                                   f"Conformer-CSS v1.0-MC (18 blocks, D=512) + MVDR, host PCM -> host waveforms",
-                       "segments": nseg, "segments_per_rank": me.seg_hi - me.seg_lo,
-                       "sharding": f"{world} ranks x segment ranges (one halo segment per seam), each rank uploads its own "
-                                   f"samples; all-gathers over {'RCCL' if backend == 'nccl' else backend}: PIT costs (72 B / "
-                                   f"boundary), activity bits (3 B / frame), then the separated waveform shards (12 B / sample: "
-                                   f"every GPU ends with the complete streams in HBM); each rank writes its own range of the "
-                                   f"result to page-locked host memory",
-                       "gather": "all"},
-            "value_is": "gather_all (waveform shards all-gathered over the process group and joined on every GPU; the ranks' "
-                        "host buffers together hold the result)",
             "gather_range": rec_n(el_range, args.steps, "one 256-sample seam block per stream crosses between neighbours instead "
                                                         "of the waveform all-gather; same result in host memory"),
             "gather_all_rank0_download": rec_n(el_r0, max(args.steps // 2, 3), "as `value`, but rank 0 alone downloads the complete "
@@ -559,7 +607,6 @@ def main():
                 "largest_phase": max(zip(phase_ms["all"]["max_over_ranks_ms"], phase_ms["all"]["phases"]))[1],
                 "note": "sum over the phases of the maximum over ranks (upload of the first piece, segments, cost exchange, scan + "
                         "mask overlap-add, activity exchange, gate + synthesis, waveform exchange, download)"},
-            "collective": evidence,
             "roofline": roof,
             "clocks": gpu_clocks(),
             "value_is_arithmetic": "CSS_LINEAR_EXACT_F32 (float32 operands): the library's default and the reference's operand precision; the opt-in split-f16 mode: `split_f16`",
@@ -585,12 +632,7 @@ def main():
             result["speedup_vs_1gpu_same_workload"] = round(ms1 / ms_all, 3)
             result["split_f16"]["single_gpu_same_workload"] = {"ms_per_step": round(ms1_split, 3), "value": round(seconds / (ms1_split * 1e-3), 2),
                                                                 "speedup": round(ms1_split / (1e3 * el_split / args.steps), 3)}
-        dist.barrier()
-        if rank == 0:
-            emit_record(result)
-        be.close()
-        sep.close()
-        dist.destroy_process_group()
+        finish()
         return
 
     # ================================================================================================ N = 1
@@ -604,7 +646,8 @@ def main():
         h.set_lanes(args.lanes)
     if args.queue_group:
         h.set_queue_group(args.queue_group)
-    result["clocks_at_start"] = gpu_clocks()
+    if args.full:
+        result["clocks_at_start"] = gpu_clocks()
     for kv in args.tune:
         name, _, val = kv.partition("=")
         h.set_tuning(name, int(val))
@@ -613,8 +656,9 @@ def main():
     out_pin = L.pinned_empty((S, int(plan.n_out)), np.float32)
     out_pin2 = L.pinned_empty((S, int(plan.n_out)), np.float32)
     outs = (out_pin, out_pin2)
-    pcm_dev = torch.from_numpy(np.ascontiguousarray(mix[0])).to(dev)
-    wav_dev = torch.empty((S, plan.n_out), dtype=torch.float32, device=dev)
+    if args.full:   # the device-resident and profiled passes
+        pcm_dev = torch.from_numpy(np.ascontiguousarray(mix[0])).to(dev)
+        wav_dev = torch.empty((S, plan.n_out), dtype=torch.float32, device=dev)
     torch.cuda.synchronize()
     group_limit = args.queue_group if args.queue_group else 8
     split_rows = dict(kv.partition("=")[::2] for kv in args.tune).get("split_batch_rows")
@@ -700,22 +744,30 @@ def main():
         """The metric in one arithmetic mode: K queued sessions, each host -> host (css_run_enqueue ... css_wait), exactly K
         steps per timed region, regions repeated until `min_seconds` have been timed, the MEDIAN region is the value; the
         same sessions as synchronous calls and device-resident; the dominant kernel's roofline on the headline's own
-        schedule (the shared estimator batch) and on one session alone."""
+        schedule (the shared estimator batch) and on one session alone.  Without --full: the timed regions alone."""
         h.set_linear_mode(mode)
         sessions_per_batch = sessions_in_a_batch(mode)
-        h.run(pcm_pin, run_cfg, out=out_pin)   # initialisation, not a step: the handle sizes its device buffers on first use
+        h.run(pcm_pin, run_cfg, out=out_pin)   # initialisation, not a step: the handle sizes its device buffers on first use,
+        # those of a full shared estimator batch on the first such batch, and the runtime its pools on the first burst as deep
+        # as the queue lets the host run ahead (api_queue.hip: CSS_QUEUE_LEAD = 3 batches + the one on the device)
+        queued(4 * sessions_per_batch)
         queued(args.warmup)
         runs = [timed_region()]
         while sum(runs) < min_seconds and len(runs) < 200:
             runs.append(timed_region())
         elapsed = float(np.median(runs))
         assert np.isfinite(out_pin).all() and (args.steps < 2 or np.array_equal(out_pin, out_pin2))
-        queued_out = (out_pin.copy(), out_pin2.copy())   # what the TIMED queue left in the caller's buffers (checked below)
         out = {"value": round(seconds * args.steps / elapsed, 2), "ms_per_step": round(1e3 * elapsed / args.steps, 3),
                "dtype": dtype_of[mode],
                "runs_ms": {"per_step_ms_of_each_timed_region": [round(1e3 * r / args.steps, 3) for r in runs], "regions": len(runs),
                            "steps_per_region": args.steps, "value_is": "median region", "timed_seconds_in_total": round(sum(runs), 3),
-                           "min": round(1e3 * min(runs) / args.steps, 3), "max": round(1e3 * max(runs) / args.steps, 3)}}
+                           "min": round(1e3 * min(runs) / args.steps, 3), "max": round(1e3 * max(runs) / args.steps, 3)},
+               "sessions_per_estimator_batch": sessions_per_batch}
+        if args.dump_outputs and mode == "exact_f32":
+            dump_outputs(args.dump_outputs, {"waveforms": outs[(args.steps - 1) % 2]})   # what css_wait handed the last session
+        if not args.full:
+            return out
+        queued_out = (out_pin.copy(), out_pin2.copy())   # what the TIMED queue left in the caller's buffers (checked below)
         # the same K sessions as K synchronous calls (css_run returns when the waveforms are in host memory)
         ms_sync = timed(lambda: h.run(pcm_pin, run_cfg, out=out_pin), warmup=args.warmup)
         out["synchronous_call"] = rec(ms_sync, "css_run: one session per call, host -> host, the call's own latency (nothing to overlap with)")
@@ -746,13 +798,12 @@ def main():
         roof["sclk_mhz_after_the_profiled_passes"] = sclk_mhz()
         out["roofline"] = attach_traffic(roof, mode)
         out["kernel_family_ms"] = {k: round(v[0], 4) for k, v in ks1.items() if k != "event_pair_overhead"}
-        out["sessions_per_estimator_batch"] = sessions_per_batch
         out["_ks_single"] = ks1
         return out
 
     # ---- the headline: the reference's own arithmetic (float32 operands on the float32 matrix instruction) ...
     head = headline("exact_f32", args.min_seconds)
-    ks_single = head.pop("_ks_single")
+    ks_single = head.pop("_ks_single", None)
     ks_queue = head.pop("_ks_queue", None)
     sessions_per_batch = head["sessions_per_estimator_batch"]
     result.update(head)
@@ -769,8 +820,13 @@ def main():
                                          f"Linear-layer launch (max_batch_segments {args.max_batch}); everything else per session; "
                                          f"each session's result is bit for bit its css_run result"},
         "value_is": "CSS_LINEAR_EXACT_F32 (float32 operands, v_mfma_f32_32x32x2_f32): the library's DEFAULT mode and the reference's "
-                    "operand precision.  The opt-in split-f16 mode (22-bit operands, faster): `split_f16` / `value_split_f16` below",
+                    "operand precision.  The opt-in split-f16 mode (22-bit operands, faster): `split_f16` / `value_split_f16` below "
+                    "(--full)",
     })
+    if not args.full:
+        emit_record(result)
+        sep.close()
+        return
     # ---- parity of the schedule that was just timed: (1) its outputs equal css_run's bit for bit (asserted
     # inside headline()); (2) the SAME handle, mode and queue shape on the screened configs[1] meeting whose every frame the
     # reference fixture covers (tests/golden/e2e60_r5.npz: the reference's own run, css/css.py:110-338): decisions exact,

@@ -6,7 +6,7 @@ cd $GRAFT_REPO_ROOT 2>/dev/null || cd "$(dirname "$0")/.."
 P=notsofar1-challenge_amd
 [ -f $P/libcss_base.so ] || { echo "no $P/libcss_base.so"; exit 1; }
 cp $P/libcss_mi355.so /tmp/libcss_new.so
-one() { python bench.py --steps 30 --warmup 5 --no-long --no-cpu-baseline 2>/dev/null | python -c "
+one() { python bench.py --full --steps 30 --warmup 5 --no-long --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); k=d['kernel_family_ms']
 print('$1', 'host->host', d['ms_per_step'], 'device-resident', d['device_resident']['ms_per_step'], 'one lane: gemm', k['linear_gemm'], 'attention', k['attention'], 'conv', k['conv_module'], 'stft', k['stft'], 'scm', k['scm'], 'features', k['features'])"; }
 for i in $(seq 1 ${1:-3}); do
