@@ -474,6 +474,44 @@ int css_handoff_logmel(css_handle_t h, const float* wav_dev, int64_t wav_ld, int
 /* istft: Y [B][2F][T] planes (Re rows then Im rows, time fastest) -> wav [B][(T-1)*hop + frame_len]. */
 int css_istft_host(css_handle_t h, const float* y_planes, int32_t batch, int64_t t_frames, float* wav);
 
+/* ---- streaming separation: chunked input, bit-exact incremental output ---------------------
+ * A stream is a session whose samples arrive in chunks of any size (1 sample upwards) and whose length is not known in
+ * advance.  Each push returns the output samples of the S separated streams that became FINAL: they equal css_run's result on
+ * the whole recording, bit for bit, whatever samples follow.  css_stream_final_samples(n_pushed) says how many there are -- a
+ * pure function of the model, the configuration and n_pushed: segments are final once a later frame exists (so they are not
+ * the last segment, whose window and zero padding differ), stitched frames once every segment covering them is, gated frames
+ * `dilation + erosion` frames later.  The lag n_pushed - final stays below max_lag = (segment_frames + dilation_frames +
+ * erosion_frames + 2) frame_hop + frame_len samples (57 856, 3.6 s, with the defaults).  finish returns the rest: the
+ * concatenation of everything a finished stream returned is css_run's output (n_out samples; css_run's status when css_run
+ * fails, e.g. CSS_ERR_ZERO_WEIGHT for a recording of one segment).  A push that would make final a frame to which no segment
+ * gives weight returns CSS_ERR_ZERO_WEIGHT and changes nothing: css_run fails css.py:297 on every recording that long.
+ *   - device and host memory per stream depend on the segmentation, not on the stream's length; no frame, segment or sample is
+ *     processed twice;
+ *   - up to CSS_MAX_STREAMS streams per handle, independent of each other and of the handle's own session (css_run, css_begin ..
+ *     between two pushes see and leave the same bits);
+ *   - CSS_LINEAR_EXACT_F32 only (the split-f16 mode takes whole-session decisions): css_stream_open in CSS_LINEAR_SPLIT_F16 and
+ *     css_set_linear_mode(h, CSS_LINEAR_SPLIT_F16) while a stream is open return CSS_ERR_STATE; so do css_set_analysis_window
+ *     and css_set_feature_options (a stream's pushes read the handle's window and feature options);
+ *   - frame_len 512 / frame_hop 256 only (CSS_ERR_INVALID_ARG otherwise); any segmentation css_make_run_cfg accepts;
+ *   - CSS_ERR_STATE while css_run_enqueue* sessions are outstanding (not yet css_wait-ed).
+ * Output: out_host [S][cap]; a push writes at most n_samples + max_lag samples per stream, finish css_plan(n_pushed).n_out -
+ * n_emitted.  A capacity below what the call would return is CSS_ERR_INVALID_ARG and leaves the stream unchanged. */
+#define CSS_MAX_STREAMS 16
+typedef struct CssStreamInfo {
+    int64_t n_pushed, n_emitted;   /* samples per channel in, per separated stream out            */
+    int64_t max_lag;               /* the lag bound above, for this stream's configuration        */
+    int64_t device_bytes;          /* device memory this stream holds                             */
+    int32_t finished;
+} CssStreamInfo;
+int css_stream_open(css_handle_t h, const CssRunCfg* cfg, int32_t n_ch, int32_t* stream_id);
+/* pcm_host [n_samples][n_ch] as css_run's */
+int css_stream_push(css_handle_t h, int32_t id, const float* pcm_host, int64_t n_samples, float* out_host, int64_t cap, int64_t* n_out);
+int css_stream_finish(css_handle_t h, int32_t id, float* out_host, int64_t cap, int64_t* n_out);
+int css_stream_close(css_handle_t h, int32_t id);
+int css_stream_info(css_handle_t h, int32_t id, CssStreamInfo* out);
+/* Pure host arithmetic, no GPU: samples of every separated stream that are final after n_pushed samples of an open stream. */
+int css_stream_final_samples(const CssModelDesc* desc, const CssRunCfg* cfg, int64_t n_pushed, int64_t* n_final);
+
 /* ---- buffer access for stage-level parity tests -------------------------------------------- */
 /* dims[0..3] (unused = 1) and element size of a buffer in the current session. */
 int css_buffer_dims(css_handle_t h, int which, int64_t dims[4], int32_t* elem_bytes);

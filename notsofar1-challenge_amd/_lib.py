@@ -73,6 +73,14 @@ class CssCfgSeconds(C.Structure):
                [(n, C.c_int32) for n in ("mc_mvdr", "stitching_loss", "stitching_input", "normalize_segment_power")]
 
 
+class CssStreamInfo(C.Structure):
+    _fields_ = [("n_pushed", C.c_int64), ("n_emitted", C.c_int64), ("max_lag", C.c_int64), ("device_bytes", C.c_int64),
+                ("finished", C.c_int32)]
+
+
+MAX_STREAMS = 16                                 # CSS_MAX_STREAMS
+
+
 class CssKernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("ms", C.c_float), ("launches", C.c_int32)]
 
@@ -154,6 +162,12 @@ SIGNATURES = {
     "css_comm_destroy": (C.c_int, [_P]),
     "css_comm_info": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "css_comm_all_gather": (C.c_int, [_P, _P, _P, C.c_int64]),
+    "css_stream_open": (C.c_int, [_P, C.POINTER(CssRunCfg), C.c_int32, C.POINTER(C.c_int32)]),
+    "css_stream_push": (C.c_int, [_P, C.c_int32, _P, C.c_int64, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "css_stream_finish": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "css_stream_close": (C.c_int, [_P, C.c_int32]),
+    "css_stream_info": (C.c_int, [_P, C.c_int32, C.POINTER(CssStreamInfo)]),
+    "css_stream_final_samples": (C.c_int, [C.POINTER(CssModelDesc), C.POINTER(CssRunCfg), C.c_int64, C.POINTER(C.c_int64)]),
     "css_buffer_dims": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "css_read_buffer": (C.c_int, [_P, C.c_int, _P, C.c_int64]),
     "css_write_buffer": (C.c_int, [_P, C.c_int, _P, C.c_int64]),
@@ -259,6 +273,15 @@ def plan(desc, run_cfg: RunCfg, n_samples: int) -> CssPlan:
     if rc != CSS_OK:
         raise CssError(rc, "css_plan: bad configuration")
     return p
+
+
+def stream_final_samples(desc, run_cfg: RunCfg, n_pushed: int) -> int:
+    """css_stream_final_samples: output samples per stream that are final after `n_pushed` input samples of a stream"""
+    n = C.c_int64()
+    rc = load().css_stream_final_samples(C.byref(make_desc(desc)), C.byref(run_cfg.c), int(n_pushed), C.byref(n))
+    if rc != CSS_OK:
+        raise CssError(rc, "css_stream_final_samples: unsupported frame geometry or bad configuration")
+    return int(n.value)
 
 
 def pit_scan(costs: np.ndarray, num_spks: int) -> np.ndarray:

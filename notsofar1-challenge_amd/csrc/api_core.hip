@@ -550,6 +550,7 @@ int css_destroy(css_handle_t h) {
     hipSetDevice(h->device);
     if (h->stream) hipStreamSynchronize(h->stream);
     if (h->comm) css_comm_destroy(h);
+    stream_destroy_all(h);
     DevBuf* bufs[] = {&h->pcm_in, &h->pcm_cm, &h->X, &h->feat, &h->hx, &h->hu, &h->ht, &h->qkv, &h->qkf, &h->ctxb, &h->masks,
                       &h->scm, &h->bfw, &h->sep, &h->costs, &h->perms, &h->mask_st, &h->activity, &h->act_b,
                       &h->act_tmp, &h->act_final, &h->Y, &h->G, &h->wav, &h->wta, &h->pnorm, &h->segw, &h->stage, &h->pit_part,
@@ -759,6 +760,7 @@ int css_set_linear_mode(css_handle_t h, int mode) {
     if (!h || (mode != CSS_LINEAR_SPLIT_F16 && mode != CSS_LINEAR_EXACT_F32)) return fail(h, CSS_ERR_INVALID_ARG, "unknown linear mode");
     const bool split = mode == CSS_LINEAR_SPLIT_F16;
     if (split == h->split) return CSS_OK;
+    if (split && stream_open_count(h)) return fail(h, CSS_ERR_STATE, "a stream is open: streams run in CSS_LINEAR_EXACT_F32 only");
     if (split && !h->split_ok) return fail(h, CSS_ERR_RANGE, "a weight of this model lies outside the split-f16 operand range (|w| > 65504)");
     HIPCHK(h, hipSetDevice(h->device));
     if (split) {
@@ -779,6 +781,7 @@ int css_set_linear_mode(css_handle_t h, int mode) {
 int css_set_feature_options(css_handle_t h, const CssFeatureCfg* c) {
     CSS_DRAIN(h);
     if (!h || !c) return fail(h, CSS_ERR_INVALID_ARG, "null argument");
+    if (stream_open_count(h)) return fail(h, CSS_ERR_STATE, "a stream is open: its pushes read the feature options it was opened with");
     const int C = h->d.num_mics, F = h->d.num_bins;
     if (c->num_pairs < 0 || c->num_pairs > CSS_MAX_IPD_PAIRS) return fail(h, CSS_ERR_INVALID_ARG, "at most 16 IPD pairs");
     if (C == 1 && c->num_pairs != 0) return fail(h, CSS_ERR_INVALID_ARG, "a single-channel model has no IPD pairs");
@@ -803,6 +806,7 @@ int css_set_feature_options(css_handle_t h, const CssFeatureCfg* c) {
 int css_set_analysis_window(css_handle_t h, int32_t window) {
     CSS_DRAIN(h);
     if (!h) return CSS_ERR_INVALID_ARG;
+    if (stream_open_count(h)) return fail(h, CSS_ERR_STATE, "a stream is open: its pushes read the analysis window it was opened with");
     if (window != CSS_WINDOW_HANN && window != CSS_WINDOW_SQRT_HANN)
         return fail(h, CSS_ERR_INVALID_ARG, "the analysis window is 'hann' or 'sqrt_hann' (feature.py:24-25)");
     HIPCHK(h, hipSetDevice(h->device));

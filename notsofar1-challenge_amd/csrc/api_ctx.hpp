@@ -232,6 +232,7 @@ struct css_ctx : SessState {
     float prof_pair_ms = 0.f;
     int32_t prof_pairs = 0;
     FeatOpts feat_opts{};   // css_set_feature_options (css_create: the shipped configuration)
+    void* streams[CSS_MAX_STREAMS] = {};   // css_stream_open: open streams (api_stream.hip StreamState), by id
 
     std::string err;
 };
@@ -297,6 +298,10 @@ int check_frames(css_ctx* h, int64_t t_lo, int64_t t_hi);
 void istft_gemm_on(css_ctx* h, int64_t f_lo, int64_t f_hi, hipStream_t st);
 void wave_ola_on(css_ctx* h, int64_t f_lo, int64_t f_hi, int64_t q_lo, int64_t q_hi, float* out, int64_t out_ld, int64_t out_q0, hipStream_t st);
 int istft_impl(css_ctx* h, int64_t f_lo, int64_t f_hi, int64_t q_lo, int64_t q_hi, float* out, int64_t out_ld, int64_t out_q0, hipStream_t st);
+
+// ---- api_stream.hip
+void stream_destroy_all(css_ctx* h);
+int stream_open_count(const css_ctx* h);
 
 // ---- api_queue.hip
 hipEvent_t pool_event(css_ctx* h);

@@ -1,0 +1,452 @@
+// libcss_mi355.so, host side of streamed sessions (css_stream_*): samples arrive in chunks of any size, every push returns the
+// output samples that became final, and what a finished stream returned is css_run's result bit for bit.  (DESIGN.md
+// "Streaming separation": the finality rule, the window, what is refused.)
+//
+// A stream keeps a linear WINDOW of the recording on the device: local frame 0 is frame seg_base * hop of the recording,
+// local segment slot j is segment seg_base + j.  Every buffer (samples, analysis planes, masks, spectra, permutations,
+// activity bits, synthesis rows) is indexed locally; when a piece would run past the window's end, the live tail is copied
+// to the front of a second set of buffers (rebase) and the two sets swap.  The window's size follows from the segmentation
+// alone, so an 8-hour stream holds what a 1-minute one holds.  A push is cut into pieces of at most PIECE_SEGMENTS
+// segments' worth of samples, so a push of any length fits the window too.
+//
+// What runs per piece is the offline path's own code on the window: the analysis FFT over the new frames, the mask estimator
+// over the segments the piece completed (one batch), covariances / MVDR / power normalisation, the stitching costs and the
+// permutation scan (continued from the last segment's permutation), then stream.hip's two stitching kernels and the
+// synthesis GEMM + overlap-add over the newly final frames.
+#include "api_ctx.hpp"
+
+#include <climits>
+
+namespace {
+
+constexpr int PIECE_SEGMENTS = 8;
+
+struct StreamState {
+    CssRunCfg cfg{};
+    std::vector<float> w;          // the three windows (cfg.w_* point here)
+    int n_ch = 0, T = 0, hop = 0, halo = 0;
+    int64_t n_pushed = 0, n_emitted = 0;
+    bool finished = false;
+    // progress in frames / segments of the recording: K frames transformed, sd segments done, act_b of frames < t_st,
+    // synthesis rows and output blocks of frames < t_g
+    int64_t K = 0, sd = 0, t_st = 0, t_g = 0;
+    int64_t seg_base = 0;
+    int64_t WF = 0, WS = 0, SC = 0, piece = 0;   // window: frames, samples, segment slots; samples per piece
+    int cur = 0;
+    DevBuf pcm[2], X[2], masks[2], sep[2], perms[2], act_b[2], G[2];
+    DevBuf scm, bfw, pnorm, costs, pit_part, Y, out, segw;
+    std::vector<float> host_cm;    // one piece, channel-major
+};
+
+StreamState* get_stream(css_ctx* h, int32_t id) {
+    if (id < 0 || id >= CSS_MAX_STREAMS) return nullptr;
+    return static_cast<StreamState*>(h->streams[id]);
+}
+
+int64_t frames_of(int64_t n) { return n < 512 ? 0 : (n - 512) / 256 + 1; }
+// segments whose frames are all known and which are not the last segment of the recording, whatever follows
+int64_t segments_done(int64_t K, int T, int hop) { return K > T ? (K - 1 - T) / hop + 1 : 0; }
+int64_t final_frames(int64_t n, int T, int hop, int halo) {
+    return std::max<int64_t>(segments_done(frames_of(n), T, hop) * hop - halo, 0);
+}
+
+void free_stream(StreamState* s) {
+    for (int b = 0; b < 2; ++b)
+        for (DevBuf* d : {&s->pcm[b], &s->X[b], &s->masks[b], &s->sep[b], &s->perms[b], &s->act_b[b], &s->G[b]})
+            if (d->p) hipFree(d->p);
+    for (DevBuf* d : {&s->scm, &s->bfw, &s->pnorm, &s->costs, &s->pit_part, &s->Y, &s->out, &s->segw})
+        if (d->p) hipFree(d->p);
+    delete s;
+}
+
+int64_t device_bytes(const StreamState* s) {
+    int64_t n = 0;
+    for (int b = 0; b < 2; ++b)
+        for (const DevBuf* d : {&s->pcm[b], &s->X[b], &s->masks[b], &s->sep[b], &s->perms[b], &s->act_b[b], &s->G[b]}) n += (int64_t)d->cap;
+    for (const DevBuf* d : {&s->scm, &s->bfw, &s->pnorm, &s->costs, &s->pit_part, &s->Y, &s->out, &s->segw}) n += (int64_t)d->cap;
+    return n;
+}
+
+int check_cfg(const CssModelDesc& d, const CssRunCfg* cfg) {
+    if (!cfg || !cfg->w_first || !cfg->w_mid || !cfg->w_last) return CSS_ERR_INVALID_ARG;
+    if (d.frame_len != 512 || d.frame_hop != 256) return CSS_ERR_INVALID_ARG;
+    if (cfg->segment_frames < 2 || cfg->segment_frames > CSS_MAX_SEGMENT_FRAMES || cfg->hop_frames < 1 ||
+        cfg->hop_frames >= cfg->segment_frames || cfg->dilation_frames < 0 || cfg->erosion_frames < 0)
+        return CSS_ERR_INVALID_ARG;
+    return CSS_OK;
+}
+
+// css.py:297 on the frames [t_lo, t_hi) a push finalises: segments covering them are done and not the last one, so their
+// total weight (summed as plan_impl sums it) is what css_run finds for every recording that reaches them
+bool zero_weight_frames(const StreamState* s, int64_t t_lo, int64_t t_hi) {
+    const int T = s->T, hop = s->hop;
+    for (int64_t t = t_lo; t < t_hi; ++t) {
+        float ws = 0.f;
+        for (int64_t seg = std::max<int64_t>(0, (t - T + hop) / hop); seg <= t / hop; ++seg) {
+            const int64_t tl = t - seg * hop;
+            if (tl < 0 || tl >= T) continue;
+            ws += (seg == 0 ? s->cfg.w_first : s->cfg.w_mid)[tl];
+        }
+        if (!(ws > 1e-5f)) return true;
+    }
+    return false;
+}
+
+StreamStitchArgs stitch_view(css_ctx* h, StreamState* s, bool closing, int64_t nseg, int64_t TL) {
+    StreamStitchArgs a{};
+    const int c = s->cur;
+    a.masks = (const float*)s->masks[c].p; a.mask_ld = s->SC * s->T;
+    a.sep = (const float*)s->sep[c].p;
+    a.perms = (const int32_t*)s->perms[c].p + h->d.num_spks;   // (slot -1 is the scan's guard)
+    a.S = h->d.num_spks; a.F = h->d.num_bins; a.T = s->T; a.hop = s->hop;
+    a.seg_base = s->seg_base; a.frame_base = s->seg_base * s->hop;
+    a.num_slots = (closing ? nseg : s->sd) - s->seg_base;
+    a.num_segments_global = closing ? nseg : INT64_MAX;
+    a.T_long_global = closing ? TL : INT64_MAX;
+    a.w_first = (const float*)s->segw.p; a.w_mid = a.w_first + s->T; a.w_last = a.w_mid + s->T;
+    a.act_b = (uint8_t*)s->act_b[c].p;
+    a.Y = (float*)s->Y.p; a.KIp = h->KIp;
+    a.ld_frames = s->WF;
+    a.activity_th = s->cfg.activity_th; a.dilation = s->cfg.dilation_frames; a.erosion = s->cfg.erosion_frames;
+    return a;
+}
+
+int copy_rows(css_ctx* h, void* dst, const void* src, size_t pitch, size_t width, size_t rows) {
+    if (!width || !rows) return CSS_OK;
+    if (rows == 1) {
+        HIPCHK(h, hipMemcpyAsync(dst, src, width, hipMemcpyDeviceToDevice, h->stream));
+        return CSS_OK;
+    }
+    HIPCHK(h, hipMemcpy2DAsync(dst, pitch, src, pitch, width, rows, hipMemcpyDeviceToDevice, h->stream));
+    return CSS_OK;
+}
+
+// Moves the window forward as far as the live state allows (whole segments): what is still read later -- the samples of
+// frames not yet transformed, the planes of segments not yet done, the segments covering frames not yet gated, the
+// permutation the scan continues from, the activity halo of the gate and the synthesis rows of the frame before the next
+// output block -- is copied to the front of the other buffer set.
+int rebase(css_ctx* h, StreamState* s) {
+    const int T = s->T, hop = s->hop;
+    const int64_t first_cover = s->t_g - T + 1 <= 0 ? 0 : (s->t_g - T + 1 + hop - 1) / hop;
+    const int64_t frame_need = s->t_g - std::max(s->halo, 1);
+    int64_t nb = std::min<int64_t>(s->sd - 1, first_cover);
+    nb = std::min<int64_t>(nb, frame_need < 0 ? 0 : frame_need / hop);
+    nb = std::max<int64_t>(nb, 0);
+    const int64_t d = nb - s->seg_base;
+    if (d <= 0) return CSS_OK;
+    const int c = s->cur, o = 1 - c;
+    const int F = h->d.num_bins, S = h->d.num_spks, C = s->n_ch, N = h->d.frame_len;
+    const int64_t df = d * hop, fb = s->seg_base * hop;
+    const int64_t ds = df * h->d.frame_hop, sb = fb * h->d.frame_hop;
+    const size_t f4 = sizeof(float);
+    int rc;
+    if ((rc = copy_rows(h, s->pcm[o].p, (float*)s->pcm[c].p + ds, s->WS * f4, (size_t)(s->n_pushed - sb - ds) * f4, C)) != CSS_OK) return rc;
+    if ((rc = copy_rows(h, s->X[o].p, (float*)s->X[c].p + df, s->WF * f4, (size_t)(s->K - fb - df) * f4,
+                        (size_t)C * X_ROWS_PER_BIN * F)) != CSS_OK) return rc;
+    const int64_t keep_seg = s->sd - s->seg_base - d;   // slots d .. sd - seg_base
+    if ((rc = copy_rows(h, s->masks[o].p, (float*)s->masks[c].p + d * T, s->SC * T * f4, (size_t)keep_seg * T * f4,
+                        (size_t)(S + 1) * F)) != CSS_OK) return rc;
+    if ((rc = copy_rows(h, s->sep[o].p, (float*)s->sep[c].p + d * (int64_t)S * F * T * 2, 0, (size_t)keep_seg * S * F * T * 2 * f4, 1)) != CSS_OK) return rc;
+    if ((rc = copy_rows(h, (int32_t*)s->perms[o].p + S, (int32_t*)s->perms[c].p + S + d * S, 0, (size_t)keep_seg * S * sizeof(int32_t), 1)) != CSS_OK) return rc;
+    if ((rc = copy_rows(h, s->act_b[o].p, (uint8_t*)s->act_b[c].p + df, s->WF, (size_t)(s->t_st - fb - df), S)) != CSS_OK) return rc;
+    if ((rc = copy_rows(h, s->G[o].p, (float*)s->G[c].p + df * N, s->WF * N * f4, (size_t)(s->t_g - fb - df) * N * f4, S)) != CSS_OK) return rc;
+    s->cur = o;
+    s->seg_base = nb;
+    return CSS_OK;
+}
+
+// Segments [g_lo, g_hi) of the recording (slots of the window): estimator, beamformer, stitching costs, permutations.
+int segments(css_ctx* h, StreamState* s, int64_t g_lo, int64_t g_hi, int64_t k_local) {
+    if (g_hi <= g_lo) return CSS_OK;
+    const int c = s->cur, T = s->T, F = h->d.num_bins, S = h->d.num_spks;
+    const int64_t lo = g_lo - s->seg_base, hi = g_hi - s->seg_base;
+    int rc;
+    MaskIo io{(const float*)s->X[c].p, s->WF, k_local, s->hop, T, (float*)s->masks[c].p, s->SC * T};
+    io.PH = (const float*)s->X[c].p + (int64_t)s->n_ch * 2 * F * s->WF;
+    const int64_t cap = batch_len(hi - lo, batch_cap(h, T));
+    if ((rc = ensure_activations(h, cap, T)) != CSS_OK) return rc;
+    for (int64_t s0 = lo; s0 < hi; s0 += cap) {
+        const int nb = (int)std::min<int64_t>(cap, hi - s0);
+        if ((rc = masknet_batch(h, io, s0, nb)) != CSS_OK) return rc;
+    }
+    MvdrArgs a{};
+    a.X = (const float*)s->X[c].p; a.T_ld = s->WF; a.stft_frames = k_local;
+    a.C = s->n_ch; a.F = F;
+    a.masks = (const float*)s->masks[c].p; a.mask_ld = s->SC * T;
+    a.S = S; a.T = T; a.hop = s->hop;
+    a.seg_lo = lo; a.nseg = (int)(hi - lo);
+    a.wta_override = nullptr;
+    a.scm = (double*)s->scm.p; a.bfw = (double*)s->bfw.p; a.sep = (float*)s->sep[c].p;
+    a.mask_floor = s->cfg.mask_floor;
+    a.use_mvdr = (s->n_ch > 1 && s->cfg.mc_mvdr) ? 1 : 0;
+    if (a.use_mvdr) {
+        if (!launch_scm(a, h->stream)) return fail(h, CSS_ERR_HIP, "the covariance kernel's LDS could not be reserved");
+        launch_mvdr_solve(a, h->stream);
+    }
+    launch_beamform(a, h->stream);
+    if (s->cfg.normalize_segment_power) launch_segment_power_norm(a, (double*)s->pnorm.p, h->stream);
+    // boundaries b (segments b, b + 1) that end in these segments (the costs' chunking is one constant: stitch.hip pit_chunks)
+    const int64_t b_lo = std::max<int64_t>(lo - 1, 0), b_hi = hi - 1;
+    if (b_hi > b_lo) {
+        StitchArgs sa{};
+        sa.masks = (const float*)s->masks[c].p; sa.mask_ld = s->SC * T; sa.sep = (const float*)s->sep[c].p;
+        sa.S = S; sa.F = F; sa.T = T; sa.hop = s->hop;
+        sa.num_segments = hi; sa.T_long = s->WF;
+        launch_pit_costs(sa, s->cfg.stitching_loss, s->cfg.stitching_input, b_lo, b_hi, (double*)s->pit_part.p,
+                         (double*)s->costs.p + S * S, h->stream);
+        // slot j's permutation lives at perms + (j + 1) S and boundary b's costs at costs + (b + 1) S S: the scan starts
+        // at its index 1 + b_lo and continues from slot b_lo's permutation (never the identity it writes for index 0)
+        launch_pit_scan((const double*)s->costs.p, 1 + b_lo, 1 + b_hi, S, (int32_t*)s->perms[c].p, h->stream);
+    }
+    HIPCHK(h, hipGetLastError());
+    return CSS_OK;
+}
+
+// frames [t_lo, t_hi) of the recording: activity bits of [a_lo, a_hi), gate + overlap-add + synthesis of [t_lo, t_hi), output
+// blocks [t_lo, q_hi) into the output buffer (block t_lo at column 0)
+int tail(css_ctx* h, StreamState* s, bool closing, int64_t nseg, int64_t TL, int64_t a_lo, int64_t a_hi, int64_t t_lo, int64_t t_hi,
+         int64_t q_hi) {
+    const int64_t fb = s->seg_base * s->hop;
+    const StreamStitchArgs a = stitch_view(h, s, closing, nseg, TL);
+    launch_stream_activity(a, a_lo - fb, a_hi - fb, h->stream);
+    launch_stream_gate_ola(a, t_lo - fb, t_hi - fb, h->stream);
+    const int S = h->d.num_spks, N = h->d.frame_len, c = s->cur;
+    if (t_hi > t_lo) {
+        GemmArgs g{};
+        g.A = (const float*)s->Y.p + (t_lo - fb) * h->KIp; g.lda = h->KIp; g.strideA = s->WF * h->KIp;
+        g.B = h->dft_inv_t; g.ldb = h->KIp; g.strideB = 0;
+        g.C = (float*)s->G[c].p + (t_lo - fb) * N; g.ldc = N; g.strideC = s->WF * N;
+        g.M = (int)(t_hi - t_lo); g.N = N; g.K = h->KIp; g.batch = S;
+        g.bias = nullptr; g.act = ACT_NONE; g.residual = nullptr; g.alpha = 1.f;
+        launch_gemm(g, h->stream);
+    }
+    if (q_hi > t_lo)
+        launch_wave_ola((const float*)s->G[c].p, (float*)s->out.p, S, s->WF, h->d.frame_hop, N, t_lo - fb, q_hi - fb, 0,
+                        (closing ? TL : t_hi) - fb, (q_hi - t_lo) * h->d.frame_hop, t_lo - fb, nullptr, h->stream);
+    HIPCHK(h, hipGetLastError());
+    return CSS_OK;
+}
+
+int download(css_ctx* h, StreamState* s, int64_t n, float* out_host, int64_t cap, int64_t at) {
+    if (n <= 0) return CSS_OK;
+    HIPCHK(h, hipMemcpy2DAsync(out_host + at, (size_t)cap * sizeof(float), s->out.p, (size_t)n * sizeof(float), (size_t)n * sizeof(float),
+                               (size_t)h->d.num_spks, hipMemcpyDeviceToHost, h->stream));
+    return CSS_OK;
+}
+
+int check_stream_call(css_ctx* h, int32_t id, StreamState** out) {
+    if (!h) return CSS_ERR_INVALID_ARG;
+    StreamState* s = get_stream(h, id);
+    if (!s) return fail(h, CSS_ERR_INVALID_ARG, "no open stream with this id");
+    if (h->queued || !h->pending.empty())
+        return fail(h, CSS_ERR_STATE, "queued sessions (css_run_enqueue*) are outstanding: css_wait before using a stream");
+    *out = s;
+    return CSS_OK;
+}
+
+}  // namespace
+
+void stream_destroy_all(css_ctx* h) {
+    for (int i = 0; i < CSS_MAX_STREAMS; ++i)
+        if (h->streams[i]) { free_stream(static_cast<StreamState*>(h->streams[i])); h->streams[i] = nullptr; }
+}
+int stream_open_count(const css_ctx* h) {
+    int n = 0;
+    for (int i = 0; i < CSS_MAX_STREAMS; ++i) n += h->streams[i] != nullptr;
+    return n;
+}
+
+int css_stream_final_samples(const CssModelDesc* desc, const CssRunCfg* cfg, int64_t n_pushed, int64_t* n_final) {
+    if (!desc || !n_final || n_pushed < 0) return CSS_ERR_INVALID_ARG;
+    const int rc = check_cfg(*desc, cfg);
+    if (rc != CSS_OK) return rc;
+    *n_final = final_frames(n_pushed, cfg->segment_frames, cfg->hop_frames, cfg->dilation_frames + cfg->erosion_frames) * desc->frame_hop;
+    return CSS_OK;
+}
+
+int css_stream_open(css_handle_t h, const CssRunCfg* cfg, int32_t n_ch, int32_t* stream_id) {
+    if (!h) return CSS_ERR_INVALID_ARG;
+    if (!cfg || !stream_id) return fail(h, CSS_ERR_INVALID_ARG, "null argument");
+    if (h->queued || !h->pending.empty())
+        return fail(h, CSS_ERR_STATE, "queued sessions (css_run_enqueue*) are outstanding: css_wait before opening a stream");
+    if (h->split) return fail(h, CSS_ERR_STATE, "streams run in CSS_LINEAR_EXACT_F32 only (the split-f16 mode takes whole-session decisions)");
+    if (h->d.frame_len != 512 || h->d.frame_hop != 256 || !h->fft512)
+        return fail(h, CSS_ERR_INVALID_ARG, "streams support frame_len 512 / frame_hop 256 only");
+    // channels, windows, mask floor, segmentation (the weights are checked frame by frame as frames become final: push, finish)
+    if (n_ch != h->d.num_mics)
+        return fail(h, CSS_ERR_SHAPE, "input has " + std::to_string(n_ch) + " channels, the model expects " + std::to_string(h->d.num_mics));
+    if (cfg->mask_floor > 1.0f || cfg->mask_floor < 0.f) return fail(h, CSS_ERR_MASK_FLOOR, "mask_floor_db must be <= 0");
+    if (cfg->stitching_loss < 0 || cfg->stitching_loss > 1 || cfg->stitching_input < 0 || cfg->stitching_input > 1)
+        return fail(h, CSS_ERR_INVALID_ARG, "unexpected stitching_loss / stitching_input");
+    if (check_cfg(h->d, cfg) != CSS_OK) return fail(h, CSS_ERR_INVALID_ARG, "segment weights missing / bad segmentation / gate");
+    int rc = CSS_OK;
+    int id = -1;
+    for (int i = 0; i < CSS_MAX_STREAMS && id < 0; ++i)
+        if (!h->streams[i]) id = i;
+    if (id < 0) return fail(h, CSS_ERR_STATE, "too many open streams on this handle (CSS_MAX_STREAMS)");
+    HIPCHK(h, hipSetDevice(h->device));
+    StreamState* s = new StreamState();
+    const int T = cfg->segment_frames, hop = cfg->hop_frames, F = h->d.num_bins, S = h->d.num_spks, N = h->d.frame_len;
+    s->cfg = *cfg;
+    s->w.resize(3 * (size_t)T);
+    std::memcpy(s->w.data(), cfg->w_first, T * sizeof(float));
+    std::memcpy(s->w.data() + T, cfg->w_mid, T * sizeof(float));
+    std::memcpy(s->w.data() + 2 * T, cfg->w_last, T * sizeof(float));
+    s->cfg.w_first = s->w.data(); s->cfg.w_mid = s->w.data() + T; s->cfg.w_last = s->w.data() + 2 * T;
+    s->n_ch = n_ch; s->T = T; s->hop = hop; s->halo = cfg->dilation_frames + cfg->erosion_frames;
+    const int64_t piece_frames = (int64_t)PIECE_SEGMENTS * hop;
+    s->piece = piece_frames * h->d.frame_hop;
+    s->WF = ((2 * (int64_t)T + 2 * s->halo + 3 * (int64_t)hop + piece_frames + 16) + 3) / 4 * 4;
+    s->WS = (s->WF * h->d.frame_hop + N + 31) / 32 * 32;
+    s->SC = s->WF / hop + 3;
+    const int64_t out_ld = (piece_frames + T + s->halo + 4) * h->d.frame_hop;
+    s->host_cm.resize((size_t)n_ch * s->piece);
+    auto alloc = [&](DevBuf& b, size_t bytes) { return ensure(h, b, bytes, true); };
+    for (int b = 0; b < 2 && rc == CSS_OK; ++b) {
+        if ((rc = alloc(s->pcm[b], (size_t)n_ch * s->WS * sizeof(float))) != CSS_OK) break;
+        if ((rc = alloc(s->X[b], (size_t)n_ch * X_ROWS_PER_BIN * F * s->WF * sizeof(float))) != CSS_OK) break;
+        if ((rc = alloc(s->masks[b], (size_t)(S + 1) * F * s->SC * T * sizeof(float))) != CSS_OK) break;
+        if ((rc = alloc(s->sep[b], (size_t)s->SC * S * F * T * 2 * sizeof(float))) != CSS_OK) break;
+        if ((rc = alloc(s->perms[b], (size_t)(s->SC + 1) * S * sizeof(int32_t))) != CSS_OK) break;
+        if ((rc = alloc(s->act_b[b], (size_t)S * s->WF)) != CSS_OK) break;
+        if ((rc = alloc(s->G[b], (size_t)S * s->WF * N * sizeof(float))) != CSS_OK) break;
+    }
+    if (rc == CSS_OK) rc = alloc(s->scm, (size_t)s->SC * (S + 1) * F * 49 * sizeof(double));
+    if (rc == CSS_OK) rc = alloc(s->bfw, (size_t)s->SC * S * F * 7 * 2 * sizeof(double));
+    if (rc == CSS_OK) rc = alloc(s->pnorm, (size_t)s->SC * sizeof(double));
+    if (rc == CSS_OK) rc = alloc(s->costs, (size_t)(s->SC + 1) * S * S * sizeof(double));
+    if (rc == CSS_OK) rc = alloc(s->pit_part, pit_cost_scratch_bytes(s->SC));
+    if (rc == CSS_OK) rc = alloc(s->Y, (size_t)S * s->WF * h->KIp * sizeof(float));
+    if (rc == CSS_OK) rc = alloc(s->out, (size_t)S * out_ld * sizeof(float));
+    if (rc == CSS_OK) rc = alloc(s->segw, 3 * (size_t)T * sizeof(float));
+    if (rc != CSS_OK) { free_stream(s); return rc; }
+    std::vector<int32_t> ident(S);
+    for (int k = 0; k < S; ++k) ident[k] = k;
+    hipError_t e = hipMemcpyAsync((int32_t*)s->perms[0].p + S, ident.data(), S * sizeof(int32_t), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(s->segw.p, s->w.data(), 3 * (size_t)T * sizeof(float), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) { free_stream(s); return fail(h, CSS_ERR_HIP, std::string("stream setup: ") + hipGetErrorString(e)); }
+    h->streams[id] = s;
+    *stream_id = id;
+    return CSS_OK;
+}
+
+int css_stream_push(css_handle_t h, int32_t id, const float* pcm_host, int64_t n_samples, float* out_host, int64_t cap, int64_t* n_out) {
+    StreamState* s = nullptr;
+    int rc = check_stream_call(h, id, &s);
+    if (rc != CSS_OK) return rc;
+    if (s->finished) return fail(h, CSS_ERR_STATE, "the stream has finished");
+    if (n_samples < 0 || (n_samples > 0 && !pcm_host) || !n_out) return fail(h, CSS_ERR_INVALID_ARG, "bad argument");
+    if (h->split) return fail(h, CSS_ERR_STATE, "streams run in CSS_LINEAR_EXACT_F32 only");
+    const int64_t halo = s->halo;
+    const int64_t need = final_frames(s->n_pushed + n_samples, s->T, s->hop, (int)halo) * h->d.frame_hop - s->n_emitted;
+    if (need > 0 && (!out_host || cap < need)) return fail(h, CSS_ERR_INVALID_ARG, "output capacity too small for the samples this push finalises");
+    if (zero_weight_frames(s, s->t_st, segments_done(frames_of(s->n_pushed + n_samples), s->T, s->hop) * s->hop))
+        return fail(h, CSS_ERR_ZERO_WEIGHT, "zero weights found. check hop_size, segment_size or m0, m1");
+    *n_out = 0;
+    if (n_samples == 0) return CSS_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    const int C = s->n_ch, hopS = h->d.frame_hop;
+    int64_t emitted = 0;
+    for (int64_t done = 0; done < n_samples;) {
+        const int64_t n = std::min<int64_t>(s->piece, n_samples - done);
+        const int64_t N1 = s->n_pushed + n, K1 = frames_of(N1);
+        if (K1 - s->seg_base * s->hop > s->WF || N1 - s->seg_base * s->hop * hopS > s->WS) {
+            if ((rc = rebase(h, s)) != CSS_OK) return rc;
+            if (K1 - s->seg_base * s->hop > s->WF || N1 - s->seg_base * s->hop * hopS > s->WS)
+                return fail(h, CSS_ERR_STATE, "stream window overflow");
+        }
+        const int64_t fb = s->seg_base * s->hop, sb = fb * hopS;
+        // samples -> the window, channel-major (a plain copy: the transform reads the same values css_run's does)
+        const float* src = pcm_host + done * C;
+        for (int ch = 0; ch < C; ++ch) {
+            float* d = s->host_cm.data() + (size_t)ch * n;
+            for (int64_t i = 0; i < n; ++i) d[i] = src[i * C + ch];
+        }
+        HIPCHK(h, hipMemcpy2DAsync((float*)s->pcm[s->cur].p + (s->n_pushed - sb), (size_t)s->WS * sizeof(float), s->host_cm.data(),
+                                   (size_t)n * sizeof(float), (size_t)n * sizeof(float), (size_t)C, hipMemcpyHostToDevice, h->stream));
+        // the host buffer is reused by the next piece
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        s->n_pushed = N1;
+        const int c = s->cur;
+        bool ph = false;
+        if (K1 > s->K &&
+            !analysis_transform(h, (const float*)s->pcm[c].p, s->WS, C, s->K - fb, K1 - fb, (float*)s->X[c].p, s->WF, h->stream,
+                                (float*)s->X[c].p + (int64_t)C * 2 * h->d.num_bins * s->WF, &ph))
+            return fail(h, CSS_ERR_HIP, "the analysis transform's LDS could not be reserved");
+        s->K = std::max(s->K, K1);
+        const int64_t sd1 = segments_done(s->K, s->T, s->hop);
+        if ((rc = segments(h, s, s->sd, sd1, s->K - fb)) != CSS_OK) return rc;
+        s->sd = sd1;
+        const int64_t t_st1 = sd1 * s->hop, t_g1 = std::max<int64_t>(t_st1 - halo, 0);
+        if ((rc = tail(h, s, false, 0, 0, s->t_st, t_st1, s->t_g, t_g1, t_g1)) != CSS_OK) return rc;
+        if ((rc = download(h, s, (t_g1 - s->t_g) * hopS, out_host, cap, emitted)) != CSS_OK) return rc;
+        emitted += (t_g1 - s->t_g) * hopS;
+        s->t_st = t_st1;
+        s->t_g = t_g1;
+        done += n;
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    s->n_emitted += emitted;
+    *n_out = emitted;
+    return CSS_OK;
+}
+
+int css_stream_finish(css_handle_t h, int32_t id, float* out_host, int64_t cap, int64_t* n_out) {
+    StreamState* s = nullptr;
+    int rc = check_stream_call(h, id, &s);
+    if (rc != CSS_OK) return rc;
+    if (s->finished) return fail(h, CSS_ERR_STATE, "the stream has finished");
+    if (!n_out) return fail(h, CSS_ERR_INVALID_ARG, "null argument");
+    if (h->split) return fail(h, CSS_ERR_STATE, "streams run in CSS_LINEAR_EXACT_F32 only");
+    CssPlan p{};
+    plan_impl(h->d, s->cfg, s->n_pushed, &p);
+    if (p.zero_weight) return fail(h, CSS_ERR_ZERO_WEIGHT, "zero weights found. check hop_size, segment_size or m0, m1");
+    const int64_t need = p.n_out - s->n_emitted;
+    if (!out_host || cap < need) return fail(h, CSS_ERR_INVALID_ARG, "output capacity too small for the rest of the stream");
+    HIPCHK(h, hipSetDevice(h->device));
+    const int64_t TL = p.mix_frames, nseg = p.num_segments, fb = s->seg_base * s->hop;
+    if (TL - fb > s->WF || nseg - s->seg_base > s->SC) return fail(h, CSS_ERR_STATE, "stream window overflow");
+    const int c = s->cur, F = h->d.num_bins;
+    // frames past the last transformed one are zero (css.py:159-164 pads a short recording; the last segment's tail)
+    if (s->WF > s->K - fb)
+        HIPCHK(h, hipMemset2DAsync((float*)s->X[c].p + (s->K - fb), (size_t)s->WF * sizeof(float), 0,
+                                   (size_t)(s->WF - (s->K - fb)) * sizeof(float), (size_t)s->n_ch * X_ROWS_PER_BIN * F, h->stream));
+    if ((rc = segments(h, s, s->sd, nseg, s->K - fb)) != CSS_OK) return rc;
+    // the rest of the output: blocks up to mix_frames (frame_len = 2 hop: block TL holds the last frame's second half)
+    const int64_t q_hi = TL + 1;
+    if ((q_hi - s->t_g) * h->d.frame_hop > (int64_t)(s->out.cap / (sizeof(float) * h->d.num_spks))) {
+        if ((rc = ensure(h, s->out, (size_t)h->d.num_spks * (q_hi - s->t_g) * h->d.frame_hop * sizeof(float))) != CSS_OK) return rc;
+    }
+    if ((rc = tail(h, s, true, nseg, TL, s->t_st, TL, s->t_g, TL, q_hi)) != CSS_OK) return rc;
+    if ((rc = download(h, s, need, out_host, cap, 0)) != CSS_OK) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    s->sd = nseg; s->t_st = s->t_g = TL;
+    s->n_emitted += need;
+    s->finished = true;
+    *n_out = need;
+    return CSS_OK;
+}
+
+int css_stream_close(css_handle_t h, int32_t id) {
+    if (!h) return CSS_ERR_INVALID_ARG;
+    StreamState* s = get_stream(h, id);
+    if (!s) return fail(h, CSS_ERR_INVALID_ARG, "no open stream with this id");
+    hipSetDevice(h->device);
+    hipStreamSynchronize(h->stream);
+    free_stream(s);
+    h->streams[id] = nullptr;
+    return CSS_OK;
+}
+
+int css_stream_info(css_handle_t h, int32_t id, CssStreamInfo* out) {
+    if (!h) return CSS_ERR_INVALID_ARG;
+    StreamState* s = get_stream(h, id);
+    if (!s || !out) return fail(h, CSS_ERR_INVALID_ARG, "no open stream with this id / null argument");
+    out->n_pushed = s->n_pushed;
+    out->n_emitted = s->n_emitted;
+    out->max_lag = (int64_t)(s->T + s->halo + 2) * h->d.frame_hop + h->d.frame_len;
+    out->device_bytes = device_bytes(s);
+    out->finished = s->finished ? 1 : 0;
+    return CSS_OK;
+}

@@ -265,4 +265,24 @@ void launch_ola_masks(const StitchArgs& a, int64_t t_lo, int64_t t_hi, hipStream
 void launch_morphology(const StitchArgs& a, int64_t t_lo, int64_t t_hi, hipStream_t s);
 void launch_ola_stft(const StitchArgs& a, int64_t t_lo, int64_t t_hi, hipStream_t s);
 
+// stream.hip: the stitching tail of a streamed session over a window of segment slots (api_stream.hip).  Local segment j of
+// the window is segment seg_base + j of the recording and starts at local frame j * hop; local frame 0 is frame frame_base.
+struct StreamStitchArgs {
+    const float* masks; int64_t mask_ld;   // [(S+1)F][mask_ld], slot j at column j*T
+    const float* sep;                      // [slots][S][F][T][2]
+    const int32_t* perms;                  // [slots][S]
+    int S; int F; int T; int hop;
+    int64_t num_slots;                     // slots holding segments
+    int64_t seg_base, frame_base;
+    int64_t num_segments_global;           // INT64_MAX while the stream is open
+    int64_t T_long_global;                 // INT64_MAX while the stream is open
+    const float* w_first; const float* w_mid; const float* w_last;
+    uint8_t* act_b;                        // [S][ld_frames]
+    float* Y; int KIp;                     // [S][ld_frames][KIp]
+    int64_t ld_frames;
+    float activity_th; int dilation; int erosion;
+};
+void launch_stream_activity(const StreamStitchArgs& a, int64_t t_lo, int64_t t_hi, hipStream_t s);
+void launch_stream_gate_ola(const StreamStitchArgs& a, int64_t t_lo, int64_t t_hi, hipStream_t s);
+
 }  // namespace css

@@ -48,12 +48,14 @@ __device__ __forceinline__ double wave_sum_dpp(double v) {
 //   input 0: masks   input 1: |separated spectrum|     loss 0: L1   loss 1: squared error
 // ------------------------------------------------------------------------------------------------
 // frequency chunks per boundary: 39 boundaries alone would occupy 39 of 256 CUs; with 48 a thread takes two (bin, frame)
-// elements, all of whose loads are in flight at once (16 chunks: six dependent rounds of loads per thread).  A long
-// meeting has boundaries enough (1 208 in 30 min: 58 k blocks of 48 chunks took 383 us against 305 us with 16), so the
-// count follows the MEETING's number of boundaries -- not the range a call or a rank computes: the chunk sums are added in
-// a fixed order and a cost must be the same bit pattern wherever it is computed.
-constexpr int PIT_CH = 48;   // the most (scratch layout)
-__host__ __device__ inline int pit_chunks(int64_t num_segments) { return num_segments - 1 < 128 ? PIT_CH : 16; }
+// elements, all of whose loads are in flight at once (16 chunks: six dependent rounds of loads per thread).  The chunk sums
+// are added in a fixed order and a cost must be the same bit pattern wherever it is computed -- by any call, any rank, and a
+// streamed session (api_stream.hip), which does not know how many segments its recording will have.  So the count is ONE
+// constant for every meeting length.  (It used to drop to 16 from 129 segments on: 1 208 boundaries of a 30-min meeting
+// took 305 us with 16 chunks against 383 us with 48 -- 78 us of a 30-min pass; the costs of such meetings moved in their last
+// float64 bits with the change, the suite's long-meeting tests hold the results.)
+constexpr int PIT_CH = 48;   // (scratch layout)
+__host__ __device__ inline int pit_chunks(int64_t) { return PIT_CH; }
 
 // One block per (boundary, frequency chunk) -> partial[b][chunk][16]; a second kernel adds the chunks in a fixed
 // order, so the cost is the same bit pattern whatever boundary range or GPU computes it.
