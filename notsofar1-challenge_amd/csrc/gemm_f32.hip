@@ -10,9 +10,9 @@
 //     of its rows (TM row tiles of 32: at most 64 accumulator registers), the slab is 16 deep and double buffered
 //     (2 x (128 + 128) rows x 20 floats = 40 960 B: exactly a quarter of the CU's 160 KB), and the kernel is held to
 //     128 registers (__launch_bounds__(256, 4)) -- four waves per SIMD from four blocks that fill each other's bubbles.
-//     The cap is met by SPILLING: hipcc -Rpass-analysis=kernel-resource-usage reports scratch for both instantiations
-//     (the epilogue's descriptors, offsets and the switch over four tile heights live across the K loop); the reloads sit
-//     outside the slab loop except for a handful in the TM = 3 / 4 tiles (DESIGN.md 3.1c records the counts per round).
+//     The kernels of the fast epilogue -- every Linear layer's -- fit that without spilling (hipcc -Rpass-analysis=
+//     kernel-resource-usage: no scratch; tests/test_gemm_f32_registers.py) because the host picks the epilogue kind: the
+//     general epilogue's state, which made the one-body kernel spill, exists only in the kernels that need it.
 //   * PERSISTENT blocks over a balanced cut of the work.  The launch is 1 024 blocks (4 x 256 CUs); the output is
 //     counted in UNITS of 32 rows x 128 columns, the units of a launch are a line (batch entry, column panel, row unit --
 //     row unit fastest), every "virtual CU" takes an equal contiguous piece of that line and each of its four blocks a
@@ -27,6 +27,7 @@
 //     operand); the epilogue requests a tile's residual values one 32 x 32 tile ahead (the first under the last slab's
 //     MFMAs) and writes 16-byte row pieces after a turn through a wave-private LDS patch.
 #include <algorithm>
+#include <type_traits>
 
 #include "gemm_common.hpp"
 
@@ -53,7 +54,8 @@ __device__ __forceinline__ float epi_value(float acc, float bn, float bm, int ac
 // W[32 j + (lane & 31)][8 kc + 4 (lane >> 5) .. + 3], i.e. what lane `lane` feeds to the four MFMAs of chunk kc for column
 // tile j): it goes global -> registers as one coalesced 1 KiB load per wave and chunk -- no LDS store, no LDS read, half the
 // slab buffer -- because every memory instruction of this loop costs matrix issue time.
-template <int TM, bool BD>
+// FAST: the fast epilogue (below), chosen on the host (f32_fast_epilogue): its launches run a kernel with no general-epilogue code.
+template <int TM, bool BD, bool FAST>
 __device__ __forceinline__ void f32_tile(const GemmArgs& g, const float* __restrict__ A, const float* __restrict__ B,
                                          float* __restrict__ C, const int m0, const int n0, float* __restrict__ lds) {
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 31, h = lane >> 5;
@@ -189,8 +191,9 @@ __device__ __forceinline__ void f32_tile(const GemmArgs& g, const float* __restr
     const bool bias_m = bias && g.bias_along_m, bias_n = bias && !g.bias_along_m, has_res = res != nullptr;
     const int64_t ldc = g.ldc, ldr = g.ldr;
     const float alpha = g.alpha;
-    const bool wide = (ldc % 4 == 0) && (N % 4 == 0) && ((reinterpret_cast<uintptr_t>(C) & 15) == 0) &&
-                      (!has_res || ((ldr % 4 == 0) && ((reinterpret_cast<uintptr_t>(res) & 15) == 0)));
+    // (the general epilogue's 16-byte pieces; the fast one always has them)
+    const bool wide = FAST || ((ldc % 4 == 0) && (N % 4 == 0) && ((reinterpret_cast<uintptr_t>(C) & 15) == 0) &&
+                               (!has_res || ((ldr % 4 == 0) && ((reinterpret_cast<uintptr_t>(res) & 15) == 0))));
     // The fast form of the epilogue (round 5): a wave in its epilogue shares its SIMD with three waves issuing MFMAs back to
     // back, and EVERY instruction it issues waits for a slot between them -- the slab-clock probe (tools, F32_PROBE) put the
     // last slab + epilogue at 15 k clocks of a K = 512 tile's 100 k and at 37 k of 162 k for the QKV tiles, ~220 vector-ALU
@@ -198,9 +201,9 @@ __device__ __forceinline__ void f32_tile(const GemmArgs& g, const float* __restr
     // the rows addressed through buffer descriptors -- one per-lane offset per tile, the row piece as a SCALAR offset, rows
     // past M dropped (stores) or read as zero (residual) by the bounds check -- a row piece costs its arithmetic and nothing
     // else.  (The scalar offset takes part in the bounds check on gfx950: tools/buffer_bounds_probe.hip, loads and stores.)
-    // Conditions: 16-byte pieces, whole 128-column panels, column bias or none, no sigmoid, operands below 2 GiB.
-    const bool fast = F32_FAST_EPILOGUE && wide && !bias_m && (N % BN == 0) && act != ACT_SIGMOID &&
-                      (int64_t)M * ldc * 4 < ((int64_t)1 << 31) && (!has_res || (int64_t)M * ldr * 4 < ((int64_t)1 << 31));
+    // Conditions (f32_fast_epilogue, on the host): 16-byte pieces, whole 128-column panels, column bias or none, no sigmoid,
+    // operands below 2 GiB.
+    constexpr bool fast = FAST;
     const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc(C, 0, fast ? (int)((int64_t)M * ldc * 4) : 0, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsR = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(res), 0, (fast && has_res) ? (int)((int64_t)M * ldr * 4) : 0, 0x00020000);
     f32x4 rv[2][4];   // residual pieces of the tile being written and of the next one
@@ -213,11 +216,12 @@ __device__ __forceinline__ void f32_tile(const GemmArgs& g, const float* __restr
             rv[slot][q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsR, vo_, (int)((32 * i * ldr + 8 * q) * 4), 0));
     };
 #else
+    // (32-bit unsigned offsets: M ldr 4 < 2^31 (f32_fast_epilogue), and the rows of a tail tile past M stay below 2^32)
     auto prefetch_fast = [&](int i, int slot, int lane_) {
-        const int vo_ = (int)((((int64_t)m0 + (lane_ >> 3)) * ldr + n0 + 32 * w + (lane_ & 7) * 4) * 4);
+        const int vo_ = (int)(((unsigned)(m0 + (lane_ >> 3)) * (unsigned)ldr + n0 + 32 * w + (lane_ & 7) * 4) * 4u);
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-            rv[slot][j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsR, vo_, (int)((32 * i + 8 * j) * ldr * 4), 0));
+            rv[slot][j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsR, vo_, (int)((unsigned)(32 * i + 8 * j) * (unsigned)ldr * 4u), 0));
     };
 #endif
     // (lane_ is `lane` behind a compiler barrier at the call sites below: the 64-bit row addresses of the epilogue must
@@ -391,30 +395,40 @@ __device__ __forceinline__ void f32_tile(const GemmArgs& g, const float* __restr
         return;
     }
 #else
-    if (fast) {
-        const int voC = (int)((((int64_t)m0 + erow) * ldc + n) * 4);
-        const bool relu = act == ACT_RELU;
+    if constexpr (FAST) {
+        const int voC = (int)(((unsigned)(m0 + erow) * (unsigned)ldc + n) * 4u);   // (32-bit unsigned, as prefetch_fast)
+        // The activation and the residual are launch constants: the combinations the estimator's launches use (residual and no
+        // activation, ReLU, neither) get their own copy of the loop, so an element costs its own arithmetic and no select
+        // between the variants (the same operations either way).  A residual with a ReLU takes the residual's copy with the
+        // ReLU as a select: a fourth copy does not fit the registers without spilling.
+        auto epilogue = [&](auto relu_c, auto res_c) {
+            const bool relu = relu_c;
+            constexpr bool res = decltype(res_c)::value;
 #pragma unroll
-        for (int i = 0; i < TM; ++i) {
+            for (int i = 0; i < TM; ++i) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) patch[((r & 3) + 8 * (r >> 2) + 4 * h) * F_PATCH_LD + c] = acc[i][r];
-            if (i + 1 < TM && has_res) prefetch_fast(i + 1, (i + 1) & 1, lane_e);
+                for (int r = 0; r < 16; ++r) patch[((r & 3) + 8 * (r >> 2) + 4 * h) * F_PATCH_LD + c] = acc[i][r];
+                if (i + 1 < TM && res) prefetch_fast(i + 1, (i + 1) & 1, lane_e);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const f32x4 v = *reinterpret_cast<const f32x4*>(patch + (erow + 8 * j) * F_PATCH_LD + col4);
-                f32x4 o;
+                for (int j = 0; j < 4; ++j) {
+                    const f32x4 v = *reinterpret_cast<const f32x4*>(patch + (erow + 8 * j) * F_PATCH_LD + col4);
+                    f32x4 o;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float t = v[e] + bn[e];                      // (epi_value's arithmetic with bm = 0: acc + bn is never -0, so the
-                    if (relu) t = fmaxf(t, 0.f);                 //  dropped "+ 0.f" changes no bit)
-                    if (has_res) t = rv[i & 1][j][e] + alpha * t;
-                    o[e] = t;
+                    for (int e = 0; e < 4; ++e) {
+                        float t = v[e] + bn[e];                      // (epi_value's arithmetic with bm = 0: acc + bn is never -0, so the
+                        if (relu) t = fmaxf(t, 0.f);                 //  dropped "+ 0.f" changes no bit)
+                        if (res) t = rv[i & 1][j][e] + alpha * t;
+                        o[e] = t;
+                    }
+                    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), rsC, voC, (int)((unsigned)(32 * i + 8 * j) * (unsigned)ldc * 4u), 0);
+                    F32_AFTER_STORE(o)
                 }
-                typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), rsC, voC, (int)((32 * i + 8 * j) * ldc * 4), 0);
-                F32_AFTER_STORE(o)
             }
-        }
+        };
+        if (has_res) epilogue(act == ACT_RELU, std::true_type{});
+        else if (act == ACT_RELU) epilogue(std::true_type{}, std::false_type{});
+        else epilogue(std::false_type{}, std::false_type{});
         F32_EPILOGUE_PROBE
         return;
     }
@@ -466,7 +480,7 @@ struct F32Plan {
 #endif
 };
 
-template <bool BD>
+template <bool BD, bool FAST>
 __global__ __launch_bounds__(256, 4) void gemm_f32_kernel(GemmArgs g, F32Plan p) {
     __shared__ __attribute__((aligned(16))) float lds[2 * F_BUF];
     const int b = blockIdx.x, v = b % p.ncu, j = b / p.ncu;
@@ -484,28 +498,47 @@ __global__ __launch_bounds__(256, 4) void gemm_f32_kernel(GemmArgs g, F32Plan p)
         p.dbg[4 * b + 3] = __builtin_readcyclecounter();
     }
 #endif
+    // (row unit r, column panel tn, batch entry bz of pos: divided out once, then stepped -- a tile never crosses a panel)
+    const int64_t panel0 = pos / p.u;
+    int r = (int)(pos - panel0 * p.u);
+    int bz = (int)(panel0 / p.tiles_n), tn = (int)(panel0 - (int64_t)bz * p.tiles_n);
     while (pos < end) {
-        const int64_t panel = pos / p.u;
-        const int r = (int)(pos - panel * p.u);
         const int tm = (int)std::min<int64_t>(std::min<int64_t>(want, end - pos), p.u - r);
-        const int bz = (int)(panel / p.tiles_n), tn = (int)(panel - (int64_t)bz * p.tiles_n);
         const float* A = g.A + (int64_t)bz * g.strideA;
         const float* B = g.B + (int64_t)bz * g.strideB;
         float* C = g.C + (int64_t)bz * g.strideC;
         if (!first) __syncthreads();   // the previous tile's epilogue patches lie over the slab buffers
         first = false;
         switch (tm) {
-            case 1: f32_tile<1, BD>(g, A, B, C, 32 * r, tn * BN, lds); break;
-            case 2: f32_tile<2, BD>(g, A, B, C, 32 * r, tn * BN, lds); break;
-            case 3: f32_tile<3, BD>(g, A, B, C, 32 * r, tn * BN, lds); break;
-            default: f32_tile<4, BD>(g, A, B, C, 32 * r, tn * BN, lds); break;
+            case 1: f32_tile<1, BD, FAST>(g, A, B, C, 32 * r, tn * BN, lds); break;
+            case 2: f32_tile<2, BD, FAST>(g, A, B, C, 32 * r, tn * BN, lds); break;
+            case 3: f32_tile<3, BD, FAST>(g, A, B, C, 32 * r, tn * BN, lds); break;
+            default: f32_tile<4, BD, FAST>(g, A, B, C, 32 * r, tn * BN, lds); break;
         }
         pos += tm;
         want = p.max_tm;
+        r += tm;
+        if (r == p.u) {
+            r = 0;
+            if (++tn == p.tiles_n) { tn = 0; ++bz; }
+        }
     }
 #if F32_TOOLS
     if (p.dbg && threadIdx.x == 0) { p.dbg[4 * b + 1] = wall_clock64(); p.dbg[4 * b + 3] = __builtin_readcyclecounter() - p.dbg[4 * b + 3]; }
 #endif
+}
+
+// Whether a launch takes the fast epilogue (f32_tile): it depends on the launch arguments only, so the host picks the
+// kernel -- 16-byte pieces (every batch entry's C aligned too), whole 128-column panels, column bias or none, no sigmoid, C and
+// the residual below 2 GiB for the descriptors' 32-bit range.
+static bool f32_fast_epilogue(const GemmArgs& g) {
+    const int64_t lim = (int64_t)1 << 31;
+    const bool has_res = g.residual != nullptr;
+    const bool wide = (g.ldc % 4 == 0) && (g.N % 4 == 0) && ((reinterpret_cast<uintptr_t>(g.C) & 15) == 0) &&
+                      (g.batch == 1 || g.strideC % 4 == 0) &&
+                      (!has_res || ((g.ldr % 4 == 0) && ((reinterpret_cast<uintptr_t>(g.residual) & 15) == 0)));
+    return F32_FAST_EPILOGUE && wide && !(g.bias && g.bias_along_m) && (g.N % BN == 0) && g.act != ACT_SIGMOID &&
+           (int64_t)g.M * g.ldc * 4 < lim && (!has_res || (int64_t)g.M * g.ldr * 4 < lim);
 }
 
 // false: an operand the 32-bit buffer offsets cannot address, or a K that is not a multiple of 16 (use gemm_kernel)
@@ -526,8 +559,10 @@ bool launch_gemm_f32(const GemmArgs& g, hipStream_t s, int forced_tm) {
 #if F32_TOOLS
     p.dbg = g.narrow_epilogue == 77 ? reinterpret_cast<unsigned long long*>(g.range_flag) : nullptr;   // (tools/gemm_f32_bench.hip)
 #endif
-    if (g.b_frag32) hipLaunchKernelGGL(gemm_f32_kernel<true>, dim3(4 * NCU), dim3(256), 0, s, g, p);
-    else hipLaunchKernelGGL(gemm_f32_kernel<false>, dim3(4 * NCU), dim3(256), 0, s, g, p);
+    const bool fast = f32_fast_epilogue(g);
+    void (*kern)(GemmArgs, F32Plan) = g.b_frag32 ? (fast ? gemm_f32_kernel<true, true> : gemm_f32_kernel<true, false>)
+                                                 : (fast ? gemm_f32_kernel<false, true> : gemm_f32_kernel<false, false>);
+    hipLaunchKernelGGL(kern, dim3(4 * NCU), dim3(256), 0, s, g, p);
     return true;
 }
 

@@ -61,10 +61,15 @@ int main(int argc, char** argv) {
     {   // census of the persistent blocks of one launch: start / end (100 MHz wall clock), shader cycles, physical CU
         unsigned long long* dbg; hipMalloc(&dbg, 1024 * 96);   // [1024][4] census + [1024][4] slab-clock sums of wave 0 (builds with -DF32_PROBE=1)
         float* Bfc = nullptr; hipMalloc(&Bfc, maxB * 4 + 4096);
-        struct Cs { int M, N, K; } cases[] = {{22320, 512, 1824}, {22320, 512, 512}, {22320, 1536, 512}, {7440, 512, 512}};
+        // (GEMM_BENCH_M: the estimator's five Linear shapes at that height with their bias / residual, as the timing table runs them)
+        struct Cs { int M, N, K, mode; } cases[] = {{22320, 512, 1824, 0}, {22320, 512, 512, 0}, {22320, 1536, 512, 0}, {7440, 512, 512, 0}, {0, 0, 0, 0}};
+        if (getenv("GEMM_BENCH_M"))
+            for (int i = 0; i < 5; ++i) cases[i] = Cs{Ms[1], shapes[i].N, shapes[i].K, shapes[i].mode};
         for (auto& cs : cases) {
+            if (!cs.M) continue;
             GemmArgs g{};
             g.A = A; g.lda = cs.K; g.B = B; g.ldb = cs.K; g.C = C; g.ldc = cs.N; g.M = cs.M; g.N = cs.N; g.K = cs.K; g.batch = 1; g.alpha = 1.f;
+            if (getenv("GEMM_BENCH_M")) { g.bias = A; if (cs.mode == 1) { g.residual = R; g.ldr = cs.N; g.alpha = 0.5f; } }
             g.layout = 1; g.narrow_epilogue = 77; g.range_flag = (unsigned int*)dbg;
             if (getenv("GEMM_BENCH_FRAG")) { launch_f32_fragments(B, cs.K, Bfc, cs.N, cs.K, st); g.B = Bfc; g.b_frag32 = 1; }
             for (int i = 0; i < 3; ++i) launch_gemm(g, st);
@@ -80,6 +85,12 @@ int main(int argc, char** argv) {
                 double pp = 0, ptl = 0, pe = 0;
                 for (int b = 0; b < 1024; ++b) { pp += d[8192 + 4 * b]; ptl += d[8192 + 4 * b + 1]; pe += d[8192 + 4 * b + 2]; }
                 if (ptl > 0) printf("   per tile of wave 0 (mean over %.0f tiles): prologue %.0f clocks, %.1f counted slabs x %.0f, last slab + epilogue %.0f\n", ptl, pp / ptl, pn / ptl, (pc + pl + pb) / pn, pe / ptl);
+                if (ptl > 0) {   // a block's clocks (10 launches) against the probe's parts: the rest is what the probe does not bracket
+                    double blk = 0; for (int b = 0; b < 1024; ++b) blk += d[4 * b + 3];
+                    blk *= 10;   // (the census holds the last launch's block clocks; the probe sums cover all 10)
+                    printf("   wave-0 clocks of the 10 launches: %.4g in all = prologue %.1f %% + slab loop %.1f %% + last slab and epilogue %.1f %% + rest %.1f %%\n", blk,
+                           100 * pp / blk, 100 * (pc + pl + pb) / blk, 100 * pe / blk, 100 * (blk - pp - pc - pl - pb - pe) / blk);
+                }
                 if (pn > 0) printf("   slab clocks of wave 0 (mean over %.0f slabs): %.0f issuing the slab's MFMAs (operand reads, loads) + %.0f LDS stores (wait for the global loads) + %.0f barrier = %.0f per slab; 32 MFMAs x 4 waves per SIMD = 8192\n",
                                    pn, pc / pn, pl / pn, pb / pn, (pc + pl + pb) / pn);
             }
