@@ -322,7 +322,8 @@ int css_run_pcm16(css_handle_t h, const int16_t* const* planes_host, int64_t n_s
  * The n_ch plane pointers are copied at the call; the planes, wav_pcm16_host [S][cap] and peaks_host (NULL or S floats) must
  * stay valid and untouched until css_wait.  With page-locked planes / output (css_host_alloc) the session joins a shared
  * batch and its PCIe legs hide under its neighbours' kernels; with pageable output it runs as a pass of its own.  Results
- * are bit for bit css_run_pcm16's (tests/test_hip_session.py).  frame_len 512 / frame_hop 256 only, like css_run_pcm16. */
+ * are bit for bit css_run_pcm16's (tests/test_hip_session.py).  Any frame geometry: other than frame_len 512 / frame_hop 256
+ * the session runs to its end inside the call, like css_run_pcm16 (nothing of it stays queued). */
 int css_run_enqueue_pcm16(css_handle_t h, const int16_t* const* planes_host, int64_t n_samples, int32_t n_ch, const CssRunCfg* cfg,
                           int16_t* wav_pcm16_host, int64_t wav_capacity_per_stream, float* peaks_host);
 int css_get_timings(css_handle_t h, CssTimings* out);

@@ -481,8 +481,10 @@ int css_create(const CssModelDesc* desc, const float* blob_host, int64_t blob_fl
     }
     for (auto& e : h->ev)
         if (hipEventCreate(&e) != hipSuccess) return bail(CSS_ERR_HIP, "hipEventCreate failed");
-    if (hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess)
-        return bail(CSS_ERR_HIP, "hipEventCreate failed");
+    // untimed events: the lanes' fork, and the overlap protocol of queued passes (api_queue.hip)
+    for (hipEvent_t* e : {&h->ev_fork, &h->tail_end, &h->pcm_free[0], &h->pcm_free[1], &h->level_free[0], &h->level_free[1],
+                          &h->pass_end[0], &h->pass_end[1], &h->pass_end[2], &h->pass_end[3]})
+        if (hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) return bail(CSS_ERR_HIP, "hipEventCreate failed");
     const bool dealt = deal_streams(h->stream, h->lane_stream, &h->copy_stream, &h->tail_stream);
     for (int l = 1; l < css_ctx::MAX_LANES; ++l)
         if ((!dealt && hipStreamCreateWithFlags(&h->lane_stream[l], hipStreamNonBlocking) != hipSuccess) ||

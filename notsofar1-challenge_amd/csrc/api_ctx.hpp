@@ -90,6 +90,32 @@ struct SessState {
     int64_t mask_ld_v = 0;
 };
 
+// Where the samples of a pass come from and where its result goes (exactly one source, exactly one sink).
+struct RunIo {
+    const float* pcm_host = nullptr;             // [n][C] float32 in host memory   (css_run)
+    const float* pcm_dev = nullptr;              // [n][C] float32 in HBM           (css_run_device)
+    const int16_t* const* planes_host = nullptr; // C mono PCM16 planes in host memory (css_run_pcm16)
+    float* wav_host = nullptr;                   // [S][cap] float32
+    float* wav_dev = nullptr;
+    int16_t* wav16_host = nullptr;               // [S][cap] peak-normalised PCM16
+    float* peaks_host = nullptr;
+    int64_t cap = 0;
+    bool enqueue_only = false;                   // css_run_enqueue: return once everything is on the streams
+    // host to host: float PCM -> float waveforms (pcm, wav) or PCM16 planes -> PCM16 streams and their peaks (planes, wav16, peaks)
+    static RunIo host(const float* pcm, const int16_t* const* planes, float* wav, int16_t* wav16, float* peaks, int64_t cap,
+                      bool enqueue_only = false) {
+        RunIo io;
+        io.pcm_host = pcm; io.planes_host = planes; io.wav_host = wav; io.wav16_host = wav16; io.peaks_host = peaks;
+        io.cap = cap; io.enqueue_only = enqueue_only;
+        return io;
+    }
+    static RunIo device(const float* pcm, float* wav, int64_t cap) {
+        RunIo io;
+        io.pcm_dev = pcm; io.wav_dev = wav; io.cap = cap;
+        return io;
+    }
+};
+
 struct css_ctx : SessState {
     CssModelDesc d{};
     int device = 0;
@@ -136,17 +162,17 @@ struct css_ctx : SessState {
     hipEvent_t ev_fork = nullptr, ev_join[MAX_LANES] = {};
     DevBuf lfeat[MAX_LANES], lhx[MAX_LANES], lhu[MAX_LANES], lht[MAX_LANES], lqkv[MAX_LANES], lqkf[MAX_LANES], lctx[MAX_LANES];   // [0] unused
     int64_t last_batch_tokens = 0;
-    // PCIe pieces of css_run* travel on their own stream, beside the kernels: the upload of the samples a lane's segments
-    // read is followed by that lane's analysis transform and mask-estimator chain while the next piece is in flight, and
-    // finished ranges of the output leave while the last ranges are still being synthesised.
+    int mel_bands = 0;                    // the filterbank mel_tab holds (0: none yet)
     // range check of the split-f16 operand format (split_f16.hpp): a device word set when the stitched activity or the
     // waveforms hold a non-finite value, mirrored into page-locked host memory at the end of every pass
-    int mel_bands = 0;                    // the filterbank mel_tab holds (0: none yet)
     unsigned int* range_flag_dev = nullptr;
     unsigned int* range_flag_host = nullptr;
     bool range_fallback = true;      // repeat such a pass on the exact float32 kernels (else: CSS_ERR_RANGE)
     int64_t range_fallbacks = 0;     // passes repeated so far
     int range_last = 0;              // the last pass hit the range limit
+    // PCIe pieces of css_run* travel on their own stream, beside the kernels: the upload of the samples a lane's segments
+    // read is followed by that lane's analysis transform and mask-estimator chain while the next piece is in flight, and
+    // finished ranges of the output leave while the last ranges are still being synthesised.
     hipStream_t copy_stream = nullptr;
     // css_run*: what follows the mask estimator (covariances and beamformer per segment on the lanes, then -- in segment
     // order, on this stream -- stitching costs, the permutation scan, overlap-add, gate, synthesis) trails the lanes unit
@@ -156,13 +182,12 @@ struct css_ctx : SessState {
     int tune[CSS_TUNE_COUNT] = {1, 0, 0, 1, 0, 2, 1, 0, 1, 0, 24576, 14000};
     const void* mapped_key = nullptr;   // last page-locked output buffer looked up, and its device address
     void* mapped_val = nullptr;
-    // css_upload_range: further pieces of the recording on their way over PCIe (copy stream); css_stage_stft_range makes
-    // the handle's stream wait for exactly the pieces its frames read
     // css_run_enqueue / css_wait: passes enqueued and not yet waited for
     int queued = 0;
     // queued passes overlap: pass P's samples cross PCIe while pass P - 1's kernels run, and P - 1's stitching / synthesis /
     // download run beside P's estimator.  The sample buffer and the level word alternate (pass parity); `pcm_free[b]` =
     // the last transform of the pass that used sample buffer b; `tail_end` = the end of the last queued pass's tail
+    // (untimed events, created with the handle)
     int64_t pass_no = 0;
     hipEvent_t pcm_free[2] = {nullptr, nullptr};
     hipEvent_t pass_end[4] = {nullptr, nullptr, nullptr, nullptr};   // ends of the last four queued passes (back-pressure)
@@ -171,14 +196,18 @@ struct css_ctx : SessState {
     bool tail_pending = false;
     bool piped_now = false;   // run_once -> begin_impl: the level word is cleared on the copy stream, not here
     int last_piped = -1;      // overlap mode of the last queued pass (-1: nothing queued): a queue never mixes modes un-drained
-    // css_run_enqueue's arguments since the last css_wait: a queued pass that left the split-f16 range is repeated from
-    // them on the exact float32 kernels (the caller keeps pcm_host valid and wav_host untouched until css_wait anyway)
-    struct QueuedPass {
+    // One session of css_run_enqueue / css_run_enqueue_pcm16: the call's arguments, with its own copy of the three stitching
+    // windows and of the plane pointers (the caller may free its own; it keeps the samples valid and the output untouched
+    // until css_wait anyway).  PCM16 session: planes set, pcm == wav == nullptr.
+    struct QueuedSession {
         const float* pcm; int64_t n; int32_t n_ch; CssRunCfg cfg; float* wav; int64_t cap;
-        std::vector<const int16_t*> planes; int16_t* wav16 = nullptr; float* peaks = nullptr;   // css_run_enqueue_pcm16 (pcm == wav == nullptr)
-        std::vector<float> w;   // the three stitching windows of cfg, copied at css_run_enqueue (the caller may free its own)
-        QueuedPass(const float* pcm_, int64_t n_, int32_t n_ch_, const CssRunCfg& c, float* wav_, int64_t cap_)
-            : pcm(pcm_), n(n_), n_ch(n_ch_), cfg(c), wav(wav_), cap(cap_) {
+        std::vector<const int16_t*> planes; int16_t* wav16; float* peaks;
+        float* wav_mapped;      // device address of the page-locked output (nullptr: pageable, or never looked up)
+        std::vector<float> w;   // w_first | w_mid | w_last of cfg
+        QueuedSession(const float* pcm_, const int16_t* const* planes_, int64_t n_, int32_t n_ch_, const CssRunCfg& c, float* wav_,
+                      int16_t* wav16_, float* peaks_, int64_t cap_, float* mapped_)
+            : pcm(pcm_), n(n_), n_ch(n_ch_), cfg(c), wav(wav_), cap(cap_), wav16(wav16_), peaks(peaks_), wav_mapped(mapped_) {
+            if (planes_) planes.assign(planes_, planes_ + n_ch_);
             const size_t T = (size_t)std::max(c.segment_frames, 0);
             w.resize(3 * T);
             if (T && c.w_first && c.w_mid && c.w_last) {
@@ -187,20 +216,29 @@ struct css_ctx : SessState {
                 std::memcpy(w.data() + 2 * T, c.w_last, T * sizeof(float));
             }
         }
-        CssRunCfg own_cfg() const {   // cfg with its window pointers at this entry's copies
+        bool pcm16() const { return !planes.empty(); }
+        CssRunCfg own_cfg() const {   // cfg with its window pointers at this record's copies
             CssRunCfg c = cfg;
             const size_t T = w.size() / 3;
             c.w_first = w.data(); c.w_mid = w.data() + T; c.w_last = w.data() + 2 * T;
             return c;
         }
+        RunIo io(bool enqueue_only) const {
+            return RunIo::host(pcm, pcm16() ? planes.data() : nullptr, wav, wav16, peaks, cap, enqueue_only);
+        }
+        // may the two share an estimator batch: one segmentation, the same three windows bit for bit
+        bool groups_with(const QueuedSession& o) const {
+            return cfg.segment_frames == o.cfg.segment_frames && cfg.hop_frames == o.cfg.hop_frames && w.size() == o.w.size() &&
+                   std::memcmp(w.data(), o.w.data(), w.size() * sizeof(float)) == 0;
+        }
     };
-    std::vector<QueuedPass> queue_log;
+    // sessions put on the streams since the last css_wait: a queued pass that left the split-f16 range is repeated from
+    // them on the exact float32 kernels
+    std::vector<QueuedSession> queue_log;
     // css_run_enqueue: sessions accepted and not yet on the streams -- they wait for company: sessions of one segment
-    // length are merged into ONE estimator batch (run_group) as long as their segments fit max_batch_segments
-    struct Pending { const float* pcm; int64_t n; int32_t n_ch; CssRunCfg cfg; std::vector<float> w; float* wav; int64_t cap;
-                     float* wav_mapped; int64_t nseg;
-                     std::vector<const int16_t*> planes; int16_t* wav16 = nullptr; float* peaks = nullptr; };   // PCM16 edges: pcm == wav == nullptr
-    std::vector<Pending> pending;
+    // length are merged into ONE estimator batch (run_group) as long as their segments fit max_batch_segments; flush_pending
+    // moves them into queue_log
+    std::vector<QueuedSession> pending;
     int64_t pending_segments = 0;
     // css_wait_sessions: one event per session put on the streams since the last css_wait, in queue order, recorded behind the
     // session's last output copy (nullptr: the session had finished inside its call)
@@ -209,6 +247,8 @@ struct css_ctx : SessState {
     size_t sess_ev_used = 0;
     void* comm = nullptr;          // ncclComm_t of css_comm_init (RCCL, loaded lazily)
     int comm_ranks = 0, comm_rank = -1;
+    // css_upload_range: further pieces of the recording on their way over PCIe (copy stream); css_stage_stft_range makes
+    // the handle's stream wait for exactly the pieces its frames read
     struct PendingUpload { int64_t s_lo, s_hi; hipEvent_t landed; };
     std::vector<PendingUpload> uploads;
     std::vector<hipEvent_t> ev_pool;   // untimed events of the pipeline (uploads landed, planes ready, ranges finished)

@@ -2,20 +2,6 @@
 // of sessions (css_run_enqueue* / css_wait / css_wait_sessions) and the estimator batches queued sessions share.  (api_ctx.hpp: shared.)
 #include "api_ctx.hpp"
 
-// ---- the fused pass --------------------------------------------------------------------------------------------------
-// Where the samples of a pass come from and where its result goes (exactly one source, exactly one sink).
-struct RunIo {
-    const float* pcm_host = nullptr;             // [n][C] float32 in host memory   (css_run)
-    const float* pcm_dev = nullptr;              // [n][C] float32 in HBM           (css_run_device)
-    const int16_t* const* planes_host = nullptr; // C mono PCM16 planes in host memory (css_run_pcm16)
-    float* wav_host = nullptr;                   // [S][cap] float32
-    float* wav_dev = nullptr;
-    int16_t* wav16_host = nullptr;               // [S][cap] peak-normalised PCM16
-    float* peaks_host = nullptr;
-    int64_t cap = 0;
-    bool enqueue_only = false;                   // css_run_enqueue: return once everything is on the streams
-};
-
 // device address of page-locked (hipHostMalloc / css_host_alloc / registered) host memory, nullptr for pageable memory
 void* mapped_host(const void* p) {
     hipPointerAttribute_t at{};
@@ -78,6 +64,150 @@ int finish_timings(css_ctx* h, HostClock t0, HostClock t1, HostClock t2, bool st
     return CSS_OK;
 }
 
+// ---- steps the schedules below share -----------------------------------------------------------------------------------
+// the synchronous ending of a pass whose last command is on the handle's stream (t0: the call's begin)
+static int sync_and_time(css_ctx* h, HostClock t0, bool staged) {
+    const auto t1 = std::chrono::steady_clock::now();
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipGetLastError());
+    return finish_timings(h, t0, t1, std::chrono::steady_clock::now(), staged);
+}
+
+// whatever the handle's three streams hold finishes on the device (the queue's bookkeeping stays with the caller)
+static int drain_streams(css_ctx* h) {
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->tail_stream));
+    HIPCHK(h, hipStreamSynchronize(h->copy_stream));
+    h->tail_pending = false;
+    return CSS_OK;
+}
+
+// Overlapping queued passes (css_ctx::pass_no) alternate between the two halves of the sample buffer, whatever their lengths
+static const char* pcm_half(const css_ctx* h, int par) { return (const char*)h->pcm_in.p + (par ? h->pcm_in.cap / 2 / 256 * 256 : 0); }
+
+// ... and open on the copy stream: this parity's sample buffer, planes and level words were last used by the pass before
+// last -- free once that pass has transformed its frames (pcm_free) and its tail, the level words' last reader, has ended
+// (level_free: the host may be several passes ahead of the device).  `level` [n_words] is cleared here, in front of the
+// peak scans (each stream is in order in itself).
+constexpr int CSS_QUEUE_LEAD = 3;   // queued passes the host may be ahead of the device (css_run_enqueue blocks beyond)
+static int open_overlapping_pass(css_ctx* h, int par, unsigned int* level, int n_words, bool after_main) {
+    // back-pressure: the host stays at most CSS_QUEUE_LEAD passes ahead of the device.  It enqueues a pass in 2 ms, the
+    // device runs one in 5; an unbounded lead only makes the runtime grow its command and signal pools (measured:
+    // 3.4 instead of 2.1 ms of enqueue time per pass while they grow, 5.7 instead of 5.4 ms per pass) and buys nothing.
+    if (h->pass_no >= CSS_QUEUE_LEAD) HIPCHK(h, hipEventSynchronize(h->pass_end[(h->pass_no - CSS_QUEUE_LEAD) & 3]));
+    if (after_main) {
+        hipEvent_t opened = pool_event(h);
+        HIPCHK(h, hipEventRecord(opened, h->stream));
+        HIPCHK(h, hipStreamWaitEvent(h->copy_stream, opened, 0));
+    }
+    if (h->pass_no >= 2) {
+        HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->pcm_free[par], 0));
+        HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->level_free[par], 0));
+    }
+    HIPCHK(h, hipMemsetAsync(level, 0, (size_t)n_words * sizeof(unsigned int), h->copy_stream));
+    return CSS_OK;
+}
+
+// ... and close on the tail stream, without a join: the next queued pass's estimator runs beside this pass's tail; css_wait
+// waits for all streams
+static int close_overlapping_pass(css_ctx* h, int par) {
+    HIPCHK(h, hipEventRecord(h->tail_end, h->tail_stream));
+    HIPCHK(h, hipEventRecord(h->level_free[par], h->tail_stream));
+    HIPCHK(h, hipEventRecord(h->pass_end[h->pass_no & 3], h->tail_stream));
+    hipEventRecord(h->ev[7], h->tail_stream);
+    h->tail_pending = true;
+    h->pass_no += 1;
+    h->queued += 1;
+    HIPCHK(h, hipGetLastError());
+    return CSS_OK;
+}
+
+// short input: zero-padded frames (css.py:159-164)
+static int zero_short_planes(css_ctx* h, hipStream_t st) {
+    if (h->plan.stft_frames < h->plan.mix_frames)
+        HIPCHK(h, hipMemsetAsync(h->X.p, 0, (size_t)h->n_ch * X_ROWS_PER_BIN * h->d.num_bins * h->T_ld * sizeof(float), st));
+    return CSS_OK;
+}
+
+// The first wav edge: samples [s_lo, s_hi) of mono PCM16 plane `c` (n samples) up to their place in dst16 [C][n] (they are
+// scaled by 2^-15 on the way to channel-major, stft_frames), and their share of the recording's level
+static int plane_up(css_ctx* h, const int16_t* const* planes, int16_t* dst16, int64_t n, int c, int64_t s_lo, int64_t s_hi, hipStream_t st) {
+    HIPCHK(h, hipMemcpyAsync(dst16 + (size_t)c * n + s_lo, planes[c] + s_lo, (size_t)(s_hi - s_lo) * sizeof(int16_t), hipMemcpyHostToDevice, st));
+    return CSS_OK;
+}
+static void plane_peak(css_ctx* h, const int16_t* dst16, int64_t n, int c, int64_t s_lo, int64_t s_hi, hipStream_t st) {
+    launch_pcm_peak_i16(dst16 + (size_t)c * n + s_lo, peak_len(h, s_lo, s_hi), h->peak_dev, st);
+}
+// (a whole recording: plane by plane, each followed by its scan)
+static int planes_up(css_ctx* h, const int16_t* const* planes, int16_t* dst16, int64_t n, int n_ch, hipStream_t st) {
+    for (int c = 0; c < n_ch; ++c) {
+        if (int e = plane_up(h, planes, dst16, n, c, 0, n, st)) return e;
+        plane_peak(h, dst16, n, c, 0, n, st);
+    }
+    return CSS_OK;
+}
+
+// The second wav edge on the device (utils/audio_utils.py:37-49 write_wav): peak normalisation and PCM16 encoding of the
+// session's streams `src` [S][n_out], then half the PCIe bytes back
+static int encode_pcm16_out(css_ctx* h, const float* src, int16_t* wav16, int64_t cap, float* peaks, hipStream_t st) {
+    const int S = h->d.num_spks;
+    const int64_t n_out = h->plan.n_out;
+    unsigned int* pk = (unsigned int*)h->enc.p;
+    int16_t* o16 = (int16_t*)((char*)h->enc.p + 64);
+    { CSS_PROF(CSS_PROF_ENCODE, st); launch_encode_pcm16(src, S, n_out, pk, o16, n_out, st); }
+    HIPCHK(h, hipMemcpy2DAsync(wav16, (size_t)cap * sizeof(int16_t), o16, (size_t)n_out * sizeof(int16_t), (size_t)n_out * sizeof(int16_t), S,
+                               hipMemcpyDeviceToHost, st));
+    if (peaks) HIPCHK(h, hipMemcpyAsync(peaks, pk, (size_t)S * sizeof(float), hipMemcpyDeviceToHost, st));
+    return CSS_OK;
+}
+
+// samples [a, b) of the float waveforms `src` [S][src_ld] to the caller's [S][cap], stream by stream
+static int waveforms_out(css_ctx* h, const float* src, int64_t src_ld, float* wav, int64_t cap, int64_t a, int64_t b, hipStream_t st) {
+    for (int sp = 0; sp < h->d.num_spks; ++sp)
+        HIPCHK(h, hipMemcpyAsync(wav + (size_t)sp * cap + a, src + (size_t)sp * src_ld + a, (size_t)(b - a) * sizeof(float), hipMemcpyDeviceToHost, st));
+    return CSS_OK;
+}
+
+// ---- the fused pass --------------------------------------------------------------------------------------------------
+// The plain stage sequence (whole transform, estimator with its lanes, beamformer, costs, scan, overlap-add, gate,
+// synthesis on one stream), samples up and waveforms down as whole copies, to its synchronous end.  Taken
+//   - by other frame sizes (ExtractorCfg.frame_len / frame_hop): the pipelined schedule is built around frame_len = 2 hop;
+//   - with nothing to hide: with the samples already in HBM it measures 2 % ahead of the unit pipeline
+//     (profiles/r02_shard_overhead.md: 5.35 vs 5.43 ms per 60 s meeting, 143.0 vs 146.2 ms per 30 min)
+static int run_plain(css_ctx* h, int64_t n, int32_t n_ch, const RunIo& io, HostClock t0) {
+    int rc;
+    const CssPlan& pl = h->plan;
+    const int64_t nseg = pl.num_segments, TL = pl.mix_frames;
+    if (io.pcm_host) HIPCHK(h, hipMemcpyAsync(h->pcm_in.p, io.pcm_host, (size_t)n * n_ch * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    if (io.planes_host) {
+        if ((rc = planes_up(h, io.planes_host, (int16_t*)h->in16.p, n, n_ch, h->stream)) != CSS_OK) return rc;
+        if ((rc = zero_short_planes(h, h->stream)) != CSS_OK) return rc;
+        if ((rc = stft_frames(h, 0, TL, (const int16_t*)h->in16.p, h->stream)) != CSS_OK) return rc;
+        hipEventRecord(h->ev[2], h->stream);
+        h->stft_done = true;
+    } else {
+        launch_pcm_peak_f32(h->pcm_src, peak_len(h, 0, n) * n_ch, h->peak_dev, h->stream);
+        if ((rc = css_stage_stft(h)) != CSS_OK) return rc;
+    }
+    if ((rc = css_stage_masknet(h, 0, nseg)) != CSS_OK) return rc;
+    if ((rc = css_stage_mvdr(h, 0, nseg)) != CSS_OK) return rc;
+    if ((rc = css_stage_pit_costs(h, 0, nseg - 1)) != CSS_OK) return rc;
+    if ((rc = css_stage_pit_scan(h)) != CSS_OK) return rc;
+    if ((rc = css_stage_stitch(h, 0, TL)) != CSS_OK) return rc;
+    float* dst = io.wav_dev;
+    int64_t dst_ld = io.cap;
+    if (!dst) {
+        if ((rc = ensure(h, h->wav, (size_t)h->d.num_spks * pl.n_out * sizeof(float))) != CSS_OK) return rc;
+        dst = (float*)h->wav.p; dst_ld = pl.n_out;
+    }
+    if ((rc = istft_impl(h, 0, TL, 0, TL - 1 + h->ovl, dst, dst_ld, 0, h->stream)) != CSS_OK) return rc;
+    if (io.wav16_host && (rc = encode_pcm16_out(h, dst, io.wav16_host, io.cap, io.peaks_host, h->stream)) != CSS_OK) return rc;
+    if (io.wav_host && (rc = waveforms_out(h, dst, dst_ld, io.wav_host, io.cap, 0, pl.n_out, h->stream)) != CSS_OK) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->range_flag_host, h->range_flag_dev, sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
+    hipEventRecord(h->ev[7], h->stream);
+    return sync_and_time(h, t0, true);
+}
+
 // One pass of css/css.py:110 separate_and_stitch as a pipeline.  The recording's segments go through the mask estimator
 // in batches, each cut into lanes (css_ctx::lanes); a (batch, lane) UNIT owns the frames no earlier unit reads.
 //   in    its samples cross PCIe on the copy stream as one piece; the lane's chain waits for that piece only, transforms
@@ -87,145 +217,15 @@ int finish_timings(css_ctx* h, HostClock t0, HostClock t1, HostClock t2, bool st
 //         them (css.py:266-285 is sequential, but only forwards), overlap-add of the frames no later segment covers,
 //         gate and synthesis of those frames less the dilate / erode halo, and their samples back over PCIe --
 //         while the lanes work on the next batch.  Only the last batch's tail is not hidden.
-constexpr int CSS_QUEUE_LEAD = 3;   // queued passes the host may be ahead of the device (css_run_enqueue blocks beyond)
-int run_once(css_handle_t h, int64_t n, int32_t n_ch, const CssRunCfg* cfg, const RunIo& io) {
-    int rc;
-    if (!h) return CSS_ERR_INVALID_ARG;
-    const auto host_t0 = std::chrono::steady_clock::now();
-    // page-locked output (css_host_alloc): its device address, for the zero-copy output path
-    float* wav_mapped = nullptr;
-    if (io.wav_host && (h->tune[CSS_TUNE_OUT_MAPPED] || io.enqueue_only)) {
-        if (h->mapped_key != io.wav_host) { h->mapped_key = io.wav_host; h->mapped_val = mapped_host(io.wav_host); }
-        wav_mapped = (float*)h->mapped_val;
-    }
-    // queued passes OVERLAP when the output is page-locked (see css_ctx::pass_no); otherwise they just queue up
-    // (with the beamformer on the tail stream -- CSS_TUNE_MVDR_ON_LANES = 0 -- a tail also reads the spectra X, which the
-    // next pass's transform overwrites: such passes queue up without overlapping)
-    const bool piped = h->fft512 && io.enqueue_only && io.pcm_host && wav_mapped && h->tune[CSS_TUNE_MVDR_ON_LANES];
-    if (io.enqueue_only && h->queued && h->last_piped != (int)piped) {
-        // the overlap mode changes inside a queue (a page-locked output follows a pageable one or the reverse): the two
-        // modes order the level word, the mask buffers and the tail differently, so the queue is drained on the device
-        // first (its bookkeeping -- css_wait, the range verdict -- stays with the caller)
-        HIPCHK(h, hipSetDevice(h->device));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->tail_stream));
-        HIPCHK(h, hipStreamSynchronize(h->copy_stream));
-        h->tail_pending = false;
-    }
-    if (io.enqueue_only) h->last_piped = (int)piped;
-    const int par = piped ? (int)(h->pass_no & 1) : 0;
-    h->peak_dev = (unsigned int*)h->level.p + 8 * par;
-    h->piped_now = piped;
-    // (overlapping passes alternate between the two sets of planes: a grouped pass in front of this one may still read
-    // its own on the tail stream -- run_group -- while this pass's transform writes)
-    if (piped) std::swap(h->X, h->X_alt);
-    rc = begin_impl(h, n, n_ch, cfg);
-    h->piped_now = false;
-    if (rc != CSS_OK) return rc;
+namespace {
+struct Unit { int64_t seg_lo; int n; int64_t f_lo, f_hi, s_lo, s_hi; hipEvent_t up, x, v, m; };   // pieces landed, planes, beamformer, costs
+
+// the units of the session's plan, in order: their segments, frames and samples (`cap`: segments per batch)
+std::vector<Unit> plan_units(const css_ctx* h, int64_t cap) {
     const CssPlan& pl = h->plan;
-    if (io.cap < pl.n_out) return fail(h, CSS_ERR_INVALID_ARG, "output buffer too small: need " + std::to_string(pl.n_out) + " samples per stream");
-    const int64_t nseg = pl.num_segments, TL = pl.mix_frames;
-    const int S = h->d.num_spks, F = h->d.num_bins, N = h->d.frame_len, fhop = h->d.frame_hop;
-    const int T = h->cfg.segment_frames, hop = h->cfg.hop_frames;
-    const bool from_host = io.pcm_host || io.planes_host;
-    h->ev_pool_used = 0;
-    if (io.pcm_host) {
-        const size_t need = ((size_t)n * n_ch * sizeof(float) + 255) / 256 * 256;
-        if ((rc = ensure(h, h->pcm_in, piped ? 2 * need : need)) != CSS_OK) return rc;
-        // (queued passes alternate between the two halves of the allocation, whatever their lengths)
-        h->pcm_src = (const float*)((const char*)h->pcm_in.p + (piped && par ? h->pcm_in.cap / 2 / 256 * 256 : 0));
-    } else if (io.planes_host) {
-        if ((rc = ensure(h, h->in16, (size_t)n * n_ch * sizeof(int16_t))) != CSS_OK) return rc;
-        for (int c = 0; c < n_ch; ++c)
-            if (!io.planes_host[c]) return fail(h, CSS_ERR_INVALID_ARG, "null channel plane");
-    } else {
-        h->pcm_src = io.pcm_dev;
-    }
-    if (io.wav16_host && (rc = ensure(h, h->enc, (size_t)S * pl.n_out * sizeof(int16_t) + 64)) != CSS_OK) return rc;
-    const int16_t* planes_dev = io.planes_host ? (const int16_t*)h->in16.p : nullptr;
-    hipEventRecord(h->ev[1], h->stream);
-    hipEventRecord(h->ev[2], h->stream);   // the analysis transform is part of the lanes' chains (CssTimings.stft = 0)
-
-    // ---- nothing to hide: with the samples already in HBM the plain stage sequence (whole transform, estimator with
-    // its lanes, beamformer, costs, scan, overlap-add, gate, synthesis on one stream) measures 2 % ahead of the unit
-    // pipeline below (profiles/r02_shard_overhead.md: 5.35 vs 5.43 ms per 60 s meeting, 143.0 vs 146.2 ms per 30 min)
-    if (!h->fft512) {
-        // Other frame sizes (ExtractorCfg.frame_len / frame_hop): the plain stage sequence on one stream, samples up and
-        // waveforms down as whole copies -- the pipelined schedules below are built around frame_len = 2 hop
-        if (io.pcm_host) {
-            if ((rc = ensure(h, h->pcm_in, (size_t)n * n_ch * sizeof(float))) != CSS_OK) return rc;
-            h->pcm_src = (const float*)h->pcm_in.p;
-            HIPCHK(h, hipMemcpyAsync(h->pcm_in.p, io.pcm_host, (size_t)n * n_ch * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        }
-        if (io.planes_host) {   // the first wav edge (round 6: any frame geometry): int16 planes up, scaled by 2^-15 on the way to channel-major
-            for (int c = 0; c < n_ch; ++c) {
-                HIPCHK(h, hipMemcpyAsync((int16_t*)h->in16.p + (size_t)c * n, io.planes_host[c], (size_t)n * sizeof(int16_t), hipMemcpyHostToDevice, h->stream));
-                launch_pcm_peak_i16(planes_dev + (size_t)c * n, peak_len(h, 0, n), h->peak_dev, h->stream);
-            }
-            if (pl.stft_frames < TL)   // short input: zero-padded frames (css.py:159-164)
-                HIPCHK(h, hipMemsetAsync(h->X.p, 0, (size_t)h->n_ch * X_ROWS_PER_BIN * F * h->T_ld * sizeof(float), h->stream));
-            if ((rc = stft_frames(h, 0, TL, planes_dev, h->stream)) != CSS_OK) return rc;
-            hipEventRecord(h->ev[2], h->stream);
-            h->stft_done = true;
-        } else {
-            launch_pcm_peak_f32(h->pcm_src, peak_len(h, 0, n) * n_ch, h->peak_dev, h->stream);
-            if ((rc = css_stage_stft(h)) != CSS_OK) return rc;
-        }
-        if ((rc = css_stage_masknet(h, 0, nseg)) != CSS_OK) return rc;
-        if ((rc = css_stage_mvdr(h, 0, nseg)) != CSS_OK) return rc;
-        if ((rc = css_stage_pit_costs(h, 0, nseg - 1)) != CSS_OK) return rc;
-        if ((rc = css_stage_pit_scan(h)) != CSS_OK) return rc;
-        if ((rc = css_stage_stitch(h, 0, TL)) != CSS_OK) return rc;
-        float* dst = io.wav_dev;
-        int64_t dst_ld = io.cap;
-        if (!dst) {
-            if ((rc = ensure(h, h->wav, (size_t)S * pl.n_out * sizeof(float))) != CSS_OK) return rc;
-            dst = (float*)h->wav.p; dst_ld = pl.n_out;
-        }
-        if ((rc = istft_impl(h, 0, TL, 0, TL - 1 + h->ovl, dst, dst_ld, 0, h->stream)) != CSS_OK) return rc;
-        if (io.wav16_host) {    // the second wav edge: peak normalisation + PCM16 encoding on the device (utils/audio_utils.py:37-49)
-            const int64_t n_out = pl.n_out;
-            unsigned int* pk = (unsigned int*)h->enc.p;
-            int16_t* o16 = (int16_t*)((char*)h->enc.p + 64);
-            { CSS_PROF(CSS_PROF_ENCODE, h->stream); launch_encode_pcm16(dst, S, n_out, pk, o16, n_out, h->stream); }
-            HIPCHK(h, hipMemcpy2DAsync(io.wav16_host, (size_t)io.cap * sizeof(int16_t), o16, (size_t)n_out * sizeof(int16_t),
-                                       (size_t)n_out * sizeof(int16_t), S, hipMemcpyDeviceToHost, h->stream));
-            if (io.peaks_host) HIPCHK(h, hipMemcpyAsync(io.peaks_host, pk, (size_t)S * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-        }
-        if (io.wav_host)
-            for (int sp = 0; sp < S; ++sp)
-                HIPCHK(h, hipMemcpyAsync(io.wav_host + (size_t)sp * io.cap, dst + (size_t)sp * dst_ld, (size_t)pl.n_out * sizeof(float),
-                                         hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(h->range_flag_host, h->range_flag_dev, sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
-        hipEventRecord(h->ev[7], h->stream);
-        const auto host_t1 = std::chrono::steady_clock::now();
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        HIPCHK(h, hipGetLastError());
-        const auto host_t2 = std::chrono::steady_clock::now();
-        return finish_timings(h, host_t0, host_t1, host_t2, true);
-    }
-    if (io.pcm_dev && io.wav_dev && !h->tune[CSS_TUNE_PIPELINE_DEVICE]) {
-        launch_pcm_peak_f32(h->pcm_src, peak_len(h, 0, n) * n_ch, h->peak_dev, h->stream);
-        if ((rc = css_stage_stft(h)) != CSS_OK) return rc;
-        if ((rc = css_stage_masknet(h, 0, nseg)) != CSS_OK) return rc;
-        if ((rc = css_stage_mvdr(h, 0, nseg)) != CSS_OK) return rc;
-        if ((rc = css_stage_pit_costs(h, 0, nseg - 1)) != CSS_OK) return rc;
-        if ((rc = css_stage_pit_scan(h)) != CSS_OK) return rc;
-        if ((rc = css_stage_stitch(h, 0, TL)) != CSS_OK) return rc;
-        if ((rc = istft_impl(h, 0, TL, 0, TL + 1, io.wav_dev, io.cap, 0, h->stream)) != CSS_OK) return rc;
-        HIPCHK(h, hipMemcpyAsync(h->range_flag_host, h->range_flag_dev, sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
-        hipEventRecord(h->ev[7], h->stream);
-        const auto host_t1 = std::chrono::steady_clock::now();
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        HIPCHK(h, hipGetLastError());
-        const auto host_t2 = std::chrono::steady_clock::now();
-        return finish_timings(h, host_t0, host_t1, host_t2, true);
-    }
-
-    // ---- units, their frames and samples
-    struct Unit { int64_t seg_lo; int n; int64_t f_lo, f_hi, s_lo, s_hi; hipEvent_t up, x, v, m; };   // pieces landed, planes, beamformer, costs
+    const int64_t nseg = pl.num_segments, TL = pl.mix_frames, n = pl.n_samples;
+    const int N = h->d.frame_len, fhop = h->d.frame_hop, T = h->cfg.segment_frames, hop = h->cfg.hop_frames;
     std::vector<Unit> units;
-    const int64_t cap = batch_len(nseg, std::min<int64_t>(batch_cap(h, h->cfg.segment_frames), nseg));
     int64_t f_prev = 0, s_prev = 0;
     for (int64_t s0 = 0; s0 < nseg; s0 += cap) {
         const int nb = (int)std::min<int64_t>(cap, nseg - s0);
@@ -242,12 +242,113 @@ int run_once(css_handle_t h, int64_t n, int32_t n_ch, const CssRunCfg* cfg, cons
             u.s_lo = s_prev;
             u.s_hi = last ? n : std::max<int64_t>(s_prev, std::min<int64_t>(fr > 0 ? (fr - 1) * fhop + N : 0, n));
             f_prev = u.f_hi; s_prev = u.s_hi;
-            u.up = from_host ? pool_event(h) : nullptr;
-            u.x = pool_event(h);
-            u.v = pool_event(h);
-            u.m = pool_event(h);
             units.push_back(u);
         }
+    }
+    return units;
+}
+
+// The tails of a pass, batch by batch in order (all earlier tails are already enqueued on the tail stream).
+// (one tail per BATCH, not per unit: these kernels are latency-bound chains of small launches -- a third of the
+// frames takes the same ~120 us -- and the lanes of a batch finish together, so per-unit tails only queue up)
+struct Tails {
+    css_ctx* h; const RunIo& io; const std::vector<Unit>& units;
+    // page-locked output: the overlap-add of the synthesis writes the samples straight into the caller's buffer over
+    // PCIe (no device-side copy of the waveforms, no copy call: the runtime's device-to-host copies made the host wait
+    // for the events they depend on); pageable output (nullptr): into the device buffer, then a copy
+    float* wav_mapped; bool piped;
+    int64_t t_done = 0, g_done = 0;     // frames overlap-added / gated and synthesised so far
+    hipEvent_t out_done = nullptr;      // the last samples have left on the copy stream
+
+    int samples_out(int64_t f_lo, int64_t g_hi, bool final_piece) {   // frames [g_done, g_hi) of the synthesis
+        hipStream_t ts = h->tail_stream, st = ts;
+        const int64_t TL = h->plan.mix_frames, n_out = h->plan.n_out, fhop = h->d.frame_hop;
+        const int64_t q_hi = (g_hi == TL) ? TL + 1 : g_hi;   // the last range also writes the tail half-frame
+        float* dst = (float*)h->wav.p;
+        int64_t dst_ld = n_out;
+        if (wav_mapped || io.wav_dev) { dst = wav_mapped ? wav_mapped : io.wav_dev; dst_ld = io.cap; }   // straight into the caller's buffer
+        const bool staged = io.wav_host && !wav_mapped;
+        if (wav_mapped && !piped) {
+            // the PCIe-bound overlap-add goes to the copy stream: the next piece's kernels run beside it
+            // (overlapping passes: the copy stream belongs to the NEXT pass's samples by now)
+            hipEvent_t done = pool_event(h);
+            HIPCHK(h, hipEventRecord(done, ts));
+            HIPCHK(h, hipStreamWaitEvent(h->copy_stream, done, 0));
+            st = h->copy_stream;
+        }
+        wave_ola_on(h, f_lo, g_hi, g_done, q_hi, dst, dst_ld, 0, st);
+        hipEventRecord(h->ev[6], st);
+        if (staged) {
+            const int64_t a = g_done * fhop, b = (g_hi == TL) ? n_out : g_hi * fhop;
+            hipEvent_t done = pool_event(h);
+            HIPCHK(h, hipEventRecord(done, ts));
+            HIPCHK(h, hipStreamWaitEvent(h->copy_stream, done, 0));
+            st = h->copy_stream;
+            if (int e = waveforms_out(h, dst, dst_ld, io.wav_host, io.cap, a, b, st)) return e;
+        }
+        if (final_piece && st == h->copy_stream) {
+            out_done = pool_event(h);
+            HIPCHK(h, hipEventRecord(out_done, st));
+        }
+        return CSS_OK;
+    }
+
+    int batch(size_t k0, size_t k1) {   // units [k0, k1)
+        hipStream_t ts = h->tail_stream;
+        const int64_t TL = h->plan.mix_frames, halo = h->cfg.dilation_frames + h->cfg.erosion_frames;
+        const StitchArgs sa = stitch_args(h);
+        const bool last = k1 == units.size();
+        for (size_t k = k0; k < k1; ++k) HIPCHK(h, hipStreamWaitEvent(ts, units[k].m, 0));
+        const int64_t seg_lo = units[k0].seg_lo, seg_hi = units[k1 - 1].seg_lo + units[k1 - 1].n;
+        const int64_t b_lo = std::max<int64_t>(seg_lo - 1, 0), b_hi = seg_hi - 1;
+        if (!h->tune[CSS_TUNE_MVDR_ON_LANES]) {   // beamformer and costs here, after the lanes, instead of on them
+            if (int e = mvdr_on(h, seg_lo, seg_hi, ts)) return e;
+            pit_costs_on(h, b_lo, b_hi, ts);
+        }
+        // (the boundaries' costs were computed on the lanes, behind each unit's beamformer)
+        pit_scan_on(h, b_lo, b_hi, ts);
+        const int64_t t_hi = last ? TL : std::min<int64_t>(seg_hi * h->cfg.hop_frames, TL);   // no later segment covers these
+        if (t_hi > t_done) { CSS_PROF(CSS_PROF_OLA_MASKS, ts); launch_ola_masks(sa, t_done, t_hi, ts); }
+        t_done = std::max(t_done, t_hi);
+        const int64_t g_end = last ? TL : std::max<int64_t>(t_done - halo, g_done);
+        if (g_end <= g_done && !last) return CSS_OK;
+        { CSS_PROF(CSS_PROF_GATE, ts); launch_morphology(sa, g_done, g_end, ts); }
+        // the last range may leave in CSS_TUNE_TAIL_PIECES pieces (default 1), the first piece's download beside the
+        // second's synthesis: measured no gain -- these launches are latency-bound, a fifth of the frames costs what all cost
+        const int pieces = (last && io.wav_host && g_end - g_done >= 512) ? std::max(h->tune[CSS_TUNE_TAIL_PIECES], 1) : 1;
+        const int64_t g_first = g_done;
+        for (int pc = 0; pc < pieces; ++pc) {
+            // (two pieces: 3/5 + 2/5, the second download is the exposed one; more: equal parts)
+            const int64_t g_hi = pc + 1 == pieces ? g_end
+                                 : (pieces == 2 ? g_first + (g_end - g_first) * 3 / 5 : g_first + (g_end - g_first) * (pc + 1) / pieces);
+            { CSS_PROF(CSS_PROF_OLA_STFT, ts); launch_ola_stft(sa, g_done, g_hi, ts); }
+            if (last && pc + 1 == pieces) hipEventRecord(h->ev[5], ts);
+            const int64_t f_lo = std::max<int64_t>(g_done - 1, 0);
+            istft_gemm_on(h, f_lo, g_hi, ts);
+            if (int e = samples_out(f_lo, g_hi, last && pc + 1 == pieces)) return e;
+            g_done = g_hi;
+        }
+        return CSS_OK;
+    }
+};
+}  // namespace
+
+static int run_pipeline(css_ctx* h, int64_t n, int32_t n_ch, const RunIo& io, bool piped, float* wav_mapped, HostClock t0) {
+    int rc;
+    const CssPlan& pl = h->plan;
+    const int64_t nseg = pl.num_segments;
+    const int T = h->cfg.segment_frames, hop = h->cfg.hop_frames;
+    const int par = piped ? (int)(h->pass_no & 1) : 0;
+    const bool from_host = io.pcm_host || io.planes_host;
+    int16_t* planes_dev = io.planes_host ? (int16_t*)h->in16.p : nullptr;
+    // ---- units, their frames and samples
+    const int64_t cap = batch_len(nseg, std::min<int64_t>(batch_cap(h, T), nseg));
+    std::vector<Unit> units = plan_units(h, cap);
+    for (Unit& u : units) {
+        u.up = from_host ? pool_event(h) : nullptr;
+        u.x = pool_event(h);
+        u.v = pool_event(h);
+        u.m = pool_event(h);
     }
     // ---- everything starts after whatever the previous pass left on the three streams
     if (!piped) {
@@ -255,26 +356,8 @@ int run_once(css_handle_t h, int64_t n, int32_t n_ch, const CssRunCfg* cfg, cons
         HIPCHK(h, hipEventRecord(start, h->stream));
         HIPCHK(h, hipStreamWaitEvent(h->copy_stream, start, 0));
         HIPCHK(h, hipStreamWaitEvent(h->tail_stream, start, 0));
-    } else {
-        // the samples go into the buffer the pass before last used: free once that pass has transformed its frames; the
-        // level word of this parity is cleared here, in front of the pieces' peak scans (each stream is in order in itself)
-        for (int b = 0; b < 2; ++b) {
-            if (!h->pcm_free[b]) HIPCHK(h, hipEventCreateWithFlags(&h->pcm_free[b], hipEventDisableTiming));
-            if (!h->level_free[b]) HIPCHK(h, hipEventCreateWithFlags(&h->level_free[b], hipEventDisableTiming));
-        }
-        if (!h->tail_end) HIPCHK(h, hipEventCreateWithFlags(&h->tail_end, hipEventDisableTiming));
-        for (auto& e : h->pass_end)
-            if (!e) HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        // back-pressure: the host stays at most CSS_QUEUE_LEAD passes ahead of the device.  It enqueues a pass in 2 ms, the
-        // device runs one in 5; an unbounded lead only makes the runtime grow its command and signal pools (measured:
-        // 3.4 instead of 2.1 ms of enqueue time per pass while they grow, 5.7 instead of 5.4 ms per pass) and buys nothing.
-        if (h->pass_no >= CSS_QUEUE_LEAD) HIPCHK(h, hipEventSynchronize(h->pass_end[(h->pass_no - CSS_QUEUE_LEAD) & 3]));
-        if (h->pass_no >= 2) {
-            HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->pcm_free[par], 0));
-            // ... and the level word when that pass's TAIL has read it (the host may be several passes ahead of the device)
-            HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->level_free[par], 0));
-        }
-        HIPCHK(h, hipMemsetAsync(h->peak_dev, 0, sizeof(unsigned int), h->copy_stream));
+    } else if ((rc = open_overlapping_pass(h, par, h->peak_dev, 1, false)) != CSS_OK) {
+        return rc;
     }
     // ---- PCIe pieces, in unit order, on the copy stream
     if (from_host) {
@@ -283,15 +366,13 @@ int run_once(css_handle_t h, int64_t n, int32_t n_ch, const CssRunCfg* cfg, cons
                 if ((rc = upload_pcm(h, io.pcm_host, u.s_lo, u.s_hi, h->copy_stream)) != CSS_OK) return rc;
             } else if (u.s_hi > u.s_lo) {
                 for (int c = 0; c < n_ch; ++c)
-                    HIPCHK(h, hipMemcpyAsync((int16_t*)h->in16.p + (size_t)c * n + u.s_lo, io.planes_host[c] + u.s_lo,
-                                             (size_t)(u.s_hi - u.s_lo) * sizeof(int16_t), hipMemcpyHostToDevice, h->copy_stream));
+                    if ((rc = plane_up(h, io.planes_host, planes_dev, n, c, u.s_lo, u.s_hi, h->copy_stream)) != CSS_OK) return rc;
             }
             HIPCHK(h, hipEventRecord(u.up, h->copy_stream));
             // the recording's level (power-of-two gain of the split synthesis operand) piece by piece, beside the next upload
             if (io.pcm_host) launch_pcm_peak_f32(h->pcm_src + u.s_lo * n_ch, peak_len(h, u.s_lo, u.s_hi) * n_ch, h->peak_dev, h->copy_stream);
             else
-                for (int c = 0; c < n_ch; ++c)
-                    launch_pcm_peak_i16(planes_dev + (size_t)c * n + u.s_lo, peak_len(h, u.s_lo, u.s_hi), h->peak_dev, h->copy_stream);
+                for (int c = 0; c < n_ch; ++c) plane_peak(h, planes_dev, n, c, u.s_lo, u.s_hi, h->copy_stream);
         }
         hipEvent_t level = pool_event(h);
         HIPCHK(h, hipEventRecord(level, h->copy_stream));
@@ -299,93 +380,12 @@ int run_once(css_handle_t h, int64_t n, int32_t n_ch, const CssRunCfg* cfg, cons
     } else {
         launch_pcm_peak_f32(h->pcm_src, peak_len(h, 0, n) * n_ch, h->peak_dev, h->tail_stream);
     }
-    if (pl.stft_frames < TL)   // short input: zero-padded frames (css.py:159-164)
-        HIPCHK(h, hipMemsetAsync(h->X.p, 0, (size_t)h->n_ch * X_ROWS_PER_BIN * F * h->T_ld * sizeof(float), h->stream));
-
-    // ---- the tail of unit `k` (all earlier tails are already enqueued on the tail stream)
-    const int64_t halo = h->cfg.dilation_frames + h->cfg.erosion_frames;
-    const StitchArgs sa = stitch_args(h);
-    int64_t t_done = 0, g_done = 0;     // frames overlap-added / gated and synthesised so far
-    hipEvent_t out_done = nullptr;
-    // page-locked output: the overlap-add of the synthesis writes the samples straight into the caller's buffer over
-    // PCIe (no device-side copy of the waveforms, no copy call: the runtime's device-to-host copies made the host wait
-    // for the events they depend on); pageable output: into the device buffer, then a copy
-    if (!piped && !h->tune[CSS_TUNE_OUT_MAPPED]) wav_mapped = nullptr;
-    // (one tail per BATCH, not per unit: these kernels are latency-bound chains of small launches -- a third of the
-    // frames takes the same ~120 us -- and the lanes of a batch finish together, so per-unit tails only queue up)
-    auto tail_of = [&](size_t k0, size_t k1) -> int {   // units [k0, k1)
-        hipStream_t ts = h->tail_stream;
-        const bool last = k1 == units.size();
-        for (size_t k = k0; k < k1; ++k) HIPCHK(h, hipStreamWaitEvent(ts, units[k].m, 0));
-        struct { int64_t seg_lo; int64_t n; } u{units[k0].seg_lo, units[k1 - 1].seg_lo + units[k1 - 1].n - units[k0].seg_lo};
-        const int64_t b_lo = std::max<int64_t>(u.seg_lo - 1, 0), b_hi = u.seg_lo + u.n - 1;
-        if (!h->tune[CSS_TUNE_MVDR_ON_LANES]) {   // beamformer and costs here, after the lanes, instead of on them
-            if (int e = mvdr_on(h, u.seg_lo, u.seg_lo + u.n, ts)) return e;
-            pit_costs_on(h, b_lo, b_hi, ts);
-        }
-        // (the boundaries' costs were computed on the lanes, behind each unit's beamformer)
-        pit_scan_on(h, b_lo, b_hi, ts);
-        const int64_t t_hi = last ? TL : std::min<int64_t>((u.seg_lo + u.n) * hop, TL);   // no later segment covers these
-        if (t_hi > t_done) { CSS_PROF(CSS_PROF_OLA_MASKS, ts); launch_ola_masks(sa, t_done, t_hi, ts); }
-        t_done = std::max(t_done, t_hi);
-        const int64_t g_end = last ? TL : std::max<int64_t>(t_done - halo, g_done);
-        if (g_end > g_done || last) {
-            { CSS_PROF(CSS_PROF_GATE, ts); launch_morphology(sa, g_done, g_end, ts); }
-            // the last range may leave in CSS_TUNE_TAIL_PIECES pieces (default 1), the first piece's download beside the
-            // second's synthesis: measured no gain -- these launches are latency-bound, a fifth of the frames costs what all cost
-            const int pieces = (last && io.wav_host && g_end - g_done >= 512) ? std::max(h->tune[CSS_TUNE_TAIL_PIECES], 1) : 1;
-            const int64_t g_first = g_done;
-            for (int pc = 0; pc < pieces; ++pc) {
-                // (two pieces: 3/5 + 2/5, the second download is the exposed one; more: equal parts)
-                const int64_t g_hi = pc + 1 == pieces ? g_end
-                                     : (pieces == 2 ? g_first + (g_end - g_first) * 3 / 5 : g_first + (g_end - g_first) * (pc + 1) / pieces);
-                { CSS_PROF(CSS_PROF_OLA_STFT, ts); launch_ola_stft(sa, g_done, g_hi, ts); }
-                if (last && pc + 1 == pieces) hipEventRecord(h->ev[5], ts);
-                const int64_t q_hi = (g_hi == TL) ? TL + 1 : g_hi;   // the last range also writes the tail half-frame
-                const int64_t f_lo = std::max<int64_t>(g_done - 1, 0);
-                istft_gemm_on(h, f_lo, g_hi, ts);
-                if (wav_mapped && piped) {   // (the copy stream belongs to the NEXT pass's samples by now)
-                    wave_ola_on(h, f_lo, g_hi, g_done, q_hi, wav_mapped, io.cap, 0, ts);
-                    hipEventRecord(h->ev[6], ts);
-                } else if (wav_mapped) {   // the PCIe-bound overlap-add goes to the copy stream: the next piece's kernels run beside it
-                    hipEvent_t done = pool_event(h);
-                    HIPCHK(h, hipEventRecord(done, ts));
-                    HIPCHK(h, hipStreamWaitEvent(h->copy_stream, done, 0));
-                    wave_ola_on(h, f_lo, g_hi, g_done, q_hi, wav_mapped, io.cap, 0, h->copy_stream);
-                    hipEventRecord(h->ev[6], h->copy_stream);
-                    if (last && pc + 1 == pieces) {
-                        out_done = pool_event(h);
-                        HIPCHK(h, hipEventRecord(out_done, h->copy_stream));
-                    }
-                } else if (io.wav_dev) {   // device-resident output: straight into the caller's buffer
-                    wave_ola_on(h, f_lo, g_hi, g_done, q_hi, io.wav_dev, io.cap, 0, ts);
-                    hipEventRecord(h->ev[6], ts);
-                } else {
-                    wave_ola_on(h, f_lo, g_hi, g_done, q_hi, (float*)h->wav.p, pl.n_out, 0, ts);
-                    hipEventRecord(h->ev[6], ts);
-                }
-                if (io.wav_host && !wav_mapped) {
-                    const int64_t a = g_done * fhop, b = (g_hi == TL) ? pl.n_out : g_hi * fhop;
-                    hipEvent_t done = pool_event(h);
-                    HIPCHK(h, hipEventRecord(done, ts));
-                    HIPCHK(h, hipStreamWaitEvent(h->copy_stream, done, 0));
-                    for (int sp = 0; sp < S; ++sp)
-                        HIPCHK(h, hipMemcpyAsync(io.wav_host + (size_t)sp * io.cap + a, (const float*)h->wav.p + (size_t)sp * pl.n_out + a,
-                                                 (size_t)(b - a) * sizeof(float), hipMemcpyDeviceToHost, h->copy_stream));
-                    if (last && pc + 1 == pieces) {
-                        out_done = pool_event(h);
-                        HIPCHK(h, hipEventRecord(out_done, h->copy_stream));
-                    }
-                }
-                g_done = g_hi;
-            }
-        }
-        return CSS_OK;
-    };
+    if ((rc = zero_short_planes(h, h->stream)) != CSS_OK) return rc;
 
     // ---- the estimator, unit by unit; each lane appends the beamformer of its own segments
+    Tails tails{h, io, units, wav_mapped, piped};
     MaskIo mio{(const float*)h->X.p, h->T_ld, pl.stft_frames, hop, T, h->masks_v, h->mask_ld_v};
-    mio.PH = (const float*)h->X.p + (int64_t)h->n_ch * 2 * F * h->T_ld;   // (every frame a segment reads was transformed in this pass)
+    mio.PH = (const float*)h->X.p + (int64_t)h->n_ch * 2 * h->d.num_bins * h->T_ld;   // (every frame a segment reads was transformed in this pass)
     size_t ui = 0;
     const LanePrep prep = [&](int64_t seg_lo, int cnt, hipStream_t st) -> int {
         Unit& u = units[ui];
@@ -424,55 +424,89 @@ int run_once(css_handle_t h, int64_t n, int32_t n_ch, const CssRunCfg* cfg, cons
                                 (piped && h->tail_pending && s0 == 0) ? h->tail_end : nullptr)) != CSS_OK) return rc;
         if (h->tune[CSS_TUNE_TAIL_PER_UNIT]) {
             for (size_t k = first; k < ui; ++k)
-                if ((rc = tail_of(k, k + 1)) != CSS_OK) return rc;
-        } else if ((rc = tail_of(first, ui)) != CSS_OK) {
+                if ((rc = tails.batch(k, k + 1)) != CSS_OK) return rc;
+        } else if ((rc = tails.batch(first, ui)) != CSS_OK) {
             return rc;
         }
     }
     h->stft_done = h->perms_done = true;
     hipEventRecord(h->ev[3], h->stream);
     hipEventRecord(h->ev[4], h->stream);
-    if (piped) {   // no join: the next queued pass's estimator runs beside this pass's tail; css_wait waits for all streams
+    if (piped) {
         HIPCHK(h, hipEventRecord(h->pcm_free[par], h->stream));
-        HIPCHK(h, hipEventRecord(h->tail_end, h->tail_stream));
-        HIPCHK(h, hipEventRecord(h->level_free[par], h->tail_stream));
-        HIPCHK(h, hipEventRecord(h->pass_end[h->pass_no & 3], h->tail_stream));
-        hipEventRecord(h->ev[7], h->tail_stream);
+        if ((rc = close_overlapping_pass(h, par)) != CSS_OK) return rc;
         mark_session_done(h, h->tail_stream);
-        h->tail_pending = true;
-        h->pass_no += 1;
-        h->queued += 1;
-        HIPCHK(h, hipGetLastError());
         return CSS_OK;
     }
     // ---- join: the main stream continues after the tail (and the last download)
     hipEvent_t tail_done = pool_event(h);
     HIPCHK(h, hipEventRecord(tail_done, h->tail_stream));
     HIPCHK(h, hipStreamWaitEvent(h->stream, tail_done, 0));
-    if (io.wav16_host) {
-        const int64_t n_out = pl.n_out;
-        unsigned int* pk = (unsigned int*)h->enc.p;
-        int16_t* o16 = (int16_t*)((char*)h->enc.p + 64);
-        { CSS_PROF(CSS_PROF_ENCODE, h->stream); launch_encode_pcm16((const float*)h->wav.p, S, n_out, pk, o16, n_out, h->stream); }
-        HIPCHK(h, hipMemcpy2DAsync(io.wav16_host, (size_t)io.cap * sizeof(int16_t), o16, (size_t)n_out * sizeof(int16_t),
-                                   (size_t)n_out * sizeof(int16_t), S, hipMemcpyDeviceToHost, h->stream));
-        if (io.peaks_host) HIPCHK(h, hipMemcpyAsync(io.peaks_host, pk, (size_t)S * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    }
+    if (io.wav16_host && (rc = encode_pcm16_out(h, (const float*)h->wav.p, io.wav16_host, io.cap, io.peaks_host, h->stream)) != CSS_OK) return rc;
     // range check (split_f16.hpp): a split GEMM whose operand left the format's range raised this word
     HIPCHK(h, hipMemcpyAsync(h->range_flag_host, h->range_flag_dev, sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
-    if (out_done) HIPCHK(h, hipStreamWaitEvent(h->stream, out_done, 0));
+    if (tails.out_done) HIPCHK(h, hipStreamWaitEvent(h->stream, tails.out_done, 0));
     hipEventRecord(h->ev[7], h->stream);
-    const auto host_t1 = std::chrono::steady_clock::now();
     if (io.enqueue_only) {   // css_wait synchronises, reads the range word and the timings of the last queued pass
         mark_session_done(h, h->stream);
         h->queued += 1;
         HIPCHK(h, hipGetLastError());
         return CSS_OK;
     }
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipGetLastError());
-    const auto host_t2 = std::chrono::steady_clock::now();
-    return finish_timings(h, host_t0, host_t1, host_t2, false);
+    return sync_and_time(h, t0, false);
+}
+
+int run_once(css_handle_t h, int64_t n, int32_t n_ch, const CssRunCfg* cfg, const RunIo& io) {
+    int rc;
+    if (!h) return CSS_ERR_INVALID_ARG;
+    const auto host_t0 = std::chrono::steady_clock::now();
+    // page-locked output (css_host_alloc): its device address, for the zero-copy output path
+    float* wav_mapped = nullptr;
+    if (io.wav_host && (h->tune[CSS_TUNE_OUT_MAPPED] || io.enqueue_only)) {
+        if (h->mapped_key != io.wav_host) { h->mapped_key = io.wav_host; h->mapped_val = mapped_host(io.wav_host); }
+        wav_mapped = (float*)h->mapped_val;
+    }
+    // queued passes OVERLAP when the output is page-locked (see css_ctx::pass_no); otherwise they just queue up
+    // (with the beamformer on the tail stream -- CSS_TUNE_MVDR_ON_LANES = 0 -- a tail also reads the spectra X, which the
+    // next pass's transform overwrites: such passes queue up without overlapping)
+    const bool piped = h->fft512 && io.enqueue_only && io.pcm_host && wav_mapped && h->tune[CSS_TUNE_MVDR_ON_LANES];
+    if (!piped && !h->tune[CSS_TUNE_OUT_MAPPED]) wav_mapped = nullptr;
+    if (io.enqueue_only && h->queued && h->last_piped != (int)piped) {
+        // the overlap mode changes inside a queue (a page-locked output follows a pageable one or the reverse): the two
+        // modes order the level word, the mask buffers and the tail differently, so the queue is drained on the device
+        // first (its bookkeeping -- css_wait, the range verdict -- stays with the caller)
+        HIPCHK(h, hipSetDevice(h->device));
+        if ((rc = drain_streams(h)) != CSS_OK) return rc;
+    }
+    if (io.enqueue_only) h->last_piped = (int)piped;
+    const int par = piped ? (int)(h->pass_no & 1) : 0;
+    h->peak_dev = (unsigned int*)h->level.p + 8 * par;
+    h->piped_now = piped;
+    // (overlapping passes alternate between the two sets of planes: a grouped pass in front of this one may still read
+    // its own on the tail stream -- run_group -- while this pass's transform writes)
+    if (piped) std::swap(h->X, h->X_alt);
+    rc = begin_impl(h, n, n_ch, cfg);
+    h->piped_now = false;
+    if (rc != CSS_OK) return rc;
+    const CssPlan& pl = h->plan;
+    if (io.cap < pl.n_out) return fail(h, CSS_ERR_INVALID_ARG, "output buffer too small: need " + std::to_string(pl.n_out) + " samples per stream");
+    h->ev_pool_used = 0;
+    if (io.pcm_host) {
+        const size_t need = ((size_t)n * n_ch * sizeof(float) + 255) / 256 * 256;
+        if ((rc = ensure(h, h->pcm_in, piped ? 2 * need : need)) != CSS_OK) return rc;
+        h->pcm_src = (const float*)pcm_half(h, par);
+    } else if (io.planes_host) {
+        if ((rc = ensure(h, h->in16, (size_t)n * n_ch * sizeof(int16_t))) != CSS_OK) return rc;
+        for (int c = 0; c < n_ch; ++c)
+            if (!io.planes_host[c]) return fail(h, CSS_ERR_INVALID_ARG, "null channel plane");
+    } else {
+        h->pcm_src = io.pcm_dev;
+    }
+    if (io.wav16_host && (rc = ensure(h, h->enc, (size_t)h->d.num_spks * pl.n_out * sizeof(int16_t) + 64)) != CSS_OK) return rc;
+    hipEventRecord(h->ev[1], h->stream);
+    hipEventRecord(h->ev[2], h->stream);   // the analysis transform is part of the lanes' chains (CssTimings.stft = 0)
+    if (!h->fft512 || (io.pcm_dev && io.wav_dev && !h->tune[CSS_TUNE_PIPELINE_DEVICE])) return run_plain(h, n, n_ch, io, host_t0);
+    return run_pipeline(h, n, n_ch, io, piped, wav_mapped, host_t0);
 }
 
 // Several queued sessions as ONE pass of the mask estimator (css_run_enqueue).  Segments are independent through the whole
@@ -498,21 +532,17 @@ struct Active {
 };
 }  // namespace
 
-int run_group(css_handle_t h, std::vector<css_ctx::Pending>& grp) {
+int run_group(css_handle_t h, const std::vector<css_ctx::QueuedSession>& grp) {
     const int G = (int)grp.size();
     const auto host_t0 = std::chrono::steady_clock::now();
     HIPCHK(h, hipSetDevice(h->device));
-    if (h->queued && h->last_piped != 1) {   // a non-overlapping pass is queued in front: drain it on the device (see run_once)
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->tail_stream));
-        HIPCHK(h, hipStreamSynchronize(h->copy_stream));
-        h->tail_pending = false;
-    }
+    int rc;
+    // a non-overlapping pass is queued in front: drain it on the device (see run_once)
+    if (h->queued && h->last_piped != 1 && (rc = drain_streams(h)) != CSS_OK) return rc;
     h->last_piped = 1;
     const int par = (int)(h->pass_no & 1);
     if ((int)h->slots.size() < G - 1) h->slots.resize((size_t)(G - 1));
     const int S = h->d.num_spks, F = h->d.num_bins;
-    int rc;
     // ---- the sessions: plans, buffers
     std::vector<int64_t> off((size_t)G), pcm_off((size_t)G);
     int64_t total = 0;
@@ -522,15 +552,16 @@ int run_group(css_handle_t h, std::vector<css_ctx::Pending>& grp) {
         std::swap(h->X, h->X_alt);   // (every grouped pass takes the planes the previous one did not)
         h->peak_dev = (unsigned int*)h->level.p + 8 * par + j;
         h->piped_now = true;
-        rc = begin_impl(h, grp[(size_t)j].n, grp[(size_t)j].n_ch, &grp[(size_t)j].cfg);
+        const css_ctx::QueuedSession& q = grp[(size_t)j];
+        const CssRunCfg own = q.own_cfg();
+        rc = begin_impl(h, q.n, q.n_ch, &own);
         h->piped_now = false;
         if (rc != CSS_OK) return rc;
         off[(size_t)j] = total;
         total += h->plan.num_segments;
         pcm_off[(size_t)j] = (int64_t)pcm_bytes;
-        const bool s16 = !grp[(size_t)j].planes.empty();
-        pcm_bytes += ((size_t)grp[(size_t)j].n * grp[(size_t)j].n_ch * (s16 ? sizeof(int16_t) : sizeof(float)) + 255) / 256 * 256;
-        if (grp[(size_t)j].wav16 && (rc = ensure(h, h->enc, (size_t)h->d.num_spks * h->plan.n_out * sizeof(int16_t) + 64)) != CSS_OK) return rc;
+        pcm_bytes += ((size_t)q.n * q.n_ch * (q.pcm16() ? sizeof(int16_t) : sizeof(float)) + 255) / 256 * 256;
+        if (q.wav16 && (rc = ensure(h, h->enc, (size_t)h->d.num_spks * h->plan.n_out * sizeof(int16_t) + 64)) != CSS_OK) return rc;
     }
     const int T = grp[0].cfg.segment_frames, hop = grp[0].cfg.hop_frames;
     // a shared batch runs on at most TWO lanes: measured equal to three (profiles/r04_queue_group_ab.md), and it leaves the
@@ -541,12 +572,12 @@ int run_group(css_handle_t h, std::vector<css_ctx::Pending>& grp) {
     if ((rc = ensure(h, h->pcm_in, 2 * pcm_bytes)) != CSS_OK) return rc;
     if ((rc = ensure(h, h->masks, (size_t)(S + 1) * F * total * T * sizeof(float))) != CSS_OK) return rc;
     if ((rc = ensure_activations(h, total, T)) != CSS_OK) return rc;
-    const char* pcm_base = (const char*)h->pcm_in.p + (par ? h->pcm_in.cap / 2 / 256 * 256 : 0);
+    const char* pcm_base = pcm_half(h, par);
     std::vector<GroupSess> gs((size_t)G);
     for (int j = 0; j < G; ++j) {
         Active act(h, j, G);
         h->pcm_src = (const float*)(pcm_base + pcm_off[(size_t)j]);
-        h->src16 = !grp[(size_t)j].planes.empty();
+        h->src16 = grp[(size_t)j].pcm16();
         h->masks_v = (float*)h->masks.p + off[(size_t)j] * T;
         h->mask_ld_v = total * T;
         gs[(size_t)j] = GroupSess{(const float*)h->X.p, h->T_ld, h->plan.stft_frames, off[(size_t)j], (int)h->plan.num_segments,
@@ -555,43 +586,20 @@ int run_group(css_handle_t h, std::vector<css_ctx::Pending>& grp) {
     h->ev_pool_used = 0;
     std::vector<hipEvent_t> planes((size_t)G), done((size_t)G);
     for (int j = 0; j < G; ++j) { planes[(size_t)j] = pool_event(h); done[(size_t)j] = pool_event(h); }
-    // ---- the overlap protocol of queued passes (run_once, `piped`)
-    for (int b = 0; b < 2; ++b) {
-        if (!h->pcm_free[b]) HIPCHK(h, hipEventCreateWithFlags(&h->pcm_free[b], hipEventDisableTiming));
-        if (!h->level_free[b]) HIPCHK(h, hipEventCreateWithFlags(&h->level_free[b], hipEventDisableTiming));
-    }
-    if (!h->tail_end) HIPCHK(h, hipEventCreateWithFlags(&h->tail_end, hipEventDisableTiming));
-    for (auto& e : h->pass_end)
-        if (!e) HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    if (h->pass_no >= CSS_QUEUE_LEAD) HIPCHK(h, hipEventSynchronize(h->pass_end[(h->pass_no - CSS_QUEUE_LEAD) & 3]));
-    if (!h->queued) {
-        // whatever the handle's stream holds from BEFORE the queue (weights, an earlier synchronous pass) comes first.  Only
-        // the first pass of a queue waits for it: a later pass's uploads are ordered by pcm_free / level_free / tail_end, and
-        // a wait on the main stream here would put them behind the previous pass's estimator instead of beside it
-        hipEvent_t opened = pool_event(h);
-        HIPCHK(h, hipEventRecord(opened, h->stream));
-        HIPCHK(h, hipStreamWaitEvent(h->copy_stream, opened, 0));
-    }
-    if (h->pass_no >= 2) {
-        // this parity's sample buffer, level words and planes were last used by the pass before last: its transforms are
-        // on this very stream; its beamformers (readers of the planes) and its tail (reader of the level words) ended with
-        // level_free
-        HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->pcm_free[par], 0));
-        HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->level_free[par], 0));
-    }
-    HIPCHK(h, hipMemsetAsync((unsigned int*)h->level.p + 8 * par, 0, 8 * sizeof(unsigned int), h->copy_stream));
+    // ---- the overlap protocol of queued passes (run_once, `piped`; here the transforms of the pass before last are on the
+    // copy stream itself, and its beamformers -- readers of the planes -- ended with level_free).
+    // Whatever the handle's stream holds from BEFORE the queue (weights, an earlier synchronous pass) comes first.  Only
+    // the first pass of a queue waits for it: a later pass's uploads are ordered by pcm_free / level_free / tail_end, and
+    // a wait on the main stream here would put them behind the previous pass's estimator instead of beside it
+    if ((rc = open_overlapping_pass(h, par, (unsigned int*)h->level.p + 8 * par, 8, !h->queued)) != CSS_OK) return rc;
     // ---- copy stream: every session's samples as one piece, its level scanned and its analysis transform behind it --
     // all of it beside the PREVIOUS pass's estimator (the host runs passes ahead), so that the main stream carries nothing
     // but estimators, back to back
     for (int j = 0; j < G; ++j) {
         Active act(h, j, G);
-        const css_ctx::Pending& q = grp[(size_t)j];
+        const css_ctx::QueuedSession& q = grp[(size_t)j];
         if (h->src16) {   // the session's mono PCM16 planes, half the PCIe bytes (css_run_enqueue_pcm16)
-            int16_t* dst16 = (int16_t*)const_cast<float*>(h->pcm_src);
-            for (int c = 0; c < q.n_ch; ++c) {
-                HIPCHK(h, hipMemcpyAsync(dst16 + (size_t)c * q.n, q.planes[(size_t)c], (size_t)q.n * sizeof(int16_t), hipMemcpyHostToDevice, h->copy_stream));
-                launch_pcm_peak_i16(dst16 + (size_t)c * q.n, peak_len(h, 0, q.n), h->peak_dev, h->copy_stream);
-            }
+            if ((rc = planes_up(h, q.planes.data(), (int16_t*)const_cast<float*>(h->pcm_src), q.n, q.n_ch, h->copy_stream)) != CSS_OK) return rc;
         } else {
             HIPCHK(h, hipMemcpyAsync(const_cast<float*>(h->pcm_src), q.pcm, (size_t)q.n * q.n_ch * sizeof(float), hipMemcpyHostToDevice,
                                      h->copy_stream));
@@ -601,8 +609,7 @@ int run_group(css_handle_t h, std::vector<css_ctx::Pending>& grp) {
             HIPCHK(h, hipEventRecord(planes[(size_t)j], h->copy_stream));
             continue;
         }
-        if (h->plan.stft_frames < h->plan.mix_frames)   // short input: zero-padded frames (css.py:159-164)
-            HIPCHK(h, hipMemsetAsync(h->X.p, 0, (size_t)h->n_ch * X_ROWS_PER_BIN * F * h->T_ld * sizeof(float), h->copy_stream));
+        if ((rc = zero_short_planes(h, h->copy_stream)) != CSS_OK) return rc;
         if ((rc = stft_frames(h, 0, h->plan.mix_frames, h->src16 ? (const int16_t*)h->pcm_src : nullptr, h->copy_stream)) != CSS_OK) return rc;
         h->stft_done = true;
         HIPCHK(h, hipEventRecord(planes[(size_t)j], h->copy_stream));
@@ -613,8 +620,7 @@ int run_group(css_handle_t h, std::vector<css_ctx::Pending>& grp) {
         HIPCHK(h, hipStreamWaitEvent(h->stream, planes[(size_t)j], 0));
         if (!xf_main) continue;
         Active act(h, j, G);
-        if (h->plan.stft_frames < h->plan.mix_frames)
-            HIPCHK(h, hipMemsetAsync(h->X.p, 0, (size_t)h->n_ch * X_ROWS_PER_BIN * F * h->T_ld * sizeof(float), h->stream));
+        if ((rc = zero_short_planes(h, h->stream)) != CSS_OK) return rc;
         if ((rc = stft_frames(h, 0, h->plan.mix_frames, h->src16 ? (const int16_t*)h->pcm_src : nullptr, h->stream)) != CSS_OK) return rc;
         h->stft_done = true;
     }
@@ -685,7 +691,7 @@ int run_group(css_handle_t h, std::vector<css_ctx::Pending>& grp) {
     }
     for (int j = 0; j < G; ++j) {
         Active act(h, j, G);
-        const css_ctx::Pending& q = grp[(size_t)j];
+        const css_ctx::QueuedSession& q = grp[(size_t)j];
         const int64_t nseg = h->plan.num_segments, TL = h->plan.mix_frames;
         if (mvdr_lanes) HIPCHK(h, hipStreamWaitEvent(ts, done[(size_t)j], 0));
         pit_scan_on(h, 0, nseg - 1, ts);
@@ -696,26 +702,18 @@ int run_group(css_handle_t h, std::vector<css_ctx::Pending>& grp) {
         if (j == G - 1) hipEventRecord(h->ev[5], ts);
         istft_gemm_on(h, 0, TL, ts);
         if (q.wav16) {
-            // the second wav edge on the device (utils/audio_utils.py:37-49 write_wav): peak normalisation and PCM16 encoding of
-            // the session's streams, then half the PCIe bytes back -- css_run_pcm16's arithmetic, launch for launch
+            // css_run_pcm16's arithmetic, launch for launch
             const int64_t n_out = h->plan.n_out;
             if ((rc = ensure(h, h->wav, (size_t)S * n_out * sizeof(float))) != CSS_OK) return rc;
             wave_ola_on(h, 0, TL, 0, TL + 1, (float*)h->wav.p, n_out, 0, ts);
-            unsigned int* pk = (unsigned int*)h->enc.p;
-            int16_t* o16 = (int16_t*)((char*)h->enc.p + 64);
-            { CSS_PROF(CSS_PROF_ENCODE, ts); launch_encode_pcm16((const float*)h->wav.p, S, n_out, pk, o16, n_out, ts); }
-            HIPCHK(h, hipMemcpy2DAsync(q.wav16, (size_t)q.cap * sizeof(int16_t), o16, (size_t)n_out * sizeof(int16_t),
-                                       (size_t)n_out * sizeof(int16_t), S, hipMemcpyDeviceToHost, ts));
-            if (q.peaks) HIPCHK(h, hipMemcpyAsync(q.peaks, pk, (size_t)S * sizeof(float), hipMemcpyDeviceToHost, ts));
+            if ((rc = encode_pcm16_out(h, (const float*)h->wav.p, q.wav16, q.cap, q.peaks, ts)) != CSS_OK) return rc;
         } else if (h->tune[CSS_TUNE_GROUP_OUT_DMA]) {
             // the PCIe leg as copies behind a 12 us kernel: written by the kernel itself the same samples keep 11 250
             // workgroups resident for 0.21 ms per session, beside the next pass's estimator (profiles/r04_queue_group_ab.md)
             const int64_t n_out = h->plan.n_out;
             if ((rc = ensure(h, h->wav, (size_t)S * n_out * sizeof(float))) != CSS_OK) return rc;
             wave_ola_on(h, 0, TL, 0, TL + 1, (float*)h->wav.p, n_out, 0, ts);
-            for (int sp = 0; sp < S; ++sp)
-                HIPCHK(h, hipMemcpyAsync(q.wav + (size_t)sp * q.cap, (const float*)h->wav.p + (size_t)sp * n_out,
-                                         (size_t)n_out * sizeof(float), hipMemcpyDeviceToHost, ts));
+            if ((rc = waveforms_out(h, (const float*)h->wav.p, n_out, q.wav, q.cap, 0, n_out, ts)) != CSS_OK) return rc;
         } else {
             wave_ola_on(h, 0, TL, 0, TL + 1, q.wav_mapped, q.cap, 0, ts);
         }
@@ -723,43 +721,33 @@ int run_group(css_handle_t h, std::vector<css_ctx::Pending>& grp) {
         h->perms_done = true;
     }
     hipEventRecord(h->ev[6], ts);
-    HIPCHK(h, hipEventRecord(h->tail_end, ts));
-    HIPCHK(h, hipEventRecord(h->level_free[par], ts));
-    HIPCHK(h, hipEventRecord(h->pass_end[h->pass_no & 3], ts));
-    hipEventRecord(h->ev[7], ts);
-    h->tail_pending = true;
-    h->pass_no += 1;
-    h->queued += 1;
-    HIPCHK(h, hipGetLastError());
+    if ((rc = close_overlapping_pass(h, par)) != CSS_OK) return rc;
     h->tim.host_enqueue = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - host_t0).count();
     return CSS_OK;
 }
 
 // the sessions css_run_enqueue has accepted and not yet put on the streams: one alone takes run_once's pipeline (its
-// lanes hide a single meeting's PCIe legs better), several take run_group
+// lanes hide a single meeting's PCIe legs better), several take run_group.  Started, they join the repeat log.
 int flush_pending(css_handle_t h) {
     if (h->pending.empty()) return CSS_OK;
-    std::vector<css_ctx::Pending> grp;
+    std::vector<css_ctx::QueuedSession> grp;
     grp.swap(h->pending);
     h->pending_segments = 0;
     int rc;
     if (grp.size() == 1) {
-        RunIo io; io.pcm_host = grp[0].pcm; io.wav_host = grp[0].wav; io.cap = grp[0].cap; io.enqueue_only = true;
-        if (!grp[0].planes.empty()) { io.planes_host = grp[0].planes.data(); io.wav16_host = grp[0].wav16; io.peaks_host = grp[0].peaks; }
-        rc = run_once(h, grp[0].n, grp[0].n_ch, &grp[0].cfg, io);
+        const CssRunCfg own = grp[0].own_cfg();
+        rc = run_once(h, grp[0].n, grp[0].n_ch, &own, grp[0].io(true));
     } else {
         rc = run_group(h, grp);
     }
     if (rc != CSS_OK) {
-        // sessions css_run_enqueue had accepted are dropped with this error: take them out of the repeat log (they are its
-        // last grp.size() entries -- nothing is logged between an acceptance and its flush) and name them
-        const size_t drop = std::min(grp.size(), h->queue_log.size());
-        const size_t first = h->queue_log.size() - drop;
-        h->queue_log.resize(first, css_ctx::QueuedPass(nullptr, 0, 0, CssRunCfg{}, nullptr, 0));
+        // sessions css_run_enqueue had accepted are dropped with this error: name them (they would have been the log's next)
+        const size_t first = h->queue_log.size();
         const std::string why = h->err;
-        return fail(h, rc, "queued session(s) " + std::to_string(first) + " .. " + std::to_string(first + drop - 1) +
+        return fail(h, rc, "queued session(s) " + std::to_string(first) + " .. " + std::to_string(first + grp.size() - 1) +
                                " (counted from the last css_wait) were accepted and could not be started; they are dropped: " + why);
     }
+    for (css_ctx::QueuedSession& q : grp) h->queue_log.push_back(std::move(q));
     return CSS_OK;
 }
 
@@ -787,8 +775,7 @@ int run_impl(css_handle_t h, int64_t n, int32_t n_ch, const CssRunCfg* cfg, cons
 int css_run(css_handle_t h, const float* pcm_host, int64_t n_samples, int32_t n_ch, const CssRunCfg* cfg, float* wav_host,
             int64_t cap) {
     if (!h || !pcm_host || !wav_host) return fail(h, CSS_ERR_INVALID_ARG, "null argument");
-    RunIo io; io.pcm_host = pcm_host; io.wav_host = wav_host; io.cap = cap;
-    return run_impl(h, n_samples, n_ch, cfg, io);
+    return run_impl(h, n_samples, n_ch, cfg, RunIo::host(pcm_host, nullptr, wav_host, nullptr, nullptr, cap));
 }
 
 // css_run_enqueue (float PCM -> float waveforms) and css_run_enqueue_pcm16 (PCM16 planes -> peak-normalised PCM16 streams): one
@@ -809,56 +796,30 @@ static int enqueue_impl(css_handle_t h, const float* pcm_host, const int16_t* co
     if (h->mapped_key != out_key) { h->mapped_key = out_key; h->mapped_val = mapped_host(out_key); }
     float* mapped = (float*)h->mapped_val;   // (PCM16 output: only WHETHER it is page-locked matters -- it leaves by DMA)
     const bool groupable = h->fft512 && h->group_limit > 1 && mapped && h->tune[CSS_TUNE_MVDR_ON_LANES] && pl.num_segments <= batch_cap(h, cfg->segment_frames);
-    auto log_entry = [&]() {
-        h->queue_log.emplace_back(pcm_host, n_samples, n_ch, *cfg, wav_host, cap);
-        if (planes) { css_ctx::QueuedPass& e = h->queue_log.back(); e.planes.assign(planes, planes + n_ch); e.wav16 = wav16; e.peaks = peaks; }
-    };
-    auto io_of = [&](bool enqueue_only) {
-        RunIo io; io.pcm_host = pcm_host; io.wav_host = wav_host; io.cap = cap; io.enqueue_only = enqueue_only;
-        if (planes) { io.planes_host = planes; io.wav16_host = wav16; io.peaks_host = peaks; }
-        return io;
-    };
+    css_ctx::QueuedSession q(pcm_host, planes, n_samples, n_ch, *cfg, wav_host, wav16, peaks, cap, mapped);
     if (!h->fft512) {
         // Frame sizes other than 512 / 256 run the plain stage sequence to its end inside the call (run_once): nothing stays
         // queued, so css_wait would never look at the range word.  The pass therefore takes css_run's own rule here -- queued
         // passes first, then this one, repeated in float32 or refused with CSS_ERR_RANGE when it left the split-f16 range.
-        rc = run_impl(h, n_samples, n_ch, cfg, io_of(false));
+        rc = run_impl(h, n_samples, n_ch, cfg, q.io(false));
         if (rc == CSS_OK) h->sess_done.push_back(nullptr);   // (finished inside the call)
         return rc;
     }
     if (!groupable) {
         if ((rc = flush_pending(h)) != CSS_OK) return rc;
-        rc = run_once(h, n_samples, n_ch, cfg, io_of(true));
-        if (rc == CSS_OK) log_entry();
+        rc = run_once(h, n_samples, n_ch, cfg, q.io(true));
+        if (rc == CSS_OK) h->queue_log.push_back(std::move(q));
         return rc;
     }
-    const int T = cfg->segment_frames;
-    if (!h->pending.empty()) {
-        const css_ctx::Pending& f = h->pending.front();
-        const bool same = f.cfg.segment_frames == T && f.cfg.hop_frames == cfg->hop_frames &&
-                          std::memcmp(f.w.data(), cfg->w_first, T * sizeof(float)) == 0 &&
-                          std::memcmp(f.w.data() + T, cfg->w_mid, T * sizeof(float)) == 0 &&
-                          std::memcmp(f.w.data() + 2 * T, cfg->w_last, T * sizeof(float)) == 0;
-        if (!same || h->pending_segments + pl.num_segments > batch_cap(h, T) || (int)h->pending.size() >= h->group_limit)
-            if ((rc = flush_pending(h)) != CSS_OK) return rc;
-    }
-    css_ctx::Pending q{pcm_host, n_samples, n_ch, *cfg, {}, wav_host, cap, mapped, pl.num_segments};
-    if (planes) { q.planes.assign(planes, planes + n_ch); q.wav16 = wav16; q.peaks = peaks; }
-    q.w.resize(3 * (size_t)T);
-    std::memcpy(q.w.data(), cfg->w_first, T * sizeof(float));
-    std::memcpy(q.w.data() + T, cfg->w_mid, T * sizeof(float));
-    std::memcpy(q.w.data() + 2 * T, cfg->w_last, T * sizeof(float));
+    const int64_t room = batch_cap(h, cfg->segment_frames);
+    if (!h->pending.empty() &&
+        (!q.groups_with(h->pending.front()) || h->pending_segments + pl.num_segments > room || (int)h->pending.size() >= h->group_limit))
+        if ((rc = flush_pending(h)) != CSS_OK) return rc;
     h->pending.push_back(std::move(q));
-    {   // (the vector may have moved: point the copies of the configuration at their own windows)
-        for (css_ctx::Pending& e : h->pending) {
-            e.cfg.w_first = e.w.data(); e.cfg.w_mid = e.w.data() + e.cfg.segment_frames; e.cfg.w_last = e.w.data() + 2 * e.cfg.segment_frames;
-        }
-    }
     h->pending_segments += pl.num_segments;
-    log_entry();
     // no session of this length would still fit, or the group is full: off it goes -- nothing waits for a css_wait that
     // could already run
-    if (h->pending_segments + pl.num_segments > batch_cap(h, cfg->segment_frames) || (int)h->pending.size() >= h->group_limit) return flush_pending(h);
+    if (h->pending_segments + pl.num_segments > room || (int)h->pending.size() >= h->group_limit) return flush_pending(h);
     return CSS_OK;
 }
 
@@ -890,22 +851,19 @@ int css_wait(css_handle_t h) {
     if (!h->queued) { h->queue_log.clear(); h->sess_done.clear(); h->sess_ev_used = 0; return CSS_OK; }
     HIPCHK(h, hipSetDevice(h->device));
     const auto t0 = std::chrono::steady_clock::now();
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->tail_stream));
-    HIPCHK(h, hipStreamSynchronize(h->copy_stream));
+    if (int rc = drain_streams(h)) return rc;
     HIPCHK(h, hipMemcpy(h->range_flag_host, h->range_flag_dev, sizeof(unsigned int), hipMemcpyDeviceToHost));
     HIPCHK(h, hipGetLastError());
     const auto t1 = std::chrono::steady_clock::now();
     h->queued = 0;
     h->sess_done.clear();
     h->sess_ev_used = 0;
-    h->tail_pending = false;
     h->last_piped = -1;
     h->pass_no = 0;
     h->peak_dev = (unsigned int*)h->level.p;
     finish_timings(h, t0, t0, t1, false);
     h->range_last = 0;
-    std::vector<css_ctx::QueuedPass> log;
+    std::vector<css_ctx::QueuedSession> log;
     log.swap(h->queue_log);
     if (*h->range_flag_host && h->split) {
         // the same rule as css_run: the queued passes accumulate into one range word, so every pass queued since the last
@@ -917,11 +875,8 @@ int css_wait(css_handle_t h) {
         int rc = css_set_linear_mode(h, CSS_LINEAR_EXACT_F32);
         size_t repeated = 0;
         for (; repeated < log.size() && rc == CSS_OK; ++repeated) {
-            const css_ctx::QueuedPass& q = log[repeated];
-            RunIo io; io.pcm_host = q.pcm; io.wav_host = q.wav; io.cap = q.cap;
-            if (!q.planes.empty()) { io.planes_host = q.planes.data(); io.wav16_host = q.wav16; io.peaks_host = q.peaks; }
-            const CssRunCfg own = q.own_cfg();
-            rc = run_once(h, q.n, q.n_ch, &own, io);
+            const CssRunCfg own = log[repeated].own_cfg();
+            rc = run_once(h, log[repeated].n, log[repeated].n_ch, &own, log[repeated].io(false));
         }
         const std::string why = h->err;
         const int rc2 = css_set_linear_mode(h, CSS_LINEAR_SPLIT_F16);
@@ -953,14 +908,12 @@ int css_wait_sessions(css_handle_t h, int64_t n) {
 int css_run_device(css_handle_t h, const float* pcm_dev, int64_t n_samples, int32_t n_ch, const CssRunCfg* cfg,
                    float* wav_dev, int64_t cap) {
     if (!h || !pcm_dev || !wav_dev) return fail(h, CSS_ERR_INVALID_ARG, "null argument");
-    RunIo io; io.pcm_dev = pcm_dev; io.wav_dev = wav_dev; io.cap = cap;
-    return run_impl(h, n_samples, n_ch, cfg, io);
+    return run_impl(h, n_samples, n_ch, cfg, RunIo::device(pcm_dev, wav_dev, cap));
 }
 
 int css_run_pcm16(css_handle_t h, const int16_t* const* planes_host, int64_t n_samples, int32_t n_ch, const CssRunCfg* cfg,
                   int16_t* wav_pcm16_host, int64_t cap, float* peaks_host) {
     if (!h || !planes_host || !wav_pcm16_host || n_samples < 1 || n_ch < 1) return fail(h, CSS_ERR_INVALID_ARG, "bad argument");
-    RunIo io; io.planes_host = planes_host; io.wav16_host = wav_pcm16_host; io.peaks_host = peaks_host; io.cap = cap;
-    return run_impl(h, n_samples, n_ch, cfg, io);
+    return run_impl(h, n_samples, n_ch, cfg, RunIo::host(nullptr, planes_host, nullptr, wav_pcm16_host, peaks_host, cap));
 }
 
