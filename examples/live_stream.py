@@ -2,7 +2,10 @@
 source would deliver it; every push returns the samples of the three separated streams that have become final (equal, bit
 for bit, to the offline result on the whole meeting).  Prints the lag and the time of each push.
 
-    python examples/live_stream.py [--seconds 30]
+With --rooms N, N synthetic meetings (different seeds) arrive tick by tick and are pushed through one CssStreamGroup: the
+segments the rooms complete in a tick share the mask estimator's batches (css_stream_push_many).
+
+    python examples/live_stream.py [--seconds 30] [--rooms N]
 """
 import argparse
 import os
@@ -20,13 +23,41 @@ import notsofar1_challenge_amd.synth as SYN        # noqa: E402
 import notsofar1_challenge_amd.weights as W        # noqa: E402
 
 
+def rooms(sep, n_rooms, seconds, fs, chunk):
+    mixes = [SYN.synth_meeting(seconds, 7, seed=1 + r)[0] for r in range(n_rooms)]
+    streams = [STR.CssStream(sep, CSS.CssCfg(), fs=fs, num_channels=7) for _ in mixes]
+    group = STR.CssStreamGroup(streams)
+    outs = [[[] for _ in range(sep.desc.num_spks)] for _ in mixes]
+    print(f"{n_rooms} rooms, lag bound {streams[0].latency_samples / fs:.2f} s")
+    for i in range(0, mixes[0].shape[0], chunk):
+        t = time.perf_counter()
+        res = group.push([m[i:i + chunk] for m in mixes])
+        ms = (time.perf_counter() - t) * 1e3
+        for room, got in zip(outs, res):
+            for k, o in enumerate(got):
+                room[k].append(o)
+        inf = streams[0].info()
+        print(f"t={inf.n_pushed / fs:6.1f} s  final={inf.n_emitted / fs:6.1f} s  tick {ms:6.2f} ms  "
+              f"estimator batches {group.stats.estimator_batches} ({group.stats.estimator_segments} segments)")
+    for s, room in zip(streams, outs):
+        for k, o in enumerate(s.finish()):
+            room[k].append(o)
+        s.close()
+    print("separated:", [[np.concatenate(x).shape[0] / fs for x in room] for room in outs], "s")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=30.0)
+    ap.add_argument("--rooms", type=int, default=1, help="meetings fed tick by tick through one CssStreamGroup")
     a = ap.parse_args()
     fs = 16000
     desc = W.ModelDesc.mc_v1()
     sep = SEP.HipSeparator(W.apply_golden_recipe(W.portable_state_dict(desc, 0)), None, device=0)
+    if a.rooms > 1:
+        rooms(sep, a.rooms, a.seconds, fs, fs // 2)
+        sep.close()
+        return
     mix = SYN.synth_meeting(a.seconds, 7, seed=1)[0]
     chunk = fs // 2
     streams = [[] for _ in range(desc.num_spks)]

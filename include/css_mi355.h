@@ -488,8 +488,11 @@ int css_istft_host(css_handle_t h, const float* y_planes, int32_t batch, int64_t
  * gives weight returns CSS_ERR_ZERO_WEIGHT and changes nothing: css_run fails css.py:297 on every recording that long.
  *   - device and host memory per stream depend on the segmentation, not on the stream's length; no frame, segment or sample is
  *     processed twice;
- *   - up to CSS_MAX_STREAMS streams per handle, independent of each other and of the handle's own session (css_run, css_begin ..
- *     between two pushes see and leave the same bits);
+ *   - up to CSS_MAX_STREAMS streams per handle (64: 12.4 GB of device memory with the default segmentation), independent of each
+ *     other and of the handle's own session (css_run, css_begin .. between two pushes see and leave the same bits);
+ *   - css_stream_push_many pushes into several streams of a handle in one call and runs the mask estimator over the segments
+ *     they complete in SHARED batches (live meetings deliver audio at the same pace, so their segments complete in the same
+ *     tick): the results are css_stream_push's, bit for bit; one call costs about one estimator pass instead of one per stream;
  *   - CSS_LINEAR_EXACT_F32 only (the split-f16 mode takes whole-session decisions): css_stream_open in CSS_LINEAR_SPLIT_F16 and
  *     css_set_linear_mode(h, CSS_LINEAR_SPLIT_F16) while a stream is open return CSS_ERR_STATE; so do css_set_analysis_window
  *     and css_set_feature_options (a stream's pushes read the handle's window and feature options);
@@ -497,7 +500,7 @@ int css_istft_host(css_handle_t h, const float* y_planes, int32_t batch, int64_t
  *   - CSS_ERR_STATE while css_run_enqueue* sessions are outstanding (not yet css_wait-ed).
  * Output: out_host [S][cap]; a push writes at most n_samples + max_lag samples per stream, finish css_plan(n_pushed).n_out -
  * n_emitted.  A capacity below what the call would return is CSS_ERR_INVALID_ARG and leaves the stream unchanged. */
-#define CSS_MAX_STREAMS 16
+#define CSS_MAX_STREAMS 64
 typedef struct CssStreamInfo {
     int64_t n_pushed, n_emitted;   /* samples per channel in, per separated stream out            */
     int64_t max_lag;               /* the lag bound above, for this stream's configuration        */
@@ -507,6 +510,28 @@ typedef struct CssStreamInfo {
 int css_stream_open(css_handle_t h, const CssRunCfg* cfg, int32_t n_ch, int32_t* stream_id);
 /* pcm_host [n_samples][n_ch] as css_run's */
 int css_stream_push(css_handle_t h, int32_t id, const float* pcm_host, int64_t n_samples, float* out_host, int64_t cap, int64_t* n_out);
+/* One call for many streams.  Every item's n_out and the samples in its out_host are exactly what css_stream_push(h, id, pcm_host,
+ * n_samples, out_host, cap, &n_out) gives, called item by item in array order.  All items are checked before anything is
+ * uploaded or any stream's state moves: the first failing item's status is returned (an id twice in one call is
+ * CSS_ERR_INVALID_ARG), css_last_error names its index and id, and every stream of the call is left as it was.
+ * Batching: a push is cut into pieces of 8 segments' worth of samples; round r of the call takes piece r of every item that
+ * still has one, and the segments the round completes in all streams that share (segment_frames, hop_frames) pass the mask
+ * estimator as ONE batch (cut to the handle's max_batch_segments like every batch).  Streams with another segmentation form
+ * their own batch in the same round.  `stats` (may be NULL) counts the batches and their segments.  A HIP error in the
+ * middle of a call leaves the streams of that call undefined, as a failed css_stream_push does. */
+typedef struct CssStreamPush {
+    int32_t id;                 /* an open, unfinished stream of this handle                     */
+    const float* pcm_host;      /* [n_samples][n_ch], as css_stream_push                          */
+    int64_t n_samples;          /* 0 is allowed                                                   */
+    float* out_host;            /* [S][cap]                                                       */
+    int64_t cap;
+    int64_t n_out;              /* out: samples per separated stream this call made final         */
+} CssStreamPush;
+typedef struct CssStreamGroupStats {
+    int32_t estimator_batches;  /* calls of the batched estimator pass this call made             */
+    int64_t estimator_segments; /* segments they held, all items together                         */
+} CssStreamGroupStats;
+int css_stream_push_many(css_handle_t h, CssStreamPush* items, int32_t n_items, CssStreamGroupStats* stats);
 int css_stream_finish(css_handle_t h, int32_t id, float* out_host, int64_t cap, int64_t* n_out);
 int css_stream_close(css_handle_t h, int32_t id);
 int css_stream_info(css_handle_t h, int32_t id, CssStreamInfo* out);

@@ -78,7 +78,16 @@ class CssStreamInfo(C.Structure):
                 ("finished", C.c_int32)]
 
 
-MAX_STREAMS = 16                                 # CSS_MAX_STREAMS
+MAX_STREAMS = 64                                 # CSS_MAX_STREAMS
+
+
+class CssStreamPush(C.Structure):
+    _fields_ = [("id", C.c_int32), ("pcm_host", C.c_void_p), ("n_samples", C.c_int64), ("out_host", C.c_void_p),
+                ("cap", C.c_int64), ("n_out", C.c_int64)]
+
+
+class CssStreamGroupStats(C.Structure):
+    _fields_ = [("estimator_batches", C.c_int32), ("estimator_segments", C.c_int64)]
 
 
 class CssKernelStat(C.Structure):
@@ -164,6 +173,7 @@ SIGNATURES = {
     "css_comm_all_gather": (C.c_int, [_P, _P, _P, C.c_int64]),
     "css_stream_open": (C.c_int, [_P, C.POINTER(CssRunCfg), C.c_int32, C.POINTER(C.c_int32)]),
     "css_stream_push": (C.c_int, [_P, C.c_int32, _P, C.c_int64, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "css_stream_push_many": (C.c_int, [_P, C.POINTER(CssStreamPush), C.c_int32, C.POINTER(CssStreamGroupStats)]),
     "css_stream_finish": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "css_stream_close": (C.c_int, [_P, C.c_int32]),
     "css_stream_info": (C.c_int, [_P, C.c_int32, C.POINTER(CssStreamInfo)]),

@@ -273,6 +273,8 @@ struct css_ctx : SessState {
     int32_t prof_pairs = 0;
     FeatOpts feat_opts{};   // css_set_feature_options (css_create: the shipped configuration)
     void* streams[CSS_MAX_STREAMS] = {};   // css_stream_open: open streams (api_stream.hip StreamState), by id
+    DevBuf stream_masks;   // api_stream.hip: the mask head's output for one estimator batch of streamed segments (never `masks`:
+                           // the handle's own session keeps its bits between two pushes)
 
     std::string err;
 };

@@ -13,6 +13,11 @@
 // over the segments the piece completed (one batch), covariances / MVDR / power normalisation, the stitching costs and the
 // permutation scan (continued from the last segment's permutation), then stream.hip's two stitching kernels and the
 // synthesis GEMM + overlap-add over the newly final frames.
+//
+// There is one push path: css_stream_push_many.  It takes piece r of every item in round r, and the segments a round completes
+// in all streams of one segmentation pass the estimator as ONE batch (every estimator kernel is batch invariant in exact
+// float32, as for queued sessions: api_queue.hip run_group), so N live meetings cost about one estimator pass per tick
+// instead of N.  css_stream_push is a group of one item; css_stream_finish runs the same segments() / tail() with one job.
 #include "api_ctx.hpp"
 
 #include <climits>
@@ -155,74 +160,147 @@ int rebase(css_ctx* h, StreamState* s) {
     return CSS_OK;
 }
 
-// Segments [g_lo, g_hi) of the recording (slots of the window): estimator, beamformer, stitching costs, permutations.
-int segments(css_ctx* h, StreamState* s, int64_t g_lo, int64_t g_hi, int64_t k_local) {
-    if (g_hi <= g_lo) return CSS_OK;
-    const int c = s->cur, T = s->T, F = h->d.num_bins, S = h->d.num_spks;
-    const int64_t lo = g_lo - s->seg_base, hi = g_hi - s->seg_base;
+// One stream's share of a round: segments [g_lo, g_hi) of its recording became complete; k_local frames of its window are transformed.
+struct SegJob { StreamState* s; int64_t g_lo, g_hi, k_local; };
+
+// The mask estimator over the segments of `jobs` (streams of ONE segmentation T / hop) as shared batches: batch segment c
+// belongs to the job whose range holds it.  The feature kernel takes a session-local first segment, and a stream's first new
+// segment is window slot g_lo - seg_base: time is the fastest axis of the planes, so a GroupSess whose planes start at frame
+// slot * hop (and whose frame count is shorter by as much) makes that slot its segment 0.  The mask head writes the batch
+// matrix into the stream code's own buffer; stream_scatter_masks_kernel moves each stream's columns into its window.
+int estimate_class(css_ctx* h, const std::vector<SegJob>& jobs, CssStreamGroupStats* stats) {
+    const int T = jobs[0].s->T, hop = jobs[0].s->hop, F = h->d.num_bins, S = h->d.num_spks;
+    int64_t total = 0;
+    for (const SegJob& j : jobs) total += j.g_hi - j.g_lo;
+    const int64_t cap = batch_len(total, batch_cap(h, T));
     int rc;
-    MaskIo io{(const float*)s->X[c].p, s->WF, k_local, s->hop, T, (float*)s->masks[c].p, s->SC * T};
-    io.PH = (const float*)s->X[c].p + (int64_t)s->n_ch * 2 * F * s->WF;
-    const int64_t cap = batch_len(hi - lo, batch_cap(h, T));
     if ((rc = ensure_activations(h, cap, T)) != CSS_OK) return rc;
-    for (int64_t s0 = lo; s0 < hi; s0 += cap) {
-        const int nb = (int)std::min<int64_t>(cap, hi - s0);
-        if ((rc = masknet_batch(h, io, s0, nb)) != CSS_OK) return rc;
-    }
-    MvdrArgs a{};
-    a.X = (const float*)s->X[c].p; a.T_ld = s->WF; a.stft_frames = k_local;
-    a.C = s->n_ch; a.F = F;
-    a.masks = (const float*)s->masks[c].p; a.mask_ld = s->SC * T;
-    a.S = S; a.T = T; a.hop = s->hop;
-    a.seg_lo = lo; a.nseg = (int)(hi - lo);
-    a.wta_override = nullptr;
-    a.scm = (double*)s->scm.p; a.bfw = (double*)s->bfw.p; a.sep = (float*)s->sep[c].p;
-    a.mask_floor = s->cfg.mask_floor;
-    a.use_mvdr = (s->n_ch > 1 && s->cfg.mc_mvdr) ? 1 : 0;
-    if (a.use_mvdr) {
-        if (!launch_scm(a, h->stream)) return fail(h, CSS_ERR_HIP, "the covariance kernel's LDS could not be reserved");
-        launch_mvdr_solve(a, h->stream);
-    }
-    launch_beamform(a, h->stream);
-    if (s->cfg.normalize_segment_power) launch_segment_power_norm(a, (double*)s->pnorm.p, h->stream);
-    // boundaries b (segments b, b + 1) that end in these segments (the costs' chunking is one constant: stitch.hip pit_chunks)
-    const int64_t b_lo = std::max<int64_t>(lo - 1, 0), b_hi = hi - 1;
-    if (b_hi > b_lo) {
-        StitchArgs sa{};
-        sa.masks = (const float*)s->masks[c].p; sa.mask_ld = s->SC * T; sa.sep = (const float*)s->sep[c].p;
-        sa.S = S; sa.F = F; sa.T = T; sa.hop = s->hop;
-        sa.num_segments = hi; sa.T_long = s->WF;
-        launch_pit_costs(sa, s->cfg.stitching_loss, s->cfg.stitching_input, b_lo, b_hi, (double*)s->pit_part.p,
-                         (double*)s->costs.p + S * S, h->stream);
-        // slot j's permutation lives at perms + (j + 1) S and boundary b's costs at costs + (b + 1) S S: the scan starts
-        // at its index 1 + b_lo and continues from slot b_lo's permutation (never the identity it writes for index 0)
-        launch_pit_scan((const double*)s->costs.p, 1 + b_lo, 1 + b_hi, S, (int32_t*)s->perms[c].p, h->stream);
+    if ((rc = ensure(h, h->stream_masks, (size_t)(S + 1) * F * cap * T * sizeof(float))) != CSS_OK) return rc;
+    std::vector<GroupSess> gs;
+    std::vector<MaskScatter> sc;
+    for (int64_t b0 = 0; b0 < total; b0 += cap) {
+        const int nb = (int)std::min<int64_t>(cap, total - b0);
+        gs.clear(); sc.clear();
+        int64_t off = 0;   // the job's first segment in the class's numbering
+        for (const SegJob& j : jobs) {
+            const int64_t n = j.g_hi - j.g_lo;
+            const int64_t lo = std::max(b0, off), hi = std::min<int64_t>(b0 + nb, off + n);
+            if (hi > lo) {
+                StreamState* s = j.s;
+                const int64_t slot = j.g_lo + (lo - off) - s->seg_base;
+                const float* X = (const float*)s->X[s->cur].p + slot * hop;
+                gs.push_back(GroupSess{X, s->WF, j.k_local - slot * hop, lo - b0, (int)(hi - lo), X + (int64_t)s->n_ch * 2 * F * s->WF});
+                sc.push_back(MaskScatter{(float*)s->masks[s->cur].p + slot * T, s->SC * T, (lo - b0) * T, (hi - lo) * T});
+            }
+            off += n;
+        }
+        MaskIo io{nullptr, 0, 0, hop, T, (float*)h->stream_masks.p, (int64_t)nb * T, &gs};
+        if ((rc = masknet_batch(h, io, 0, nb)) != CSS_OK) return rc;
+        launch_stream_scatter_masks((const float*)h->stream_masks.p, (int64_t)nb * T, (S + 1) * F, sc.data(), (int)sc.size(), h->stream);
+        if (stats) { stats->estimator_batches += 1; stats->estimator_segments += nb; }
     }
     HIPCHK(h, hipGetLastError());
     return CSS_OK;
 }
 
-// frames [t_lo, t_hi) of the recording: activity bits of [a_lo, a_hi), gate + overlap-add + synthesis of [t_lo, t_hi), output
-// blocks [t_lo, q_hi) into the output buffer (block t_lo at column 0)
-int tail(css_ctx* h, StreamState* s, bool closing, int64_t nseg, int64_t TL, int64_t a_lo, int64_t a_hi, int64_t t_lo, int64_t t_hi,
-         int64_t q_hi) {
-    const int64_t fb = s->seg_base * s->hop;
-    const StreamStitchArgs a = stitch_view(h, s, closing, nseg, TL);
-    launch_stream_activity(a, a_lo - fb, a_hi - fb, h->stream);
-    launch_stream_gate_ola(a, t_lo - fb, t_hi - fb, h->stream);
-    const int S = h->d.num_spks, N = h->d.frame_len, c = s->cur;
-    if (t_hi > t_lo) {
-        GemmArgs g{};
-        g.A = (const float*)s->Y.p + (t_lo - fb) * h->KIp; g.lda = h->KIp; g.strideA = s->WF * h->KIp;
-        g.B = h->dft_inv_t; g.ldb = h->KIp; g.strideB = 0;
-        g.C = (float*)s->G[c].p + (t_lo - fb) * N; g.ldc = N; g.strideC = s->WF * N;
-        g.M = (int)(t_hi - t_lo); g.N = N; g.K = h->KIp; g.batch = S;
-        g.bias = nullptr; g.act = ACT_NONE; g.residual = nullptr; g.alpha = 1.f;
-        launch_gemm(g, h->stream);
+// The segments the jobs completed: the estimator per (T, hop) class, then per stream covariances, MVDR (one table launch
+// for all streams), beamformer, power normalisation, the stitching costs of the boundaries that ended and the permutation
+// scan.  (The costs stay per stream: launch_pit_costs_multi computes a session's boundaries from 0, a stream needs a range.)
+int segments(css_ctx* h, const std::vector<SegJob>& all, CssStreamGroupStats* stats) {
+    std::vector<SegJob> jobs;
+    for (const SegJob& j : all)
+        if (j.g_hi > j.g_lo) jobs.push_back(j);
+    if (jobs.empty()) return CSS_OK;
+    int rc;
+    std::vector<char> taken(jobs.size(), 0);
+    std::vector<SegJob> cls;
+    for (size_t i = 0; i < jobs.size(); ++i) {
+        if (taken[i]) continue;
+        cls.clear();
+        for (size_t k = i; k < jobs.size(); ++k)
+            if (!taken[k] && jobs[k].s->T == jobs[i].s->T && jobs[k].s->hop == jobs[i].s->hop) { cls.push_back(jobs[k]); taken[k] = 1; }
+        if ((rc = estimate_class(h, cls, stats)) != CSS_OK) return rc;
     }
-    if (q_hi > t_lo)
-        launch_wave_ola((const float*)s->G[c].p, (float*)s->out.p, S, s->WF, h->d.frame_hop, N, t_lo - fb, q_hi - fb, 0,
-                        (closing ? TL : t_hi) - fb, (q_hi - t_lo) * h->d.frame_hop, t_lo - fb, nullptr, h->stream);
+    const int F = h->d.num_bins, S = h->d.num_spks;
+    std::vector<MvdrArgs> mv(jobs.size()), solve;
+    for (size_t i = 0; i < jobs.size(); ++i) {
+        StreamState* s = jobs[i].s;
+        const int c = s->cur;
+        MvdrArgs& a = mv[i];
+        a = MvdrArgs{};
+        a.X = (const float*)s->X[c].p; a.T_ld = s->WF; a.stft_frames = jobs[i].k_local;
+        a.C = s->n_ch; a.F = F;
+        a.masks = (const float*)s->masks[c].p; a.mask_ld = s->SC * s->T;
+        a.S = S; a.T = s->T; a.hop = s->hop;
+        a.seg_lo = jobs[i].g_lo - s->seg_base; a.nseg = (int)(jobs[i].g_hi - jobs[i].g_lo);
+        a.wta_override = nullptr;
+        a.scm = (double*)s->scm.p; a.bfw = (double*)s->bfw.p; a.sep = (float*)s->sep[c].p;
+        a.mask_floor = s->cfg.mask_floor;
+        a.use_mvdr = (s->n_ch > 1 && s->cfg.mc_mvdr) ? 1 : 0;
+        if (a.use_mvdr) {
+            if (!launch_scm(a, h->stream)) return fail(h, CSS_ERR_HIP, "the covariance kernel's LDS could not be reserved");
+            solve.push_back(a);
+        }
+    }
+    if (!solve.empty()) launch_mvdr_solve_multi(solve.data(), (int)solve.size(), h->stream);
+    for (size_t i = 0; i < jobs.size(); ++i) {
+        StreamState* s = jobs[i].s;
+        const int c = s->cur, T = s->T;
+        const int64_t lo = mv[i].seg_lo, hi = lo + mv[i].nseg;
+        launch_beamform(mv[i], h->stream);
+        if (s->cfg.normalize_segment_power) launch_segment_power_norm(mv[i], (double*)s->pnorm.p, h->stream);
+        // boundaries b (segments b, b + 1) that end in these segments (the costs' chunking is one constant: stitch.hip pit_chunks)
+        const int64_t b_lo = std::max<int64_t>(lo - 1, 0), b_hi = hi - 1;
+        if (b_hi > b_lo) {
+            StitchArgs sa{};
+            sa.masks = (const float*)s->masks[c].p; sa.mask_ld = s->SC * T; sa.sep = (const float*)s->sep[c].p;
+            sa.S = S; sa.F = F; sa.T = T; sa.hop = s->hop;
+            sa.num_segments = hi; sa.T_long = s->WF;
+            launch_pit_costs(sa, s->cfg.stitching_loss, s->cfg.stitching_input, b_lo, b_hi, (double*)s->pit_part.p,
+                             (double*)s->costs.p + S * S, h->stream);
+            // slot j's permutation lives at perms + (j + 1) S and boundary b's costs at costs + (b + 1) S S: the scan starts
+            // at its index 1 + b_lo and continues from slot b_lo's permutation (never the identity it writes for index 0)
+            launch_pit_scan((const double*)s->costs.p, 1 + b_lo, 1 + b_hi, S, (int32_t*)s->perms[c].p, h->stream);
+        }
+    }
+    HIPCHK(h, hipGetLastError());
+    return CSS_OK;
+}
+
+// One stream's frames [t_lo, t_hi) of the recording: activity bits of [a_lo, a_hi), gate + overlap-add + synthesis of [t_lo, t_hi),
+// output blocks [t_lo, q_hi) into the stream's output buffer (block t_lo at column 0)
+struct TailJob { StreamState* s; bool closing; int64_t nseg, TL, a_lo, a_hi, t_lo, t_hi, q_hi; };
+
+int tail(css_ctx* h, const std::vector<TailJob>& jobs) {
+    std::vector<StreamStitchArgs> a(jobs.size());
+    std::vector<StreamFrames> ra(jobs.size()), rg(jobs.size());
+    for (size_t i = 0; i < jobs.size(); ++i) {
+        const TailJob& j = jobs[i];
+        const int64_t fb = j.s->seg_base * j.s->hop;
+        a[i] = stitch_view(h, j.s, j.closing, j.nseg, j.TL);
+        ra[i] = StreamFrames{j.a_lo - fb, j.a_hi - fb};
+        rg[i] = StreamFrames{j.t_lo - fb, j.t_hi - fb};
+    }
+    launch_stream_activity_multi(a.data(), ra.data(), (int)jobs.size(), h->stream);
+    launch_stream_gate_ola_multi(a.data(), rg.data(), (int)jobs.size(), h->stream);
+    const int S = h->d.num_spks, N = h->d.frame_len;
+    for (const TailJob& j : jobs) {
+        StreamState* s = j.s;
+        const int64_t fb = s->seg_base * s->hop, t_lo = j.t_lo, t_hi = j.t_hi;
+        const int c = s->cur;
+        if (t_hi > t_lo) {
+            GemmArgs g{};
+            g.A = (const float*)s->Y.p + (t_lo - fb) * h->KIp; g.lda = h->KIp; g.strideA = s->WF * h->KIp;
+            g.B = h->dft_inv_t; g.ldb = h->KIp; g.strideB = 0;
+            g.C = (float*)s->G[c].p + (t_lo - fb) * N; g.ldc = N; g.strideC = s->WF * N;
+            g.M = (int)(t_hi - t_lo); g.N = N; g.K = h->KIp; g.batch = S;
+            g.bias = nullptr; g.act = ACT_NONE; g.residual = nullptr; g.alpha = 1.f;
+            launch_gemm(g, h->stream);
+        }
+        if (j.q_hi > t_lo)
+            launch_wave_ola((const float*)s->G[c].p, (float*)s->out.p, S, s->WF, h->d.frame_hop, N, t_lo - fb, j.q_hi - fb, 0,
+                            (j.closing ? j.TL : t_hi) - fb, (j.q_hi - t_lo) * h->d.frame_hop, t_lo - fb, nullptr, h->stream);
+    }
     HIPCHK(h, hipGetLastError());
     return CSS_OK;
 }
@@ -249,6 +327,8 @@ int check_stream_call(css_ctx* h, int32_t id, StreamState** out) {
 void stream_destroy_all(css_ctx* h) {
     for (int i = 0; i < CSS_MAX_STREAMS; ++i)
         if (h->streams[i]) { free_stream(static_cast<StreamState*>(h->streams[i])); h->streams[i] = nullptr; }
+    if (h->stream_masks.p) hipFree(h->stream_masks.p);
+    h->stream_masks = DevBuf{};
 }
 int stream_open_count(const css_ctx* h) {
     int n = 0;
@@ -331,65 +411,121 @@ int css_stream_open(css_handle_t h, const CssRunCfg* cfg, int32_t n_ch, int32_t*
     return CSS_OK;
 }
 
-int css_stream_push(css_handle_t h, int32_t id, const float* pcm_host, int64_t n_samples, float* out_host, int64_t cap, int64_t* n_out) {
-    StreamState* s = nullptr;
-    int rc = check_stream_call(h, id, &s);
-    if (rc != CSS_OK) return rc;
-    if (s->finished) return fail(h, CSS_ERR_STATE, "the stream has finished");
-    if (n_samples < 0 || (n_samples > 0 && !pcm_host) || !n_out) return fail(h, CSS_ERR_INVALID_ARG, "bad argument");
-    if (h->split) return fail(h, CSS_ERR_STATE, "streams run in CSS_LINEAR_EXACT_F32 only");
-    const int64_t halo = s->halo;
-    const int64_t need = final_frames(s->n_pushed + n_samples, s->T, s->hop, (int)halo) * h->d.frame_hop - s->n_emitted;
-    if (need > 0 && (!out_host || cap < need)) return fail(h, CSS_ERR_INVALID_ARG, "output capacity too small for the samples this push finalises");
-    if (zero_weight_frames(s, s->t_st, segments_done(frames_of(s->n_pushed + n_samples), s->T, s->hop) * s->hop))
-        return fail(h, CSS_ERR_ZERO_WEIGHT, "zero weights found. check hop_size, segment_size or m0, m1");
-    *n_out = 0;
-    if (n_samples == 0) return CSS_OK;
+// css_stream_push_many.  Every item is checked against its stream's state before anything moves (ids are distinct, so the
+// checks are those of the item-by-item calls); then the call works in rounds: round r takes piece r of every item that still
+// has one -- uploads (one synchronise per round: every stream owns its staging buffer), analysis transforms, the estimator
+// over all segments the round completed (segments), the stitching tail of all streams (tail), the downloads.
+int css_stream_push_many(css_handle_t h, CssStreamPush* items, int32_t n_items, CssStreamGroupStats* stats) {
+    if (!h) return CSS_ERR_INVALID_ARG;
+    if (n_items < 0 || (n_items > 0 && !items)) return fail(h, CSS_ERR_INVALID_ARG, "bad argument");
+    struct Item { StreamState* s; CssStreamPush* p; int64_t done, emitted, n, t_g1; };
+    std::vector<Item> its((size_t)n_items);
+    for (int32_t i = 0; i < n_items; ++i) {
+        CssStreamPush& p = items[i];
+        auto refuse = [&](int code, const std::string& msg) {
+            return fail(h, code, "item " + std::to_string(i) + " (stream " + std::to_string(p.id) + "): " + msg);
+        };
+        StreamState* s = get_stream(h, p.id);
+        if (!s) return refuse(CSS_ERR_INVALID_ARG, "no open stream with this id");
+        if (h->queued || !h->pending.empty())
+            return refuse(CSS_ERR_STATE, "queued sessions (css_run_enqueue*) are outstanding: css_wait before using a stream");
+        for (int32_t k = 0; k < i; ++k)
+            if (items[k].id == p.id) return refuse(CSS_ERR_INVALID_ARG, "the stream is named twice in one call");
+        if (s->finished) return refuse(CSS_ERR_STATE, "the stream has finished");
+        if (p.n_samples < 0 || (p.n_samples > 0 && !p.pcm_host)) return refuse(CSS_ERR_INVALID_ARG, "bad argument");
+        if (h->split) return refuse(CSS_ERR_STATE, "streams run in CSS_LINEAR_EXACT_F32 only");
+        const int64_t need = final_frames(s->n_pushed + p.n_samples, s->T, s->hop, s->halo) * h->d.frame_hop - s->n_emitted;
+        if (need > 0 && (!p.out_host || p.cap < need))
+            return refuse(CSS_ERR_INVALID_ARG, "output capacity too small for the samples this push finalises");
+        if (zero_weight_frames(s, s->t_st, segments_done(frames_of(s->n_pushed + p.n_samples), s->T, s->hop) * s->hop))
+            return refuse(CSS_ERR_ZERO_WEIGHT, "zero weights found. check hop_size, segment_size or m0, m1");
+        its[(size_t)i] = Item{s, &p, 0, 0, 0, 0};
+    }
+    if (stats) *stats = CssStreamGroupStats{};
+    bool any = false;
+    for (Item& it : its) { it.p->n_out = 0; any = any || it.p->n_samples > 0; }
+    if (!any) return CSS_OK;
     HIPCHK(h, hipSetDevice(h->device));
-    const int C = s->n_ch, hopS = h->d.frame_hop;
-    int64_t emitted = 0;
-    for (int64_t done = 0; done < n_samples;) {
-        const int64_t n = std::min<int64_t>(s->piece, n_samples - done);
-        const int64_t N1 = s->n_pushed + n, K1 = frames_of(N1);
-        if (K1 - s->seg_base * s->hop > s->WF || N1 - s->seg_base * s->hop * hopS > s->WS) {
-            if ((rc = rebase(h, s)) != CSS_OK) return rc;
-            if (K1 - s->seg_base * s->hop > s->WF || N1 - s->seg_base * s->hop * hopS > s->WS)
-                return fail(h, CSS_ERR_STATE, "stream window overflow");
+    const int hopS = h->d.frame_hop;
+    int rc;
+    std::vector<Item*> act;
+    std::vector<SegJob> sj;
+    std::vector<TailJob> tj;
+    for (;;) {
+        act.clear();
+        for (Item& it : its)
+            if (it.done < it.p->n_samples) act.push_back(&it);
+        if (act.empty()) break;
+        for (Item* it : act) {
+            StreamState* s = it->s;
+            const int C = s->n_ch;
+            const int64_t n = it->n = std::min<int64_t>(s->piece, it->p->n_samples - it->done);
+            const int64_t N1 = s->n_pushed + n, K1 = frames_of(N1);
+            if (K1 - s->seg_base * s->hop > s->WF || N1 - s->seg_base * s->hop * hopS > s->WS) {
+                if ((rc = rebase(h, s)) != CSS_OK) return rc;
+                if (K1 - s->seg_base * s->hop > s->WF || N1 - s->seg_base * s->hop * hopS > s->WS)
+                    return fail(h, CSS_ERR_STATE, "stream window overflow");
+            }
+            const int64_t sb = s->seg_base * s->hop * hopS;
+            // samples -> the window, channel-major (a plain copy: the transform reads the same values css_run's does)
+            const float* src = it->p->pcm_host + it->done * C;
+            for (int ch = 0; ch < C; ++ch) {
+                float* d = s->host_cm.data() + (size_t)ch * n;
+                for (int64_t i = 0; i < n; ++i) d[i] = src[i * C + ch];
+            }
+            HIPCHK(h, hipMemcpy2DAsync((float*)s->pcm[s->cur].p + (s->n_pushed - sb), (size_t)s->WS * sizeof(float), s->host_cm.data(),
+                                       (size_t)n * sizeof(float), (size_t)n * sizeof(float), (size_t)C, hipMemcpyHostToDevice, h->stream));
         }
-        const int64_t fb = s->seg_base * s->hop, sb = fb * hopS;
-        // samples -> the window, channel-major (a plain copy: the transform reads the same values css_run's does)
-        const float* src = pcm_host + done * C;
-        for (int ch = 0; ch < C; ++ch) {
-            float* d = s->host_cm.data() + (size_t)ch * n;
-            for (int64_t i = 0; i < n; ++i) d[i] = src[i * C + ch];
-        }
-        HIPCHK(h, hipMemcpy2DAsync((float*)s->pcm[s->cur].p + (s->n_pushed - sb), (size_t)s->WS * sizeof(float), s->host_cm.data(),
-                                   (size_t)n * sizeof(float), (size_t)n * sizeof(float), (size_t)C, hipMemcpyHostToDevice, h->stream));
-        // the host buffer is reused by the next piece
+        // the staging buffers are reused by the next round
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        s->n_pushed = N1;
-        const int c = s->cur;
-        bool ph = false;
-        if (K1 > s->K &&
-            !analysis_transform(h, (const float*)s->pcm[c].p, s->WS, C, s->K - fb, K1 - fb, (float*)s->X[c].p, s->WF, h->stream,
-                                (float*)s->X[c].p + (int64_t)C * 2 * h->d.num_bins * s->WF, &ph))
-            return fail(h, CSS_ERR_HIP, "the analysis transform's LDS could not be reserved");
-        s->K = std::max(s->K, K1);
-        const int64_t sd1 = segments_done(s->K, s->T, s->hop);
-        if ((rc = segments(h, s, s->sd, sd1, s->K - fb)) != CSS_OK) return rc;
-        s->sd = sd1;
-        const int64_t t_st1 = sd1 * s->hop, t_g1 = std::max<int64_t>(t_st1 - halo, 0);
-        if ((rc = tail(h, s, false, 0, 0, s->t_st, t_st1, s->t_g, t_g1, t_g1)) != CSS_OK) return rc;
-        if ((rc = download(h, s, (t_g1 - s->t_g) * hopS, out_host, cap, emitted)) != CSS_OK) return rc;
-        emitted += (t_g1 - s->t_g) * hopS;
-        s->t_st = t_st1;
-        s->t_g = t_g1;
-        done += n;
+        sj.clear(); tj.clear();
+        for (Item* it : act) {
+            StreamState* s = it->s;
+            const int c = s->cur;
+            const int64_t fb = s->seg_base * s->hop;
+            s->n_pushed += it->n;
+            const int64_t K1 = frames_of(s->n_pushed);
+            bool ph = false;
+            if (K1 > s->K &&
+                !analysis_transform(h, (const float*)s->pcm[c].p, s->WS, s->n_ch, s->K - fb, K1 - fb, (float*)s->X[c].p, s->WF, h->stream,
+                                    (float*)s->X[c].p + (int64_t)s->n_ch * 2 * h->d.num_bins * s->WF, &ph))
+                return fail(h, CSS_ERR_HIP, "the analysis transform's LDS could not be reserved");
+            s->K = std::max(s->K, K1);
+            const int64_t sd1 = segments_done(s->K, s->T, s->hop);
+            sj.push_back(SegJob{s, s->sd, sd1, s->K - fb});
+            const int64_t t_st1 = sd1 * s->hop;
+            it->t_g1 = std::max<int64_t>(t_st1 - s->halo, 0);
+            tj.push_back(TailJob{s, false, 0, 0, s->t_st, t_st1, s->t_g, it->t_g1, it->t_g1});
+        }
+        if ((rc = segments(h, sj, stats)) != CSS_OK) return rc;
+        for (const SegJob& j : sj) j.s->sd = j.g_hi;
+        if ((rc = tail(h, tj)) != CSS_OK) return rc;
+        for (Item* it : act) {
+            StreamState* s = it->s;
+            const int64_t n_new = (it->t_g1 - s->t_g) * hopS;
+            if ((rc = download(h, s, n_new, it->p->out_host, it->p->cap, it->emitted)) != CSS_OK) return rc;
+            it->emitted += n_new;
+            s->t_st = s->sd * s->hop;
+            s->t_g = it->t_g1;
+            it->done += it->n;
+        }
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    s->n_emitted += emitted;
-    *n_out = emitted;
+    for (Item& it : its) {
+        it.s->n_emitted += it.emitted;
+        it.p->n_out = it.emitted;
+    }
     return CSS_OK;
+}
+
+// a group of one item
+int css_stream_push(css_handle_t h, int32_t id, const float* pcm_host, int64_t n_samples, float* out_host, int64_t cap, int64_t* n_out) {
+    if (!h) return CSS_ERR_INVALID_ARG;
+    if (!n_out) return fail(h, CSS_ERR_INVALID_ARG, "bad argument");
+    CssStreamPush p{id, pcm_host, n_samples, out_host, cap, 0};
+    const int rc = css_stream_push_many(h, &p, 1, nullptr);
+    if (rc == CSS_OK) *n_out = p.n_out;
+    return rc;
 }
 
 int css_stream_finish(css_handle_t h, int32_t id, float* out_host, int64_t cap, int64_t* n_out) {
@@ -412,13 +548,13 @@ int css_stream_finish(css_handle_t h, int32_t id, float* out_host, int64_t cap, 
     if (s->WF > s->K - fb)
         HIPCHK(h, hipMemset2DAsync((float*)s->X[c].p + (s->K - fb), (size_t)s->WF * sizeof(float), 0,
                                    (size_t)(s->WF - (s->K - fb)) * sizeof(float), (size_t)s->n_ch * X_ROWS_PER_BIN * F, h->stream));
-    if ((rc = segments(h, s, s->sd, nseg, s->K - fb)) != CSS_OK) return rc;
+    if ((rc = segments(h, {SegJob{s, s->sd, nseg, s->K - fb}}, nullptr)) != CSS_OK) return rc;
     // the rest of the output: blocks up to mix_frames (frame_len = 2 hop: block TL holds the last frame's second half)
     const int64_t q_hi = TL + 1;
     if ((q_hi - s->t_g) * h->d.frame_hop > (int64_t)(s->out.cap / (sizeof(float) * h->d.num_spks))) {
         if ((rc = ensure(h, s->out, (size_t)h->d.num_spks * (q_hi - s->t_g) * h->d.frame_hop * sizeof(float))) != CSS_OK) return rc;
     }
-    if ((rc = tail(h, s, true, nseg, TL, s->t_st, TL, s->t_g, TL, q_hi)) != CSS_OK) return rc;
+    if ((rc = tail(h, {TailJob{s, true, nseg, TL, s->t_st, TL, s->t_g, TL, q_hi}})) != CSS_OK) return rc;
     if ((rc = download(h, s, need, out_host, cap, 0)) != CSS_OK) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     s->sd = nseg; s->t_st = s->t_g = TL;

@@ -284,5 +284,15 @@ struct StreamStitchArgs {
 };
 void launch_stream_activity(const StreamStitchArgs& a, int64_t t_lo, int64_t t_hi, hipStream_t s);
 void launch_stream_gate_ola(const StreamStitchArgs& a, int64_t t_lo, int64_t t_hi, hipStream_t s);
+// the same for n streams' windows (a grouped push: same S and F), each with its own local frame range, in launches of up to
+// STREAM_MULTI_MAX entries; every frame written is the single launch's (which IS this launch with one entry)
+constexpr int STREAM_MULTI_MAX = 16;
+struct StreamFrames { int64_t t_lo, t_hi; };
+void launch_stream_activity_multi(const StreamStitchArgs* a, const StreamFrames* r, int n, hipStream_t s);
+void launch_stream_gate_ola_multi(const StreamStitchArgs* a, const StreamFrames* r, int n, hipStream_t s);
+// mask columns of a shared estimator batch -> the streams' windows: for entry e, rows 0 .. rows - 1, columns [src_col, src_col +
+// n_cols) of src (leading dimension src_ld) to dst[row * dst_ld + c], c < n_cols.  A pure copy, any number of entries.
+struct MaskScatter { float* dst; int64_t dst_ld; int64_t src_col; int64_t n_cols; };
+void launch_stream_scatter_masks(const float* src, int64_t src_ld, int rows, const MaskScatter* e, int n, hipStream_t s);
 
 }  // namespace css

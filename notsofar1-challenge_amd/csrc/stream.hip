@@ -7,6 +7,11 @@
 //   stream_activity_kernel   weighted overlap-add of the permuted masks, mean over frequency, threshold -> act_b
 //   stream_gate_ola_kernel   dilate / erode of act_b (left halo from earlier pushes), weighted overlap-add of the permuted
 //                            spectra, gating -> synthesis rows Y
+// Both are table launches (the idiom of mvdr_solve_multi_kernel): up to STREAM_MULTI_MAX streams' windows and frame ranges
+// by value, blockIdx.z selects the entry, blocks past an entry's range return at once.  One stream is a table of one entry,
+// so there is one copy of each body and one kernel for css_stream_push, css_stream_push_many and css_stream_finish.
+//   stream_scatter_masks_kernel   the mask columns of an estimator batch shared by several streams -> each stream's window
+#include <algorithm>
 #include <climits>
 
 #include "kernels.hpp"
@@ -29,7 +34,10 @@ __device__ __forceinline__ void stream_cover(const StreamStitchArgs& a, int64_t 
 // ola_masks_kernel's block shape and reduction order: 16 frames x 16 frequency groups, float64 partial sums per group,
 // the 16 groups added in a fixed order
 constexpr int SA_T = 16, SA_FG = 16;
-__global__ __launch_bounds__(256) void stream_activity_kernel(StreamStitchArgs a, int64_t t_lo, int64_t t_hi) {
+struct StreamMulti { StreamStitchArgs a[STREAM_MULTI_MAX]; StreamFrames r[STREAM_MULTI_MAX]; };
+static_assert(sizeof(StreamMulti) <= 4096, "the table travels by value as a kernel argument");
+
+__device__ __forceinline__ void stream_activity_body(const StreamStitchArgs& a, int64_t t_lo, int64_t t_hi) {
     __shared__ double red[SA_FG][SA_T];
     const int s = blockIdx.y;
     const int lane = threadIdx.x & (SA_T - 1), fg = threadIdx.x / SA_T;
@@ -62,10 +70,16 @@ __global__ __launch_bounds__(256) void stream_activity_kernel(StreamStitchArgs a
     }
 }
 
+__global__ __launch_bounds__(256) void stream_activity_kernel(StreamMulti m) {
+    const StreamFrames r = m.r[blockIdx.z];
+    if (r.t_lo + (int64_t)blockIdx.x * SA_T >= r.t_hi) return;
+    stream_activity_body(m.a[blockIdx.z], r.t_lo, r.t_hi);
+}
+
 // morph_kernel twice (dilate with zeros outside the recording, erode with ones outside it), then ola_stft_kernel's
 // overlap-add, division and gate, written as float32 synthesis rows.  Block = 16 frames of one stream.
 constexpr int SG_T = 16;
-__global__ __launch_bounds__(256) void stream_gate_ola_kernel(StreamStitchArgs a, int64_t t_lo, int64_t t_hi) {
+__device__ __forceinline__ void stream_gate_ola_body(const StreamStitchArgs& a, int64_t t_lo, int64_t t_hi) {
     extern __shared__ __attribute__((aligned(16))) float tile[];   // [SG_T][2F + 1], then the dilated bits
     const int TS = 2 * a.F + 1;
     uint8_t* dil = reinterpret_cast<uint8_t*>(tile + SG_T * TS);   // [SG_T + 2 E]
@@ -129,17 +143,74 @@ __global__ __launch_bounds__(256) void stream_gate_ola_kernel(StreamStitchArgs a
     }
 }
 
-void launch_stream_activity(const StreamStitchArgs& a, int64_t t_lo, int64_t t_hi, hipStream_t s) {
-    if (t_hi <= t_lo) return;
-    hipLaunchKernelGGL(stream_activity_kernel, dim3((unsigned)((t_hi - t_lo + SA_T - 1) / SA_T), a.S), dim3(SA_T * SA_FG), 0, s,
-                       a, t_lo, t_hi);
+__global__ __launch_bounds__(256) void stream_gate_ola_kernel(StreamMulti m) {
+    const StreamFrames r = m.r[blockIdx.z];
+    if (r.t_lo + (int64_t)blockIdx.x * SG_T >= r.t_hi) return;
+    stream_gate_ola_body(m.a[blockIdx.z], r.t_lo, r.t_hi);
 }
 
+// The mask head of a shared batch writes ONE matrix [rows][src_ld] (time fastest, batch segment c at column c T); stream e's
+// segments are n_cols consecutive columns of it and belong at a column of that stream's own window matrix.  Rows are runs of
+// T floats (186: not a multiple of 4) whose source and destination columns differ mod 4, so neither side can be 16-byte
+// aligned for more than one row in four: a wave copies one row with dword loads and stores, 64 consecutive floats per
+// access (256 contiguous bytes on both sides).  It is 0.77 MB per segment behind an estimator pass of milliseconds.
+constexpr int SC_ENTRIES = 16, SC_ROWS = 4;
+struct MaskScatterTable { MaskScatter e[SC_ENTRIES]; };
+__global__ __launch_bounds__(64 * SC_ROWS) void stream_scatter_masks_kernel(const float* __restrict__ src, int64_t src_ld, int rows,
+                                                                            MaskScatterTable tab) {
+    const MaskScatter e = tab.e[blockIdx.y];
+    const int row = blockIdx.x * SC_ROWS + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    const float* __restrict__ in = src + (int64_t)row * src_ld + e.src_col;
+    float* __restrict__ out = e.dst + (int64_t)row * e.dst_ld;
+    for (int64_t c = lane; c < e.n_cols; c += 64) out[c] = in[c];
+}
+
+void launch_stream_activity_multi(const StreamStitchArgs* a, const StreamFrames* r, int n, hipStream_t s) {
+    for (int i0 = 0; i0 < n; i0 += STREAM_MULTI_MAX) {
+        const int cnt = std::min(STREAM_MULTI_MAX, n - i0);
+        StreamMulti m{};
+        int64_t most = 0;
+        for (int i = 0; i < cnt; ++i) { m.a[i] = a[i0 + i]; m.r[i] = r[i0 + i]; most = std::max(most, r[i0 + i].t_hi - r[i0 + i].t_lo); }
+        if (most > 0)
+            hipLaunchKernelGGL(stream_activity_kernel, dim3((unsigned)((most + SA_T - 1) / SA_T), a[i0].S, cnt), dim3(SA_T * SA_FG), 0, s, m);
+    }
+}
+
+void launch_stream_gate_ola_multi(const StreamStitchArgs* a, const StreamFrames* r, int n, hipStream_t s) {
+    for (int i0 = 0; i0 < n; i0 += STREAM_MULTI_MAX) {
+        const int cnt = std::min(STREAM_MULTI_MAX, n - i0);
+        StreamMulti m{};
+        int64_t most = 0;
+        int erosion = 0;   // the dynamic LDS of the launch is the largest entry's
+        for (int i = 0; i < cnt; ++i) {
+            m.a[i] = a[i0 + i]; m.r[i] = r[i0 + i];
+            most = std::max(most, r[i0 + i].t_hi - r[i0 + i].t_lo);
+            erosion = std::max(erosion, a[i0 + i].erosion);
+        }
+        const size_t lds = (size_t)SG_T * (2 * a[i0].F + 1) * sizeof(float) + (size_t)SG_T + 2 * (size_t)erosion;
+        if (most > 0)
+            hipLaunchKernelGGL(stream_gate_ola_kernel, dim3((unsigned)((most + SG_T - 1) / SG_T), a[i0].S, cnt), dim3(256), lds, s, m);
+    }
+}
+
+void launch_stream_activity(const StreamStitchArgs& a, int64_t t_lo, int64_t t_hi, hipStream_t s) {
+    const StreamFrames r{t_lo, t_hi};
+    launch_stream_activity_multi(&a, &r, 1, s);
+}
 void launch_stream_gate_ola(const StreamStitchArgs& a, int64_t t_lo, int64_t t_hi, hipStream_t s) {
-    if (t_hi <= t_lo) return;
-    const size_t lds = (size_t)SG_T * (2 * a.F + 1) * sizeof(float) + (size_t)SG_T + 2 * (size_t)a.erosion;
-    hipLaunchKernelGGL(stream_gate_ola_kernel, dim3((unsigned)((t_hi - t_lo + SG_T - 1) / SG_T), a.S), dim3(256), lds, s,
-                       a, t_lo, t_hi);
+    const StreamFrames r{t_lo, t_hi};
+    launch_stream_gate_ola_multi(&a, &r, 1, s);
+}
+
+void launch_stream_scatter_masks(const float* src, int64_t src_ld, int rows, const MaskScatter* e, int n, hipStream_t s) {
+    for (int i0 = 0; i0 < n; i0 += SC_ENTRIES) {
+        const int cnt = std::min(SC_ENTRIES, n - i0);
+        MaskScatterTable tab{};
+        for (int i = 0; i < cnt; ++i) tab.e[i] = e[i0 + i];
+        hipLaunchKernelGGL(stream_scatter_masks_kernel, dim3((unsigned)((rows + SC_ROWS - 1) / SC_ROWS), cnt), dim3(64 * SC_ROWS), 0, s,
+                           src, src_ld, rows, tab);
+    }
 }
 
 }  // namespace css

@@ -3,6 +3,14 @@ device-to-host copy), aggregate real-time factor, observed lag, device memory pe
 in the same process for context.  Prints one JSON document (profiles/r07_stream_bench.json holds a run).
 
     python tools/stream_bench.py [--minutes 1 10] [--pushes 0.5 1.5] [--out FILE]
+
+With --streams N: N live meetings of 60 s fed in rounds of 1.5 s per stream, two arms on the same streams in alternating
+blocks of rounds (so that clock and power state are shared): (A) N css_stream_push calls per round, one after the other;
+(B) one css_stream_push_many per round.  A stream's output does not depend on the arm that pushed a round, so both arms
+work on ONE set of streams; every returned piece is compared with css_run's output for the recording.  Per arm: p50 / p99 ms
+per round, streams served in real time per GPU (1.5 s / round time x N), bit_identical (profiles/r09_stream_group.json).
+
+    python tools/stream_bench.py --streams 16 [--out FILE]
 """
 import argparse
 import json
@@ -19,12 +27,89 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 FS = 16000
 
 
+def group_bench(n_streams, out_path, seconds=60.0, round_s=1.5, block=5, passes=2):
+    import notsofar1_challenge_amd.css as CSS
+    import notsofar1_challenge_amd.separator as SEP
+    import notsofar1_challenge_amd.stream as STR
+    import notsofar1_challenge_amd.synth as SYN
+    import notsofar1_challenge_amd.weights as W
+    desc = W.ModelDesc.mc_v1()
+    st = W.apply_golden_recipe(W.portable_state_dict(desc, 0))
+    sep = SEP.HipSeparator(st, None, device=0, max_batch_segments=256)
+    cfg = CSS.CssCfg()
+    rc = CSS.make_run_cfg(cfg, FS, 7)
+    recs = [np.ascontiguousarray(SYN.synth_meeting(seconds, 7, seed=1000 + i)[0]) for i in range(n_streams)]
+    sep.handle.run(recs[0][:FS * 10], rc)   # warm-up
+    refs = [sep.handle.run(x, rc).copy() for x in recs]
+    step = int(round_s * FS)
+    ms = {"A": [], "B": []}
+    same = {"A": True, "B": True}
+    seg_per_batch = []
+
+    def one_pass(first_arm, timed):
+        streams = [STR.CssStream(sep, cfg) for _ in recs]
+        group = STR.CssStreamGroup(streams)
+        em = [0] * n_streams
+        n_rounds = (recs[0].shape[0] + step - 1) // step if timed else 2 * block
+        for r in range(n_rounds):
+            arm = "AB"[(r // block + (first_arm == "B")) % 2]
+            chunks = [x[r * step:(r + 1) * step] for x in recs]
+            t = time.perf_counter()
+            if arm == "A":
+                res = [s.push(c) for s, c in zip(streams, chunks)]
+            else:
+                res = group.push(chunks)
+            dt = time.perf_counter() - t
+            if not timed:
+                continue
+            ms[arm].append(dt * 1e3)
+            if arm == "B" and group.stats.estimator_batches:
+                seg_per_batch.append(group.stats.estimator_segments / group.stats.estimator_batches)
+            for i, got in enumerate(res):
+                got = np.stack(got)
+                same[arm] = same[arm] and bool(np.array_equal(got, refs[i][:, em[i]:em[i] + got.shape[1]]))
+                em[i] += got.shape[1]
+        if timed:
+            for i, s in enumerate(streams):
+                got = np.stack(s.finish())
+                ok = bool(np.array_equal(got, refs[i][:, em[i]:])) and em[i] + got.shape[1] == refs[i].shape[1]
+                same["A"], same["B"] = same["A"] and ok, same["B"] and ok
+        dev = streams[0].info().device_bytes
+        for s in streams:
+            s.close()
+        return dev
+
+    one_pass("A", False)   # warm-up: both arms, segments included
+    dev = 0
+    for p in range(passes):
+        dev = one_pass("AB"[p % 2], True)
+    res = {"model": "mc_v1 (18 blocks, exact float32)", "cfg": "3 s / 1.5 s segments, defaults", "streams": n_streams,
+           "meeting_s": seconds, "round_s": round_s, "block_rounds": block, "device_bytes_per_stream": int(dev),
+           "segments_per_estimator_batch_median": float(np.median(seg_per_batch)) if seg_per_batch else 0.0, "arms": {}}
+    for arm, what in (("A", "one css_stream_push per stream and round"), ("B", "one css_stream_push_many per round")):
+        v = np.array(ms[arm])
+        p50 = float(np.percentile(v, 50))
+        res["arms"][arm] = {"what": what, "rounds": int(v.size), "round_ms_p50": round(p50, 3),
+                            "round_ms_p99": round(float(np.percentile(v, 99)), 3),
+                            "streams_in_real_time_per_gpu": round(round_s * 1e3 / p50 * n_streams, 1), "bit_identical": same[arm]}
+    res["p50_ratio_B_over_A"] = round(res["arms"]["B"]["round_ms_p50"] / res["arms"]["A"]["round_ms_p50"], 4)
+    sep.close()
+    text = json.dumps(res, indent=1)
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write(text + "\n")
+    print(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--minutes", type=float, nargs="+", default=[1.0, 10.0])
     ap.add_argument("--pushes", type=float, nargs="+", default=[0.5, 1.5])
+    ap.add_argument("--streams", type=int, default=0, help="grouped pushes: N live meetings, per-stream pushes against one grouped push per round")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.streams:
+        return group_bench(a.streams, a.out)
     import notsofar1_challenge_amd.css as CSS
     import notsofar1_challenge_amd.separator as SEP
     import notsofar1_challenge_amd.stream as STR
