@@ -5,7 +5,11 @@ for bit, to the offline result on the whole meeting).  Prints the lag and the ti
 With --rooms N, N synthetic meetings (different seeds) arrive tick by tick and are pushed through one CssStreamGroup: the
 segments the rooms complete in a tick share the mask estimator's batches (css_stream_push_many).
 
-    python examples/live_stream.py [--seconds 30] [--rooms N]
+With --logmel every stream has the hand-off to the ASR front end on: each tick also returns, per room and speaker, the raw
+Whisper log-mel frames and the sample ranges of the audio the activity gate kept (CssStream(handoff=...)); a Whisper host
+collects 3 000 frames per window and normalises each window with whisper_normalize.
+
+    python examples/live_stream.py [--seconds 30] [--rooms N] [--logmel]
 """
 import argparse
 import os
@@ -23,9 +27,20 @@ import notsofar1_challenge_amd.synth as SYN        # noqa: E402
 import notsofar1_challenge_amd.weights as W        # noqa: E402
 
 
-def rooms(sep, n_rooms, seconds, fs, chunk):
+HANDOFF = dict(n_mels=80, pad_frames=8, drop_silence=True)
+
+
+def print_handoff(streams, fs):
+    """per room and speaker: log-mel frames and kept seconds of this tick"""
+    for r, s in enumerate(streams):
+        h = s.handoff
+        per = [f"{m.shape[1]:4d} fr {float((g[:, 1] - g[:, 0]).sum()) / fs:5.2f} s" for m, g in zip(h.mel, h.ranges)]
+        print(f"    room {r}: " + " | ".join(per))
+
+
+def rooms(sep, n_rooms, seconds, fs, chunk, logmel=False):
     mixes = [SYN.synth_meeting(seconds, 7, seed=1 + r)[0] for r in range(n_rooms)]
-    streams = [STR.CssStream(sep, CSS.CssCfg(), fs=fs, num_channels=7) for _ in mixes]
+    streams = [STR.CssStream(sep, CSS.CssCfg(), fs=fs, num_channels=7, handoff=HANDOFF if logmel else None) for _ in mixes]
     group = STR.CssStreamGroup(streams)
     outs = [[[] for _ in range(sep.desc.num_spks)] for _ in mixes]
     print(f"{n_rooms} rooms, lag bound {streams[0].latency_samples / fs:.2f} s")
@@ -39,6 +54,8 @@ def rooms(sep, n_rooms, seconds, fs, chunk):
         inf = streams[0].info()
         print(f"t={inf.n_pushed / fs:6.1f} s  final={inf.n_emitted / fs:6.1f} s  tick {ms:6.2f} ms  "
               f"estimator batches {group.stats.estimator_batches} ({group.stats.estimator_segments} segments)")
+        if logmel:
+            print_handoff(streams, fs)
     for s, room in zip(streams, outs):
         for k, o in enumerate(s.finish()):
             room[k].append(o)
@@ -50,18 +67,20 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=30.0)
     ap.add_argument("--rooms", type=int, default=1, help="meetings fed tick by tick through one CssStreamGroup")
+    ap.add_argument("--logmel", action="store_true", help="also return Whisper log-mel frames and kept ranges with every tick")
     a = ap.parse_args()
     fs = 16000
     desc = W.ModelDesc.mc_v1()
     sep = SEP.HipSeparator(W.apply_golden_recipe(W.portable_state_dict(desc, 0)), None, device=0)
     if a.rooms > 1:
-        rooms(sep, a.rooms, a.seconds, fs, fs // 2)
+        rooms(sep, a.rooms, a.seconds, fs, fs // 2, a.logmel)
         sep.close()
         return
     mix = SYN.synth_meeting(a.seconds, 7, seed=1)[0]
     chunk = fs // 2
     streams = [[] for _ in range(desc.num_spks)]
-    with STR.CssStream(sep, CSS.CssCfg(), fs=fs, num_channels=7) as s:
+    mels = [[] for _ in range(desc.num_spks)]
+    with STR.CssStream(sep, CSS.CssCfg(), fs=fs, num_channels=7, handoff=HANDOFF if a.logmel else None) as s:
         print(f"lag bound {s.latency_samples / fs:.2f} s")
         for i in range(0, mix.shape[0], chunk):
             t = time.perf_counter()
@@ -72,8 +91,20 @@ def main():
             inf = s.info()
             print(f"t={inf.n_pushed / fs:6.1f} s  final={inf.n_emitted / fs:6.1f} s  lag={(inf.n_pushed - inf.n_emitted) / fs:4.2f} s  "
                   f"push {ms:6.2f} ms")
+            if a.logmel:
+                print_handoff([s], fs)
+                for k, m in enumerate(s.handoff.mel):
+                    mels[k].append(m)
         for k, o in enumerate(s.finish()):
             streams[k].append(o)
+        if a.logmel:
+            for k, m in enumerate(s.handoff.mel):
+                mels[k].append(m)
+            # a Whisper host: windows of 3 000 frames, each normalised with its own maximum
+            for k in range(desc.num_spks):
+                raw = np.concatenate(mels[k], axis=1)
+                windows = [STR.whisper_normalize(raw[:, i:i + 3000]) for i in range(0, raw.shape[1], 3000)]
+                print(f"speaker {k}: {raw.shape[1]} log-mel frames in {len(windows)} Whisper window(s)")
     wavs = [np.concatenate(x) for x in streams]
     print("separated:", [w.shape[0] / fs for w in wavs], "s")
     sep.close()

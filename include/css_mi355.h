@@ -497,7 +497,8 @@ int css_istft_host(css_handle_t h, const float* y_planes, int32_t batch, int64_t
  *     css_set_linear_mode(h, CSS_LINEAR_SPLIT_F16) while a stream is open return CSS_ERR_STATE; so do css_set_analysis_window
  *     and css_set_feature_options (a stream's pushes read the handle's window and feature options);
  *   - frame_len 512 / frame_hop 256 only (CSS_ERR_INVALID_ARG otherwise); any segmentation css_make_run_cfg accepts;
- *   - CSS_ERR_STATE while css_run_enqueue* sessions are outstanding (not yet css_wait-ed).
+ *   - CSS_ERR_STATE while css_run_enqueue* sessions are outstanding (not yet css_wait-ed);
+ *   - css_stream_handoff_* (below): the ASR front end's log-mel frames, kept ranges and gate bits with every push.
  * Output: out_host [S][cap]; a push writes at most n_samples + max_lag samples per stream, finish css_plan(n_pushed).n_out -
  * n_emitted.  A capacity below what the call would return is CSS_ERR_INVALID_ARG and leaves the stream unchanged. */
 #define CSS_MAX_STREAMS 64
@@ -537,6 +538,62 @@ int css_stream_close(css_handle_t h, int32_t id);
 int css_stream_info(css_handle_t h, int32_t id, CssStreamInfo* out);
 /* Pure host arithmetic, no GPU: samples of every separated stream that are final after n_pushed samples of an open stream. */
 int css_stream_final_samples(const CssModelDesc* desc, const CssRunCfg* cfg, int64_t n_pushed, int64_t* n_final);
+
+/* ---- the hand-off of a stream: Whisper log-mel frames, kept sample ranges and gate bits as samples become final ----------
+ * css_handoff_logmel for a meeting that is still going on.  A stream with the hand-off switched on returns with every push
+ * (css_stream_push, every item of css_stream_push_many) and with css_stream_finish, per separated stream k:
+ *   - the gate bits act[k][t] of the frames t that became final in the call (CSS_BUF_ACT_FINAL of css_run on the whole recording);
+ *   - the sample ranges [a, b) of the meeting, ascending and disjoint, that the call appended to stream k's concatenation of
+ *     kept samples (a range may start where the previous call's last one ended: one region going on); all calls' ranges,
+ *     touching ones merged, are css_handoff_logmel's regions_host;
+ *   - the RAW log-mel frames log10(max(mel power, 1e-10)) of the concatenation that are complete, [n_mels][n], time fastest
+ *     (frame j reads concatenated samples below 160 j + 200, so (A - 200) / 160 + 1 frames are complete with A >= 201 samples
+ *     appended; finish emits the rest up to A / 160 with the trailing reflection).  Raw: without the max - 8 clamp and
+ *     (x + 4) / 4, which need a maximum over a span the consumer chooses (Whisper normalises per 30 s window);
+ *   - raw_max[k]: the maximum of every raw value returned for k so far (-inf before the first frame).
+ * For a finished stream, all frames of k, then (max(raw, raw_max - 8) + 4) * 0.25 in float32, are css_handoff_logmel's mel_host
+ * for (k, n_mels, pad_frames, drop_silence) after css_run_device on the whole recording, bit for bit.
+ * What is decided when: a sample n is kept iff an active frame t has max(t - pad_frames, 0) hop <= n < min((t + pad_frames) hop
+ * + frame_len, n_out); a frame that is not gated-final yet can only keep samples from (t_g - pad_frames) hop on, so after a push
+ * every sample below max(t_g - pad_frames, 0) hop is decided (t_g: gated-final frames) and at finish all are: the hand-off
+ * trails the waveforms by pad_frames hop samples.  With drop_silence = 0 every final sample is kept at once and pad_frames is unused.
+ * Per stream, before its first sample: n_mels (80 / 128), pad_frames (0 .. 4096), drop_silence. */
+typedef struct CssStreamHandoffCfg { int32_t n_mels, pad_frames, drop_silence; } CssStreamHandoffCfg;
+/* CSS_ERR_STATE after the stream's first sample or when the hand-off is on already; CSS_ERR_INVALID_ARG for other values */
+int css_stream_handoff_open(css_handle_t h, int32_t id, const CssStreamHandoffCfg* cfg);
+/* Caller-owned, bound to a stream and filled by every later push / finish of it (the struct and its arrays stay valid while
+ * bound).  A call needs the capacities css_stream_handoff_bounds gives for its n_samples: less is CSS_ERR_INVALID_ARG and, as
+ * for the waveforms, leaves every stream of the call unchanged.  A stream with the hand-off on and nothing bound refuses
+ * pushes and finish with CSS_ERR_STATE (frames are never dropped silently).  These refusals come before anything moves.  A
+ * CSS_ERR_STATE whose message starts with "hand-off:" after a call has run is an internal inconsistency (the device's frame
+ * counts against the host's range rule), not a refusal: the stream has moved, it is marked finished and only
+ * css_stream_close is left for it. */
+typedef struct CssStreamHandoffOut {
+    float* mel_host;        int64_t cap_frames;     /* [S][n_mels][cap_frames], raw                              */
+    int64_t* ranges_host;   int32_t cap_ranges;     /* [S][cap_ranges][2]                                        */
+    uint8_t* activity_host; int64_t cap_activity;   /* [S][cap_activity]; NULL: the gate bits are not wanted     */
+    int64_t* n_frames; int32_t* n_ranges; float* raw_max;   /* [S] each, out                                     */
+    int64_t n_activity, first_activity_frame;       /* out: frames in activity_host, and the first one's index   */
+} CssStreamHandoffOut;
+int css_stream_handoff_bind(css_handle_t h, int32_t id, CssStreamHandoffOut* out);   /* NULL unbinds */
+/* Pure host arithmetic: capacities that suffice for a push of n_samples (css_stream_finish: n_samples = -1). */
+int css_stream_handoff_bounds(const CssModelDesc* desc, const CssRunCfg* cfg, const CssStreamHandoffCfg* hcfg, int64_t n_samples,
+                              int64_t* frames, int32_t* ranges, int64_t* activity);
+/* Pure, drop_silence = 0 only: log-mel frames that are final after n_pushed samples of an open stream. */
+int css_stream_handoff_final_frames(const CssModelDesc* desc, const CssRunCfg* cfg, const CssStreamHandoffCfg* hcfg, int64_t n_pushed,
+                                    int64_t* n_frames);
+/* Pure host arithmetic, the range rule itself (what css_handoff_logmel and the streams run; 512 / 256 frames): act[i] is the gate
+ * bit of frame first_frame + i, the frames below n_known are known.  Appends to ranges [cap_ranges][2], which holds n_ranges_in
+ * ranges already, the sample ranges of [a, b) that the active frames keep with pad_frames (a range that touches the last one
+ * extends it) and sets *n_ranges.  Every frame from a / 256 - pad_frames - 2 on must be in act (CSS_ERR_INVALID_ARG otherwise, as
+ * for too little room).  css_handoff_logmel asks for [0, n_out) of all frames; a stream asks, round by round, for the samples
+ * [D before, D after) with the frames gated-final so far, and keeps the gate bits from t_g - 2 pad_frames - 3 on. */
+int css_handoff_kept_ranges(const uint8_t* act, int64_t first_frame, int64_t n_known, int32_t pad_frames, int64_t a, int64_t b,
+                            int64_t n_out, int64_t* ranges, int32_t n_ranges_in, int32_t cap_ranges, int32_t* n_ranges);
+/* Per handle: kernel launches of the hand-off in the last stream call (append + products + mel), the DFT products among
+ * them, and the frames of the products' operands.  A round of a call costs three launches whatever the number of streams
+ * (tables of 16 streams), one of them the product. */
+int css_stream_handoff_stats(css_handle_t h, int32_t* launches, int32_t* products, int64_t* frames);
 
 /* ---- buffer access for stage-level parity tests -------------------------------------------- */
 /* dims[0..3] (unused = 1) and element size of a buffer in the current session. */

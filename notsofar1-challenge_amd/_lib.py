@@ -90,6 +90,16 @@ class CssStreamGroupStats(C.Structure):
     _fields_ = [("estimator_batches", C.c_int32), ("estimator_segments", C.c_int64)]
 
 
+class CssStreamHandoffCfg(C.Structure):
+    _fields_ = [("n_mels", C.c_int32), ("pad_frames", C.c_int32), ("drop_silence", C.c_int32)]
+
+
+class CssStreamHandoffOut(C.Structure):
+    _fields_ = [("mel_host", C.c_void_p), ("cap_frames", C.c_int64), ("ranges_host", C.c_void_p), ("cap_ranges", C.c_int32),
+                ("activity_host", C.c_void_p), ("cap_activity", C.c_int64), ("n_frames", C.c_void_p), ("n_ranges", C.c_void_p),
+                ("raw_max", C.c_void_p), ("n_activity", C.c_int64), ("first_activity_frame", C.c_int64)]
+
+
 class CssKernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("ms", C.c_float), ("launches", C.c_int32)]
 
@@ -178,6 +188,15 @@ SIGNATURES = {
     "css_stream_close": (C.c_int, [_P, C.c_int32]),
     "css_stream_info": (C.c_int, [_P, C.c_int32, C.POINTER(CssStreamInfo)]),
     "css_stream_final_samples": (C.c_int, [C.POINTER(CssModelDesc), C.POINTER(CssRunCfg), C.c_int64, C.POINTER(C.c_int64)]),
+    "css_stream_handoff_open": (C.c_int, [_P, C.c_int32, C.POINTER(CssStreamHandoffCfg)]),
+    "css_stream_handoff_bind": (C.c_int, [_P, C.c_int32, C.POINTER(CssStreamHandoffOut)]),
+    "css_stream_handoff_bounds": (C.c_int, [C.POINTER(CssModelDesc), C.POINTER(CssRunCfg), C.POINTER(CssStreamHandoffCfg), C.c_int64,
+                                            C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "css_stream_handoff_final_frames": (C.c_int, [C.POINTER(CssModelDesc), C.POINTER(CssRunCfg), C.POINTER(CssStreamHandoffCfg), C.c_int64,
+                                                  C.POINTER(C.c_int64)]),
+    "css_handoff_kept_ranges": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int32, C.c_int32,
+                                          C.POINTER(C.c_int32)]),
+    "css_stream_handoff_stats": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "css_buffer_dims": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "css_read_buffer": (C.c_int, [_P, C.c_int, _P, C.c_int64]),
     "css_write_buffer": (C.c_int, [_P, C.c_int, _P, C.c_int64]),
@@ -291,6 +310,45 @@ def stream_final_samples(desc, run_cfg: RunCfg, n_pushed: int) -> int:
     rc = load().css_stream_final_samples(C.byref(make_desc(desc)), C.byref(run_cfg.c), int(n_pushed), C.byref(n))
     if rc != CSS_OK:
         raise CssError(rc, "css_stream_final_samples: unsupported frame geometry or bad configuration")
+    return int(n.value)
+
+
+def handoff_cfg(n_mels: int = 80, pad_frames: int = 8, drop_silence: bool = True) -> CssStreamHandoffCfg:
+    return CssStreamHandoffCfg(int(n_mels), int(pad_frames), int(bool(drop_silence)))
+
+
+def stream_handoff_bounds(desc, run_cfg: RunCfg, hcfg: CssStreamHandoffCfg, n_samples: int):
+    """css_stream_handoff_bounds: (frames, ranges, gate frames) that suffice for a push of `n_samples` (-1: finish)"""
+    f, r, a = C.c_int64(), C.c_int32(), C.c_int64()
+    rc = load().css_stream_handoff_bounds(C.byref(make_desc(desc)), C.byref(run_cfg.c), C.byref(hcfg), int(n_samples),
+                                          C.byref(f), C.byref(r), C.byref(a))
+    if rc != CSS_OK:
+        raise CssError(rc, "css_stream_handoff_bounds: bad configuration")
+    return int(f.value), int(r.value), int(a.value)
+
+
+def handoff_kept_ranges(act: np.ndarray, first_frame: int, n_known: int, pad_frames: int, a: int, b: int, n_out: int,
+                        ranges: Optional[np.ndarray] = None, cap: int = 4096) -> np.ndarray:
+    """css_handoff_kept_ranges: `ranges` [n, 2] (or None) extended by the sample ranges of [a, b) the gate bits keep"""
+    act = np.ascontiguousarray(act, dtype=np.uint8)
+    buf = np.zeros((cap, 2), np.int64)
+    n_in = 0 if ranges is None else int(len(ranges))
+    if n_in:
+        buf[:n_in] = ranges
+    n = C.c_int32()
+    rc = load().css_handoff_kept_ranges(_np_ptr(act), int(first_frame), int(n_known), int(pad_frames), int(a), int(b), int(n_out),
+                                        _np_ptr(buf), n_in, cap, C.byref(n))
+    if rc != CSS_OK:
+        raise CssError(rc, "css_handoff_kept_ranges: bad argument, a missing frame or too little room")
+    return buf[:n.value].copy()
+
+
+def stream_handoff_final_frames(desc, run_cfg: RunCfg, hcfg: CssStreamHandoffCfg, n_pushed: int) -> int:
+    """css_stream_handoff_final_frames (drop_silence = 0 only): log-mel frames that are final after `n_pushed` samples"""
+    n = C.c_int64()
+    rc = load().css_stream_handoff_final_frames(C.byref(make_desc(desc)), C.byref(run_cfg.c), C.byref(hcfg), int(n_pushed), C.byref(n))
+    if rc != CSS_OK:
+        raise CssError(rc, "css_stream_handoff_final_frames: bad configuration, or drop_silence is on")
     return int(n.value)
 
 
@@ -688,6 +746,12 @@ class Handle:
                                                   max_regions, C.byref(nreg)))
         del mel
         return flat[:n_mels * nfr.value].reshape(n_mels, nfr.value).copy(), regions[:nreg.value].copy()
+
+    def stream_handoff_stats(self):
+        """(hand-off launches, DFT products among them, operand frames) of the last stream call on this handle"""
+        a, b, c = C.c_int32(), C.c_int32(), C.c_int64()
+        check(self.h, self.lib.css_stream_handoff_stats(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        return int(a.value), int(b.value), int(c.value)
 
     def validation_loss(self, mix: np.ndarray, gt_spk0: np.ndarray, gt_noise0: np.ndarray, loss_name: str = "masked_mag",
                         base_loss: str = "mse", clip_gt_to_mixture: bool = False, noise_weight: float = 1.0):

@@ -273,6 +273,7 @@ struct css_ctx : SessState {
     int32_t prof_pairs = 0;
     FeatOpts feat_opts{};   // css_set_feature_options (css_create: the shipped configuration)
     void* streams[CSS_MAX_STREAMS] = {};   // css_stream_open: open streams (api_stream.hip StreamState), by id
+    void* handoff = nullptr;   // api_stream.hip: what the hand-off of streams shares on this handle (HandoffCtx), made on first use
     DevBuf stream_masks;   // api_stream.hip: the mask head's output for one estimator batch of streamed segments (never `masks`:
                            // the handle's own session keeps its bits between two pushes)
 
@@ -340,6 +341,28 @@ int check_frames(css_ctx* h, int64_t t_lo, int64_t t_hi);
 void istft_gemm_on(css_ctx* h, int64_t f_lo, int64_t f_hi, hipStream_t st);
 void wave_ola_on(css_ctx* h, int64_t f_lo, int64_t f_hi, int64_t q_lo, int64_t q_hi, float* out, int64_t out_ld, int64_t out_q0, hipStream_t st);
 int istft_impl(css_ctx* h, int64_t f_lo, int64_t f_hi, int64_t q_lo, int64_t q_hi, float* out, int64_t out_ld, int64_t out_q0, hipStream_t st);
+
+// Sample ranges of [a, b) that the gate keeps, appended to `reg` (pairs; a range that touches reg's last one extends it):
+// act[i] is the gate byte of frame t0 + i, frames below t_known are known; a run of active frames [t, e) keeps the samples
+// [max(t - pad, 0) hop, min((e - 1 + pad) hop + N, n_out)).  The frames that can keep a sample of [a, b) must be known.
+// css_handoff_logmel asks for [0, n_out) of a finished pass, a stream for the samples a push decided.
+inline void handoff_kept_ranges(const uint8_t* act, int64_t t0, int64_t t_known, int pad, int hop, int N, int64_t a, int64_t b,
+                                int64_t n_out, std::vector<int64_t>& reg) {
+    const int64_t t_lo = std::max<int64_t>(std::max<int64_t>(a / hop - pad - N / hop, 0), t0);
+    const int64_t t_hi = std::min<int64_t>(t_known, (b + hop - 1) / hop + pad);
+    for (int64_t t = t_lo; t < t_hi;) {
+        if (!act[(size_t)(t - t0)]) { ++t; continue; }
+        int64_t e = t;
+        while (e < t_hi && act[(size_t)(e - t0)]) ++e;
+        const int64_t ra = std::max(std::max<int64_t>(t - pad, 0) * hop, a);
+        const int64_t rb = std::min(std::min<int64_t>((e - 1 + pad) * hop + N, n_out), b);
+        if (rb > ra) {
+            if (!reg.empty() && ra <= reg.back()) reg.back() = std::max(reg.back(), rb);
+            else { reg.push_back(ra); reg.push_back(rb); }
+        }
+        t = e;
+    }
+}
 
 // ---- api_stream.hip
 void stream_destroy_all(css_ctx* h);

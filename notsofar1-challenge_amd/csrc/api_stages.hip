@@ -900,15 +900,7 @@ int css_handoff_logmel(css_handle_t h, const float* wav_dev, int64_t wav_ld, int
     if (!drop_silence) {
         reg = {0, n_out};
     } else {
-        for (int64_t t = 0; t < TL;) {
-            if (!act[(size_t)t]) { ++t; continue; }
-            int64_t e = t;
-            while (e < TL && act[(size_t)e]) ++e;
-            const int64_t a = std::max<int64_t>(t - pad_frames, 0) * hop, b = std::min<int64_t>((e - 1 + pad_frames) * hop + N, n_out);
-            if (!reg.empty() && a <= reg.back()) reg.back() = std::max(reg.back(), b);
-            else { reg.push_back(a); reg.push_back(b); }
-            t = e;
-        }
+        handoff_kept_ranges(act.data(), 0, TL, pad_frames, hop, N, 0, n_out, n_out, reg);
     }
     const int nr = (int)(reg.size() / 2);
     *n_regions = nr;

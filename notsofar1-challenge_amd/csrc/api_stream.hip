@@ -18,6 +18,11 @@
 // in all streams of one segmentation pass the estimator as ONE batch (every estimator kernel is batch invariant in exact
 // float32, as for queued sessions: api_queue.hip run_group), so N live meetings cost about one estimator pass per tick
 // instead of N.  css_stream_push is a group of one item; css_stream_finish runs the same segments() / tail() with one job.
+//
+// The hand-off (css_stream_handoff_*): a stream that has it switched on also returns, with every call, the gate
+// bits, the kept sample ranges and the raw Whisper log-mel frames that became final.  The step sits between tail() and the
+// downloads of a round: three launches for all streams of the round (handoff.hip: append, ONE DFT product, mel), results
+// into page-locked staging under the call's final synchronise, where the host trims them into the caller's buffers.
 #include "api_ctx.hpp"
 
 #include <climits>
@@ -26,7 +31,35 @@ namespace {
 
 constexpr int PIECE_SEGMENTS = 8;
 
+// Per stream with the hand-off on.  Nothing here is part of the window: the rebase never touches it.
+struct HandoffStream {
+    CssStreamHandoffCfg cfg{};
+    int pad = 0;                        // pad_frames with drop_silence, else 0 (nothing waits for the gate)
+    CssStreamHandoffOut* bound = nullptr;
+    // gate ring [S][gate_ld] (frame t at t & gate_mask); undecided samples and concatenation tail in two generations
+    DevBuf gate, carry[2], tail[2];
+    int64_t gate_ld = 0, gate_mask = 0, carry_ld = 1;
+    int cur = 0;
+    int64_t D = 0;                      // decided samples
+    // host mirrors: gate bytes of frames [hist_base, t_g) per speaker, samples appended, frames emitted, running maximum
+    std::vector<std::vector<uint8_t>> hist;
+    int64_t hist_base = 0;
+    std::vector<int64_t> A, J;
+    std::vector<float> raw_max;
+};
+
+// Per handle, made when the first stream switches the hand-off on.
+struct HandoffCtx {
+    DevBuf tab, operand, spec, res, state;   // DFT matrix + both filterbanks; frame operand; spectra; a round's results; HandoffState per (id, k)
+    struct Pinned { void* p = nullptr; size_t cap = 0; };
+    std::vector<Pinned> pinned;              // staging of round r of a call
+    int32_t launches = 0, products = 0;
+    int64_t frames = 0;
+};
+constexpr size_t HO_DFT_F = (size_t)402 * 416, HO_MEL80_F = (size_t)80 * 201, HO_MEL128_F = (size_t)128 * 201;
+
 struct StreamState {
+    HandoffStream* ho = nullptr;
     CssRunCfg cfg{};
     std::vector<float> w;          // the three windows (cfg.w_* point here)
     int n_ch = 0, T = 0, hop = 0, halo = 0;
@@ -61,6 +94,11 @@ void free_stream(StreamState* s) {
             if (d->p) hipFree(d->p);
     for (DevBuf* d : {&s->scm, &s->bfw, &s->pnorm, &s->costs, &s->pit_part, &s->Y, &s->out, &s->segw})
         if (d->p) hipFree(d->p);
+    if (s->ho) {
+        for (DevBuf* d : {&s->ho->gate, &s->ho->carry[0], &s->ho->carry[1], &s->ho->tail[0], &s->ho->tail[1]})
+            if (d->p) hipFree(d->p);
+        delete s->ho;
+    }
     delete s;
 }
 
@@ -69,6 +107,10 @@ int64_t device_bytes(const StreamState* s) {
     for (int b = 0; b < 2; ++b)
         for (const DevBuf* d : {&s->pcm[b], &s->X[b], &s->masks[b], &s->sep[b], &s->perms[b], &s->act_b[b], &s->G[b]}) n += (int64_t)d->cap;
     for (const DevBuf* d : {&s->scm, &s->bfw, &s->pnorm, &s->costs, &s->pit_part, &s->Y, &s->out, &s->segw}) n += (int64_t)d->cap;
+    if (s->ho) {
+        for (const DevBuf* d : {&s->ho->gate, &s->ho->carry[0], &s->ho->carry[1], &s->ho->tail[0], &s->ho->tail[1]}) n += (int64_t)d->cap;
+        n += (int64_t)(SMAX * sizeof(HandoffState));
+    }
     return n;
 }
 
@@ -113,6 +155,7 @@ StreamStitchArgs stitch_view(css_ctx* h, StreamState* s, bool closing, int64_t n
     a.Y = (float*)s->Y.p; a.KIp = h->KIp;
     a.ld_frames = s->WF;
     a.activity_th = s->cfg.activity_th; a.dilation = s->cfg.dilation_frames; a.erosion = s->cfg.erosion_frames;
+    if (s->ho) { a.gate_out = (uint8_t*)s->ho->gate.p; a.gate_ld = s->ho->gate_ld; a.gate_mask = s->ho->gate_mask; }
     return a;
 }
 
@@ -312,6 +355,216 @@ int download(css_ctx* h, StreamState* s, int64_t n, float* out_host, int64_t cap
     return CSS_OK;
 }
 
+// ---- hand-off ----------------------------------------------------------------------------------------------------------
+// Capacities that suffice for one call.  A push of n samples adds at most n / 256 + 1 frames to the transform, hence at most
+// that plus hop_frames to the segments' frames, the gated-final frames and the decided blocks; finish decides what is left:
+// fewer than T + halo + pad + 2 blocks (t_g >= K - T - halo, n_out = (max(K, T) + 1) blocks).  J frames need 160 J + 40
+// samples, so a call that appends dn samples completes at most dn / 160 + 1 frames -- (dn + 200) / 160 + 1 at finish, which
+// also emits the frames the trailing reflection completes.  Two ranges of a call have a dropped block between them.
+struct HandoffNeed { int64_t frames; int32_t ranges; int64_t activity; };
+HandoffNeed handoff_need(int T, int hop, int halo, const CssStreamHandoffCfg& c, int64_t n_samples) {
+    const int pad = c.drop_silence ? c.pad_frames : 0;
+    const int64_t blocks = n_samples < 0 ? (int64_t)T + hop + halo + pad + 3 : n_samples / 256 + 1 + hop;
+    HandoffNeed n;
+    n.frames = (blocks * 256 + 200) / 160 + 2;
+    n.ranges = c.drop_silence ? (int32_t)std::min<int64_t>(blocks / 2 + 1, INT32_MAX) : 1;
+    n.activity = blocks;
+    return n;
+}
+// frames of the operand a round reserves for one speaker that appends at most dn samples: the frames it can complete, the
+// rows the last frame's 416 columns reach into, and the gap to the next owner
+int64_t handoff_rows(int64_t dn) { return (dn + 200) / 160 + 2 + 3; }
+
+int check_handoff_cfg(const CssStreamHandoffCfg* c) {
+    if (!c || (c->n_mels != 80 && c->n_mels != 128) || c->pad_frames < 0 || c->pad_frames > 4096) return CSS_ERR_INVALID_ARG;
+    return CSS_OK;
+}
+
+// what a call must find bound to a stream with the hand-off on
+int check_handoff_call(css_ctx* h, const StreamState* s, int64_t n_samples, std::string* why) {
+    if (!s->ho) return CSS_OK;
+    const CssStreamHandoffOut* o = s->ho->bound;
+    if (!o) { *why = "the hand-off is on and nothing is bound (css_stream_handoff_bind)"; return CSS_ERR_STATE; }
+    const HandoffNeed n = handoff_need(s->T, s->hop, s->halo, s->ho->cfg, n_samples);
+    if (!o->mel_host || !o->ranges_host || !o->n_frames || !o->n_ranges || !o->raw_max || o->cap_frames < n.frames ||
+        o->cap_ranges < n.ranges || (o->activity_host && o->cap_activity < n.activity)) {
+        *why = "hand-off capacities below css_stream_handoff_bounds for this call";
+        return CSS_ERR_INVALID_ARG;
+    }
+    return CSS_OK;
+}
+
+HandoffCtx* handoff_ctx(css_ctx* h) { return static_cast<HandoffCtx*>(h->handoff); }
+
+void handoff_begin_call(css_ctx* h) {
+    if (HandoffCtx* c = handoff_ctx(h)) { c->launches = c->products = 0; c->frames = 0; }
+}
+
+// One stream's share of a round's hand-off: frames [t_g0, t_g1) became gated-final, the output buffer holds out_ld samples per
+// speaker from sample t_g0 * hop on.  HandoffRec is what the host needs after the call's synchronise to hand the round's results out.
+struct HandoffJob { StreamState* s; int item; int64_t t_g0, t_g1, out_ld; bool closing; int64_t n_out; };
+struct HandoffRec {
+    StreamState* s; int item; int64_t t_g0, t_g1, D0, D1, n_out; bool closing;
+    const uint8_t* act; const int32_t* n_new; const float* mel; int64_t mel_ld; const HandoffState* st;   // in page-locked staging
+};
+
+int handoff_round(css_ctx* h, const std::vector<HandoffJob>& all, size_t round, std::vector<HandoffRec>* recs) {
+    HandoffCtx* c = handoff_ctx(h);
+    std::vector<HandoffJob> jobs;
+    for (const HandoffJob& j : all)
+        if (j.s->ho && (j.t_g1 > j.t_g0 || j.closing)) jobs.push_back(j);
+    if (jobs.empty() || !c) return CSS_OK;
+    const int S = h->d.num_spks, hopS = h->d.frame_hop;
+    const size_t n = jobs.size();
+    std::vector<HandoffAppend> ap(n);
+    std::vector<HandoffMel> me(n);
+    std::vector<size_t> act_off(n), new_off(n), mel_off(n);
+    int64_t rows_total = 0;
+    size_t res_b = 0;
+    auto al = [](size_t v) { return (v + 63) / 64 * 64; };
+    for (size_t i = 0; i < n; ++i) {
+        const HandoffJob& j = jobs[i];
+        HandoffStream* o = j.s->ho;
+        const int64_t D1 = j.closing ? j.n_out : std::max<int64_t>(j.t_g1 - o->pad, 0) * hopS;
+        HandoffAppend& a = ap[i];
+        a = HandoffAppend{};
+        a.gate = (const uint8_t*)o->gate.p; a.gate_ld = o->gate_ld; a.gate_mask = o->gate_mask;
+        a.out = (const float*)j.s->out.p; a.out_ld = j.out_ld; a.out_base = j.t_g0 * hopS;
+        a.carry_in = (const float*)o->carry[o->cur].p; a.carry_out = (float*)o->carry[1 - o->cur].p; a.carry_ld = o->carry_ld;
+        a.tail_in = (const float*)o->tail[o->cur].p; a.tail_out = (float*)o->tail[1 - o->cur].p;
+        a.t_g0 = j.t_g0; a.t_g1 = j.t_g1; a.D0 = o->D; a.D1 = D1;
+        a.pad = o->pad; a.drop = o->cfg.drop_silence ? 1 : 0; a.closing = j.closing ? 1 : 0; a.S = S;
+        a.rows = handoff_rows(D1 - o->D); a.row0 = rows_total;
+        rows_total += a.rows * S;
+        act_off[i] = res_b; res_b = al(res_b + (size_t)S * (size_t)(j.t_g1 - j.t_g0));
+        new_off[i] = res_b; res_b = al(res_b + (size_t)S * sizeof(int32_t));
+        mel_off[i] = res_b; res_b = al(res_b + (size_t)S * o->cfg.n_mels * (size_t)a.rows * sizeof(float));
+    }
+    const size_t state_b = (size_t)CSS_MAX_STREAMS * SMAX * sizeof(HandoffState);
+    const int64_t ld = (rows_total + 3) / 4 * 4;
+    int rc;
+    // The product reads 416 columns from every row; columns 400 .. 415 meet zeros of the matrix, so what they read only has to
+    // be finite.  The append kernel rewrites ALL rows of every owner each round, the floats behind the last row are zeros
+    // from the allocation or finite values an earlier, larger round left there.
+    if ((rc = ensure(h, c->operand, ((size_t)rows_total * 160 + 1024) * sizeof(float), true)) != CSS_OK) return rc;
+    if ((rc = ensure(h, c->spec, (size_t)402 * ld * sizeof(float))) != CSS_OK) return rc;
+    if ((rc = ensure(h, c->res, res_b)) != CSS_OK) return rc;
+    if (c->pinned.size() <= round) c->pinned.resize(round + 1);
+    HandoffCtx::Pinned& pin = c->pinned[round];
+    if (pin.cap < res_b + state_b) {
+        if (pin.p) HIPCHK(h, hipHostFree(pin.p));
+        pin = HandoffCtx::Pinned{};
+        HIPCHK(h, hipHostMalloc(&pin.p, res_b + state_b, hipHostMallocDefault));
+        pin.cap = res_b + state_b;
+    }
+    const float* dftm = (const float*)c->tab.p;
+    for (size_t i = 0; i < n; ++i) {
+        const HandoffJob& j = jobs[i];
+        HandoffStream* o = j.s->ho;
+        int id = 0;
+        while (h->streams[id] != j.s) ++id;
+        HandoffState* st = (HandoffState*)c->state.p + (size_t)id * SMAX;
+        ap[i].st = st;
+        ap[i].act_out = (uint8_t*)c->res.p + act_off[i];
+        ap[i].n_new = (int32_t*)((char*)c->res.p + new_off[i]);
+        me[i] = HandoffMel{ap[i].row0, ap[i].rows, ap[i].n_new, st, dftm + HO_DFT_F + (o->cfg.n_mels == 80 ? 0 : HO_MEL80_F), o->cfg.n_mels,
+                           (float*)((char*)c->res.p + mel_off[i]), ap[i].rows};
+        HandoffRec r{};
+        r.s = j.s; r.item = j.item; r.t_g0 = j.t_g0; r.t_g1 = j.t_g1; r.D0 = ap[i].D0; r.D1 = ap[i].D1; r.n_out = j.n_out; r.closing = j.closing;
+        r.act = (const uint8_t*)pin.p + act_off[i];
+        r.n_new = (const int32_t*)((const char*)pin.p + new_off[i]);
+        r.mel = (const float*)((const char*)pin.p + mel_off[i]);
+        r.mel_ld = ap[i].rows;
+        r.st = (const HandoffState*)((const char*)pin.p + res_b) + (size_t)id * SMAX;
+        recs->push_back(r);
+        o->D = ap[i].D1;
+        o->cur = 1 - o->cur;
+    }
+    launch_handoff_append_multi(ap.data(), (int)n, (float*)c->operand.p, h->stream);
+    GemmArgs g{};
+    g.A = dftm; g.lda = 416; g.B = (const float*)c->operand.p; g.ldb = 160; g.C = (float*)c->spec.p; g.ldc = ld;
+    g.M = 402; g.N = (int)rows_total; g.K = 416; g.batch = 1; g.alpha = 1.f;
+    launch_gemm(g, h->stream);
+    launch_handoff_mel_multi(me.data(), (int)n, S, (const float*)c->spec.p, ld, h->stream);
+    const int tables = (int)((n + HANDOFF_MULTI_MAX - 1) / HANDOFF_MULTI_MAX);
+    c->launches += 2 * tables + 1; c->products += 1; c->frames += rows_total;
+    HIPCHK(h, hipMemcpyAsync(pin.p, c->res.p, res_b, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync((char*)pin.p + res_b, c->state.p, state_b, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipGetLastError());
+    return CSS_OK;
+}
+
+// After the call's synchronise: the rounds' results of ONE stream, in order, trimmed into what is bound to it.
+int handoff_collect(css_ctx* h, StreamState* s, int item, int64_t t_g_before, const std::vector<HandoffRec>& recs) {
+    HandoffStream* o = s->ho;
+    CssStreamHandoffOut* out = o->bound;
+    const int S = h->d.num_spks, hopS = h->d.frame_hop, N = h->d.frame_len, nm = o->cfg.n_mels;
+    std::vector<std::vector<int64_t>> reg((size_t)S);
+    std::vector<int64_t> nfr((size_t)S, 0);
+    int64_t n_act = 0;
+    for (const HandoffRec& r : recs) {
+        if (r.s != s || r.item != item) continue;
+        const int64_t nt = r.t_g1 - r.t_g0;
+        for (int k = 0; k < S; ++k) {
+            std::vector<uint8_t>& hist = o->hist[(size_t)k];
+            hist.insert(hist.end(), r.act + (size_t)k * nt, r.act + (size_t)(k + 1) * nt);
+            if (out->activity_host && nt > 0)
+                std::memcpy(out->activity_host + (size_t)k * out->cap_activity + n_act, r.act + (size_t)k * nt, (size_t)nt);
+            std::vector<int64_t>& g = reg[(size_t)k];
+            const size_t before = g.size();
+            const int64_t last_end = before ? g.back() : -1;
+            if (!o->cfg.drop_silence) {
+                if (r.D1 > r.D0) {
+                    if (before && g.back() == r.D0) g.back() = r.D1;
+                    else { g.push_back(r.D0); g.push_back(r.D1); }
+                }
+            } else {
+                handoff_kept_ranges(hist.data(), o->hist_base, r.t_g1, o->pad, hopS, N, r.D0, r.D1, r.closing ? r.n_out : INT64_MAX, g);
+            }
+            int64_t added = 0;   // samples this round appended: the new ranges, and what the last old one grew by
+            for (size_t i = before; i + 1 < g.size(); i += 2) added += g[i + 1] - g[i];
+            if (before) added += g[before - 1] - last_end;
+            const int64_t A1 = o->A[(size_t)k] + added;
+            const int64_t J1 = r.closing ? A1 / 160 : (A1 >= 201 ? (A1 - 200) / 160 + 1 : 0);
+            const int64_t nj = J1 - o->J[(size_t)k];
+            // internal consistency, not refusals: the stream has moved already, so it ends here (only css_stream_close is left)
+            if (nj != r.n_new[k] || r.st[k].A != A1 || r.st[k].J != J1) {
+                s->finished = true;
+                return fail(h, CSS_ERR_STATE, "hand-off: the device's counts differ from the host's range rule; the stream is closed to further calls");
+            }
+            if (nfr[(size_t)k] + nj > out->cap_frames || (int64_t)(g.size() / 2) > out->cap_ranges) {
+                s->finished = true;
+                return fail(h, CSS_ERR_STATE, "hand-off: the bound capacities were exceeded; the stream is closed to further calls");
+            }
+            for (int m = 0; m < nm && nj > 0; ++m)
+                std::memcpy(out->mel_host + ((size_t)k * nm + m) * out->cap_frames + nfr[(size_t)k],
+                            r.mel + ((size_t)k * nm + m) * r.mel_ld, (size_t)nj * sizeof(float));
+            nfr[(size_t)k] += nj;
+            o->A[(size_t)k] = A1; o->J[(size_t)k] = J1;
+            const int b = r.st[k].gmax;
+            const int bits = b >= 0 ? b : b ^ 0x7fffffff;
+            std::memcpy(&o->raw_max[(size_t)k], &bits, sizeof(float));
+        }
+        n_act += nt;
+        // frames that can still keep an undecided sample: from t_g - 2 pad - 2 on
+        const int64_t keep_from = std::max<int64_t>(r.t_g1 - 2 * (int64_t)o->pad - 3, o->hist_base);
+        if (keep_from > o->hist_base) {
+            for (int k = 0; k < S; ++k) o->hist[(size_t)k].erase(o->hist[(size_t)k].begin(), o->hist[(size_t)k].begin() + (keep_from - o->hist_base));
+            o->hist_base = keep_from;
+        }
+    }
+    for (int k = 0; k < S; ++k) {
+        const std::vector<int64_t>& g = reg[(size_t)k];
+        std::memcpy(out->ranges_host + (size_t)k * out->cap_ranges * 2, g.data(), g.size() * sizeof(int64_t));
+        out->n_ranges[k] = (int32_t)(g.size() / 2);
+        out->n_frames[k] = nfr[(size_t)k];
+        out->raw_max[k] = o->raw_max[(size_t)k];
+    }
+    out->n_activity = n_act;
+    out->first_activity_frame = t_g_before;
+    return CSS_OK;
+}
+
 int check_stream_call(css_ctx* h, int32_t id, StreamState** out) {
     if (!h) return CSS_ERR_INVALID_ARG;
     StreamState* s = get_stream(h, id);
@@ -329,6 +582,14 @@ void stream_destroy_all(css_ctx* h) {
         if (h->streams[i]) { free_stream(static_cast<StreamState*>(h->streams[i])); h->streams[i] = nullptr; }
     if (h->stream_masks.p) hipFree(h->stream_masks.p);
     h->stream_masks = DevBuf{};
+    if (HandoffCtx* c = handoff_ctx(h)) {
+        for (DevBuf* d : {&c->tab, &c->operand, &c->spec, &c->res, &c->state})
+            if (d->p) hipFree(d->p);
+        for (HandoffCtx::Pinned& p : c->pinned)
+            if (p.p) hipHostFree(p.p);
+        delete c;
+        h->handoff = nullptr;
+    }
 }
 int stream_open_count(const css_ctx* h) {
     int n = 0;
@@ -418,7 +679,7 @@ int css_stream_open(css_handle_t h, const CssRunCfg* cfg, int32_t n_ch, int32_t*
 int css_stream_push_many(css_handle_t h, CssStreamPush* items, int32_t n_items, CssStreamGroupStats* stats) {
     if (!h) return CSS_ERR_INVALID_ARG;
     if (n_items < 0 || (n_items > 0 && !items)) return fail(h, CSS_ERR_INVALID_ARG, "bad argument");
-    struct Item { StreamState* s; CssStreamPush* p; int64_t done, emitted, n, t_g1; };
+    struct Item { StreamState* s; CssStreamPush* p; int64_t done, emitted, n, t_g1, t_g_before; };
     std::vector<Item> its((size_t)n_items);
     for (int32_t i = 0; i < n_items; ++i) {
         CssStreamPush& p = items[i];
@@ -439,19 +700,33 @@ int css_stream_push_many(css_handle_t h, CssStreamPush* items, int32_t n_items, 
             return refuse(CSS_ERR_INVALID_ARG, "output capacity too small for the samples this push finalises");
         if (zero_weight_frames(s, s->t_st, segments_done(frames_of(s->n_pushed + p.n_samples), s->T, s->hop) * s->hop))
             return refuse(CSS_ERR_ZERO_WEIGHT, "zero weights found. check hop_size, segment_size or m0, m1");
-        its[(size_t)i] = Item{s, &p, 0, 0, 0, 0};
+        std::string why;
+        const int hrc = check_handoff_call(h, s, p.n_samples, &why);
+        if (hrc != CSS_OK) return refuse(hrc, why);
+        its[(size_t)i] = Item{s, &p, 0, 0, 0, 0, s->t_g};
     }
     if (stats) *stats = CssStreamGroupStats{};
+    handoff_begin_call(h);
+    std::vector<HandoffJob> hj;
+    std::vector<HandoffRec> recs;
+    auto hand_out = [&]() {   // (a call that moved nothing still reports its empty hand-off)
+        for (size_t i = 0; i < its.size(); ++i)
+            if (its[i].s->ho) {
+                const int hrc = handoff_collect(h, its[i].s, (int)i, its[i].t_g_before, recs);
+                if (hrc != CSS_OK) return hrc;
+            }
+        return (int)CSS_OK;
+    };
     bool any = false;
     for (Item& it : its) { it.p->n_out = 0; any = any || it.p->n_samples > 0; }
-    if (!any) return CSS_OK;
+    if (!any) return hand_out();
     HIPCHK(h, hipSetDevice(h->device));
     const int hopS = h->d.frame_hop;
     int rc;
     std::vector<Item*> act;
     std::vector<SegJob> sj;
     std::vector<TailJob> tj;
-    for (;;) {
+    for (size_t round = 0;; ++round) {
         act.clear();
         for (Item& it : its)
             if (it.done < it.p->n_samples) act.push_back(&it);
@@ -500,6 +775,10 @@ int css_stream_push_many(css_handle_t h, CssStreamPush* items, int32_t n_items, 
         if ((rc = segments(h, sj, stats)) != CSS_OK) return rc;
         for (const SegJob& j : sj) j.s->sd = j.g_hi;
         if ((rc = tail(h, tj)) != CSS_OK) return rc;
+        hj.clear();
+        for (Item* it : act)
+            if (it->s->ho) hj.push_back(HandoffJob{it->s, (int)(it - its.data()), it->s->t_g, it->t_g1, (it->t_g1 - it->s->t_g) * hopS, false, 0});
+        if ((rc = handoff_round(h, hj, round, &recs)) != CSS_OK) return rc;
         for (Item* it : act) {
             StreamState* s = it->s;
             const int64_t n_new = (it->t_g1 - s->t_g) * hopS;
@@ -515,7 +794,7 @@ int css_stream_push_many(css_handle_t h, CssStreamPush* items, int32_t n_items, 
         it.s->n_emitted += it.emitted;
         it.p->n_out = it.emitted;
     }
-    return CSS_OK;
+    return hand_out();
 }
 
 // a group of one item
@@ -540,6 +819,11 @@ int css_stream_finish(css_handle_t h, int32_t id, float* out_host, int64_t cap, 
     if (p.zero_weight) return fail(h, CSS_ERR_ZERO_WEIGHT, "zero weights found. check hop_size, segment_size or m0, m1");
     const int64_t need = p.n_out - s->n_emitted;
     if (!out_host || cap < need) return fail(h, CSS_ERR_INVALID_ARG, "output capacity too small for the rest of the stream");
+    std::string why;
+    if ((rc = check_handoff_call(h, s, -1, &why)) != CSS_OK) return fail(h, rc, why);
+    handoff_begin_call(h);
+    std::vector<HandoffRec> recs;
+    const int64_t t_g_before = s->t_g;
     HIPCHK(h, hipSetDevice(h->device));
     const int64_t TL = p.mix_frames, nseg = p.num_segments, fb = s->seg_base * s->hop;
     if (TL - fb > s->WF || nseg - s->seg_base > s->SC) return fail(h, CSS_ERR_STATE, "stream window overflow");
@@ -555,8 +839,10 @@ int css_stream_finish(css_handle_t h, int32_t id, float* out_host, int64_t cap, 
         if ((rc = ensure(h, s->out, (size_t)h->d.num_spks * (q_hi - s->t_g) * h->d.frame_hop * sizeof(float))) != CSS_OK) return rc;
     }
     if ((rc = tail(h, {TailJob{s, true, nseg, TL, s->t_st, TL, s->t_g, TL, q_hi}})) != CSS_OK) return rc;
+    if ((rc = handoff_round(h, {HandoffJob{s, 0, s->t_g, TL, (q_hi - s->t_g) * h->d.frame_hop, true, p.n_out}}, 0, &recs)) != CSS_OK) return rc;
     if ((rc = download(h, s, need, out_host, cap, 0)) != CSS_OK) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (s->ho && (rc = handoff_collect(h, s, 0, t_g_before, recs)) != CSS_OK) return rc;
     s->sd = nseg; s->t_st = s->t_g = TL;
     s->n_emitted += need;
     s->finished = true;
@@ -584,5 +870,117 @@ int css_stream_info(css_handle_t h, int32_t id, CssStreamInfo* out) {
     out->max_lag = (int64_t)(s->T + s->halo + 2) * h->d.frame_hop + h->d.frame_len;
     out->device_bytes = device_bytes(s);
     out->finished = s->finished ? 1 : 0;
+    return CSS_OK;
+}
+
+// ---- hand-off entry points ------------------------------------------------------------------------------------------------
+int css_stream_handoff_bounds(const CssModelDesc* desc, const CssRunCfg* cfg, const CssStreamHandoffCfg* hcfg, int64_t n_samples,
+                              int64_t* frames, int32_t* ranges, int64_t* activity) {
+    if (!desc || !frames || !ranges || !activity || n_samples < -1) return CSS_ERR_INVALID_ARG;
+    int rc = check_cfg(*desc, cfg);
+    if (rc == CSS_OK) rc = check_handoff_cfg(hcfg);
+    if (rc != CSS_OK) return rc;
+    const HandoffNeed n = handoff_need(cfg->segment_frames, cfg->hop_frames, cfg->dilation_frames + cfg->erosion_frames, *hcfg, n_samples);
+    *frames = n.frames; *ranges = n.ranges; *activity = n.activity;
+    return CSS_OK;
+}
+
+int css_stream_handoff_final_frames(const CssModelDesc* desc, const CssRunCfg* cfg, const CssStreamHandoffCfg* hcfg, int64_t n_pushed,
+                                    int64_t* n_frames) {
+    if (!desc || !n_frames || n_pushed < 0) return CSS_ERR_INVALID_ARG;
+    int rc = check_cfg(*desc, cfg);
+    if (rc == CSS_OK) rc = check_handoff_cfg(hcfg);
+    if (rc != CSS_OK) return rc;
+    if (hcfg->drop_silence) return CSS_ERR_INVALID_ARG;   // with the gate in play the count depends on the audio
+    const int64_t fin = final_frames(n_pushed, cfg->segment_frames, cfg->hop_frames, cfg->dilation_frames + cfg->erosion_frames) * desc->frame_hop;
+    *n_frames = fin >= 201 ? (fin - 200) / 160 + 1 : 0;
+    return CSS_OK;
+}
+
+int css_stream_handoff_open(css_handle_t h, int32_t id, const CssStreamHandoffCfg* cfg) {
+    StreamState* s = nullptr;
+    int rc = check_stream_call(h, id, &s);
+    if (rc != CSS_OK) return rc;
+    if (check_handoff_cfg(cfg) != CSS_OK) return fail(h, CSS_ERR_INVALID_ARG, "n_mels is 80 or 128, pad_frames 0 .. 4096");
+    if (s->ho) return fail(h, CSS_ERR_STATE, "the hand-off of this stream is on already");
+    if (s->n_pushed > 0 || s->finished) return fail(h, CSS_ERR_STATE, "the hand-off is switched on before the stream's first sample");
+    HIPCHK(h, hipSetDevice(h->device));
+    const int S = h->d.num_spks;
+    HandoffCtx* c = handoff_ctx(h);
+    if (!c) {
+        c = new HandoffCtx();
+        h->handoff = c;
+    }
+    if (!c->tab.p || !c->state.p) {
+        std::vector<float> t(HO_DFT_F + HO_MEL80_F + HO_MEL128_F, 0.f);
+        handoff_build_dft(t.data());
+        handoff_build_mel(t.data() + HO_DFT_F, 80);
+        handoff_build_mel(t.data() + HO_DFT_F + HO_MEL80_F, 128);
+        if ((rc = ensure(h, c->state, (size_t)CSS_MAX_STREAMS * SMAX * sizeof(HandoffState), true)) != CSS_OK) return rc;
+        if ((rc = ensure(h, c->tab, t.size() * sizeof(float))) != CSS_OK) return rc;
+        HIPCHK(h, hipMemcpy(c->tab.p, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    HandoffStream* o = new HandoffStream();
+    o->cfg = *cfg;
+    o->cfg.drop_silence = cfg->drop_silence ? 1 : 0;
+    o->pad = o->cfg.drop_silence ? cfg->pad_frames : 0;
+    // the ring holds a round's frames (at most the window) and the 2 pad + 2 frames before them that can keep its blocks
+    int64_t ring = 64;
+    while (ring < s->WF + 2 * (int64_t)o->pad + 8) ring *= 2;
+    o->gate_ld = ring; o->gate_mask = ring - 1;
+    o->carry_ld = std::max<int64_t>((int64_t)o->pad * h->d.frame_hop, 1);
+    rc = ensure(h, o->gate, (size_t)S * ring, true);
+    for (int b = 0; b < 2 && rc == CSS_OK; ++b) {
+        rc = ensure(h, o->carry[b], (size_t)S * o->carry_ld * sizeof(float), true);
+        if (rc == CSS_OK) rc = ensure(h, o->tail[b], (size_t)S * HANDOFF_TAIL_LD * sizeof(float), true);
+    }
+    std::vector<HandoffState> init((size_t)SMAX, HandoffState{0, 0, HANDOFF_GMAX_NONE, 0});
+    hipError_t e = hipSuccess;
+    if (rc == CSS_OK) {
+        e = hipMemcpyAsync((HandoffState*)c->state.p + (size_t)id * SMAX, init.data(), init.size() * sizeof(HandoffState), hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    }
+    if (rc != CSS_OK || e != hipSuccess) {
+        for (DevBuf* d : {&o->gate, &o->carry[0], &o->carry[1], &o->tail[0], &o->tail[1]})
+            if (d->p) hipFree(d->p);
+        delete o;
+        return rc != CSS_OK ? rc : fail(h, CSS_ERR_HIP, std::string("hand-off setup: ") + hipGetErrorString(e));
+    }
+    o->hist.assign((size_t)S, std::vector<uint8_t>());
+    o->A.assign((size_t)S, 0); o->J.assign((size_t)S, 0);
+    o->raw_max.assign((size_t)S, -INFINITY);
+    s->ho = o;
+    return CSS_OK;
+}
+
+int css_stream_handoff_bind(css_handle_t h, int32_t id, CssStreamHandoffOut* out) {
+    if (!h) return CSS_ERR_INVALID_ARG;
+    StreamState* s = get_stream(h, id);
+    if (!s) return fail(h, CSS_ERR_INVALID_ARG, "no open stream with this id");
+    if (!s->ho) return fail(h, CSS_ERR_STATE, "the hand-off of this stream is off (css_stream_handoff_open)");
+    s->ho->bound = out;
+    return CSS_OK;
+}
+
+int css_stream_handoff_stats(css_handle_t h, int32_t* launches, int32_t* products, int64_t* frames) {
+    if (!h) return CSS_ERR_INVALID_ARG;
+    const HandoffCtx* c = handoff_ctx(h);
+    if (launches) *launches = c ? c->launches : 0;
+    if (products) *products = c ? c->products : 0;
+    if (frames) *frames = c ? c->frames : 0;
+    return CSS_OK;
+}
+
+int css_handoff_kept_ranges(const uint8_t* act, int64_t first_frame, int64_t n_known, int32_t pad_frames, int64_t a, int64_t b,
+                            int64_t n_out, int64_t* ranges, int32_t n_ranges_in, int32_t cap_ranges, int32_t* n_ranges) {
+    if (!ranges || !n_ranges || pad_frames < 0 || first_frame < 0 || n_known < first_frame || a < 0 || b < a || n_out < 0 ||
+        n_ranges_in < 0 || n_ranges_in > cap_ranges || (n_known > first_frame && !act))
+        return CSS_ERR_INVALID_ARG;
+    if (a / 256 - pad_frames - 2 < first_frame && first_frame > 0) return CSS_ERR_INVALID_ARG;   // a frame that can keep a sample of [a, b) is missing
+    std::vector<int64_t> reg(ranges, ranges + 2 * (size_t)n_ranges_in);
+    handoff_kept_ranges(act, first_frame, n_known, pad_frames, 256, 512, a, b, n_out, reg);
+    *n_ranges = (int32_t)(reg.size() / 2);
+    if ((int64_t)(reg.size() / 2) > cap_ranges) return CSS_ERR_INVALID_ARG;
+    std::memcpy(ranges, reg.data(), reg.size() * sizeof(int64_t));
     return CSS_OK;
 }

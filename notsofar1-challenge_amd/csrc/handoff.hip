@@ -8,6 +8,7 @@
 // (whisper/audio.py log_mel_spectrogram -- a dependency that is not under the reference tree and not installed here:
 // its published algorithm is restated; tests compare with the oracle's numpy restatement, which is held to
 // transformers.WhisperFeatureExtractor in tests/test_oracle_whisper_pin.py).
+#include <algorithm>
 #include <cmath>
 #include <vector>
 
@@ -83,19 +84,20 @@ __global__ void handoff_gather_kernel(const float* __restrict__ wav, const int64
     out[i] = v;
 }
 
-// spec [402][ld] (rows f: Re, 201 + f: Im; time fastest) -> mel[m][j] = log10(max(sum_f w[m][f] |X|^2, 1e-10)) and the
-// running maximum (as an order-preserving integer)
-__global__ __launch_bounds__(256) void handoff_mel_kernel(const float* __restrict__ spec, int64_t ld, int64_t nfr,
-                                                          const float* __restrict__ w, int n_mels, float* __restrict__ mel,
-                                                          int* __restrict__ gmax) {
+// One tile of 32 frames, shared by the offline kernel and the streamed one so that both round alike (re * re + im * im is
+// open to contraction: one copy of the expression, one rounding).  spec [402][ld] (rows f: Re, 201 + f: Im; time fastest),
+// the tile's frames are columns col0 + j0 .. of it -> mel[m * mel_ld + j] = log10(max(sum_f w[m][f] |X|^2, 1e-10)) for the
+// frames j < nfr, and the maximum of what was written into *gmax (as an order-preserving integer)
+__device__ __forceinline__ void handoff_mel_tile(const float* __restrict__ spec, int64_t ld, int64_t col0, int64_t j0, int64_t nfr,
+                                                 const float* __restrict__ w, int n_mels, float* __restrict__ mel, int64_t mel_ld,
+                                                 int* __restrict__ gmax) {
     __shared__ float pw[MEL_BINS][33];
-    const int64_t j0 = (int64_t)blockIdx.x * 32;
     const int tj = threadIdx.x & 31, ty = threadIdx.x >> 5;
     for (int f = ty; f < MEL_BINS; f += 8) {
         const int64_t j = j0 + tj;
         float p = 0.f;
         if (j < nfr) {
-            const float re = spec[(int64_t)f * ld + j], im = spec[(int64_t)(MEL_BINS + f) * ld + j];
+            const float re = spec[(int64_t)f * ld + col0 + j], im = spec[(int64_t)(MEL_BINS + f) * ld + col0 + j];
             p = re * re + im * im;
         }
         pw[f][tj] = p;
@@ -108,7 +110,7 @@ __global__ __launch_bounds__(256) void handoff_mel_kernel(const float* __restric
         for (int f = 0; f < MEL_BINS; ++f) acc = fmaf(wm[f], pw[f][tj], acc);
         const float v = log10f(fmaxf(acc, 1e-10f));
         if (j0 + tj < nfr) {
-            mel[(int64_t)m * nfr + j0 + tj] = v;
+            mel[(int64_t)m * mel_ld + j0 + tj] = v;
             best = fmaxf(best, v);
         }
     }
@@ -118,6 +120,12 @@ __global__ __launch_bounds__(256) void handoff_mel_kernel(const float* __restric
         const int b = __float_as_int(best);
         atomicMax(gmax, b >= 0 ? b : b ^ 0x7fffffff);       // monotone map float -> int
     }
+}
+
+__global__ __launch_bounds__(256) void handoff_mel_kernel(const float* __restrict__ spec, int64_t ld, int64_t nfr,
+                                                          const float* __restrict__ w, int n_mels, float* __restrict__ mel,
+                                                          int* __restrict__ gmax) {
+    handoff_mel_tile(spec, ld, 0, (int64_t)blockIdx.x * 32, nfr, w, n_mels, mel, nfr, gmax);
 }
 
 __global__ void handoff_norm_kernel(float* __restrict__ mel, int64_t count, const int* __restrict__ gmax) {
@@ -139,6 +147,123 @@ void launch_handoff_mel(const float* spec, int64_t ld, int64_t nfr, const float*
     hipLaunchKernelGGL(handoff_mel_kernel, dim3((unsigned)((nfr + 31) / 32)), dim3(256), 0, s, spec, ld, nfr, w, n_mels, mel, gmax);
     const int64_t count = nfr * n_mels;
     hipLaunchKernelGGL(handoff_norm_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, mel, count, gmax);
+}
+
+// ---- streamed sessions ----------------------------------------------------------------------------------------------
+struct HandoffAppendTable { HandoffAppend e[HANDOFF_MULTI_MAX]; };
+struct HandoffMelTable { HandoffMel e[HANDOFF_MULTI_MAX]; };
+static_assert(sizeof(HandoffAppendTable) <= 4096 && sizeof(HandoffMelTable) <= 4096, "the tables travel by value as kernel arguments");
+
+// One block per (stream, speaker).  Block q of 256 samples is kept iff an active frame t has t - pad <= q <= t + pad + 1
+// (frame t spans blocks t and t + 1); every frame that can keep a block below D1 is gated-final.  The kept samples of
+// [D0, D1) go behind the A samples already in the concatenation; with J frames emitted, frame j is the 400 samples from
+// 160 j of the concatenation reflect-padded by 200, so operand column x of this speaker's rows is padded sample 160 J + x.
+__global__ __launch_bounds__(256) void handoff_append_kernel(HandoffAppendTable tab, float* __restrict__ operand) {
+    const HandoffAppend& e = tab.e[blockIdx.z];
+    const int k = blockIdx.y, tid = threadIdx.x;
+    constexpr int HOP = 256;
+    __shared__ int len[256], off[256];
+    __shared__ int total;
+    const int64_t A0 = e.st[k].A, J0 = e.st[k].J;
+    const int64_t tail0 = J0 > 0 ? 160 * J0 - 200 : 0;
+    float* __restrict__ op = operand + (e.row0 + (int64_t)k * e.rows) * 160;
+    const int64_t op_n = e.rows * 160;
+    const uint8_t* __restrict__ gate = e.gate + (int64_t)k * e.gate_ld;
+    const float* __restrict__ out = e.out + (int64_t)k * e.out_ld;
+    const float* __restrict__ carry = e.carry_in + (int64_t)k * e.carry_ld;
+    const float* __restrict__ tail_in = e.tail_in + (int64_t)k * HANDOFF_TAIL_LD;
+    auto sample = [&](int64_t n) { return n >= e.out_base ? out[n - e.out_base] : carry[n - e.D0]; };
+    // ---- the kept blocks of [D0, D1), compacted behind sample A0 of the concatenation
+    int64_t A1 = A0;
+    const int64_t q_lo = e.D0 / HOP, q_hi = (e.D1 + HOP - 1) / HOP;
+    for (int64_t c0 = q_lo; c0 < q_hi; c0 += 256) {
+        const int64_t q = c0 + tid;
+        int n = 0;
+        if (q < q_hi) {
+            bool keep = !e.drop;
+            if (e.drop) {
+                const int64_t t_lo = q - e.pad - 1 < 0 ? 0 : q - e.pad - 1, t_hi = q + e.pad < e.t_g1 - 1 ? q + e.pad : e.t_g1 - 1;
+                for (int64_t t = t_lo; t <= t_hi; ++t) keep = keep || gate[t & e.gate_mask] != 0;
+            }
+            if (keep) n = (int)(((q + 1) * HOP < e.D1 ? (q + 1) * HOP : e.D1) - q * HOP);
+        }
+        len[tid] = n;
+        __syncthreads();
+        if (tid == 0) {
+            int acc = 0;
+            for (int i = 0; i < 256; ++i) { off[i] = acc; acc += len[i]; }
+            total = acc;
+        }
+        __syncthreads();
+        for (int i = tid; i < 256 * HOP; i += 256) {
+            const int b = i >> 8, r = i & (HOP - 1);
+            if (r < len[b]) {
+                const int64_t x = A1 + off[b] + r + 200 - 160 * J0;
+                if (x < op_n) op[x] = sample((c0 + b) * HOP + r);
+            }
+        }
+        A1 += total;
+        __syncthreads();
+    }
+    // ---- frames complete now; the rest of the operand: what the tail carried, the reflections, zeros
+    const int64_t J1 = e.closing ? A1 / 160 : (A1 >= 201 ? (A1 - 200) / 160 + 1 : 0);
+    auto concat = [&](int64_t c) { return c < A0 ? tail_in[c - tail0] : op[c + 200 - 160 * J0]; };
+    for (int64_t x = tid; x < op_n; x += 256) {
+        const int64_t i = 160 * J0 + x;
+        int64_t j = i - 200;
+        bool mirrored = j < 0, own = false;   // own: a new sample in its own place, written above
+        if (mirrored) j = -j;
+        float v = 0.f;
+        if (e.closing ? (A1 > 0 && i < A1 + 400) : j < A1) {
+            if (j >= A1) { j = 2 * (A1 - 1) - j; mirrored = true; }   // (the gather kernel's reflection, clamp included)
+            j = j < 0 ? 0 : j;
+            own = !mirrored && j >= A0;
+            if (!own) v = concat(j);
+        }
+        if (!own) op[x] = v;
+    }
+    __syncthreads();
+    const int64_t tail1 = J1 > 0 ? 160 * J1 - 200 : 0;
+    float* __restrict__ tail_out = e.tail_out + (int64_t)k * HANDOFF_TAIL_LD;
+    for (int64_t c = tail1 + tid; c < A1 && c - tail1 < HANDOFF_TAIL_LD; c += 256) tail_out[c - tail1] = concat(c);
+    // ---- the samples still undecided, for the next round; the gate bytes of the round; the counts
+    const int64_t end = e.t_g1 * HOP;
+    float* __restrict__ carry_out = e.carry_out + (int64_t)k * e.carry_ld;
+    for (int64_t n = e.D1 + tid; n < end; n += 256) carry_out[n - e.D1] = sample(n);
+    uint8_t* __restrict__ act = e.act_out + (int64_t)k * (e.t_g1 - e.t_g0);
+    for (int64_t t = e.t_g0 + tid; t < e.t_g1; t += 256) act[t - e.t_g0] = gate[t & e.gate_mask];
+    if (tid == 0) {
+        e.st[k].A = A1;
+        e.st[k].J = J1;
+        e.n_new[k] = (int)(J1 - J0);
+    }
+}
+
+__global__ __launch_bounds__(256) void handoff_mel_multi_kernel(HandoffMelTable tab, const float* __restrict__ spec, int64_t ld) {
+    const HandoffMel& e = tab.e[blockIdx.z];
+    const int k = blockIdx.y;
+    const int64_t nfr = e.n_new[k] < e.rows ? e.n_new[k] : e.rows, j0 = (int64_t)blockIdx.x * 32;
+    if (j0 >= nfr) return;
+    handoff_mel_tile(spec, ld, e.row0 + (int64_t)k * e.rows, j0, nfr, e.w, e.n_mels, e.mel + (int64_t)k * e.n_mels * e.mel_ld, e.mel_ld,
+                     &e.st[k].gmax);
+}
+
+void launch_handoff_append_multi(const HandoffAppend* e, int n, float* operand, hipStream_t s) {
+    for (int i0 = 0; i0 < n; i0 += HANDOFF_MULTI_MAX) {
+        const int cnt = std::min(HANDOFF_MULTI_MAX, n - i0);
+        HandoffAppendTable tab{};
+        for (int i = 0; i < cnt; ++i) tab.e[i] = e[i0 + i];
+        hipLaunchKernelGGL(handoff_append_kernel, dim3(1, e[i0].S, cnt), dim3(256), 0, s, tab, operand);
+    }
+}
+void launch_handoff_mel_multi(const HandoffMel* e, int n, int S, const float* spec, int64_t ld, hipStream_t s) {
+    for (int i0 = 0; i0 < n; i0 += HANDOFF_MULTI_MAX) {
+        const int cnt = std::min(HANDOFF_MULTI_MAX, n - i0);
+        HandoffMelTable tab{};
+        int64_t most = 1;
+        for (int i = 0; i < cnt; ++i) { tab.e[i] = e[i0 + i]; most = std::max(most, e[i0 + i].rows); }
+        hipLaunchKernelGGL(handoff_mel_multi_kernel, dim3((unsigned)((most + 31) / 32), S, cnt), dim3(256), 0, s, tab, spec, ld);
+    }
 }
 
 }  // namespace css

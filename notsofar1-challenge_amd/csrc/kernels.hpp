@@ -200,6 +200,35 @@ void launch_handoff_gather(const float* wav, const int64_t* regions, const int64
                            int64_t total, hipStream_t s);
 void launch_handoff_mel(const float* spec, int64_t ld, int64_t nfr, const float* w, int n_mels, float* mel, int* gmax, hipStream_t s);
 
+// The hand-off of STREAMED sessions (api_stream.hip): per round of a push, the samples whose membership in the concatenation
+// became decided are appended, the Whisper frames they complete are laid out as rows of ONE frame operand for all streams and
+// speakers of the round (one DFT product), and their raw log-mel values (no max - 8 clamp: that needs a maximum over a span
+// the consumer chooses) are written with the running maximum.  Table launches: blockIdx.z = entry (a stream), blockIdx.y =
+// speaker.  What is carried between rounds lives in per-stream buffers of two generations (read one, write the other).
+constexpr int HANDOFF_TAIL_LD = 512;          // floats per speaker of the concatenation tail (< 400 are used)
+constexpr int HANDOFF_GMAX_NONE = (int)0x807fffff;   // -inf in the order-preserving integer form of the running maximum
+struct HandoffState { int64_t A; int64_t J; int gmax; int pad_; };   // per (stream, speaker): samples appended, frames emitted, max
+struct HandoffAppend {
+    const uint8_t* gate; int64_t gate_ld, gate_mask;   // the gate ring (StreamStitchArgs::gate_out)
+    const float* out; int64_t out_ld, out_base;         // the round's output samples [S][out_ld]; column 0 is sample out_base
+    const float* carry_in; float* carry_out; int64_t carry_ld;   // undecided samples [D0, out_base) -> [D1, the round's end)
+    const float* tail_in; float* tail_out;              // [S][HANDOFF_TAIL_LD]: concatenated samples not yet behind a frame
+    HandoffState* st;                                   // [S]
+    int64_t t_g0, t_g1, D0, D1;                         // gated-final frames and decided samples before / after the round
+    int pad, drop, closing, S;
+    int64_t row0, rows;                                 // speaker k owns operand rows [row0 + k rows, row0 + (k + 1) rows)
+    uint8_t* act_out; int32_t* n_new;                   // out: gate bytes [S][t_g1 - t_g0], frames completed [S]
+};
+struct HandoffMel {
+    int64_t row0, rows;                                 // as above: the entry's columns of the spectra
+    const int32_t* n_new; HandoffState* st;             // [S] each
+    const float* w; int n_mels;                         // the entry's filterbank [n_mels][201]
+    float* mel; int64_t mel_ld;                         // out [S][n_mels][mel_ld]
+};
+constexpr int HANDOFF_MULTI_MAX = 16;
+void launch_handoff_append_multi(const HandoffAppend* e, int n, float* operand, hipStream_t s);
+void launch_handoff_mel_multi(const HandoffMel* e, int n, int S, const float* spec, int64_t ld, hipStream_t s);
+
 // ------------------------------------------------------------------------------------------------
 // loss.hip -- validation loss of the training loop (train.py:411 _calc_loss): S x S base-loss sums + the noise term
 // ------------------------------------------------------------------------------------------------
@@ -281,6 +310,9 @@ struct StreamStitchArgs {
     float* Y; int KIp;                     // [S][ld_frames][KIp]
     int64_t ld_frames;
     float activity_th; int dilation; int erosion;
+    // hand-off (handoff.hip): nullptr, or the ring [S][gate_ld] that receives the gate byte of every frame the gate kernel
+    // finalises, frame t of the recording at column t & gate_mask
+    uint8_t* gate_out; int64_t gate_ld, gate_mask;
 };
 void launch_stream_activity(const StreamStitchArgs& a, int64_t t_lo, int64_t t_hi, hipStream_t s);
 void launch_stream_gate_ola(const StreamStitchArgs& a, int64_t t_lo, int64_t t_hi, hipStream_t s);

@@ -6,7 +6,7 @@
 // ola_masks_kernel / morph_kernel / ola_stft_kernel exactly, so that every frame they produce is the offline frame bit for bit.
 //   stream_activity_kernel   weighted overlap-add of the permuted masks, mean over frequency, threshold -> act_b
 //   stream_gate_ola_kernel   dilate / erode of act_b (left halo from earlier pushes), weighted overlap-add of the permuted
-//                            spectra, gating -> synthesis rows Y
+//                            spectra, gating -> synthesis rows Y (and, for a stream with the hand-off on, the gate bytes)
 // Both are table launches (the idiom of mvdr_solve_multi_kernel): up to STREAM_MULTI_MAX streams' windows and frame ranges
 // by value, blockIdx.z selects the entry, blocks past an entry's range return at once.  One stream is a table of one entry,
 // so there is one copy of each body and one kernel for css_stream_push, css_stream_push_many and css_stream_finish.
@@ -110,6 +110,7 @@ __device__ __forceinline__ void stream_gate_ola_body(const StreamStitchArgs& a, 
             keep = keep & x;
         }
     const float gate = active && keep ? 1.f : 0.f;
+    if (a.gate_out && active && fy == 0) a.gate_out[(int64_t)s * a.gate_ld + ((t + a.frame_base) & a.gate_mask)] = keep;
     const float2* sep = reinterpret_cast<const float2*>(a.sep);
     int64_t gs0 = 0, gs1 = -1;
     float wsum = 0.f;

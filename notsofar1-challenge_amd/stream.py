@@ -8,6 +8,11 @@ segmentation (``latency_samples``: 3.6 s with the default 3 s / 1.5 s segments).
 ``CssStreamGroup`` pushes into many streams of one separator in one call (css_stream_push_many): the segments the streams
 complete in that call share the mask estimator's batches, so N live meetings cost about one estimator pass per tick instead
 of N.  Every stream's output is what its own ``push`` would have returned, bit for bit.
+
+``CssStream(..., handoff=dict(n_mels=80, pad_frames=8, drop_silence=True))`` switches the hand-off to the ASR front end on
+(css_stream_handoff_*): after every ``push`` / ``finish`` / grouped push, ``stream.handoff`` holds what became final in that
+call -- raw Whisper log-mel frames, the kept sample ranges and the gate bits per separated stream (``Handoff``).  All calls'
+frames of a finished stream, through ``whisper_normalize``, are ``Handle.handoff_logmel`` of the whole recording, bit for bit.
 """
 from __future__ import annotations
 
@@ -21,11 +26,33 @@ from .css import CssCfg, make_run_cfg
 from .separator import HipSeparator
 
 
+def whisper_normalize(raw: np.ndarray, raw_max: Optional[float] = None) -> np.ndarray:
+    """Whisper's clamp and scaling of raw log-mel frames: (max(raw, raw_max - 8) + 4) / 4 in float32.  ``raw_max`` defaults to
+    the maximum of ``raw`` itself -- what Whisper does with one (30 s) window; pass a stream's running maximum to reproduce
+    ``Handle.handoff_logmel`` over everything the stream returned."""
+    raw = np.asarray(raw, dtype=np.float32)
+    if raw.size == 0:
+        return raw.copy()
+    mx = np.float32(raw.max() if raw_max is None else raw_max)
+    return (np.maximum(raw, mx - np.float32(8.0)) + np.float32(4.0)) * np.float32(0.25)
+
+
+class Handoff:
+    """What one call made final for the ASR front end, per separated stream k: ``mel[k]`` raw log-mel frames [n_mels, n],
+    ``ranges[k]`` the sample ranges [r, 2] (int64) appended to k's concatenation, ``activity[k]`` the gate bits of frames
+    ``first_activity_frame`` .. and ``raw_max[k]`` the maximum of every raw value returned for k so far."""
+
+    def __init__(self, mel, ranges, activity, raw_max, first_activity_frame):
+        self.mel, self.ranges, self.activity, self.raw_max = mel, ranges, activity, raw_max
+        self.first_activity_frame = first_activity_frame
+
+
 class CssStream:
     """One stream on a ``HipSeparator``'s handle.  ``push(chunk)`` -> list of S float32 arrays (the newly final samples),
-    ``finish()`` -> the rest; use as a context manager (closes the stream)."""
+    ``finish()`` -> the rest; use as a context manager (closes the stream).  ``handoff``: see the module text."""
 
-    def __init__(self, separator: HipSeparator, cfg: Optional[CssCfg] = None, fs: int = 16000, num_channels: int = 7):
+    def __init__(self, separator: HipSeparator, cfg: Optional[CssCfg] = None, fs: int = 16000, num_channels: int = 7,
+                 handoff: Optional[Mapping[str, object]] = None):
         self.separator = separator
         self.cfg = cfg if cfg is not None else CssCfg()
         desc = separator.desc
@@ -38,6 +65,54 @@ class CssStream:
         self.id = int(sid.value)
         self.latency_samples = self.info().max_lag
         self._out = np.empty((self.num_spks, 0), np.float32)
+        self.handoff: Optional[Handoff] = None
+        self._hcfg = None
+        if handoff is not None:
+            self._hcfg = _lib.handoff_cfg(**dict(handoff))
+            try:
+                _lib.check(self._h.h, self._h.lib.css_stream_handoff_open(self._h.h, self.id, C.byref(self._hcfg)))
+            except Exception:
+                self.close()
+                raise
+            self._ho = _lib.CssStreamHandoffOut()
+            self._ho_caps = (0, 0, 0)
+            S = self.num_spks
+            self._ho_n = (np.zeros(S, np.int64), np.zeros(S, np.int32), np.zeros(S, np.float32))
+
+    def handoff_bounds(self, n_samples: int):
+        """(frames, ranges, gate frames) a push of ``n_samples`` (-1: finish) needs room for"""
+        return _lib.stream_handoff_bounds(self.separator.desc, self._run_cfg, self._hcfg, n_samples)
+
+    def handoff_final_frames(self, n_pushed: int) -> int:
+        return _lib.stream_handoff_final_frames(self.separator.desc, self._run_cfg, self._hcfg, n_pushed)
+
+    def _handoff_bind(self, n_samples: int):
+        """binds buffers that suffice for a call with ``n_samples`` (kept while they are large enough)"""
+        if self._hcfg is None:
+            return
+        need = self.handoff_bounds(n_samples)
+        if any(n > c for n, c in zip(need, self._ho_caps)) or not self._ho.mel_host:
+            S, nm = self.num_spks, int(self._hcfg.n_mels)
+            caps = tuple(max(n, c) for n, c in zip(need, self._ho_caps))
+            self._ho_mel = np.empty((S, nm, caps[0]), np.float32)
+            self._ho_ranges = np.empty((S, caps[1], 2), np.int64)
+            self._ho_act = np.empty((S, caps[2]), np.uint8)
+            self._ho_caps = caps
+            o = self._ho
+            o.mel_host, o.cap_frames = self._ho_mel.ctypes.data, caps[0]
+            o.ranges_host, o.cap_ranges = self._ho_ranges.ctypes.data, caps[1]
+            o.activity_host, o.cap_activity = self._ho_act.ctypes.data, caps[2]
+            o.n_frames, o.n_ranges, o.raw_max = (a.ctypes.data for a in self._ho_n)
+        _lib.check(self._h.h, self._h.lib.css_stream_handoff_bind(self._h.h, self.id, C.byref(self._ho)))
+
+    def _handoff_take(self):
+        if self._hcfg is None:
+            return
+        nf, nr, mx = self._ho_n
+        na = int(self._ho.n_activity)
+        S = range(self.num_spks)
+        self.handoff = Handoff([self._ho_mel[k, :, :nf[k]].copy() for k in S], [self._ho_ranges[k, :nr[k]].copy() for k in S],
+                               [self._ho_act[k, :na].copy() for k in S], mx.copy(), int(self._ho.first_activity_frame))
 
     def info(self) -> _lib.CssStreamInfo:
         inf = _lib.CssStreamInfo()
@@ -66,8 +141,10 @@ class CssStream:
         cap = n + self.latency_samples
         out = self._buffer(cap)
         n_out = C.c_int64(0)
+        self._handoff_bind(n)
         _lib.check(self._h.h, self._h.lib.css_stream_push(self._h.h, self.id, x.ctypes.data_as(C.c_void_p), n,
                                                           out.ctypes.data_as(C.c_void_p), out.shape[1], C.byref(n_out)))
+        self._handoff_take()
         return [out[s, :n_out.value].copy() for s in range(self.num_spks)]
 
     def finish(self) -> List[np.ndarray]:
@@ -75,8 +152,10 @@ class CssStream:
         rest = _lib.plan(self.separator.desc, self._run_cfg, inf.n_pushed).n_out - inf.n_emitted
         out = self._buffer(max(rest, 1))
         n_out = C.c_int64(0)
+        self._handoff_bind(-1)
         _lib.check(self._h.h, self._h.lib.css_stream_finish(self._h.h, self.id, out.ctypes.data_as(C.c_void_p), out.shape[1],
                                                             C.byref(n_out)))
+        self._handoff_take()
         return [out[s, :n_out.value].copy() for s in range(self.num_spks)]
 
     def close(self):
@@ -125,8 +204,11 @@ class CssStreamGroup:
             outs.append(out)
             it.id, it.pcm_host, it.n_samples = s.id, x.ctypes.data, x.shape[0]
             it.out_host, it.cap, it.n_out = out.ctypes.data, out.shape[1], 0
+            s._handoff_bind(x.shape[0])
         stats = _lib.CssStreamGroupStats()
         _lib.check(self._h.h, self._h.lib.css_stream_push_many(self._h.h, items, len(part), C.byref(stats)))
         self.stats = stats
+        for s, _ in part:
+            s._handoff_take()
         got = {id(s): [out[k, :it.n_out].copy() for k in range(s.num_spks)] for it, (s, _), out in zip(items, part, outs)}
         return [got.get(id(s), [np.empty(0, np.float32) for _ in range(s.num_spks)]) for s in self.streams]

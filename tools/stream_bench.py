@@ -11,6 +11,9 @@ work on ONE set of streams; every returned piece is compared with css_run's outp
 per round, streams served in real time per GPU (1.5 s / round time x N), bit_identical (profiles/r09_stream_group.json).
 
     python tools/stream_bench.py --streams 16 [--out FILE]
+
+With --handoff every stream has the hand-off to the ASR front end switched on (80 bands, pad 8, drop silence): the rounds
+then also return log-mel frames, kept ranges and gate bits (profiles/r10_stream_handoff.json).  --only-grouped runs arm B alone.
 """
 import argparse
 import json
@@ -27,7 +30,10 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 FS = 16000
 
 
-def group_bench(n_streams, out_path, seconds=60.0, round_s=1.5, block=5, passes=2):
+HANDOFF = dict(n_mels=80, pad_frames=8, drop_silence=True)
+
+
+def group_bench(n_streams, out_path, seconds=60.0, round_s=1.5, block=5, passes=2, handoff=False, only_grouped=False):
     import notsofar1_challenge_amd.css as CSS
     import notsofar1_challenge_amd.separator as SEP
     import notsofar1_challenge_amd.stream as STR
@@ -45,14 +51,15 @@ def group_bench(n_streams, out_path, seconds=60.0, round_s=1.5, block=5, passes=
     ms = {"A": [], "B": []}
     same = {"A": True, "B": True}
     seg_per_batch = []
+    mel_frames = []
 
     def one_pass(first_arm, timed):
-        streams = [STR.CssStream(sep, cfg) for _ in recs]
+        streams = [STR.CssStream(sep, cfg, handoff=HANDOFF) if handoff else STR.CssStream(sep, cfg) for _ in recs]
         group = STR.CssStreamGroup(streams)
         em = [0] * n_streams
         n_rounds = (recs[0].shape[0] + step - 1) // step if timed else 2 * block
         for r in range(n_rounds):
-            arm = "AB"[(r // block + (first_arm == "B")) % 2]
+            arm = "B" if only_grouped else "AB"[(r // block + (first_arm == "B")) % 2]
             chunks = [x[r * step:(r + 1) * step] for x in recs]
             t = time.perf_counter()
             if arm == "A":
@@ -65,6 +72,8 @@ def group_bench(n_streams, out_path, seconds=60.0, round_s=1.5, block=5, passes=
             ms[arm].append(dt * 1e3)
             if arm == "B" and group.stats.estimator_batches:
                 seg_per_batch.append(group.stats.estimator_segments / group.stats.estimator_batches)
+            if handoff:
+                mel_frames.append(sum(m.shape[1] for s in streams for m in s.handoff.mel))
             for i, got in enumerate(res):
                 got = np.stack(got)
                 same[arm] = same[arm] and bool(np.array_equal(got, refs[i][:, em[i]:em[i] + got.shape[1]]))
@@ -86,13 +95,19 @@ def group_bench(n_streams, out_path, seconds=60.0, round_s=1.5, block=5, passes=
     res = {"model": "mc_v1 (18 blocks, exact float32)", "cfg": "3 s / 1.5 s segments, defaults", "streams": n_streams,
            "meeting_s": seconds, "round_s": round_s, "block_rounds": block, "device_bytes_per_stream": int(dev),
            "segments_per_estimator_batch_median": float(np.median(seg_per_batch)) if seg_per_batch else 0.0, "arms": {}}
+    if handoff:
+        res["handoff"] = dict(HANDOFF, mel_frames_per_round_median=float(np.median(mel_frames)),
+                              launches_products_frames_last_call=list(sep.handle.stream_handoff_stats()))
     for arm, what in (("A", "one css_stream_push per stream and round"), ("B", "one css_stream_push_many per round")):
+        if not ms[arm]:
+            continue
         v = np.array(ms[arm])
         p50 = float(np.percentile(v, 50))
         res["arms"][arm] = {"what": what, "rounds": int(v.size), "round_ms_p50": round(p50, 3),
                             "round_ms_p99": round(float(np.percentile(v, 99)), 3),
                             "streams_in_real_time_per_gpu": round(round_s * 1e3 / p50 * n_streams, 1), "bit_identical": same[arm]}
-    res["p50_ratio_B_over_A"] = round(res["arms"]["B"]["round_ms_p50"] / res["arms"]["A"]["round_ms_p50"], 4)
+    if "A" in res["arms"]:
+        res["p50_ratio_B_over_A"] = round(res["arms"]["B"]["round_ms_p50"] / res["arms"]["A"]["round_ms_p50"], 4)
     sep.close()
     text = json.dumps(res, indent=1)
     if out_path:
@@ -106,10 +121,12 @@ def main():
     ap.add_argument("--minutes", type=float, nargs="+", default=[1.0, 10.0])
     ap.add_argument("--pushes", type=float, nargs="+", default=[0.5, 1.5])
     ap.add_argument("--streams", type=int, default=0, help="grouped pushes: N live meetings, per-stream pushes against one grouped push per round")
+    ap.add_argument("--handoff", action="store_true", help="with --streams: every stream returns log-mel frames, kept ranges and gate bits")
+    ap.add_argument("--only-grouped", action="store_true", help="with --streams: arm B alone (twice the rounds)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.streams:
-        return group_bench(a.streams, a.out)
+        return group_bench(a.streams, a.out, handoff=a.handoff, only_grouped=a.only_grouped)
     import notsofar1_challenge_amd.css as CSS
     import notsofar1_challenge_amd.separator as SEP
     import notsofar1_challenge_amd.stream as STR
