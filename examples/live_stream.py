@@ -9,7 +9,10 @@ With --logmel every stream has the hand-off to the ASR front end on: each tick a
 Whisper log-mel frames and the sample ranges of the audio the activity gate kept (CssStream(handoff=...)); a Whisper host
 collects 3 000 frames per window and normalises each window with whisper_normalize.
 
-    python examples/live_stream.py [--seconds 30] [--rooms N] [--logmel]
+With --pcm16 the source delivers 16-bit PCM, as a capture device does: the int16 chunks go to push_pcm16 as they are (2 bytes
+per sample over PCIe, scaled and de-interleaved on the device); the result is that of pushing chunk.astype(float32) / 32768.
+
+    python examples/live_stream.py [--seconds 30] [--rooms N] [--logmel] [--pcm16]
 """
 import argparse
 import os
@@ -38,15 +41,22 @@ def print_handoff(streams, fs):
         print(f"    room {r}: " + " | ".join(per))
 
 
-def rooms(sep, n_rooms, seconds, fs, chunk, logmel=False):
+def capture(mix):
+    """what a 16-bit capture device would have delivered: [n, 7] int16, interleaved"""
+    return np.clip(np.rint(mix.astype(np.float64) * 0.2 * 32768.0), -32768, 32767).astype(np.int16)
+
+
+def rooms(sep, n_rooms, seconds, fs, chunk, logmel=False, pcm16=False):
     mixes = [SYN.synth_meeting(seconds, 7, seed=1 + r)[0] for r in range(n_rooms)]
+    if pcm16:
+        mixes = [capture(m) for m in mixes]
     streams = [STR.CssStream(sep, CSS.CssCfg(), fs=fs, num_channels=7, handoff=HANDOFF if logmel else None) for _ in mixes]
     group = STR.CssStreamGroup(streams)
     outs = [[[] for _ in range(sep.desc.num_spks)] for _ in mixes]
     print(f"{n_rooms} rooms, lag bound {streams[0].latency_samples / fs:.2f} s")
     for i in range(0, mixes[0].shape[0], chunk):
         t = time.perf_counter()
-        res = group.push([m[i:i + chunk] for m in mixes])
+        res = (group.push_pcm16 if pcm16 else group.push)([m[i:i + chunk] for m in mixes])
         ms = (time.perf_counter() - t) * 1e3
         for room, got in zip(outs, res):
             for k, o in enumerate(got):
@@ -68,15 +78,18 @@ def main():
     ap.add_argument("--seconds", type=float, default=30.0)
     ap.add_argument("--rooms", type=int, default=1, help="meetings fed tick by tick through one CssStreamGroup")
     ap.add_argument("--logmel", action="store_true", help="also return Whisper log-mel frames and kept ranges with every tick")
+    ap.add_argument("--pcm16", action="store_true", help="the source delivers int16 samples: push_pcm16 instead of push")
     a = ap.parse_args()
     fs = 16000
     desc = W.ModelDesc.mc_v1()
     sep = SEP.HipSeparator(W.apply_golden_recipe(W.portable_state_dict(desc, 0)), None, device=0)
     if a.rooms > 1:
-        rooms(sep, a.rooms, a.seconds, fs, fs // 2, a.logmel)
+        rooms(sep, a.rooms, a.seconds, fs, fs // 2, a.logmel, a.pcm16)
         sep.close()
         return
     mix = SYN.synth_meeting(a.seconds, 7, seed=1)[0]
+    if a.pcm16:
+        mix = capture(mix)
     chunk = fs // 2
     streams = [[] for _ in range(desc.num_spks)]
     mels = [[] for _ in range(desc.num_spks)]
@@ -84,7 +97,7 @@ def main():
         print(f"lag bound {s.latency_samples / fs:.2f} s")
         for i in range(0, mix.shape[0], chunk):
             t = time.perf_counter()
-            out = s.push(mix[i:i + chunk])
+            out = (s.push_pcm16 if a.pcm16 else s.push)(mix[i:i + chunk])
             ms = (time.perf_counter() - t) * 1e3
             for k, o in enumerate(out):
                 streams[k].append(o)

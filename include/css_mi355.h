@@ -498,7 +498,9 @@ int css_istft_host(css_handle_t h, const float* y_planes, int32_t batch, int64_t
  *     and css_set_feature_options (a stream's pushes read the handle's window and feature options);
  *   - frame_len 512 / frame_hop 256 only (CSS_ERR_INVALID_ARG otherwise); any segmentation css_make_run_cfg accepts;
  *   - CSS_ERR_STATE while css_run_enqueue* sessions are outstanding (not yet css_wait-ed);
- *   - css_stream_handoff_* (below): the ASR front end's log-mel frames, kept ranges and gate bits with every push.
+ *   - css_stream_handoff_* (below): the ASR front end's log-mel frames, kept ranges and gate bits with every push;
+ *   - css_stream_push_pcm16 / css_stream_push_many_pcm16: the same pushes for int16 samples, interleaved or planar, scaled and
+ *     de-interleaved on the device; the bits are those of pushing (float)q / 32768.
  * Output: out_host [S][cap]; a push writes at most n_samples + max_lag samples per stream, finish css_plan(n_pushed).n_out -
  * n_emitted.  A capacity below what the call would return is CSS_ERR_INVALID_ARG and leaves the stream unchanged. */
 #define CSS_MAX_STREAMS 64
@@ -533,6 +535,30 @@ typedef struct CssStreamGroupStats {
     int64_t estimator_segments; /* segments they held, all items together                         */
 } CssStreamGroupStats;
 int css_stream_push_many(css_handle_t h, CssStreamPush* items, int32_t n_items, CssStreamGroupStats* stats);
+/* The same two calls for 16-bit PCM, as capture devices and decoders deliver it: the int16 samples cross PCIe as they are (2
+ * bytes per sample, straight from the caller's buffer: no host transposition, no host staging) and one kernel launch per
+ * round de-interleaves and scales them into the windows of all streams of the round.  The call IS css_stream_push(_many) with
+ * pcm[i][c] = (float)q[i][c] * (1.0f / 32768.0f) -- exact in float32, the scaling of css_run_pcm16: n_out and the samples,
+ * the finality rule and max_lag, the zero-weight check, the hand-off outputs, CssStreamGroupStats and every refusal with its
+ * "nothing moved" guarantee are those of the float call, bit for bit.  A stream may receive float and PCM16 pushes in any
+ * order across calls; all items of one call are of the call's kind.
+ * Sample i of channel c is pcm16_host[i * sample_stride + c * channel_stride] (strides in elements).  Two layouts:
+ *   interleaved   sample_stride == n_ch, channel_stride == 1             (a capture buffer; one contiguous copy per piece)
+ *   planar        sample_stride == 1,    channel_stride >= n_samples     (n_ch mono recordings or a slice of them; one 2-D copy)
+ * (for one channel they coincide: sample_stride == 1 with any channel_stride); other strides are CSS_ERR_INVALID_ARG for an
+ * item with samples (n_samples == 0 takes no part, as in the float call, and its source and strides are not looked at).
+ * pcm16_host may be pageable memory; from page-locked memory (css_host_alloc) the uploads are asynchronous DMA and the
+ * call's only synchronise is the one that ends it.  The first PCM16 push of a stream allocates its device staging (one
+ * piece: 8 hop_frames * frame_hop * n_ch int16), counted in CssStreamInfo.device_bytes from then on. */
+typedef struct CssStreamPushPcm16 {
+    int32_t id;
+    const int16_t* pcm16_host;
+    int64_t n_samples, sample_stride, channel_stride;
+    float* out_host; int64_t cap; int64_t n_out;   /* as CssStreamPush */
+} CssStreamPushPcm16;
+int css_stream_push_pcm16(css_handle_t h, int32_t id, const int16_t* pcm16_host, int64_t n_samples,
+                          int64_t sample_stride, int64_t channel_stride, float* out_host, int64_t cap, int64_t* n_out);
+int css_stream_push_many_pcm16(css_handle_t h, CssStreamPushPcm16* items, int32_t n_items, CssStreamGroupStats* stats);
 int css_stream_finish(css_handle_t h, int32_t id, float* out_host, int64_t cap, int64_t* n_out);
 int css_stream_close(css_handle_t h, int32_t id);
 int css_stream_info(css_handle_t h, int32_t id, CssStreamInfo* out);

@@ -86,6 +86,11 @@ class CssStreamPush(C.Structure):
                 ("cap", C.c_int64), ("n_out", C.c_int64)]
 
 
+class CssStreamPushPcm16(C.Structure):
+    _fields_ = [("id", C.c_int32), ("pcm16_host", C.c_void_p), ("n_samples", C.c_int64), ("sample_stride", C.c_int64),
+                ("channel_stride", C.c_int64), ("out_host", C.c_void_p), ("cap", C.c_int64), ("n_out", C.c_int64)]
+
+
 class CssStreamGroupStats(C.Structure):
     _fields_ = [("estimator_batches", C.c_int32), ("estimator_segments", C.c_int64)]
 
@@ -184,6 +189,8 @@ SIGNATURES = {
     "css_stream_open": (C.c_int, [_P, C.POINTER(CssRunCfg), C.c_int32, C.POINTER(C.c_int32)]),
     "css_stream_push": (C.c_int, [_P, C.c_int32, _P, C.c_int64, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "css_stream_push_many": (C.c_int, [_P, C.POINTER(CssStreamPush), C.c_int32, C.POINTER(CssStreamGroupStats)]),
+    "css_stream_push_pcm16": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "css_stream_push_many_pcm16": (C.c_int, [_P, C.POINTER(CssStreamPushPcm16), C.c_int32, C.POINTER(CssStreamGroupStats)]),
     "css_stream_finish": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "css_stream_close": (C.c_int, [_P, C.c_int32]),
     "css_stream_info": (C.c_int, [_P, C.c_int32, C.POINTER(CssStreamInfo)]),

@@ -14,10 +14,11 @@
 // permutation scan (continued from the last segment's permutation), then stream.hip's two stitching kernels and the
 // synthesis GEMM + overlap-add over the newly final frames.
 //
-// There is one push path: css_stream_push_many.  It takes piece r of every item in round r, and the segments a round completes
+// There is one push path: push_items, behind css_stream_push_many (float32 samples) and css_stream_push_many_pcm16 (int16
+// samples, converted on the device).  It takes piece r of every item in round r, and the segments a round completes
 // in all streams of one segmentation pass the estimator as ONE batch (every estimator kernel is batch invariant in exact
 // float32, as for queued sessions: api_queue.hip run_group), so N live meetings cost about one estimator pass per tick
-// instead of N.  css_stream_push is a group of one item; css_stream_finish runs the same segments() / tail() with one job.
+// instead of N.  css_stream_push(_pcm16) is a group of one item; css_stream_finish runs the same segments() / tail() with one job.
 //
 // The hand-off (css_stream_handoff_*): a stream that has it switched on also returns, with every call, the gate
 // bits, the kept sample ranges and the raw Whisper log-mel frames that became final.  The step sits between tail() and the
@@ -73,7 +74,8 @@ struct StreamState {
     int cur = 0;
     DevBuf pcm[2], X[2], masks[2], sep[2], perms[2], act_b[2], G[2];
     DevBuf scm, bfw, pnorm, costs, pit_part, Y, out, segw;
-    std::vector<float> host_cm;    // one piece, channel-major
+    std::vector<float> host_cm;    // one piece, channel-major (float pushes)
+    DevBuf pcm16_stage;            // one piece of int16 as the caller laid it out, from the first PCM16 push on
 };
 
 StreamState* get_stream(css_ctx* h, int32_t id) {
@@ -92,7 +94,7 @@ void free_stream(StreamState* s) {
     for (int b = 0; b < 2; ++b)
         for (DevBuf* d : {&s->pcm[b], &s->X[b], &s->masks[b], &s->sep[b], &s->perms[b], &s->act_b[b], &s->G[b]})
             if (d->p) hipFree(d->p);
-    for (DevBuf* d : {&s->scm, &s->bfw, &s->pnorm, &s->costs, &s->pit_part, &s->Y, &s->out, &s->segw})
+    for (DevBuf* d : {&s->scm, &s->bfw, &s->pnorm, &s->costs, &s->pit_part, &s->Y, &s->out, &s->segw, &s->pcm16_stage})
         if (d->p) hipFree(d->p);
     if (s->ho) {
         for (DevBuf* d : {&s->ho->gate, &s->ho->carry[0], &s->ho->carry[1], &s->ho->tail[0], &s->ho->tail[1]})
@@ -106,7 +108,7 @@ int64_t device_bytes(const StreamState* s) {
     int64_t n = 0;
     for (int b = 0; b < 2; ++b)
         for (const DevBuf* d : {&s->pcm[b], &s->X[b], &s->masks[b], &s->sep[b], &s->perms[b], &s->act_b[b], &s->G[b]}) n += (int64_t)d->cap;
-    for (const DevBuf* d : {&s->scm, &s->bfw, &s->pnorm, &s->costs, &s->pit_part, &s->Y, &s->out, &s->segw}) n += (int64_t)d->cap;
+    for (const DevBuf* d : {&s->scm, &s->bfw, &s->pnorm, &s->costs, &s->pit_part, &s->Y, &s->out, &s->segw, &s->pcm16_stage}) n += (int64_t)d->cap;
     if (s->ho) {
         for (const DevBuf* d : {&s->ho->gate, &s->ho->carry[0], &s->ho->carry[1], &s->ho->tail[0], &s->ho->tail[1]}) n += (int64_t)d->cap;
         n += (int64_t)(SMAX * sizeof(HandoffState));
@@ -672,17 +674,34 @@ int css_stream_open(css_handle_t h, const CssRunCfg* cfg, int32_t n_ch, int32_t*
     return CSS_OK;
 }
 
-// css_stream_push_many.  Every item is checked against its stream's state before anything moves (ids are distinct, so the
-// checks are those of the item-by-item calls); then the call works in rounds: round r takes piece r of every item that still
-// has one -- uploads (one synchronise per round: every stream owns its staging buffer), analysis transforms, the estimator
-// over all segments the round completed (segments), the stitching tail of all streams (tail), the downloads.
-int css_stream_push_many(css_handle_t h, CssStreamPush* items, int32_t n_items, CssStreamGroupStats* stats) {
-    if (!h) return CSS_ERR_INVALID_ARG;
-    if (n_items < 0 || (n_items > 0 && !items)) return fail(h, CSS_ERR_INVALID_ARG, "bad argument");
-    struct Item { StreamState* s; CssStreamPush* p; int64_t done, emitted, n, t_g1, t_g_before; };
-    std::vector<Item> its((size_t)n_items);
-    for (int32_t i = 0; i < n_items; ++i) {
-        CssStreamPush& p = items[i];
+// The one push path (css_stream_push_many, css_stream_push_many_pcm16 and their single-item forms).  An item's samples come as
+// float32 [n][C] or as int16 with strides; the source of a piece is the only thing the two kinds of call differ in.  Every
+// item is checked against its stream's state before anything moves (ids are distinct, so the checks are those of the
+// item-by-item calls); then the call works in rounds: round r takes piece r of every item that still has one -- the samples
+// into the windows, analysis transforms, the estimator over all segments the round completed (segments), the stitching tail
+// of all streams (tail), the downloads.
+//   float32: the piece is transposed on the host into the stream's staging buffer and uploaded from there; one synchronise
+//            per round, because the next round reuses that buffer.
+//   int16:   the piece is copied as it is from the caller's memory into the stream's device staging (one contiguous copy
+//            for an interleaved piece, one 2-D copy for a planar one) and ONE table launch per round converts all streams'
+//            pieces into their windows (stream.hip stream_ingest_pcm16_kernel).  No host buffer is reused, the next round's
+//            copy into the staging is ordered behind the launch on the stream: no synchronise but the one that ends the call.
+//            (Nothing else leans on the per-round synchronise: the hand-off's page-locked staging is per round of a call, and
+//            every device buffer the rounds share is written and read in stream order.)
+namespace {
+
+struct PushItem {
+    int32_t id;
+    const float* f32;                                   // float call: [n_samples][C]
+    const int16_t* i16; int64_t sample_stride, channel_stride;   // PCM16 call
+    int64_t n_samples; float* out_host; int64_t cap; int64_t* n_out;
+};
+
+int push_items(css_ctx* h, const std::vector<PushItem>& items, bool pcm16, CssStreamGroupStats* stats) {
+    struct Item { StreamState* s; const PushItem* p; int64_t done, emitted, n, t_g1, t_g_before; bool planar; };
+    std::vector<Item> its(items.size());
+    for (size_t i = 0; i < items.size(); ++i) {
+        const PushItem& p = items[i];
         auto refuse = [&](int code, const std::string& msg) {
             return fail(h, code, "item " + std::to_string(i) + " (stream " + std::to_string(p.id) + "): " + msg);
         };
@@ -690,10 +709,20 @@ int css_stream_push_many(css_handle_t h, CssStreamPush* items, int32_t n_items, 
         if (!s) return refuse(CSS_ERR_INVALID_ARG, "no open stream with this id");
         if (h->queued || !h->pending.empty())
             return refuse(CSS_ERR_STATE, "queued sessions (css_run_enqueue*) are outstanding: css_wait before using a stream");
-        for (int32_t k = 0; k < i; ++k)
+        for (size_t k = 0; k < i; ++k)
             if (items[k].id == p.id) return refuse(CSS_ERR_INVALID_ARG, "the stream is named twice in one call");
         if (s->finished) return refuse(CSS_ERR_STATE, "the stream has finished");
-        if (p.n_samples < 0 || (p.n_samples > 0 && !p.pcm_host)) return refuse(CSS_ERR_INVALID_ARG, "bad argument");
+        const void* src = pcm16 ? (const void*)p.i16 : (const void*)p.f32;
+        if (p.n_samples < 0 || (p.n_samples > 0 && !src)) return refuse(CSS_ERR_INVALID_ARG, "bad argument");
+        bool planar = false;
+        if (pcm16 && p.n_samples > 0) {   // (an item without samples takes no part, whatever its strides say)
+            // (one channel: consecutive samples are both layouts, whatever channel_stride says, and are copied as one run)
+            const bool inter = (p.sample_stride == s->n_ch && p.channel_stride == 1) || (s->n_ch == 1 && p.sample_stride == 1);
+            planar = !inter && p.sample_stride == 1 && p.channel_stride >= p.n_samples;
+            if (!inter && !planar)
+                return refuse(CSS_ERR_INVALID_ARG, "PCM16 strides: interleaved (sample_stride = channels, channel_stride = 1) or planar "
+                                                   "(sample_stride = 1, channel_stride >= n_samples)");
+        }
         if (h->split) return refuse(CSS_ERR_STATE, "streams run in CSS_LINEAR_EXACT_F32 only");
         const int64_t need = final_frames(s->n_pushed + p.n_samples, s->T, s->hop, s->halo) * h->d.frame_hop - s->n_emitted;
         if (need > 0 && (!p.out_host || p.cap < need))
@@ -703,7 +732,7 @@ int css_stream_push_many(css_handle_t h, CssStreamPush* items, int32_t n_items, 
         std::string why;
         const int hrc = check_handoff_call(h, s, p.n_samples, &why);
         if (hrc != CSS_OK) return refuse(hrc, why);
-        its[(size_t)i] = Item{s, &p, 0, 0, 0, 0, s->t_g};
+        its[i] = Item{s, &p, 0, 0, 0, 0, s->t_g, planar};
     }
     if (stats) *stats = CssStreamGroupStats{};
     handoff_begin_call(h);
@@ -718,19 +747,26 @@ int css_stream_push_many(css_handle_t h, CssStreamPush* items, int32_t n_items, 
         return (int)CSS_OK;
     };
     bool any = false;
-    for (Item& it : its) { it.p->n_out = 0; any = any || it.p->n_samples > 0; }
+    for (Item& it : its) { *it.p->n_out = 0; any = any || it.p->n_samples > 0; }
     if (!any) return hand_out();
     HIPCHK(h, hipSetDevice(h->device));
     const int hopS = h->d.frame_hop;
     int rc;
+    // a stream's first PCM16 push: device staging for one piece, [piece][C] interleaved or C planes of `piece` values
+    if (pcm16)
+        for (Item& it : its)
+            if (it.p->n_samples > 0 &&
+                (rc = ensure(h, it.s->pcm16_stage, (size_t)it.s->n_ch * it.s->piece * sizeof(int16_t))) != CSS_OK) return rc;
     std::vector<Item*> act;
     std::vector<SegJob> sj;
     std::vector<TailJob> tj;
+    std::vector<StreamIngestPcm16> ing;
     for (size_t round = 0;; ++round) {
         act.clear();
         for (Item& it : its)
             if (it.done < it.p->n_samples) act.push_back(&it);
         if (act.empty()) break;
+        ing.clear();
         for (Item* it : act) {
             StreamState* s = it->s;
             const int C = s->n_ch;
@@ -742,17 +778,33 @@ int css_stream_push_many(css_handle_t h, CssStreamPush* items, int32_t n_items, 
                     return fail(h, CSS_ERR_STATE, "stream window overflow");
             }
             const int64_t sb = s->seg_base * s->hop * hopS;
+            float* win = (float*)s->pcm[s->cur].p + (s->n_pushed - sb);
+            if (pcm16) {
+                int16_t* stage = (int16_t*)s->pcm16_stage.p;
+                if (it->planar)
+                    HIPCHK(h, hipMemcpy2DAsync(stage, (size_t)s->piece * sizeof(int16_t), it->p->i16 + it->done,
+                                               (size_t)it->p->channel_stride * sizeof(int16_t), (size_t)n * sizeof(int16_t), (size_t)C,
+                                               hipMemcpyHostToDevice, h->stream));
+                else
+                    HIPCHK(h, hipMemcpyAsync(stage, it->p->i16 + it->done * C, (size_t)n * C * sizeof(int16_t), hipMemcpyHostToDevice, h->stream));
+                ing.push_back(StreamIngestPcm16{stage, it->planar ? s->piece : 0, n, C, win, s->WS});
+                continue;
+            }
             // samples -> the window, channel-major (a plain copy: the transform reads the same values css_run's does)
-            const float* src = it->p->pcm_host + it->done * C;
+            const float* src = it->p->f32 + it->done * C;
             for (int ch = 0; ch < C; ++ch) {
                 float* d = s->host_cm.data() + (size_t)ch * n;
                 for (int64_t i = 0; i < n; ++i) d[i] = src[i * C + ch];
             }
-            HIPCHK(h, hipMemcpy2DAsync((float*)s->pcm[s->cur].p + (s->n_pushed - sb), (size_t)s->WS * sizeof(float), s->host_cm.data(),
+            HIPCHK(h, hipMemcpy2DAsync(win, (size_t)s->WS * sizeof(float), s->host_cm.data(),
                                        (size_t)n * sizeof(float), (size_t)n * sizeof(float), (size_t)C, hipMemcpyHostToDevice, h->stream));
         }
-        // the staging buffers are reused by the next round
-        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (pcm16) {
+            launch_stream_ingest_pcm16_multi(ing.data(), (int)ing.size(), h->stream);
+        } else {
+            // the staging buffers are reused by the next round
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+        }
         sj.clear(); tj.clear();
         for (Item* it : act) {
             StreamState* s = it->s;
@@ -792,9 +844,33 @@ int css_stream_push_many(css_handle_t h, CssStreamPush* items, int32_t n_items, 
     HIPCHK(h, hipStreamSynchronize(h->stream));
     for (Item& it : its) {
         it.s->n_emitted += it.emitted;
-        it.p->n_out = it.emitted;
+        *it.p->n_out = it.emitted;
     }
     return hand_out();
+}
+
+}  // namespace
+
+int css_stream_push_many(css_handle_t h, CssStreamPush* items, int32_t n_items, CssStreamGroupStats* stats) {
+    if (!h) return CSS_ERR_INVALID_ARG;
+    if (n_items < 0 || (n_items > 0 && !items)) return fail(h, CSS_ERR_INVALID_ARG, "bad argument");
+    std::vector<PushItem> v((size_t)n_items);
+    for (int32_t i = 0; i < n_items; ++i) {
+        CssStreamPush& p = items[i];
+        v[(size_t)i] = PushItem{p.id, p.pcm_host, nullptr, 0, 0, p.n_samples, p.out_host, p.cap, &p.n_out};
+    }
+    return push_items(h, v, false, stats);
+}
+
+int css_stream_push_many_pcm16(css_handle_t h, CssStreamPushPcm16* items, int32_t n_items, CssStreamGroupStats* stats) {
+    if (!h) return CSS_ERR_INVALID_ARG;
+    if (n_items < 0 || (n_items > 0 && !items)) return fail(h, CSS_ERR_INVALID_ARG, "bad argument");
+    std::vector<PushItem> v((size_t)n_items);
+    for (int32_t i = 0; i < n_items; ++i) {
+        CssStreamPushPcm16& p = items[i];
+        v[(size_t)i] = PushItem{p.id, nullptr, p.pcm16_host, p.sample_stride, p.channel_stride, p.n_samples, p.out_host, p.cap, &p.n_out};
+    }
+    return push_items(h, v, true, stats);
 }
 
 // a group of one item
@@ -803,6 +879,16 @@ int css_stream_push(css_handle_t h, int32_t id, const float* pcm_host, int64_t n
     if (!n_out) return fail(h, CSS_ERR_INVALID_ARG, "bad argument");
     CssStreamPush p{id, pcm_host, n_samples, out_host, cap, 0};
     const int rc = css_stream_push_many(h, &p, 1, nullptr);
+    if (rc == CSS_OK) *n_out = p.n_out;
+    return rc;
+}
+
+int css_stream_push_pcm16(css_handle_t h, int32_t id, const int16_t* pcm16_host, int64_t n_samples, int64_t sample_stride,
+                          int64_t channel_stride, float* out_host, int64_t cap, int64_t* n_out) {
+    if (!h) return CSS_ERR_INVALID_ARG;
+    if (!n_out) return fail(h, CSS_ERR_INVALID_ARG, "bad argument");
+    CssStreamPushPcm16 p{id, pcm16_host, n_samples, sample_stride, channel_stride, out_host, cap, 0};
+    const int rc = css_stream_push_many_pcm16(h, &p, 1, nullptr);
     if (rc == CSS_OK) *n_out = p.n_out;
     return rc;
 }

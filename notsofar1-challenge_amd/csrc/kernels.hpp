@@ -326,5 +326,11 @@ void launch_stream_gate_ola_multi(const StreamStitchArgs* a, const StreamFrames*
 // n_cols) of src (leading dimension src_ld) to dst[row * dst_ld + c], c < n_cols.  A pure copy, any number of entries.
 struct MaskScatter { float* dst; int64_t dst_ld; int64_t src_col; int64_t n_cols; };
 void launch_stream_scatter_masks(const float* src, int64_t src_ld, int rows, const MaskScatter* e, int n, hipStream_t s);
+// PCM16 pieces of a round (css_stream_push_many_pcm16) -> the streams' sample windows: dst[c * dst_ld + i] = (float)q[i][c] * 2^-15
+// for i < n, c < C.  src is device staging, 16-byte aligned: interleaved [n][C] (plane_ld = 0), or planar with channel c at
+// src + c * plane_ld (one channel is planar with any plane_ld).  One launch per STREAM_MULTI_MAX entries; all entries of a
+// call have the handle's channel count.
+struct StreamIngestPcm16 { const int16_t* src; int64_t plane_ld; int64_t n; int C; float* dst; int64_t dst_ld; };
+void launch_stream_ingest_pcm16_multi(const StreamIngestPcm16* e, int n, hipStream_t s);
 
 }  // namespace css

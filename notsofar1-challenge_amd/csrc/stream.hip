@@ -11,6 +11,7 @@
 // by value, blockIdx.z selects the entry, blocks past an entry's range return at once.  One stream is a table of one entry,
 // so there is one copy of each body and one kernel for css_stream_push, css_stream_push_many and css_stream_finish.
 //   stream_scatter_masks_kernel   the mask columns of an estimator batch shared by several streams -> each stream's window
+//   stream_ingest_pcm16_kernel    the int16 pieces of a round, interleaved or planar -> float32 rows of each stream's window
 #include <algorithm>
 #include <climits>
 
@@ -165,6 +166,61 @@ __global__ __launch_bounds__(64 * SC_ROWS) void stream_scatter_masks_kernel(cons
     const float* __restrict__ in = src + (int64_t)row * src_ld + e.src_col;
     float* __restrict__ out = e.dst + (int64_t)row * e.dst_ld;
     for (int64_t c = lane; c < e.n_cols; c += 64) out[c] = in[c];
+}
+
+// The PCM16 pieces of a round (css_stream_push_many_pcm16): int16 in device staging -> float32 rows of each stream's sample
+// window, the scaling of pcm16_to_cm_kernel ((float)q * 2^-15, exact).  A table launch: blockIdx.y = entry, a block takes
+// `tile` samples of all channels, blocks past an entry's n return at once.  A planar entry (and one channel) needs no LDS:
+// lane i converts sample i of a channel, a wave reads 128 contiguous bytes and writes 64 consecutive dwords.  An interleaved
+// row is 2 C bytes (14 for 7 channels), so the block copies its contiguous span of tile * C values into LDS with 16-byte
+// loads (tile is a multiple of 8 and the staging 16-byte aligned, so every span starts aligned; the last values of the last
+// span go one by one) and then writes channel after channel from there.  The destination column is arbitrary mod 4 (any
+// number of samples was pushed before), so the stores are dwords, 64 consecutive ones per wave, as in
+// stream_scatter_masks_kernel.
+constexpr int IN_THREADS = 256, IN_TILE_MAX = 1024, IN_LDS_MAX = 32768;
+struct StreamIngestTable { StreamIngestPcm16 e[STREAM_MULTI_MAX]; };
+__global__ __launch_bounds__(IN_THREADS) void stream_ingest_pcm16_kernel(StreamIngestTable tab, int tile) {
+    extern __shared__ __attribute__((aligned(16))) int16_t span[];   // [tile][C] of an interleaved entry
+    const StreamIngestPcm16 e = tab.e[blockIdx.y];
+    const int64_t i0 = (int64_t)blockIdx.x * tile;
+    if (i0 >= e.n) return;
+    const int nt = (int)(e.n - i0 < tile ? e.n - i0 : tile);
+    const float scale = 1.0f / 32768.0f;
+    float* __restrict__ out = e.dst + i0;
+    if (e.plane_ld > 0 || e.C == 1) {
+        for (int c = 0; c < e.C; ++c) {
+            const int16_t* __restrict__ in = e.src + (int64_t)c * e.plane_ld + i0;
+            float* __restrict__ o = out + (int64_t)c * e.dst_ld;
+            for (int i = threadIdx.x; i < nt; i += IN_THREADS) o[i] = __fmul_rn((float)in[i], scale);
+        }
+        return;
+    }
+    const int total = nt * e.C;
+    const int16_t* __restrict__ in = e.src + i0 * e.C;
+    const uint4* __restrict__ in16 = reinterpret_cast<const uint4*>(in);
+    uint4* span16 = reinterpret_cast<uint4*>(span);
+    for (int v = threadIdx.x; v < total / 8; v += IN_THREADS) span16[v] = in16[v];
+    for (int j = (total & ~7) + threadIdx.x; j < total; j += IN_THREADS) span[j] = in[j];
+    __syncthreads();
+    for (int c = 0; c < e.C; ++c) {
+        float* __restrict__ o = out + (int64_t)c * e.dst_ld;
+        for (int i = threadIdx.x; i < nt; i += IN_THREADS) o[i] = __fmul_rn((float)span[i * e.C + c], scale);
+    }
+}
+
+void launch_stream_ingest_pcm16_multi(const StreamIngestPcm16* e, int n, hipStream_t s) {
+    for (int i0 = 0; i0 < n; i0 += STREAM_MULTI_MAX) {
+        const int cnt = std::min(STREAM_MULTI_MAX, n - i0);
+        StreamIngestTable tab{};
+        int64_t most = 0;
+        int C = 1;
+        for (int i = 0; i < cnt; ++i) { tab.e[i] = e[i0 + i]; most = std::max(most, e[i0 + i].n); C = std::max(C, e[i0 + i].C); }
+        // the largest multiple of 64 samples whose interleaved span fits IN_LDS_MAX (at least 64: C is 1 or 7 here)
+        const int tile = std::max(64, std::min(IN_TILE_MAX, IN_LDS_MAX / (2 * C) / 64 * 64));
+        if (most > 0)
+            hipLaunchKernelGGL(stream_ingest_pcm16_kernel, dim3((unsigned)((most + tile - 1) / tile), cnt), dim3(IN_THREADS),
+                               (size_t)tile * C * sizeof(int16_t), s, tab, tile);
+    }
 }
 
 void launch_stream_activity_multi(const StreamStitchArgs* a, const StreamFrames* r, int n, hipStream_t s) {

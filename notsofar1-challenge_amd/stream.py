@@ -9,6 +9,10 @@ segmentation (``latency_samples``: 3.6 s with the default 3 s / 1.5 s segments).
 complete in that call share the mask estimator's batches, so N live meetings cost about one estimator pass per tick instead
 of N.  Every stream's output is what its own ``push`` would have returned, bit for bit.
 
+``push_pcm16`` on both takes 16-bit PCM as a capture device or a decoder delivers it -- int16 [n, C] interleaved, or the planar
+view ``planes.T`` of C mono recordings -- moves it to the device as int16 and scales and de-interleaves it there
+(css_stream_push_pcm16, css_stream_push_many_pcm16): the result is that of ``push(chunk.astype(float32) / 32768)``, bit for bit.
+
 ``CssStream(..., handoff=dict(n_mels=80, pad_frames=8, drop_silence=True))`` switches the hand-off to the ASR front end on
 (css_stream_handoff_*): after every ``push`` / ``finish`` / grouped push, ``stream.handoff`` holds what became final in that
 call -- raw Whisper log-mel frames, the kept sample ranges and the gate bits per separated stream (``Handoff``).  All calls'
@@ -35,6 +39,28 @@ def whisper_normalize(raw: np.ndarray, raw_max: Optional[float] = None) -> np.nd
         return raw.copy()
     mx = np.float32(raw.max() if raw_max is None else raw_max)
     return (np.maximum(raw, mx - np.float32(8.0)) + np.float32(4.0)) * np.float32(0.25)
+
+
+def pcm16_layout(chunk, num_channels: int):
+    """int16 samples [n, C] (or [n] for one channel) -> (array, sample_stride, channel_stride) as css_stream_push_pcm16 takes
+    them (strides in elements): a C-contiguous [n, C] array is interleaved (C, 1); the transposed view of a [C, n] array --
+    ``planes.T``, or a slice of it, ``planes[:, a:b].T`` -- is planar (1, row pitch of ``planes``).  Both are passed on as
+    they are; any other layout is copied to C-contiguous once.  Other dtypes raise TypeError: there is no silent conversion."""
+    a = np.asarray(chunk)
+    if a.dtype != np.int16:
+        raise TypeError(f"push_pcm16 takes int16 samples, got {a.dtype} (push takes float sample values)")
+    if a.ndim == 1:
+        a = a[:, None]
+    C_ = int(num_channels)
+    if a.ndim != 2 or a.shape[1] != C_:
+        raise ValueError(f"expected [n, {C_}] samples, got {a.shape}")
+    n = a.shape[0]
+    if a.flags.c_contiguous and a.flags.aligned:
+        return a, C_, 1
+    cs = a.strides[1] // 2   # (a planar view: consecutive samples of a channel, channels a row pitch apart)
+    if n >= 1 and a.flags.aligned and (n == 1 or a.strides[0] == 2) and a.strides[1] == 2 * cs and cs >= n:
+        return a, 1, cs
+    return np.ascontiguousarray(a), C_, 1
 
 
 class Handoff:
@@ -147,6 +173,19 @@ class CssStream:
         self._handoff_take()
         return [out[s, :n_out.value].copy() for s in range(self.num_spks)]
 
+    def push_pcm16(self, chunk) -> List[np.ndarray]:
+        """``push`` for int16 samples [n, C] (interleaved, or the planar view ``planes.T``: ``pcm16_layout``): what ``push`` of
+        ``chunk.astype(float32) / 32768`` returns, bit for bit; the samples are scaled and de-interleaved on the device."""
+        x, ss, cs = pcm16_layout(chunk, self.num_channels)
+        n = x.shape[0]
+        out = self._buffer(n + self.latency_samples)
+        n_out = C.c_int64(0)
+        self._handoff_bind(n)
+        _lib.check(self._h.h, self._h.lib.css_stream_push_pcm16(self._h.h, self.id, C.c_void_p(x.ctypes.data), n, ss, cs,
+                                                                out.ctypes.data_as(C.c_void_p), out.shape[1], C.byref(n_out)))
+        self._handoff_take()
+        return [out[s, :n_out.value].copy() for s in range(self.num_spks)]
+
     def finish(self) -> List[np.ndarray]:
         inf = self.info()
         rest = _lib.plan(self.separator.desc, self._run_cfg, inf.n_pushed).n_out - inf.n_emitted
@@ -187,16 +226,27 @@ class CssStreamGroup:
         self._h = self.streams[0]._h
         self.stats = _lib.CssStreamGroupStats()
 
-    def push(self, chunks: Union[Mapping[CssStream, object], Sequence[object]]) -> List[List[np.ndarray]]:
+    def _per_stream(self, chunks) -> list:
         if isinstance(chunks, Mapping):
             if any(s not in self.streams for s in chunks):
                 raise ValueError("a chunk for a stream that is not in this group")
-            per = [chunks.get(s) for s in self.streams]
-        else:
-            per = list(chunks)
-            if len(per) != len(self.streams):
-                raise ValueError(f"expected {len(self.streams)} chunks (None: the stream takes no part), got {len(per)}")
-        part = [(s, s._samples(c)) for s, c in zip(self.streams, per) if c is not None]
+            return [chunks.get(s) for s in self.streams]
+        per = list(chunks)
+        if len(per) != len(self.streams):
+            raise ValueError(f"expected {len(self.streams)} chunks (None: the stream takes no part), got {len(per)}")
+        return per
+
+    def _call(self, fn, items, part, outs) -> List[List[np.ndarray]]:
+        stats = _lib.CssStreamGroupStats()
+        _lib.check(self._h.h, fn(self._h.h, items, len(part), C.byref(stats)))
+        self.stats = stats
+        for s, _ in part:
+            s._handoff_take()
+        got = {id(s): [out[k, :it.n_out].copy() for k in range(s.num_spks)] for it, (s, _), out in zip(items, part, outs)}
+        return [got.get(id(s), [np.empty(0, np.float32) for _ in range(s.num_spks)]) for s in self.streams]
+
+    def push(self, chunks: Union[Mapping[CssStream, object], Sequence[object]]) -> List[List[np.ndarray]]:
+        part = [(s, s._samples(c)) for s, c in zip(self.streams, self._per_stream(chunks)) if c is not None]
         items = (_lib.CssStreamPush * max(len(part), 1))()
         outs = []
         for it, (s, x) in zip(items, part):
@@ -205,10 +255,17 @@ class CssStreamGroup:
             it.id, it.pcm_host, it.n_samples = s.id, x.ctypes.data, x.shape[0]
             it.out_host, it.cap, it.n_out = out.ctypes.data, out.shape[1], 0
             s._handoff_bind(x.shape[0])
-        stats = _lib.CssStreamGroupStats()
-        _lib.check(self._h.h, self._h.lib.css_stream_push_many(self._h.h, items, len(part), C.byref(stats)))
-        self.stats = stats
-        for s, _ in part:
-            s._handoff_take()
-        got = {id(s): [out[k, :it.n_out].copy() for k in range(s.num_spks)] for it, (s, _), out in zip(items, part, outs)}
-        return [got.get(id(s), [np.empty(0, np.float32) for _ in range(s.num_spks)]) for s in self.streams]
+        return self._call(self._h.lib.css_stream_push_many, items, part, outs)
+
+    def push_pcm16(self, chunks: Union[Mapping[CssStream, object], Sequence[object]]) -> List[List[np.ndarray]]:
+        """``push`` for int16 chunks (``CssStream.push_pcm16``): one css_stream_push_many_pcm16 for the group."""
+        part = [(s, pcm16_layout(c, s.num_channels)) for s, c in zip(self.streams, self._per_stream(chunks)) if c is not None]
+        items = (_lib.CssStreamPushPcm16 * max(len(part), 1))()
+        outs = []
+        for it, (s, (x, ss, cs)) in zip(items, part):
+            out = s._buffer(x.shape[0] + s.latency_samples)
+            outs.append(out)
+            it.id, it.pcm16_host, it.n_samples, it.sample_stride, it.channel_stride = s.id, x.ctypes.data, x.shape[0], ss, cs
+            it.out_host, it.cap, it.n_out = out.ctypes.data, out.shape[1], 0
+            s._handoff_bind(x.shape[0])
+        return self._call(self._h.lib.css_stream_push_many_pcm16, items, part, outs)

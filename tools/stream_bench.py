@@ -14,6 +14,11 @@ per round, streams served in real time per GPU (1.5 s / round time x N), bit_ide
 
 With --handoff every stream has the hand-off to the ASR front end switched on (80 bands, pad 8, drop silence): the rounds
 then also return log-mel frames, kept ranges and gate bits (profiles/r10_stream_handoff.json).  --only-grouped runs arm B alone.
+
+With --pcm16 the recordings are 16-bit PCM (quantised at 0.2 of full scale) and the arms that alternate are B, fed the
+dequantised float32 samples, and (C) one css_stream_push_many_pcm16 per round on the int16 samples themselves, interleaved
+as a capture device delivers them (--pinned: in page-locked memory).  Every arm's input is laid out before the clock starts;
+every arm is compared with css_run of the dequantised recording (profiles/r11_stream_pcm16.json).
 """
 import argparse
 import json
@@ -33,7 +38,8 @@ FS = 16000
 HANDOFF = dict(n_mels=80, pad_frames=8, drop_silence=True)
 
 
-def group_bench(n_streams, out_path, seconds=60.0, round_s=1.5, block=5, passes=2, handoff=False, only_grouped=False):
+def group_bench(n_streams, out_path, seconds=60.0, round_s=1.5, block=5, passes=2, handoff=False, only_grouped=False, pcm16=False,
+                pinned=False):
     import notsofar1_challenge_amd.css as CSS
     import notsofar1_challenge_amd.separator as SEP
     import notsofar1_challenge_amd.stream as STR
@@ -45,11 +51,19 @@ def group_bench(n_streams, out_path, seconds=60.0, round_s=1.5, block=5, passes=
     cfg = CSS.CssCfg()
     rc = CSS.make_run_cfg(cfg, FS, 7)
     recs = [np.ascontiguousarray(SYN.synth_meeting(seconds, 7, seed=1000 + i)[0]) for i in range(n_streams)]
+    q16 = []
+    if pcm16:
+        import notsofar1_challenge_amd._lib as LIB
+        q16 = [np.clip(np.rint(x.astype(np.float64) * 0.2 * 32768.0), -32768, 32767).astype(np.int16) for x in recs]
+        recs = [np.ascontiguousarray(q.astype(np.float32) / np.float32(32768.0)) for q in q16]
+        if pinned:
+            q16 = [LIB.pinned_copy(q) for q in q16]
     sep.handle.run(recs[0][:FS * 10], rc)   # warm-up
     refs = [sep.handle.run(x, rc).copy() for x in recs]
     step = int(round_s * FS)
-    ms = {"A": [], "B": []}
-    same = {"A": True, "B": True}
+    arms = "BC" if pcm16 else "AB"
+    ms = {"A": [], "B": [], "C": []}
+    same = {"A": True, "B": True, "C": True}
     seg_per_batch = []
     mel_frames = []
 
@@ -59,18 +73,20 @@ def group_bench(n_streams, out_path, seconds=60.0, round_s=1.5, block=5, passes=
         em = [0] * n_streams
         n_rounds = (recs[0].shape[0] + step - 1) // step if timed else 2 * block
         for r in range(n_rounds):
-            arm = "B" if only_grouped else "AB"[(r // block + (first_arm == "B")) % 2]
-            chunks = [x[r * step:(r + 1) * step] for x in recs]
+            arm = "B" if only_grouped else arms[(r // block + (first_arm == arms[1])) % 2]
+            chunks = [x[r * step:(r + 1) * step] for x in (q16 if arm == "C" else recs)]
             t = time.perf_counter()
             if arm == "A":
                 res = [s.push(c) for s, c in zip(streams, chunks)]
+            elif arm == "C":
+                res = group.push_pcm16(chunks)
             else:
                 res = group.push(chunks)
             dt = time.perf_counter() - t
             if not timed:
                 continue
             ms[arm].append(dt * 1e3)
-            if arm == "B" and group.stats.estimator_batches:
+            if arm != "A" and group.stats.estimator_batches:
                 seg_per_batch.append(group.stats.estimator_segments / group.stats.estimator_batches)
             if handoff:
                 mel_frames.append(sum(m.shape[1] for s in streams for m in s.handoff.mel))
@@ -82,23 +98,28 @@ def group_bench(n_streams, out_path, seconds=60.0, round_s=1.5, block=5, passes=
             for i, s in enumerate(streams):
                 got = np.stack(s.finish())
                 ok = bool(np.array_equal(got, refs[i][:, em[i]:])) and em[i] + got.shape[1] == refs[i].shape[1]
-                same["A"], same["B"] = same["A"] and ok, same["B"] and ok
+                for a in same:
+                    same[a] = same[a] and ok
         dev = streams[0].info().device_bytes
         for s in streams:
             s.close()
         return dev
 
-    one_pass("A", False)   # warm-up: both arms, segments included
+    one_pass(arms[0], False)   # warm-up: both arms, segments included
     dev = 0
     for p in range(passes):
-        dev = one_pass("AB"[p % 2], True)
+        dev = one_pass(arms[p % 2], True)
     res = {"model": "mc_v1 (18 blocks, exact float32)", "cfg": "3 s / 1.5 s segments, defaults", "streams": n_streams,
            "meeting_s": seconds, "round_s": round_s, "block_rounds": block, "device_bytes_per_stream": int(dev),
            "segments_per_estimator_batch_median": float(np.median(seg_per_batch)) if seg_per_batch else 0.0, "arms": {}}
     if handoff:
         res["handoff"] = dict(HANDOFF, mel_frames_per_round_median=float(np.median(mel_frames)),
                               launches_products_frames_last_call=list(sep.handle.stream_handoff_stats()))
-    for arm, what in (("A", "one css_stream_push per stream and round"), ("B", "one css_stream_push_many per round")):
+    if pcm16:
+        res["input"] = "16-bit PCM at 0.2 of full scale; arm B is fed the dequantised float32 samples, arm C the int16 samples (%s)" % (
+            "page-locked" if pinned else "pageable")
+    for arm, what in (("A", "one css_stream_push per stream and round"), ("B", "one css_stream_push_many per round"),
+                      ("C", "one css_stream_push_many_pcm16 per round")):
         if not ms[arm]:
             continue
         v = np.array(ms[arm])
@@ -106,6 +127,8 @@ def group_bench(n_streams, out_path, seconds=60.0, round_s=1.5, block=5, passes=
         res["arms"][arm] = {"what": what, "rounds": int(v.size), "round_ms_p50": round(p50, 3),
                             "round_ms_p99": round(float(np.percentile(v, 99)), 3),
                             "streams_in_real_time_per_gpu": round(round_s * 1e3 / p50 * n_streams, 1), "bit_identical": same[arm]}
+    if "C" in res["arms"]:
+        res["p50_ratio_C_over_B"] = round(res["arms"]["C"]["round_ms_p50"] / res["arms"]["B"]["round_ms_p50"], 4)
     if "A" in res["arms"]:
         res["p50_ratio_B_over_A"] = round(res["arms"]["B"]["round_ms_p50"] / res["arms"]["A"]["round_ms_p50"], 4)
     sep.close()
@@ -123,10 +146,12 @@ def main():
     ap.add_argument("--streams", type=int, default=0, help="grouped pushes: N live meetings, per-stream pushes against one grouped push per round")
     ap.add_argument("--handoff", action="store_true", help="with --streams: every stream returns log-mel frames, kept ranges and gate bits")
     ap.add_argument("--only-grouped", action="store_true", help="with --streams: arm B alone (twice the rounds)")
+    ap.add_argument("--pcm16", action="store_true", help="with --streams: arms B (float32) and C (css_stream_push_many_pcm16) on 16-bit recordings")
+    ap.add_argument("--pinned", action="store_true", help="with --pcm16: arm C's int16 samples in page-locked memory")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.streams:
-        return group_bench(a.streams, a.out, handoff=a.handoff, only_grouped=a.only_grouped)
+        return group_bench(a.streams, a.out, handoff=a.handoff, only_grouped=a.only_grouped, pcm16=a.pcm16, pinned=a.pinned)
     import notsofar1_challenge_amd.css as CSS
     import notsofar1_challenge_amd.separator as SEP
     import notsofar1_challenge_amd.stream as STR
