@@ -361,6 +361,40 @@ int css_check_range(css_handle_t h);
  * 32 / 64 / 96 / 4 / 128; kernels 1, 2: 8 / 4 / 64).  For unit tests of the arithmetic; not on the hot path. */
 int css_linear_host(css_handle_t h, const float* x, const float* w, const float* bias, int32_t M, int32_t N, int32_t K,
                     int32_t kernel, int32_t layout, float* y);
+/* One launch of a GEMM kernel of the path in ANY of its forms, on caller data:
+ *   C[bz][m][n] = residual[m][n] + alpha * act( sum_k A[bz][m][k] B[bz][n][k] + bias )     (without a residual: act(...))
+ * kernel as in css_linear_host; layout forces a tile layout of kernels 1 and 2 (8 / 4 / 64; kernel 2 also 1 = the persistent
+ * float32 kernel, 2 = the LDS-staged one with its own choice, 11 .. 14 = the persistent one with tiles of 32 .. 128 rows),
+ * tile_rows one of kernel 0 (32 / 64 / 96 / 128 / 4 / 65); 0 = the launcher's choice.
+ *   a, b        row-major float32, rows lda / ldb apart (multiples of 4, >= K; K % 32 == 0); batch entry bz starts strideA /
+ *               strideB floats further (0: one matrix shared by all entries).  The matrix A starts a_off floats into a: the
+ *               library places a on a 16-byte boundary of the device, so a_off % 4 != 0 is a misaligned operand.  Kernels 0
+ *               and 1 read split-f16 copies the call makes of A and B (the copies are aligned whatever a_off is).
+ *   c           the WHOLE output allocation, c_floats floats: uploaded before the launch and downloaded in full after it, so
+ *               that the caller sees every float the launch did not own.  C starts c_off floats into it, rows ldc apart,
+ *               entries strideC apart.  c_transposed (kernel 0): C^T[n][m] at c_off + n * ldc + m.
+ *   bias        0 none, 1 bias[N] along the columns, 2 bias[M] along the rows
+ *   residual    0 none, 1 the array `residual` (r_floats floats, the matrix r_off floats into it, rows ldr apart, shared by all
+ *               batch entries), 2 C itself (the in-place form x = x + alpha * (...); batch 1)
+ *   act         0 none, 1 ReLU, 2 sigmoid
+ *   b_frag32    kernel 2: the weight in the float32 fragment order the Linear layers of CSS_LINEAR_EXACT_F32 use, built here
+ *               from b; the row-major b is handed along as the launch's fallback operand (batch 1, N % 32 == 0)
+ *   split_out   kernels 0, 1: columns [0, split_out) of C leave in the split-f16 format (a multiple of 32, <= N)
+ *   m_fastest, nt_store, concurrent   the launch hints of the same names, passed on
+ * CSS_ERR_INVALID_ARG for anything a kernel excludes: kernel 0 with batch > 1, N % 32, or a C that is not made of 16-byte
+ * pieces (c_off % 4, ldc % 4; the transposed form writes single floats and takes any); c_transposed with a residual, a split
+ * output, a row bias or another kernel; split_out or b_frag32 on the wrong kernel; an array shorter than its description;
+ * batch entries of C that overlap.  The attention's fragment output is not reachable.  For unit tests of the arithmetic; not
+ * on the hot path. */
+typedef struct CssGemmDesc {
+    int32_t kernel, layout, tile_rows, batch, M, N, K, act;
+    int64_t lda, ldb, ldc, ldr, strideA, strideB, strideC, a_off, c_off, r_off, a_floats, b_floats, c_floats, r_floats;
+    int32_t bias, residual;
+    float alpha;
+    int32_t b_frag32, split_out, c_transposed, m_fastest, nt_store, concurrent;
+} CssGemmDesc;
+int css_gemm_host(css_handle_t h, const CssGemmDesc* d, const float* a, const float* b, const float* bias, const float* residual,
+                  float* c);
 int css_get_plan(css_handle_t h, CssPlan* out);
 
 /* ---- stages (each replaces one reference function; state lives in the handle) -------------- */

@@ -105,6 +105,14 @@ class CssStreamHandoffOut(C.Structure):
                 ("raw_max", C.c_void_p), ("n_activity", C.c_int64), ("first_activity_frame", C.c_int64)]
 
 
+class CssGemmDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("kernel", "layout", "tile_rows", "batch", "M", "N", "K", "act")] + \
+               [(n, C.c_int64) for n in ("lda", "ldb", "ldc", "ldr", "strideA", "strideB", "strideC", "a_off", "c_off", "r_off",
+                                         "a_floats", "b_floats", "c_floats", "r_floats")] + \
+               [("bias", C.c_int32), ("residual", C.c_int32), ("alpha", C.c_float)] + \
+               [(n, C.c_int32) for n in ("b_frag32", "split_out", "c_transposed", "m_fastest", "nt_store", "concurrent")]
+
+
 class CssKernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("ms", C.c_float), ("launches", C.c_int32)]
 
@@ -151,6 +159,7 @@ SIGNATURES = {
     "css_range_status": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "css_check_range": (C.c_int, [_P]),
     "css_linear_host": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "css_gemm_host": (C.c_int, [_P, C.POINTER(CssGemmDesc), _P, _P, _P, _P, _P]),
     "css_get_plan": (C.c_int, [_P, C.POINTER(CssPlan)]),
     "css_begin": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.POINTER(CssRunCfg), C.c_int]),
     "css_begin_range": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.POINTER(CssRunCfg), C.c_int64, C.c_int64]),
@@ -598,6 +607,35 @@ class Handle:
         check(self.h, self.lib.css_linear_host(self.h, _np_ptr(x), _np_ptr(w), _np_ptr(b) if b is not None else None,
                                                m, n, k, int(kernel), int(layout), _np_ptr(y)))
         return y
+
+    def gemm(self, a: np.ndarray, b: np.ndarray, c: np.ndarray, M: int, N: int, K: int, *, kernel: int = 2, layout: int = 0,
+             tile_rows: int = 0, batch: int = 1, lda=None, ldb=None, ldc=None, ldr=None, strideA: int = 0, strideB: int = 0,
+             strideC: int = 0, a_off: int = 0, c_off: int = 0, r_off: int = 0, act: int = 0, bias=None, bias_along_m: bool = False,
+             residual=None, alpha: float = 1.0, b_frag32: bool = False, split_out: int = 0, c_transposed: bool = False,
+             m_fastest: bool = False, nt_store: bool = False, concurrent: bool = False) -> np.ndarray:
+        """One GEMM launch of the path in any of its forms (css_gemm_host; the header describes every field).  a, b, c and a
+        separate residual are the WHOLE flat float32 allocations, the matrices a_off / c_off / r_off floats into them;
+        residual = "inplace" is the form C = C + alpha * (...).  Returns c as the launch left it, every float of it."""
+        flat = lambda x: np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+        a, b, out = flat(a), flat(b), flat(c).copy()
+        inplace = isinstance(residual, str)
+        if inplace and residual != "inplace":
+            raise ValueError("residual: None, an array, or 'inplace'")
+        r = None if residual is None or inplace else flat(residual)
+        bv = None if bias is None else flat(bias)
+        d = CssGemmDesc(kernel=int(kernel), layout=int(layout), tile_rows=int(tile_rows), batch=int(batch), M=int(M), N=int(N), K=int(K),
+                        act=int(act), lda=int(K if lda is None else lda), ldb=int(K if ldb is None else ldb),
+                        ldc=int((M if c_transposed else N) if ldc is None else ldc), ldr=int(N if ldr is None else ldr),
+                        strideA=int(strideA), strideB=int(strideB), strideC=int(strideC), a_off=int(a_off), c_off=int(c_off),
+                        r_off=int(r_off), a_floats=a.size, b_floats=b.size, c_floats=out.size, r_floats=0 if r is None else r.size,
+                        bias=0 if bv is None else (2 if bias_along_m else 1), residual=2 if inplace else (0 if r is None else 1),
+                        alpha=float(alpha), b_frag32=int(bool(b_frag32)), split_out=int(split_out), c_transposed=int(bool(c_transposed)),
+                        m_fastest=int(bool(m_fastest)), nt_store=int(bool(nt_store)), concurrent=int(bool(concurrent)))
+        if bv is not None and bv.size != (M if bias_along_m else N):
+            raise ValueError("bias: one value per output column (or per row with bias_along_m)")
+        check(self.h, self.lib.css_gemm_host(self.h, C.byref(d), _np_ptr(a), _np_ptr(b), _np_ptr(bv) if bv is not None else None,
+                                             _np_ptr(r) if r is not None else None, _np_ptr(out)))
+        return out
 
     # ---- RCCL through the C ABI (css_comm_*): what a host in another language would call
     def comm_init(self, unique_id: bytes, nranks: int, rank: int):

@@ -101,6 +101,25 @@ def test_pcm16_stream_is_bit_identical_to_css_run(mc_state, mix60):
     sep.close()
 
 
+def test_short_pieces_at_arbitrary_destination_columns(mc_state):
+    """4 s, 7 channels, pieces of 1, 7, 8, 9, 63, 1023, 1024, 1025 and 2049 samples and then the rest, interleaved and planar: the
+    pieces begin at destination columns 0, 1, 8, 16, 25, 88, 1111, 2135, 3160 and 5209 -- on, one past and well off the edges of
+    the ingest kernel's 16-byte spans -- and their lengths sit on either side of the span and of its tile."""
+    sep = _sep(mc_state)
+    cfg = pkg("css").CssCfg()
+    q = _rec16(4.0, 960)
+    n = q.shape[0]
+    assert q.shape == (64000, 7)
+    planes = np.ascontiguousarray(q.T)
+    ref = _offline(sep, q, cfg)
+    sizes = [1, 7, 8, 9, 63, 1023, 1024, 1025, 2049, n]
+    got = _stream(sep, n, cfg, sizes, ref, lambda s, a, b, i: s.push_pcm16(q[a:b]))
+    assert got.shape == ref.shape and np.array_equal(got, ref)
+    got = _stream(sep, n, cfg, sizes, ref, lambda s, a, b, i: s.push_pcm16(planes[:, a:b].T))
+    assert got.shape == ref.shape and np.array_equal(got, ref)
+    sep.close()
+
+
 def test_float_and_pcm16_pushes_alternate_on_one_stream(mc_state, mix60):
     sep = _sep(mc_state)
     cfg = pkg("css").CssCfg()
