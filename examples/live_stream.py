@@ -12,7 +12,11 @@ collects 3 000 frames per window and normalises each window with whisper_normali
 With --pcm16 the source delivers 16-bit PCM, as a capture device does: the int16 chunks go to push_pcm16 as they are (2 bytes
 per sample over PCIe, scaled and de-interleaved on the device); the result is that of pushing chunk.astype(float32) / 32768.
 
-    python examples/live_stream.py [--seconds 30] [--rooms N] [--logmel] [--pcm16]
+With --rate HZ the source delivers 16-bit PCM at HZ (48000, 44100, 32000, 8000 ...): the stream is opened with input_rate=HZ,
+the int16 chunks cross PCIe as they were captured and the ingest kernel resamples them to the model's 16 kHz
+(scipy.signal.resample_poly's default filter); what comes back stays at 16 kHz.
+
+    python examples/live_stream.py [--seconds 30] [--rooms N] [--logmel] [--pcm16] [--rate HZ]
 """
 import argparse
 import os
@@ -46,11 +50,23 @@ def capture(mix):
     return np.clip(np.rint(mix.astype(np.float64) * 0.2 * 32768.0), -32768, 32767).astype(np.int16)
 
 
-def rooms(sep, n_rooms, seconds, fs, chunk, logmel=False, pcm16=False):
+def capture_at(mix, fs, rate):
+    """the meeting as a 16-bit capture device running at `rate` would have delivered it (linear interpolation of the synthetic
+    16 kHz samples: a stand-in for a real device, not a resampler)"""
+    t = np.arange(int(round(mix.shape[0] * rate / fs))) * (float(fs) / rate)
+    at = np.arange(mix.shape[0])
+    return capture(np.stack([np.interp(t, at, mix[:, c]) for c in range(mix.shape[1])], axis=1))
+
+
+def rooms(sep, n_rooms, seconds, fs, chunk, logmel=False, pcm16=False, rate=None):
     mixes = [SYN.synth_meeting(seconds, 7, seed=1 + r)[0] for r in range(n_rooms)]
-    if pcm16:
+    if rate:
+        mixes = [capture_at(m, fs, rate) for m in mixes]
+        chunk = chunk * rate // fs
+    elif pcm16:
         mixes = [capture(m) for m in mixes]
-    streams = [STR.CssStream(sep, CSS.CssCfg(), fs=fs, num_channels=7, handoff=HANDOFF if logmel else None) for _ in mixes]
+    streams = [STR.CssStream(sep, CSS.CssCfg(), fs=fs, num_channels=7, handoff=HANDOFF if logmel else None, input_rate=rate)
+               for _ in mixes]
     group = STR.CssStreamGroup(streams)
     outs = [[[] for _ in range(sep.desc.num_spks)] for _ in mixes]
     print(f"{n_rooms} rooms, lag bound {streams[0].latency_samples / fs:.2f} s")
@@ -79,22 +95,26 @@ def main():
     ap.add_argument("--rooms", type=int, default=1, help="meetings fed tick by tick through one CssStreamGroup")
     ap.add_argument("--logmel", action="store_true", help="also return Whisper log-mel frames and kept ranges with every tick")
     ap.add_argument("--pcm16", action="store_true", help="the source delivers int16 samples: push_pcm16 instead of push")
+    ap.add_argument("--rate", type=int, default=0, help="the source delivers int16 samples at this rate: CssStream(input_rate=HZ)")
     a = ap.parse_args()
     fs = 16000
+    a.pcm16 = a.pcm16 or bool(a.rate)
     desc = W.ModelDesc.mc_v1()
     sep = SEP.HipSeparator(W.apply_golden_recipe(W.portable_state_dict(desc, 0)), None, device=0)
     if a.rooms > 1:
-        rooms(sep, a.rooms, a.seconds, fs, fs // 2, a.logmel, a.pcm16)
+        rooms(sep, a.rooms, a.seconds, fs, fs // 2, a.logmel, a.pcm16, a.rate or None)
         sep.close()
         return
     mix = SYN.synth_meeting(a.seconds, 7, seed=1)[0]
-    if a.pcm16:
+    if a.rate:
+        mix = capture_at(mix, fs, a.rate)
+    elif a.pcm16:
         mix = capture(mix)
-    chunk = fs // 2
+    chunk = (a.rate or fs) // 2
     streams = [[] for _ in range(desc.num_spks)]
     mels = [[] for _ in range(desc.num_spks)]
-    with STR.CssStream(sep, CSS.CssCfg(), fs=fs, num_channels=7, handoff=HANDOFF if a.logmel else None) as s:
-        print(f"lag bound {s.latency_samples / fs:.2f} s")
+    with STR.CssStream(sep, CSS.CssCfg(), fs=fs, num_channels=7, handoff=HANDOFF if a.logmel else None, input_rate=a.rate or None) as s:
+        print(f"lag bound {s.latency_samples / fs:.2f} s" + (f" + {s.resampler_lag_samples} input samples of the resampler" if s.rate else ""))
         for i in range(0, mix.shape[0], chunk):
             t = time.perf_counter()
             out = (s.push_pcm16 if a.pcm16 else s.push)(mix[i:i + chunk])

@@ -219,6 +219,16 @@ SIGNATURES = {
     "css_buffer_devptr": (C.c_int, [_P, C.c_int, C.POINTER(_P)]),
 }
 
+# the entry points include/css_mi355_rate.h declares (pushes at the capture rate), bound next to the table above
+SIGNATURES_RATE = {
+    "css_stream_set_rate": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32]),
+    "css_stream_rate_samples": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
+    "css_resample_taps": (C.c_int, [C.c_int32, C.c_int32, _P, C.c_int32, C.POINTER(C.c_int32)]),
+    "css_resample_host": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int64,
+                                    C.POINTER(C.c_int64)]),
+}
+RESAMPLE_TILE = 256                              # output samples per block of the two resampling kernels (resample.hip RS_TILE)
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -258,7 +268,7 @@ def load() -> C.CDLL:
         lib = C.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover
         raise CssLibraryError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_RATE.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -327,6 +337,36 @@ def stream_final_samples(desc, run_cfg: RunCfg, n_pushed: int) -> int:
     if rc != CSS_OK:
         raise CssError(rc, "css_stream_final_samples: unsupported frame geometry or bad configuration")
     return int(n.value)
+
+
+def rate_ratio(input_rate: int, fs: int = 16000):
+    """(up, down) = fs / input_rate in lowest terms: 48000 -> (1, 3), 44100 -> (160, 441), 8000 -> (2, 1)"""
+    import math
+    input_rate, fs = int(input_rate), int(fs)
+    if input_rate <= 0 or fs <= 0:
+        raise ValueError("sample rates are positive")
+    g = math.gcd(input_rate, fs)
+    return fs // g, input_rate // g
+
+
+def stream_rate_samples(up: int, down: int, n_in: int, finished: bool = False) -> int:
+    """css_stream_rate_samples: model-rate samples after `n_in` input samples at the ratio up / down (finished: of the whole recording)"""
+    n = C.c_int64()
+    rc = load().css_stream_rate_samples(int(up), int(down), int(n_in), int(bool(finished)), C.byref(n))
+    if rc != CSS_OK:
+        raise CssError(rc, f"css_stream_rate_samples: the ratio {up} / {down} is not supported, or a negative count")
+    return int(n.value)
+
+
+def resample_taps(up: int, down: int) -> np.ndarray:
+    """css_resample_taps: the float32 taps the device uses for the ratio up / down (scipy.signal.resample_poly's default filter)"""
+    n = C.c_int32()
+    load().css_resample_taps(int(up), int(down), None, 0, C.byref(n))
+    taps = np.empty(max(n.value, 1), np.float32)
+    rc = load().css_resample_taps(int(up), int(down), _np_ptr(taps), taps.size, C.byref(n))
+    if rc != CSS_OK:
+        raise CssError(rc, f"css_resample_taps: the ratio {up} / {down} is not supported")
+    return taps[:n.value]
 
 
 def handoff_cfg(n_mels: int = 80, pad_frames: int = 8, drop_silence: bool = True) -> CssStreamHandoffCfg:
@@ -791,6 +831,35 @@ class Handle:
                                                   max_regions, C.byref(nreg)))
         del mel
         return flat[:n_mels * nfr.value].reshape(n_mels, nfr.value).copy(), regions[:nreg.value].copy()
+
+    def resample(self, x, input_rate: int, fs: int = 16000) -> np.ndarray:
+        """A recording at `input_rate` -> float32 [n_out, C] at `fs` on the device (css_resample_host): the samples a stream opened
+        with ``input_rate`` forms from the same input, bit for bit -- scipy.signal.resample_poly's default filter in float32.
+        `x`: float32 or int16, [n, C] or [n]; a C-contiguous array and the planar view ``planes.T`` are passed on as they are
+        (stream.pcm16_layout's rule), anything else is copied once.  int16 samples count as q / 32768."""
+        a = np.asarray(x)
+        if a.dtype not in (np.int16, np.float32):
+            a = a.astype(np.float32)
+        if a.ndim == 1:
+            a = a[:, None]
+        if a.ndim != 2:
+            raise ValueError(f"expected [n, C] or [n] samples, got {a.shape}")
+        n, c = a.shape
+        up, down = rate_ratio(input_rate, fs)
+        el = a.dtype.itemsize
+        if a.flags.c_contiguous and a.flags.aligned:
+            ss, cs = c, 1
+        elif n >= 1 and a.flags.aligned and (n == 1 or a.strides[0] == el) and a.strides[1] % el == 0 and a.strides[1] // el >= n:
+            ss, cs = 1, a.strides[1] // el
+        else:
+            a, ss, cs = np.ascontiguousarray(a), c, 1
+        m = stream_rate_samples(up, down, n, True)
+        out = np.empty((m, c), np.float32)
+        n_out = C.c_int64()
+        check(self.h, self.lib.css_resample_host(self.h, C.c_void_p(a.ctypes.data), int(a.dtype == np.int16), n, c, ss, cs, up, down,
+                                                 _np_ptr(out), m, C.byref(n_out)))
+        assert n_out.value == m
+        return out
 
     def stream_handoff_stats(self):
         """(hand-off launches, DFT products among them, operand frames) of the last stream call on this handle"""

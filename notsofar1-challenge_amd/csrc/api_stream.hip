@@ -24,7 +24,13 @@
 // bits, the kept sample ranges and the raw Whisper log-mel frames that became final.  The step sits between tail() and the
 // downloads of a round: three launches for all streams of the round (handoff.hip: append, ONE DFT product, mel), results
 // into page-locked staging under the call's final synchronise, where the host trims them into the caller's buffers.
+//
+// A stream with a rate ratio (css_stream_set_rate, include/css_mi355_rate.h) takes its pushes at the capture rate:
+// a piece is copied as the caller laid it out into the stream's device staging and ONE launch per round (resample.hip) filters,
+// decimates and de-interleaves the rate streams' pieces into their windows.  Everything behind the window is unchanged and
+// counts model-rate samples; the call's checks are evaluated on the model-rate samples its inputs make computable.
 #include "api_ctx.hpp"
+#include "../../include/css_mi355_rate.h"
 
 #include <climits>
 
@@ -59,8 +65,22 @@ struct HandoffCtx {
 };
 constexpr size_t HO_DFT_F = (size_t)402 * 416, HO_MEL80_F = (size_t)80 * 201, HO_MEL128_F = (size_t)128 * 201;
 
+// Per stream with a rate ratio (css_stream_set_rate; resample.hip).  Nothing here is part of the window: the rebase never touches
+// it.  n_in inputs have arrived and all avail(n_in) model-rate samples they make computable are in the window (that count IS
+// the stream's n_pushed); hist[cur] holds inputs [n_in - H, n_in) as float, channel-major (zeros before the recording's start),
+// and every later output reads no earlier input: output avail(n_in) needs an input that has not arrived, and a chain is P <= H
+// inputs long.
+struct RateStream {
+    ResampleRatio r{};
+    int H = 0;                          // carried inputs per channel: ceil(2 half / up) + 1
+    int64_t n_in = 0, max_in = 0;       // inputs so far; the most a piece takes
+    int cur = 0;
+    DevBuf stage, hist[2], tab;         // one piece as the caller laid it out (sized for float32); the carried inputs; the taps by phase
+};
+
 struct StreamState {
     HandoffStream* ho = nullptr;
+    RateStream* rate = nullptr;
     CssRunCfg cfg{};
     std::vector<float> w;          // the three windows (cfg.w_* point here)
     int n_ch = 0, T = 0, hop = 0, halo = 0;
@@ -101,6 +121,11 @@ void free_stream(StreamState* s) {
             if (d->p) hipFree(d->p);
         delete s->ho;
     }
+    if (s->rate) {
+        for (DevBuf* d : {&s->rate->stage, &s->rate->hist[0], &s->rate->hist[1], &s->rate->tab})
+            if (d->p) hipFree(d->p);
+        delete s->rate;
+    }
     delete s;
 }
 
@@ -113,6 +138,8 @@ int64_t device_bytes(const StreamState* s) {
         for (const DevBuf* d : {&s->ho->gate, &s->ho->carry[0], &s->ho->carry[1], &s->ho->tail[0], &s->ho->tail[1]}) n += (int64_t)d->cap;
         n += (int64_t)(SMAX * sizeof(HandoffState));
     }
+    if (s->rate)
+        for (const DevBuf* d : {&s->rate->stage, &s->rate->hist[0], &s->rate->hist[1], &s->rate->tab}) n += (int64_t)d->cap;
     return n;
 }
 
@@ -567,6 +594,27 @@ int handoff_collect(css_ctx* h, StreamState* s, int item, int64_t t_g_before, co
     return CSS_OK;
 }
 
+// ---- rate streams -----------------------------------------------------------------------------------------------------------
+// model-rate samples in the window once `more` further inputs have arrived (a rate-less stream: its samples are the inputs)
+int64_t model_samples_after(const StreamState* s, int64_t more) {
+    return s->rate ? resample_count(s->rate->r, s->rate->n_in + more, false) : s->n_pushed + more;
+}
+
+// The entry of the resample launch that takes `n_in` inputs staged in s->rate->stage (0 with `flush`: zeros past the end) and
+// writes outputs [n_pushed, m1) at `win`; flips the history's generation (the launch writes the other one).
+ResampleJob rate_job(StreamState* s, bool i16, bool planar, int64_t n_in, int64_t m1, float* win, bool flush) {
+    RateStream* q = s->rate;
+    ResampleJob j{};
+    j.src = q->stage.p; j.is_i16 = i16 ? 1 : 0; j.plane_ld = planar ? q->max_in : 0; j.n = n_in;
+    j.hist_in = (const float*)q->hist[q->cur].p; j.hist_out = flush ? nullptr : (float*)q->hist[1 - q->cur].p; j.H = q->H;
+    j.N0 = q->n_in; j.m0 = s->n_pushed; j.n_m = m1 - s->n_pushed;
+    j.up = q->r.up; j.down = q->r.down; j.half = q->r.half; j.P = q->r.P; j.P_ld = q->r.P_ld; j.tab = (const float*)q->tab.p;
+    j.C = s->n_ch; j.dst = win; j.dst_ld = s->WS;
+    if (!flush) q->cur = 1 - q->cur;
+    q->n_in += n_in;
+    return j;
+}
+
 int check_stream_call(css_ctx* h, int32_t id, StreamState** out) {
     if (!h) return CSS_ERR_INVALID_ARG;
     StreamState* s = get_stream(h, id);
@@ -688,6 +736,10 @@ int css_stream_open(css_handle_t h, const CssRunCfg* cfg, int32_t n_ch, int32_t*
 //            copy into the staging is ordered behind the launch on the stream: no synchronise but the one that ends the call.
 //            (Nothing else leans on the per-round synchronise: the hand-off's page-locked staging is per round of a call, and
 //            every device buffer the rounds share is written and read in stream order.)
+//   a rate stream (either kind of call): the piece, cut in INPUT samples, is copied as it is into the stream's device staging
+//            and ONE table launch per round resamples all rate streams' pieces into their windows (resample.hip
+//            stream_ingest_resample_kernel); the rate-less items of the call take their own route above.  No host buffer,
+//            no synchronise of its own.
 namespace {
 
 struct PushItem {
@@ -698,7 +750,7 @@ struct PushItem {
 };
 
 int push_items(css_ctx* h, const std::vector<PushItem>& items, bool pcm16, CssStreamGroupStats* stats) {
-    struct Item { StreamState* s; const PushItem* p; int64_t done, emitted, n, t_g1, t_g_before; bool planar; };
+    struct Item { StreamState* s; const PushItem* p; int64_t done, emitted, n, t_g1, t_g_before; bool planar; int64_t n_in; };
     std::vector<Item> its(items.size());
     for (size_t i = 0; i < items.size(); ++i) {
         const PushItem& p = items[i];
@@ -724,15 +776,17 @@ int push_items(css_ctx* h, const std::vector<PushItem>& items, bool pcm16, CssSt
                                                    "(sample_stride = 1, channel_stride >= n_samples)");
         }
         if (h->split) return refuse(CSS_ERR_STATE, "streams run in CSS_LINEAR_EXACT_F32 only");
-        const int64_t need = final_frames(s->n_pushed + p.n_samples, s->T, s->hop, s->halo) * h->d.frame_hop - s->n_emitted;
+        // (a rate stream: n_samples counts inputs; every check below is on the model-rate samples they make available)
+        const int64_t n_after = model_samples_after(s, p.n_samples);
+        const int64_t need = final_frames(n_after, s->T, s->hop, s->halo) * h->d.frame_hop - s->n_emitted;
         if (need > 0 && (!p.out_host || p.cap < need))
             return refuse(CSS_ERR_INVALID_ARG, "output capacity too small for the samples this push finalises");
-        if (zero_weight_frames(s, s->t_st, segments_done(frames_of(s->n_pushed + p.n_samples), s->T, s->hop) * s->hop))
+        if (zero_weight_frames(s, s->t_st, segments_done(frames_of(n_after), s->T, s->hop) * s->hop))
             return refuse(CSS_ERR_ZERO_WEIGHT, "zero weights found. check hop_size, segment_size or m0, m1");
         std::string why;
-        const int hrc = check_handoff_call(h, s, p.n_samples, &why);
+        const int hrc = check_handoff_call(h, s, n_after - s->n_pushed, &why);
         if (hrc != CSS_OK) return refuse(hrc, why);
-        its[i] = Item{s, &p, 0, 0, 0, 0, s->t_g, planar};
+        its[i] = Item{s, &p, 0, 0, 0, 0, s->t_g, planar, 0};
     }
     if (stats) *stats = CssStreamGroupStats{};
     handoff_begin_call(h);
@@ -755,22 +809,30 @@ int push_items(css_ctx* h, const std::vector<PushItem>& items, bool pcm16, CssSt
     // a stream's first PCM16 push: device staging for one piece, [piece][C] interleaved or C planes of `piece` values
     if (pcm16)
         for (Item& it : its)
-            if (it.p->n_samples > 0 &&
+            if (it.p->n_samples > 0 && !it.s->rate &&
                 (rc = ensure(h, it.s->pcm16_stage, (size_t)it.s->n_ch * it.s->piece * sizeof(int16_t))) != CSS_OK) return rc;
     std::vector<Item*> act;
     std::vector<SegJob> sj;
     std::vector<TailJob> tj;
     std::vector<StreamIngestPcm16> ing;
+    std::vector<ResampleJob> rsj;
     for (size_t round = 0;; ++round) {
         act.clear();
         for (Item& it : its)
             if (it.done < it.p->n_samples) act.push_back(&it);
         if (act.empty()) break;
-        ing.clear();
+        ing.clear(); rsj.clear();
+        bool host_staging = false;
         for (Item* it : act) {
             StreamState* s = it->s;
             const int C = s->n_ch;
-            const int64_t n = it->n = std::min<int64_t>(s->piece, it->p->n_samples - it->done);
+            // a rate stream's piece is cut in inputs so that the outputs it makes available are at most `piece` window samples:
+            // avail(N) <= n_pushed + piece  <=>  N <= ((n_pushed + piece) down + half) / up
+            if (RateStream* q = s->rate)
+                it->n_in = std::min<int64_t>(it->p->n_samples - it->done, ((s->n_pushed + s->piece) * q->r.down + q->r.half) / q->r.up - q->n_in);
+            else
+                it->n_in = std::min<int64_t>(s->piece, it->p->n_samples - it->done);
+            const int64_t n = it->n = model_samples_after(s, it->n_in) - s->n_pushed;
             const int64_t N1 = s->n_pushed + n, K1 = frames_of(N1);
             if (K1 - s->seg_base * s->hop > s->WF || N1 - s->seg_base * s->hop * hopS > s->WS) {
                 if ((rc = rebase(h, s)) != CSS_OK) return rc;
@@ -779,6 +841,19 @@ int push_items(css_ctx* h, const std::vector<PushItem>& items, bool pcm16, CssSt
             }
             const int64_t sb = s->seg_base * s->hop * hopS;
             float* win = (float*)s->pcm[s->cur].p + (s->n_pushed - sb);
+            if (RateStream* q = s->rate) {
+                // the caller's samples as they are into the device staging, then the round's resample launch
+                const int64_t ni = it->n_in;
+                const size_t el = pcm16 ? sizeof(int16_t) : sizeof(float);
+                const char* src = pcm16 ? (const char*)it->p->i16 : (const char*)it->p->f32;
+                if (it->planar)
+                    HIPCHK(h, hipMemcpy2DAsync(q->stage.p, (size_t)q->max_in * el, src + (size_t)it->done * el, (size_t)it->p->channel_stride * el,
+                                               (size_t)ni * el, (size_t)C, hipMemcpyHostToDevice, h->stream));
+                else
+                    HIPCHK(h, hipMemcpyAsync(q->stage.p, src + (size_t)it->done * C * el, (size_t)ni * C * el, hipMemcpyHostToDevice, h->stream));
+                rsj.push_back(rate_job(s, pcm16, it->planar, ni, s->n_pushed + n, win, false));
+                continue;
+            }
             if (pcm16) {
                 int16_t* stage = (int16_t*)s->pcm16_stage.p;
                 if (it->planar)
@@ -791,6 +866,7 @@ int push_items(css_ctx* h, const std::vector<PushItem>& items, bool pcm16, CssSt
                 continue;
             }
             // samples -> the window, channel-major (a plain copy: the transform reads the same values css_run's does)
+            host_staging = true;
             const float* src = it->p->f32 + it->done * C;
             for (int ch = 0; ch < C; ++ch) {
                 float* d = s->host_cm.data() + (size_t)ch * n;
@@ -799,10 +875,12 @@ int push_items(css_ctx* h, const std::vector<PushItem>& items, bool pcm16, CssSt
             HIPCHK(h, hipMemcpy2DAsync(win, (size_t)s->WS * sizeof(float), s->host_cm.data(),
                                        (size_t)n * sizeof(float), (size_t)n * sizeof(float), (size_t)C, hipMemcpyHostToDevice, h->stream));
         }
+        if (!rsj.empty() && !launch_stream_ingest_resample_multi(rsj.data(), (int)rsj.size(), h->stream))
+            return fail(h, CSS_ERR_HIP, "the resampling kernel's LDS could not be reserved");
         if (pcm16) {
             launch_stream_ingest_pcm16_multi(ing.data(), (int)ing.size(), h->stream);
-        } else {
-            // the staging buffers are reused by the next round
+        } else if (host_staging) {
+            // the host staging buffers are reused by the next round (a rate stream has none: its piece went from the caller's memory)
             HIPCHK(h, hipStreamSynchronize(h->stream));
         }
         sj.clear(); tj.clear();
@@ -838,7 +916,7 @@ int push_items(css_ctx* h, const std::vector<PushItem>& items, bool pcm16, CssSt
             it->emitted += n_new;
             s->t_st = s->sd * s->hop;
             s->t_g = it->t_g1;
-            it->done += it->n;
+            it->done += it->n_in;
         }
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -900,8 +978,10 @@ int css_stream_finish(css_handle_t h, int32_t id, float* out_host, int64_t cap, 
     if (s->finished) return fail(h, CSS_ERR_STATE, "the stream has finished");
     if (!n_out) return fail(h, CSS_ERR_INVALID_ARG, "null argument");
     if (h->split) return fail(h, CSS_ERR_STATE, "streams run in CSS_LINEAR_EXACT_F32 only");
+    // (a rate stream: the recording is ceil(n_in up / down) model-rate samples long, the last of them read zeros past the end)
+    const int64_t n_total = s->rate ? resample_count(s->rate->r, s->rate->n_in, true) : s->n_pushed;
     CssPlan p{};
-    plan_impl(h->d, s->cfg, s->n_pushed, &p);
+    plan_impl(h->d, s->cfg, n_total, &p);
     if (p.zero_weight) return fail(h, CSS_ERR_ZERO_WEIGHT, "zero weights found. check hop_size, segment_size or m0, m1");
     const int64_t need = p.n_out - s->n_emitted;
     if (!out_host || cap < need) return fail(h, CSS_ERR_INVALID_ARG, "output capacity too small for the rest of the stream");
@@ -911,6 +991,27 @@ int css_stream_finish(css_handle_t h, int32_t id, float* out_host, int64_t cap, 
     std::vector<HandoffRec> recs;
     const int64_t t_g_before = s->t_g;
     HIPCHK(h, hipSetDevice(h->device));
+    if (n_total > s->n_pushed) {
+        // flush the resampler: the samples that waited for inputs, into the window, and the frames they complete (fewer than a
+        // frame's worth: half / down + 1 samples); the segments and the tail below take them as they take a push's
+        const int64_t K1 = frames_of(n_total), hopS = h->d.frame_hop;
+        if (K1 - s->seg_base * s->hop > s->WF || n_total - s->seg_base * s->hop * hopS > s->WS) {
+            if ((rc = rebase(h, s)) != CSS_OK) return rc;
+            if (K1 - s->seg_base * s->hop > s->WF || n_total - s->seg_base * s->hop * hopS > s->WS)
+                return fail(h, CSS_ERR_STATE, "stream window overflow");
+        }
+        const int64_t fb0 = s->seg_base * s->hop;
+        const ResampleJob j = rate_job(s, false, false, 0, n_total, (float*)s->pcm[s->cur].p + (s->n_pushed - fb0 * hopS), true);
+        if (!launch_stream_ingest_resample_multi(&j, 1, h->stream))
+            return fail(h, CSS_ERR_HIP, "the resampling kernel's LDS could not be reserved");
+        s->n_pushed = n_total;
+        bool ph = false;
+        if (K1 > s->K &&
+            !analysis_transform(h, (const float*)s->pcm[s->cur].p, s->WS, s->n_ch, s->K - fb0, K1 - fb0, (float*)s->X[s->cur].p, s->WF, h->stream,
+                                (float*)s->X[s->cur].p + (int64_t)s->n_ch * 2 * h->d.num_bins * s->WF, &ph))
+            return fail(h, CSS_ERR_HIP, "the analysis transform's LDS could not be reserved");
+        s->K = std::max(s->K, K1);
+    }
     const int64_t TL = p.mix_frames, nseg = p.num_segments, fb = s->seg_base * s->hop;
     if (TL - fb > s->WF || nseg - s->seg_base > s->SC) return fail(h, CSS_ERR_STATE, "stream window overflow");
     const int c = s->cur, F = h->d.num_bins;
@@ -956,6 +1057,42 @@ int css_stream_info(css_handle_t h, int32_t id, CssStreamInfo* out) {
     out->max_lag = (int64_t)(s->T + s->halo + 2) * h->d.frame_hop + h->d.frame_len;
     out->device_bytes = device_bytes(s);
     out->finished = s->finished ? 1 : 0;
+    return CSS_OK;
+}
+
+// ---- the rate ratio of a stream (include/css_mi355_rate.h) -----------------------------------------------------------------------
+int css_stream_set_rate(css_handle_t h, int32_t id, int32_t up, int32_t down) {
+    StreamState* s = nullptr;
+    int rc = check_stream_call(h, id, &s);
+    if (rc != CSS_OK) return rc;
+    ResampleRatio r;
+    if (!resample_ratio(up, down, &r) || !resample_fits(r, s->n_ch))
+        return fail(h, CSS_ERR_INVALID_ARG, "rate ratio: up != down in lowest terms, at most 128 taps per output sample and 16384 taps");
+    if (s->rate) return fail(h, CSS_ERR_STATE, "this stream has a rate ratio already");
+    if (s->n_pushed > 0 || s->finished) return fail(h, CSS_ERR_STATE, "the rate ratio is set before the stream's first sample");
+    HIPCHK(h, hipSetDevice(h->device));
+    RateStream* q = new RateStream();
+    q->r = r;
+    q->H = (2 * r.half + r.up - 1) / r.up + 1;
+    q->max_in = (s->piece * r.down + r.half) / r.up + 1;
+    std::vector<float> taps((size_t)r.L), tab((size_t)r.up * r.P_ld);
+    resample_taps_f32(r, taps.data());
+    resample_phase_table(r, taps.data(), tab.data());
+    rc = ensure(h, q->stage, (size_t)s->n_ch * q->max_in * sizeof(float));
+    for (int b = 0; b < 2 && rc == CSS_OK; ++b) rc = ensure(h, q->hist[b], (size_t)s->n_ch * q->H * sizeof(float), true);
+    if (rc == CSS_OK) rc = ensure(h, q->tab, tab.size() * sizeof(float));
+    hipError_t e = hipSuccess;
+    if (rc == CSS_OK) {
+        e = hipMemcpyAsync(q->tab.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    }
+    if (rc != CSS_OK || e != hipSuccess) {
+        for (DevBuf* d : {&q->stage, &q->hist[0], &q->hist[1], &q->tab})
+            if (d->p) hipFree(d->p);
+        delete q;
+        return rc != CSS_OK ? rc : fail(h, CSS_ERR_HIP, std::string("rate setup: ") + hipGetErrorString(e));
+    }
+    s->rate = q;
     return CSS_OK;
 }
 

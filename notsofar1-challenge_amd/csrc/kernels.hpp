@@ -333,4 +333,28 @@ void launch_stream_scatter_masks(const float* src, int64_t src_ld, int rows, con
 struct StreamIngestPcm16 { const int16_t* src; int64_t plane_ld; int64_t n; int C; float* dst; int64_t dst_ld; };
 void launch_stream_ingest_pcm16_multi(const StreamIngestPcm16* e, int n, hipStream_t s);
 
+// ---- resample.hip: rate conversion at a stream's ingest and of whole recordings (scipy.signal.resample_poly's default filter)
+// up / down in lowest terms; half = 10 max(up, down), L = 2 half + 1 taps, P = ceil(L / up) taps per output sample; P_ld = P | 1
+// is the pitch of a phase's taps in the table (odd: the per-lane gather of up > 1 spreads over the LDS banks)
+constexpr int RS_TILE = 256, RS_P_MAX = 128;
+struct ResampleRatio { int up, down, half, L, P, P_ld; };
+bool resample_ratio(int up, int down, ResampleRatio* r);                       // false: a ratio the library refuses
+void resample_taps_f32(const ResampleRatio& r, float* taps);                   // the L float32 taps (float64 on the host, rounded once)
+void resample_phase_table(const ResampleRatio& r, const float* taps, float* tab);   // [up][P_ld], a phase's taps in the chain's order
+int64_t resample_count(const ResampleRatio& r, int64_t n_in, bool finished);   // outputs computable after n_in inputs / of a recording of n_in
+bool resample_fits(const ResampleRatio& r, int C);                             // the tile's LDS (taps + C rows of the span) fits a workgroup
+// Outputs [m0, m0 + n_m) of a recording whose inputs [N0 - H, N0) are hist_in [C][H] (float) and [N0, N0 + n) the piece at src
+// (device memory; int16 or float32; interleaved [n][C] with plane_ld = 0, or planar with channel c at src + c * plane_ld);
+// every other input is zero.  The stream launch writes dst[c * dst_ld + (m - m0)] and, with hist_out, the last H inputs of
+// [hist_in | piece] to hist_out [C][H] (another buffer than hist_in); launch_resample writes dst[m * C + c].
+struct ResampleJob {
+    const void* src; int is_i16; int64_t plane_ld, n;
+    const float* hist_in; float* hist_out; int H;
+    int64_t N0, m0, n_m;
+    int up, down, half, P, P_ld; const float* tab;
+    int C; float* dst; int64_t dst_ld;
+};
+bool launch_stream_ingest_resample_multi(const ResampleJob* e, int n, hipStream_t s);   // false: the LDS could not be reserved
+bool launch_resample(const ResampleJob& e, hipStream_t s);
+
 }  // namespace css

@@ -17,6 +17,12 @@ view ``planes.T`` of C mono recordings -- moves it to the device as int16 and sc
 (css_stream_handoff_*): after every ``push`` / ``finish`` / grouped push, ``stream.handoff`` holds what became final in that
 call -- raw Whisper log-mel frames, the kept sample ranges and the gate bits per separated stream (``Handoff``).  All calls'
 frames of a finished stream, through ``whisper_normalize``, are ``Handle.handoff_logmel`` of the whole recording, bit for bit.
+
+``CssStream(..., input_rate=48000)`` takes its pushes at the capture rate (css_stream_set_rate): ``push`` and ``push_pcm16`` move the
+samples to the device as they were captured and the rate conversion to the model's ``fs`` -- ``scipy.signal.resample_poly``'s
+default filter, in float32 -- is part of the ingest kernel.  A finished stream returned ``css_run`` of
+``handle.resample(recording, input_rate)``, bit for bit; ``final_samples``, ``handoff_bounds`` and ``handoff_final_frames`` then
+count input samples, everything a stream returns stays at the model rate.
 """
 from __future__ import annotations
 
@@ -78,7 +84,7 @@ class CssStream:
     ``finish()`` -> the rest; use as a context manager (closes the stream).  ``handoff``: see the module text."""
 
     def __init__(self, separator: HipSeparator, cfg: Optional[CssCfg] = None, fs: int = 16000, num_channels: int = 7,
-                 handoff: Optional[Mapping[str, object]] = None):
+                 handoff: Optional[Mapping[str, object]] = None, input_rate: Optional[int] = None):
         self.separator = separator
         self.cfg = cfg if cfg is not None else CssCfg()
         desc = separator.desc
@@ -90,6 +96,20 @@ class CssStream:
         _lib.check(self._h.h, self._h.lib.css_stream_open(self._h.h, C.byref(self._run_cfg.c), self.num_channels, C.byref(sid)))
         self.id = int(sid.value)
         self.latency_samples = self.info().max_lag
+        # the rate ratio (up, down) of a stream pushed at another rate than the model's, the inputs pushed so far and the
+        # resampler's own lag in input samples (half / up: 30 samples at 48 kHz) on top of latency_samples (model rate)
+        self.rate = None
+        self._n_in = 0
+        self.resampler_lag_samples = 0
+        if input_rate is not None and int(input_rate) != int(fs):
+            up, down = _lib.rate_ratio(input_rate, fs)
+            try:
+                _lib.check(self._h.h, self._h.lib.css_stream_set_rate(self._h.h, self.id, up, down))
+            except Exception:
+                self.close()
+                raise
+            self.rate = (up, down)
+            self.resampler_lag_samples = 10 * max(up, down) // up
         self._out = np.empty((self.num_spks, 0), np.float32)
         self.handoff: Optional[Handoff] = None
         self._hcfg = None
@@ -105,12 +125,21 @@ class CssStream:
             S = self.num_spks
             self._ho_n = (np.zeros(S, np.int64), np.zeros(S, np.int32), np.zeros(S, np.float32))
 
+    def _model_samples(self, n_in: int, finished: bool = False) -> int:
+        """model-rate samples after ``n_in`` samples as they are pushed (css_stream_rate_samples; without a rate: ``n_in``)"""
+        return n_in if self.rate is None else _lib.stream_rate_samples(self.rate[0], self.rate[1], n_in, finished)
+
+    def _model_new(self, n: int) -> int:
+        """model-rate samples that the next push of ``n`` samples adds to the window"""
+        return self._model_samples(self._n_in + n) - self._model_samples(self._n_in)
+
     def handoff_bounds(self, n_samples: int):
-        """(frames, ranges, gate frames) a push of ``n_samples`` (-1: finish) needs room for"""
-        return _lib.stream_handoff_bounds(self.separator.desc, self._run_cfg, self._hcfg, n_samples)
+        """(frames, ranges, gate frames) the next push of ``n_samples`` (-1: finish) needs room for"""
+        n = self._model_new(n_samples) if n_samples >= 0 else n_samples
+        return _lib.stream_handoff_bounds(self.separator.desc, self._run_cfg, self._hcfg, n)
 
     def handoff_final_frames(self, n_pushed: int) -> int:
-        return _lib.stream_handoff_final_frames(self.separator.desc, self._run_cfg, self._hcfg, n_pushed)
+        return _lib.stream_handoff_final_frames(self.separator.desc, self._run_cfg, self._hcfg, self._model_samples(n_pushed))
 
     def _handoff_bind(self, n_samples: int):
         """binds buffers that suffice for a call with ``n_samples`` (kept while they are large enough)"""
@@ -146,7 +175,12 @@ class CssStream:
         return inf
 
     def final_samples(self, n_pushed: int) -> int:
-        return _lib.stream_final_samples(self.separator.desc, self._run_cfg, n_pushed)
+        """output samples per separated stream that are final after ``n_pushed`` pushed samples (input samples with ``input_rate``)"""
+        return _lib.stream_final_samples(self.separator.desc, self._run_cfg, self._model_samples(n_pushed))
+
+    def _cap(self, n: int) -> int:
+        """an output capacity that suffices for the next push of ``n`` samples"""
+        return self._model_new(n) + self.latency_samples
 
     def _buffer(self, cap: int) -> np.ndarray:
         if self._out.shape[1] < cap:
@@ -164,12 +198,12 @@ class CssStream:
     def push(self, chunk) -> List[np.ndarray]:
         x = self._samples(chunk)
         n = x.shape[0]
-        cap = n + self.latency_samples
-        out = self._buffer(cap)
+        out = self._buffer(self._cap(n))
         n_out = C.c_int64(0)
         self._handoff_bind(n)
         _lib.check(self._h.h, self._h.lib.css_stream_push(self._h.h, self.id, x.ctypes.data_as(C.c_void_p), n,
                                                           out.ctypes.data_as(C.c_void_p), out.shape[1], C.byref(n_out)))
+        self._n_in += n
         self._handoff_take()
         return [out[s, :n_out.value].copy() for s in range(self.num_spks)]
 
@@ -178,17 +212,19 @@ class CssStream:
         ``chunk.astype(float32) / 32768`` returns, bit for bit; the samples are scaled and de-interleaved on the device."""
         x, ss, cs = pcm16_layout(chunk, self.num_channels)
         n = x.shape[0]
-        out = self._buffer(n + self.latency_samples)
+        out = self._buffer(self._cap(n))
         n_out = C.c_int64(0)
         self._handoff_bind(n)
         _lib.check(self._h.h, self._h.lib.css_stream_push_pcm16(self._h.h, self.id, C.c_void_p(x.ctypes.data), n, ss, cs,
                                                                 out.ctypes.data_as(C.c_void_p), out.shape[1], C.byref(n_out)))
+        self._n_in += n
         self._handoff_take()
         return [out[s, :n_out.value].copy() for s in range(self.num_spks)]
 
     def finish(self) -> List[np.ndarray]:
         inf = self.info()
-        rest = _lib.plan(self.separator.desc, self._run_cfg, inf.n_pushed).n_out - inf.n_emitted
+        n_total = inf.n_pushed if self.rate is None else self._model_samples(self._n_in, True)
+        rest = _lib.plan(self.separator.desc, self._run_cfg, n_total).n_out - inf.n_emitted
         out = self._buffer(max(rest, 1))
         n_out = C.c_int64(0)
         self._handoff_bind(-1)
@@ -240,7 +276,8 @@ class CssStreamGroup:
         stats = _lib.CssStreamGroupStats()
         _lib.check(self._h.h, fn(self._h.h, items, len(part), C.byref(stats)))
         self.stats = stats
-        for s, _ in part:
+        for it, (s, _) in zip(items, part):
+            s._n_in += int(it.n_samples)
             s._handoff_take()
         got = {id(s): [out[k, :it.n_out].copy() for k in range(s.num_spks)] for it, (s, _), out in zip(items, part, outs)}
         return [got.get(id(s), [np.empty(0, np.float32) for _ in range(s.num_spks)]) for s in self.streams]
@@ -250,7 +287,7 @@ class CssStreamGroup:
         items = (_lib.CssStreamPush * max(len(part), 1))()
         outs = []
         for it, (s, x) in zip(items, part):
-            out = s._buffer(x.shape[0] + s.latency_samples)
+            out = s._buffer(s._cap(x.shape[0]))
             outs.append(out)
             it.id, it.pcm_host, it.n_samples = s.id, x.ctypes.data, x.shape[0]
             it.out_host, it.cap, it.n_out = out.ctypes.data, out.shape[1], 0
@@ -263,7 +300,7 @@ class CssStreamGroup:
         items = (_lib.CssStreamPushPcm16 * max(len(part), 1))()
         outs = []
         for it, (s, (x, ss, cs)) in zip(items, part):
-            out = s._buffer(x.shape[0] + s.latency_samples)
+            out = s._buffer(s._cap(x.shape[0]))
             outs.append(out)
             it.id, it.pcm16_host, it.n_samples, it.sample_stride, it.channel_stride = s.id, x.ctypes.data, x.shape[0], ss, cs
             it.out_host, it.cap, it.n_out = out.ctypes.data, out.shape[1], 0

@@ -19,6 +19,10 @@ With --pcm16 the recordings are 16-bit PCM (quantised at 0.2 of full scale) and 
 dequantised float32 samples, and (C) one css_stream_push_many_pcm16 per round on the int16 samples themselves, interleaved
 as a capture device delivers them (--pinned: in page-locked memory).  Every arm's input is laid out before the clock starts;
 every arm is compared with css_run of the dequantised recording (profiles/r11_stream_pcm16.json).
+
+With --rate HZ the recordings are 16-bit PCM at HZ (the synthetic meeting interpolated to that rate) and the streams are opened
+with input_rate=HZ: one arm, (R) one css_stream_push_many_pcm16 per round of 1.5 s at HZ, resampled to 16 kHz by the ingest
+kernel; compared with css_run of Handle.resample of the recording (--pinned as above; profiles/r12_stream_rate.json).
 """
 import argparse
 import json
@@ -39,7 +43,7 @@ HANDOFF = dict(n_mels=80, pad_frames=8, drop_silence=True)
 
 
 def group_bench(n_streams, out_path, seconds=60.0, round_s=1.5, block=5, passes=2, handoff=False, only_grouped=False, pcm16=False,
-                pinned=False):
+                pinned=False, rate=0):
     import notsofar1_challenge_amd.css as CSS
     import notsofar1_challenge_amd.separator as SEP
     import notsofar1_challenge_amd.stream as STR
@@ -52,7 +56,16 @@ def group_bench(n_streams, out_path, seconds=60.0, round_s=1.5, block=5, passes=
     rc = CSS.make_run_cfg(cfg, FS, 7)
     recs = [np.ascontiguousarray(SYN.synth_meeting(seconds, 7, seed=1000 + i)[0]) for i in range(n_streams)]
     q16 = []
-    if pcm16:
+    if rate:
+        import notsofar1_challenge_amd._lib as LIB
+        t = np.arange(int(round(seconds * rate))) * (float(FS) / rate)
+        at = np.arange(recs[0].shape[0])
+        q16 = [np.clip(np.rint(np.stack([np.interp(t, at, x[:, c]) for c in range(7)], axis=1) * 0.2 * 32768.0), -32768, 32767).astype(np.int16)
+               for x in recs]
+        recs = [sep.handle.resample(q, rate) for q in q16]
+        if pinned:
+            q16 = [LIB.pinned_copy(q) for q in q16]
+    elif pcm16:
         import notsofar1_challenge_amd._lib as LIB
         q16 = [np.clip(np.rint(x.astype(np.float64) * 0.2 * 32768.0), -32768, 32767).astype(np.int16) for x in recs]
         recs = [np.ascontiguousarray(q.astype(np.float32) / np.float32(32768.0)) for q in q16]
@@ -60,25 +73,25 @@ def group_bench(n_streams, out_path, seconds=60.0, round_s=1.5, block=5, passes=
             q16 = [LIB.pinned_copy(q) for q in q16]
     sep.handle.run(recs[0][:FS * 10], rc)   # warm-up
     refs = [sep.handle.run(x, rc).copy() for x in recs]
-    step = int(round_s * FS)
-    arms = "BC" if pcm16 else "AB"
-    ms = {"A": [], "B": [], "C": []}
-    same = {"A": True, "B": True, "C": True}
+    step = int(round_s * (rate or FS))
+    arms = "RR" if rate else ("BC" if pcm16 else "AB")
+    ms = {"A": [], "B": [], "C": [], "R": []}
+    same = {"A": True, "B": True, "C": True, "R": True}
     seg_per_batch = []
     mel_frames = []
 
     def one_pass(first_arm, timed):
-        streams = [STR.CssStream(sep, cfg, handoff=HANDOFF) if handoff else STR.CssStream(sep, cfg) for _ in recs]
+        streams = [STR.CssStream(sep, cfg, handoff=HANDOFF if handoff else None, input_rate=rate or None) for _ in recs]
         group = STR.CssStreamGroup(streams)
         em = [0] * n_streams
-        n_rounds = (recs[0].shape[0] + step - 1) // step if timed else 2 * block
+        n_rounds = ((q16 if rate else recs)[0].shape[0] + step - 1) // step if timed else 2 * block
         for r in range(n_rounds):
             arm = "B" if only_grouped else arms[(r // block + (first_arm == arms[1])) % 2]
-            chunks = [x[r * step:(r + 1) * step] for x in (q16 if arm == "C" else recs)]
+            chunks = [x[r * step:(r + 1) * step] for x in (q16 if arm in "CR" else recs)]
             t = time.perf_counter()
             if arm == "A":
                 res = [s.push(c) for s, c in zip(streams, chunks)]
-            elif arm == "C":
+            elif arm in "CR":
                 res = group.push_pcm16(chunks)
             else:
                 res = group.push(chunks)
@@ -115,11 +128,15 @@ def group_bench(n_streams, out_path, seconds=60.0, round_s=1.5, block=5, passes=
     if handoff:
         res["handoff"] = dict(HANDOFF, mel_frames_per_round_median=float(np.median(mel_frames)),
                               launches_products_frames_last_call=list(sep.handle.stream_handoff_stats()))
-    if pcm16:
+    if rate:
+        res["input"] = "16-bit PCM at %d Hz, 0.2 of full scale (%s); the streams resample to %d Hz at ingest" % (
+            rate, "page-locked" if pinned else "pageable", FS)
+    elif pcm16:
         res["input"] = "16-bit PCM at 0.2 of full scale; arm B is fed the dequantised float32 samples, arm C the int16 samples (%s)" % (
             "page-locked" if pinned else "pageable")
     for arm, what in (("A", "one css_stream_push per stream and round"), ("B", "one css_stream_push_many per round"),
-                      ("C", "one css_stream_push_many_pcm16 per round")):
+                      ("C", "one css_stream_push_many_pcm16 per round"),
+                      ("R", "one css_stream_push_many_pcm16 per round, streams opened with input_rate")):
         if not ms[arm]:
             continue
         v = np.array(ms[arm])
@@ -148,10 +165,11 @@ def main():
     ap.add_argument("--only-grouped", action="store_true", help="with --streams: arm B alone (twice the rounds)")
     ap.add_argument("--pcm16", action="store_true", help="with --streams: arms B (float32) and C (css_stream_push_many_pcm16) on 16-bit recordings")
     ap.add_argument("--pinned", action="store_true", help="with --pcm16: arm C's int16 samples in page-locked memory")
+    ap.add_argument("--rate", type=int, default=0, help="with --streams: 16-bit recordings at this rate, streams opened with input_rate (arm R alone)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.streams:
-        return group_bench(a.streams, a.out, handoff=a.handoff, only_grouped=a.only_grouped, pcm16=a.pcm16, pinned=a.pinned)
+        return group_bench(a.streams, a.out, handoff=a.handoff, only_grouped=a.only_grouped, pcm16=a.pcm16, pinned=a.pinned, rate=a.rate)
     import notsofar1_challenge_amd.css as CSS
     import notsofar1_challenge_amd.separator as SEP
     import notsofar1_challenge_amd.stream as STR
