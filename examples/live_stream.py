@@ -16,7 +16,12 @@ With --rate HZ the source delivers 16-bit PCM at HZ (48000, 44100, 32000, 8000 .
 the int16 chunks cross PCIe as they were captured and the ingest kernel resamples them to the model's 16 kHz
 (scipy.signal.resample_poly's default filter); what comes back stays at 16 kHz.
 
-    python examples/live_stream.py [--seconds 30] [--rooms N] [--logmel] [--pcm16] [--rate HZ]
+With --preview every tick also asks for the unfinished tail (CssStream.preview / CssStreamGroup.preview): the provisional
+samples between the final ones and the present -- css_run of what was pushed so far -- while the stream stays as it was.  Each
+tick prints how far the final and the provisional output reach behind the input; a caption host shows the provisional part
+at once and replaces it as it becomes final.
+
+    python examples/live_stream.py [--seconds 30] [--rooms N] [--logmel] [--pcm16] [--rate HZ] [--preview]
 """
 import argparse
 import os
@@ -58,7 +63,15 @@ def capture_at(mix, fs, rate):
     return capture(np.stack([np.interp(t, at, mix[:, c]) for c in range(mix.shape[1])], axis=1))
 
 
-def rooms(sep, n_rooms, seconds, fs, chunk, logmel=False, pcm16=False, rate=None):
+def behind(inf, first, count, fs):
+    """how far the final and the provisional output end behind the input's last sample, in seconds (count None: no preview yet)"""
+    final = f"final {(inf.n_pushed - inf.n_emitted) / fs:4.2f} s behind"
+    if count is None:
+        return final + ", no preview yet (css_run refuses a recording of at most one segment)"
+    return final + f", provisional {max(inf.n_pushed - (first + count), 0) / fs:4.2f} s behind ({count / fs:4.2f} s of preview)"
+
+
+def rooms(sep, n_rooms, seconds, fs, chunk, logmel=False, pcm16=False, rate=None, preview=False):
     mixes = [SYN.synth_meeting(seconds, 7, seed=1 + r)[0] for r in range(n_rooms)]
     if rate:
         mixes = [capture_at(m, fs, rate) for m in mixes]
@@ -82,6 +95,12 @@ def rooms(sep, n_rooms, seconds, fs, chunk, logmel=False, pcm16=False, rate=None
               f"estimator batches {group.stats.estimator_batches} ({group.stats.estimator_segments} segments)")
         if logmel:
             print_handoff(streams, fs)
+        if preview:
+            t = time.perf_counter()
+            pv = group.preview()
+            ms = (time.perf_counter() - t) * 1e3
+            print(f"    preview {ms:6.2f} ms, one batch of {group.stats.estimator_segments} segments; room 0: "
+                  + behind(inf, streams[0].preview_first_sample, None if pv[0] is None else pv[0][0].shape[0], fs))
     for s, room in zip(streams, outs):
         for k, o in enumerate(s.finish()):
             room[k].append(o)
@@ -95,6 +114,7 @@ def main():
     ap.add_argument("--rooms", type=int, default=1, help="meetings fed tick by tick through one CssStreamGroup")
     ap.add_argument("--logmel", action="store_true", help="also return Whisper log-mel frames and kept ranges with every tick")
     ap.add_argument("--pcm16", action="store_true", help="the source delivers int16 samples: push_pcm16 instead of push")
+    ap.add_argument("--preview", action="store_true", help="after each tick's push, also fetch the provisional tail (preview)")
     ap.add_argument("--rate", type=int, default=0, help="the source delivers int16 samples at this rate: CssStream(input_rate=HZ)")
     a = ap.parse_args()
     fs = 16000
@@ -102,7 +122,7 @@ def main():
     desc = W.ModelDesc.mc_v1()
     sep = SEP.HipSeparator(W.apply_golden_recipe(W.portable_state_dict(desc, 0)), None, device=0)
     if a.rooms > 1:
-        rooms(sep, a.rooms, a.seconds, fs, fs // 2, a.logmel, a.pcm16, a.rate or None)
+        rooms(sep, a.rooms, a.seconds, fs, fs // 2, a.logmel, a.pcm16, a.rate or None, a.preview)
         sep.close()
         return
     mix = SYN.synth_meeting(a.seconds, 7, seed=1)[0]
@@ -128,6 +148,12 @@ def main():
                 print_handoff([s], fs)
                 for k, m in enumerate(s.handoff.mel):
                     mels[k].append(m)
+            if a.preview:
+                try:
+                    count = s.preview()[0].shape[0]
+                except AssertionError:   # css_run's own refusal of a recording of at most one segment (css.py:297)
+                    count = None
+                print("    " + behind(inf, s.preview_first_sample, count, fs))
         for k, o in enumerate(s.finish()):
             streams[k].append(o)
         if a.logmel:

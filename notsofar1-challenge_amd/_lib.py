@@ -95,6 +95,11 @@ class CssStreamGroupStats(C.Structure):
     _fields_ = [("estimator_batches", C.c_int32), ("estimator_segments", C.c_int64)]
 
 
+class CssStreamPreview(C.Structure):
+    _fields_ = [("id", C.c_int32), ("out_host", C.c_void_p), ("cap", C.c_int64), ("n_out", C.c_int64), ("first_sample", C.c_int64),
+                ("status", C.c_int32)]
+
+
 class CssStreamHandoffCfg(C.Structure):
     _fields_ = [("n_mels", C.c_int32), ("pad_frames", C.c_int32), ("drop_silence", C.c_int32)]
 
@@ -227,6 +232,13 @@ SIGNATURES_RATE = {
     "css_resample_host": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int64,
                                     C.POINTER(C.c_int64)]),
 }
+# the entry points include/css_mi355_preview.h declares (the unfinished tail of a stream), the third table load() applies
+SIGNATURES_PREVIEW = {
+    "css_stream_preview_samples": (C.c_int, [C.POINTER(CssModelDesc), C.POINTER(CssRunCfg), C.c_int64, C.POINTER(C.c_int64),
+                                             C.POINTER(C.c_int64)]),
+    "css_stream_preview": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "css_stream_preview_many": (C.c_int, [_P, C.POINTER(CssStreamPreview), C.c_int32, C.POINTER(CssStreamGroupStats)]),
+}
 RESAMPLE_TILE = 256                              # output samples per block of the two resampling kernels (resample.hip RS_TILE)
 
 _lib: Optional[C.CDLL] = None
@@ -268,7 +280,7 @@ def load() -> C.CDLL:
         lib = C.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover
         raise CssLibraryError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_RATE.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_RATE.items()) + list(SIGNATURES_PREVIEW.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -337,6 +349,16 @@ def stream_final_samples(desc, run_cfg: RunCfg, n_pushed: int) -> int:
     if rc != CSS_OK:
         raise CssError(rc, "css_stream_final_samples: unsupported frame geometry or bad configuration")
     return int(n.value)
+
+
+def stream_preview_samples(desc, run_cfg: RunCfg, n_pushed: int):
+    """css_stream_preview_samples: (first, count, status) -- a preview after `n_pushed` model-rate samples returns samples
+    [first, first + count) per separated stream; status is CSS_OK or what css_run gives for this prefix (CSS_ERR_ZERO_WEIGHT)"""
+    first, count = C.c_int64(), C.c_int64()
+    rc = load().css_stream_preview_samples(C.byref(make_desc(desc)), C.byref(run_cfg.c), int(n_pushed), C.byref(first), C.byref(count))
+    if rc not in (CSS_OK, CSS_ERR_ZERO_WEIGHT):
+        raise CssError(rc, "css_stream_preview_samples: unsupported frame geometry or bad configuration")
+    return int(first.value), int(count.value), int(rc)
 
 
 def rate_ratio(input_rate: int, fs: int = 16000):

@@ -18,7 +18,8 @@
 // samples, converted on the device).  It takes piece r of every item in round r, and the segments a round completes
 // in all streams of one segmentation pass the estimator as ONE batch (every estimator kernel is batch invariant in exact
 // float32, as for queued sessions: api_queue.hip run_group), so N live meetings cost about one estimator pass per tick
-// instead of N.  css_stream_push(_pcm16) is a group of one item; css_stream_finish runs the same segments() / tail() with one job.
+// instead of N.  css_stream_push(_pcm16) is a group of one item; css_stream_finish and the previews (css_stream_preview*,
+// include/css_mi355_preview.h) run the same segments() / tail() in closing_pass: finish with one job, a preview with N and no commit.
 //
 // The hand-off (css_stream_handoff_*): a stream that has it switched on also returns, with every call, the gate
 // bits, the kept sample ranges and the raw Whisper log-mel frames that became final.  The step sits between tail() and the
@@ -31,6 +32,7 @@
 // counts model-rate samples; the call's checks are evaluated on the model-rate samples its inputs make computable.
 #include "api_ctx.hpp"
 #include "../../include/css_mi355_rate.h"
+#include "../../include/css_mi355_preview.h"
 
 #include <climits>
 
@@ -341,7 +343,8 @@ int segments(css_ctx* h, const std::vector<SegJob>& all, CssStreamGroupStats* st
 
 // One stream's frames [t_lo, t_hi) of the recording: activity bits of [a_lo, a_hi), gate + overlap-add + synthesis of [t_lo, t_hi),
 // output blocks [t_lo, q_hi) into the stream's output buffer (block t_lo at column 0)
-struct TailJob { StreamState* s; bool closing; int64_t nseg, TL, a_lo, a_hi, t_lo, t_hi, q_hi; };
+// (gate: whether a hand-off stream's gate ring receives the gate bytes; a preview's closing pass leaves it alone)
+struct TailJob { StreamState* s; bool closing; int64_t nseg, TL, a_lo, a_hi, t_lo, t_hi, q_hi; bool gate = true; };
 
 int tail(css_ctx* h, const std::vector<TailJob>& jobs) {
     std::vector<StreamStitchArgs> a(jobs.size());
@@ -350,6 +353,7 @@ int tail(css_ctx* h, const std::vector<TailJob>& jobs) {
         const TailJob& j = jobs[i];
         const int64_t fb = j.s->seg_base * j.s->hop;
         a[i] = stitch_view(h, j.s, j.closing, j.nseg, j.TL);
+        if (!j.gate) { a[i].gate_out = nullptr; a[i].gate_ld = 0; a[i].gate_mask = 0; }
         ra[i] = StreamFrames{j.a_lo - fb, j.a_hi - fb};
         rg[i] = StreamFrames{j.t_lo - fb, j.t_hi - fb};
     }
@@ -971,6 +975,113 @@ int css_stream_push_pcm16(css_handle_t h, int32_t id, const int16_t* pcm16_host,
     return rc;
 }
 
+// ---- the closing pass: css_stream_finish and the previews (include/css_mi355_preview.h) ------------------------------------------
+// What ends a recording after its last pushed sample, for a vector of streams: a rate stream's resampler is flushed into the
+// window (one table launch for all of them) and the frames the flushed samples complete are transformed; the frames the one
+// pending segment reads past the last transformed one are zeroed (css.py:159-164 pads a short recording; the last segment's
+// tail); segments() runs that segment of every stream (the estimator as one batch per segmentation) and tail() closes every
+// stream's output with the last-segment window; then the downloads and ONE synchronise.
+//   commit      css_stream_finish: the hand-off's closing round runs, and the progress counters move to the recording's end.
+//   no commit   a preview: no hand-off (StreamStitchArgs::gate_out stays null, so the gate ring is not written) and nothing
+//               of StreamState, RateStream or HandoffStream changes but the window's generation, if a rebase was needed.  Every
+//               device region written here is written again before a later pass reads it, because sd, t_st and t_g stay:
+//               mask / sep / permutation / cost slots from sd - seg_base on, act_b from t_st on, G rows from t_g on, the window
+//               samples from n_pushed and the planes from frame K on (the next push's ingest and transform), and the scratch
+//               (scm, bfw, pnorm, pit_part, Y, out).  The flush passes no hist_out, so the carried inputs stay too.
+// finish zero-fills to the window's end, once; a preview, which runs every tick, only the frames its segment reads.
+namespace {
+
+struct CloseJob {
+    StreamState* s; CssPlan p; int64_t n_total;   // the recording's length in model-rate samples, its plan
+    float* out_host; int64_t cap, need;           // samples [n_emitted, p.n_out) -> out_host[S][cap]
+};
+
+int closing_pass(css_ctx* h, const std::vector<CloseJob>& jobs, bool commit, CssStreamGroupStats* stats) {
+    if (jobs.empty()) return CSS_OK;
+    int rc;
+    std::vector<HandoffRec> recs;
+    std::vector<int64_t> t_g_before(jobs.size());
+    if (commit) handoff_begin_call(h);
+    HIPCHK(h, hipSetDevice(h->device));
+    const int hopS = h->d.frame_hop, F = h->d.num_bins, S = h->d.num_spks;
+    std::vector<ResampleJob> rsj;
+    for (size_t i = 0; i < jobs.size(); ++i) {
+        StreamState* s = jobs[i].s;
+        t_g_before[i] = s->t_g;
+        const int64_t n_total = jobs[i].n_total, K1 = std::max(s->K, frames_of(n_total));
+        const int64_t TL = jobs[i].p.mix_frames, nseg = jobs[i].p.num_segments;
+        auto past_window = [&]() {
+            const int64_t fb = s->seg_base * s->hop;
+            return K1 - fb > s->WF || n_total - fb * hopS > s->WS || TL - fb > s->WF || nseg - s->seg_base > s->SC;
+        };
+        if (past_window()) {
+            if ((rc = rebase(h, s)) != CSS_OK) return rc;
+            if (past_window()) return fail(h, CSS_ERR_STATE, "stream window overflow");
+        }
+        // flush the resampler: the samples that waited for inputs, into the window (fewer than a frame's worth: half / down + 1)
+        if (n_total > s->n_pushed)
+            rsj.push_back(rate_job(s, false, false, 0, n_total, (float*)s->pcm[s->cur].p + (s->n_pushed - s->seg_base * s->hop * hopS), true));
+    }
+    if (!rsj.empty() && !launch_stream_ingest_resample_multi(rsj.data(), (int)rsj.size(), h->stream))
+        return fail(h, CSS_ERR_HIP, "the resampling kernel's LDS could not be reserved");
+    std::vector<SegJob> sj;
+    std::vector<TailJob> tj;
+    for (const CloseJob& j : jobs) {
+        StreamState* s = j.s;
+        const int c = s->cur;
+        const int64_t fb = s->seg_base * s->hop, K1 = std::max(s->K, frames_of(j.n_total));
+        const int64_t TL = j.p.mix_frames, nseg = j.p.num_segments;
+        bool ph = false;
+        if (K1 > s->K &&
+            !analysis_transform(h, (const float*)s->pcm[c].p, s->WS, s->n_ch, s->K - fb, K1 - fb, (float*)s->X[c].p, s->WF, h->stream,
+                                (float*)s->X[c].p + (int64_t)s->n_ch * 2 * F * s->WF, &ph))
+            return fail(h, CSS_ERR_HIP, "the analysis transform's LDS could not be reserved");
+        // frames past the last transformed one are zero: to the window's end, or to the end of the pending segment
+        const int64_t z_hi = commit ? s->WF : std::min<int64_t>(s->WF, (nseg - 1) * s->hop + s->T - fb);
+        if (z_hi > K1 - fb)
+            HIPCHK(h, hipMemset2DAsync((float*)s->X[c].p + (K1 - fb), (size_t)s->WF * sizeof(float), 0,
+                                       (size_t)(z_hi - (K1 - fb)) * sizeof(float), (size_t)s->n_ch * X_ROWS_PER_BIN * F, h->stream));
+        sj.push_back(SegJob{s, s->sd, nseg, K1 - fb});
+        // the rest of the output: blocks up to mix_frames (frame_len = 2 hop: block TL holds the last frame's second half)
+        const int64_t q_hi = TL + 1;
+        if ((q_hi - s->t_g) * hopS > (int64_t)(s->out.cap / (sizeof(float) * S)) &&
+            (rc = ensure(h, s->out, (size_t)S * (q_hi - s->t_g) * hopS * sizeof(float))) != CSS_OK) return rc;
+        TailJob t{s, true, nseg, TL, s->t_st, TL, s->t_g, TL, q_hi};
+        t.gate = commit;
+        tj.push_back(t);
+    }
+    if ((rc = segments(h, sj, stats)) != CSS_OK) return rc;
+    if ((rc = tail(h, tj)) != CSS_OK) return rc;
+    if (commit) {
+        std::vector<HandoffJob> hj;
+        for (size_t i = 0; i < jobs.size(); ++i) {
+            StreamState* s = jobs[i].s;
+            const int64_t TL = jobs[i].p.mix_frames;
+            hj.push_back(HandoffJob{s, (int)i, s->t_g, TL, (TL + 1 - s->t_g) * hopS, true, jobs[i].p.n_out});
+        }
+        if ((rc = handoff_round(h, hj, 0, &recs)) != CSS_OK) return rc;
+    }
+    for (const CloseJob& j : jobs)
+        if ((rc = download(h, j.s, j.need, j.out_host, j.cap, 0)) != CSS_OK) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (!commit) return CSS_OK;
+    for (size_t i = 0; i < jobs.size(); ++i) {
+        StreamState* s = jobs[i].s;
+        if (s->ho && (rc = handoff_collect(h, s, (int)i, t_g_before[i], recs)) != CSS_OK) return rc;
+        s->n_pushed = jobs[i].n_total;
+        s->K = std::max(s->K, frames_of(jobs[i].n_total));
+        s->sd = jobs[i].p.num_segments; s->t_st = s->t_g = jobs[i].p.mix_frames;
+        s->n_emitted += jobs[i].need;
+        s->finished = true;
+    }
+    return CSS_OK;
+}
+
+// the recording a closing pass ends: ceil(n_in up / down) model-rate samples for a rate stream (the last of them read zeros past the end)
+int64_t closing_samples(const StreamState* s) { return s->rate ? resample_count(s->rate->r, s->rate->n_in, true) : s->n_pushed; }
+
+}  // namespace
+
 int css_stream_finish(css_handle_t h, int32_t id, float* out_host, int64_t cap, int64_t* n_out) {
     StreamState* s = nullptr;
     int rc = check_stream_call(h, id, &s);
@@ -978,62 +1089,78 @@ int css_stream_finish(css_handle_t h, int32_t id, float* out_host, int64_t cap, 
     if (s->finished) return fail(h, CSS_ERR_STATE, "the stream has finished");
     if (!n_out) return fail(h, CSS_ERR_INVALID_ARG, "null argument");
     if (h->split) return fail(h, CSS_ERR_STATE, "streams run in CSS_LINEAR_EXACT_F32 only");
-    // (a rate stream: the recording is ceil(n_in up / down) model-rate samples long, the last of them read zeros past the end)
-    const int64_t n_total = s->rate ? resample_count(s->rate->r, s->rate->n_in, true) : s->n_pushed;
-    CssPlan p{};
-    plan_impl(h->d, s->cfg, n_total, &p);
-    if (p.zero_weight) return fail(h, CSS_ERR_ZERO_WEIGHT, "zero weights found. check hop_size, segment_size or m0, m1");
-    const int64_t need = p.n_out - s->n_emitted;
-    if (!out_host || cap < need) return fail(h, CSS_ERR_INVALID_ARG, "output capacity too small for the rest of the stream");
+    CloseJob j{s, CssPlan{}, closing_samples(s), out_host, cap, 0};
+    plan_impl(h->d, s->cfg, j.n_total, &j.p);
+    if (j.p.zero_weight) return fail(h, CSS_ERR_ZERO_WEIGHT, "zero weights found. check hop_size, segment_size or m0, m1");
+    j.need = j.p.n_out - s->n_emitted;
+    if (!out_host || cap < j.need) return fail(h, CSS_ERR_INVALID_ARG, "output capacity too small for the rest of the stream");
     std::string why;
     if ((rc = check_handoff_call(h, s, -1, &why)) != CSS_OK) return fail(h, rc, why);
-    handoff_begin_call(h);
-    std::vector<HandoffRec> recs;
-    const int64_t t_g_before = s->t_g;
-    HIPCHK(h, hipSetDevice(h->device));
-    if (n_total > s->n_pushed) {
-        // flush the resampler: the samples that waited for inputs, into the window, and the frames they complete (fewer than a
-        // frame's worth: half / down + 1 samples); the segments and the tail below take them as they take a push's
-        const int64_t K1 = frames_of(n_total), hopS = h->d.frame_hop;
-        if (K1 - s->seg_base * s->hop > s->WF || n_total - s->seg_base * s->hop * hopS > s->WS) {
-            if ((rc = rebase(h, s)) != CSS_OK) return rc;
-            if (K1 - s->seg_base * s->hop > s->WF || n_total - s->seg_base * s->hop * hopS > s->WS)
-                return fail(h, CSS_ERR_STATE, "stream window overflow");
-        }
-        const int64_t fb0 = s->seg_base * s->hop;
-        const ResampleJob j = rate_job(s, false, false, 0, n_total, (float*)s->pcm[s->cur].p + (s->n_pushed - fb0 * hopS), true);
-        if (!launch_stream_ingest_resample_multi(&j, 1, h->stream))
-            return fail(h, CSS_ERR_HIP, "the resampling kernel's LDS could not be reserved");
-        s->n_pushed = n_total;
-        bool ph = false;
-        if (K1 > s->K &&
-            !analysis_transform(h, (const float*)s->pcm[s->cur].p, s->WS, s->n_ch, s->K - fb0, K1 - fb0, (float*)s->X[s->cur].p, s->WF, h->stream,
-                                (float*)s->X[s->cur].p + (int64_t)s->n_ch * 2 * h->d.num_bins * s->WF, &ph))
-            return fail(h, CSS_ERR_HIP, "the analysis transform's LDS could not be reserved");
-        s->K = std::max(s->K, K1);
+    if ((rc = closing_pass(h, {j}, true, nullptr)) != CSS_OK) return rc;
+    *n_out = j.need;
+    return CSS_OK;
+}
+
+// ---- previews (include/css_mi355_preview.h) ------------------------------------------------------------------------------------
+int css_stream_preview_samples(const CssModelDesc* desc, const CssRunCfg* cfg, int64_t n_pushed, int64_t* first, int64_t* count) {
+    if (!desc || !first || !count || n_pushed < 0) return CSS_ERR_INVALID_ARG;
+    const int rc = check_cfg(*desc, cfg);
+    if (rc != CSS_OK) return rc;
+    CssPlan p{};
+    if (plan_impl(*desc, *cfg, n_pushed, &p) != CSS_OK) return CSS_ERR_INVALID_ARG;
+    *first = final_frames(n_pushed, cfg->segment_frames, cfg->hop_frames, cfg->dilation_frames + cfg->erosion_frames) * desc->frame_hop;
+    *count = p.n_out - *first;
+    return p.zero_weight ? CSS_ERR_ZERO_WEIGHT : CSS_OK;
+}
+
+int css_stream_preview_many(css_handle_t h, CssStreamPreview* items, int32_t n_items, CssStreamGroupStats* stats) {
+    if (!h) return CSS_ERR_INVALID_ARG;
+    if (n_items < 0 || (n_items > 0 && !items)) return fail(h, CSS_ERR_INVALID_ARG, "bad argument");
+    std::vector<CloseJob> jobs;
+    std::vector<int32_t> status((size_t)n_items, CSS_OK);
+    std::vector<int64_t> first((size_t)n_items, 0);
+    for (int32_t i = 0; i < n_items; ++i) {
+        const CssStreamPreview& p = items[i];
+        auto refuse = [&](int code, const std::string& msg) {
+            return fail(h, code, "item " + std::to_string(i) + " (stream " + std::to_string(p.id) + "): " + msg);
+        };
+        StreamState* s = get_stream(h, p.id);
+        if (!s) return refuse(CSS_ERR_INVALID_ARG, "no open stream with this id");
+        if (h->queued || !h->pending.empty())
+            return refuse(CSS_ERR_STATE, "queued sessions (css_run_enqueue*) are outstanding: css_wait before using a stream");
+        for (int32_t k = 0; k < i; ++k)
+            if (items[k].id == p.id) return refuse(CSS_ERR_INVALID_ARG, "the stream is named twice in one call");
+        if (s->finished) return refuse(CSS_ERR_STATE, "the stream has finished");
+        if (h->split) return refuse(CSS_ERR_STATE, "streams run in CSS_LINEAR_EXACT_F32 only");
+        CloseJob j{s, CssPlan{}, closing_samples(s), p.out_host, p.cap, 0};
+        plan_impl(h->d, s->cfg, j.n_total, &j.p);
+        first[(size_t)i] = s->n_emitted;
+        if (j.p.zero_weight) { status[(size_t)i] = CSS_ERR_ZERO_WEIGHT; continue; }   // (css_run's refusal of this prefix: the item's own)
+        j.need = j.p.n_out - s->n_emitted;
+        if (!p.out_host || p.cap < j.need) return refuse(CSS_ERR_INVALID_ARG, "output capacity too small for the preview (css_stream_preview_samples)");
+        jobs.push_back(j);
     }
-    const int64_t TL = p.mix_frames, nseg = p.num_segments, fb = s->seg_base * s->hop;
-    if (TL - fb > s->WF || nseg - s->seg_base > s->SC) return fail(h, CSS_ERR_STATE, "stream window overflow");
-    const int c = s->cur, F = h->d.num_bins;
-    // frames past the last transformed one are zero (css.py:159-164 pads a short recording; the last segment's tail)
-    if (s->WF > s->K - fb)
-        HIPCHK(h, hipMemset2DAsync((float*)s->X[c].p + (s->K - fb), (size_t)s->WF * sizeof(float), 0,
-                                   (size_t)(s->WF - (s->K - fb)) * sizeof(float), (size_t)s->n_ch * X_ROWS_PER_BIN * F, h->stream));
-    if ((rc = segments(h, {SegJob{s, s->sd, nseg, s->K - fb}}, nullptr)) != CSS_OK) return rc;
-    // the rest of the output: blocks up to mix_frames (frame_len = 2 hop: block TL holds the last frame's second half)
-    const int64_t q_hi = TL + 1;
-    if ((q_hi - s->t_g) * h->d.frame_hop > (int64_t)(s->out.cap / (sizeof(float) * h->d.num_spks))) {
-        if ((rc = ensure(h, s->out, (size_t)h->d.num_spks * (q_hi - s->t_g) * h->d.frame_hop * sizeof(float))) != CSS_OK) return rc;
+    if (stats) *stats = CssStreamGroupStats{};
+    const int rc = closing_pass(h, jobs, false, stats);
+    if (rc != CSS_OK) return rc;
+    size_t k = 0;
+    for (int32_t i = 0; i < n_items; ++i) {
+        items[i].status = status[(size_t)i];
+        items[i].first_sample = first[(size_t)i];
+        items[i].n_out = status[(size_t)i] == CSS_OK ? jobs[k++].need : 0;
     }
-    if ((rc = tail(h, {TailJob{s, true, nseg, TL, s->t_st, TL, s->t_g, TL, q_hi}})) != CSS_OK) return rc;
-    if ((rc = handoff_round(h, {HandoffJob{s, 0, s->t_g, TL, (q_hi - s->t_g) * h->d.frame_hop, true, p.n_out}}, 0, &recs)) != CSS_OK) return rc;
-    if ((rc = download(h, s, need, out_host, cap, 0)) != CSS_OK) return rc;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (s->ho && (rc = handoff_collect(h, s, 0, t_g_before, recs)) != CSS_OK) return rc;
-    s->sd = nseg; s->t_st = s->t_g = TL;
-    s->n_emitted += need;
-    s->finished = true;
-    *n_out = need;
+    return CSS_OK;
+}
+
+// a group of one item
+int css_stream_preview(css_handle_t h, int32_t id, float* out_host, int64_t cap, int64_t* n_out, int64_t* first_sample) {
+    if (!h) return CSS_ERR_INVALID_ARG;
+    if (!n_out || !first_sample) return fail(h, CSS_ERR_INVALID_ARG, "null argument");
+    CssStreamPreview p{id, out_host, cap, 0, 0, CSS_OK};
+    const int rc = css_stream_preview_many(h, &p, 1, nullptr);
+    if (rc != CSS_OK) return rc;
+    if (p.status != CSS_OK) return fail(h, p.status, "zero weights found. check hop_size, segment_size or m0, m1");
+    *n_out = p.n_out; *first_sample = p.first_sample;
     return CSS_OK;
 }
 

@@ -23,6 +23,10 @@ samples to the device as they were captured and the rate conversion to the model
 default filter, in float32 -- is part of the ingest kernel.  A finished stream returned ``css_run`` of
 ``handle.resample(recording, input_rate)``, bit for bit; ``final_samples``, ``handoff_bounds`` and ``handoff_final_frames`` then
 count input samples, everything a stream returns stays at the model rate.
+
+``preview()`` on both (css_stream_preview, css_stream_preview_many; include/css_mi355_preview.h) returns the unfinished tail: the
+samples between the final ones and the present, equal to ``css_run`` of what was pushed so far, bit for bit, while the stream
+stays as it was.  One pending segment per stream passes the estimator; a grouped preview is one batch for all its streams.
 """
 from __future__ import annotations
 
@@ -112,6 +116,7 @@ class CssStream:
             self.resampler_lag_samples = 10 * max(up, down) // up
         self._out = np.empty((self.num_spks, 0), np.float32)
         self.handoff: Optional[Handoff] = None
+        self.preview_first_sample = 0
         self._hcfg = None
         if handoff is not None:
             self._hcfg = _lib.handoff_cfg(**dict(handoff))
@@ -233,6 +238,27 @@ class CssStream:
         self._handoff_take()
         return [out[s, :n_out.value].copy() for s in range(self.num_spks)]
 
+    def preview_samples(self, n_pushed: int):
+        """(first, count): a preview after ``n_pushed`` pushed samples (input samples with ``input_rate``) returns samples
+        [first, first + count) per separated stream; ``first`` is ``final_samples(n_pushed)``"""
+        desc = self.separator.desc
+        first = _lib.stream_final_samples(desc, self._run_cfg, self._model_samples(n_pushed))
+        f, c, _ = _lib.stream_preview_samples(desc, self._run_cfg, self._model_samples(n_pushed, True))
+        return first, f + c - first
+
+    def preview(self) -> List[np.ndarray]:
+        """The unfinished tail (css_stream_preview): samples [n_emitted, n_out) of ``css_run`` on what was pushed so far --
+        what ``finish`` would return now -- while the stream stays as it was.  The samples are provisional: later pushes
+        return other values for them once they are final.  ``preview_first_sample`` holds the first one's index.  Raises
+        what ``css_run`` of the prefix raises (with the default windows: the reference's assert until more than one segment
+        was pushed)."""
+        out = np.empty((self.num_spks, max(self.latency_samples, 1)), np.float32)
+        n_out, first = C.c_int64(0), C.c_int64(0)
+        _lib.check(self._h.h, self._h.lib.css_stream_preview(self._h.h, self.id, out.ctypes.data_as(C.c_void_p), out.shape[1],
+                                                             C.byref(n_out), C.byref(first)))
+        self.preview_first_sample = int(first.value)
+        return [out[s, :n_out.value].copy() for s in range(self.num_spks)]
+
     def close(self):
         if self.id >= 0 and self._h.h:
             self._h.lib.css_stream_close(self._h.h, self.id)
@@ -306,3 +332,26 @@ class CssStreamGroup:
             it.out_host, it.cap, it.n_out = out.ctypes.data, out.shape[1], 0
             s._handoff_bind(x.shape[0])
         return self._call(self._h.lib.css_stream_push_many_pcm16, items, part, outs)
+
+    def preview(self, streams: Optional[Sequence[CssStream]] = None) -> List[Optional[List[np.ndarray]]]:
+        """``CssStream.preview`` of ``streams`` (default: every stream of the group) in ONE css_stream_preview_many: the pending
+        segments of all of them share one estimator batch (``stats``).  Per stream of the group: its S arrays, or None for a
+        stream that took no part or whose prefix ``css_run`` refuses (a meeting that began less than a segment ago)."""
+        part = self.streams if streams is None else list(streams)
+        if any(s not in self.streams for s in part):
+            raise ValueError("a stream that is not in this group")
+        items = (_lib.CssStreamPreview * max(len(part), 1))()
+        outs = []
+        for it, s in zip(items, part):
+            out = np.empty((s.num_spks, max(s.latency_samples, 1)), np.float32)
+            outs.append(out)
+            it.id, it.out_host, it.cap = s.id, out.ctypes.data, out.shape[1]
+        stats = _lib.CssStreamGroupStats()
+        _lib.check(self._h.h, self._h.lib.css_stream_preview_many(self._h.h, items, len(part), C.byref(stats)))
+        self.stats = stats
+        got = {}
+        for it, s, out in zip(items, part, outs):
+            if it.status == _lib.CSS_OK:
+                s.preview_first_sample = int(it.first_sample)
+                got[id(s)] = [out[k, :it.n_out].copy() for k in range(s.num_spks)]
+        return [got.get(id(s)) for s in self.streams]

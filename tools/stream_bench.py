@@ -23,6 +23,10 @@ every arm is compared with css_run of the dequantised recording (profiles/r11_st
 With --rate HZ the recordings are 16-bit PCM at HZ (the synthetic meeting interpolated to that rate) and the streams are opened
 with input_rate=HZ: one arm, (R) one css_stream_push_many_pcm16 per round of 1.5 s at HZ, resampled to 16 kHz by the ingest
 kernel; compared with css_run of Handle.resample of the recording (--pinned as above; profiles/r12_stream_rate.json).
+
+With --preview arm B runs alone and every round is followed by (P) one css_stream_preview_many of all streams, timed on its own;
+at three rounds of a pass every stream's preview is compared with css_run of the samples pushed so far, outside the clock
+(profiles/r13_stream_preview.json).  --passes sets the timed passes over the recordings (default 2).
 """
 import argparse
 import json
@@ -43,7 +47,7 @@ HANDOFF = dict(n_mels=80, pad_frames=8, drop_silence=True)
 
 
 def group_bench(n_streams, out_path, seconds=60.0, round_s=1.5, block=5, passes=2, handoff=False, only_grouped=False, pcm16=False,
-                pinned=False, rate=0):
+                pinned=False, rate=0, preview=False):
     import notsofar1_challenge_amd.css as CSS
     import notsofar1_challenge_amd.separator as SEP
     import notsofar1_challenge_amd.stream as STR
@@ -75,8 +79,10 @@ def group_bench(n_streams, out_path, seconds=60.0, round_s=1.5, block=5, passes=
     refs = [sep.handle.run(x, rc).copy() for x in recs]
     step = int(round_s * (rate or FS))
     arms = "RR" if rate else ("BC" if pcm16 else "AB")
-    ms = {"A": [], "B": [], "C": [], "R": []}
-    same = {"A": True, "B": True, "C": True, "R": True}
+    only_grouped = only_grouped or preview
+    ms = {"A": [], "B": [], "C": [], "R": [], "P": []}
+    same = {"A": True, "B": True, "C": True, "R": True, "P": True}
+    preview_checks, preview_samples, preview_segments = [], [], []
     seg_per_batch = []
     mel_frames = []
 
@@ -96,11 +102,26 @@ def group_bench(n_streams, out_path, seconds=60.0, round_s=1.5, block=5, passes=
             else:
                 res = group.push(chunks)
             dt = time.perf_counter() - t
+            batches, segments = group.stats.estimator_batches, group.stats.estimator_segments
+            if preview:
+                t = time.perf_counter()
+                pv = group.preview()
+                dt_p = time.perf_counter() - t
+                if timed:
+                    ms["P"].append(dt_p * 1e3)
+                    preview_segments.append(group.stats.estimator_segments / max(group.stats.estimator_batches, 1))
+                    preview_samples.append(float(np.median([p[0].shape[0] for p in pv if p is not None] or [0])))
+                    if r in (n_rounds // 8, n_rounds // 2, n_rounds - 2):   # css_run of every prefix, outside the clock
+                        for i, p in enumerate(pv):
+                            n = min((r + 1) * step, recs[i].shape[0])
+                            want = sep.handle.run(recs[i][:n], rc)[:, em[i] + res[i][0].shape[0]:]
+                            same["P"] = same["P"] and p is not None and bool(np.array_equal(np.stack(p), want))
+                        preview_checks.append(r)
             if not timed:
                 continue
             ms[arm].append(dt * 1e3)
-            if arm != "A" and group.stats.estimator_batches:
-                seg_per_batch.append(group.stats.estimator_segments / group.stats.estimator_batches)
+            if arm != "A" and batches:
+                seg_per_batch.append(segments / batches)
             if handoff:
                 mel_frames.append(sum(m.shape[1] for s in streams for m in s.handoff.mel))
             for i, got in enumerate(res):
@@ -134,7 +155,12 @@ def group_bench(n_streams, out_path, seconds=60.0, round_s=1.5, block=5, passes=
     elif pcm16:
         res["input"] = "16-bit PCM at 0.2 of full scale; arm B is fed the dequantised float32 samples, arm C the int16 samples (%s)" % (
             "page-locked" if pinned else "pageable")
+    if preview:
+        res["preview"] = {"rounds_compared_with_css_run_of_the_prefix": preview_checks,
+                          "samples_per_stream_median": float(np.median(preview_samples)) if preview_samples else 0.0,
+                          "segments_per_estimator_batch_median": float(np.median(preview_segments)) if preview_segments else 0.0}
     for arm, what in (("A", "one css_stream_push per stream and round"), ("B", "one css_stream_push_many per round"),
+                      ("P", "one css_stream_preview_many per round, after arm B's push"),
                       ("C", "one css_stream_push_many_pcm16 per round"),
                       ("R", "one css_stream_push_many_pcm16 per round, streams opened with input_rate")):
         if not ms[arm]:
@@ -146,6 +172,9 @@ def group_bench(n_streams, out_path, seconds=60.0, round_s=1.5, block=5, passes=
                             "streams_in_real_time_per_gpu": round(round_s * 1e3 / p50 * n_streams, 1), "bit_identical": same[arm]}
     if "C" in res["arms"]:
         res["p50_ratio_C_over_B"] = round(res["arms"]["C"]["round_ms_p50"] / res["arms"]["B"]["round_ms_p50"], 4)
+    if "P" in res["arms"]:
+        res["arms"]["P"].pop("streams_in_real_time_per_gpu")
+        res["p50_ratio_P_over_B"] = round(res["arms"]["P"]["round_ms_p50"] / res["arms"]["B"]["round_ms_p50"], 4)
     if "A" in res["arms"]:
         res["p50_ratio_B_over_A"] = round(res["arms"]["B"]["round_ms_p50"] / res["arms"]["A"]["round_ms_p50"], 4)
     sep.close()
@@ -166,10 +195,13 @@ def main():
     ap.add_argument("--pcm16", action="store_true", help="with --streams: arms B (float32) and C (css_stream_push_many_pcm16) on 16-bit recordings")
     ap.add_argument("--pinned", action="store_true", help="with --pcm16: arm C's int16 samples in page-locked memory")
     ap.add_argument("--rate", type=int, default=0, help="with --streams: 16-bit recordings at this rate, streams opened with input_rate (arm R alone)")
+    ap.add_argument("--preview", action="store_true", help="with --streams: arm B alone, each round followed by one css_stream_preview_many (arm P)")
+    ap.add_argument("--passes", type=int, default=2, help="with --streams: timed passes over the recordings")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.streams:
-        return group_bench(a.streams, a.out, handoff=a.handoff, only_grouped=a.only_grouped, pcm16=a.pcm16, pinned=a.pinned, rate=a.rate)
+        return group_bench(a.streams, a.out, handoff=a.handoff, only_grouped=a.only_grouped, pcm16=a.pcm16, pinned=a.pinned, rate=a.rate,
+                           preview=a.preview, passes=a.passes)
     import notsofar1_challenge_amd.css as CSS
     import notsofar1_challenge_amd.separator as SEP
     import notsofar1_challenge_amd.stream as STR
