@@ -19,7 +19,9 @@ the int16 chunks cross PCIe as they were captured and the ingest kernel resample
 With --preview every tick also asks for the unfinished tail (CssStream.preview / CssStreamGroup.preview): the provisional
 samples between the final ones and the present -- css_run of what was pushed so far -- while the stream stays as it was.  Each
 tick prints how far the final and the provisional output reach behind the input; a caption host shows the provisional part
-at once and replaces it as it becomes final.
+at once and replaces it as it becomes final.  With --preview --logmel the preview also hands off (preview(handoff=True)): the
+provisional log-mel frames and kept seconds up to the present are printed next to the final ones; the host places them behind
+frame preview_handoff.first_frame[k] of speaker k's frames so far and normalises with preview_handoff.raw_max[k].
 
     python examples/live_stream.py [--seconds 30] [--rooms N] [--logmel] [--pcm16] [--rate HZ] [--preview]
 """
@@ -48,6 +50,16 @@ def print_handoff(streams, fs):
         h = s.handoff
         per = [f"{m.shape[1]:4d} fr {float((g[:, 1] - g[:, 0]).sum()) / fs:5.2f} s" for m, g in zip(h.mel, h.ranges)]
         print(f"    room {r}: " + " | ".join(per))
+
+
+def print_preview_handoff(streams, fs):
+    """per room and speaker: provisional log-mel frames (from which frame of the concatenation on) and kept seconds"""
+    for r, s in enumerate(streams):
+        h = s.preview_handoff
+        if h is None:
+            continue
+        per = [f"{m.shape[1]:4d} fr from {int(j):5d} {float((g[:, 1] - g[:, 0]).sum()) / fs:5.2f} s" for m, g, j in zip(h.mel, h.ranges, h.first_frame)]
+        print(f"    room {r} provisional: " + " | ".join(per))
 
 
 def capture(mix):
@@ -97,10 +109,12 @@ def rooms(sep, n_rooms, seconds, fs, chunk, logmel=False, pcm16=False, rate=None
             print_handoff(streams, fs)
         if preview:
             t = time.perf_counter()
-            pv = group.preview()
+            pv = group.preview(handoff=logmel)
             ms = (time.perf_counter() - t) * 1e3
             print(f"    preview {ms:6.2f} ms, one batch of {group.stats.estimator_segments} segments; room 0: "
                   + behind(inf, streams[0].preview_first_sample, None if pv[0] is None else pv[0][0].shape[0], fs))
+            if logmel:
+                print_preview_handoff(streams, fs)
     for s, room in zip(streams, outs):
         for k, o in enumerate(s.finish()):
             room[k].append(o)
@@ -150,10 +164,12 @@ def main():
                     mels[k].append(m)
             if a.preview:
                 try:
-                    count = s.preview()[0].shape[0]
+                    count = s.preview(handoff=a.logmel)[0].shape[0]
                 except AssertionError:   # css_run's own refusal of a recording of at most one segment (css.py:297)
                     count = None
                 print("    " + behind(inf, s.preview_first_sample, count, fs))
+                if a.logmel and count is not None:
+                    print_preview_handoff([s], fs)
         for k, o in enumerate(s.finish()):
             streams[k].append(o)
         if a.logmel:

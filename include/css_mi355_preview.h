@@ -10,7 +10,8 @@
  *
  * Cost: for every prefix exactly one segment is not done yet, so a preview passes ONE segment per stream through the mask
  * estimator; the grouped call passes the pending segments of all its streams as one batch, as a grouped push does.  The
- * hand-off takes no part: no log-mel frame, range or gate byte is produced or moved.
+ * hand-off takes no part in the calls of this header: no log-mel frame, range or gate byte is produced or moved.  The preview
+ * that also returns the hand-off's outputs up to the present is declared in css_mi355_preview_handoff.h.
  */
 #ifndef CSS_MI355_PREVIEW_H
 #define CSS_MI355_PREVIEW_H

@@ -110,6 +110,10 @@ class CssStreamHandoffOut(C.Structure):
                 ("raw_max", C.c_void_p), ("n_activity", C.c_int64), ("first_activity_frame", C.c_int64)]
 
 
+class CssStreamPreviewHandoff(C.Structure):
+    _fields_ = [("p", CssStreamPreview), ("ho", C.POINTER(CssStreamHandoffOut)), ("first_frame", C.c_void_p)]
+
+
 class CssGemmDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("kernel", "layout", "tile_rows", "batch", "M", "N", "K", "act")] + \
                [(n, C.c_int64) for n in ("lda", "ldb", "ldc", "ldr", "strideA", "strideB", "strideC", "a_off", "c_off", "r_off",
@@ -239,6 +243,12 @@ SIGNATURES_PREVIEW = {
     "css_stream_preview": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "css_stream_preview_many": (C.c_int, [_P, C.POINTER(CssStreamPreview), C.c_int32, C.POINTER(CssStreamGroupStats)]),
 }
+# the entry points include/css_mi355_preview_handoff.h declares (a preview that also hands off), the fourth table load() applies
+SIGNATURES_PREVIEW_HANDOFF = {
+    "css_stream_preview_handoff": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                             C.POINTER(CssStreamHandoffOut), _P]),
+    "css_stream_preview_handoff_many": (C.c_int, [_P, C.POINTER(CssStreamPreviewHandoff), C.c_int32, C.POINTER(CssStreamGroupStats)]),
+}
 RESAMPLE_TILE = 256                              # output samples per block of the two resampling kernels (resample.hip RS_TILE)
 
 _lib: Optional[C.CDLL] = None
@@ -280,7 +290,8 @@ def load() -> C.CDLL:
         lib = C.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover
         raise CssLibraryError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_RATE.items()) + list(SIGNATURES_PREVIEW.items()):
+    for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_RATE.items()) + list(SIGNATURES_PREVIEW.items()) +
+                              list(SIGNATURES_PREVIEW_HANDOFF.items())):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -19,7 +19,8 @@
 // in all streams of one segmentation pass the estimator as ONE batch (every estimator kernel is batch invariant in exact
 // float32, as for queued sessions: api_queue.hip run_group), so N live meetings cost about one estimator pass per tick
 // instead of N.  css_stream_push(_pcm16) is a group of one item; css_stream_finish and the previews (css_stream_preview*,
-// include/css_mi355_preview.h) run the same segments() / tail() in closing_pass: finish with one job, a preview with N and no commit.
+// include/css_mi355_preview.h, css_mi355_preview_handoff.h) run the same segments() / tail() in closing_pass: finish with one job,
+// a preview with N and no commit.
 //
 // The hand-off (css_stream_handoff_*): a stream that has it switched on also returns, with every call, the gate
 // bits, the kept sample ranges and the raw Whisper log-mel frames that became final.  The step sits between tail() and the
@@ -33,12 +34,22 @@
 #include "api_ctx.hpp"
 #include "../../include/css_mi355_rate.h"
 #include "../../include/css_mi355_preview.h"
+#include "../../include/css_mi355_preview_handoff.h"
 
 #include <climits>
 
 namespace {
 
 constexpr int PIECE_SEGMENTS = 8;
+
+// The host's mirrors of a hand-off stream: gate bytes of frames [hist_base, t_g) per speaker, samples appended, frames emitted,
+// running maximum.  (A preview collects on a copy.)
+struct HandoffMirror {
+    std::vector<std::vector<uint8_t>> hist;
+    int64_t hist_base = 0;
+    std::vector<int64_t> A, J;
+    std::vector<float> raw_max;
+};
 
 // Per stream with the hand-off on.  Nothing here is part of the window: the rebase never touches it.
 struct HandoffStream {
@@ -50,16 +61,13 @@ struct HandoffStream {
     int64_t gate_ld = 0, gate_mask = 0, carry_ld = 1;
     int cur = 0;
     int64_t D = 0;                      // decided samples
-    // host mirrors: gate bytes of frames [hist_base, t_g) per speaker, samples appended, frames emitted, running maximum
-    std::vector<std::vector<uint8_t>> hist;
-    int64_t hist_base = 0;
-    std::vector<int64_t> A, J;
-    std::vector<float> raw_max;
+    HandoffMirror m;
 };
 
 // Per handle, made when the first stream switches the hand-off on.
 struct HandoffCtx {
     DevBuf tab, operand, spec, res, state;   // DFT matrix + both filterbanks; frame operand; spectra; a round's results; HandoffState per (id, k)
+    DevBuf state_pv;                         // a preview's closing round writes its counts and maximum here, never into `state`
     struct Pinned { void* p = nullptr; size_t cap = 0; };
     std::vector<Pinned> pinned;              // staging of round r of a call
     int32_t launches = 0, products = 0;
@@ -413,11 +421,8 @@ int check_handoff_cfg(const CssStreamHandoffCfg* c) {
     return CSS_OK;
 }
 
-// what a call must find bound to a stream with the hand-off on
-int check_handoff_call(css_ctx* h, const StreamState* s, int64_t n_samples, std::string* why) {
-    if (!s->ho) return CSS_OK;
-    const CssStreamHandoffOut* o = s->ho->bound;
-    if (!o) { *why = "the hand-off is on and nothing is bound (css_stream_handoff_bind)"; return CSS_ERR_STATE; }
+// what a call must find in the hand-off outputs `o` of a stream with the hand-off on
+int check_handoff_out(const StreamState* s, const CssStreamHandoffOut* o, int64_t n_samples, std::string* why) {
     const HandoffNeed n = handoff_need(s->T, s->hop, s->halo, s->ho->cfg, n_samples);
     if (!o->mel_host || !o->ranges_host || !o->n_frames || !o->n_ranges || !o->raw_max || o->cap_frames < n.frames ||
         o->cap_ranges < n.ranges || (o->activity_host && o->cap_activity < n.activity)) {
@@ -425,6 +430,12 @@ int check_handoff_call(css_ctx* h, const StreamState* s, int64_t n_samples, std:
         return CSS_ERR_INVALID_ARG;
     }
     return CSS_OK;
+}
+// ... bound to it
+int check_handoff_call(css_ctx* h, const StreamState* s, int64_t n_samples, std::string* why) {
+    if (!s->ho) return CSS_OK;
+    if (!s->ho->bound) { *why = "the hand-off is on and nothing is bound (css_stream_handoff_bind)"; return CSS_ERR_STATE; }
+    return check_handoff_out(s, s->ho->bound, n_samples, why);
 }
 
 HandoffCtx* handoff_ctx(css_ctx* h) { return static_cast<HandoffCtx*>(h->handoff); }
@@ -441,7 +452,10 @@ struct HandoffRec {
     const uint8_t* act; const int32_t* n_new; const float* mel; int64_t mel_ld; const HandoffState* st;   // in page-locked staging
 };
 
-int handoff_round(css_ctx* h, const std::vector<HandoffJob>& all, size_t round, std::vector<HandoffRec>* recs) {
+// commit: the streams' decided counts, generations and device state move (a push, finish).  Without it (a preview with hand-off)
+// the round reads the same inputs and writes only what is scratch until a commit: the other generation of carry and tail, the
+// handle's operand / spectra / results and the state_pv rows.
+int handoff_round(css_ctx* h, const std::vector<HandoffJob>& all, size_t round, std::vector<HandoffRec>* recs, bool commit = true) {
     HandoffCtx* c = handoff_ctx(h);
     std::vector<HandoffJob> jobs;
     for (const HandoffJob& j : all)
@@ -496,8 +510,9 @@ int handoff_round(css_ctx* h, const std::vector<HandoffJob>& all, size_t round, 
         HandoffStream* o = j.s->ho;
         int id = 0;
         while (h->streams[id] != j.s) ++id;
-        HandoffState* st = (HandoffState*)c->state.p + (size_t)id * SMAX;
-        ap[i].st = st;
+        ap[i].st = (const HandoffState*)c->state.p + (size_t)id * SMAX;
+        HandoffState* st = (HandoffState*)(commit ? c->state.p : c->state_pv.p) + (size_t)id * SMAX;
+        ap[i].st_out = st;
         ap[i].act_out = (uint8_t*)c->res.p + act_off[i];
         ap[i].n_new = (int32_t*)((char*)c->res.p + new_off[i]);
         me[i] = HandoffMel{ap[i].row0, ap[i].rows, ap[i].n_new, st, dftm + HO_DFT_F + (o->cfg.n_mels == 80 ? 0 : HO_MEL80_F), o->cfg.n_mels,
@@ -510,8 +525,10 @@ int handoff_round(css_ctx* h, const std::vector<HandoffJob>& all, size_t round, 
         r.mel_ld = ap[i].rows;
         r.st = (const HandoffState*)((const char*)pin.p + res_b) + (size_t)id * SMAX;
         recs->push_back(r);
-        o->D = ap[i].D1;
-        o->cur = 1 - o->cur;
+        if (commit) {
+            o->D = ap[i].D1;
+            o->cur = 1 - o->cur;
+        }
     }
     launch_handoff_append_multi(ap.data(), (int)n, (float*)c->operand.p, h->stream);
     GemmArgs g{};
@@ -522,15 +539,17 @@ int handoff_round(css_ctx* h, const std::vector<HandoffJob>& all, size_t round, 
     const int tables = (int)((n + HANDOFF_MULTI_MAX - 1) / HANDOFF_MULTI_MAX);
     c->launches += 2 * tables + 1; c->products += 1; c->frames += rows_total;
     HIPCHK(h, hipMemcpyAsync(pin.p, c->res.p, res_b, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync((char*)pin.p + res_b, c->state.p, state_b, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync((char*)pin.p + res_b, commit ? c->state.p : c->state_pv.p, state_b, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipGetLastError());
     return CSS_OK;
 }
 
-// After the call's synchronise: the rounds' results of ONE stream, in order, trimmed into what is bound to it.
-int handoff_collect(css_ctx* h, StreamState* s, int item, int64_t t_g_before, const std::vector<HandoffRec>& recs) {
-    HandoffStream* o = s->ho;
-    CssStreamHandoffOut* out = o->bound;
+// After the call's synchronise: the rounds' results of ONE stream, in order, trimmed into `out`, on the mirrors `mir`: the
+// stream's own and what is bound to it (a push, finish: a failure ends the stream, which has moved already), or a copy and the
+// caller's outputs (a preview: the failure is that call's error, the stream has not moved).
+int handoff_collect(css_ctx* h, StreamState* s, int item, int64_t t_g_before, const std::vector<HandoffRec>& recs, HandoffMirror& mir,
+                    CssStreamHandoffOut* out, bool commit) {
+    const HandoffStream* o = s->ho;
     const int S = h->d.num_spks, hopS = h->d.frame_hop, N = h->d.frame_len, nm = o->cfg.n_mels;
     std::vector<std::vector<int64_t>> reg((size_t)S);
     std::vector<int64_t> nfr((size_t)S, 0);
@@ -539,7 +558,7 @@ int handoff_collect(css_ctx* h, StreamState* s, int item, int64_t t_g_before, co
         if (r.s != s || r.item != item) continue;
         const int64_t nt = r.t_g1 - r.t_g0;
         for (int k = 0; k < S; ++k) {
-            std::vector<uint8_t>& hist = o->hist[(size_t)k];
+            std::vector<uint8_t>& hist = mir.hist[(size_t)k];
             hist.insert(hist.end(), r.act + (size_t)k * nt, r.act + (size_t)(k + 1) * nt);
             if (out->activity_host && nt > 0)
                 std::memcpy(out->activity_host + (size_t)k * out->cap_activity + n_act, r.act + (size_t)k * nt, (size_t)nt);
@@ -552,20 +571,22 @@ int handoff_collect(css_ctx* h, StreamState* s, int item, int64_t t_g_before, co
                     else { g.push_back(r.D0); g.push_back(r.D1); }
                 }
             } else {
-                handoff_kept_ranges(hist.data(), o->hist_base, r.t_g1, o->pad, hopS, N, r.D0, r.D1, r.closing ? r.n_out : INT64_MAX, g);
+                handoff_kept_ranges(hist.data(), mir.hist_base, r.t_g1, o->pad, hopS, N, r.D0, r.D1, r.closing ? r.n_out : INT64_MAX, g);
             }
             int64_t added = 0;   // samples this round appended: the new ranges, and what the last old one grew by
             for (size_t i = before; i + 1 < g.size(); i += 2) added += g[i + 1] - g[i];
             if (before) added += g[before - 1] - last_end;
-            const int64_t A1 = o->A[(size_t)k] + added;
+            const int64_t A1 = mir.A[(size_t)k] + added;
             const int64_t J1 = r.closing ? A1 / 160 : (A1 >= 201 ? (A1 - 200) / 160 + 1 : 0);
-            const int64_t nj = J1 - o->J[(size_t)k];
-            // internal consistency, not refusals: the stream has moved already, so it ends here (only css_stream_close is left)
+            const int64_t nj = J1 - mir.J[(size_t)k];
+            // internal consistency, not refusals: a stream that has moved already ends here (only css_stream_close is left)
             if (nj != r.n_new[k] || r.st[k].A != A1 || r.st[k].J != J1) {
+                if (!commit) return fail(h, CSS_ERR_STATE, "hand-off: the device's counts differ from the host's range rule in this preview");
                 s->finished = true;
                 return fail(h, CSS_ERR_STATE, "hand-off: the device's counts differ from the host's range rule; the stream is closed to further calls");
             }
             if (nfr[(size_t)k] + nj > out->cap_frames || (int64_t)(g.size() / 2) > out->cap_ranges) {
+                if (!commit) return fail(h, CSS_ERR_STATE, "hand-off: the capacities were exceeded in this preview");
                 s->finished = true;
                 return fail(h, CSS_ERR_STATE, "hand-off: the bound capacities were exceeded; the stream is closed to further calls");
             }
@@ -573,17 +594,17 @@ int handoff_collect(css_ctx* h, StreamState* s, int item, int64_t t_g_before, co
                 std::memcpy(out->mel_host + ((size_t)k * nm + m) * out->cap_frames + nfr[(size_t)k],
                             r.mel + ((size_t)k * nm + m) * r.mel_ld, (size_t)nj * sizeof(float));
             nfr[(size_t)k] += nj;
-            o->A[(size_t)k] = A1; o->J[(size_t)k] = J1;
+            mir.A[(size_t)k] = A1; mir.J[(size_t)k] = J1;
             const int b = r.st[k].gmax;
             const int bits = b >= 0 ? b : b ^ 0x7fffffff;
-            std::memcpy(&o->raw_max[(size_t)k], &bits, sizeof(float));
+            std::memcpy(&mir.raw_max[(size_t)k], &bits, sizeof(float));
         }
         n_act += nt;
         // frames that can still keep an undecided sample: from t_g - 2 pad - 2 on
-        const int64_t keep_from = std::max<int64_t>(r.t_g1 - 2 * (int64_t)o->pad - 3, o->hist_base);
-        if (keep_from > o->hist_base) {
-            for (int k = 0; k < S; ++k) o->hist[(size_t)k].erase(o->hist[(size_t)k].begin(), o->hist[(size_t)k].begin() + (keep_from - o->hist_base));
-            o->hist_base = keep_from;
+        const int64_t keep_from = std::max<int64_t>(r.t_g1 - 2 * (int64_t)o->pad - 3, mir.hist_base);
+        if (keep_from > mir.hist_base) {
+            for (int k = 0; k < S; ++k) mir.hist[(size_t)k].erase(mir.hist[(size_t)k].begin(), mir.hist[(size_t)k].begin() + (keep_from - mir.hist_base));
+            mir.hist_base = keep_from;
         }
     }
     for (int k = 0; k < S; ++k) {
@@ -591,7 +612,7 @@ int handoff_collect(css_ctx* h, StreamState* s, int item, int64_t t_g_before, co
         std::memcpy(out->ranges_host + (size_t)k * out->cap_ranges * 2, g.data(), g.size() * sizeof(int64_t));
         out->n_ranges[k] = (int32_t)(g.size() / 2);
         out->n_frames[k] = nfr[(size_t)k];
-        out->raw_max[k] = o->raw_max[(size_t)k];
+        out->raw_max[k] = mir.raw_max[(size_t)k];
     }
     out->n_activity = n_act;
     out->first_activity_frame = t_g_before;
@@ -637,7 +658,7 @@ void stream_destroy_all(css_ctx* h) {
     if (h->stream_masks.p) hipFree(h->stream_masks.p);
     h->stream_masks = DevBuf{};
     if (HandoffCtx* c = handoff_ctx(h)) {
-        for (DevBuf* d : {&c->tab, &c->operand, &c->spec, &c->res, &c->state})
+        for (DevBuf* d : {&c->tab, &c->operand, &c->spec, &c->res, &c->state, &c->state_pv})
             if (d->p) hipFree(d->p);
         for (HandoffCtx::Pinned& p : c->pinned)
             if (p.p) hipHostFree(p.p);
@@ -799,7 +820,7 @@ int push_items(css_ctx* h, const std::vector<PushItem>& items, bool pcm16, CssSt
     auto hand_out = [&]() {   // (a call that moved nothing still reports its empty hand-off)
         for (size_t i = 0; i < its.size(); ++i)
             if (its[i].s->ho) {
-                const int hrc = handoff_collect(h, its[i].s, (int)i, its[i].t_g_before, recs);
+                const int hrc = handoff_collect(h, its[i].s, (int)i, its[i].t_g_before, recs, its[i].s->ho->m, its[i].s->ho->bound, true);
                 if (hrc != CSS_OK) return hrc;
             }
         return (int)CSS_OK;
@@ -982,8 +1003,15 @@ int css_stream_push_pcm16(css_handle_t h, int32_t id, const int16_t* pcm16_host,
 // tail); segments() runs that segment of every stream (the estimator as one batch per segmentation) and tail() closes every
 // stream's output with the last-segment window; then the downloads and ONE synchronise.
 //   commit      css_stream_finish: the hand-off's closing round runs, and the progress counters move to the recording's end.
-//   no commit   a preview: no hand-off (StreamStitchArgs::gate_out stays null, so the gate ring is not written) and nothing
-//               of StreamState, RateStream or HandoffStream changes but the window's generation, if a rebase was needed.  Every
+//   no commit   a preview: nothing of StreamState, RateStream or HandoffStream changes but the window's generation, if a rebase
+//               was needed.  Without hand-off outputs (CloseJob::ho null) StreamStitchArgs::gate_out stays null, so the gate
+//               ring is not written.  With them (css_mi355_preview_handoff.h) the gate bytes of frames [t_g, mix_frames) go
+//               into the stream's own ring and the hand-off's closing round runs without a commit (handoff_round): D, cur, the
+//               device's HandoffState rows and the host mirrors stay, the results are collected on a copy of the mirrors into
+//               the caller's outputs.  The ring holds >= WF + 2 pad + 8 frames and mix_frames - t_g <= WF (both lie in the
+//               window and the window starts at or before t_g), so the provisional bytes replace no frame from
+//               t_g - 2 pad - 3 on, the oldest a later round reads; a later round writes frames [t_g, its t_g1) again before
+//               its append kernel reads them, and reads none from its t_g1 on.  Every
 //               device region written here is written again before a later pass reads it, because sd, t_st and t_g stay:
 //               mask / sep / permutation / cost slots from sd - seg_base on, act_b from t_st on, G rows from t_g on, the window
 //               samples from n_pushed and the planes from frame K on (the next push's ingest and transform), and the scratch
@@ -994,6 +1022,8 @@ namespace {
 struct CloseJob {
     StreamState* s; CssPlan p; int64_t n_total;   // the recording's length in model-rate samples, its plan
     float* out_host; int64_t cap, need;           // samples [n_emitted, p.n_out) -> out_host[S][cap]
+    CssStreamHandoffOut* ho = nullptr;            // a preview with hand-off: the caller's outputs and first_frame [S]
+    int64_t* first_frame = nullptr;
 };
 
 int closing_pass(css_ctx* h, const std::vector<CloseJob>& jobs, bool commit, CssStreamGroupStats* stats) {
@@ -1001,7 +1031,9 @@ int closing_pass(css_ctx* h, const std::vector<CloseJob>& jobs, bool commit, Css
     int rc;
     std::vector<HandoffRec> recs;
     std::vector<int64_t> t_g_before(jobs.size());
-    if (commit) handoff_begin_call(h);
+    bool any_ho = commit;
+    for (const CloseJob& j : jobs) any_ho = any_ho || j.ho;
+    if (any_ho) handoff_begin_call(h);
     HIPCHK(h, hipSetDevice(h->device));
     const int hopS = h->d.frame_hop, F = h->d.num_bins, S = h->d.num_spks;
     std::vector<ResampleJob> rsj;
@@ -1047,27 +1079,35 @@ int closing_pass(css_ctx* h, const std::vector<CloseJob>& jobs, bool commit, Css
         if ((q_hi - s->t_g) * hopS > (int64_t)(s->out.cap / (sizeof(float) * S)) &&
             (rc = ensure(h, s->out, (size_t)S * (q_hi - s->t_g) * hopS * sizeof(float))) != CSS_OK) return rc;
         TailJob t{s, true, nseg, TL, s->t_st, TL, s->t_g, TL, q_hi};
-        t.gate = commit;
+        t.gate = commit || j.ho;
         tj.push_back(t);
     }
     if ((rc = segments(h, sj, stats)) != CSS_OK) return rc;
     if ((rc = tail(h, tj)) != CSS_OK) return rc;
-    if (commit) {
+    if (any_ho) {
         std::vector<HandoffJob> hj;
         for (size_t i = 0; i < jobs.size(); ++i) {
             StreamState* s = jobs[i].s;
             const int64_t TL = jobs[i].p.mix_frames;
-            hj.push_back(HandoffJob{s, (int)i, s->t_g, TL, (TL + 1 - s->t_g) * hopS, true, jobs[i].p.n_out});
+            if (commit || jobs[i].ho) hj.push_back(HandoffJob{s, (int)i, s->t_g, TL, (TL + 1 - s->t_g) * hopS, true, jobs[i].p.n_out});
         }
-        if ((rc = handoff_round(h, hj, 0, &recs)) != CSS_OK) return rc;
+        if ((rc = handoff_round(h, hj, 0, &recs, commit)) != CSS_OK) return rc;
     }
     for (const CloseJob& j : jobs)
         if ((rc = download(h, j.s, j.need, j.out_host, j.cap, 0)) != CSS_OK) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (!commit) return CSS_OK;
+    if (!commit) {
+        for (size_t i = 0; i < jobs.size(); ++i) {
+            if (!jobs[i].ho) continue;
+            HandoffMirror m = jobs[i].s->ho->m;
+            for (int k = 0; k < S; ++k) jobs[i].first_frame[k] = m.J[(size_t)k];
+            if ((rc = handoff_collect(h, jobs[i].s, (int)i, t_g_before[i], recs, m, jobs[i].ho, false)) != CSS_OK) return rc;
+        }
+        return CSS_OK;
+    }
     for (size_t i = 0; i < jobs.size(); ++i) {
         StreamState* s = jobs[i].s;
-        if (s->ho && (rc = handoff_collect(h, s, (int)i, t_g_before[i], recs)) != CSS_OK) return rc;
+        if (s->ho && (rc = handoff_collect(h, s, (int)i, t_g_before[i], recs, s->ho->m, s->ho->bound, true)) != CSS_OK) return rc;
         s->n_pushed = jobs[i].n_total;
         s->K = std::max(s->K, frames_of(jobs[i].n_total));
         s->sd = jobs[i].p.num_segments; s->t_st = s->t_g = jobs[i].p.mix_frames;
@@ -1113,14 +1153,18 @@ int css_stream_preview_samples(const CssModelDesc* desc, const CssRunCfg* cfg, i
     return p.zero_weight ? CSS_ERR_ZERO_WEIGHT : CSS_OK;
 }
 
-int css_stream_preview_many(css_handle_t h, CssStreamPreview* items, int32_t n_items, CssStreamGroupStats* stats) {
-    if (!h) return CSS_ERR_INVALID_ARG;
-    if (n_items < 0 || (n_items > 0 && !items)) return fail(h, CSS_ERR_INVALID_ARG, "bad argument");
+namespace {
+
+// one item of a grouped preview: the waveform item and, for a preview with hand-off, the caller's outputs
+struct PreviewItem { CssStreamPreview* p; CssStreamHandoffOut* ho; int64_t* first_frame; };
+
+int preview_items(css_ctx* h, const std::vector<PreviewItem>& items, CssStreamGroupStats* stats) {
+    const int32_t n_items = (int32_t)items.size();
     std::vector<CloseJob> jobs;
     std::vector<int32_t> status((size_t)n_items, CSS_OK);
     std::vector<int64_t> first((size_t)n_items, 0);
     for (int32_t i = 0; i < n_items; ++i) {
-        const CssStreamPreview& p = items[i];
+        const CssStreamPreview& p = *items[(size_t)i].p;
         auto refuse = [&](int code, const std::string& msg) {
             return fail(h, code, "item " + std::to_string(i) + " (stream " + std::to_string(p.id) + "): " + msg);
         };
@@ -1129,10 +1173,18 @@ int css_stream_preview_many(css_handle_t h, CssStreamPreview* items, int32_t n_i
         if (h->queued || !h->pending.empty())
             return refuse(CSS_ERR_STATE, "queued sessions (css_run_enqueue*) are outstanding: css_wait before using a stream");
         for (int32_t k = 0; k < i; ++k)
-            if (items[k].id == p.id) return refuse(CSS_ERR_INVALID_ARG, "the stream is named twice in one call");
+            if (items[(size_t)k].p->id == p.id) return refuse(CSS_ERR_INVALID_ARG, "the stream is named twice in one call");
         if (s->finished) return refuse(CSS_ERR_STATE, "the stream has finished");
         if (h->split) return refuse(CSS_ERR_STATE, "streams run in CSS_LINEAR_EXACT_F32 only");
         CloseJob j{s, CssPlan{}, closing_samples(s), p.out_host, p.cap, 0};
+        if (CssStreamHandoffOut* ho = items[(size_t)i].ho) {
+            if (!s->ho) return refuse(CSS_ERR_STATE, "the hand-off of this stream is off (css_stream_handoff_open)");
+            if (!items[(size_t)i].first_frame) return refuse(CSS_ERR_INVALID_ARG, "hand-off outputs without first_frame");
+            std::string why;
+            const int hrc = check_handoff_out(s, ho, -1, &why);   // a preview is a finish at this moment
+            if (hrc != CSS_OK) return refuse(hrc, why);
+            j.ho = ho; j.first_frame = items[(size_t)i].first_frame;
+        }
         plan_impl(h->d, s->cfg, j.n_total, &j.p);
         first[(size_t)i] = s->n_emitted;
         if (j.p.zero_weight) { status[(size_t)i] = CSS_ERR_ZERO_WEIGHT; continue; }   // (css_run's refusal of this prefix: the item's own)
@@ -1145,10 +1197,43 @@ int css_stream_preview_many(css_handle_t h, CssStreamPreview* items, int32_t n_i
     if (rc != CSS_OK) return rc;
     size_t k = 0;
     for (int32_t i = 0; i < n_items; ++i) {
-        items[i].status = status[(size_t)i];
-        items[i].first_sample = first[(size_t)i];
-        items[i].n_out = status[(size_t)i] == CSS_OK ? jobs[k++].need : 0;
+        CssStreamPreview& p = *items[(size_t)i].p;
+        p.status = status[(size_t)i];
+        p.first_sample = first[(size_t)i];
+        p.n_out = status[(size_t)i] == CSS_OK ? jobs[k++].need : 0;
     }
+    return CSS_OK;
+}
+
+}  // namespace
+
+int css_stream_preview_many(css_handle_t h, CssStreamPreview* items, int32_t n_items, CssStreamGroupStats* stats) {
+    if (!h) return CSS_ERR_INVALID_ARG;
+    if (n_items < 0 || (n_items > 0 && !items)) return fail(h, CSS_ERR_INVALID_ARG, "bad argument");
+    std::vector<PreviewItem> v;
+    for (int32_t i = 0; i < n_items; ++i) v.push_back(PreviewItem{&items[i], nullptr, nullptr});
+    return preview_items(h, v, stats);
+}
+
+// ---- previews with hand-off (include/css_mi355_preview_handoff.h) -------------------------------------------------------------
+int css_stream_preview_handoff_many(css_handle_t h, CssStreamPreviewHandoff* items, int32_t n_items, CssStreamGroupStats* stats) {
+    if (!h) return CSS_ERR_INVALID_ARG;
+    if (n_items < 0 || (n_items > 0 && !items)) return fail(h, CSS_ERR_INVALID_ARG, "bad argument");
+    std::vector<PreviewItem> v;
+    for (int32_t i = 0; i < n_items; ++i) v.push_back(PreviewItem{&items[i].p, items[i].ho, items[i].first_frame});
+    return preview_items(h, v, stats);
+}
+
+// a group of one item
+int css_stream_preview_handoff(css_handle_t h, int32_t id, float* out_host, int64_t cap, int64_t* n_out, int64_t* first_sample,
+                               CssStreamHandoffOut* ho, int64_t* first_frame) {
+    if (!h) return CSS_ERR_INVALID_ARG;
+    if (!n_out || !first_sample || !ho || !first_frame) return fail(h, CSS_ERR_INVALID_ARG, "null argument");
+    CssStreamPreviewHandoff it{CssStreamPreview{id, out_host, cap, 0, 0, CSS_OK}, ho, first_frame};
+    const int rc = css_stream_preview_handoff_many(h, &it, 1, nullptr);
+    if (rc != CSS_OK) return rc;
+    if (it.p.status != CSS_OK) return fail(h, it.p.status, "zero weights found. check hop_size, segment_size or m0, m1");
+    *n_out = it.p.n_out; *first_sample = it.p.first_sample;
     return CSS_OK;
 }
 
@@ -1261,12 +1346,13 @@ int css_stream_handoff_open(css_handle_t h, int32_t id, const CssStreamHandoffCf
         c = new HandoffCtx();
         h->handoff = c;
     }
-    if (!c->tab.p || !c->state.p) {
+    if (!c->tab.p || !c->state.p || !c->state_pv.p) {
         std::vector<float> t(HO_DFT_F + HO_MEL80_F + HO_MEL128_F, 0.f);
         handoff_build_dft(t.data());
         handoff_build_mel(t.data() + HO_DFT_F, 80);
         handoff_build_mel(t.data() + HO_DFT_F + HO_MEL80_F, 128);
         if ((rc = ensure(h, c->state, (size_t)CSS_MAX_STREAMS * SMAX * sizeof(HandoffState), true)) != CSS_OK) return rc;
+        if ((rc = ensure(h, c->state_pv, (size_t)CSS_MAX_STREAMS * SMAX * sizeof(HandoffState), true)) != CSS_OK) return rc;
         if ((rc = ensure(h, c->tab, t.size() * sizeof(float))) != CSS_OK) return rc;
         HIPCHK(h, hipMemcpy(c->tab.p, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));
     }
@@ -1296,9 +1382,9 @@ int css_stream_handoff_open(css_handle_t h, int32_t id, const CssStreamHandoffCf
         delete o;
         return rc != CSS_OK ? rc : fail(h, CSS_ERR_HIP, std::string("hand-off setup: ") + hipGetErrorString(e));
     }
-    o->hist.assign((size_t)S, std::vector<uint8_t>());
-    o->A.assign((size_t)S, 0); o->J.assign((size_t)S, 0);
-    o->raw_max.assign((size_t)S, -INFINITY);
+    o->m.hist.assign((size_t)S, std::vector<uint8_t>());
+    o->m.A.assign((size_t)S, 0); o->m.J.assign((size_t)S, 0);
+    o->m.raw_max.assign((size_t)S, -INFINITY);
     s->ho = o;
     return CSS_OK;
 }

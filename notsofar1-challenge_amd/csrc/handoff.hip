@@ -233,8 +233,9 @@ __global__ __launch_bounds__(256) void handoff_append_kernel(HandoffAppendTable 
     uint8_t* __restrict__ act = e.act_out + (int64_t)k * (e.t_g1 - e.t_g0);
     for (int64_t t = e.t_g0 + tid; t < e.t_g1; t += 256) act[t - e.t_g0] = gate[t & e.gate_mask];
     if (tid == 0) {
-        e.st[k].A = A1;
-        e.st[k].J = J1;
+        if (e.st_out != e.st) e.st_out[k].gmax = e.st[k].gmax;   // (a preview: the mel kernel folds into the scratch row)
+        e.st_out[k].A = A1;
+        e.st_out[k].J = J1;
         e.n_new[k] = (int)(J1 - J0);
     }
 }

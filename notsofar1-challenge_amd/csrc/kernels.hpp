@@ -213,7 +213,8 @@ struct HandoffAppend {
     const float* out; int64_t out_ld, out_base;         // the round's output samples [S][out_ld]; column 0 is sample out_base
     const float* carry_in; float* carry_out; int64_t carry_ld;   // undecided samples [D0, out_base) -> [D1, the round's end)
     const float* tail_in; float* tail_out;              // [S][HANDOFF_TAIL_LD]: concatenated samples not yet behind a frame
-    HandoffState* st;                                   // [S]
+    const HandoffState* st;                             // [S]: the counts and the maximum before the round
+    HandoffState* st_out;                               // [S]: after it.  A push: st itself; a preview: scratch rows (gmax is copied across)
     int64_t t_g0, t_g1, D0, D1;                         // gated-final frames and decided samples before / after the round
     int pad, drop, closing, S;
     int64_t row0, rows;                                 // speaker k owns operand rows [row0 + k rows, row0 + (k + 1) rows)
@@ -221,7 +222,7 @@ struct HandoffAppend {
 };
 struct HandoffMel {
     int64_t row0, rows;                                 // as above: the entry's columns of the spectra
-    const int32_t* n_new; HandoffState* st;             // [S] each
+    const int32_t* n_new; HandoffState* st;             // [S] each (st: the append entry's st_out)
     const float* w; int n_mels;                         // the entry's filterbank [n_mels][201]
     float* mel; int64_t mel_ld;                         // out [S][n_mels][mel_ld]
 };

@@ -27,6 +27,12 @@ count input samples, everything a stream returns stays at the model rate.
 ``preview()`` on both (css_stream_preview, css_stream_preview_many; include/css_mi355_preview.h) returns the unfinished tail: the
 samples between the final ones and the present, equal to ``css_run`` of what was pushed so far, bit for bit, while the stream
 stays as it was.  One pending segment per stream passes the estimator; a grouped preview is one batch for all its streams.
+
+``preview(handoff=True)`` on a stream opened with ``handoff=`` (css_stream_preview_handoff, css_stream_preview_handoff_many;
+include/css_mi355_preview_handoff.h) also sets ``stream.preview_handoff``: the hand-off outputs ``finish`` would return at this
+moment -- provisional raw log-mel frames from frame ``first_frame[k]`` of stream k's concatenation on, the kept ranges of the
+undecided samples, the gate bits up to the present and the maximum over all of it -- while ``stream.handoff``, the last push's,
+and the stream stay as they were.  With what the pushes returned this is ``Handle.handoff_logmel`` of the prefix, bit for bit.
 """
 from __future__ import annotations
 
@@ -78,9 +84,11 @@ class Handoff:
     ``ranges[k]`` the sample ranges [r, 2] (int64) appended to k's concatenation, ``activity[k]`` the gate bits of frames
     ``first_activity_frame`` .. and ``raw_max[k]`` the maximum of every raw value returned for k so far."""
 
-    def __init__(self, mel, ranges, activity, raw_max, first_activity_frame):
+    def __init__(self, mel, ranges, activity, raw_max, first_activity_frame, first_frame=None):
         self.mel, self.ranges, self.activity, self.raw_max = mel, ranges, activity, raw_max
         self.first_activity_frame = first_activity_frame
+        # a preview's hand-off only (``preview_handoff``): ``mel[k]`` starts at frame ``first_frame[k]`` of k's concatenation
+        self.first_frame = first_frame
 
 
 class CssStream:
@@ -116,6 +124,8 @@ class CssStream:
             self.resampler_lag_samples = 10 * max(up, down) // up
         self._out = np.empty((self.num_spks, 0), np.float32)
         self.handoff: Optional[Handoff] = None
+        self.preview_handoff: Optional[Handoff] = None
+        self._pv = None
         self.preview_first_sample = 0
         self._hcfg = None
         if handoff is not None:
@@ -246,16 +256,48 @@ class CssStream:
         f, c, _ = _lib.stream_preview_samples(desc, self._run_cfg, self._model_samples(n_pushed, True))
         return first, f + c - first
 
-    def preview(self) -> List[np.ndarray]:
+    def _preview_handoff_out(self):
+        """the outputs of a preview with hand-off (kept): (CssStreamHandoffOut, first_frame); sized for finish, which suffices"""
+        if self._pv is None:
+            S, nm = self.num_spks, int(self._hcfg.n_mels)
+            caps = _lib.stream_handoff_bounds(self.separator.desc, self._run_cfg, self._hcfg, -1)
+            arrays = (np.empty((S, nm, caps[0]), np.float32), np.empty((S, caps[1], 2), np.int64), np.empty((S, caps[2]), np.uint8),
+                      np.zeros(S, np.int64), np.zeros(S, np.int32), np.zeros(S, np.float32), np.zeros(S, np.int64))
+            o = _lib.CssStreamHandoffOut()
+            o.mel_host, o.cap_frames = arrays[0].ctypes.data, caps[0]
+            o.ranges_host, o.cap_ranges = arrays[1].ctypes.data, caps[1]
+            o.activity_host, o.cap_activity = arrays[2].ctypes.data, caps[2]
+            o.n_frames, o.n_ranges, o.raw_max = (a.ctypes.data for a in arrays[3:6])
+            self._pv = (o, arrays)
+        return self._pv[0], self._pv[1][6]
+
+    def _preview_handoff_take(self):
+        o, (mel, ranges, act, nf, nr, mx, first) = self._pv
+        na = int(o.n_activity)
+        S = range(self.num_spks)
+        self.preview_handoff = Handoff([mel[k, :, :nf[k]].copy() for k in S], [ranges[k, :nr[k]].copy() for k in S],
+                                       [act[k, :na].copy() for k in S], mx.copy(), int(o.first_activity_frame), first.copy())
+
+    def preview(self, handoff: bool = False) -> List[np.ndarray]:
         """The unfinished tail (css_stream_preview): samples [n_emitted, n_out) of ``css_run`` on what was pushed so far --
         what ``finish`` would return now -- while the stream stays as it was.  The samples are provisional: later pushes
         return other values for them once they are final.  ``preview_first_sample`` holds the first one's index.  Raises
         what ``css_run`` of the prefix raises (with the default windows: the reference's assert until more than one segment
-        was pushed)."""
+        was pushed).  ``handoff=True`` (css_stream_preview_handoff; a stream opened with ``handoff=``, else ValueError) also
+        sets ``preview_handoff`` to the hand-off outputs ``finish`` would return now; ``handoff`` stays the last push's."""
+        if handoff and self._hcfg is None:
+            raise ValueError("preview(handoff=True) needs a stream opened with handoff=")
         out = np.empty((self.num_spks, max(self.latency_samples, 1)), np.float32)
         n_out, first = C.c_int64(0), C.c_int64(0)
-        _lib.check(self._h.h, self._h.lib.css_stream_preview(self._h.h, self.id, out.ctypes.data_as(C.c_void_p), out.shape[1],
-                                                             C.byref(n_out), C.byref(first)))
+        if handoff:
+            ho, first_frame = self._preview_handoff_out()
+            _lib.check(self._h.h, self._h.lib.css_stream_preview_handoff(
+                self._h.h, self.id, out.ctypes.data_as(C.c_void_p), out.shape[1], C.byref(n_out), C.byref(first), C.byref(ho),
+                first_frame.ctypes.data_as(C.c_void_p)))
+            self._preview_handoff_take()
+        else:
+            _lib.check(self._h.h, self._h.lib.css_stream_preview(self._h.h, self.id, out.ctypes.data_as(C.c_void_p), out.shape[1],
+                                                                 C.byref(n_out), C.byref(first)))
         self.preview_first_sample = int(first.value)
         return [out[s, :n_out.value].copy() for s in range(self.num_spks)]
 
@@ -333,25 +375,37 @@ class CssStreamGroup:
             s._handoff_bind(x.shape[0])
         return self._call(self._h.lib.css_stream_push_many_pcm16, items, part, outs)
 
-    def preview(self, streams: Optional[Sequence[CssStream]] = None) -> List[Optional[List[np.ndarray]]]:
+    def preview(self, streams: Optional[Sequence[CssStream]] = None, handoff: bool = False) -> List[Optional[List[np.ndarray]]]:
         """``CssStream.preview`` of ``streams`` (default: every stream of the group) in ONE css_stream_preview_many: the pending
         segments of all of them share one estimator batch (``stats``).  Per stream of the group: its S arrays, or None for a
-        stream that took no part or whose prefix ``css_run`` refuses (a meeting that began less than a segment ago)."""
+        stream that took no part or whose prefix ``css_run`` refuses (a meeting that began less than a segment ago).
+        ``handoff=True``: ONE css_stream_preview_handoff_many; every previewed stream opened with ``handoff=`` gets its
+        ``preview_handoff``, the others (and a refused prefix) ``preview_handoff = None``."""
         part = self.streams if streams is None else list(streams)
         if any(s not in self.streams for s in part):
             raise ValueError("a stream that is not in this group")
-        items = (_lib.CssStreamPreview * max(len(part), 1))()
+        items = ((_lib.CssStreamPreviewHandoff if handoff else _lib.CssStreamPreview) * max(len(part), 1))()
         outs = []
         for it, s in zip(items, part):
             out = np.empty((s.num_spks, max(s.latency_samples, 1)), np.float32)
             outs.append(out)
-            it.id, it.out_host, it.cap = s.id, out.ctypes.data, out.shape[1]
+            p = it.p if handoff else it
+            p.id, p.out_host, p.cap = s.id, out.ctypes.data, out.shape[1]
+            if handoff and s._hcfg is not None:
+                ho, first_frame = s._preview_handoff_out()
+                it.ho, it.first_frame = C.pointer(ho), first_frame.ctypes.data
         stats = _lib.CssStreamGroupStats()
-        _lib.check(self._h.h, self._h.lib.css_stream_preview_many(self._h.h, items, len(part), C.byref(stats)))
+        fn = self._h.lib.css_stream_preview_handoff_many if handoff else self._h.lib.css_stream_preview_many
+        _lib.check(self._h.h, fn(self._h.h, items, len(part), C.byref(stats)))
         self.stats = stats
         got = {}
         for it, s, out in zip(items, part, outs):
-            if it.status == _lib.CSS_OK:
-                s.preview_first_sample = int(it.first_sample)
-                got[id(s)] = [out[k, :it.n_out].copy() for k in range(s.num_spks)]
+            p = it.p if handoff else it
+            if handoff:
+                s.preview_handoff = None
+            if p.status == _lib.CSS_OK:
+                s.preview_first_sample = int(p.first_sample)
+                got[id(s)] = [out[k, :p.n_out].copy() for k in range(s.num_spks)]
+                if handoff and s._hcfg is not None:
+                    s._preview_handoff_take()
         return [got.get(id(s)) for s in self.streams]

@@ -27,6 +27,10 @@ kernel; compared with css_run of Handle.resample of the recording (--pinned as a
 With --preview arm B runs alone and every round is followed by (P) one css_stream_preview_many of all streams, timed on its own;
 at three rounds of a pass every stream's preview is compared with css_run of the samples pushed so far, outside the clock
 (profiles/r13_stream_preview.json).  --passes sets the timed passes over the recordings (default 2).
+
+With --handoff --preview a third call follows: (PH) one css_stream_preview_handoff_many of all streams, timed on its own; at the
+same three rounds every stream's provisional frames, ranges and gate bits, with what its pushes returned so far, are compared
+with css_run_device + css_handoff_logmel of the samples pushed so far, outside the clock (profiles/r14_stream_preview_handoff.json).
 """
 import argparse
 import json
@@ -80,16 +84,45 @@ def group_bench(n_streams, out_path, seconds=60.0, round_s=1.5, block=5, passes=
     step = int(round_s * (rate or FS))
     arms = "RR" if rate else ("BC" if pcm16 else "AB")
     only_grouped = only_grouped or preview
-    ms = {"A": [], "B": [], "C": [], "R": [], "P": []}
-    same = {"A": True, "B": True, "C": True, "R": True, "P": True}
+    ms = {"A": [], "B": [], "C": [], "R": [], "P": [], "PH": []}
+    same = {"A": True, "B": True, "C": True, "R": True, "P": True, "PH": True}
+    preview_frames = []
     preview_checks, preview_samples, preview_segments = [], [], []
     seg_per_batch = []
     mel_frames = []
+
+    def prefix_handoff_equal(x, calls, pv_wav, pv):
+        """pushes' hand-offs + the preview's against css_run_device + css_handoff_logmel of the prefix x"""
+        import torch
+        import notsofar1_challenge_amd._lib as LIB
+        h = sep.handle
+        n_out = int(LIB.plan(desc, rc, x.shape[0]).n_out)
+        pcm = torch.from_numpy(np.ascontiguousarray(x)).cuda()
+        wav = torch.empty((3, n_out), dtype=torch.float32, device="cuda")
+        h.run_device(pcm.data_ptr(), x.shape[0], 7, rc, wav.data_ptr(), n_out)
+        torch.cuda.synchronize()
+        act = h.read(LIB.BUF_ACT_FINAL).copy()
+        ok = bool(np.array_equal(pv_wav, wav.cpu().numpy()[:, n_out - pv_wav.shape[1]:]))
+        for k in range(3):
+            mel, regions = h.handoff_logmel(wav.data_ptr(), n_out, k, **HANDOFF)
+            merged = []
+            for lo, hi in np.concatenate([c.ranges[k] for c in calls] + [pv.ranges[k]]):
+                if merged and lo <= merged[-1][1]:
+                    merged[-1][1] = max(merged[-1][1], int(hi))
+                else:
+                    merged.append([int(lo), int(hi)])
+            raw = np.concatenate([c.mel[k] for c in calls] + [pv.mel[k]], axis=1)
+            ok = ok and bool(np.array_equal(np.array(merged, np.int64).reshape(-1, 2), regions))
+            ok = ok and bool(np.array_equal(np.concatenate([c.activity[k] for c in calls] + [pv.activity[k]]), act[k]))
+            ok = ok and pv.first_frame[k] == sum(c.mel[k].shape[1] for c in calls)
+            ok = ok and bool(np.array_equal(STR.whisper_normalize(raw, pv.raw_max[k]), mel))
+        return ok
 
     def one_pass(first_arm, timed):
         streams = [STR.CssStream(sep, cfg, handoff=HANDOFF if handoff else None, input_rate=rate or None) for _ in recs]
         group = STR.CssStreamGroup(streams)
         em = [0] * n_streams
+        calls = [[] for _ in recs]   # (arm PH: every push's hand-off, for the comparison with the offline call)
         n_rounds = ((q16 if rate else recs)[0].shape[0] + step - 1) // step if timed else 2 * block
         for r in range(n_rounds):
             arm = "B" if only_grouped else arms[(r // block + (first_arm == arms[1])) % 2]
@@ -117,6 +150,21 @@ def group_bench(n_streams, out_path, seconds=60.0, round_s=1.5, block=5, passes=
                             want = sep.handle.run(recs[i][:n], rc)[:, em[i] + res[i][0].shape[0]:]
                             same["P"] = same["P"] and p is not None and bool(np.array_equal(np.stack(p), want))
                         preview_checks.append(r)
+            if preview and handoff:
+                for i, s in enumerate(streams):
+                    calls[i].append(s.handoff)
+                t = time.perf_counter()
+                pvh = group.preview(handoff=True)
+                dt_ph = time.perf_counter() - t
+                if timed:
+                    ms["PH"].append(dt_ph * 1e3)
+                    preview_frames.append(float(np.median([sum(m.shape[1] for m in s.preview_handoff.mel) for s in streams
+                                                           if s.preview_handoff is not None] or [0])))
+                    if r in (n_rounds // 8, n_rounds // 2, n_rounds - 2):   # the offline hand-off of every prefix, outside the clock
+                        for i, p in enumerate(pvh):
+                            n = min((r + 1) * step, recs[i].shape[0])
+                            same["PH"] = same["PH"] and p is not None and streams[i].preview_handoff is not None and \
+                                prefix_handoff_equal(recs[i][:n], calls[i], np.stack(p), streams[i].preview_handoff)
             if not timed:
                 continue
             ms[arm].append(dt * 1e3)
@@ -159,8 +207,11 @@ def group_bench(n_streams, out_path, seconds=60.0, round_s=1.5, block=5, passes=
         res["preview"] = {"rounds_compared_with_css_run_of_the_prefix": preview_checks,
                           "samples_per_stream_median": float(np.median(preview_samples)) if preview_samples else 0.0,
                           "segments_per_estimator_batch_median": float(np.median(preview_segments)) if preview_segments else 0.0}
+        if handoff:
+            res["preview"]["handoff_mel_frames_per_stream_median"] = float(np.median(preview_frames)) if preview_frames else 0.0
     for arm, what in (("A", "one css_stream_push per stream and round"), ("B", "one css_stream_push_many per round"),
                       ("P", "one css_stream_preview_many per round, after arm B's push"),
+                      ("PH", "one css_stream_preview_handoff_many per round, after arm P's preview"),
                       ("C", "one css_stream_push_many_pcm16 per round"),
                       ("R", "one css_stream_push_many_pcm16 per round, streams opened with input_rate")):
         if not ms[arm]:
@@ -175,6 +226,9 @@ def group_bench(n_streams, out_path, seconds=60.0, round_s=1.5, block=5, passes=
     if "P" in res["arms"]:
         res["arms"]["P"].pop("streams_in_real_time_per_gpu")
         res["p50_ratio_P_over_B"] = round(res["arms"]["P"]["round_ms_p50"] / res["arms"]["B"]["round_ms_p50"], 4)
+    if "PH" in res["arms"]:
+        res["arms"]["PH"].pop("streams_in_real_time_per_gpu")
+        res["p50_ratio_PH_over_P"] = round(res["arms"]["PH"]["round_ms_p50"] / res["arms"]["P"]["round_ms_p50"], 4)
     if "A" in res["arms"]:
         res["p50_ratio_B_over_A"] = round(res["arms"]["B"]["round_ms_p50"] / res["arms"]["A"]["round_ms_p50"], 4)
     sep.close()
@@ -195,7 +249,8 @@ def main():
     ap.add_argument("--pcm16", action="store_true", help="with --streams: arms B (float32) and C (css_stream_push_many_pcm16) on 16-bit recordings")
     ap.add_argument("--pinned", action="store_true", help="with --pcm16: arm C's int16 samples in page-locked memory")
     ap.add_argument("--rate", type=int, default=0, help="with --streams: 16-bit recordings at this rate, streams opened with input_rate (arm R alone)")
-    ap.add_argument("--preview", action="store_true", help="with --streams: arm B alone, each round followed by one css_stream_preview_many (arm P)")
+    ap.add_argument("--preview", action="store_true", help="with --streams: arm B alone, each round followed by one css_stream_preview_many (arm P) and, with --handoff, "
+                    "one css_stream_preview_handoff_many (arm PH)")
     ap.add_argument("--passes", type=int, default=2, help="with --streams: timed passes over the recordings")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
