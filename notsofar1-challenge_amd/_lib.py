@@ -122,6 +122,21 @@ class CssGemmDesc(C.Structure):
                [(n, C.c_int32) for n in ("b_frag32", "split_out", "c_transposed", "m_fastest", "nt_store", "concurrent")]
 
 
+class CssLayerNormDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("form", "rows", "D", "inplace")] + [(n, C.c_int64) for n in ("x_floats", "out_floats")]
+
+
+class CssConvModuleDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("form", "nseg", "T", "D", "taps", "reserved")] + \
+               [(n, C.c_int64) for n in ("x_floats", "out_floats")]
+
+
+class CssAttentionDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("mode", "nseg", "T", "D", "H", "maxlen", "K", "split_out")] + \
+               [("canary", C.c_uint32), ("reserved", C.c_int32)] + \
+               [(n, C.c_int64) for n in ("x_floats", "w_floats", "pe_floats", "qkv_floats", "ctx_floats")]
+
+
 class CssKernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("ms", C.c_float), ("launches", C.c_int32)]
 
@@ -249,6 +264,13 @@ SIGNATURES_PREVIEW_HANDOFF = {
                                              C.POINTER(CssStreamHandoffOut), _P]),
     "css_stream_preview_handoff_many": (C.c_int, [_P, C.POINTER(CssStreamPreviewHandoff), C.c_int32, C.POINTER(CssStreamGroupStats)]),
 }
+# the entry points include/css_mi355_encoder.h declares (the kernels of csrc/encoder.hip on caller data), the fifth table load() applies
+SIGNATURES_ENCODER = {
+    "css_layernorm_host": (C.c_int, [_P, C.POINTER(CssLayerNormDesc), _P, _P, _P, _P, _P, _P, _P, _P]),
+    "css_conv_module_host": (C.c_int, [_P, C.POINTER(CssConvModuleDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                       C.POINTER(C.c_int32)]),
+    "css_attention_host": (C.c_int, [_P, C.POINTER(CssAttentionDesc), _P, _P, _P, _P, _P, _P]),
+}
 RESAMPLE_TILE = 256                              # output samples per block of the two resampling kernels (resample.hip RS_TILE)
 
 _lib: Optional[C.CDLL] = None
@@ -291,7 +313,7 @@ def load() -> C.CDLL:
     except OSError as e:  # pragma: no cover
         raise CssLibraryError(f"cannot load {LIB_PATH}: {e}") from e
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_RATE.items()) + list(SIGNATURES_PREVIEW.items()) +
-                              list(SIGNATURES_PREVIEW_HANDOFF.items())):
+                              list(SIGNATURES_PREVIEW_HANDOFF.items()) + list(SIGNATURES_ENCODER.items())):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -709,6 +731,64 @@ class Handle:
         check(self.h, self.lib.css_gemm_host(self.h, C.byref(d), _np_ptr(a), _np_ptr(b), _np_ptr(bv) if bv is not None else None,
                                              _np_ptr(r) if r is not None else None, _np_ptr(out)))
         return out
+
+    # ---- the kernels of csrc/encoder.hip on caller data (include/css_mi355_encoder.h; tests/test_hip_encoder_kernels.py)
+    def layernorm(self, form: int, x: np.ndarray, rows: int, D: int, w, b, w2=None, b2=None, *, inplace: bool = False, y=None,
+                  z=None, ys=None):
+        """One LayerNorm launch (css_layernorm_host; the header describes the forms).  x, y, z, ys are the WHOLE flat float32
+        allocations (None: the launch does not get that pointer).  Returns (x, y, z, ys) as the launch left them."""
+        flat = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float32).reshape(-1).copy()
+        x, y, z, ys = flat(x), flat(y), flat(z), flat(ys)
+        w, b, w2, b2 = flat(w), flat(b), flat(w2), flat(b2)
+        outs = [a.size for a in (y, z, ys) if a is not None]
+        if len(set(outs)) > 1:
+            raise ValueError("y, z and ys are allocations of one length")
+        d = CssLayerNormDesc(form=int(form), rows=int(rows), D=int(D), inplace=int(bool(inplace)), x_floats=x.size,
+                             out_floats=outs[0] if outs else 0)
+        ptr = lambda a: None if a is None else _np_ptr(a)
+        check(self.h, self.lib.css_layernorm_host(self.h, C.byref(d), ptr(x), ptr(w), ptr(b), ptr(w2), ptr(b2), ptr(y), ptr(z), ptr(ys)))
+        return x, y, z, ys
+
+    def conv_module(self, form: int, x: np.ndarray, nseg: int, T: int, D: int, taps: int, ln_w, ln_b, pw, dw_wt, dw_b, bn_alpha,
+                    bn_beta, ln2_w=None, ln2_b=None, *, x_out=None, z=None, zs=None):
+        """The conv module, fused (form 0) or as its two-kernel fallback in place (form 1) (css_conv_module_host).  Returns
+        (launched, x, x_out, z, zs): whole allocations as the launches left them; launched is False when the fused kernel does
+        not cover (D, taps) or the device refused its LDS."""
+        flat = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float32).reshape(-1).copy()
+        x, x_out, z, zs = flat(x), flat(x_out), flat(z), flat(zs)
+        ops = [flat(a) for a in (ln_w, ln_b, pw, dw_wt, dw_b, bn_alpha, bn_beta, ln2_w, ln2_b)]
+        outs = [a.size for a in (x_out, z, zs) if a is not None]
+        if len(set(outs)) > 1:
+            raise ValueError("x_out, z and zs are allocations of one length")
+        if ops[2].size != 6 or ops[3].size != taps * D or any(a is not None and a.size != D for a in ops[:2] + ops[4:]):
+            raise ValueError("pw [6], dw_wt [taps][D], every other operand [D]")
+        d = CssConvModuleDesc(form=int(form), nseg=int(nseg), T=int(T), D=int(D), taps=int(taps), x_floats=x.size,
+                              out_floats=outs[0] if outs else 0)
+        ptr = lambda a: None if a is None else _np_ptr(a)
+        launched = C.c_int32(-1)
+        check(self.h, self.lib.css_conv_module_host(self.h, C.byref(d), ptr(x), *[ptr(a) for a in ops], ptr(x_out), ptr(z), ptr(zs),
+                                                    C.byref(launched)))
+        return bool(launched.value), x, x_out, z, zs
+
+    def attention(self, mode: int, x: np.ndarray, w: np.ndarray, bias: np.ndarray, pe: np.ndarray, nseg: int, T: int, D: int, H: int,
+                  maxlen: int, *, split_out: int = 0, canary: int = 0x7FC0BEEF, slack_rows: int = 0):
+        """QKV product + relative-position attention (css_attention_host; mode 0 exact float32, 1 split-f16, 2 any length).
+        Returns (qkv, ctx): the allocations of nseg * T + slack_rows rows of 3 D / D floats as the launches left them; every
+        float they did not write holds `canary`."""
+        flat = lambda a: np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
+        x, w, bias, pe = flat(x), flat(w), flat(bias), flat(pe)
+        K = w.size // (3 * D)
+        rows = nseg * T + int(slack_rows)
+        qkv = np.empty(rows * 3 * D, np.float32)
+        ctx = np.empty(rows * D, np.float32)
+        if bias.size != 3 * D:
+            raise ValueError("bias [3 D]")
+        d = CssAttentionDesc(mode=int(mode), nseg=int(nseg), T=int(T), D=int(D), H=int(H), maxlen=int(maxlen), K=int(K),
+                             split_out=int(split_out), canary=int(canary), x_floats=x.size, w_floats=w.size, pe_floats=pe.size,
+                             qkv_floats=qkv.size, ctx_floats=ctx.size)
+        check(self.h, self.lib.css_attention_host(self.h, C.byref(d), _np_ptr(x), _np_ptr(w), _np_ptr(bias), _np_ptr(pe), _np_ptr(qkv),
+                                                  _np_ptr(ctx)))
+        return qkv, ctx
 
     # ---- RCCL through the C ABI (css_comm_*): what a host in another language would call
     def comm_init(self, unique_id: bytes, nranks: int, rank: int):
