@@ -10,12 +10,18 @@ int fail(css_ctx* h, int code, const std::string& msg) {
     return code;
 }
 
+// `bytes` of fresh device memory in b (what it held is released first); css_create and css_resample_host word their own errors
+hipError_t dev_alloc(DevBuf& b, size_t bytes) {
+    hipError_t e = b.reset();
+    if (e == hipSuccess) e = hipMalloc(&b.p, bytes);
+    if (e == hipSuccess) b.cap = bytes;
+    return e;
+}
+
 int ensure(css_ctx* h, DevBuf& b, size_t bytes, bool zero) {
     if (bytes <= b.cap) return CSS_OK;
     if (b.p && h->queued) HIPCHK(h, hipDeviceSynchronize());   // queued passes may still use the old allocation
-    if (b.p) HIPCHK(h, hipFree(b.p));
-    b.p = nullptr;
-    b.cap = 0;
+    if (const hipError_t e = b.reset()) return fail(h, CSS_ERR_HIP, std::string("hipFree(b.p): ") + hipGetErrorString(e));
     HIPCHK(h, hipMalloc(&b.p, bytes));
     b.cap = bytes;
     if (zero) HIPCHK(h, hipMemsetAsync(b.p, 0, bytes, h->stream));
@@ -130,8 +136,8 @@ bool streams_share_a_queue(hipStream_t a, hipStream_t b, hipEvent_t e0, hipEvent
 // streams for lanes 1 .. 3, the copy stream and the tail stream, none of them on `main`'s hardware queue where that can
 // be had; false: something failed, the caller creates them plainly
 bool deal_streams(hipStream_t main, hipStream_t lane[4], hipStream_t* copy, hipStream_t* tail) {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return false;
+    Event e0, e1;
+    if (e0.create() != hipSuccess || e1.create() != hipSuccess) return false;
     std::vector<std::vector<hipStream_t>> cls;   // classes of candidates that share a queue; none shares the main stream's
     std::vector<hipStream_t> with_main;
     auto enough = [&]() {
@@ -151,8 +157,8 @@ bool deal_streams(hipStream_t main, hipStream_t lane[4], hipStream_t* copy, hipS
             if (streams_share_a_queue(c[0], st, e0, e1)) { c.push_back(st); placed = true; break; }
         if (!placed) cls.push_back({st});
     }
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
+    e0.reset();
+    e1.reset();
     if (hipGetLastError() != hipSuccess) ok = false;
     std::vector<hipStream_t> take;   // lane1, lane2, copy, tail, lane3
     if (ok && !cls.empty()) {
@@ -322,13 +328,14 @@ int ensure_activations(css_ctx* h, int64_t nb, int T) {
 // tile-major (gemm_split_wd.hip: the weight operand goes straight from global memory into MFMA registers) for the
 // layers whose weight is the B operand, row-major for the mask head, where the weight is the A operand.
 int make_split_weights(css_ctx* h) {
-    if (h->wsplit) return CSS_OK;
+    if (h->wsplit.p) return CSS_OK;
     const CssModelDesc& d = h->d;
     const int64_t need = bind_weights(d, nullptr, nullptr);
-    HIPCHK(h, hipMalloc((void**)&h->wsplit, need * sizeof(float)));
+    int rc;
+    if ((rc = ensure(h, h->wsplit, need * sizeof(float))) != CSS_OK) return rc;
     const int D = d.attention_dim, FF = d.linear_units;
     auto conv = [&](const float* w, int rows, int K) {
-        launch_split_convert_tiled(w, K, h->wsplit + (w - h->blob), rows, K, h->stream);
+        launch_split_convert_tiled(w, K, h->wsplit.as() + (w - h->blob.as()), rows, K, h->stream);
     };
     conv(h->w.embed_w, D, h->Kp);
     for (const BlockWeights& b : h->w.blocks) {
@@ -336,21 +343,21 @@ int make_split_weights(css_ctx* h) {
         conv(b.wqkv, 3 * D, D); conv(b.wo, D, D);
         conv(b.ffo_w1, FF, D); conv(b.ffo_w2, D, FF);
     }
-    launch_split_convert(h->w.head_w, D, h->wsplit + (h->w.head_w - h->blob), (int64_t)d.num_bins * (d.num_spks + d.num_nois), D,
+    launch_split_convert(h->w.head_w, D, h->wsplit.as() + (h->w.head_w - h->blob.as()), (int64_t)d.num_bins * (d.num_spks + d.num_nois), D,
                          D, h->stream);
     {
         const int nout = d.num_bins * (d.num_spks + d.num_nois);
-        HIPCHK(h, hipMalloc((void**)&h->head_tiled, (size_t)((nout + 31) / 32 * 32) * D * sizeof(float)));
-        launch_split_convert_tiled(h->w.head_w, D, h->head_tiled, nout, D, h->stream);
+        if ((rc = ensure(h, h->head_tiled, (size_t)((nout + 31) / 32 * 32) * D * sizeof(float))) != CSS_OK) return rc;
+        launch_split_convert_tiled(h->w.head_w, D, h->head_tiled.as(), nout, D, h->stream);
     }
     // the synthesis transform matrix, row-major split
-    HIPCHK(h, hipMalloc((void**)&h->dft_split, (size_t)d.frame_len * h->KIp * sizeof(float)));
-    launch_split_convert(h->dft_inv_t, h->KIp, h->dft_split, d.frame_len, h->KIp, h->KIp, h->stream);
-    HIPCHK(h, hipMalloc((void**)&h->dft_tiled, (size_t)((d.frame_len + 31) / 32 * 32) * h->KIp * sizeof(float)));
-    launch_split_convert_tiled(h->dft_inv_t, h->KIp, h->dft_tiled, d.frame_len, h->KIp, h->stream);
+    if ((rc = ensure(h, h->dft_split, (size_t)d.frame_len * h->KIp * sizeof(float))) != CSS_OK) return rc;
+    launch_split_convert(h->dft_inv_t.as(), h->KIp, h->dft_split.as(), d.frame_len, h->KIp, h->KIp, h->stream);
+    if ((rc = ensure(h, h->dft_tiled, (size_t)((d.frame_len + 31) / 32 * 32) * h->KIp * sizeof(float))) != CSS_OK) return rc;
+    launch_split_convert_tiled(h->dft_inv_t.as(), h->KIp, h->dft_tiled.as(), d.frame_len, h->KIp, h->stream);
     // the relative-position table, row-major split: the attention kernel uses its rows like key rows
     const int dk = D / d.attention_heads;
-    launch_split_convert(h->w.pe_k, dk, h->wsplit + (h->w.pe_k - h->blob), 2 * (int64_t)d.maxlen, dk, dk, h->stream);
+    launch_split_convert(h->w.pe_k, dk, h->wsplit.as() + (h->w.pe_k - h->blob.as()), 2 * (int64_t)d.maxlen, dk, dk, h->stream);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipGetLastError());
     return CSS_OK;
@@ -359,12 +366,12 @@ int make_split_weights(css_ctx* h) {
 // CSS_LINEAR_EXACT_F32: the Linear weights once more, float32 in the fragment order of gemm_f32.hip (GemmArgs::b_frag32): a
 // wave reads its 32 columns' operands of a slab as two coalesced 1 KiB loads straight into registers.  Built on first use.
 int make_frag_weights(css_ctx* h) {
-    if (h->wfrag) return CSS_OK;
+    if (h->wfrag.p) return CSS_OK;
     const CssModelDesc& d = h->d;
     const int64_t need = bind_weights(d, nullptr, nullptr);
-    HIPCHK(h, hipMalloc((void**)&h->wfrag, need * sizeof(float)));
+    if (const int rc = ensure(h, h->wfrag, need * sizeof(float))) return rc;
     const int D = d.attention_dim, FF = d.linear_units;
-    auto conv = [&](const float* w, int rows, int K) { launch_f32_fragments(w, K, h->wfrag + (w - h->blob), rows, K, h->stream); };
+    auto conv = [&](const float* w, int rows, int K) { launch_f32_fragments(w, K, h->wfrag.as() + (w - h->blob.as()), rows, K, h->stream); };
     conv(h->w.embed_w, D, h->Kp);
     for (const BlockWeights& b : h->w.blocks) {
         conv(b.ffi_w1, FF, D); conv(b.ffi_w2, D, FF);
@@ -416,7 +423,7 @@ int upload_analysis_matrix(css_ctx* h, int window) {
             m[(size_t)(F + f) * Lp + n] = (float)(0.0 - s_ * w);
         }
     }
-    return hipMemcpy(h->dft_fwd, m.data(), m.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess ? (int)CSS_OK : (int)CSS_ERR_HIP;
+    return hipMemcpy(h->dft_fwd.p, m.data(), m.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess ? (int)CSS_OK : (int)CSS_ERR_HIP;
 }
 
 // Frames [t_lo, t_hi) of C channels (channel c's samples at x + c x_stride, zero or finite up to 32 floats past the last
@@ -429,11 +436,11 @@ bool analysis_transform(css_ctx* h, const float* x, int64_t x_stride, int C, int
     if (t_hi <= t_lo) return true;
     if (h->fft512) {
         if (phase_done) *phase_done = phase != nullptr;
-        return launch_stft_fft(x, x_stride, C, t_lo, t_hi, h->stft_tab, out, row_ld, st, phase);
+        return launch_stft_fft(x, x_stride, C, t_lo, t_hi, h->stft_tab.as(), out, row_ld, st, phase);
     }
     const int F = h->d.num_bins;
     GemmArgs g{};
-    g.A = h->dft_fwd; g.lda = h->Lp; g.strideA = 0;
+    g.A = h->dft_fwd.as(); g.lda = h->Lp; g.strideA = 0;
     g.B = x + t_lo * h->d.frame_hop; g.ldb = h->d.frame_hop; g.strideB = x_stride;
     g.C = out + t_lo; g.ldc = row_ld; g.strideC = (int64_t)2 * F * row_ld;
     g.M = 2 * F; g.N = (int)(t_hi - t_lo); g.K = h->Lp; g.batch = C; g.alpha = 1.f;
@@ -479,31 +486,29 @@ int css_create(const CssModelDesc* desc, const float* blob_host, int64_t blob_fl
         if (hipStreamCreate(&h->stream) != hipSuccess) return bail(CSS_ERR_HIP, "hipStreamCreate failed");
         h->own_stream = true;
     }
-    for (auto& e : h->ev)
-        if (hipEventCreate(&e) != hipSuccess) return bail(CSS_ERR_HIP, "hipEventCreate failed");
+    for (Event& e : h->ev)
+        if (e.create() != hipSuccess) return bail(CSS_ERR_HIP, "hipEventCreate failed");
     // untimed events: the lanes' fork, and the overlap protocol of queued passes (api_queue.hip)
-    for (hipEvent_t* e : {&h->ev_fork, &h->tail_end, &h->pcm_free[0], &h->pcm_free[1], &h->level_free[0], &h->level_free[1],
-                          &h->pass_end[0], &h->pass_end[1], &h->pass_end[2], &h->pass_end[3]})
-        if (hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) return bail(CSS_ERR_HIP, "hipEventCreate failed");
+    for (Event* e : {&h->ev_fork, &h->tail_end, &h->pcm_free[0], &h->pcm_free[1], &h->level_free[0], &h->level_free[1],
+                     &h->pass_end[0], &h->pass_end[1], &h->pass_end[2], &h->pass_end[3]})
+        if (e->create(hipEventDisableTiming) != hipSuccess) return bail(CSS_ERR_HIP, "hipEventCreate failed");
     const bool dealt = deal_streams(h->stream, h->lane_stream, &h->copy_stream, &h->tail_stream);
     for (int l = 1; l < css_ctx::MAX_LANES; ++l)
         if ((!dealt && hipStreamCreateWithFlags(&h->lane_stream[l], hipStreamNonBlocking) != hipSuccess) ||
-            hipEventCreateWithFlags(&h->ev_join[l], hipEventDisableTiming) != hipSuccess)
+            h->ev_join[l].create(hipEventDisableTiming) != hipSuccess)
             return bail(CSS_ERR_HIP, "lane stream / event could not be created");
     if (!dealt && (hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking) != hipSuccess ||
                    hipStreamCreateWithFlags(&h->tail_stream, hipStreamNonBlocking) != hipSuccess))
         return bail(CSS_ERR_HIP, "copy / tail stream could not be created");
-    if (hipMalloc(&h->level.p, 64) != hipSuccess || hipMemset(h->level.p, 0, 64) != hipSuccess ||
-        hipMalloc((void**)&h->range_flag_dev, 64) != hipSuccess ||
-        hipHostMalloc((void**)&h->range_flag_host, 64, hipHostMallocDefault) != hipSuccess)
+    if (dev_alloc(h->level, 64) != hipSuccess || hipMemset(h->level.p, 0, 64) != hipSuccess ||
+        dev_alloc(h->range_flag_dev, 64) != hipSuccess || h->range_flag_host.alloc(64) != hipSuccess)
         return bail(CSS_ERR_HIP, "range flag could not be allocated");
-    *h->range_flag_host = 0;
-    h->level.cap = 64;
-    h->peak_dev = (unsigned int*)h->level.p;
-    if (hipMalloc((void**)&h->blob, need * sizeof(float)) != hipSuccess) return bail(CSS_ERR_HIP, "hipMalloc(weights) failed");
-    if (hipMemcpy(h->blob, blob_host, need * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+    *h->range_flag_host.as<unsigned int>() = 0;
+    h->peak_dev = h->level.as<unsigned int>();
+    if (dev_alloc(h->blob, need * sizeof(float)) != hipSuccess) return bail(CSS_ERR_HIP, "hipMalloc(weights) failed");
+    if (hipMemcpy(h->blob.p, blob_host, need * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
         return bail(CSS_ERR_HIP, "weight upload failed");
-    bind_weights(*desc, h->blob, &h->w);
+    bind_weights(*desc, h->blob.as(), &h->w);
     // transforms (feature.py:19-45): analysis = Hann-windowed 512-point FFT (stft.hip); synthesis = a GEMM with the
     // matrix sqrt-Hann * DFT / 16 (its output rows overlap-add, and its input is the stitched spectra in GEMM row format)
     // L window samples, NF FFT points (feature.py:27: frame_len rounded up to a power of two, or frame_len), F = NF / 2 + 1
@@ -524,14 +529,14 @@ int css_create(const CssModelDesc* desc, const float* blob_host, int64_t blob_fl
             inv[(size_t)n * KI + F + f] = (float)(0.0 - s * ws / S);
         }
     }
-    if (hipMalloc((void**)&h->stft_tab, tab.size() * sizeof(float)) != hipSuccess ||
-        hipMalloc((void**)&h->dft_inv_t, inv.size() * sizeof(float)) != hipSuccess)
+    if (dev_alloc(h->stft_tab, tab.size() * sizeof(float)) != hipSuccess ||
+        dev_alloc(h->dft_inv_t, inv.size() * sizeof(float)) != hipSuccess)
         return bail(CSS_ERR_HIP, "hipMalloc(transform tables) failed");
-    if (hipMemcpy(h->stft_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(h->dft_inv_t, inv.data(), inv.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+    if (hipMemcpy(h->stft_tab.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(h->dft_inv_t.p, inv.data(), inv.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
         return bail(CSS_ERR_HIP, "transform table upload failed");
     if (!h->fft512) {
-        if (hipMalloc((void**)&h->dft_fwd, (size_t)2 * F * h->Lp * sizeof(float)) != hipSuccess) return bail(CSS_ERR_HIP, "hipMalloc(analysis matrix) failed");
+        if (dev_alloc(h->dft_fwd, (size_t)2 * F * h->Lp * sizeof(float)) != hipSuccess) return bail(CSS_ERR_HIP, "hipMalloc(analysis matrix) failed");
         if (upload_analysis_matrix(h, CSS_WINDOW_HANN) != CSS_OK) return bail(CSS_ERR_HIP, "analysis matrix upload failed");
     }
     // a weight beyond the split-f16 operand range (never seen in a trained checkpoint; weights are O(1)): this model
@@ -542,7 +547,7 @@ int css_create(const CssModelDesc* desc, const float* blob_host, int64_t blob_fl
     // the handle starts in the reference's arithmetic (float32 operands); the split-f16 images of the weights are built by the
     // first css_set_linear_mode(h, CSS_LINEAR_SPLIT_F16)
     h->split = false;
-    if (make_frag_weights(h) != CSS_OK) { (void)hipGetLastError(); if (h->wfrag) { hipFree(h->wfrag); h->wfrag = nullptr; } }
+    if (make_frag_weights(h) != CSS_OK) { (void)hipGetLastError(); h->wfrag.reset(); }
     *out = h;
     return CSS_OK;
 }
@@ -553,49 +558,12 @@ int css_destroy(css_handle_t h) {
     if (h->stream) hipStreamSynchronize(h->stream);
     if (h->comm) css_comm_destroy(h);
     stream_destroy_all(h);
-    DevBuf* bufs[] = {&h->pcm_in, &h->pcm_cm, &h->X, &h->feat, &h->hx, &h->hu, &h->ht, &h->qkv, &h->qkf, &h->ctxb, &h->masks,
-                      &h->scm, &h->bfw, &h->sep, &h->costs, &h->perms, &h->mask_st, &h->activity, &h->act_b,
-                      &h->act_tmp, &h->act_final, &h->Y, &h->G, &h->wav, &h->wta, &h->pnorm, &h->segw, &h->stage, &h->pit_part,
-                      &h->in16, &h->pcm_f, &h->enc, &h->level, &h->mel_tab, &h->mel_work, &h->X_alt};
-    for (int l = 1; l < css_ctx::MAX_LANES; ++l) {
-        for (DevBuf* b : {&h->lfeat[l], &h->lhx[l], &h->lhu[l], &h->lht[l], &h->lqkv[l], &h->lqkf[l], &h->lctx[l]})
-            if (b->p) hipFree(b->p);
+    for (int l = 1; l < css_ctx::MAX_LANES; ++l)
         if (h->lane_stream[l]) { hipStreamSynchronize(h->lane_stream[l]); hipStreamDestroy(h->lane_stream[l]); }
-        if (h->ev_join[l]) hipEventDestroy(h->ev_join[l]);
-    }
-    for (DevBuf* b : bufs)
-        if (b->p) hipFree(b->p);
-    for (SessState& sl : h->slots)
-        for (DevBuf* b : {&sl.pcm_cm, &sl.X, &sl.scm, &sl.bfw, &sl.sep, &sl.costs, &sl.perms, &sl.mask_st, &sl.activity, &sl.act_b,
-                          &sl.act_tmp, &sl.act_final, &sl.Y, &sl.G, &sl.wav, &sl.wta, &sl.pnorm, &sl.pit_part, &sl.X_alt})
-            if (b->p) hipFree(b->p);
-    if (h->blob) hipFree(h->blob);
-    if (h->ev_fork) hipEventDestroy(h->ev_fork);
-    if (h->tail_end) hipEventDestroy(h->tail_end);
-    for (auto& e : h->pcm_free) if (e) hipEventDestroy(e);
-    for (auto& e : h->level_free) if (e) hipEventDestroy(e);
-    for (auto& e : h->pass_end) if (e) hipEventDestroy(e);
     if (h->copy_stream) { hipStreamSynchronize(h->copy_stream); hipStreamDestroy(h->copy_stream); }
     if (h->tail_stream) { hipStreamSynchronize(h->tail_stream); hipStreamDestroy(h->tail_stream); }
-    if (h->range_flag_dev) hipFree(h->range_flag_dev);
-    if (h->range_flag_host) hipHostFree(h->range_flag_host);
-    for (auto& e : h->ev_pool) hipEventDestroy(e);
-    for (auto& e : h->sess_ev_pool) hipEventDestroy(e);
-    if (h->wsplit) hipFree(h->wsplit);
-    if (h->wfrag) hipFree(h->wfrag);
-    if (h->dft_split) hipFree(h->dft_split);
-    if (h->dft_tiled) hipFree(h->dft_tiled);
-    if (h->head_tiled) hipFree(h->head_tiled);
-    for (auto& b : h->pe_frag)
-        if (b.p) hipFree(b.p);
-    if (h->stft_tab) hipFree(h->stft_tab);
-    if (h->dft_fwd) hipFree(h->dft_fwd);
-    if (h->dft_inv_t) hipFree(h->dft_inv_t);
-    for (auto& e : h->ev)
-        if (e) hipEventDestroy(e);
-    for (auto& pr : h->prof_events) { hipEventDestroy(pr.a); hipEventDestroy(pr.b); }
     if (h->own_stream && h->stream) hipStreamDestroy(h->stream);
-    delete h;
+    delete h;   // buffers and events are members: they go with it
     return CSS_OK;
 }
 
@@ -705,9 +673,9 @@ int css_check_range(css_handle_t h) {
     int rc = check_session(h);
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipMemcpyAsync(h->range_flag_host, h->range_flag_dev, sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->range_flag_host.p, h->range_flag_dev.p, sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (*h->range_flag_host && h->split)
+    if (*h->range_flag_host.as<unsigned int>() && h->split)
         return fail(h, CSS_ERR_RANGE, "an operand of a Linear layer left the split-f16 range (|x| > 65504): use CSS_LINEAR_EXACT_F32");
     return CSS_OK;
 }
@@ -875,7 +843,7 @@ int css_set_linear_mode(css_handle_t h, int mode) {
         if (rc) return rc;
     } else if (make_frag_weights(h) != CSS_OK) {
         (void)hipGetLastError();   // (no room for the second image: the float32 kernel takes the row-major weights through LDS)
-        if (h->wfrag) { hipFree(h->wfrag); h->wfrag = nullptr; }
+        h->wfrag.reset();
     }
     // the feature rows change format; their K padding must read as zero in either
     if (h->feat.p) HIPCHK(h, hipMemsetAsync(h->feat.p, 0, h->feat.cap, h->stream));
@@ -920,7 +888,7 @@ int css_set_analysis_window(css_handle_t h, int32_t window) {
     std::vector<float> tab(stft_table_floats());
     stft_build_tables(tab.data(), window);
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipMemcpy(h->stft_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(h->stft_tab.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
     if (!h->fft512 && upload_analysis_matrix(h, window) != CSS_OK) return fail(h, CSS_ERR_HIP, "analysis matrix upload failed");
     return CSS_OK;
 }
@@ -938,9 +906,9 @@ int css_set_profile(css_handle_t h, int enable) {
         // calibration: 64 empty brackets behind a kernel each (the bracket's cost depends on the stream being busy)
         HIPCHK(h, hipSetDevice(h->device));
         constexpr int NP = 64;
-        hipEvent_t ev[2 * NP];
-        for (auto& e : ev) HIPCHK(h, hipEventCreate(&e));
-        unsigned int* scratch = h->range_flag_dev + 8;   // (a word of the 64-byte allocation nobody reads)
+        Event ev[2 * NP];
+        for (Event& e : ev) HIPCHK(h, e.create());
+        unsigned int* scratch = h->range_flag_dev.as<unsigned int>() + 8;   // (a word of the 64-byte allocation nobody reads)
         for (int i = 0; i < NP; ++i) {
             HIPCHK(h, hipMemsetAsync(scratch, 0, 4, h->stream));
             HIPCHK(h, hipEventRecord(ev[2 * i], h->stream));
@@ -949,7 +917,6 @@ int css_set_profile(css_handle_t h, int enable) {
         HIPCHK(h, hipStreamSynchronize(h->stream));
         float tot = 0.f;
         for (int i = 0; i < NP; ++i) { float v = 0.f; hipEventElapsedTime(&v, ev[2 * i], ev[2 * i + 1]); tot += v; }
-        for (auto& e : ev) hipEventDestroy(e);
         h->prof_pair_ms = tot;
         h->prof_pairs = NP;
     }

@@ -1,9 +1,10 @@
-// Internal header of libcss_mi355.so's host side (round 6: api.hip split into three units).  The C ABI is include/css_mi355.h;
+// Internal header of libcss_mi355.so's host side (the api_*.hip units).  The C ABI is include/css_mi355.h;
 // nothing here is exported on purpose.  css_ctx is the handle: the model, its streams and workspaces, and -- through SessState --
 // the session the stage entry points see.
-//   api_core.hip    handle life cycle (css_create / css_destroy), weights, setters, timings, buffers, the RCCL communicator
-//   api_stages.hip  one stage per reference function (css_begin .. css_stage_*), the mask estimator's lanes, the separator protocol
-//   api_queue.hip   the fused pass (css_run*), the queue of sessions (css_run_enqueue* / css_wait*), shared estimator batches
+// Four owners hold what the library keeps on the GPU: DevBuf (device memory), PinnedBuf (page-locked host memory), Event (a
+// hipEvent_t) and std::unique_ptr (a stream's optional parts, api_stream.hip).  The rule is "members, not lists": a resource is a
+// member of the handle, of a stream or of one call's stack and is released with it; no function enumerates what to free.
+// HIP streams stay explicit (css_destroy): the handle's own may be the caller's, and the order of synchronise and destroy matters.
 #pragma once
 #include "../../include/css_mi355.h"
 
@@ -14,7 +15,10 @@
 #include <cstring>
 #include <chrono>
 #include <functional>
+#include <memory>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include <dlfcn.h>
@@ -38,10 +42,56 @@ static const char* const kProfNames[CSS_PROF_COUNT] = {
 
 thread_local extern std::string g_create_error;   // css_last_error(NULL): why the last css_create of this thread failed
 
-struct DevBuf {
+// ---- the owners (see the top of this file).  Move-only, a moved-from owner is empty; none has static or thread storage
+// duration: the HIP runtime may be gone when such destructors run.
+struct DevBuf {   // device memory (allocated by ensure / dev_alloc, api_core.hip)
     void* p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { reset(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; } return *this; }
+    ~DevBuf() { reset(); }
+    hipError_t reset() { const hipError_t e = p ? hipFree(p) : hipSuccess; p = nullptr; cap = 0; return e; }
+    template <class T = float> T* as() const { return static_cast<T*>(p); }
 };
+
+struct PinnedBuf {   // page-locked host memory
+    void* p = nullptr;
+    size_t cap = 0;
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf&) = delete;
+    PinnedBuf& operator=(const PinnedBuf&) = delete;
+    PinnedBuf(PinnedBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    PinnedBuf& operator=(PinnedBuf&& o) noexcept { if (this != &o) { reset(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; } return *this; }
+    ~PinnedBuf() { reset(); }
+    hipError_t reset() { const hipError_t e = p ? hipHostFree(p) : hipSuccess; p = nullptr; cap = 0; return e; }
+    hipError_t alloc(size_t bytes) {   // (what it held is released first)
+        hipError_t e = reset();
+        if (e == hipSuccess) e = hipHostMalloc(&p, bytes, hipHostMallocDefault);
+        if (e == hipSuccess) cap = bytes;
+        return e;
+    }
+    template <class T> T* as() const { return static_cast<T*>(p); }
+};
+
+struct Event {   // a hipEvent_t; passes as one wherever an event is recorded, waited for or timed
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(const Event&) = delete;
+    Event& operator=(const Event&) = delete;
+    Event(Event&& o) noexcept : e(o.e) { o.e = nullptr; }
+    Event& operator=(Event&& o) noexcept { if (this != &o) { reset(); e = o.e; o.e = nullptr; } return *this; }
+    ~Event() { reset(); }
+    void reset() { if (e) hipEventDestroy(e); e = nullptr; }
+    hipError_t create(unsigned flags = hipEventDefault) { reset(); return hipEventCreateWithFlags(&e, flags); }
+    hipEvent_t get() const { return e; }
+    operator hipEvent_t() const { return e; }
+};
+static_assert(!std::is_copy_constructible<DevBuf>::value && !std::is_copy_constructible<PinnedBuf>::value && !std::is_copy_constructible<Event>::value &&
+              std::is_nothrow_move_constructible<DevBuf>::value && std::is_nothrow_move_constructible<PinnedBuf>::value &&
+              std::is_nothrow_move_constructible<Event>::value, "the owners are move-only");
 
 struct BlockWeights {
     const float *ffi_ln_w, *ffi_ln_b, *ffi_w1, *ffi_b1, *ffi_w2, *ffi_b2;
@@ -123,25 +173,25 @@ struct css_ctx : SessState {
     bool own_stream = false;
     int max_batch = 64;
     int Kp = 0, KIp = 0;
-    float* blob = nullptr;
+    DevBuf blob;                 // the weights as uploaded (w points into it)
     Weights w;
     // Linear-layer arithmetic.  Default (round 6): float32 operands on the float32 matrix instruction (gemm_f32.hip) -- the
     // reference's own operand precision (conformer.py:137-150 runs torch.nn.Linear in float32).  Opt-in, after
     // css_set_linear_mode(h, CSS_LINEAR_SPLIT_F16): split-f16 operands on the f16 matrix cores (22-bit operands, gemm_split*.hip).
     bool split = false;
     bool split_ok = true;        // false: a weight lies outside the split-f16 operand range, CSS_LINEAR_SPLIT_F16 is refused
-    float* wsplit = nullptr;     // split-f16 images of the Linear weights, at the blob's own offsets
-    float* dft_split = nullptr;  // split-f16 image of dft_inv_t (row-major)
-    float* wfrag = nullptr;      // exact float32 mode: the Linear weights in gemm_f32.hip's fragment order (same offsets as blob)
-    float* dft_tiled = nullptr;  // ... and in the tile-major layout of the weights-direct GEMM (whole-meeting synthesis)
-    float* head_tiled = nullptr; // the mask head's weights in that layout (rows rounded up to 32; wsplit keeps the row-major image)
+    DevBuf wsplit;               // split-f16 images of the Linear weights, at the blob's own offsets
+    DevBuf dft_split;            // split-f16 image of dft_inv_t (row-major)
+    DevBuf wfrag;                // exact float32 mode: the Linear weights in gemm_f32.hip's fragment order (same offsets as blob)
+    DevBuf dft_tiled;            // ... and in the tile-major layout of the weights-direct GEMM (whole-meeting synthesis)
+    DevBuf head_tiled;           // the mask head's weights in that layout (rows rounded up to 32; wsplit keeps the row-major image)
     DevBuf pe_frag[2];           // relative-position rows in attention-operand order for segment length pe_frag_T
     int pe_frag_T[2] = {0, 0};   // ([0] from the float32 table, [1] from the split-f16 one; encoder.hip pe_fragments_kernel)
-    float* stft_tab = nullptr;   // window and twiddles of the analysis FFT (stft.hip)
+    DevBuf stft_tab;             // window and twiddles of the analysis FFT (stft.hip)
     bool fft512 = true;          // frame_len 512 / hop 256 / 257 bins: the FFT kernel and the pipelined schedules; else the generic forms
-    float* dft_fwd = nullptr;    // generic analysis: [2F][Lp] = (cos | -sin)(2 pi f n / N) * window[n], n < frame_len (zero beyond)
+    DevBuf dft_fwd;              // generic analysis: [2F][Lp] = (cos | -sin)(2 pi f n / N) * window[n], n < frame_len (zero beyond)
     int Lp = 0, ovl = 2;         // frame_len rounded up to 32; frames over an output sample = ceil(frame_len / hop)
-    float* dft_inv_t = nullptr;  // [frame_len][KIp]
+    DevBuf dft_inv_t;            // [frame_len][KIp]
 
     // shared by the sessions of a handle: upload staging, the estimator's activations, the mask buffer, small tables
     std::vector<float> w_on_device;   // what segw holds (uploaded when a session's windows differ)
@@ -159,14 +209,14 @@ struct css_ctx : SessState {
     static constexpr int MAX_LANES = 4;
     int lanes = 3;
     hipStream_t lane_stream[MAX_LANES] = {};   // [0] unused
-    hipEvent_t ev_fork = nullptr, ev_join[MAX_LANES] = {};
+    Event ev_fork, ev_join[MAX_LANES];
     DevBuf lfeat[MAX_LANES], lhx[MAX_LANES], lhu[MAX_LANES], lht[MAX_LANES], lqkv[MAX_LANES], lqkf[MAX_LANES], lctx[MAX_LANES];   // [0] unused
     int64_t last_batch_tokens = 0;
     int mel_bands = 0;                    // the filterbank mel_tab holds (0: none yet)
     // range check of the split-f16 operand format (split_f16.hpp): a device word set when the stitched activity or the
     // waveforms hold a non-finite value, mirrored into page-locked host memory at the end of every pass
-    unsigned int* range_flag_dev = nullptr;
-    unsigned int* range_flag_host = nullptr;
+    DevBuf range_flag_dev;           // (64 bytes; word 0 is the flag)
+    PinnedBuf range_flag_host;
     bool range_fallback = true;      // repeat such a pass on the exact float32 kernels (else: CSS_ERR_RANGE)
     int64_t range_fallbacks = 0;     // passes repeated so far
     int range_last = 0;              // the last pass hit the range limit
@@ -189,10 +239,10 @@ struct css_ctx : SessState {
     // the last transform of the pass that used sample buffer b; `tail_end` = the end of the last queued pass's tail
     // (untimed events, created with the handle)
     int64_t pass_no = 0;
-    hipEvent_t pcm_free[2] = {nullptr, nullptr};
-    hipEvent_t pass_end[4] = {nullptr, nullptr, nullptr, nullptr};   // ends of the last four queued passes (back-pressure)
-    hipEvent_t level_free[2] = {nullptr, nullptr};   // end of the tail of the pass that used level word b (its last reader)
-    hipEvent_t tail_end = nullptr;
+    Event pcm_free[2];
+    Event pass_end[4];     // ends of the last four queued passes (back-pressure)
+    Event level_free[2];   // end of the tail of the pass that used level word b (its last reader)
+    Event tail_end;
     bool tail_pending = false;
     bool piped_now = false;   // run_once -> begin_impl: the level word is cleared on the copy stream, not here
     int last_piped = -1;      // overlap mode of the last queued pass (-1: nothing queued): a queue never mixes modes un-drained
@@ -243,7 +293,7 @@ struct css_ctx : SessState {
     // css_wait_sessions: one event per session put on the streams since the last css_wait, in queue order, recorded behind the
     // session's last output copy (nullptr: the session had finished inside its call)
     std::vector<hipEvent_t> sess_done;
-    std::vector<hipEvent_t> sess_ev_pool;
+    std::vector<Event> sess_ev_pool;
     size_t sess_ev_used = 0;
     void* comm = nullptr;          // ncclComm_t of css_comm_init (RCCL, loaded lazily)
     int comm_ranks = 0, comm_rank = -1;
@@ -251,16 +301,16 @@ struct css_ctx : SessState {
     // the handle's stream wait for exactly the pieces its frames read
     struct PendingUpload { int64_t s_lo, s_hi; hipEvent_t landed; };
     std::vector<PendingUpload> uploads;
-    std::vector<hipEvent_t> ev_pool;   // untimed events of the pipeline (uploads landed, planes ready, ranges finished)
+    std::vector<Event> ev_pool;   // untimed events of the pipeline (uploads landed, planes ready, ranges finished)
     size_t ev_pool_used = 0;
 
     // timing
-    hipEvent_t ev[10]{};
+    Event ev[10];
     CssTimings tim{};
     // css_set_profile: every kernel launch of a pass is bracketed by a pair of HIP events on its stream (one lane, so
     // that the pairs are ordered); durations are summed per kernel family (css_get_kernel_stats)
     bool profile_gemm = false;
-    struct ProfEvent { hipEvent_t a, b; int cat; };
+    struct ProfEvent { Event a, b; int cat = 0; };
     std::vector<ProfEvent> prof_events;
     size_t prof_used = 0;
     size_t prof_reduced = 0;   // brackets already summed into prof_ms (a staged session has no closing call that does it)
@@ -290,6 +340,7 @@ struct css_ctx : SessState {
 
 // ---- api_core.hip
 int fail(css_ctx* h, int code, const std::string& msg);
+hipError_t dev_alloc(DevBuf& b, size_t bytes);
 int ensure(css_ctx* h, DevBuf& b, size_t bytes, bool zero = false);
 int64_t bind_weights(const CssModelDesc& d, const float* base, Weights* w);
 const char* validate_desc(const CssModelDesc& d);
@@ -379,10 +430,10 @@ struct Prof {
     Prof(css_ctx* h_, int cat, hipStream_t st_) : h(h_), st(st_) {
         if (!h->profile_gemm) return;
         if (h->prof_used == h->prof_events.size()) {
-            css_ctx::ProfEvent e{};
-            hipEventCreate(&e.a);
-            hipEventCreate(&e.b);
-            h->prof_events.push_back(e);
+            css_ctx::ProfEvent e;
+            e.a.create();
+            e.b.create();
+            h->prof_events.push_back(std::move(e));
         }
         css_ctx::ProfEvent& e = h->prof_events[h->prof_used++];
         e.cat = cat;

@@ -202,7 +202,7 @@ int css_attention_host(css_handle_t h, const CssAttentionDesc* d, const float* x
         launch_split_convert(xd, K, xs, M, K, K, st);
         launch_split_convert_tiled(wd, K, wc, N, K, st);
         g.A = xs; g.B = wc; g.split_in = 1; g.b_tiled = 1; g.split_out = N;
-        g.range_flag = h->range_flag_dev;
+        g.range_flag = h->range_flag_dev.as<unsigned int>();
         g.frag_out = qkf; g.frag_D = D; g.frag_T = T; g.frag_heads = H; g.frag_invT = 1.0f / T;
     } else {
         launch_f32_fragments(wd, K, wc, N, K, st);

@@ -12,9 +12,8 @@ void* mapped_host(const void* p) {
 // the completion event of the session whose last output copy was just enqueued on `st` (css_wait_sessions)
 void mark_session_done(css_ctx* h, hipStream_t st) {
     if (h->sess_ev_used == h->sess_ev_pool.size()) {
-        hipEvent_t e = nullptr;
-        hipEventCreateWithFlags(&e, hipEventDisableTiming);
-        h->sess_ev_pool.push_back(e);
+        h->sess_ev_pool.emplace_back();
+        h->sess_ev_pool.back().create(hipEventDisableTiming);
     }
     hipEvent_t e = h->sess_ev_pool[h->sess_ev_used++];
     hipEventRecord(e, st);
@@ -23,9 +22,8 @@ void mark_session_done(css_ctx* h, hipStream_t st) {
 
 hipEvent_t pool_event(css_ctx* h) {
     if (h->ev_pool_used == h->ev_pool.size()) {
-        hipEvent_t e = nullptr;
-        hipEventCreateWithFlags(&e, hipEventDisableTiming);
-        h->ev_pool.push_back(e);
+        h->ev_pool.emplace_back();
+        h->ev_pool.back().create(hipEventDisableTiming);
     }
     return h->ev_pool[h->ev_pool_used++];
 }
@@ -203,7 +201,7 @@ static int run_plain(css_ctx* h, int64_t n, int32_t n_ch, const RunIo& io, HostC
     if ((rc = istft_impl(h, 0, TL, 0, TL - 1 + h->ovl, dst, dst_ld, 0, h->stream)) != CSS_OK) return rc;
     if (io.wav16_host && (rc = encode_pcm16_out(h, dst, io.wav16_host, io.cap, io.peaks_host, h->stream)) != CSS_OK) return rc;
     if (io.wav_host && (rc = waveforms_out(h, dst, dst_ld, io.wav_host, io.cap, 0, pl.n_out, h->stream)) != CSS_OK) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->range_flag_host, h->range_flag_dev, sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->range_flag_host.p, h->range_flag_dev.p, sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
     hipEventRecord(h->ev[7], h->stream);
     return sync_and_time(h, t0, true);
 }
@@ -421,7 +419,7 @@ static int run_pipeline(css_ctx* h, int64_t n, int32_t n_ch, const RunIo& io, bo
     for (int64_t s0 = 0; s0 < nseg; s0 += cap) {
         first = ui;
         if ((rc = masknet_batch(h, mio, s0, (int)std::min<int64_t>(cap, nseg - s0), prep, post,
-                                (piped && h->tail_pending && s0 == 0) ? h->tail_end : nullptr)) != CSS_OK) return rc;
+                                (piped && h->tail_pending && s0 == 0) ? h->tail_end.get() : nullptr)) != CSS_OK) return rc;
         if (h->tune[CSS_TUNE_TAIL_PER_UNIT]) {
             for (size_t k = first; k < ui; ++k)
                 if ((rc = tails.batch(k, k + 1)) != CSS_OK) return rc;
@@ -444,7 +442,7 @@ static int run_pipeline(css_ctx* h, int64_t n, int32_t n_ch, const RunIo& io, bo
     HIPCHK(h, hipStreamWaitEvent(h->stream, tail_done, 0));
     if (io.wav16_host && (rc = encode_pcm16_out(h, (const float*)h->wav.p, io.wav16_host, io.cap, io.peaks_host, h->stream)) != CSS_OK) return rc;
     // range check (split_f16.hpp): a split GEMM whose operand left the format's range raised this word
-    HIPCHK(h, hipMemcpyAsync(h->range_flag_host, h->range_flag_dev, sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->range_flag_host.p, h->range_flag_dev.p, sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
     if (tails.out_done) HIPCHK(h, hipStreamWaitEvent(h->stream, tails.out_done, 0));
     hipEventRecord(h->ev[7], h->stream);
     if (io.enqueue_only) {   // css_wait synchronises, reads the range word and the timings of the last queued pass
@@ -630,7 +628,7 @@ int run_group(css_handle_t h, const std::vector<css_ctx::QueuedSession>& grp) {
     // the mask buffer that tail reads)
     MaskIo io{nullptr, 0, 0, hop, T, (float*)h->masks.p, total * T, &gs};
     const LanePrep none = [](int64_t, int, hipStream_t) { return (int)CSS_OK; };
-    if ((rc = masknet_batch(h, io, 0, (int)total, none, none, h->tail_pending ? h->tail_end : nullptr)) != CSS_OK) return rc;
+    if ((rc = masknet_batch(h, io, 0, (int)total, none, none, h->tail_pending ? h->tail_end.get() : nullptr)) != CSS_OK) return rc;
     hipEventRecord(h->ev[3], h->stream);
     hipEvent_t masks_ready = pool_event(h);
     HIPCHK(h, hipEventRecord(masks_ready, h->stream));
@@ -759,7 +757,7 @@ int run_impl(css_handle_t h, int64_t n, int32_t n_ch, const CssRunCfg* cfg, cons
     rc = run_once(h, n, n_ch, cfg, io);
     if (rc != CSS_OK) return rc;
     h->range_last = 0;
-    if (!*h->range_flag_host || !h->split) return CSS_OK;
+    if (!*h->range_flag_host.as<unsigned int>() || !h->split) return CSS_OK;
     h->range_last = 1;
     if (!h->range_fallback)
         return fail(h, CSS_ERR_RANGE, "an operand of a Linear layer left the split-f16 range (|x| > 65504): use CSS_LINEAR_EXACT_F32");
@@ -852,7 +850,7 @@ int css_wait(css_handle_t h) {
     HIPCHK(h, hipSetDevice(h->device));
     const auto t0 = std::chrono::steady_clock::now();
     if (int rc = drain_streams(h)) return rc;
-    HIPCHK(h, hipMemcpy(h->range_flag_host, h->range_flag_dev, sizeof(unsigned int), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(h->range_flag_host.p, h->range_flag_dev.p, sizeof(unsigned int), hipMemcpyDeviceToHost));
     HIPCHK(h, hipGetLastError());
     const auto t1 = std::chrono::steady_clock::now();
     h->queued = 0;
@@ -865,7 +863,7 @@ int css_wait(css_handle_t h) {
     h->range_last = 0;
     std::vector<css_ctx::QueuedSession> log;
     log.swap(h->queue_log);
-    if (*h->range_flag_host && h->split) {
+    if (*h->range_flag_host.as<unsigned int>() && h->split) {
         // the same rule as css_run: the queued passes accumulate into one range word, so every pass queued since the last
         // css_wait is repeated, one by one, on the exact float32 kernels (their inputs are still the caller's to keep)
         h->range_last = 1;

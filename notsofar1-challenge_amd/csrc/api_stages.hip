@@ -59,7 +59,7 @@ int begin_impl(css_handle_t h, int64_t n_samples, int32_t n_ch, const CssRunCfg*
     if ((rc = ensure(h, h->buf, (size_t)(bytes), ##__VA_ARGS__)) != CSS_OK) return rc;
     hipEventRecord(h->ev[0], h->stream);
     if (!h->piped_now) HIPCHK(h, hipMemsetAsync(h->peak_dev, 0, sizeof(unsigned int), h->stream));
-    if (!h->queued) HIPCHK(h, hipMemsetAsync(h->range_flag_dev, 0, sizeof(unsigned int), h->stream));   // queued passes accumulate
+    if (!h->queued) HIPCHK(h, hipMemsetAsync(h->range_flag_dev.p, 0, sizeof(unsigned int), h->stream));   // queued passes accumulate
     ENS(pcm_cm, (size_t)n_ch * h->n_pad * sizeof(float))
     ENS(X, (size_t)n_ch * X_ROWS_PER_BIN * F * h->T_ld * sizeof(float))
     h->ph_valid = false;
@@ -241,18 +241,18 @@ int masknet_lane(css_ctx* h, const MaskIo& io, int64_t s0, int nb, int lane, int
     // Linear layers: split-f16 operands (h->split) -- every producer of a GEMM input writes the split format
     // directly (features, LayerNorm, the FFN's first GEMM, attention), the residual stream x stays float32.
     const int sp = h->split ? 1 : 0;
-    auto WS = [&](const float* w) { return sp ? h->wsplit + (w - h->blob) : w; };
+    auto WS = [&](const float* w) { return sp ? h->wsplit.as() + (w - h->blob.as()) : w; };
     // exact float32: the weights in fragment order for gemm_f32.hip (CSS_TUNE_F32_GEMM 0 and 2..5; 1 = round 4's kernel and
     // 6 = gemm_f32.hip with both operands through LDS read the row-major weights) -- same bits either way
     const int f32_tune = h->tune[CSS_TUNE_F32_GEMM];
-    const bool frag = !sp && h->wfrag && f32_tune != 1 && f32_tune != 6 && (int64_t)M * std::max(h->Kp, FF) * 4 < ((int64_t)1 << 30);
+    const bool frag = !sp && h->wfrag.p && f32_tune != 1 && f32_tune != 6 && (int64_t)M * std::max(h->Kp, FF) * 4 < ((int64_t)1 << 30);
     auto lin = [&](const float* A, int64_t lda, const float* Wt, const float* bias, float* C, int64_t ldc, int n, int k,
                    int act, int split_out) {
-        GemmArgs g = linear(A, lda, frag ? h->wfrag + (Wt - h->blob) : WS(Wt), lda, bias, C, ldc, M, n, k, act);
+        GemmArgs g = linear(A, lda, frag ? h->wfrag.as() + (Wt - h->blob.as()) : WS(Wt), lda, bias, C, ldc, M, n, k, act);
         g.split_in = sp; g.split_out = sp ? split_out : 0; g.b_tiled = sp; g.concurrent = concurrent ? 1 : 0;
         g.b_frag32 = frag ? 1 : 0;
         g.B_rows = frag ? Wt : nullptr;   // (the row-major weight, should gemm_f32.hip decline the launch: launch_gemm)
-        g.range_flag = sp ? h->range_flag_dev : nullptr;
+        g.range_flag = sp ? h->range_flag_dev.as<unsigned int>() : nullptr;
         return g;
     };
     if (ph_lo < 0) {
@@ -346,12 +346,12 @@ int masknet_lane(css_ctx* h, const MaskIo& io, int64_t s0, int nb, int lane, int
         // (kernel trace, A/B on one box: 87 us per 60 segments against 101 us for the LDS-staged kernel with the weights as
         // its A operand; the step itself did not move measurably, 4.903 vs 4.907 ms)
         g.A = u; g.lda = D; g.strideA = 0;
-        g.B = h->head_tiled; g.ldb = D; g.strideB = 0; g.b_tiled = 1;
+        g.B = h->head_tiled.as(); g.ldb = D; g.strideB = 0; g.b_tiled = 1;
         g.C = io.masks + s0 * T; g.ldc = io.mask_ld; g.strideC = 0; g.c_transposed = 1;
         g.M = M; g.N = nout; g.K = D; g.batch = 1;
         g.bias = W.head_b; g.bias_along_m = 0; g.act = ACT_SIGMOID; g.residual = nullptr; g.alpha = 1.f;
         g.split_in = 1; g.concurrent = concurrent ? 1 : 0;
-        g.range_flag = h->range_flag_dev;
+        g.range_flag = h->range_flag_dev.as<unsigned int>();
     } else {
         g.A = WS(W.head_w); g.lda = D; g.strideA = 0;
         g.B = sp ? u : x; g.ldb = D; g.strideB = 0;
@@ -359,7 +359,7 @@ int masknet_lane(css_ctx* h, const MaskIo& io, int64_t s0, int nb, int lane, int
         g.M = nout; g.N = M; g.K = D; g.batch = 1;
         g.bias = W.head_b; g.bias_along_m = 1; g.act = ACT_SIGMOID; g.residual = nullptr; g.alpha = 1.f;
         g.split_in = sp;
-        g.range_flag = sp ? h->range_flag_dev : nullptr;
+        g.range_flag = sp ? h->range_flag_dev.as<unsigned int>() : nullptr;
         // (the tokens are the large operand here: 17 row tiles of weights against hundreds of token panels; walked row panel by
         // row panel every XCD streamed all tokens twice -- 376 MB fetched per launch of 120 segments against 48 MB of operands;
         // kernel trace, A/B on one box: 107.8 -> 101.0 us at 60 segments per lane, 161.7 -> 137.6 us at 120)
@@ -398,7 +398,7 @@ int masknet_batch(css_ctx* h, const MaskIo& io, int64_t s0, int nb, const LanePr
     const bool long_seg = io.T > 512 || css_force_long_path();   // (the any-length attention reads the position table itself)
     if (!long_seg && h->pe_frag_T[sp] != io.T) {   // the attention kernel's position operands depend on the segment length only
         if ((rc = ensure(h, h->pe_frag[sp], (size_t)pe_fragment_tiles(io.T) * 2048 * sizeof(float))) != CSS_OK) return rc;
-        launch_pe_fragments(sp ? h->wsplit + (h->w.pe_k - h->blob) : h->w.pe_k, (float*)h->pe_frag[sp].p, io.T, h->d.maxlen,
+        launch_pe_fragments(sp ? h->wsplit.as() + (h->w.pe_k - h->blob.as()) : h->w.pe_k, (float*)h->pe_frag[sp].p, io.T, h->d.maxlen,
                             sp, h->stream);
         h->pe_frag_T[sp] = io.T;
     }
@@ -570,9 +570,9 @@ void istft_gemm_on(css_ctx* h, int64_t f_lo, int64_t f_hi, hipStream_t st) {
     const int64_t TL = h->plan.mix_frames;
     GemmArgs g{};
     g.split_in = h->split ? 1 : 0;   // Y rows were written as split operands by the stitch stage
-    g.range_flag = h->split ? h->range_flag_dev : nullptr;
+    g.range_flag = h->split ? h->range_flag_dev.as<unsigned int>() : nullptr;
     g.A = (const float*)h->Y.p + f_lo * h->KIp; g.lda = h->KIp; g.strideA = TL * h->KIp;
-    g.B = h->split ? h->dft_split : h->dft_inv_t; g.ldb = h->KIp; g.strideB = 0;
+    g.B = h->split ? h->dft_split.as() : h->dft_inv_t.as(); g.ldb = h->KIp; g.strideB = 0;
     g.C = (float*)h->G.p + f_lo * N; g.ldc = N; g.strideC = TL * N;
     g.M = (int)(f_hi - f_lo); g.N = N; g.K = h->KIp; g.batch = S;
     g.bias = nullptr; g.act = ACT_NONE; g.residual = nullptr; g.alpha = 1.f;
@@ -583,7 +583,7 @@ void istft_gemm_on(css_ctx* h, int64_t f_lo, int64_t f_hi, hipStream_t st) {
     // A/B on one box, interleaved: 35 vs 43 us per 60 s meeting)
     if (h->split && f_lo == 0 && f_hi == TL && N % 32 == 0 && (int64_t)S * TL < (int64_t)1 << 31) {
         g.M = (int)(S * TL); g.batch = 1; g.strideA = 0; g.strideC = 0;
-        g.B = h->dft_tiled; g.b_tiled = 1;
+        g.B = h->dft_tiled.as(); g.b_tiled = 1;
     }
     CSS_PROF(CSS_PROF_ISTFT_GEMM, st);
     launch_gemm(g, st);
@@ -967,7 +967,7 @@ int css_istft_host(css_handle_t h, const float* y_planes, int32_t batch, int64_t
     launch_planes_to_rows(in, rows, batch, 2 * F, t_frames, KI, h->stream);
     GemmArgs g{};
     g.A = rows; g.lda = KI; g.strideA = t_frames * KI;
-    g.B = h->dft_inv_t; g.ldb = KI; g.strideB = 0;
+    g.B = h->dft_inv_t.as(); g.ldb = KI; g.strideB = 0;
     g.C = G; g.ldc = N; g.strideC = t_frames * N;
     g.M = (int)t_frames; g.N = N; g.K = KI; g.batch = batch;
     g.alpha = 1.f;

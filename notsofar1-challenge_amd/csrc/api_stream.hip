@@ -68,8 +68,7 @@ struct HandoffStream {
 struct HandoffCtx {
     DevBuf tab, operand, spec, res, state;   // DFT matrix + both filterbanks; frame operand; spectra; a round's results; HandoffState per (id, k)
     DevBuf state_pv;                         // a preview's closing round writes its counts and maximum here, never into `state`
-    struct Pinned { void* p = nullptr; size_t cap = 0; };
-    std::vector<Pinned> pinned;              // staging of round r of a call
+    std::vector<PinnedBuf> pinned;           // staging of round r of a call
     int32_t launches = 0, products = 0;
     int64_t frames = 0;
 };
@@ -89,8 +88,8 @@ struct RateStream {
 };
 
 struct StreamState {
-    HandoffStream* ho = nullptr;
-    RateStream* rate = nullptr;
+    std::unique_ptr<HandoffStream> ho;
+    std::unique_ptr<RateStream> rate;
     CssRunCfg cfg{};
     std::vector<float> w;          // the three windows (cfg.w_* point here)
     int n_ch = 0, T = 0, hop = 0, halo = 0;
@@ -120,36 +119,21 @@ int64_t final_frames(int64_t n, int T, int hop, int halo) {
     return std::max<int64_t>(segments_done(frames_of(n), T, hop) * hop - halo, 0);
 }
 
-void free_stream(StreamState* s) {
+// every device buffer of a stream, its hand-off and its rate conversion (css_stream_info: what the stream holds on the device)
+template <class Fn>
+void for_each_buffer(const StreamState* s, Fn fn) {
     for (int b = 0; b < 2; ++b)
-        for (DevBuf* d : {&s->pcm[b], &s->X[b], &s->masks[b], &s->sep[b], &s->perms[b], &s->act_b[b], &s->G[b]})
-            if (d->p) hipFree(d->p);
-    for (DevBuf* d : {&s->scm, &s->bfw, &s->pnorm, &s->costs, &s->pit_part, &s->Y, &s->out, &s->segw, &s->pcm16_stage})
-        if (d->p) hipFree(d->p);
-    if (s->ho) {
-        for (DevBuf* d : {&s->ho->gate, &s->ho->carry[0], &s->ho->carry[1], &s->ho->tail[0], &s->ho->tail[1]})
-            if (d->p) hipFree(d->p);
-        delete s->ho;
-    }
-    if (s->rate) {
-        for (DevBuf* d : {&s->rate->stage, &s->rate->hist[0], &s->rate->hist[1], &s->rate->tab})
-            if (d->p) hipFree(d->p);
-        delete s->rate;
-    }
-    delete s;
+        for (const DevBuf* d : {&s->pcm[b], &s->X[b], &s->masks[b], &s->sep[b], &s->perms[b], &s->act_b[b], &s->G[b]}) fn(*d);
+    for (const DevBuf* d : {&s->scm, &s->bfw, &s->pnorm, &s->costs, &s->pit_part, &s->Y, &s->out, &s->segw, &s->pcm16_stage}) fn(*d);
+    if (s->ho)
+        for (const DevBuf* d : {&s->ho->gate, &s->ho->carry[0], &s->ho->carry[1], &s->ho->tail[0], &s->ho->tail[1]}) fn(*d);
+    if (s->rate)
+        for (const DevBuf* d : {&s->rate->stage, &s->rate->hist[0], &s->rate->hist[1], &s->rate->tab}) fn(*d);
 }
 
 int64_t device_bytes(const StreamState* s) {
-    int64_t n = 0;
-    for (int b = 0; b < 2; ++b)
-        for (const DevBuf* d : {&s->pcm[b], &s->X[b], &s->masks[b], &s->sep[b], &s->perms[b], &s->act_b[b], &s->G[b]}) n += (int64_t)d->cap;
-    for (const DevBuf* d : {&s->scm, &s->bfw, &s->pnorm, &s->costs, &s->pit_part, &s->Y, &s->out, &s->segw, &s->pcm16_stage}) n += (int64_t)d->cap;
-    if (s->ho) {
-        for (const DevBuf* d : {&s->ho->gate, &s->ho->carry[0], &s->ho->carry[1], &s->ho->tail[0], &s->ho->tail[1]}) n += (int64_t)d->cap;
-        n += (int64_t)(SMAX * sizeof(HandoffState));
-    }
-    if (s->rate)
-        for (const DevBuf* d : {&s->rate->stage, &s->rate->hist[0], &s->rate->hist[1], &s->rate->tab}) n += (int64_t)d->cap;
+    int64_t n = s->ho ? (int64_t)(SMAX * sizeof(HandoffState)) : 0;   // (its rows of the handle's hand-off state)
+    for_each_buffer(s, [&](const DevBuf& d) { n += (int64_t)d.cap; });
     return n;
 }
 
@@ -375,7 +359,7 @@ int tail(css_ctx* h, const std::vector<TailJob>& jobs) {
         if (t_hi > t_lo) {
             GemmArgs g{};
             g.A = (const float*)s->Y.p + (t_lo - fb) * h->KIp; g.lda = h->KIp; g.strideA = s->WF * h->KIp;
-            g.B = h->dft_inv_t; g.ldb = h->KIp; g.strideB = 0;
+            g.B = h->dft_inv_t.as(); g.ldb = h->KIp; g.strideB = 0;
             g.C = (float*)s->G[c].p + (t_lo - fb) * N; g.ldc = N; g.strideC = s->WF * N;
             g.M = (int)(t_hi - t_lo); g.N = N; g.K = h->KIp; g.batch = S;
             g.bias = nullptr; g.act = ACT_NONE; g.residual = nullptr; g.alpha = 1.f;
@@ -471,7 +455,7 @@ int handoff_round(css_ctx* h, const std::vector<HandoffJob>& all, size_t round, 
     auto al = [](size_t v) { return (v + 63) / 64 * 64; };
     for (size_t i = 0; i < n; ++i) {
         const HandoffJob& j = jobs[i];
-        HandoffStream* o = j.s->ho;
+        HandoffStream* o = j.s->ho.get();
         const int64_t D1 = j.closing ? j.n_out : std::max<int64_t>(j.t_g1 - o->pad, 0) * hopS;
         HandoffAppend& a = ap[i];
         a = HandoffAppend{};
@@ -497,17 +481,12 @@ int handoff_round(css_ctx* h, const std::vector<HandoffJob>& all, size_t round, 
     if ((rc = ensure(h, c->spec, (size_t)402 * ld * sizeof(float))) != CSS_OK) return rc;
     if ((rc = ensure(h, c->res, res_b)) != CSS_OK) return rc;
     if (c->pinned.size() <= round) c->pinned.resize(round + 1);
-    HandoffCtx::Pinned& pin = c->pinned[round];
-    if (pin.cap < res_b + state_b) {
-        if (pin.p) HIPCHK(h, hipHostFree(pin.p));
-        pin = HandoffCtx::Pinned{};
-        HIPCHK(h, hipHostMalloc(&pin.p, res_b + state_b, hipHostMallocDefault));
-        pin.cap = res_b + state_b;
-    }
+    PinnedBuf& pin = c->pinned[round];
+    if (pin.cap < res_b + state_b) HIPCHK(h, pin.alloc(res_b + state_b));
     const float* dftm = (const float*)c->tab.p;
     for (size_t i = 0; i < n; ++i) {
         const HandoffJob& j = jobs[i];
-        HandoffStream* o = j.s->ho;
+        HandoffStream* o = j.s->ho.get();
         int id = 0;
         while (h->streams[id] != j.s) ++id;
         ap[i].st = (const HandoffState*)c->state.p + (size_t)id * SMAX;
@@ -549,7 +528,7 @@ int handoff_round(css_ctx* h, const std::vector<HandoffJob>& all, size_t round, 
 // caller's outputs (a preview: the failure is that call's error, the stream has not moved).
 int handoff_collect(css_ctx* h, StreamState* s, int item, int64_t t_g_before, const std::vector<HandoffRec>& recs, HandoffMirror& mir,
                     CssStreamHandoffOut* out, bool commit) {
-    const HandoffStream* o = s->ho;
+    const HandoffStream* o = s->ho.get();
     const int S = h->d.num_spks, hopS = h->d.frame_hop, N = h->d.frame_len, nm = o->cfg.n_mels;
     std::vector<std::vector<int64_t>> reg((size_t)S);
     std::vector<int64_t> nfr((size_t)S, 0);
@@ -628,7 +607,7 @@ int64_t model_samples_after(const StreamState* s, int64_t more) {
 // The entry of the resample launch that takes `n_in` inputs staged in s->rate->stage (0 with `flush`: zeros past the end) and
 // writes outputs [n_pushed, m1) at `win`; flips the history's generation (the launch writes the other one).
 ResampleJob rate_job(StreamState* s, bool i16, bool planar, int64_t n_in, int64_t m1, float* win, bool flush) {
-    RateStream* q = s->rate;
+    RateStream* q = s->rate.get();
     ResampleJob j{};
     j.src = q->stage.p; j.is_i16 = i16 ? 1 : 0; j.plane_ld = planar ? q->max_in : 0; j.n = n_in;
     j.hist_in = (const float*)q->hist[q->cur].p; j.hist_out = flush ? nullptr : (float*)q->hist[1 - q->cur].p; j.H = q->H;
@@ -654,17 +633,10 @@ int check_stream_call(css_ctx* h, int32_t id, StreamState** out) {
 
 void stream_destroy_all(css_ctx* h) {
     for (int i = 0; i < CSS_MAX_STREAMS; ++i)
-        if (h->streams[i]) { free_stream(static_cast<StreamState*>(h->streams[i])); h->streams[i] = nullptr; }
-    if (h->stream_masks.p) hipFree(h->stream_masks.p);
-    h->stream_masks = DevBuf{};
-    if (HandoffCtx* c = handoff_ctx(h)) {
-        for (DevBuf* d : {&c->tab, &c->operand, &c->spec, &c->res, &c->state, &c->state_pv})
-            if (d->p) hipFree(d->p);
-        for (HandoffCtx::Pinned& p : c->pinned)
-            if (p.p) hipHostFree(p.p);
-        delete c;
-        h->handoff = nullptr;
-    }
+        if (h->streams[i]) { delete static_cast<StreamState*>(h->streams[i]); h->streams[i] = nullptr; }
+    h->stream_masks.reset();
+    delete handoff_ctx(h);
+    h->handoff = nullptr;
 }
 int stream_open_count(const css_ctx* h) {
     int n = 0;
@@ -701,7 +673,8 @@ int css_stream_open(css_handle_t h, const CssRunCfg* cfg, int32_t n_ch, int32_t*
         if (!h->streams[i]) id = i;
     if (id < 0) return fail(h, CSS_ERR_STATE, "too many open streams on this handle (CSS_MAX_STREAMS)");
     HIPCHK(h, hipSetDevice(h->device));
-    StreamState* s = new StreamState();
+    std::unique_ptr<StreamState> owner(new StreamState());
+    StreamState* s = owner.get();
     const int T = cfg->segment_frames, hop = cfg->hop_frames, F = h->d.num_bins, S = h->d.num_spks, N = h->d.frame_len;
     s->cfg = *cfg;
     s->w.resize(3 * (size_t)T);
@@ -735,14 +708,14 @@ int css_stream_open(css_handle_t h, const CssRunCfg* cfg, int32_t n_ch, int32_t*
     if (rc == CSS_OK) rc = alloc(s->Y, (size_t)S * s->WF * h->KIp * sizeof(float));
     if (rc == CSS_OK) rc = alloc(s->out, (size_t)S * out_ld * sizeof(float));
     if (rc == CSS_OK) rc = alloc(s->segw, 3 * (size_t)T * sizeof(float));
-    if (rc != CSS_OK) { free_stream(s); return rc; }
+    if (rc != CSS_OK) return rc;
     std::vector<int32_t> ident(S);
     for (int k = 0; k < S; ++k) ident[k] = k;
     hipError_t e = hipMemcpyAsync((int32_t*)s->perms[0].p + S, ident.data(), S * sizeof(int32_t), hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(s->segw.p, s->w.data(), 3 * (size_t)T * sizeof(float), hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) { free_stream(s); return fail(h, CSS_ERR_HIP, std::string("stream setup: ") + hipGetErrorString(e)); }
-    h->streams[id] = s;
+    if (e != hipSuccess) return fail(h, CSS_ERR_HIP, std::string("stream setup: ") + hipGetErrorString(e));
+    h->streams[id] = owner.release();
     *stream_id = id;
     return CSS_OK;
 }
@@ -853,7 +826,7 @@ int push_items(css_ctx* h, const std::vector<PushItem>& items, bool pcm16, CssSt
             const int C = s->n_ch;
             // a rate stream's piece is cut in inputs so that the outputs it makes available are at most `piece` window samples:
             // avail(N) <= n_pushed + piece  <=>  N <= ((n_pushed + piece) down + half) / up
-            if (RateStream* q = s->rate)
+            if (RateStream* q = s->rate.get())
                 it->n_in = std::min<int64_t>(it->p->n_samples - it->done, ((s->n_pushed + s->piece) * q->r.down + q->r.half) / q->r.up - q->n_in);
             else
                 it->n_in = std::min<int64_t>(s->piece, it->p->n_samples - it->done);
@@ -866,7 +839,7 @@ int push_items(css_ctx* h, const std::vector<PushItem>& items, bool pcm16, CssSt
             }
             const int64_t sb = s->seg_base * s->hop * hopS;
             float* win = (float*)s->pcm[s->cur].p + (s->n_pushed - sb);
-            if (RateStream* q = s->rate) {
+            if (RateStream* q = s->rate.get()) {
                 // the caller's samples as they are into the device staging, then the round's resample launch
                 const int64_t ni = it->n_in;
                 const size_t el = pcm16 ? sizeof(int16_t) : sizeof(float);
@@ -1255,7 +1228,7 @@ int css_stream_close(css_handle_t h, int32_t id) {
     if (!s) return fail(h, CSS_ERR_INVALID_ARG, "no open stream with this id");
     hipSetDevice(h->device);
     hipStreamSynchronize(h->stream);
-    free_stream(s);
+    delete s;
     h->streams[id] = nullptr;
     return CSS_OK;
 }
@@ -1283,7 +1256,7 @@ int css_stream_set_rate(css_handle_t h, int32_t id, int32_t up, int32_t down) {
     if (s->rate) return fail(h, CSS_ERR_STATE, "this stream has a rate ratio already");
     if (s->n_pushed > 0 || s->finished) return fail(h, CSS_ERR_STATE, "the rate ratio is set before the stream's first sample");
     HIPCHK(h, hipSetDevice(h->device));
-    RateStream* q = new RateStream();
+    std::unique_ptr<RateStream> q(new RateStream());
     q->r = r;
     q->H = (2 * r.half + r.up - 1) / r.up + 1;
     q->max_in = (s->piece * r.down + r.half) / r.up + 1;
@@ -1298,13 +1271,9 @@ int css_stream_set_rate(css_handle_t h, int32_t id, int32_t up, int32_t down) {
         e = hipMemcpyAsync(q->tab.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice, h->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     }
-    if (rc != CSS_OK || e != hipSuccess) {
-        for (DevBuf* d : {&q->stage, &q->hist[0], &q->hist[1], &q->tab})
-            if (d->p) hipFree(d->p);
-        delete q;
-        return rc != CSS_OK ? rc : fail(h, CSS_ERR_HIP, std::string("rate setup: ") + hipGetErrorString(e));
-    }
-    s->rate = q;
+    if (rc != CSS_OK) return rc;
+    if (e != hipSuccess) return fail(h, CSS_ERR_HIP, std::string("rate setup: ") + hipGetErrorString(e));
+    s->rate = std::move(q);
     return CSS_OK;
 }
 
@@ -1356,7 +1325,7 @@ int css_stream_handoff_open(css_handle_t h, int32_t id, const CssStreamHandoffCf
         if ((rc = ensure(h, c->tab, t.size() * sizeof(float))) != CSS_OK) return rc;
         HIPCHK(h, hipMemcpy(c->tab.p, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));
     }
-    HandoffStream* o = new HandoffStream();
+    std::unique_ptr<HandoffStream> o(new HandoffStream());
     o->cfg = *cfg;
     o->cfg.drop_silence = cfg->drop_silence ? 1 : 0;
     o->pad = o->cfg.drop_silence ? cfg->pad_frames : 0;
@@ -1376,16 +1345,12 @@ int css_stream_handoff_open(css_handle_t h, int32_t id, const CssStreamHandoffCf
         e = hipMemcpyAsync((HandoffState*)c->state.p + (size_t)id * SMAX, init.data(), init.size() * sizeof(HandoffState), hipMemcpyHostToDevice, h->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     }
-    if (rc != CSS_OK || e != hipSuccess) {
-        for (DevBuf* d : {&o->gate, &o->carry[0], &o->carry[1], &o->tail[0], &o->tail[1]})
-            if (d->p) hipFree(d->p);
-        delete o;
-        return rc != CSS_OK ? rc : fail(h, CSS_ERR_HIP, std::string("hand-off setup: ") + hipGetErrorString(e));
-    }
+    if (rc != CSS_OK) return rc;
+    if (e != hipSuccess) return fail(h, CSS_ERR_HIP, std::string("hand-off setup: ") + hipGetErrorString(e));
     o->m.hist.assign((size_t)S, std::vector<uint8_t>());
     o->m.A.assign((size_t)S, 0); o->m.J.assign((size_t)S, 0);
     o->m.raw_max.assign((size_t)S, -INFINITY);
-    s->ho = o;
+    s->ho = std::move(o);
     return CSS_OK;
 }
 

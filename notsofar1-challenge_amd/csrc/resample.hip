@@ -306,32 +306,27 @@ int css_resample_host(css_handle_t h, const void* src, int32_t is_int16, int64_t
     std::vector<float> taps((size_t)r.L), tab((size_t)r.up * r.P_ld);
     resample_taps_f32(r, taps.data());
     resample_phase_table(r, taps.data(), tab.data());
-    void *d_src = nullptr, *d_tab = nullptr, *d_out = nullptr;
-    auto release = [&]() {
-        for (void* p : {d_src, d_tab, d_out})
-            if (p) hipFree(p);
-    };
-    hipError_t e = hipMalloc(&d_src, (size_t)n_in * n_ch * el);
-    if (e == hipSuccess) e = hipMalloc(&d_tab, tab.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&d_out, (size_t)m * n_ch * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpyAsync(d_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice, h->stream);
+    DevBuf d_src, d_tab, d_out;   // released when the call returns, behind the synchronise below
+    hipError_t e = dev_alloc(d_src, (size_t)n_in * n_ch * el);
+    if (e == hipSuccess) e = dev_alloc(d_tab, tab.size() * sizeof(float));
+    if (e == hipSuccess) e = dev_alloc(d_out, (size_t)m * n_ch * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpyAsync(d_tab.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess)
-        e = planar ? hipMemcpy2DAsync(d_src, (size_t)n_in * el, src, (size_t)channel_stride * el, (size_t)n_in * el, (size_t)n_ch,
+        e = planar ? hipMemcpy2DAsync(d_src.p, (size_t)n_in * el, src, (size_t)channel_stride * el, (size_t)n_in * el, (size_t)n_ch,
                                       hipMemcpyHostToDevice, h->stream)
-                   : hipMemcpyAsync(d_src, src, (size_t)n_in * n_ch * el, hipMemcpyHostToDevice, h->stream);
+                   : hipMemcpyAsync(d_src.p, src, (size_t)n_in * n_ch * el, hipMemcpyHostToDevice, h->stream);
     bool launched = true;
     if (e == hipSuccess) {
         ResampleJob j{};
-        j.src = d_src; j.is_i16 = is_int16 ? 1 : 0; j.plane_ld = planar ? n_in : 0; j.n = n_in;
+        j.src = d_src.p; j.is_i16 = is_int16 ? 1 : 0; j.plane_ld = planar ? n_in : 0; j.n = n_in;
         j.N0 = 0; j.m0 = 0; j.n_m = m;
-        j.up = r.up; j.down = r.down; j.half = r.half; j.P = r.P; j.P_ld = r.P_ld; j.tab = (const float*)d_tab;
-        j.C = n_ch; j.dst = (float*)d_out; j.dst_ld = 0;
+        j.up = r.up; j.down = r.down; j.half = r.half; j.P = r.P; j.P_ld = r.P_ld; j.tab = d_tab.as();
+        j.C = n_ch; j.dst = d_out.as(); j.dst_ld = 0;
         launched = launch_resample(j, h->stream);
         if (launched) e = hipGetLastError();
     }
-    if (e == hipSuccess && launched) e = hipMemcpyAsync(out_host, d_out, (size_t)m * n_ch * sizeof(float), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess && launched) e = hipMemcpyAsync(out_host, d_out.p, (size_t)m * n_ch * sizeof(float), hipMemcpyDeviceToHost, h->stream);
     const hipError_t es = hipStreamSynchronize(h->stream);
-    release();
     if (!launched) return fail(h, CSS_ERR_HIP, "the resampling kernel's LDS could not be reserved");
     if (e != hipSuccess || es != hipSuccess)
         return fail(h, CSS_ERR_HIP, std::string("css_resample_host: ") + hipGetErrorString(e != hipSuccess ? e : es));
