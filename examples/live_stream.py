@@ -23,7 +23,12 @@ at once and replaces it as it becomes final.  With --preview --logmel the previe
 provisional log-mel frames and kept seconds up to the present are printed next to the final ones; the host places them behind
 frame preview_handoff.first_frame[k] of speaker k's frames so far and normalises with preview_handoff.raw_max[k].
 
-    python examples/live_stream.py [--seconds 30] [--rooms N] [--logmel] [--pcm16] [--rate HZ] [--preview]
+With --window (implies --logmel) every stream also keeps its last 3 000 raw frames on the device
+(CssStream(window_history=3000)) and every tick ends with ONE call that writes a Whisper encoder input per room and speaker --
+the last frames, normalised over the window, padded to 3 000 columns, float16 -- into a torch tensor on the GPU
+(CssStream.window / CssStreamGroup.windows): what a PyTorch-ROCm Whisper encoder takes, without the frames crossing PCIe again.
+
+    python examples/live_stream.py [--seconds 30] [--rooms N] [--logmel] [--pcm16] [--rate HZ] [--preview] [--window]
 """
 import argparse
 import os
@@ -83,16 +88,36 @@ def behind(inf, first, count, fs):
     return final + f", provisional {max(inf.n_pushed - (first + count), 0) / fs:4.2f} s behind ({count / fs:4.2f} s of preview)"
 
 
-def rooms(sep, n_rooms, seconds, fs, chunk, logmel=False, pcm16=False, rate=None, preview=False):
+def encoder_windows(group, streams, batch):
+    """one css_stream_windows for every (room, speaker) that holds a frame -> the float16 batch [B, 80, 3000] on the device"""
+    reqs = []
+    for s in streams:
+        first, end = s.window_range()
+        reqs += [(s, k) for k in range(s.num_spks) if end[k] > first[k]]
+    if not reqs:
+        print("    no encoder windows yet")
+        return None
+    t = time.perf_counter()
+    out = group.windows(reqs, out=batch[:len(reqs)])
+    ms = (time.perf_counter() - t) * 1e3
+    print(f"    {len(reqs)} encoder windows {tuple(out.shape)} {out.dtype} on {out.device} in {ms:5.2f} ms, "
+          f"{group.window_launches} launch(es)")
+    return out
+
+
+def rooms(sep, n_rooms, seconds, fs, chunk, logmel=False, pcm16=False, rate=None, preview=False, window=False):
     mixes = [SYN.synth_meeting(seconds, 7, seed=1 + r)[0] for r in range(n_rooms)]
     if rate:
         mixes = [capture_at(m, fs, rate) for m in mixes]
         chunk = chunk * rate // fs
     elif pcm16:
         mixes = [capture(m) for m in mixes]
-    streams = [STR.CssStream(sep, CSS.CssCfg(), fs=fs, num_channels=7, handoff=HANDOFF if logmel else None, input_rate=rate)
-               for _ in mixes]
+    streams = [STR.CssStream(sep, CSS.CssCfg(), fs=fs, num_channels=7, handoff=HANDOFF if logmel else None, input_rate=rate,
+                             window_history=3000 if window else None) for _ in mixes]
     group = STR.CssStreamGroup(streams)
+    if window:
+        import torch
+        batch = torch.empty((n_rooms * sep.desc.num_spks, HANDOFF["n_mels"], 3000), dtype=torch.float16, device="cuda")
     outs = [[[] for _ in range(sep.desc.num_spks)] for _ in mixes]
     print(f"{n_rooms} rooms, lag bound {streams[0].latency_samples / fs:.2f} s")
     for i in range(0, mixes[0].shape[0], chunk):
@@ -115,6 +140,8 @@ def rooms(sep, n_rooms, seconds, fs, chunk, logmel=False, pcm16=False, rate=None
                   + behind(inf, streams[0].preview_first_sample, None if pv[0] is None else pv[0][0].shape[0], fs))
             if logmel:
                 print_preview_handoff(streams, fs)
+        if window:
+            encoder_windows(group, streams, batch)   # -> whisper_encoder(batch[:B]) on the same GPU
     for s, room in zip(streams, outs):
         for k, o in enumerate(s.finish()):
             room[k].append(o)
@@ -130,13 +157,15 @@ def main():
     ap.add_argument("--pcm16", action="store_true", help="the source delivers int16 samples: push_pcm16 instead of push")
     ap.add_argument("--preview", action="store_true", help="after each tick's push, also fetch the provisional tail (preview)")
     ap.add_argument("--rate", type=int, default=0, help="the source delivers int16 samples at this rate: CssStream(input_rate=HZ)")
+    ap.add_argument("--window", action="store_true", help="after each tick, Whisper encoder windows per room and speaker in a torch tensor on the GPU")
     a = ap.parse_args()
     fs = 16000
+    a.logmel = a.logmel or a.window
     a.pcm16 = a.pcm16 or bool(a.rate)
     desc = W.ModelDesc.mc_v1()
     sep = SEP.HipSeparator(W.apply_golden_recipe(W.portable_state_dict(desc, 0)), None, device=0)
     if a.rooms > 1:
-        rooms(sep, a.rooms, a.seconds, fs, fs // 2, a.logmel, a.pcm16, a.rate or None, a.preview)
+        rooms(sep, a.rooms, a.seconds, fs, fs // 2, a.logmel, a.pcm16, a.rate or None, a.preview, a.window)
         sep.close()
         return
     mix = SYN.synth_meeting(a.seconds, 7, seed=1)[0]
@@ -147,7 +176,11 @@ def main():
     chunk = (a.rate or fs) // 2
     streams = [[] for _ in range(desc.num_spks)]
     mels = [[] for _ in range(desc.num_spks)]
-    with STR.CssStream(sep, CSS.CssCfg(), fs=fs, num_channels=7, handoff=HANDOFF if a.logmel else None, input_rate=a.rate or None) as s:
+    with STR.CssStream(sep, CSS.CssCfg(), fs=fs, num_channels=7, handoff=HANDOFF if a.logmel else None, input_rate=a.rate or None,
+                       window_history=3000 if a.window else None) as s:
+        if a.window:
+            import torch
+            batch = torch.empty((desc.num_spks, HANDOFF["n_mels"], 3000), dtype=torch.float16, device="cuda")
         print(f"lag bound {s.latency_samples / fs:.2f} s" + (f" + {s.resampler_lag_samples} input samples of the resampler" if s.rate else ""))
         for i in range(0, mix.shape[0], chunk):
             t = time.perf_counter()
@@ -170,6 +203,8 @@ def main():
                 print("    " + behind(inf, s.preview_first_sample, count, fs))
                 if a.logmel and count is not None:
                     print_preview_handoff([s], fs)
+            if a.window:
+                encoder_windows(STR.CssStreamGroup([s]), [s], batch)
         for k, o in enumerate(s.finish()):
             streams[k].append(o)
         if a.logmel:

@@ -114,6 +114,16 @@ class CssStreamPreviewHandoff(C.Structure):
     _fields_ = [("p", CssStreamPreview), ("ho", C.POINTER(CssStreamHandoffOut)), ("first_frame", C.c_void_p)]
 
 
+WINDOW_DTYPES = {"float32": 0, "float16": 1}     # CSS_WINDOW_F32, CSS_WINDOW_F16 (include/css_mi355_window.h)
+WINDOW_MAX_WIDTH = 3000                          # CSS_WINDOW_MAX_WIDTH
+WINDOW_TABLE = 32                                # CSS_WINDOW_TABLE: windows per launch of css_stream_windows
+
+
+class CssStreamWindow(C.Structure):
+    _fields_ = [("id", C.c_int32), ("speaker", C.c_int32), ("first_frame", C.c_int64), ("n_frames", C.c_int32), ("width", C.c_int32),
+                ("dtype", C.c_int32), ("out_dev", C.c_void_p), ("ld", C.c_int64), ("window_max", C.c_float)]
+
+
 class CssGemmDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("kernel", "layout", "tile_rows", "batch", "M", "N", "K", "act")] + \
                [(n, C.c_int64) for n in ("lda", "ldb", "ldc", "ldr", "strideA", "strideB", "strideC", "a_off", "c_off", "r_off",
@@ -271,6 +281,12 @@ SIGNATURES_ENCODER = {
                                        C.POINTER(C.c_int32)]),
     "css_attention_host": (C.c_int, [_P, C.POINTER(CssAttentionDesc), _P, _P, _P, _P, _P, _P]),
 }
+# the entry points include/css_mi355_window.h declares (encoder windows out of a stream's frame history), the sixth table load() applies
+SIGNATURES_WINDOW = {
+    "css_stream_window_open": (C.c_int, [_P, C.c_int32, C.c_int32]),
+    "css_stream_window_range": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "css_stream_windows": (C.c_int, [_P, C.POINTER(CssStreamWindow), C.c_int32, C.POINTER(C.c_int32)]),
+}
 RESAMPLE_TILE = 256                              # output samples per block of the two resampling kernels (resample.hip RS_TILE)
 
 _lib: Optional[C.CDLL] = None
@@ -313,7 +329,8 @@ def load() -> C.CDLL:
     except OSError as e:  # pragma: no cover
         raise CssLibraryError(f"cannot load {LIB_PATH}: {e}") from e
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_RATE.items()) + list(SIGNATURES_PREVIEW.items()) +
-                              list(SIGNATURES_PREVIEW_HANDOFF.items()) + list(SIGNATURES_ENCODER.items())):
+                              list(SIGNATURES_PREVIEW_HANDOFF.items()) + list(SIGNATURES_ENCODER.items()) +
+                              list(SIGNATURES_WINDOW.items())):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

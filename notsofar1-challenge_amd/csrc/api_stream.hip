@@ -31,10 +31,15 @@
 // a piece is copied as the caller laid it out into the stream's device staging and ONE launch per round (resample.hip) filters,
 // decimates and de-interleaves the rate streams' pieces into their windows.  Everything behind the window is unchanged and
 // counts model-rate samples; the call's checks are evaluated on the model-rate samples its inputs make computable.
+//
+// A hand-off stream with a frame history (css_stream_window_open, include/css_mi355_window.h) also keeps its last raw
+// log-mel frames in a ring on the device: the mel launch of a committed round leaves them there.  css_stream_windows turns spans
+// of them into Whisper encoder inputs in the caller's device memory, one table launch per WINDOW_MULTI_MAX windows.
 #include "api_ctx.hpp"
 #include "../../include/css_mi355_rate.h"
 #include "../../include/css_mi355_preview.h"
 #include "../../include/css_mi355_preview_handoff.h"
+#include "../../include/css_mi355_window.h"
 
 #include <climits>
 
@@ -62,6 +67,10 @@ struct HandoffStream {
     int cur = 0;
     int64_t D = 0;                      // decided samples
     HandoffMirror m;
+    // the frame history (css_stream_window_open, include/css_mi355_window.h): raw frames [S][n_mels][hist_frames], frame j in slot
+    // j mod hist_frames, and their maxima over the bands [S][hist_frames]; one generation, written by committed rounds only
+    DevBuf ring, fmax;
+    int64_t hist_frames = 0;
 };
 
 // Per handle, made when the first stream switches the hand-off on.
@@ -126,7 +135,7 @@ void for_each_buffer(const StreamState* s, Fn fn) {
         for (const DevBuf* d : {&s->pcm[b], &s->X[b], &s->masks[b], &s->sep[b], &s->perms[b], &s->act_b[b], &s->G[b]}) fn(*d);
     for (const DevBuf* d : {&s->scm, &s->bfw, &s->pnorm, &s->costs, &s->pit_part, &s->Y, &s->out, &s->segw, &s->pcm16_stage}) fn(*d);
     if (s->ho)
-        for (const DevBuf* d : {&s->ho->gate, &s->ho->carry[0], &s->ho->carry[1], &s->ho->tail[0], &s->ho->tail[1]}) fn(*d);
+        for (const DevBuf* d : {&s->ho->gate, &s->ho->carry[0], &s->ho->carry[1], &s->ho->tail[0], &s->ho->tail[1], &s->ho->ring, &s->ho->fmax}) fn(*d);
     if (s->rate)
         for (const DevBuf* d : {&s->rate->stage, &s->rate->hist[0], &s->rate->hist[1], &s->rate->tab}) fn(*d);
 }
@@ -495,7 +504,8 @@ int handoff_round(css_ctx* h, const std::vector<HandoffJob>& all, size_t round, 
         ap[i].act_out = (uint8_t*)c->res.p + act_off[i];
         ap[i].n_new = (int32_t*)((char*)c->res.p + new_off[i]);
         me[i] = HandoffMel{ap[i].row0, ap[i].rows, ap[i].n_new, st, dftm + HO_DFT_F + (o->cfg.n_mels == 80 ? 0 : HO_MEL80_F), o->cfg.n_mels,
-                           (float*)((char*)c->res.p + mel_off[i]), ap[i].rows};
+                           (float*)((char*)c->res.p + mel_off[i]), ap[i].rows, nullptr, nullptr, 0};
+        if (commit && o->hist_frames) { me[i].ring = (float*)o->ring.p; me[i].fmax = (float*)o->fmax.p; me[i].hist = o->hist_frames; }
         HandoffRec r{};
         r.s = j.s; r.item = j.item; r.t_g0 = j.t_g0; r.t_g1 = j.t_g1; r.D0 = ap[i].D0; r.D1 = ap[i].D1; r.n_out = j.n_out; r.closing = j.closing;
         r.act = (const uint8_t*)pin.p + act_off[i];
@@ -635,6 +645,7 @@ void stream_destroy_all(css_ctx* h) {
     for (int i = 0; i < CSS_MAX_STREAMS; ++i)
         if (h->streams[i]) { delete static_cast<StreamState*>(h->streams[i]); h->streams[i] = nullptr; }
     h->stream_masks.reset();
+    h->window_max.reset();
     delete handoff_ctx(h);
     h->handoff = nullptr;
 }
@@ -1369,6 +1380,93 @@ int css_stream_handoff_stats(css_handle_t h, int32_t* launches, int32_t* product
     if (launches) *launches = c ? c->launches : 0;
     if (products) *products = c ? c->products : 0;
     if (frames) *frames = c ? c->frames : 0;
+    return CSS_OK;
+}
+
+// ---- encoder windows out of the frame history (include/css_mi355_window.h) -------------------------------------------------------
+int css_stream_window_open(css_handle_t h, int32_t id, int32_t history_frames) {
+    StreamState* s = nullptr;
+    int rc = check_stream_call(h, id, &s);
+    if (rc != CSS_OK) return rc;
+    if (history_frames < 32 || history_frames > (1 << 20)) return fail(h, CSS_ERR_INVALID_ARG, "history_frames is 32 .. 2^20");
+    if (!s->ho) return fail(h, CSS_ERR_STATE, "the hand-off of this stream is off (css_stream_handoff_open)");
+    if (s->ho->hist_frames) return fail(h, CSS_ERR_STATE, "this stream has a frame history already");
+    if (s->n_pushed > 0 || s->finished || (s->rate && s->rate->n_in > 0))
+        return fail(h, CSS_ERR_STATE, "the frame history is switched on before the stream's first sample");
+    HIPCHK(h, hipSetDevice(h->device));
+    HandoffStream* o = s->ho.get();
+    const size_t S = (size_t)h->d.num_spks, H = (size_t)history_frames;
+    DevBuf ring, fmax;
+    if ((rc = ensure(h, ring, S * o->cfg.n_mels * H * sizeof(float), true)) != CSS_OK) return rc;
+    if ((rc = ensure(h, fmax, S * H * sizeof(float), true)) != CSS_OK) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    o->ring = std::move(ring); o->fmax = std::move(fmax);
+    o->hist_frames = history_frames;
+    return CSS_OK;
+}
+
+int css_stream_window_range(css_handle_t h, int32_t id, int64_t* first_frame, int64_t* end_frame) {
+    if (!h) return CSS_ERR_INVALID_ARG;
+    StreamState* s = get_stream(h, id);
+    if (!s || !first_frame || !end_frame) return fail(h, CSS_ERR_INVALID_ARG, "no open stream with this id / null argument");
+    if (!s->ho || !s->ho->hist_frames) return fail(h, CSS_ERR_STATE, "this stream has no frame history (css_stream_window_open)");
+    for (int k = 0; k < h->d.num_spks; ++k) {
+        const int64_t J = s->ho->m.J[(size_t)k];
+        first_frame[k] = std::max<int64_t>(J - s->ho->hist_frames, 0);
+        end_frame[k] = J;
+    }
+    return CSS_OK;
+}
+
+int css_stream_windows(css_handle_t h, CssStreamWindow* items, int32_t n_items, int32_t* launches) {
+    if (!h) return CSS_ERR_INVALID_ARG;
+    if (n_items < 0 || (n_items > 0 && !items)) return fail(h, CSS_ERR_INVALID_ARG, "bad argument");
+    if (h->queued || !h->pending.empty())
+        return fail(h, CSS_ERR_STATE, "queued sessions (css_run_enqueue*) are outstanding: css_wait before using a stream");
+    static_assert(WINDOW_MULTI_MAX == CSS_WINDOW_TABLE, "the header states the table's size");
+    std::vector<WindowItem> w((size_t)n_items);
+    for (int32_t i = 0; i < n_items; ++i) {
+        const CssStreamWindow& p = items[i];
+        auto refuse = [&](const std::string& msg) {
+            return fail(h, CSS_ERR_INVALID_ARG, "item " + std::to_string(i) + " (stream " + std::to_string(p.id) + "): " + msg);
+        };
+        const StreamState* s = get_stream(h, p.id);
+        if (!s) return refuse("no open stream with this id");
+        const HandoffStream* o = s->ho.get();
+        if (!o || !o->hist_frames) return refuse("the stream has no frame history (css_stream_window_open)");
+        if (p.speaker < 0 || p.speaker >= h->d.num_spks) return refuse("speaker out of range");
+        if (p.dtype != CSS_WINDOW_F32 && p.dtype != CSS_WINDOW_F16) return refuse("dtype is CSS_WINDOW_F32 or CSS_WINDOW_F16");
+        if (p.n_frames < 1 || p.width < p.n_frames || p.width > CSS_WINDOW_MAX_WIDTH) return refuse("1 <= n_frames <= width <= 3000");
+        if (p.ld < p.width) return refuse("ld < width");
+        const int64_t J = o->m.J[(size_t)p.speaker], first = std::max<int64_t>(J - o->hist_frames, 0);
+        if (p.first_frame < first || p.first_frame > J - p.n_frames) return refuse("frames outside the history (css_stream_window_range)");
+        const size_t el = p.dtype == CSS_WINDOW_F16 ? 2 : 4;
+        if (!p.out_dev || (uintptr_t)p.out_dev % el) return refuse("out_dev is null or not aligned to its element size");
+        WindowItem& e = w[(size_t)i];
+        const int64_t H = o->hist_frames;
+        e.ring = (const float*)o->ring.p + (int64_t)p.speaker * o->cfg.n_mels * H;
+        e.fmax = (const float*)o->fmax.p + (int64_t)p.speaker * H;
+        e.out = p.out_dev; e.wmax = nullptr;
+        e.hist = H; e.ld = p.ld; e.slot0 = p.first_frame % H;
+        e.n_frames = p.n_frames; e.width = p.width; e.n_mels = o->cfg.n_mels; e.f16 = p.dtype == CSS_WINDOW_F16 ? 1 : 0;
+    }
+    if (launches) *launches = 0;
+    if (n_items == 0) return CSS_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc;
+    if ((rc = ensure(h, h->window_max, (size_t)n_items * sizeof(float))) != CSS_OK) return rc;
+    std::vector<float> mx((size_t)n_items);
+    int32_t n_launch = 0;
+    for (int32_t i0 = 0; i0 < n_items; i0 += WINDOW_MULTI_MAX, ++n_launch) {
+        const int cnt = std::min<int32_t>(WINDOW_MULTI_MAX, n_items - i0);
+        for (int i = 0; i < cnt; ++i) w[(size_t)(i0 + i)].wmax = (float*)h->window_max.p + i0 + i;
+        launch_stream_windows(w.data() + i0, cnt, h->stream);
+    }
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(mx.data(), h->window_max.p, mx.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (int32_t i = 0; i < n_items; ++i) items[i].window_max = mx[(size_t)i];
+    if (launches) *launches = n_launch;
     return CSS_OK;
 }
 

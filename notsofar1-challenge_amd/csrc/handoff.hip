@@ -12,10 +12,13 @@
 #include <cmath>
 #include <vector>
 
+#include <hip/hip_fp16.h>
+
 #include "kernels.hpp"
 
 namespace css {
 
+constexpr int MEL_TILE_FRAMES = 32, MEL_TILE_ROWS = 8;   // a mel tile: thread t has frame t % 32 and bands t / 32, t / 32 + 8, ...
 constexpr int MEL_NFFT = 400, MEL_BINS = 201, MEL_K = 416;   // hop 160 (the row stride of the frame operand);   // K padded to the GEMM's 32
 
 // ---- host: tables ---------------------------------------------------------------------------------------------------
@@ -87,13 +90,15 @@ __global__ void handoff_gather_kernel(const float* __restrict__ wav, const int64
 // One tile of 32 frames, shared by the offline kernel and the streamed one so that both round alike (re * re + im * im is
 // open to contraction: one copy of the expression, one rounding).  spec [402][ld] (rows f: Re, 201 + f: Im; time fastest),
 // the tile's frames are columns col0 + j0 .. of it -> mel[m * mel_ld + j] = log10(max(sum_f w[m][f] |X|^2, 1e-10)) for the
-// frames j < nfr, and the maximum of what was written into *gmax (as an order-preserving integer)
-__device__ __forceinline__ void handoff_mel_tile(const float* __restrict__ spec, int64_t ld, int64_t col0, int64_t j0, int64_t nfr,
+// frames j < nfr, and the maximum of what was written into *gmax (as an order-preserving integer).  pw: the block's LDS for the
+// tile's power spectra, the caller's (free again once every thread has returned)
+using MelTilePw = float[MEL_BINS][MEL_TILE_FRAMES + 1];
+__device__ __forceinline__ void handoff_mel_tile(MelTilePw& pw, const float* __restrict__ spec, int64_t ld, int64_t col0, int64_t j0, int64_t nfr,
                                                  const float* __restrict__ w, int n_mels, float* __restrict__ mel, int64_t mel_ld,
                                                  int* __restrict__ gmax) {
-    __shared__ float pw[MEL_BINS][33];
+    static_assert(MEL_TILE_FRAMES == 32 && MEL_TILE_ROWS == 8, "256 threads: the low five bits are the frame");
     const int tj = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    for (int f = ty; f < MEL_BINS; f += 8) {
+    for (int f = ty; f < MEL_BINS; f += MEL_TILE_ROWS) {
         const int64_t j = j0 + tj;
         float p = 0.f;
         if (j < nfr) {
@@ -104,7 +109,7 @@ __device__ __forceinline__ void handoff_mel_tile(const float* __restrict__ spec,
     }
     __syncthreads();
     float best = -INFINITY;
-    for (int m = ty; m < n_mels; m += 8) {
+    for (int m = ty; m < n_mels; m += MEL_TILE_ROWS) {
         float acc = 0.f;
         const float* wm = w + (size_t)m * MEL_BINS;
         for (int f = 0; f < MEL_BINS; ++f) acc = fmaf(wm[f], pw[f][tj], acc);
@@ -125,7 +130,8 @@ __device__ __forceinline__ void handoff_mel_tile(const float* __restrict__ spec,
 __global__ __launch_bounds__(256) void handoff_mel_kernel(const float* __restrict__ spec, int64_t ld, int64_t nfr,
                                                           const float* __restrict__ w, int n_mels, float* __restrict__ mel,
                                                           int* __restrict__ gmax) {
-    handoff_mel_tile(spec, ld, 0, (int64_t)blockIdx.x * 32, nfr, w, n_mels, mel, nfr, gmax);
+    __shared__ MelTilePw pw;
+    handoff_mel_tile(pw, spec, ld, 0, (int64_t)blockIdx.x * MEL_TILE_FRAMES, nfr, w, n_mels, mel, nfr, gmax);
 }
 
 __global__ void handoff_norm_kernel(float* __restrict__ mel, int64_t count, const int* __restrict__ gmax) {
@@ -144,7 +150,7 @@ void launch_handoff_gather(const float* wav, const int64_t* regions, const int64
 void launch_handoff_mel(const float* spec, int64_t ld, int64_t nfr, const float* w, int n_mels, float* mel, int* gmax, hipStream_t s) {
     if (nfr <= 0) return;
     hipMemsetAsync(gmax, 0x80, sizeof(int), s);             // 0x80808080: below every mapped finite value
-    hipLaunchKernelGGL(handoff_mel_kernel, dim3((unsigned)((nfr + 31) / 32)), dim3(256), 0, s, spec, ld, nfr, w, n_mels, mel, gmax);
+    hipLaunchKernelGGL(handoff_mel_kernel, dim3((unsigned)((nfr + MEL_TILE_FRAMES - 1) / MEL_TILE_FRAMES)), dim3(256), 0, s, spec, ld, nfr, w, n_mels, mel, gmax);
     const int64_t count = nfr * n_mels;
     hipLaunchKernelGGL(handoff_norm_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, mel, count, gmax);
 }
@@ -243,10 +249,148 @@ __global__ __launch_bounds__(256) void handoff_append_kernel(HandoffAppendTable 
 __global__ __launch_bounds__(256) void handoff_mel_multi_kernel(HandoffMelTable tab, const float* __restrict__ spec, int64_t ld) {
     const HandoffMel& e = tab.e[blockIdx.z];
     const int k = blockIdx.y;
-    const int64_t nfr = e.n_new[k] < e.rows ? e.n_new[k] : e.rows, j0 = (int64_t)blockIdx.x * 32;
+    const int64_t nfr = e.n_new[k] < e.rows ? e.n_new[k] : e.rows, j0 = (int64_t)blockIdx.x * MEL_TILE_FRAMES;
     if (j0 >= nfr) return;
-    handoff_mel_tile(spec, ld, e.row0 + (int64_t)k * e.rows, j0, nfr, e.w, e.n_mels, e.mel + (int64_t)k * e.n_mels * e.mel_ld, e.mel_ld,
+    __shared__ MelTilePw pw;
+    handoff_mel_tile(pw, spec, ld, e.row0 + (int64_t)k * e.rows, j0, nfr, e.w, e.n_mels, e.mel + (int64_t)k * e.n_mels * e.mel_ld, e.mel_ld,
                      &e.st[k].gmax);
+    if (!e.ring) return;
+    // The frame history: every thread reads back the values it stored itself (the tile's own float32 results: MEL_TILE_FRAMES /
+    // MEL_TILE_ROWS are the tile's mapping of threads to outputs, so no thread reads another's store) and leaves them in the
+    // ring with the frame's maximum over the bands, which the row groups of a column gather in the tile's LDS once every
+    // thread is done with it (a kernel without a history pays no LDS and no barrier for this).  The append kernel has moved st.J to the count after the round, so
+    // the round's frame j is frame J - n_new + j of the concatenation; only the last `hist` frames of a round are kept, so no
+    // two blocks of a launch write one slot.
+    float (*fm)[MEL_TILE_FRAMES] = reinterpret_cast<float (*)[MEL_TILE_FRAMES]>(&pw[0][0]);   // [MEL_TILE_ROWS][MEL_TILE_FRAMES]
+    const int tj = threadIdx.x & (MEL_TILE_FRAMES - 1), ty = threadIdx.x / MEL_TILE_FRAMES;
+    const int64_t j = j0 + tj;
+    const bool keep = j < nfr && j >= nfr - e.hist;
+    int64_t slot = 0;
+    float best = -INFINITY;
+    if (keep) {
+        slot = (e.st[k].J - e.n_new[k] + j) % e.hist;
+        const float* mel = e.mel + (int64_t)k * e.n_mels * e.mel_ld + j;
+        float* ring = e.ring + (int64_t)k * e.n_mels * e.hist + slot;
+        for (int m = ty; m < e.n_mels; m += MEL_TILE_ROWS) {
+            const float v = mel[(int64_t)m * e.mel_ld];
+            ring[(int64_t)m * e.hist] = v;
+            best = fmaxf(best, v);
+        }
+    }
+    __syncthreads();   // (the tile's last reads of pw)
+    fm[ty][tj] = best;
+    __syncthreads();
+    if (ty == 0 && keep) {
+#pragma unroll
+        for (int i = 1; i < MEL_TILE_ROWS; ++i) best = fmaxf(best, fm[i][tj]);
+        e.fmax[(int64_t)k * e.hist + slot] = best;
+    }
+}
+
+// ---- encoder windows out of the frame history -----------------------------------------------------------------------
+struct WindowTable { WindowItem e[WINDOW_MULTI_MAX]; };
+static_assert(sizeof(WindowTable) <= 4096, "the table travels by value as a kernel argument");
+
+template <typename T> struct WindowVec;
+template <> struct WindowVec<float> {
+    static constexpr int V = 4;
+    static __device__ __forceinline__ void store(float* p, float v) { *p = v; }
+    static __device__ __forceinline__ void store16(float* p, const float* v) { *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]); }
+};
+template <> struct WindowVec<__half> {
+    static constexpr int V = 8;
+    static __device__ __forceinline__ void store(__half* p, float v) { *p = __float2half_rn(v); }
+    static __device__ __forceinline__ void store16(__half* p, const float* v) {
+        auto two = [&](int i) {
+            return (uint32_t)__half_as_ushort(__float2half_rn(v[i])) | ((uint32_t)__half_as_ushort(__float2half_rn(v[i + 1])) << 16);
+        };
+        *reinterpret_cast<uint4*>(p) = make_uint4(two(0), two(2), two(4), two(6));
+    }
+};
+
+// One wave per band: consecutive lanes on consecutive columns.  The destination row is written with scalar stores up to its
+// first 16-byte boundary, 16-byte stores from there, scalar stores behind the last whole one; a 16-byte group reads the ring
+// with 16-byte loads where its frames lie in one stretch of the ring (at a 16-byte boundary: as they are; off it: the aligned
+// pieces around them), and frame by frame otherwise (the ring's wrap and its ends, the last frames before the padding).
+template <typename T>
+__device__ __forceinline__ void window_row(const WindowItem& e, const float* __restrict__ src, T* __restrict__ dst, float lo, float fill,
+                                           int lane) {
+    constexpr int V = WindowVec<T>::V;
+    auto norm = [&](float raw) { return (fmaxf(raw, lo) + 4.0f) * 0.25f; };
+    auto one = [&](int c) {
+        if (c >= e.n_frames) return fill;
+        int64_t s = e.slot0 + c;
+        if (s >= e.hist) s -= e.hist;
+        return norm(src[s]);
+    };
+    const int head = min((int)(((16 - ((uintptr_t)dst & 15)) & 15) / sizeof(T)), e.width);
+    const int nvec = (e.width - head) / V, tail = head + nvec * V;
+    for (int c = lane; c < head; c += 64) WindowVec<T>::store(dst + c, one(c));
+    for (int c = tail + lane; c < e.width; c += 64) WindowVec<T>::store(dst + c, one(c));
+    for (int g = lane; g < nvec; g += 64) {
+        const int c = head + g * V;
+        float v[V];
+        int64_t s = e.slot0 + c;
+        if (s >= e.hist) s -= e.hist;
+        const int d = (int)(((uintptr_t)(src + s) >> 2) & 3);   // floats past a 16-byte boundary
+        if (c + V <= e.n_frames && s + V <= e.hist && d == 0) {
+#pragma unroll
+            for (int i = 0; i < V; i += 4) {
+                const float4 q = *reinterpret_cast<const float4*>(src + s + i);
+                v[i] = norm(q.x); v[i + 1] = norm(q.y); v[i + 2] = norm(q.z); v[i + 3] = norm(q.w);
+            }
+        } else if (c + V <= e.n_frames && s >= d && s - d + V + 4 <= e.hist) {
+            // a source that sits d floats off the destination's alignment: the 16-byte pieces that cover the group, all inside
+            // this band's row of the ring, and the group picked out of them (selects on constant positions: no scratch)
+            float b[V + 4];
+#pragma unroll
+            for (int i = 0; i < V + 4; i += 4) {
+                const float4 q = *reinterpret_cast<const float4*>(src + s - d + i);
+                b[i] = q.x; b[i + 1] = q.y; b[i + 2] = q.z; b[i + 3] = q.w;
+            }
+#pragma unroll
+            for (int i = 0; i < V; ++i) v[i] = norm(d == 1 ? b[i + 1] : d == 2 ? b[i + 2] : b[i + 3]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < V; ++i) v[i] = one(c + i);
+        }
+        WindowVec<T>::store16(dst + c, v);
+    }
+}
+
+__global__ __launch_bounds__(256) void stream_window_kernel(WindowTable tab) {
+    const WindowItem& e = tab.e[blockIdx.z];
+    const int m0 = blockIdx.x * WINDOW_ROWS;
+    if (m0 >= e.n_mels) return;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // the window's maximum: over the per-frame maxima of its frames (a maximum is exact in any order)
+    __shared__ float wm[4];
+    float M = -INFINITY;
+    for (int c = tid; c < e.n_frames; c += 256) {
+        int64_t s = e.slot0 + c;
+        if (s >= e.hist) s -= e.hist;
+        M = fmaxf(M, e.fmax[s]);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) M = fmaxf(M, __shfl_xor(M, o));
+    if (lane == 0) wm[wave] = M;
+    __syncthreads();
+    M = fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]));
+    if (blockIdx.x == 0 && tid == 0) *e.wmax = M;
+    const float lo = M - 8.0f, fill = (fmaxf(-10.0f, lo) + 4.0f) * 0.25f;
+    for (int m = m0 + wave; m < e.n_mels && m < m0 + WINDOW_ROWS; m += 4) {
+        const float* src = e.ring + (int64_t)m * e.hist;
+        if (e.f16) window_row<__half>(e, src, (__half*)e.out + (int64_t)m * e.ld, lo, fill, lane);
+        else window_row<float>(e, src, (float*)e.out + (int64_t)m * e.ld, lo, fill, lane);
+    }
+}
+
+void launch_stream_windows(const WindowItem* e, int n, hipStream_t s) {
+    if (n <= 0) return;
+    WindowTable tab{};
+    int most = 1;
+    for (int i = 0; i < n; ++i) { tab.e[i] = e[i]; most = std::max(most, (int)e[i].n_mels); }
+    hipLaunchKernelGGL(stream_window_kernel, dim3((unsigned)((most + WINDOW_ROWS - 1) / WINDOW_ROWS), 1, n), dim3(256), 0, s, tab);
 }
 
 void launch_handoff_append_multi(const HandoffAppend* e, int n, float* operand, hipStream_t s) {
@@ -263,7 +407,7 @@ void launch_handoff_mel_multi(const HandoffMel* e, int n, int S, const float* sp
         HandoffMelTable tab{};
         int64_t most = 1;
         for (int i = 0; i < cnt; ++i) { tab.e[i] = e[i0 + i]; most = std::max(most, e[i0 + i].rows); }
-        hipLaunchKernelGGL(handoff_mel_multi_kernel, dim3((unsigned)((most + 31) / 32), S, cnt), dim3(256), 0, s, tab, spec, ld);
+        hipLaunchKernelGGL(handoff_mel_multi_kernel, dim3((unsigned)((most + MEL_TILE_FRAMES - 1) / MEL_TILE_FRAMES), S, cnt), dim3(256), 0, s, tab, spec, ld);
     }
 }
 

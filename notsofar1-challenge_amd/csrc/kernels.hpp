@@ -225,10 +225,26 @@ struct HandoffMel {
     const int32_t* n_new; HandoffState* st;             // [S] each (st: the append entry's st_out)
     const float* w; int n_mels;                         // the entry's filterbank [n_mels][201]
     float* mel; int64_t mel_ld;                         // out [S][n_mels][mel_ld]
+    // the stream's frame history (css_stream_window_open), null without one and in a preview's round: frame j of speaker k's
+    // concatenation at ring[(k n_mels + m) hist + j mod hist], its maximum over the bands at fmax[k hist + j mod hist]
+    float* ring; float* fmax; int64_t hist;
 };
 constexpr int HANDOFF_MULTI_MAX = 16;
 void launch_handoff_append_multi(const HandoffAppend* e, int n, float* operand, hipStream_t s);
 void launch_handoff_mel_multi(const HandoffMel* e, int n, int S, const float* spec, int64_t ld, hipStream_t s);
+
+// Whisper encoder windows out of a stream's frame history (include/css_mi355_window.h): frames [first, first + n_frames) of one
+// speaker's ring, clamped at their own maximum - 8, (x + 4) / 4, padded to `width` columns with the value a frame of digital
+// zeros takes, as float32 or float16 into the caller's device memory.  A table launch: blockIdx.z = window.
+struct WindowItem {
+    const float* ring; const float* fmax;               // the speaker's rows of the history: [n_mels][hist], [hist]
+    void* out; float* wmax;                             // out [n_mels][ld] of the dtype; the maximum the clamp used
+    int64_t hist, ld, slot0;                            // slot0 = first frame mod hist
+    int32_t n_frames, width, n_mels, f16;
+};
+constexpr int WINDOW_MULTI_MAX = 32;                    // (CSS_WINDOW_TABLE of the header)
+constexpr int WINDOW_ROWS = 8;                          // mel bands per block
+void launch_stream_windows(const WindowItem* e, int n, hipStream_t s);   // one launch; n <= WINDOW_MULTI_MAX
 
 // ------------------------------------------------------------------------------------------------
 // loss.hip -- validation loss of the training loop (train.py:411 _calc_loss): S x S base-loss sums + the noise term

@@ -33,6 +33,12 @@ include/css_mi355_preview_handoff.h) also sets ``stream.preview_handoff``: the h
 moment -- provisional raw log-mel frames from frame ``first_frame[k]`` of stream k's concatenation on, the kept ranges of the
 undecided samples, the gate bits up to the present and the maximum over all of it -- while ``stream.handoff``, the last push's,
 and the stream stay as they were.  With what the pushes returned this is ``Handle.handoff_logmel`` of the prefix, bit for bit.
+
+``CssStream(..., handoff={...}, window_history=3000)`` (css_stream_window_open, include/css_mi355_window.h) also keeps the last
+``window_history`` raw frames of every separated stream on the device.  ``window(k)`` and ``CssStreamGroup.windows(requests)``
+(css_stream_windows) return Whisper encoder inputs as torch tensors on the handle's device -- a span of those frames clamped at
+its own maximum - 8, (x + 4) / 4, padded to ``width`` columns, float16 or float32 -- without the frames crossing PCIe again:
+``whisper_window`` of the frames the pushes returned, bit for bit.
 """
 from __future__ import annotations
 
@@ -55,6 +61,45 @@ def whisper_normalize(raw: np.ndarray, raw_max: Optional[float] = None) -> np.nd
         return raw.copy()
     mx = np.float32(raw.max() if raw_max is None else raw_max)
     return (np.maximum(raw, mx - np.float32(8.0)) + np.float32(4.0)) * np.float32(0.25)
+
+
+def whisper_window(raw: np.ndarray, width: int = 3000, dtype="float16") -> np.ndarray:
+    """The numpy statement of css_stream_windows: raw log-mel frames [n_mels, n] of one span -> [n_mels, width].  Columns < n are
+    ``whisper_normalize(raw)``, clamped at the span's own maximum M; the columns behind them hold what a frame of digital zeros
+    (log10(1e-10) = -10) takes under the same clamp, (max(-10, M - 8) + 4) / 4 in float32; float16 is ``astype`` of that."""
+    raw = np.asarray(raw, dtype=np.float32)
+    dt = np.dtype(dtype)
+    if dt not in (np.dtype(np.float32), np.dtype(np.float16)):
+        raise ValueError(f"windows are float32 or float16, got {dt}")
+    if raw.ndim != 2 or not 1 <= raw.shape[1] <= width:
+        raise ValueError(f"expected [n_mels, 1 .. {width}] frames, got {raw.shape}")
+    fill = (np.maximum(np.float32(-10.0), np.float32(raw.max()) - np.float32(8.0)) + np.float32(4.0)) * np.float32(0.25)
+    out = np.full((raw.shape[0], int(width)), fill, np.float32)
+    out[:, :raw.shape[1]] = whisper_normalize(raw)
+    return out.astype(dt)
+
+
+def _torch():
+    import torch
+    return torch
+
+
+def _window_out(h, n, n_mels, width, dtype, out):
+    """the tensor [n, n_mels, width] a windows call writes (a new one, or the caller's: any view whose last stride is 1 and whose
+    rows of one window are a constant pitch apart, windows that do not overlap) -> (tensor, ld)"""
+    torch = _torch()
+    if dtype not in _lib.WINDOW_DTYPES:
+        raise ValueError(f"windows are float32 or float16, got {dtype!r}")
+    dt = getattr(torch, dtype)
+    if out is None:
+        out = torch.empty((n, n_mels, width), dtype=dt, device=f"cuda:{h.device}")
+    if (out.dtype != dt or tuple(out.shape) != (n, n_mels, width) or not out.is_cuda or (out.device.index or 0) != h.device or
+            (width > 1 and out.stride(2) != 1) or (n_mels > 1 and out.stride(1) < width)):
+        raise ValueError(f"out: a {dtype} tensor {(n, n_mels, width)} on cuda:{h.device} with unit stride along the columns")
+    ld = out.stride(1) if n_mels > 1 else width
+    if n > 1 and out.stride(0) < n_mels * ld:
+        raise ValueError("out: the windows overlap (an expanded or overlapping view)")
+    return out, ld
 
 
 def pcm16_layout(chunk, num_channels: int):
@@ -96,7 +141,8 @@ class CssStream:
     ``finish()`` -> the rest; use as a context manager (closes the stream).  ``handoff``: see the module text."""
 
     def __init__(self, separator: HipSeparator, cfg: Optional[CssCfg] = None, fs: int = 16000, num_channels: int = 7,
-                 handoff: Optional[Mapping[str, object]] = None, input_rate: Optional[int] = None):
+                 handoff: Optional[Mapping[str, object]] = None, input_rate: Optional[int] = None,
+                 window_history: Optional[int] = None):
         self.separator = separator
         self.cfg = cfg if cfg is not None else CssCfg()
         desc = separator.desc
@@ -139,6 +185,17 @@ class CssStream:
             self._ho_caps = (0, 0, 0)
             S = self.num_spks
             self._ho_n = (np.zeros(S, np.int64), np.zeros(S, np.int32), np.zeros(S, np.float32))
+        self.window_history = None
+        self.window_max = None
+        if window_history is not None:
+            try:
+                if handoff is None:
+                    raise ValueError("window_history needs a stream opened with handoff=")
+                _lib.check(self._h.h, self._h.lib.css_stream_window_open(self._h.h, self.id, int(window_history)))
+            except Exception:
+                self.close()
+                raise
+            self.window_history = int(window_history)
 
     def _model_samples(self, n_in: int, finished: bool = False) -> int:
         """model-rate samples after ``n_in`` samples as they are pushed (css_stream_rate_samples; without a rate: ``n_in``)"""
@@ -301,6 +358,35 @@ class CssStream:
         self.preview_first_sample = int(first.value)
         return [out[s, :n_out.value].copy() for s in range(self.num_spks)]
 
+    def window_range(self):
+        """(first, end): the frames [first[k], end[k]) of separated stream k's concatenation the history holds (css_stream_window_range)"""
+        first, end = np.zeros(self.num_spks, np.int64), np.zeros(self.num_spks, np.int64)
+        _lib.check(self._h.h, self._h.lib.css_stream_window_range(self._h.h, self.id, first.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                                  end.ctypes.data_as(C.POINTER(C.c_int64))))
+        return first, end
+
+    def _window_span(self, k: int, first_frame, n_frames, width: int):
+        """the defaults of a window request: the last min(end - first, width) retained frames"""
+        if first_frame is None or n_frames is None:
+            first, end = self.window_range()
+            if first_frame is None:
+                n = min(int(end[k] - first[k]), width) if n_frames is None else int(n_frames)
+                first_frame = int(end[k]) - n
+            if n_frames is None:
+                n_frames = min(int(end[k]) - int(first_frame), width)
+        return int(first_frame), int(n_frames)
+
+    def window(self, k: int, first_frame: Optional[int] = None, n_frames: Optional[int] = None, width: int = 3000,
+               dtype: str = "float16", out=None):
+        """One Whisper encoder input of separated stream k as a torch tensor [n_mels, width] on the handle's device
+        (css_stream_windows): frames [first_frame, first_frame + n_frames) of the history -- by default the last
+        min(end - first, width) retained ones -- normalised over the span, padded, in ``dtype``.  ``out``: a tensor (or a slice
+        of one) to write into.  ``window_max`` holds the maximum the clamp used."""
+        if self._hcfg is None or self.window_history is None:
+            raise ValueError("window() needs a stream opened with handoff= and window_history=")
+        got = CssStreamGroup([self]).windows([(self, k, first_frame, n_frames)], width, dtype, None if out is None else out[None])
+        return got[0]
+
     def close(self):
         if self.id >= 0 and self._h.h:
             self._h.lib.css_stream_close(self._h.h, self.id)
@@ -317,7 +403,8 @@ class CssStream:
 class CssStreamGroup:
     """Streams of ONE ``HipSeparator`` pushed together.  ``push(chunks)`` takes a mapping stream -> chunk, or a sequence with
     one chunk (or None) per stream of the group, and returns per stream of the group what ``CssStream.push`` returns (empty
-    arrays for a stream that took no part).  ``stats`` holds the estimator batches and segments of the last push."""
+    arrays for a stream that took no part).  ``stats`` holds the estimator batches and segments of the last push.
+    ``windows(requests)`` writes Whisper encoder inputs of any of its streams in one call (``CssStream.window`` for many)."""
 
     def __init__(self, streams: Sequence[CssStream]):
         self.streams = list(streams)
@@ -329,6 +416,7 @@ class CssStreamGroup:
             raise ValueError("a stream appears twice in the group")
         self._h = self.streams[0]._h
         self.stats = _lib.CssStreamGroupStats()
+        self.window_launches = 0
 
     def _per_stream(self, chunks) -> list:
         if isinstance(chunks, Mapping):
@@ -409,3 +497,37 @@ class CssStreamGroup:
                 if handoff and s._hcfg is not None:
                     s._preview_handoff_take()
         return [got.get(id(s)) for s in self.streams]
+
+    def windows(self, requests, width: int = 3000, dtype: str = "float16", out=None):
+        """Many encoder inputs in ONE css_stream_windows: ``requests`` are (stream, k) or (stream, k, first_frame, n_frames) with
+        the defaults of ``CssStream.window`` -> a torch tensor [B, n_mels, width] on the handle's device (``out``, or a slice of a
+        caller's tensor, if given).  All streams of the requests hand off the same n_mels.  ``window_launches`` holds the
+        kernel launches of the call, and every named stream's ``window_max`` the maximum of its last request."""
+        reqs = [tuple(r) + (None,) * (4 - len(r)) for r in requests]
+        if not reqs:
+            raise ValueError("no window requests")
+        for s, *_ in reqs:
+            if s not in self.streams:
+                raise ValueError("a stream that is not in this group")
+            if s._hcfg is None or s.window_history is None:
+                raise ValueError("windows() needs streams opened with handoff= and window_history=")
+        n_mels = int(reqs[0][0]._hcfg.n_mels)
+        if any(int(s._hcfg.n_mels) != n_mels for s, *_ in reqs):
+            raise ValueError("the streams of one windows() call hand off the same n_mels")
+        width = int(width)
+        out, ld = _window_out(self._h, len(reqs), n_mels, width, dtype, out)
+        items = (_lib.CssStreamWindow * len(reqs))()
+        el = out.element_size()
+        for i, (it, (s, k, first_frame, n_frames)) in enumerate(zip(items, reqs)):
+            first_frame, n_frames = s._window_span(int(k), first_frame, n_frames, width)
+            it.id, it.speaker, it.first_frame, it.n_frames, it.width = s.id, int(k), first_frame, n_frames, width
+            it.dtype, it.out_dev, it.ld = _lib.WINDOW_DTYPES[dtype], out.data_ptr() + i * out.stride(0) * el, ld
+        # (the library works on the handle's stream and returns after a synchronise of it: what torch has queued for `out` on its
+        # own stream is finished first)
+        _torch().cuda.current_stream(out.device).synchronize()
+        launches = C.c_int32(0)
+        _lib.check(self._h.h, self._h.lib.css_stream_windows(self._h.h, items, len(reqs), C.byref(launches)))
+        self.window_launches = int(launches.value)
+        for it, (s, *_) in zip(items, reqs):
+            s.window_max = float(it.window_max)
+        return out

@@ -31,6 +31,14 @@ at three rounds of a pass every stream's preview is compared with css_run of the
 With --handoff --preview a third call follows: (PH) one css_stream_preview_handoff_many of all streams, timed on its own; at the
 same three rounds every stream's provisional frames, ranges and gate bits, with what its pushes returned so far, are compared
 with css_run_device + css_handoff_logmel of the samples pushed so far, outside the clock (profiles/r14_stream_preview_handoff.json).
+
+With --handoff --window arm B runs alone on streams opened with window_history=3000 and, from the first round after which every
+separated stream holds a frame, two calls follow each round, timed on their own: (W) one css_stream_windows for 3 float16 windows
+of width 3000 per stream (the last frames of every separated stream) into one torch tensor on the device, and (H) what a host
+does today with the same frames, which it has accumulated from the pushes' hand-offs outside the clock: numpy whisper_normalize
+over the span, pad, cast to float16 and torch.from_numpy(...).cuda().  At three rounds both are compared, outside the clock
+(profiles/r15_stream_window.json).  --handoff --history opens the streams with the same history and runs arm B alone: what the
+history costs a round, without the two calls between the rounds.
 """
 import argparse
 import json
@@ -51,7 +59,7 @@ HANDOFF = dict(n_mels=80, pad_frames=8, drop_silence=True)
 
 
 def group_bench(n_streams, out_path, seconds=60.0, round_s=1.5, block=5, passes=2, handoff=False, only_grouped=False, pcm16=False,
-                pinned=False, rate=0, preview=False):
+                pinned=False, rate=0, preview=False, window=False, history=False):
     import notsofar1_challenge_amd.css as CSS
     import notsofar1_challenge_amd.separator as SEP
     import notsofar1_challenge_amd.stream as STR
@@ -83,9 +91,11 @@ def group_bench(n_streams, out_path, seconds=60.0, round_s=1.5, block=5, passes=
     refs = [sep.handle.run(x, rc).copy() for x in recs]
     step = int(round_s * (rate or FS))
     arms = "RR" if rate else ("BC" if pcm16 else "AB")
-    only_grouped = only_grouped or preview
-    ms = {"A": [], "B": [], "C": [], "R": [], "P": [], "PH": []}
-    same = {"A": True, "B": True, "C": True, "R": True, "P": True, "PH": True}
+    only_grouped = only_grouped or preview or window or history
+    ms = {"A": [], "B": [], "C": [], "R": [], "P": [], "PH": [], "W": [], "H": []}
+    same = {"A": True, "B": True, "C": True, "R": True, "P": True, "PH": True, "W": True, "H": True}
+    window_bytes, window_frames, window_launches, window_checks = [], [], [], []
+    WIDTH = 3000
     preview_frames = []
     preview_checks, preview_samples, preview_segments = [], [], []
     seg_per_batch = []
@@ -119,8 +129,13 @@ def group_bench(n_streams, out_path, seconds=60.0, round_s=1.5, block=5, passes=
         return ok
 
     def one_pass(first_arm, timed):
-        streams = [STR.CssStream(sep, cfg, handoff=HANDOFF if handoff else None, input_rate=rate or None) for _ in recs]
+        streams = [STR.CssStream(sep, cfg, handoff=HANDOFF if handoff else None, input_rate=rate or None,
+                                 window_history=WIDTH if window or history else None) for _ in recs]
         group = STR.CssStreamGroup(streams)
+        raw = [[np.zeros((HANDOFF["n_mels"], 0), np.float32) for _ in range(3)] for _ in recs]   # (arm H: the host's own history)
+        if window:
+            import torch
+            w_out = torch.empty((3 * n_streams, HANDOFF["n_mels"], WIDTH), dtype=torch.float16, device="cuda")
         em = [0] * n_streams
         calls = [[] for _ in recs]   # (arm PH: every push's hand-off, for the comparison with the offline call)
         n_rounds = ((q16 if rate else recs)[0].shape[0] + step - 1) // step if timed else 2 * block
@@ -165,6 +180,31 @@ def group_bench(n_streams, out_path, seconds=60.0, round_s=1.5, block=5, passes=
                             n = min((r + 1) * step, recs[i].shape[0])
                             same["PH"] = same["PH"] and p is not None and streams[i].preview_handoff is not None and \
                                 prefix_handoff_equal(recs[i][:n], calls[i], np.stack(p), streams[i].preview_handoff)
+            if window:
+                for i, s in enumerate(streams):
+                    raw[i] = [np.concatenate([a, m], axis=1)[:, -WIDTH:] for a, m in zip(raw[i], s.handoff.mel)]
+                if all(a.shape[1] > 0 for r_ in raw for a in r_):
+                    reqs = [(s, k) for s in streams for k in range(3)]
+                    t = time.perf_counter()
+                    group.windows(reqs, width=WIDTH, dtype="float16", out=w_out)
+                    dt_w = time.perf_counter() - t
+                    t = time.perf_counter()
+                    host = np.stack([STR.whisper_window(a, WIDTH, "float16") for r_ in raw for a in r_])
+                    up = torch.from_numpy(host).cuda()
+                    torch.cuda.synchronize()
+                    dt_h = time.perf_counter() - t
+                    if timed:
+                        ms["W"].append(dt_w * 1e3)
+                        ms["H"].append(dt_h * 1e3)
+                        nm = HANDOFF["n_mels"]
+                        frames = [a.shape[1] for r_ in raw for a in r_]
+                        window_frames.append(float(np.median(frames)))
+                        window_bytes.append(sum(f * (nm + 1) * 4 for f in frames) + len(frames) * nm * WIDTH * 2)
+                        window_launches.append(group.window_launches)
+                        if r in (n_rounds // 8, n_rounds // 2, n_rounds - 2):   # outside the clock
+                            same["W"] = same["W"] and bool(np.array_equal(w_out.cpu().numpy(), host))
+                            same["H"] = same["H"] and bool(torch.equal(up, w_out))
+                            window_checks.append(r)
             if not timed:
                 continue
             ms[arm].append(dt * 1e3)
@@ -195,6 +235,7 @@ def group_bench(n_streams, out_path, seconds=60.0, round_s=1.5, block=5, passes=
            "meeting_s": seconds, "round_s": round_s, "block_rounds": block, "device_bytes_per_stream": int(dev),
            "segments_per_estimator_batch_median": float(np.median(seg_per_batch)) if seg_per_batch else 0.0, "arms": {}}
     if handoff:
+        res["window_history_frames"] = WIDTH if window or history else 0
         res["handoff"] = dict(HANDOFF, mel_frames_per_round_median=float(np.median(mel_frames)),
                               launches_products_frames_last_call=list(sep.handle.stream_handoff_stats()))
     if rate:
@@ -209,9 +250,25 @@ def group_bench(n_streams, out_path, seconds=60.0, round_s=1.5, block=5, passes=
                           "segments_per_estimator_batch_median": float(np.median(preview_segments)) if preview_segments else 0.0}
         if handoff:
             res["preview"]["handoff_mel_frames_per_stream_median"] = float(np.median(preview_frames)) if preview_frames else 0.0
+    if window and ms["W"]:
+        w50 = float(np.percentile(np.array(ms["W"]), 50))
+        # bytes the windows need (frames and their maxima read, windows written) over the wall time of the whole CALL -- checks,
+        # launches, the download of the maxima, the synchronise -- per round; the kernel's own rate needs a kernel trace
+        rate = [b / (m * 1e-3) for b, m in zip(window_bytes, ms["W"])]
+        res["window"] = {"windows_per_call": 3 * n_streams, "width": WIDTH, "dtype": "float16", "history_frames": WIDTH,
+                         "launches_per_call": int(max(window_launches)), "rounds_compared": window_checks,
+                         "frames_per_window_median": float(np.median(window_frames)),
+                         "bytes_per_call_median": float(np.median(window_bytes)), "bytes_per_call_mean": float(np.mean(window_bytes)),
+                         "calls": len(window_bytes),
+                         "frames_per_window_max": float(max(window_frames)),
+                         "call_GB_per_s_median": round(float(np.median(rate)) * 1e-9, 2),
+                         "call_GB_per_s_last_round": round(rate[-1] * 1e-9, 2),
+                         "p50_ratio_H_over_W": round(float(np.percentile(np.array(ms["H"]), 50)) / w50, 3)}
     for arm, what in (("A", "one css_stream_push per stream and round"), ("B", "one css_stream_push_many per round"),
                       ("P", "one css_stream_preview_many per round, after arm B's push"),
                       ("PH", "one css_stream_preview_handoff_many per round, after arm P's preview"),
+                      ("W", "one css_stream_windows per round: 3 float16 windows of width 3000 per stream, on the device"),
+                      ("H", "the same windows by numpy whisper_window of the host's frames + torch.from_numpy(...).cuda()"),
                       ("C", "one css_stream_push_many_pcm16 per round"),
                       ("R", "one css_stream_push_many_pcm16 per round, streams opened with input_rate")):
         if not ms[arm]:
@@ -226,6 +283,9 @@ def group_bench(n_streams, out_path, seconds=60.0, round_s=1.5, block=5, passes=
     if "P" in res["arms"]:
         res["arms"]["P"].pop("streams_in_real_time_per_gpu")
         res["p50_ratio_P_over_B"] = round(res["arms"]["P"]["round_ms_p50"] / res["arms"]["B"]["round_ms_p50"], 4)
+    for arm in ("W", "H"):
+        if arm in res["arms"]:
+            res["arms"][arm].pop("streams_in_real_time_per_gpu")
     if "PH" in res["arms"]:
         res["arms"]["PH"].pop("streams_in_real_time_per_gpu")
         res["p50_ratio_PH_over_P"] = round(res["arms"]["PH"]["round_ms_p50"] / res["arms"]["P"]["round_ms_p50"], 4)
@@ -251,12 +311,15 @@ def main():
     ap.add_argument("--rate", type=int, default=0, help="with --streams: 16-bit recordings at this rate, streams opened with input_rate (arm R alone)")
     ap.add_argument("--preview", action="store_true", help="with --streams: arm B alone, each round followed by one css_stream_preview_many (arm P) and, with --handoff, "
                     "one css_stream_preview_handoff_many (arm PH)")
+    ap.add_argument("--window", action="store_true", help="with --streams --handoff: streams keep a 3000-frame history; arm B alone, each round followed by one "
+                    "css_stream_windows (arm W) and the host's route to the same windows (arm H)")
+    ap.add_argument("--history", action="store_true", help="with --streams --handoff: streams keep a 3000-frame history; arm B alone")
     ap.add_argument("--passes", type=int, default=2, help="with --streams: timed passes over the recordings")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.streams:
         return group_bench(a.streams, a.out, handoff=a.handoff, only_grouped=a.only_grouped, pcm16=a.pcm16, pinned=a.pinned, rate=a.rate,
-                           preview=a.preview, passes=a.passes)
+                           preview=a.preview, passes=a.passes, window=a.window and a.handoff, history=a.history and a.handoff)
     import notsofar1_challenge_amd.css as CSS
     import notsofar1_challenge_amd.separator as SEP
     import notsofar1_challenge_amd.stream as STR
