@@ -28,7 +28,12 @@ With --window (implies --logmel) every stream also keeps its last 3 000 raw fram
 the last frames, normalised over the window, padded to 3 000 columns, float16 -- into a torch tensor on the GPU
 (CssStream.window / CssStreamGroup.windows): what a PyTorch-ROCm Whisper encoder takes, without the frames crossing PCIe again.
 
-    python examples/live_stream.py [--seconds 30] [--rooms N] [--logmel] [--pcm16] [--rate HZ] [--preview] [--window]
+With --present (implies --window) the windows reach the present: ONE call per tick previews every room and writes, per room and
+speaker, the last frames of the history followed by the preview's provisional frames, normalised over the whole span
+(CssStream.present_window / CssStreamGroup.present_windows) -- an encoder input that ends at the microphone instead of up to
+3.6 s behind it, without the provisional frames going through the host.
+
+    python examples/live_stream.py [--seconds 30] [--rooms N] [--logmel] [--pcm16] [--rate HZ] [--preview] [--window] [--present]
 """
 import argparse
 import os
@@ -105,7 +110,20 @@ def encoder_windows(group, streams, batch):
     return out
 
 
-def rooms(sep, n_rooms, seconds, fs, chunk, logmel=False, pcm16=False, rate=None, preview=False, window=False):
+def present_windows(group, streams, batch):
+    """one css_stream_present_windows for every (room, speaker): the preview of all rooms and the float16 batch [B, 80, 3000] that
+    ends at the present, on the device; rows of rooms without a preview or a frame yet stay unwritten (n_used 0)"""
+    reqs = [(s, k) for s in streams for k in range(s.num_spks)]
+    t = time.perf_counter()
+    out, spans, _ = group.present_windows(reqs, out=batch[:len(reqs)])
+    ms = (time.perf_counter() - t) * 1e3
+    live = spans[:, 1] > 0
+    print(f"    {int(live.sum())} of {len(reqs)} encoder windows up to the present in {ms:5.2f} ms, {group.window_launches} launch(es); "
+          f"frames per window {spans[live, 1].tolist()}, of them provisional {spans[live, 2].tolist()}")
+    return out, live
+
+
+def rooms(sep, n_rooms, seconds, fs, chunk, logmel=False, pcm16=False, rate=None, preview=False, window=False, present=False):
     mixes = [SYN.synth_meeting(seconds, 7, seed=1 + r)[0] for r in range(n_rooms)]
     if rate:
         mixes = [capture_at(m, fs, rate) for m in mixes]
@@ -142,6 +160,8 @@ def rooms(sep, n_rooms, seconds, fs, chunk, logmel=False, pcm16=False, rate=None
                 print_preview_handoff(streams, fs)
         if window:
             encoder_windows(group, streams, batch)   # -> whisper_encoder(batch[:B]) on the same GPU
+        if present:
+            present_windows(group, streams, batch)   # -> whisper_encoder(batch[live]): captions up to the present
     for s, room in zip(streams, outs):
         for k, o in enumerate(s.finish()):
             room[k].append(o)
@@ -158,14 +178,16 @@ def main():
     ap.add_argument("--preview", action="store_true", help="after each tick's push, also fetch the provisional tail (preview)")
     ap.add_argument("--rate", type=int, default=0, help="the source delivers int16 samples at this rate: CssStream(input_rate=HZ)")
     ap.add_argument("--window", action="store_true", help="after each tick, Whisper encoder windows per room and speaker in a torch tensor on the GPU")
+    ap.add_argument("--present", action="store_true", help="after each tick, encoder windows that end at the present: the history and a preview's frames in one call")
     a = ap.parse_args()
     fs = 16000
+    a.window = a.window or a.present
     a.logmel = a.logmel or a.window
     a.pcm16 = a.pcm16 or bool(a.rate)
     desc = W.ModelDesc.mc_v1()
     sep = SEP.HipSeparator(W.apply_golden_recipe(W.portable_state_dict(desc, 0)), None, device=0)
     if a.rooms > 1:
-        rooms(sep, a.rooms, a.seconds, fs, fs // 2, a.logmel, a.pcm16, a.rate or None, a.preview, a.window)
+        rooms(sep, a.rooms, a.seconds, fs, fs // 2, a.logmel, a.pcm16, a.rate or None, a.preview, a.window, a.present)
         sep.close()
         return
     mix = SYN.synth_meeting(a.seconds, 7, seed=1)[0]
@@ -205,6 +227,8 @@ def main():
                     print_preview_handoff([s], fs)
             if a.window:
                 encoder_windows(STR.CssStreamGroup([s]), [s], batch)
+            if a.present:
+                present_windows(STR.CssStreamGroup([s]), [s], batch)
         for k, o in enumerate(s.finish()):
             streams[k].append(o)
         if a.logmel:

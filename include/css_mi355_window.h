@@ -14,8 +14,8 @@
  * hand-off changes: the frames still arrive in the bound CssStreamHandoffOut as before, and a stream without a history holds
  * and returns what it did.
  *
- * Not covered: windows over a preview's provisional frames (css_mi355_preview_handoff.h; a preview never writes the history),
- * bfloat16, and spans longer than 3000 frames.
+ * Windows whose span goes on over a preview's provisional frames, up to the present, are css_mi355_present_window.h's (a preview
+ * never writes the history).  Not covered: bfloat16, and spans longer than 3000 frames.
  */
 #ifndef CSS_MI355_WINDOW_H
 #define CSS_MI355_WINDOW_H

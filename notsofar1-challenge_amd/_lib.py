@@ -124,6 +124,16 @@ class CssStreamWindow(C.Structure):
                 ("dtype", C.c_int32), ("out_dev", C.c_void_p), ("ld", C.c_int64), ("window_max", C.c_float)]
 
 
+class CssStreamPresentWindow(C.Structure):      # include/css_mi355_present_window.h
+    _fields_ = [("speaker", C.c_int32), ("n_frames", C.c_int32), ("width", C.c_int32), ("dtype", C.c_int32), ("out_dev", C.c_void_p),
+                ("ld", C.c_int64), ("first_frame", C.c_int64), ("n_used", C.c_int32), ("n_provisional", C.c_int32),
+                ("window_max", C.c_float)]
+
+
+class CssStreamPresentItem(C.Structure):
+    _fields_ = [("ph", CssStreamPreviewHandoff), ("windows", C.POINTER(CssStreamPresentWindow)), ("n_windows", C.c_int32)]
+
+
 class CssGemmDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("kernel", "layout", "tile_rows", "batch", "M", "N", "K", "act")] + \
                [(n, C.c_int64) for n in ("lda", "ldb", "ldc", "ldr", "strideA", "strideB", "strideC", "a_off", "c_off", "r_off",
@@ -287,6 +297,12 @@ SIGNATURES_WINDOW = {
     "css_stream_window_range": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "css_stream_windows": (C.c_int, [_P, C.POINTER(CssStreamWindow), C.c_int32, C.POINTER(C.c_int32)]),
 }
+# the entry point include/css_mi355_present_window.h declares (a preview that also writes encoder windows up to the present), the
+# seventh table load() applies
+SIGNATURES_PRESENT = {
+    "css_stream_present_windows": (C.c_int, [_P, C.POINTER(CssStreamPresentItem), C.c_int32, C.POINTER(CssStreamGroupStats),
+                                             C.POINTER(C.c_int32)]),
+}
 RESAMPLE_TILE = 256                              # output samples per block of the two resampling kernels (resample.hip RS_TILE)
 
 _lib: Optional[C.CDLL] = None
@@ -330,7 +346,7 @@ def load() -> C.CDLL:
         raise CssLibraryError(f"cannot load {LIB_PATH}: {e}") from e
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_RATE.items()) + list(SIGNATURES_PREVIEW.items()) +
                               list(SIGNATURES_PREVIEW_HANDOFF.items()) + list(SIGNATURES_ENCODER.items()) +
-                              list(SIGNATURES_WINDOW.items())):
+                              list(SIGNATURES_WINDOW.items()) + list(SIGNATURES_PRESENT.items())):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

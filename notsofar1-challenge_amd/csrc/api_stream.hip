@@ -40,6 +40,7 @@
 #include "../../include/css_mi355_preview.h"
 #include "../../include/css_mi355_preview_handoff.h"
 #include "../../include/css_mi355_window.h"
+#include "../../include/css_mi355_present_window.h"
 
 #include <climits>
 
@@ -78,6 +79,7 @@ struct HandoffCtx {
     DevBuf tab, operand, spec, res, state;   // DFT matrix + both filterbanks; frame operand; spectra; a round's results; HandoffState per (id, k)
     DevBuf state_pv;                         // a preview's closing round writes its counts and maximum here, never into `state`
     std::vector<PinnedBuf> pinned;           // staging of round r of a call
+    DevBuf present; PinnedBuf present_pin;   // css_stream_present_windows: a PresentWindowOut per window of one call, and its staging
     int32_t launches = 0, products = 0;
     int64_t frames = 0;
 };
@@ -439,10 +441,12 @@ void handoff_begin_call(css_ctx* h) {
 
 // One stream's share of a round's hand-off: frames [t_g0, t_g1) became gated-final, the output buffer holds out_ld samples per
 // speaker from sample t_g0 * hop on.  HandoffRec is what the host needs after the call's synchronise to hand the round's results out.
-struct HandoffJob { StreamState* s; int item; int64_t t_g0, t_g1, out_ld; bool closing; int64_t n_out; };
+// pvmax (a preview's round only): also leave the maxima over the bands of the frames the round makes, for windows up to the present.
+struct HandoffJob { StreamState* s; int item; int64_t t_g0, t_g1, out_ld; bool closing; int64_t n_out; bool pvmax = false; };
 struct HandoffRec {
     StreamState* s; int item; int64_t t_g0, t_g1, D0, D1, n_out; bool closing;
     const uint8_t* act; const int32_t* n_new; const float* mel; int64_t mel_ld; const HandoffState* st;   // in page-locked staging
+    const int32_t* n_new_dev; const float* mel_dev; const float* pvmax_dev;   // the round's results on the device (pvmax_dev: with HandoffJob::pvmax)
 };
 
 // commit: the streams' decided counts, generations and device state move (a push, finish).  Without it (a preview with hand-off)
@@ -458,7 +462,7 @@ int handoff_round(css_ctx* h, const std::vector<HandoffJob>& all, size_t round, 
     const size_t n = jobs.size();
     std::vector<HandoffAppend> ap(n);
     std::vector<HandoffMel> me(n);
-    std::vector<size_t> act_off(n), new_off(n), mel_off(n);
+    std::vector<size_t> act_off(n), new_off(n), mel_off(n), pvm_off(n, 0);
     int64_t rows_total = 0;
     size_t res_b = 0;
     auto al = [](size_t v) { return (v + 63) / 64 * 64; };
@@ -479,6 +483,7 @@ int handoff_round(css_ctx* h, const std::vector<HandoffJob>& all, size_t round, 
         act_off[i] = res_b; res_b = al(res_b + (size_t)S * (size_t)(j.t_g1 - j.t_g0));
         new_off[i] = res_b; res_b = al(res_b + (size_t)S * sizeof(int32_t));
         mel_off[i] = res_b; res_b = al(res_b + (size_t)S * o->cfg.n_mels * (size_t)a.rows * sizeof(float));
+        if (j.pvmax && !commit) { pvm_off[i] = res_b; res_b = al(res_b + (size_t)S * (size_t)a.rows * sizeof(float)); }
     }
     const size_t state_b = (size_t)CSS_MAX_STREAMS * SMAX * sizeof(HandoffState);
     const int64_t ld = (rows_total + 3) / 4 * 4;
@@ -506,6 +511,7 @@ int handoff_round(css_ctx* h, const std::vector<HandoffJob>& all, size_t round, 
         me[i] = HandoffMel{ap[i].row0, ap[i].rows, ap[i].n_new, st, dftm + HO_DFT_F + (o->cfg.n_mels == 80 ? 0 : HO_MEL80_F), o->cfg.n_mels,
                            (float*)((char*)c->res.p + mel_off[i]), ap[i].rows, nullptr, nullptr, 0};
         if (commit && o->hist_frames) { me[i].ring = (float*)o->ring.p; me[i].fmax = (float*)o->fmax.p; me[i].hist = o->hist_frames; }
+        if (j.pvmax && !commit) me[i].pvmax = (float*)((char*)c->res.p + pvm_off[i]);
         HandoffRec r{};
         r.s = j.s; r.item = j.item; r.t_g0 = j.t_g0; r.t_g1 = j.t_g1; r.D0 = ap[i].D0; r.D1 = ap[i].D1; r.n_out = j.n_out; r.closing = j.closing;
         r.act = (const uint8_t*)pin.p + act_off[i];
@@ -513,6 +519,7 @@ int handoff_round(css_ctx* h, const std::vector<HandoffJob>& all, size_t round, 
         r.mel = (const float*)((const char*)pin.p + mel_off[i]);
         r.mel_ld = ap[i].rows;
         r.st = (const HandoffState*)((const char*)pin.p + res_b) + (size_t)id * SMAX;
+        r.n_new_dev = ap[i].n_new; r.mel_dev = me[i].mel; r.pvmax_dev = me[i].pvmax;
         recs->push_back(r);
         if (commit) {
             o->D = ap[i].D1;
@@ -1008,9 +1015,55 @@ struct CloseJob {
     float* out_host; int64_t cap, need;           // samples [n_emitted, p.n_out) -> out_host[S][cap]
     CssStreamHandoffOut* ho = nullptr;            // a preview with hand-off: the caller's outputs and first_frame [S]
     int64_t* first_frame = nullptr;
+    CssStreamPresentWindow* windows = nullptr;    // ... that also writes windows up to the present (css_mi355_present_window.h):
+    int32_t n_windows = 0; size_t win0 = 0;       // the item's windows; the index of its first one among the call's
 };
 
-int closing_pass(css_ctx* h, const std::vector<CloseJob>& jobs, bool commit, CssStreamGroupStats* stats) {
+// What one css_stream_present_windows call launches: `total` windows over all jobs, `launches` kernel launches; after the call's
+// synchronise `res` (page-locked) holds the spans the kernel resolved, window CloseJob::win0 + w of a job at that index.
+struct PresentCall { size_t total = 0; int32_t launches = 0; const PresentWindowOut* res = nullptr; };
+
+// The windows of a preview's jobs, behind the hand-off round `recs` on the handle's stream: the provisional frames, their maxima
+// and their counts are that round's results, which the next round overwrites.
+int present_windows(css_ctx* h, const std::vector<CloseJob>& jobs, const std::vector<HandoffRec>& recs, PresentCall* pc) {
+    HandoffCtx* c = handoff_ctx(h);
+    static_assert(WINDOW_MULTI_MAX == CSS_WINDOW_TABLE, "the header states the table's size");
+    int rc;
+    if ((rc = ensure(h, c->present, pc->total * sizeof(PresentWindowOut))) != CSS_OK) return rc;
+    if (c->present_pin.cap < pc->total * sizeof(PresentWindowOut)) HIPCHK(h, c->present_pin.alloc(pc->total * sizeof(PresentWindowOut)));
+    std::vector<PresentWindowItem> w(pc->total);
+    for (size_t i = 0; i < jobs.size(); ++i) {
+        const CloseJob& j = jobs[i];
+        if (!j.n_windows) continue;
+        const HandoffRec* r = nullptr;
+        for (const HandoffRec& x : recs)
+            if (x.s == j.s && x.item == (int)i) r = &x;
+        if (!r || !r->pvmax_dev) return fail(h, CSS_ERR_STATE, "windows up to the present without the preview's hand-off round");
+        const HandoffStream* o = j.s->ho.get();
+        const int64_t H = o->hist_frames, nm = o->cfg.n_mels;
+        for (int32_t q = 0; q < j.n_windows; ++q) {
+            const CssStreamPresentWindow& p = j.windows[q];
+            PresentWindowItem& e = w[j.win0 + (size_t)q];
+            const int64_t k = p.speaker;
+            e.ring = (const float*)o->ring.p + k * nm * H;
+            e.fmax = (const float*)o->fmax.p + k * H;
+            e.pv = r->mel_dev + k * nm * r->mel_ld;
+            e.pvmax = r->pvmax_dev + k * r->mel_ld;
+            e.n_new = r->n_new_dev + k;
+            e.out = p.out_dev; e.res = (PresentWindowOut*)c->present.p + j.win0 + (size_t)q;
+            e.hist = H; e.ld = p.ld; e.J = o->m.J[(size_t)k]; e.pv_ld = r->mel_ld;
+            e.n_frames = p.n_frames; e.width = p.width; e.n_mels = (int32_t)nm; e.f16 = p.dtype == CSS_WINDOW_F16 ? 1 : 0;
+        }
+    }
+    for (size_t i0 = 0; i0 < pc->total; i0 += WINDOW_MULTI_MAX, ++pc->launches)
+        launch_stream_present_windows(w.data() + i0, (int)std::min<size_t>(WINDOW_MULTI_MAX, pc->total - i0), h->stream);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(c->present_pin.p, c->present.p, pc->total * sizeof(PresentWindowOut), hipMemcpyDeviceToHost, h->stream));
+    pc->res = c->present_pin.as<PresentWindowOut>();
+    return CSS_OK;
+}
+
+int closing_pass(css_ctx* h, const std::vector<CloseJob>& jobs, bool commit, CssStreamGroupStats* stats, PresentCall* pc = nullptr) {
     if (jobs.empty()) return CSS_OK;
     int rc;
     std::vector<HandoffRec> recs;
@@ -1073,9 +1126,11 @@ int closing_pass(css_ctx* h, const std::vector<CloseJob>& jobs, bool commit, Css
         for (size_t i = 0; i < jobs.size(); ++i) {
             StreamState* s = jobs[i].s;
             const int64_t TL = jobs[i].p.mix_frames;
-            if (commit || jobs[i].ho) hj.push_back(HandoffJob{s, (int)i, s->t_g, TL, (TL + 1 - s->t_g) * hopS, true, jobs[i].p.n_out});
+            if (commit || jobs[i].ho)
+                hj.push_back(HandoffJob{s, (int)i, s->t_g, TL, (TL + 1 - s->t_g) * hopS, true, jobs[i].p.n_out, jobs[i].n_windows > 0});
         }
         if ((rc = handoff_round(h, hj, 0, &recs, commit)) != CSS_OK) return rc;
+        if (pc && pc->total && (rc = present_windows(h, jobs, recs, pc)) != CSS_OK) return rc;
     }
     for (const CloseJob& j : jobs)
         if ((rc = download(h, j.s, j.need, j.out_host, j.cap, 0)) != CSS_OK) return rc;
@@ -1140,9 +1195,14 @@ int css_stream_preview_samples(const CssModelDesc* desc, const CssRunCfg* cfg, i
 namespace {
 
 // one item of a grouped preview: the waveform item and, for a preview with hand-off, the caller's outputs
-struct PreviewItem { CssStreamPreview* p; CssStreamHandoffOut* ho; int64_t* first_frame; };
+// ... and, for css_stream_present_windows (`present`), its windows
+struct PreviewItem {
+    CssStreamPreview* p; CssStreamHandoffOut* ho; int64_t* first_frame;
+    bool present = false; CssStreamPresentWindow* windows = nullptr; int32_t n_windows = 0;
+};
 
-int preview_items(css_ctx* h, const std::vector<PreviewItem>& items, CssStreamGroupStats* stats) {
+int preview_items(css_ctx* h, const std::vector<PreviewItem>& items, CssStreamGroupStats* stats, int32_t* window_launches = nullptr) {
+    PresentCall pc;
     const int32_t n_items = (int32_t)items.size();
     std::vector<CloseJob> jobs;
     std::vector<int32_t> status((size_t)n_items, CSS_OK);
@@ -1169,16 +1229,43 @@ int preview_items(css_ctx* h, const std::vector<PreviewItem>& items, CssStreamGr
             if (hrc != CSS_OK) return refuse(hrc, why);
             j.ho = ho; j.first_frame = items[(size_t)i].first_frame;
         }
+        if (items[(size_t)i].present) {
+            const PreviewItem& it = items[(size_t)i];
+            if (!s->ho || !s->ho->hist_frames) return refuse(CSS_ERR_STATE, "the stream has no frame history (css_stream_window_open)");
+            if (it.n_windows < 0 || (it.n_windows > 0 && (!it.windows || !it.ho)))
+                return refuse(CSS_ERR_INVALID_ARG, "n_windows < 0, or windows without `windows` or without hand-off outputs (ph.ho)");
+            for (int32_t q = 0; q < it.n_windows; ++q) {
+                const CssStreamPresentWindow& w = it.windows[q];
+                auto bad = [&](const std::string& msg) { return refuse(CSS_ERR_INVALID_ARG, "window " + std::to_string(q) + ": " + msg); };
+                if (w.speaker < 0 || w.speaker >= h->d.num_spks) return bad("speaker out of range");
+                if (w.dtype != CSS_WINDOW_F32 && w.dtype != CSS_WINDOW_F16) return bad("dtype is CSS_WINDOW_F32 or CSS_WINDOW_F16");
+                if (w.n_frames < 1 || w.width < w.n_frames || w.width > CSS_WINDOW_MAX_WIDTH) return bad("1 <= n_frames <= width <= 3000");
+                if (w.ld < w.width) return bad("ld < width");
+                const size_t el = w.dtype == CSS_WINDOW_F16 ? 2 : 4;
+                if (!w.out_dev || (uintptr_t)w.out_dev % el) return bad("out_dev is null or not aligned to its element size");
+            }
+            j.windows = it.windows; j.n_windows = it.n_windows;
+        }
         plan_impl(h->d, s->cfg, j.n_total, &j.p);
         first[(size_t)i] = s->n_emitted;
         if (j.p.zero_weight) { status[(size_t)i] = CSS_ERR_ZERO_WEIGHT; continue; }   // (css_run's refusal of this prefix: the item's own)
         j.need = j.p.n_out - s->n_emitted;
         if (!p.out_host || p.cap < j.need) return refuse(CSS_ERR_INVALID_ARG, "output capacity too small for the preview (css_stream_preview_samples)");
+        j.win0 = pc.total;
+        pc.total += (size_t)j.n_windows;
         jobs.push_back(j);
     }
     if (stats) *stats = CssStreamGroupStats{};
-    const int rc = closing_pass(h, jobs, false, stats);
+    const int rc = closing_pass(h, jobs, false, stats, &pc);
     if (rc != CSS_OK) return rc;
+    for (const CloseJob& j : jobs)
+        for (int32_t q = 0; q < j.n_windows; ++q) {
+            const PresentWindowOut& r = pc.res[j.win0 + (size_t)q];
+            CssStreamPresentWindow& w = j.windows[q];
+            w.first_frame = r.first_frame; w.n_used = r.n_used; w.n_provisional = r.n_provisional;
+            if (r.n_used > 0) w.window_max = r.window_max;
+        }
+    if (window_launches) *window_launches = pc.launches;
     size_t k = 0;
     for (int32_t i = 0; i < n_items; ++i) {
         CssStreamPreview& p = *items[(size_t)i].p;
@@ -1206,6 +1293,17 @@ int css_stream_preview_handoff_many(css_handle_t h, CssStreamPreviewHandoff* ite
     std::vector<PreviewItem> v;
     for (int32_t i = 0; i < n_items; ++i) v.push_back(PreviewItem{&items[i].p, items[i].ho, items[i].first_frame});
     return preview_items(h, v, stats);
+}
+
+// ---- previews that also write windows up to the present (include/css_mi355_present_window.h) -----------------------------------
+int css_stream_present_windows(css_handle_t h, CssStreamPresentItem* items, int32_t n_items, CssStreamGroupStats* stats,
+                               int32_t* window_launches) {
+    if (!h) return CSS_ERR_INVALID_ARG;
+    if (n_items < 1 || !items) return fail(h, CSS_ERR_INVALID_ARG, "bad argument");
+    std::vector<PreviewItem> v;
+    for (int32_t i = 0; i < n_items; ++i)
+        v.push_back(PreviewItem{&items[i].ph.p, items[i].ph.ho, items[i].ph.first_frame, true, items[i].windows, items[i].n_windows});
+    return preview_items(h, v, stats, window_launches);
 }
 
 // a group of one item

@@ -246,6 +246,9 @@ __global__ __launch_bounds__(256) void handoff_append_kernel(HandoffAppendTable 
     }
 }
 
+// PVMAX: the launch of a preview's round that has an entry with HandoffMel::pvmax (windows up to the present); every other launch
+// is the <false> instance, which has no code for it.
+template <bool PVMAX>
 __global__ __launch_bounds__(256) void handoff_mel_multi_kernel(HandoffMelTable tab, const float* __restrict__ spec, int64_t ld) {
     const HandoffMel& e = tab.e[blockIdx.z];
     const int k = blockIdx.y;
@@ -254,6 +257,29 @@ __global__ __launch_bounds__(256) void handoff_mel_multi_kernel(HandoffMelTable 
     __shared__ MelTilePw pw;
     handoff_mel_tile(pw, spec, ld, e.row0 + (int64_t)k * e.rows, j0, nfr, e.w, e.n_mels, e.mel + (int64_t)k * e.n_mels * e.mel_ld, e.mel_ld,
                      &e.st[k].gmax);
+    if constexpr (PVMAX) {
+        // The provisional frames stay where the tile wrote them; each frame's maximum over the bands goes next to them, gathered
+        // as below: every thread over the values it stored itself, the row groups of a column through the tile's LDS.
+        if (e.pvmax) {
+            float (*fm)[MEL_TILE_FRAMES] = reinterpret_cast<float (*)[MEL_TILE_FRAMES]>(&pw[0][0]);
+            const int tj = threadIdx.x & (MEL_TILE_FRAMES - 1), ty = threadIdx.x / MEL_TILE_FRAMES;
+            const int64_t j = j0 + tj;
+            float best = -INFINITY;
+            if (j < nfr) {
+                const float* mel = e.mel + (int64_t)k * e.n_mels * e.mel_ld + j;
+                for (int m = ty; m < e.n_mels; m += MEL_TILE_ROWS) best = fmaxf(best, mel[(int64_t)m * e.mel_ld]);
+            }
+            __syncthreads();   // (the tile's last reads of pw)
+            fm[ty][tj] = best;
+            __syncthreads();
+            if (ty == 0 && j < nfr) {
+#pragma unroll
+                for (int i = 1; i < MEL_TILE_ROWS; ++i) best = fmaxf(best, fm[i][tj]);
+                e.pvmax[(int64_t)k * e.rows + j] = best;
+            }
+            return;
+        }
+    }
     if (!e.ring) return;
     // The frame history: every thread reads back the values it stored itself (the tile's own float32 results: MEL_TILE_FRAMES /
     // MEL_TILE_ROWS are the tile's mapping of threads to outputs, so no thread reads another's store) and leaves them in the
@@ -393,6 +419,139 @@ void launch_stream_windows(const WindowItem* e, int n, hipStream_t s) {
     hipLaunchKernelGGL(stream_window_kernel, dim3((unsigned)((most + WINDOW_ROWS - 1) / WINDOW_ROWS), 1, n), dim3(256), 0, s, tab);
 }
 
+// ---- encoder windows that reach the present: the history, then a preview's provisional frames ---------------------------------
+struct PresentWindowTable { PresentWindowItem e[WINDOW_MULTI_MAX]; };
+static_assert(sizeof(PresentWindowTable) <= 4096, "the table travels by value as a kernel argument");
+
+// Frames s .. s + V - 1 of one band's row of `len` floats (the caller has s + V <= len) through 16-byte loads: as they are at a
+// 16-byte boundary; off it, the aligned pieces around them where those lie inside the row (selects on constant positions: no
+// scratch).  false: neither fits, nothing was loaded.
+template <int V>
+__device__ __forceinline__ bool window_load16(const float* __restrict__ row, int64_t s, int64_t len, float (&v)[V]) {
+    const int d = (int)(((uintptr_t)(row + s) >> 2) & 3);   // floats past a 16-byte boundary
+    if (d == 0) {
+#pragma unroll
+        for (int i = 0; i < V; i += 4) {
+            const float4 q = *reinterpret_cast<const float4*>(row + s + i);
+            v[i] = q.x; v[i + 1] = q.y; v[i + 2] = q.z; v[i + 3] = q.w;
+        }
+        return true;
+    }
+    if (s >= d && s - d + V + 4 <= len) {
+        float b[V + 4];
+#pragma unroll
+        for (int i = 0; i < V + 4; i += 4) {
+            const float4 q = *reinterpret_cast<const float4*>(row + s - d + i);
+            b[i] = q.x; b[i + 1] = q.y; b[i + 2] = q.z; b[i + 3] = q.w;
+        }
+#pragma unroll
+        for (int i = 0; i < V; ++i) v[i] = d == 1 ? b[i + 1] : d == 2 ? b[i + 2] : b[i + 3];
+        return true;
+    }
+    return false;
+}
+
+// The span as the block resolved it: columns [0, n_ring) are the ring's slots slot0 .. (wrapping at hist), columns
+// [n_ring, used) the provisional frames p0 .., the rest padding.
+struct PresentSpan { int64_t slot0; int n_ring, used, p0; };
+
+// window_row with two sources.  A 16-byte group that lies in one stretch of the ring, or wholly in the provisional frames, is
+// read with 16-byte loads inside that source; the ring's wrap, the seam between the sources and the last frames before the
+// padding are taken frame by frame.
+template <typename T>
+__device__ __forceinline__ void present_window_row(const PresentWindowItem& e, const PresentSpan& sp, const float* __restrict__ ring,
+                                                   const float* __restrict__ pv, T* __restrict__ dst, float lo, float fill, int lane) {
+    constexpr int V = WindowVec<T>::V;
+    auto norm = [&](float raw) { return (fmaxf(raw, lo) + 4.0f) * 0.25f; };
+    auto one = [&](int c) {
+        if (c >= sp.used) return fill;
+        if (c >= sp.n_ring) return norm(pv[sp.p0 + (c - sp.n_ring)]);
+        int64_t s = sp.slot0 + c;
+        if (s >= e.hist) s -= e.hist;
+        return norm(ring[s]);
+    };
+    const int head = min((int)(((16 - ((uintptr_t)dst & 15)) & 15) / sizeof(T)), e.width);
+    const int nvec = (e.width - head) / V, tail = head + nvec * V;
+    for (int c = lane; c < head; c += 64) WindowVec<T>::store(dst + c, one(c));
+    for (int c = tail + lane; c < e.width; c += 64) WindowVec<T>::store(dst + c, one(c));
+    for (int g = lane; g < nvec; g += 64) {
+        const int c = head + g * V;
+        float v[V];
+        bool done = false;
+        if (c + V <= sp.n_ring) {
+            int64_t s = sp.slot0 + c;
+            if (s >= e.hist) s -= e.hist;
+            if (s + V <= e.hist) done = window_load16<V>(ring, s, e.hist, v);
+        } else if (c >= sp.n_ring && c + V <= sp.used) {
+            done = window_load16<V>(pv, sp.p0 + (c - sp.n_ring), e.pv_ld, v);
+        }
+        if (done) {
+#pragma unroll
+            for (int i = 0; i < V; ++i) v[i] = norm(v[i]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < V; ++i) v[i] = one(c + i);
+        }
+        WindowVec<T>::store16(dst + c, v);
+    }
+}
+
+__global__ __launch_bounds__(256) void stream_present_window_kernel(PresentWindowTable tab) {
+    const PresentWindowItem& e = tab.e[blockIdx.z];
+    const int m0 = blockIdx.x * WINDOW_ROWS;
+    if (m0 >= e.n_mels) return;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // the span: P provisional frames behind the J final ones, of which the ring holds [R, J)
+    const int64_t n_new = *e.n_new;
+    const int64_t P = n_new < e.pv_ld ? n_new : e.pv_ld;
+    const int64_t E = e.J + P, R = e.J > e.hist ? e.J - e.hist : 0, a = E - e.n_frames > R ? E - e.n_frames : R;
+    PresentSpan sp;
+    sp.used = (int)(E - a);
+    const int n_prov = sp.used < P ? sp.used : (int)P;
+    sp.n_ring = sp.used - n_prov;
+    sp.p0 = (int)P - n_prov;
+    sp.slot0 = a % e.hist;
+    if (blockIdx.x == 0 && tid == 0) {
+        e.res->first_frame = a;
+        e.res->n_used = sp.used;
+        e.res->n_provisional = n_prov;
+    }
+    if (sp.used == 0) return;
+    // the window's maximum: over the per-frame maxima of its frames (a maximum is exact in any order)
+    __shared__ float wm[4];
+    float M = -INFINITY;
+    for (int c = tid; c < sp.used; c += 256) {
+        if (c >= sp.n_ring) {
+            M = fmaxf(M, e.pvmax[sp.p0 + (c - sp.n_ring)]);
+        } else {
+            int64_t s = sp.slot0 + c;
+            if (s >= e.hist) s -= e.hist;
+            M = fmaxf(M, e.fmax[s]);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) M = fmaxf(M, __shfl_xor(M, o));
+    if (lane == 0) wm[wave] = M;
+    __syncthreads();
+    M = fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]));
+    if (blockIdx.x == 0 && tid == 0) e.res->window_max = M;
+    const float lo = M - 8.0f, fill = (fmaxf(-10.0f, lo) + 4.0f) * 0.25f;
+    for (int m = m0 + wave; m < e.n_mels && m < m0 + WINDOW_ROWS; m += 4) {
+        const float* ring = e.ring + (int64_t)m * e.hist;
+        const float* pv = e.pv + (int64_t)m * e.pv_ld;
+        if (e.f16) present_window_row<__half>(e, sp, ring, pv, (__half*)e.out + (int64_t)m * e.ld, lo, fill, lane);
+        else present_window_row<float>(e, sp, ring, pv, (float*)e.out + (int64_t)m * e.ld, lo, fill, lane);
+    }
+}
+
+void launch_stream_present_windows(const PresentWindowItem* e, int n, hipStream_t s) {
+    if (n <= 0) return;
+    PresentWindowTable tab{};
+    int most = 1;
+    for (int i = 0; i < n; ++i) { tab.e[i] = e[i]; most = std::max(most, (int)e[i].n_mels); }
+    hipLaunchKernelGGL(stream_present_window_kernel, dim3((unsigned)((most + WINDOW_ROWS - 1) / WINDOW_ROWS), 1, n), dim3(256), 0, s, tab);
+}
+
 void launch_handoff_append_multi(const HandoffAppend* e, int n, float* operand, hipStream_t s) {
     for (int i0 = 0; i0 < n; i0 += HANDOFF_MULTI_MAX) {
         const int cnt = std::min(HANDOFF_MULTI_MAX, n - i0);
@@ -406,8 +565,11 @@ void launch_handoff_mel_multi(const HandoffMel* e, int n, int S, const float* sp
         const int cnt = std::min(HANDOFF_MULTI_MAX, n - i0);
         HandoffMelTable tab{};
         int64_t most = 1;
-        for (int i = 0; i < cnt; ++i) { tab.e[i] = e[i0 + i]; most = std::max(most, e[i0 + i].rows); }
-        hipLaunchKernelGGL(handoff_mel_multi_kernel, dim3((unsigned)((most + MEL_TILE_FRAMES - 1) / MEL_TILE_FRAMES), S, cnt), dim3(256), 0, s, tab, spec, ld);
+        bool pvmax = false;
+        for (int i = 0; i < cnt; ++i) { tab.e[i] = e[i0 + i]; most = std::max(most, e[i0 + i].rows); pvmax = pvmax || e[i0 + i].pvmax; }
+        const dim3 grid((unsigned)((most + MEL_TILE_FRAMES - 1) / MEL_TILE_FRAMES), S, cnt);
+        if (pvmax) hipLaunchKernelGGL(handoff_mel_multi_kernel<true>, grid, dim3(256), 0, s, tab, spec, ld);
+        else hipLaunchKernelGGL(handoff_mel_multi_kernel<false>, grid, dim3(256), 0, s, tab, spec, ld);
     }
 }
 

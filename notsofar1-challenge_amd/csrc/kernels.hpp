@@ -228,6 +228,9 @@ struct HandoffMel {
     // the stream's frame history (css_stream_window_open), null without one and in a preview's round: frame j of speaker k's
     // concatenation at ring[(k n_mels + m) hist + j mod hist], its maximum over the bands at fmax[k hist + j mod hist]
     float* ring; float* fmax; int64_t hist;
+    // a preview's round whose stream is asked for windows up to the present (css_stream_present_windows), null otherwise: the
+    // maximum over the bands of provisional frame j of speaker k at pvmax[k rows + j]
+    float* pvmax;
 };
 constexpr int HANDOFF_MULTI_MAX = 16;
 void launch_handoff_append_multi(const HandoffAppend* e, int n, float* operand, hipStream_t s);
@@ -245,6 +248,21 @@ struct WindowItem {
 constexpr int WINDOW_MULTI_MAX = 32;                    // (CSS_WINDOW_TABLE of the header)
 constexpr int WINDOW_ROWS = 8;                          // mel bands per block
 void launch_stream_windows(const WindowItem* e, int n, hipStream_t s);   // one launch; n <= WINDOW_MULTI_MAX
+
+// Windows that reach the present (include/css_mi355_present_window.h): at most n_frames frames counted back from the end of a
+// preview's provisional frames -- the ring's frames [a, J), then the last provisional ones -- under the same rule.  How many
+// frames the preview made (P = *n_new, at most pv_ld) is known on the device only, so the kernel resolves the span itself:
+// E = J + P, a = max(E - n_frames, max(J - hist, 0)), used = E - a, of which min(used, P) are provisional; it leaves them in *res.
+struct PresentWindowOut { int64_t first_frame; int32_t n_used, n_provisional; float window_max; int32_t pad_; };
+struct PresentWindowItem {
+    const float* ring; const float* fmax;               // the speaker's rows of the history: [n_mels][hist], [hist]
+    const float* pv; const float* pvmax;                // the speaker's provisional frames [n_mels][pv_ld] and their maxima [pv_ld]
+    const int32_t* n_new;                               // the speaker's count of the preview's round (HandoffAppend::n_new + k)
+    void* out; PresentWindowOut* res;                   // out [n_mels][ld] of the dtype; the span (window_max only where used > 0)
+    int64_t hist, ld, J, pv_ld;                         // J: frames the pushes returned for the speaker
+    int32_t n_frames, width, n_mels, f16;
+};
+void launch_stream_present_windows(const PresentWindowItem* e, int n, hipStream_t s);   // one launch; n <= WINDOW_MULTI_MAX
 
 // ------------------------------------------------------------------------------------------------
 // loss.hip -- validation loss of the training loop (train.py:411 _calc_loss): S x S base-loss sums + the noise term

@@ -39,6 +39,12 @@ and the stream stay as they were.  With what the pushes returned this is ``Handl
 (css_stream_windows) return Whisper encoder inputs as torch tensors on the handle's device -- a span of those frames clamped at
 its own maximum - 8, (x + 4) / 4, padded to ``width`` columns, float16 or float32 -- without the frames crossing PCIe again:
 ``whisper_window`` of the frames the pushes returned, bit for bit.
+
+``present_window(k)`` and ``CssStreamGroup.present_windows(requests)`` (css_stream_present_windows,
+include/css_mi355_present_window.h) are ``preview(handoff=True)`` and windows in one call and under one synchronise: the span
+ends at the present frame -- the history's final frames, then the preview's provisional ones, which never leave the device for
+this -- and ``present_span`` tells (first_frame, n_used, n_provisional).  ``whisper_window`` of the frames the pushes returned
+followed by ``preview_handoff.mel[k]``, bit for bit.
 """
 from __future__ import annotations
 
@@ -187,6 +193,7 @@ class CssStream:
             self._ho_n = (np.zeros(S, np.int64), np.zeros(S, np.int32), np.zeros(S, np.float32))
         self.window_history = None
         self.window_max = None
+        self.present_span = None
         if window_history is not None:
             try:
                 if handoff is None:
@@ -387,6 +394,19 @@ class CssStream:
         got = CssStreamGroup([self]).windows([(self, k, first_frame, n_frames)], width, dtype, None if out is None else out[None])
         return got[0]
 
+    def present_window(self, k: int, n_frames: Optional[int] = None, width: int = 3000, dtype: str = "float16", out=None):
+        """One Whisper encoder input of separated stream k that ends at the present (css_stream_present_windows): at most
+        ``n_frames`` (default ``width``) frames counted back from the last provisional frame of a preview made in the same call
+        -- the history's final frames, then the provisional ones -- normalised over the span and padded, as a torch tensor
+        [n_mels, width] on the handle's device (``out``, if given); None when there is no frame yet and no ``out`` was given.
+        Sets ``present_span`` = (first_frame, n_used, n_provisional) and ``window_max``, and ``preview_handoff`` /
+        ``preview_first_sample`` as ``preview(handoff=True)`` does; raises what that raises.  The stream stays as it was."""
+        if self._hcfg is None or self.window_history is None:
+            raise ValueError("present_window() needs a stream opened with handoff= and window_history=")
+        got, spans, _ = CssStreamGroup([self]).present_windows([(self, k, n_frames)], width, dtype, None if out is None else out[None],
+                                                               _raise_refused=True)
+        return got[0] if out is not None or spans[0, 1] > 0 else None
+
     def close(self):
         if self.id >= 0 and self._h.h:
             self._h.lib.css_stream_close(self._h.h, self.id)
@@ -531,3 +551,66 @@ class CssStreamGroup:
         for it, (s, *_) in zip(items, reqs):
             s.window_max = float(it.window_max)
         return out
+
+    def present_windows(self, requests, width: int = 3000, dtype: str = "float16", out=None, _raise_refused: bool = False):
+        """Encoder inputs that end at the present, in ONE css_stream_present_windows: ``requests`` are (stream, k) or
+        (stream, k, n_frames) (default ``width``); every stream that is named becomes one preview item of the call, so the
+        pending segments share one estimator batch (``stats``) and all windows one synchronise (``window_launches``: their kernel
+        launches).  -> (torch tensor [n, n_mels, width] on the handle's device -- ``out``, by ``windows``' rules, if given --,
+        spans int64 [n, 3] of (first_frame, n_used, n_provisional), maxima float32 [n]).  A window without a frame (n_used 0), and
+        every window of a stream whose prefix ``css_run`` refuses (spans row (-1, 0, 0), ``preview_handoff`` None), is left
+        unwritten with a NaN maximum.  Every named stream gets ``preview_handoff`` / ``preview_first_sample`` as
+        ``preview(handoff=True)`` sets them, and ``present_span`` / ``window_max`` of its last request."""
+        reqs = [tuple(r) + (None,) * (3 - len(r)) for r in requests]
+        if not reqs:
+            raise ValueError("no window requests")
+        for s, *_ in reqs:
+            if s not in self.streams:
+                raise ValueError("a stream that is not in this group")
+            if s._hcfg is None or s.window_history is None:
+                raise ValueError("present_windows() needs streams opened with handoff= and window_history=")
+        n_mels = int(reqs[0][0]._hcfg.n_mels)
+        if any(int(s._hcfg.n_mels) != n_mels for s, *_ in reqs):
+            raise ValueError("the streams of one present_windows() call hand off the same n_mels")
+        width = int(width)
+        out, ld = _window_out(self._h, len(reqs), n_mels, width, dtype, out)
+        el = out.element_size()
+        part = [s for s in self.streams if any(r[0] is s for r in reqs)]
+        items = (_lib.CssStreamPresentItem * len(part))()
+        outs, tables, where = [], [], {}
+        for it, s in zip(items, part):
+            mine = [i for i, r in enumerate(reqs) if r[0] is s]
+            wav = np.empty((s.num_spks, max(s.latency_samples, 1)), np.float32)
+            outs.append(wav)
+            it.ph.p.id, it.ph.p.out_host, it.ph.p.cap = s.id, wav.ctypes.data, wav.shape[1]
+            ho, first_frame = s._preview_handoff_out()
+            it.ph.ho, it.ph.first_frame = C.pointer(ho), first_frame.ctypes.data
+            tab = (_lib.CssStreamPresentWindow * len(mine))()
+            tables.append(tab)
+            for w, i in zip(tab, mine):
+                _, k, n_frames = reqs[i]
+                w.speaker, w.n_frames, w.width = int(k), width if n_frames is None else int(n_frames), width
+                w.dtype, w.out_dev, w.ld = _lib.WINDOW_DTYPES[dtype], out.data_ptr() + i * out.stride(0) * el, ld
+                w.first_frame, w.window_max = -1, float("nan")
+                where[i] = w
+            it.windows, it.n_windows = tab, len(mine)
+        # (as in windows(): what torch has queued for `out` on its own stream is finished first)
+        _torch().cuda.current_stream(out.device).synchronize()
+        stats, launches = _lib.CssStreamGroupStats(), C.c_int32(0)
+        _lib.check(self._h.h, self._h.lib.css_stream_present_windows(self._h.h, items, len(part), C.byref(stats), C.byref(launches)))
+        self.stats = stats
+        self.window_launches = int(launches.value)
+        for it, s, wav in zip(items, part, outs):
+            s.preview_handoff = None
+            if it.ph.p.status == _lib.CSS_OK:
+                s.preview_first_sample = int(it.ph.p.first_sample)
+                s._preview_handoff_take()
+            elif _raise_refused:
+                _lib.check(self._h.h, it.ph.p.status)
+        spans = np.array([[where[i].first_frame, where[i].n_used, where[i].n_provisional] for i in range(len(reqs))], np.int64)
+        maxima = np.array([where[i].window_max for i in range(len(reqs))], np.float32)
+        for i, (s, *_) in enumerate(reqs):
+            s.present_span = tuple(int(v) for v in spans[i])
+            if spans[i, 1] > 0:
+                s.window_max = float(maxima[i])
+        return out, spans, maxima

@@ -39,6 +39,12 @@ does today with the same frames, which it has accumulated from the pushes' hand-
 over the span, pad, cast to float16 and torch.from_numpy(...).cuda().  At three rounds both are compared, outside the clock
 (profiles/r15_stream_window.json).  --handoff --history opens the streams with the same history and runs arm B alone: what the
 history costs a round, without the two calls between the rounds.
+
+With --handoff --preview --window everything above runs in every round and one more call follows, timed on its own: (PW) one
+css_stream_present_windows of all streams -- arm PH's preview and arm W's 3 float16 windows of width 3000 per stream in one call
+and under one synchronise, the windows reaching over the preview's provisional frames to the present.  PH, W and PW follow one
+another inside every round, so they share clock and power state; at three rounds PW's windows are compared with whisper_window of
+the host's frames followed by the preview's, outside the clock (profiles/r16_stream_present_window.json).
 """
 import argparse
 import json
@@ -92,8 +98,10 @@ def group_bench(n_streams, out_path, seconds=60.0, round_s=1.5, block=5, passes=
     step = int(round_s * (rate or FS))
     arms = "RR" if rate else ("BC" if pcm16 else "AB")
     only_grouped = only_grouped or preview or window or history
-    ms = {"A": [], "B": [], "C": [], "R": [], "P": [], "PH": [], "W": [], "H": []}
-    same = {"A": True, "B": True, "C": True, "R": True, "P": True, "PH": True, "W": True, "H": True}
+    ms = {"A": [], "B": [], "C": [], "R": [], "P": [], "PH": [], "W": [], "H": [], "PW": []}
+    same = {"A": True, "B": True, "C": True, "R": True, "P": True, "PH": True, "W": True, "H": True, "PW": True}
+    present = preview and handoff and window
+    present_launches, present_provisional, present_checks, pw_rounds = [], [], [], []
     window_bytes, window_frames, window_launches, window_checks = [], [], [], []
     WIDTH = 3000
     preview_frames = []
@@ -136,6 +144,7 @@ def group_bench(n_streams, out_path, seconds=60.0, round_s=1.5, block=5, passes=
         if window:
             import torch
             w_out = torch.empty((3 * n_streams, HANDOFF["n_mels"], WIDTH), dtype=torch.float16, device="cuda")
+            pw_out = torch.empty_like(w_out) if present else None
         em = [0] * n_streams
         calls = [[] for _ in recs]   # (arm PH: every push's hand-off, for the comparison with the offline call)
         n_rounds = ((q16 if rate else recs)[0].shape[0] + step - 1) // step if timed else 2 * block
@@ -205,6 +214,20 @@ def group_bench(n_streams, out_path, seconds=60.0, round_s=1.5, block=5, passes=
                             same["W"] = same["W"] and bool(np.array_equal(w_out.cpu().numpy(), host))
                             same["H"] = same["H"] and bool(torch.equal(up, w_out))
                             window_checks.append(r)
+                    if present:
+                        t = time.perf_counter()
+                        _, spans, _ = group.present_windows(reqs, width=WIDTH, dtype="float16", out=pw_out)
+                        dt_pw = time.perf_counter() - t
+                        if timed:
+                            ms["PW"].append(dt_pw * 1e3)
+                            pw_rounds.append((dt_ph * 1e3, dt_w * 1e3, dt_pw * 1e3))
+                            present_launches.append(group.window_launches)
+                            present_provisional.append(float(np.median(spans[:, 2])))
+                            if r in (n_rounds // 8, n_rounds // 2, n_rounds - 2):   # outside the clock
+                                want = np.stack([STR.whisper_window(np.concatenate([a, s.preview_handoff.mel[k]], axis=1)[:, -WIDTH:], WIDTH, "float16")
+                                                 for s, r_ in zip(streams, raw) for k, a in enumerate(r_)])
+                                same["PW"] = same["PW"] and bool(np.array_equal(pw_out.cpu().numpy(), want))
+                                present_checks.append(r)
             if not timed:
                 continue
             ms[arm].append(dt * 1e3)
@@ -264,11 +287,23 @@ def group_bench(n_streams, out_path, seconds=60.0, round_s=1.5, block=5, passes=
                          "call_GB_per_s_median": round(float(np.median(rate)) * 1e-9, 2),
                          "call_GB_per_s_last_round": round(rate[-1] * 1e-9, 2),
                          "p50_ratio_H_over_W": round(float(np.percentile(np.array(ms["H"]), 50)) / w50, 3)}
+    if present and ms["PW"]:
+        v = np.array(pw_rounds)   # [rounds, (PH, W, PW)] of the rounds that ran all three
+        p50 = [float(np.percentile(v[:, i], 50)) for i in range(3)]
+        res["present_window"] = {"windows_per_call": 3 * n_streams, "width": WIDTH, "dtype": "float16", "history_frames": WIDTH,
+                                 "launches_per_call": int(max(present_launches)), "rounds_compared": present_checks,
+                                 "provisional_frames_per_window_median": float(np.median(present_provisional)),
+                                 "rounds_with_PH_W_and_PW": int(v.shape[0]),
+                                 "PH_ms_p50_same_rounds": round(p50[0], 3), "W_ms_p50_same_rounds": round(p50[1], 3),
+                                 "PW_ms_p50": round(p50[2], 3),
+                                 "PW_minus_PH_plus_W_ms_p50_of_rounds": round(float(np.percentile(v[:, 2] - v[:, 0] - v[:, 1], 50)), 3),
+                                 "PW_minus_PH_plus_W_ms_p10_p90_of_rounds": [round(float(np.percentile(v[:, 2] - v[:, 0] - v[:, 1], q)), 3) for q in (10, 90)]}
     for arm, what in (("A", "one css_stream_push per stream and round"), ("B", "one css_stream_push_many per round"),
                       ("P", "one css_stream_preview_many per round, after arm B's push"),
                       ("PH", "one css_stream_preview_handoff_many per round, after arm P's preview"),
                       ("W", "one css_stream_windows per round: 3 float16 windows of width 3000 per stream, on the device"),
                       ("H", "the same windows by numpy whisper_window of the host's frames + torch.from_numpy(...).cuda()"),
+                      ("PW", "one css_stream_present_windows per round: arm PH's preview and arm W's windows, up to the present, in one call"),
                       ("C", "one css_stream_push_many_pcm16 per round"),
                       ("R", "one css_stream_push_many_pcm16 per round, streams opened with input_rate")):
         if not ms[arm]:
@@ -283,7 +318,7 @@ def group_bench(n_streams, out_path, seconds=60.0, round_s=1.5, block=5, passes=
     if "P" in res["arms"]:
         res["arms"]["P"].pop("streams_in_real_time_per_gpu")
         res["p50_ratio_P_over_B"] = round(res["arms"]["P"]["round_ms_p50"] / res["arms"]["B"]["round_ms_p50"], 4)
-    for arm in ("W", "H"):
+    for arm in ("W", "H", "PW"):
         if arm in res["arms"]:
             res["arms"][arm].pop("streams_in_real_time_per_gpu")
     if "PH" in res["arms"]:
@@ -312,7 +347,8 @@ def main():
     ap.add_argument("--preview", action="store_true", help="with --streams: arm B alone, each round followed by one css_stream_preview_many (arm P) and, with --handoff, "
                     "one css_stream_preview_handoff_many (arm PH)")
     ap.add_argument("--window", action="store_true", help="with --streams --handoff: streams keep a 3000-frame history; arm B alone, each round followed by one "
-                    "css_stream_windows (arm W) and the host's route to the same windows (arm H)")
+                    "css_stream_windows (arm W) and the host's route to the same windows (arm H); with --preview also one "
+                    "css_stream_present_windows (arm PW)")
     ap.add_argument("--history", action="store_true", help="with --streams --handoff: streams keep a 3000-frame history; arm B alone")
     ap.add_argument("--passes", type=int, default=2, help="with --streams: timed passes over the recordings")
     ap.add_argument("--out", default=None)
