@@ -157,6 +157,30 @@ class CssAttentionDesc(C.Structure):
                [(n, C.c_int64) for n in ("x_floats", "w_floats", "pe_floats", "qkv_floats", "ctx_floats")]
 
 
+class CssAnalysisDesc(C.Structure):             # include/css_mi355_frontend.h
+    _fields_ = [(n, C.c_int32) for n in ("C", "t_lo", "t_hi", "offset", "window", "want_phase")] + \
+               [(n, C.c_int64) for n in ("x_stride", "row_ld", "x_floats", "out_floats", "phase_floats")]
+
+
+class CssFeaturesDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("C", "F", "nseg", "T", "hop", "Kp", "split_out", "reserved")] + \
+               [(n, C.c_int64) for n in ("T_ld", "stft_frames", "seg_lo", "x_floats", "ph_floats", "feat_floats")] + \
+               [("cfg", CssFeatureCfg)]
+
+
+class CssSynthesisTailDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("form", "B", "hop", "L", "world", "S", "F2", "KIp", "has_level")] + \
+               [("level", C.c_uint32)] + \
+               [(n, C.c_int64) for n in ("T_frames", "q_lo", "q_hi", "f_lo", "f_hi", "out_ld", "out_q0", "ld", "n_out", "in_floats",
+                                         "out_floats")] + \
+               [("t_lo", C.c_int64 * 64), ("t_hi", C.c_int64 * 64)]
+
+
+class CssPcmEdgesDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("form", "C", "split_out", "S", "src_offset")] + [("peak_before", C.c_uint32)] + \
+               [(n, C.c_int64) for n in ("n", "n_pad", "i_lo", "i_hi", "count", "out_ld", "in_elems", "out_elems")]
+
+
 class CssKernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("ms", C.c_float), ("launches", C.c_int32)]
 
@@ -303,6 +327,14 @@ SIGNATURES_PRESENT = {
     "css_stream_present_windows": (C.c_int, [_P, C.POINTER(CssStreamPresentItem), C.c_int32, C.POINTER(CssStreamGroupStats),
                                              C.POINTER(C.c_int32)]),
 }
+# the entry points include/css_mi355_frontend.h declares (the kernels of csrc/stft.hip and csrc/frontend.hip on caller data), the
+# eighth table load() applies
+SIGNATURES_FRONTEND = {
+    "css_analysis_host": (C.c_int, [_P, C.POINTER(CssAnalysisDesc), _P, _P, _P]),
+    "css_features_host": (C.c_int, [_P, C.POINTER(CssFeaturesDesc), _P, _P, _P, _P, _P]),
+    "css_synthesis_tail_host": (C.c_int, [_P, C.POINTER(CssSynthesisTailDesc), _P, _P]),
+    "css_pcm_edges_host": (C.c_int, [_P, C.POINTER(CssPcmEdgesDesc), _P, _P, _P]),
+}
 RESAMPLE_TILE = 256                              # output samples per block of the two resampling kernels (resample.hip RS_TILE)
 
 _lib: Optional[C.CDLL] = None
@@ -346,7 +378,8 @@ def load() -> C.CDLL:
         raise CssLibraryError(f"cannot load {LIB_PATH}: {e}") from e
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_RATE.items()) + list(SIGNATURES_PREVIEW.items()) +
                               list(SIGNATURES_PREVIEW_HANDOFF.items()) + list(SIGNATURES_ENCODER.items()) +
-                              list(SIGNATURES_WINDOW.items()) + list(SIGNATURES_PRESENT.items())):
+                              list(SIGNATURES_WINDOW.items()) + list(SIGNATURES_PRESENT.items()) +
+                              list(SIGNATURES_FRONTEND.items())):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -822,6 +855,62 @@ class Handle:
         check(self.h, self.lib.css_attention_host(self.h, C.byref(d), _np_ptr(x), _np_ptr(w), _np_ptr(bias), _np_ptr(pe), _np_ptr(qkv),
                                                   _np_ptr(ctx)))
         return qkv, ctx
+
+    # ---- the kernels of csrc/stft.hip and csrc/frontend.hip on caller data (include/css_mi355_frontend.h;
+    #      tests/test_hip_frontend_kernels.py).  Arrays are the WHOLE allocations; outputs are returned as the launch left them.
+    def analysis(self, x: np.ndarray, C_: int, x_stride: int, t_lo: int, t_hi: int, row_ld: int, out: np.ndarray, *, offset: int = 0,
+                 window: int = 0, phase=None):
+        """launch_stft_fft (css_analysis_host).  Returns (out, phase)."""
+        flat = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float32).reshape(-1).copy()
+        x, out, phase = np.ascontiguousarray(x, dtype=np.float32).reshape(-1), flat(out), flat(phase)
+        d = CssAnalysisDesc(C=int(C_), t_lo=int(t_lo), t_hi=int(t_hi), offset=int(offset), window=int(window),
+                            want_phase=int(phase is not None), x_stride=int(x_stride), row_ld=int(row_ld), x_floats=x.size,
+                            out_floats=out.size, phase_floats=0 if phase is None else phase.size)
+        check(self.h, self.lib.css_analysis_host(self.h, C.byref(d), _np_ptr(x), _np_ptr(out), None if phase is None else _np_ptr(phase)))
+        return out, phase
+
+    def features_host(self, X: np.ndarray, C_: int, F: int, T_ld: int, stft_frames: int, seg_lo: int, nseg: int, T: int, hop: int,
+                      Kp: int, cfg: "CssFeatureCfg", in_bias, in_scale, feat: np.ndarray, *, split_out: int = 0, PH=None):
+        """launch_features (css_features_host).  Returns feat."""
+        f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
+        X, in_bias, in_scale, feat = f32(X), f32(in_bias), f32(in_scale), f32(feat).copy()
+        PH = None if PH is None else f32(PH)
+        d = CssFeaturesDesc(C=int(C_), F=int(F), nseg=int(nseg), T=int(T), hop=int(hop), Kp=int(Kp), split_out=int(split_out),
+                            T_ld=int(T_ld), stft_frames=int(stft_frames), seg_lo=int(seg_lo), x_floats=X.size,
+                            ph_floats=0 if PH is None else PH.size, feat_floats=feat.size, cfg=cfg)
+        if in_bias.size != F * (1 + cfg.num_pairs) or in_scale.size != in_bias.size:
+            raise ValueError("in_bias, in_scale [F (1 + pairs)]")
+        check(self.h, self.lib.css_features_host(self.h, C.byref(d), _np_ptr(X), None if PH is None else _np_ptr(PH), _np_ptr(in_bias),
+                                                 _np_ptr(in_scale), _np_ptr(feat)))
+        return feat
+
+    def synthesis_tail(self, form: int, src: np.ndarray, out: np.ndarray, *, t_lo=(), t_hi=(), level=None, **fields):
+        """launch_wave_ola (0), launch_join_shards (1), launch_planes_to_rows (2) (css_synthesis_tail_host); fields are the
+        descriptor's.  level: None (absent) or the word.  Returns out."""
+        src = np.ascontiguousarray(src, dtype=np.float32).reshape(-1)
+        out = np.ascontiguousarray(out, dtype=np.float32).reshape(-1).copy()
+        d = CssSynthesisTailDesc(form=int(form), has_level=int(level is not None), level=int(level or 0), in_floats=src.size,
+                                 out_floats=out.size, **{k: int(v) for k, v in fields.items()})
+        for k, (lo, hi) in enumerate(zip(t_lo, t_hi)):
+            d.t_lo[k], d.t_hi[k] = int(lo), int(hi)
+        check(self.h, self.lib.css_synthesis_tail_host(self.h, C.byref(d), _np_ptr(src), _np_ptr(out)))
+        return out
+
+    def pcm_edges(self, form: int, src: np.ndarray, out=None, **fields):
+        """The PCM edges (css_pcm_edges_host; the header lists the forms); fields are the descriptor's.  Returns (out, peak):
+        the output allocation (None for the peak forms) and the peak words (None for forms 0 .. 2)."""
+        src = np.ascontiguousarray(src).reshape(-1)
+        out = None if out is None else np.ascontiguousarray(out).reshape(-1).copy()
+        want = {0: (np.float32, np.float32), 1: (np.int16, np.float32), 2: (np.int16, np.float32), 3: (np.float32, None),
+                4: (np.int16, None), 5: (np.float32, np.int16)}[int(form)]
+        if src.dtype != want[0] or (out is not None and out.dtype != want[1]):
+            raise ValueError("array types do not match the form")
+        peak = np.zeros(max(1, int(fields.get("S", 1))), np.uint32) if form >= 3 else None
+        d = CssPcmEdgesDesc(form=int(form), in_elems=src.size, out_elems=0 if out is None else out.size,
+                            **{k: int(v) for k, v in fields.items()})
+        check(self.h, self.lib.css_pcm_edges_host(self.h, C.byref(d), _np_ptr(src), None if out is None else _np_ptr(out),
+                                                  None if peak is None else _np_ptr(peak)))
+        return out, peak
 
     # ---- RCCL through the C ABI (css_comm_*): what a host in another language would call
     def comm_init(self, unique_id: bytes, nranks: int, rank: int):

@@ -186,6 +186,17 @@ void launch_encode_pcm16(const float* wav, int S, int64_t n, unsigned int* peak_
 // FEAT_TMAX: segment lengths an instantiation covers (256: up to 4 s, the shipped 3 s; 512: up to 8 s)
 #define CSS_EPS32 1.1920928955078125e-07f
 
+// the input affine of conformer.py:298-299 as ONE float32 value for both row formats.  Inlined in front of split_f16 the product
+// was fused into what follows it: x - hi became fma(v + bias, scale, -hi), and the conversion to hi took the unrounded product
+// (v_fma_mixlo_f16), so the split rows were not the split_encode of the float32 rows -- lo in a third of the elements, hi where
+// the float32 value sits on a float16 tie (tests/test_hip_frontend_kernels.py).  The empty asm makes the rounded value the only
+// thing later code can see.
+__device__ __forceinline__ float feat_affine(float v, float bi, float sc) {
+    float y = (v + bi) * sc;
+    asm volatile("" : "+v"(y));
+    return y;
+}
+
 template <int FEAT_TMAX>
 __global__ __launch_bounds__(256) void features_kernel(const float* __restrict__ X, int64_t T_ld, int64_t stft_frames,
                                                        int F, float* __restrict__ feat, int Kp,
@@ -320,10 +331,10 @@ __global__ __launch_bounds__(256) void features_kernel(const float* __restrict__
         if (split_out) {   // rows in the split-f16 GEMM operand format (split_f16.hpp) for the embed Linear
             float* out = feat + (int64_t)segl * T * Kp;
             for (int t = wave * 2 + (lane >> 5); t < T; t += 8)
-                split_store(reinterpret_cast<_Float16*>(out + (int64_t)t * Kp), col, (tile[fl * FEAT_LD + t] + bi) * sc);
+                split_store(reinterpret_cast<_Float16*>(out + (int64_t)t * Kp), col, feat_affine(tile[fl * FEAT_LD + t], bi, sc));
         } else {
             float* out = feat + (int64_t)segl * T * Kp + col;
-            for (int t = wave * 2 + (lane >> 5); t < T; t += 8) out[(int64_t)t * Kp] = (tile[fl * FEAT_LD + t] + bi) * sc;
+            for (int t = wave * 2 + (lane >> 5); t < T; t += 8) out[(int64_t)t * Kp] = feat_affine(tile[fl * FEAT_LD + t], bi, sc);
         }
     }
 }
@@ -372,7 +383,7 @@ __global__ __launch_bounds__(64) void features_long_kernel(const float* __restri
     const float bi = in_bias[col], sc = in_scale[col];
     float* out = feat + (int64_t)segl * T * Kp;
     auto put = [&](int t, float v) {
-        const float y = (v + bi) * sc;
+        const float y = feat_affine(v, bi, sc);
         if (split_out) split_store(reinterpret_cast<_Float16*>(out + (int64_t)t * Kp), col, y);
         else out[(int64_t)t * Kp + col] = y;
     };

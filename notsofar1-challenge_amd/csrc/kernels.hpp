@@ -127,6 +127,9 @@ void stft_build_tables(float* host, int window = 0);   // window (0: hann, 1: sq
 // phase != nullptr: also the PHASE planes phase[(c * 257 + f) * row_ld + t] = css_phase_of(Re, Im) -- the angle the IPD
 // features are made of (feature.py:214-221), formed once per frame here instead of once per segment and microphone pair in
 // the feature kernel (a frame lies in two segments, microphone 0 in six pairs: 18 atan2 per feature element became 6 + 7/2).
+// PRECONDITION: x_stride is even and x 8-byte aligned (samples are read as float2); t_lo >= 0.  The spectrum leaves as float4
+// stores when row_ld % 4 == 0 and `out` is 16-byte aligned -- the decision looks at `out` ALONE, and the phase planes leave
+// through the same kind of store: `phase` must have the alignment of `out` modulo 16 bytes (every caller gives both the same).
 bool launch_stft_fft(const float* x, int64_t x_stride, int C, int64_t t_lo, int64_t t_hi, const float* tables, float* out,
                      int64_t row_ld, hipStream_t s, float* phase = nullptr);
 

@@ -139,11 +139,17 @@ __global__ __launch_bounds__(FFT_THREADS) void stft_fft_kernel(const float* __re
         if (f == 0) { re = z0.x + z0.y; im = 0.f; }
         else if (f == FFT_H) { re = z0.x - z0.y; im = 0.f; }
         else {
+            // W O in ONE stated form: this lambda is inlined into both store phases, and left to itself the compiler contracted
+            // w.x o.x - w.y o.y as fma(-w.y, o.y, fl(w.x o.x)) in the float4 phase and as fma(w.x, o.x, -fl(w.y o.y)) in the scalar
+            // one -- the same frame differed in the last bit of Re with the alignment of `out`
+            // (tests/test_hip_frontend_kernels.py).  The form below is the float4 phase's, the one every path has shipped with.
+#pragma clang fp contract(off)
             const float2 e = make_float2(0.5f * (z0.x + z1.x), 0.5f * (z0.y - z1.y));
             const float2 o = make_float2(0.5f * (z0.y + z1.y), 0.5f * (z1.x - z0.x));
-            const float2 wo = cmulf(w5, o);
-            re = e.x + wo.x;
-            im = e.y + wo.y;
+            const float wox = __builtin_fmaf(-w5.y, o.y, w5.x * o.x);
+            const float woy = __builtin_fmaf(w5.y, o.x, w5.x * o.y);
+            re = e.x + wox;
+            im = e.y + woy;
         }
     };
     float* oc = out + (int64_t)c * 2 * F * row_ld + t0;

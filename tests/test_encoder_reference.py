@@ -37,7 +37,7 @@ def test_header_library_and_binding_agree():
     declared = re.findall(r"\bint\s+(css_\w+)\s*\(", text)
     assert sorted(declared) == sorted(NAMES) == sorted(L.SIGNATURES_ENCODER)
     assert not set(L.SIGNATURES_ENCODER) & (set(L.SIGNATURES) | set(L.SIGNATURES_RATE) | set(L.SIGNATURES_PREVIEW) |
-                                            set(L.SIGNATURES_PREVIEW_HANDOFF))
+                                            set(L.SIGNATURES_PREVIEW_HANDOFF) | set(L.SIGNATURES_FRONTEND))
     main = open(os.path.join(ROOT, "include", "css_mi355.h")).read()
     assert len(L.SIGNATURES) == 85
     kinds = {"int32_t": C.c_int32, "int64_t": C.c_int64, "uint32_t": C.c_uint32, "float": C.c_float}
@@ -62,7 +62,10 @@ def test_header_library_and_binding_agree():
     assert C.sizeof(L.CssConvModuleDesc) == 40 and L.CssConvModuleDesc.x_floats.offset == 24
     assert C.sizeof(L.CssAttentionDesc) == 80 and L.CssAttentionDesc.canary.offset == 32 and L.CssAttentionDesc.x_floats.offset == 40
     deps = re.findall(r"^build(?:_asan)?/%\.o:.*$", open(os.path.join(CSRC, "Makefile")).read(), flags=re.M)
-    assert len(deps) == 2 and all("../../include/css_mi355_encoder.h" in d for d in deps)
+    assert len(deps) == 2 and all("../../include/css_mi355_encoder.h" in d and "../../include/css_mi355_frontend.h" in d for d in deps)
+    front = open(os.path.join(ROOT, "include", "css_mi355_frontend.h")).read()
+    for name in NAMES + tuple(DESCS):
+        assert not re.search(rf"\b{name}\b", front), f"{name} belongs to css_mi355_encoder.h alone"
 
 
 def test_null_handle_and_null_descriptor_are_refused():

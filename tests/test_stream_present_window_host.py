@@ -11,7 +11,7 @@ from conftest import ROOT, pkg
 CSRC = os.path.join(ROOT, "notsofar1-challenge_amd", "csrc")
 HEADER = "css_mi355_present_window.h"
 OTHERS = ("css_mi355.h", "css_mi355_rate.h", "css_mi355_preview.h", "css_mi355_preview_handoff.h", "css_mi355_encoder.h",
-          "css_mi355_window.h")
+          "css_mi355_window.h", "css_mi355_frontend.h")
 NAMES = ("css_stream_present_windows",)
 
 
@@ -32,7 +32,8 @@ def test_header_library_and_binding_agree():
     declared = re.findall(r"\bint\s+(css_\w+)\s*\(", text)
     assert sorted(declared) == sorted(NAMES) == sorted(L.SIGNATURES_PRESENT)
     assert not set(L.SIGNATURES_PRESENT) & (set(L.SIGNATURES) | set(L.SIGNATURES_RATE) | set(L.SIGNATURES_PREVIEW) |
-                                            set(L.SIGNATURES_PREVIEW_HANDOFF) | set(L.SIGNATURES_ENCODER) | set(L.SIGNATURES_WINDOW))
+                                            set(L.SIGNATURES_PREVIEW_HANDOFF) | set(L.SIGNATURES_ENCODER) | set(L.SIGNATURES_WINDOW) |
+                                            set(L.SIGNATURES_FRONTEND))
     others = [open(os.path.join(ROOT, "include", f)).read() for f in OTHERS]
     for name in NAMES + ("CssStreamPresentWindow", "CssStreamPresentItem"):
         for other in others:

@@ -13,7 +13,8 @@ from conftest import ROOT, pkg
 
 CSRC = os.path.join(ROOT, "notsofar1-challenge_amd", "csrc")
 HEADER = "css_mi355_window.h"
-OTHERS = ("css_mi355.h", "css_mi355_rate.h", "css_mi355_preview.h", "css_mi355_preview_handoff.h", "css_mi355_encoder.h")
+OTHERS = ("css_mi355.h", "css_mi355_rate.h", "css_mi355_preview.h", "css_mi355_preview_handoff.h", "css_mi355_encoder.h",
+          "css_mi355_frontend.h")
 NAMES = ("css_stream_window_open", "css_stream_window_range", "css_stream_windows")
 
 
@@ -29,7 +30,7 @@ def test_header_library_and_binding_agree():
     declared = re.findall(r"\bint\s+(css_\w+)\s*\(", text)
     assert sorted(declared) == sorted(NAMES) == sorted(L.SIGNATURES_WINDOW)
     assert not set(L.SIGNATURES_WINDOW) & (set(L.SIGNATURES) | set(L.SIGNATURES_RATE) | set(L.SIGNATURES_PREVIEW) |
-                                           set(L.SIGNATURES_PREVIEW_HANDOFF) | set(L.SIGNATURES_ENCODER))
+                                           set(L.SIGNATURES_PREVIEW_HANDOFF) | set(L.SIGNATURES_ENCODER) | set(L.SIGNATURES_FRONTEND))
     others = [open(os.path.join(ROOT, "include", f)).read() for f in OTHERS]
     kinds = {"css_handle_t": C.c_void_p, "int32_t": C.c_int32, "int64_t": C.c_int64}
     for name in NAMES + ("CssStreamWindow", "CSS_WINDOW_F32", "CSS_WINDOW_F16", "CSS_WINDOW_TABLE", "CSS_WINDOW_MAX_WIDTH"):
