@@ -324,7 +324,6 @@ struct css_ctx : SessState {
     FeatOpts feat_opts{};   // css_set_feature_options (css_create: the shipped configuration)
     void* streams[CSS_MAX_STREAMS] = {};   // css_stream_open: open streams (api_stream.hip StreamState), by id
     void* handoff = nullptr;   // api_stream.hip: what the hand-off of streams shares on this handle (HandoffCtx), made on first use
-    DevBuf window_max;     // api_stream.hip: the maxima of one css_stream_windows call, one float per item
     DevBuf stream_masks;   // api_stream.hip: the mask head's output for one estimator batch of streamed segments (never `masks`:
                            // the handle's own session keeps its bits between two pushes)
 

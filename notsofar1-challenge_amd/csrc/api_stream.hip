@@ -34,7 +34,8 @@
 //
 // A hand-off stream with a frame history (css_stream_window_open, include/css_mi355_window.h) also keeps its last raw
 // log-mel frames in a ring on the device: the mel launch of a committed round leaves them there.  css_stream_windows turns spans
-// of them into Whisper encoder inputs in the caller's device memory, one table launch per WINDOW_MULTI_MAX windows.
+// of them into Whisper encoder inputs in the caller's device memory, css_stream_present_windows spans that end in a preview's
+// provisional frames: one kernel (handoff.hip stream_window_kernel), one table launch per WINDOW_MULTI_MAX windows (launch_windows).
 #include "api_ctx.hpp"
 #include "../../include/css_mi355_rate.h"
 #include "../../include/css_mi355_preview.h"
@@ -79,7 +80,7 @@ struct HandoffCtx {
     DevBuf tab, operand, spec, res, state;   // DFT matrix + both filterbanks; frame operand; spectra; a round's results; HandoffState per (id, k)
     DevBuf state_pv;                         // a preview's closing round writes its counts and maximum here, never into `state`
     std::vector<PinnedBuf> pinned;           // staging of round r of a call
-    DevBuf present; PinnedBuf present_pin;   // css_stream_present_windows: a PresentWindowOut per window of one call, and its staging
+    DevBuf present; PinnedBuf present_pin;   // css_stream_windows / css_stream_present_windows: a WindowOut per window of one call, and its staging
     int32_t launches = 0, products = 0;
     int64_t frames = 0;
 };
@@ -646,13 +647,79 @@ int check_stream_call(css_ctx* h, int32_t id, StreamState** out) {
     return CSS_OK;
 }
 
+// What opens every item of a grouped push or preview, item i of a call whose item k names stream id_of(k): the stream is open,
+// no queued session is outstanding, no earlier item names it, it has not finished.  -> CSS_OK and *out, or the code and *why.
+template <typename IdOf>
+int check_group_item(css_ctx* h, size_t i, IdOf id_of, StreamState** out, std::string* why) {
+    StreamState* s = get_stream(h, id_of(i));
+    if (!s) { *why = "no open stream with this id"; return CSS_ERR_INVALID_ARG; }
+    if (h->queued || !h->pending.empty()) {
+        *why = "queued sessions (css_run_enqueue*) are outstanding: css_wait before using a stream";
+        return CSS_ERR_STATE;
+    }
+    for (size_t k = 0; k < i; ++k)
+        if (id_of(k) == id_of(i)) { *why = "the stream is named twice in one call"; return CSS_ERR_INVALID_ARG; }
+    if (s->finished) { *why = "the stream has finished"; return CSS_ERR_STATE; }
+    *out = s;
+    return CSS_OK;
+}
+
+// What is wrong with a window request (CssStreamWindow, CssStreamPresentWindow) of a stream with the history `o`, or null.
+// first_frame: of a request that names its span (css_stream_windows); null where the device resolves it.  `o` is read only with
+// first_frame (either way the caller has refused a stream without a history before).
+template <typename W>
+const char* window_refusal(const css_ctx* h, const HandoffStream* o, const W& w, const int64_t* first_frame) {
+    if (w.speaker < 0 || w.speaker >= h->d.num_spks) return "speaker out of range";
+    if (w.dtype != CSS_WINDOW_F32 && w.dtype != CSS_WINDOW_F16) return "dtype is CSS_WINDOW_F32 or CSS_WINDOW_F16";
+    if (w.n_frames < 1 || w.width < w.n_frames || w.width > CSS_WINDOW_MAX_WIDTH) return "1 <= n_frames <= width <= 3000";
+    if (w.ld < w.width) return "ld < width";
+    if (first_frame) {
+        const int64_t J = o->m.J[(size_t)w.speaker], first = std::max<int64_t>(J - o->hist_frames, 0);
+        if (*first_frame < first || *first_frame > J - w.n_frames) return "frames outside the history (css_stream_window_range)";
+    }
+    const size_t el = w.dtype == CSS_WINDOW_F16 ? 2 : 4;
+    if (!w.out_dev || (uintptr_t)w.out_dev % el) return "out_dev is null or not aligned to its element size";
+    return nullptr;
+}
+
+// The history half of an accepted request's kernel item; the caller adds the span (J, and the provisional frames if it has any).
+template <typename W>
+WindowItem history_item(const HandoffStream* o, const W& w) {
+    WindowItem e{};
+    const int64_t H = o->hist_frames, nm = o->cfg.n_mels;
+    e.ring = (const float*)o->ring.p + w.speaker * nm * H;
+    e.fmax = (const float*)o->fmax.p + w.speaker * H;
+    e.out = w.out_dev;
+    e.hist = H; e.ld = w.ld;
+    e.n_frames = w.n_frames; e.width = w.width; e.n_mels = (int32_t)nm; e.f16 = w.dtype == CSS_WINDOW_F16 ? 1 : 0;
+    return e;
+}
+
+// The windows of one call on the handle's stream, WINDOW_MULTI_MAX per launch, and the download of what the kernel resolved: after
+// the call's synchronise (*res)[i] (page-locked) is window i's.  Every call that gets here ends in that synchronise, so one
+// staging serves them all.
+int launch_windows(css_ctx* h, std::vector<WindowItem>& w, int32_t* launches, const WindowOut** res) {
+    static_assert(WINDOW_MULTI_MAX == CSS_WINDOW_TABLE, "the header states the table's size");
+    HandoffCtx* c = handoff_ctx(h);   // (a stream with a frame history has the hand-off on)
+    const size_t bytes = w.size() * sizeof(WindowOut);
+    int rc;
+    if ((rc = ensure(h, c->present, bytes)) != CSS_OK) return rc;
+    if (c->present_pin.cap < bytes) HIPCHK(h, c->present_pin.alloc(bytes));
+    for (size_t i = 0; i < w.size(); ++i) w[i].res = (WindowOut*)c->present.p + i;
+    for (size_t i0 = 0; i0 < w.size(); i0 += WINDOW_MULTI_MAX, ++*launches)
+        launch_stream_windows(w.data() + i0, (int)std::min<size_t>(WINDOW_MULTI_MAX, w.size() - i0), h->stream);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(c->present_pin.p, c->present.p, bytes, hipMemcpyDeviceToHost, h->stream));
+    *res = c->present_pin.as<WindowOut>();
+    return CSS_OK;
+}
+
 }  // namespace
 
 void stream_destroy_all(css_ctx* h) {
     for (int i = 0; i < CSS_MAX_STREAMS; ++i)
         if (h->streams[i]) { delete static_cast<StreamState*>(h->streams[i]); h->streams[i] = nullptr; }
     h->stream_masks.reset();
-    h->window_max.reset();
     delete handoff_ctx(h);
     h->handoff = nullptr;
 }
@@ -773,13 +840,10 @@ int push_items(css_ctx* h, const std::vector<PushItem>& items, bool pcm16, CssSt
         auto refuse = [&](int code, const std::string& msg) {
             return fail(h, code, "item " + std::to_string(i) + " (stream " + std::to_string(p.id) + "): " + msg);
         };
-        StreamState* s = get_stream(h, p.id);
-        if (!s) return refuse(CSS_ERR_INVALID_ARG, "no open stream with this id");
-        if (h->queued || !h->pending.empty())
-            return refuse(CSS_ERR_STATE, "queued sessions (css_run_enqueue*) are outstanding: css_wait before using a stream");
-        for (size_t k = 0; k < i; ++k)
-            if (items[k].id == p.id) return refuse(CSS_ERR_INVALID_ARG, "the stream is named twice in one call");
-        if (s->finished) return refuse(CSS_ERR_STATE, "the stream has finished");
+        StreamState* s = nullptr;
+        std::string why;
+        const int irc = check_group_item(h, i, [&](size_t k) { return items[k].id; }, &s, &why);
+        if (irc != CSS_OK) return refuse(irc, why);
         const void* src = pcm16 ? (const void*)p.i16 : (const void*)p.f32;
         if (p.n_samples < 0 || (p.n_samples > 0 && !src)) return refuse(CSS_ERR_INVALID_ARG, "bad argument");
         bool planar = false;
@@ -799,7 +863,6 @@ int push_items(css_ctx* h, const std::vector<PushItem>& items, bool pcm16, CssSt
             return refuse(CSS_ERR_INVALID_ARG, "output capacity too small for the samples this push finalises");
         if (zero_weight_frames(s, s->t_st, segments_done(frames_of(n_after), s->T, s->hop) * s->hop))
             return refuse(CSS_ERR_ZERO_WEIGHT, "zero weights found. check hop_size, segment_size or m0, m1");
-        std::string why;
         const int hrc = check_handoff_call(h, s, n_after - s->n_pushed, &why);
         if (hrc != CSS_OK) return refuse(hrc, why);
         its[i] = Item{s, &p, 0, 0, 0, 0, s->t_g, planar, 0};
@@ -1021,17 +1084,12 @@ struct CloseJob {
 
 // What one css_stream_present_windows call launches: `total` windows over all jobs, `launches` kernel launches; after the call's
 // synchronise `res` (page-locked) holds the spans the kernel resolved, window CloseJob::win0 + w of a job at that index.
-struct PresentCall { size_t total = 0; int32_t launches = 0; const PresentWindowOut* res = nullptr; };
+struct PresentCall { size_t total = 0; int32_t launches = 0; const WindowOut* res = nullptr; };
 
 // The windows of a preview's jobs, behind the hand-off round `recs` on the handle's stream: the provisional frames, their maxima
 // and their counts are that round's results, which the next round overwrites.
 int present_windows(css_ctx* h, const std::vector<CloseJob>& jobs, const std::vector<HandoffRec>& recs, PresentCall* pc) {
-    HandoffCtx* c = handoff_ctx(h);
-    static_assert(WINDOW_MULTI_MAX == CSS_WINDOW_TABLE, "the header states the table's size");
-    int rc;
-    if ((rc = ensure(h, c->present, pc->total * sizeof(PresentWindowOut))) != CSS_OK) return rc;
-    if (c->present_pin.cap < pc->total * sizeof(PresentWindowOut)) HIPCHK(h, c->present_pin.alloc(pc->total * sizeof(PresentWindowOut)));
-    std::vector<PresentWindowItem> w(pc->total);
+    std::vector<WindowItem> w(pc->total);
     for (size_t i = 0; i < jobs.size(); ++i) {
         const CloseJob& j = jobs[i];
         if (!j.n_windows) continue;
@@ -1040,27 +1098,17 @@ int present_windows(css_ctx* h, const std::vector<CloseJob>& jobs, const std::ve
             if (x.s == j.s && x.item == (int)i) r = &x;
         if (!r || !r->pvmax_dev) return fail(h, CSS_ERR_STATE, "windows up to the present without the preview's hand-off round");
         const HandoffStream* o = j.s->ho.get();
-        const int64_t H = o->hist_frames, nm = o->cfg.n_mels;
         for (int32_t q = 0; q < j.n_windows; ++q) {
-            const CssStreamPresentWindow& p = j.windows[q];
-            PresentWindowItem& e = w[j.win0 + (size_t)q];
-            const int64_t k = p.speaker;
-            e.ring = (const float*)o->ring.p + k * nm * H;
-            e.fmax = (const float*)o->fmax.p + k * H;
-            e.pv = r->mel_dev + k * nm * r->mel_ld;
+            WindowItem& e = w[j.win0 + (size_t)q];
+            e = history_item(o, j.windows[q]);
+            const int64_t k = j.windows[q].speaker;
+            e.pv = r->mel_dev + k * o->cfg.n_mels * r->mel_ld;
             e.pvmax = r->pvmax_dev + k * r->mel_ld;
             e.n_new = r->n_new_dev + k;
-            e.out = p.out_dev; e.res = (PresentWindowOut*)c->present.p + j.win0 + (size_t)q;
-            e.hist = H; e.ld = p.ld; e.J = o->m.J[(size_t)k]; e.pv_ld = r->mel_ld;
-            e.n_frames = p.n_frames; e.width = p.width; e.n_mels = (int32_t)nm; e.f16 = p.dtype == CSS_WINDOW_F16 ? 1 : 0;
+            e.J = o->m.J[(size_t)k]; e.pv_ld = r->mel_ld;
         }
     }
-    for (size_t i0 = 0; i0 < pc->total; i0 += WINDOW_MULTI_MAX, ++pc->launches)
-        launch_stream_present_windows(w.data() + i0, (int)std::min<size_t>(WINDOW_MULTI_MAX, pc->total - i0), h->stream);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(c->present_pin.p, c->present.p, pc->total * sizeof(PresentWindowOut), hipMemcpyDeviceToHost, h->stream));
-    pc->res = c->present_pin.as<PresentWindowOut>();
-    return CSS_OK;
+    return launch_windows(h, w, &pc->launches, &pc->res);
 }
 
 int closing_pass(css_ctx* h, const std::vector<CloseJob>& jobs, bool commit, CssStreamGroupStats* stats, PresentCall* pc = nullptr) {
@@ -1212,19 +1260,15 @@ int preview_items(css_ctx* h, const std::vector<PreviewItem>& items, CssStreamGr
         auto refuse = [&](int code, const std::string& msg) {
             return fail(h, code, "item " + std::to_string(i) + " (stream " + std::to_string(p.id) + "): " + msg);
         };
-        StreamState* s = get_stream(h, p.id);
-        if (!s) return refuse(CSS_ERR_INVALID_ARG, "no open stream with this id");
-        if (h->queued || !h->pending.empty())
-            return refuse(CSS_ERR_STATE, "queued sessions (css_run_enqueue*) are outstanding: css_wait before using a stream");
-        for (int32_t k = 0; k < i; ++k)
-            if (items[(size_t)k].p->id == p.id) return refuse(CSS_ERR_INVALID_ARG, "the stream is named twice in one call");
-        if (s->finished) return refuse(CSS_ERR_STATE, "the stream has finished");
+        StreamState* s = nullptr;
+        std::string why;
+        const int irc = check_group_item(h, (size_t)i, [&](size_t k) { return items[k].p->id; }, &s, &why);
+        if (irc != CSS_OK) return refuse(irc, why);
         if (h->split) return refuse(CSS_ERR_STATE, "streams run in CSS_LINEAR_EXACT_F32 only");
         CloseJob j{s, CssPlan{}, closing_samples(s), p.out_host, p.cap, 0};
         if (CssStreamHandoffOut* ho = items[(size_t)i].ho) {
             if (!s->ho) return refuse(CSS_ERR_STATE, "the hand-off of this stream is off (css_stream_handoff_open)");
             if (!items[(size_t)i].first_frame) return refuse(CSS_ERR_INVALID_ARG, "hand-off outputs without first_frame");
-            std::string why;
             const int hrc = check_handoff_out(s, ho, -1, &why);   // a preview is a finish at this moment
             if (hrc != CSS_OK) return refuse(hrc, why);
             j.ho = ho; j.first_frame = items[(size_t)i].first_frame;
@@ -1235,14 +1279,8 @@ int preview_items(css_ctx* h, const std::vector<PreviewItem>& items, CssStreamGr
             if (it.n_windows < 0 || (it.n_windows > 0 && (!it.windows || !it.ho)))
                 return refuse(CSS_ERR_INVALID_ARG, "n_windows < 0, or windows without `windows` or without hand-off outputs (ph.ho)");
             for (int32_t q = 0; q < it.n_windows; ++q) {
-                const CssStreamPresentWindow& w = it.windows[q];
-                auto bad = [&](const std::string& msg) { return refuse(CSS_ERR_INVALID_ARG, "window " + std::to_string(q) + ": " + msg); };
-                if (w.speaker < 0 || w.speaker >= h->d.num_spks) return bad("speaker out of range");
-                if (w.dtype != CSS_WINDOW_F32 && w.dtype != CSS_WINDOW_F16) return bad("dtype is CSS_WINDOW_F32 or CSS_WINDOW_F16");
-                if (w.n_frames < 1 || w.width < w.n_frames || w.width > CSS_WINDOW_MAX_WIDTH) return bad("1 <= n_frames <= width <= 3000");
-                if (w.ld < w.width) return bad("ld < width");
-                const size_t el = w.dtype == CSS_WINDOW_F16 ? 2 : 4;
-                if (!w.out_dev || (uintptr_t)w.out_dev % el) return bad("out_dev is null or not aligned to its element size");
+                if (const char* bad = window_refusal(h, s->ho.get(), it.windows[q], nullptr))
+                    return refuse(CSS_ERR_INVALID_ARG, "window " + std::to_string(q) + ": " + bad);
             }
             j.windows = it.windows; j.n_windows = it.n_windows;
         }
@@ -1260,7 +1298,7 @@ int preview_items(css_ctx* h, const std::vector<PreviewItem>& items, CssStreamGr
     if (rc != CSS_OK) return rc;
     for (const CloseJob& j : jobs)
         for (int32_t q = 0; q < j.n_windows; ++q) {
-            const PresentWindowOut& r = pc.res[j.win0 + (size_t)q];
+            const WindowOut& r = pc.res[j.win0 + (size_t)q];
             CssStreamPresentWindow& w = j.windows[q];
             w.first_frame = r.first_frame; w.n_used = r.n_used; w.n_provisional = r.n_provisional;
             if (r.n_used > 0) w.window_max = r.window_max;
@@ -1521,7 +1559,6 @@ int css_stream_windows(css_handle_t h, CssStreamWindow* items, int32_t n_items, 
     if (n_items < 0 || (n_items > 0 && !items)) return fail(h, CSS_ERR_INVALID_ARG, "bad argument");
     if (h->queued || !h->pending.empty())
         return fail(h, CSS_ERR_STATE, "queued sessions (css_run_enqueue*) are outstanding: css_wait before using a stream");
-    static_assert(WINDOW_MULTI_MAX == CSS_WINDOW_TABLE, "the header states the table's size");
     std::vector<WindowItem> w((size_t)n_items);
     for (int32_t i = 0; i < n_items; ++i) {
         const CssStreamWindow& p = items[i];
@@ -1532,38 +1569,19 @@ int css_stream_windows(css_handle_t h, CssStreamWindow* items, int32_t n_items, 
         if (!s) return refuse("no open stream with this id");
         const HandoffStream* o = s->ho.get();
         if (!o || !o->hist_frames) return refuse("the stream has no frame history (css_stream_window_open)");
-        if (p.speaker < 0 || p.speaker >= h->d.num_spks) return refuse("speaker out of range");
-        if (p.dtype != CSS_WINDOW_F32 && p.dtype != CSS_WINDOW_F16) return refuse("dtype is CSS_WINDOW_F32 or CSS_WINDOW_F16");
-        if (p.n_frames < 1 || p.width < p.n_frames || p.width > CSS_WINDOW_MAX_WIDTH) return refuse("1 <= n_frames <= width <= 3000");
-        if (p.ld < p.width) return refuse("ld < width");
-        const int64_t J = o->m.J[(size_t)p.speaker], first = std::max<int64_t>(J - o->hist_frames, 0);
-        if (p.first_frame < first || p.first_frame > J - p.n_frames) return refuse("frames outside the history (css_stream_window_range)");
-        const size_t el = p.dtype == CSS_WINDOW_F16 ? 2 : 4;
-        if (!p.out_dev || (uintptr_t)p.out_dev % el) return refuse("out_dev is null or not aligned to its element size");
-        WindowItem& e = w[(size_t)i];
-        const int64_t H = o->hist_frames;
-        e.ring = (const float*)o->ring.p + (int64_t)p.speaker * o->cfg.n_mels * H;
-        e.fmax = (const float*)o->fmax.p + (int64_t)p.speaker * H;
-        e.out = p.out_dev; e.wmax = nullptr;
-        e.hist = H; e.ld = p.ld; e.slot0 = p.first_frame % H;
-        e.n_frames = p.n_frames; e.width = p.width; e.n_mels = o->cfg.n_mels; e.f16 = p.dtype == CSS_WINDOW_F16 ? 1 : 0;
+        if (const char* bad = window_refusal(h, o, p, &p.first_frame)) return refuse(bad);
+        w[(size_t)i] = history_item(o, p);
+        w[(size_t)i].J = p.first_frame + p.n_frames;   // (no provisional frames: the span the kernel resolves is the request's)
     }
     if (launches) *launches = 0;
     if (n_items == 0) return CSS_OK;
     HIPCHK(h, hipSetDevice(h->device));
-    int rc;
-    if ((rc = ensure(h, h->window_max, (size_t)n_items * sizeof(float))) != CSS_OK) return rc;
-    std::vector<float> mx((size_t)n_items);
     int32_t n_launch = 0;
-    for (int32_t i0 = 0; i0 < n_items; i0 += WINDOW_MULTI_MAX, ++n_launch) {
-        const int cnt = std::min<int32_t>(WINDOW_MULTI_MAX, n_items - i0);
-        for (int i = 0; i < cnt; ++i) w[(size_t)(i0 + i)].wmax = (float*)h->window_max.p + i0 + i;
-        launch_stream_windows(w.data() + i0, cnt, h->stream);
-    }
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(mx.data(), h->window_max.p, mx.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    const WindowOut* res = nullptr;
+    const int rc = launch_windows(h, w, &n_launch, &res);
+    if (rc != CSS_OK) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    for (int32_t i = 0; i < n_items; ++i) items[i].window_max = mx[(size_t)i];
+    for (int32_t i = 0; i < n_items; ++i) items[i].window_max = res[i].window_max;
     if (launches) *launches = n_launch;
     return CSS_OK;
 }

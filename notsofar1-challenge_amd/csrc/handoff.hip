@@ -246,6 +246,31 @@ __global__ __launch_bounds__(256) void handoff_append_kernel(HandoffAppendTable 
     }
 }
 
+// A frame's maximum over the bands, for the tile's frame of this thread's column: every thread reads back the values it stored
+// itself (the tile's own float32 results: MEL_TILE_FRAMES / MEL_TILE_ROWS are the tile's mapping of threads to outputs, so no
+// thread reads another's store), hands each to keep(m, v) and folds them; the row groups of a column gather in the tile's LDS once
+// every thread is done with it.  take: whether this thread's frame takes part.  The maximum is row 0's (ty == 0) result.
+template <typename Keep>
+__device__ __forceinline__ float handoff_frame_max(MelTilePw& pw, bool take, const float* __restrict__ mel, int64_t mel_ld, int n_mels, Keep keep) {
+    float (*fm)[MEL_TILE_FRAMES] = reinterpret_cast<float (*)[MEL_TILE_FRAMES]>(&pw[0][0]);   // [MEL_TILE_ROWS][MEL_TILE_FRAMES]
+    const int tj = threadIdx.x & (MEL_TILE_FRAMES - 1), ty = threadIdx.x / MEL_TILE_FRAMES;
+    float best = -INFINITY;
+    if (take)
+        for (int m = ty; m < n_mels; m += MEL_TILE_ROWS) {
+            const float v = mel[(int64_t)m * mel_ld];
+            keep(m, v);
+            best = fmaxf(best, v);
+        }
+    __syncthreads();   // (the tile's last reads of pw)
+    fm[ty][tj] = best;
+    __syncthreads();
+    if (ty == 0) {
+#pragma unroll
+        for (int i = 1; i < MEL_TILE_ROWS; ++i) best = fmaxf(best, fm[i][tj]);
+    }
+    return best;
+}
+
 // PVMAX: the launch of a preview's round that has an entry with HandoffMel::pvmax (windows up to the present); every other launch
 // is the <false> instance, which has no code for it.
 template <bool PVMAX>
@@ -257,63 +282,29 @@ __global__ __launch_bounds__(256) void handoff_mel_multi_kernel(HandoffMelTable 
     __shared__ MelTilePw pw;
     handoff_mel_tile(pw, spec, ld, e.row0 + (int64_t)k * e.rows, j0, nfr, e.w, e.n_mels, e.mel + (int64_t)k * e.n_mels * e.mel_ld, e.mel_ld,
                      &e.st[k].gmax);
+    const int64_t j = j0 + (threadIdx.x & (MEL_TILE_FRAMES - 1));
+    const bool row0 = threadIdx.x < MEL_TILE_FRAMES;
+    const float* mel = e.mel + (int64_t)k * e.n_mels * e.mel_ld + j;
     if constexpr (PVMAX) {
-        // The provisional frames stay where the tile wrote them; each frame's maximum over the bands goes next to them, gathered
-        // as below: every thread over the values it stored itself, the row groups of a column through the tile's LDS.
+        // The provisional frames stay where the tile wrote them; each frame's maximum over the bands goes next to them.
         if (e.pvmax) {
-            float (*fm)[MEL_TILE_FRAMES] = reinterpret_cast<float (*)[MEL_TILE_FRAMES]>(&pw[0][0]);
-            const int tj = threadIdx.x & (MEL_TILE_FRAMES - 1), ty = threadIdx.x / MEL_TILE_FRAMES;
-            const int64_t j = j0 + tj;
-            float best = -INFINITY;
-            if (j < nfr) {
-                const float* mel = e.mel + (int64_t)k * e.n_mels * e.mel_ld + j;
-                for (int m = ty; m < e.n_mels; m += MEL_TILE_ROWS) best = fmaxf(best, mel[(int64_t)m * e.mel_ld]);
-            }
-            __syncthreads();   // (the tile's last reads of pw)
-            fm[ty][tj] = best;
-            __syncthreads();
-            if (ty == 0 && j < nfr) {
-#pragma unroll
-                for (int i = 1; i < MEL_TILE_ROWS; ++i) best = fmaxf(best, fm[i][tj]);
-                e.pvmax[(int64_t)k * e.rows + j] = best;
-            }
+            const float best = handoff_frame_max(pw, j < nfr, mel, e.mel_ld, e.n_mels, [](int, float) {});
+            if (row0 && j < nfr) e.pvmax[(int64_t)k * e.rows + j] = best;
             return;
         }
     }
     if (!e.ring) return;
-    // The frame history: every thread reads back the values it stored itself (the tile's own float32 results: MEL_TILE_FRAMES /
-    // MEL_TILE_ROWS are the tile's mapping of threads to outputs, so no thread reads another's store) and leaves them in the
-    // ring with the frame's maximum over the bands, which the row groups of a column gather in the tile's LDS once every
-    // thread is done with it (a kernel without a history pays no LDS and no barrier for this).  The append kernel has moved st.J to the count after the round, so
-    // the round's frame j is frame J - n_new + j of the concatenation; only the last `hist` frames of a round are kept, so no
-    // two blocks of a launch write one slot.
-    float (*fm)[MEL_TILE_FRAMES] = reinterpret_cast<float (*)[MEL_TILE_FRAMES]>(&pw[0][0]);   // [MEL_TILE_ROWS][MEL_TILE_FRAMES]
-    const int tj = threadIdx.x & (MEL_TILE_FRAMES - 1), ty = threadIdx.x / MEL_TILE_FRAMES;
-    const int64_t j = j0 + tj;
+    // The frame history: the frames go into the ring with their maxima over the bands (a kernel without a history pays no LDS and
+    // no barrier for this).  The append kernel has moved st.J to the count after the round, so the round's frame j is frame
+    // J - n_new + j of the concatenation; only the last `hist` frames of a round are kept, so no two blocks of a launch write one slot.
     const bool keep = j < nfr && j >= nfr - e.hist;
-    int64_t slot = 0;
-    float best = -INFINITY;
-    if (keep) {
-        slot = (e.st[k].J - e.n_new[k] + j) % e.hist;
-        const float* mel = e.mel + (int64_t)k * e.n_mels * e.mel_ld + j;
-        float* ring = e.ring + (int64_t)k * e.n_mels * e.hist + slot;
-        for (int m = ty; m < e.n_mels; m += MEL_TILE_ROWS) {
-            const float v = mel[(int64_t)m * e.mel_ld];
-            ring[(int64_t)m * e.hist] = v;
-            best = fmaxf(best, v);
-        }
-    }
-    __syncthreads();   // (the tile's last reads of pw)
-    fm[ty][tj] = best;
-    __syncthreads();
-    if (ty == 0 && keep) {
-#pragma unroll
-        for (int i = 1; i < MEL_TILE_ROWS; ++i) best = fmaxf(best, fm[i][tj]);
-        e.fmax[(int64_t)k * e.hist + slot] = best;
-    }
+    const int64_t slot = keep ? (e.st[k].J - e.n_new[k] + j) % e.hist : 0;
+    float* ring = e.ring + (int64_t)k * e.n_mels * e.hist + slot;
+    const float best = handoff_frame_max(pw, keep, mel, e.mel_ld, e.n_mels, [&](int m, float v) { ring[(int64_t)m * e.hist] = v; });
+    if (row0 && keep) e.fmax[(int64_t)k * e.hist + slot] = best;
 }
 
-// ---- encoder windows out of the frame history -----------------------------------------------------------------------
+// ---- encoder windows: a span of the frame history, then a preview's provisional frames where the window reaches the present ----
 struct WindowTable { WindowItem e[WINDOW_MULTI_MAX]; };
 static_assert(sizeof(WindowTable) <= 4096, "the table travels by value as a kernel argument");
 
@@ -333,95 +324,6 @@ template <> struct WindowVec<__half> {
         *reinterpret_cast<uint4*>(p) = make_uint4(two(0), two(2), two(4), two(6));
     }
 };
-
-// One wave per band: consecutive lanes on consecutive columns.  The destination row is written with scalar stores up to its
-// first 16-byte boundary, 16-byte stores from there, scalar stores behind the last whole one; a 16-byte group reads the ring
-// with 16-byte loads where its frames lie in one stretch of the ring (at a 16-byte boundary: as they are; off it: the aligned
-// pieces around them), and frame by frame otherwise (the ring's wrap and its ends, the last frames before the padding).
-template <typename T>
-__device__ __forceinline__ void window_row(const WindowItem& e, const float* __restrict__ src, T* __restrict__ dst, float lo, float fill,
-                                           int lane) {
-    constexpr int V = WindowVec<T>::V;
-    auto norm = [&](float raw) { return (fmaxf(raw, lo) + 4.0f) * 0.25f; };
-    auto one = [&](int c) {
-        if (c >= e.n_frames) return fill;
-        int64_t s = e.slot0 + c;
-        if (s >= e.hist) s -= e.hist;
-        return norm(src[s]);
-    };
-    const int head = min((int)(((16 - ((uintptr_t)dst & 15)) & 15) / sizeof(T)), e.width);
-    const int nvec = (e.width - head) / V, tail = head + nvec * V;
-    for (int c = lane; c < head; c += 64) WindowVec<T>::store(dst + c, one(c));
-    for (int c = tail + lane; c < e.width; c += 64) WindowVec<T>::store(dst + c, one(c));
-    for (int g = lane; g < nvec; g += 64) {
-        const int c = head + g * V;
-        float v[V];
-        int64_t s = e.slot0 + c;
-        if (s >= e.hist) s -= e.hist;
-        const int d = (int)(((uintptr_t)(src + s) >> 2) & 3);   // floats past a 16-byte boundary
-        if (c + V <= e.n_frames && s + V <= e.hist && d == 0) {
-#pragma unroll
-            for (int i = 0; i < V; i += 4) {
-                const float4 q = *reinterpret_cast<const float4*>(src + s + i);
-                v[i] = norm(q.x); v[i + 1] = norm(q.y); v[i + 2] = norm(q.z); v[i + 3] = norm(q.w);
-            }
-        } else if (c + V <= e.n_frames && s >= d && s - d + V + 4 <= e.hist) {
-            // a source that sits d floats off the destination's alignment: the 16-byte pieces that cover the group, all inside
-            // this band's row of the ring, and the group picked out of them (selects on constant positions: no scratch)
-            float b[V + 4];
-#pragma unroll
-            for (int i = 0; i < V + 4; i += 4) {
-                const float4 q = *reinterpret_cast<const float4*>(src + s - d + i);
-                b[i] = q.x; b[i + 1] = q.y; b[i + 2] = q.z; b[i + 3] = q.w;
-            }
-#pragma unroll
-            for (int i = 0; i < V; ++i) v[i] = norm(d == 1 ? b[i + 1] : d == 2 ? b[i + 2] : b[i + 3]);
-        } else {
-#pragma unroll
-            for (int i = 0; i < V; ++i) v[i] = one(c + i);
-        }
-        WindowVec<T>::store16(dst + c, v);
-    }
-}
-
-__global__ __launch_bounds__(256) void stream_window_kernel(WindowTable tab) {
-    const WindowItem& e = tab.e[blockIdx.z];
-    const int m0 = blockIdx.x * WINDOW_ROWS;
-    if (m0 >= e.n_mels) return;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // the window's maximum: over the per-frame maxima of its frames (a maximum is exact in any order)
-    __shared__ float wm[4];
-    float M = -INFINITY;
-    for (int c = tid; c < e.n_frames; c += 256) {
-        int64_t s = e.slot0 + c;
-        if (s >= e.hist) s -= e.hist;
-        M = fmaxf(M, e.fmax[s]);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) M = fmaxf(M, __shfl_xor(M, o));
-    if (lane == 0) wm[wave] = M;
-    __syncthreads();
-    M = fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]));
-    if (blockIdx.x == 0 && tid == 0) *e.wmax = M;
-    const float lo = M - 8.0f, fill = (fmaxf(-10.0f, lo) + 4.0f) * 0.25f;
-    for (int m = m0 + wave; m < e.n_mels && m < m0 + WINDOW_ROWS; m += 4) {
-        const float* src = e.ring + (int64_t)m * e.hist;
-        if (e.f16) window_row<__half>(e, src, (__half*)e.out + (int64_t)m * e.ld, lo, fill, lane);
-        else window_row<float>(e, src, (float*)e.out + (int64_t)m * e.ld, lo, fill, lane);
-    }
-}
-
-void launch_stream_windows(const WindowItem* e, int n, hipStream_t s) {
-    if (n <= 0) return;
-    WindowTable tab{};
-    int most = 1;
-    for (int i = 0; i < n; ++i) { tab.e[i] = e[i]; most = std::max(most, (int)e[i].n_mels); }
-    hipLaunchKernelGGL(stream_window_kernel, dim3((unsigned)((most + WINDOW_ROWS - 1) / WINDOW_ROWS), 1, n), dim3(256), 0, s, tab);
-}
-
-// ---- encoder windows that reach the present: the history, then a preview's provisional frames ---------------------------------
-struct PresentWindowTable { PresentWindowItem e[WINDOW_MULTI_MAX]; };
-static_assert(sizeof(PresentWindowTable) <= 4096, "the table travels by value as a kernel argument");
 
 // Frames s .. s + V - 1 of one band's row of `len` floats (the caller has s + V <= len) through 16-byte loads: as they are at a
 // 16-byte boundary; off it, the aligned pieces around them where those lie inside the row (selects on constant positions: no
@@ -453,14 +355,16 @@ __device__ __forceinline__ bool window_load16(const float* __restrict__ row, int
 
 // The span as the block resolved it: columns [0, n_ring) are the ring's slots slot0 .. (wrapping at hist), columns
 // [n_ring, used) the provisional frames p0 .., the rest padding.
-struct PresentSpan { int64_t slot0; int n_ring, used, p0; };
+struct WindowSpan { int64_t slot0; int n_ring, used, p0; };
 
-// window_row with two sources.  A 16-byte group that lies in one stretch of the ring, or wholly in the provisional frames, is
-// read with 16-byte loads inside that source; the ring's wrap, the seam between the sources and the last frames before the
-// padding are taken frame by frame.
+// One wave per band: consecutive lanes on consecutive columns.  The destination row is written with scalar stores up to its
+// first 16-byte boundary, 16-byte stores from there, scalar stores behind the last whole one.  A 16-byte group that lies in one
+// stretch of the ring, or wholly in the provisional frames, is read with 16-byte loads inside that source; the ring's wrap, the
+// seam between the sources and the last frames before the padding are taken frame by frame.  (A window out of the history alone
+// has n_ring == used: no column is provisional.)
 template <typename T>
-__device__ __forceinline__ void present_window_row(const PresentWindowItem& e, const PresentSpan& sp, const float* __restrict__ ring,
-                                                   const float* __restrict__ pv, T* __restrict__ dst, float lo, float fill, int lane) {
+__device__ __forceinline__ void window_row(const WindowItem& e, const WindowSpan& sp, const float* __restrict__ ring,
+                                           const float* __restrict__ pv, T* __restrict__ dst, float lo, float fill, int lane) {
     constexpr int V = WindowVec<T>::V;
     auto norm = [&](float raw) { return (fmaxf(raw, lo) + 4.0f) * 0.25f; };
     auto one = [&](int c) {
@@ -496,16 +400,16 @@ __device__ __forceinline__ void present_window_row(const PresentWindowItem& e, c
     }
 }
 
-__global__ __launch_bounds__(256) void stream_present_window_kernel(PresentWindowTable tab) {
-    const PresentWindowItem& e = tab.e[blockIdx.z];
+__global__ __launch_bounds__(256) void stream_window_kernel(WindowTable tab) {
+    const WindowItem& e = tab.e[blockIdx.z];
     const int m0 = blockIdx.x * WINDOW_ROWS;
     if (m0 >= e.n_mels) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // the span: P provisional frames behind the J final ones, of which the ring holds [R, J)
-    const int64_t n_new = *e.n_new;
+    const int64_t n_new = e.n_new ? *e.n_new : 0;
     const int64_t P = n_new < e.pv_ld ? n_new : e.pv_ld;
     const int64_t E = e.J + P, R = e.J > e.hist ? e.J - e.hist : 0, a = E - e.n_frames > R ? E - e.n_frames : R;
-    PresentSpan sp;
+    WindowSpan sp;
     sp.used = (int)(E - a);
     const int n_prov = sp.used < P ? sp.used : (int)P;
     sp.n_ring = sp.used - n_prov;
@@ -539,17 +443,17 @@ __global__ __launch_bounds__(256) void stream_present_window_kernel(PresentWindo
     for (int m = m0 + wave; m < e.n_mels && m < m0 + WINDOW_ROWS; m += 4) {
         const float* ring = e.ring + (int64_t)m * e.hist;
         const float* pv = e.pv + (int64_t)m * e.pv_ld;
-        if (e.f16) present_window_row<__half>(e, sp, ring, pv, (__half*)e.out + (int64_t)m * e.ld, lo, fill, lane);
-        else present_window_row<float>(e, sp, ring, pv, (float*)e.out + (int64_t)m * e.ld, lo, fill, lane);
+        if (e.f16) window_row<__half>(e, sp, ring, pv, (__half*)e.out + (int64_t)m * e.ld, lo, fill, lane);
+        else window_row<float>(e, sp, ring, pv, (float*)e.out + (int64_t)m * e.ld, lo, fill, lane);
     }
 }
 
-void launch_stream_present_windows(const PresentWindowItem* e, int n, hipStream_t s) {
+void launch_stream_windows(const WindowItem* e, int n, hipStream_t s) {
     if (n <= 0) return;
-    PresentWindowTable tab{};
+    WindowTable tab{};
     int most = 1;
     for (int i = 0; i < n; ++i) { tab.e[i] = e[i]; most = std::max(most, (int)e[i].n_mels); }
-    hipLaunchKernelGGL(stream_present_window_kernel, dim3((unsigned)((most + WINDOW_ROWS - 1) / WINDOW_ROWS), 1, n), dim3(256), 0, s, tab);
+    hipLaunchKernelGGL(stream_window_kernel, dim3((unsigned)((most + WINDOW_ROWS - 1) / WINDOW_ROWS), 1, n), dim3(256), 0, s, tab);
 }
 
 void launch_handoff_append_multi(const HandoffAppend* e, int n, float* operand, hipStream_t s) {

@@ -239,33 +239,27 @@ constexpr int HANDOFF_MULTI_MAX = 16;
 void launch_handoff_append_multi(const HandoffAppend* e, int n, float* operand, hipStream_t s);
 void launch_handoff_mel_multi(const HandoffMel* e, int n, int S, const float* spec, int64_t ld, hipStream_t s);
 
-// Whisper encoder windows out of a stream's frame history (include/css_mi355_window.h): frames [first, first + n_frames) of one
-// speaker's ring, clamped at their own maximum - 8, (x + 4) / 4, padded to `width` columns with the value a frame of digital
-// zeros takes, as float32 or float16 into the caller's device memory.  A table launch: blockIdx.z = window.
+// Whisper encoder windows (include/css_mi355_window.h, css_mi355_present_window.h): at most n_frames frames of one speaker counted
+// back from the end of a preview's provisional frames -- the ring's frames [a, J), then the last provisional ones -- clamped at their
+// own maximum - 8, (x + 4) / 4, padded to `width` columns with the value a frame of digital zeros takes, as float32 or float16 into
+// the caller's device memory.  How many frames the preview made (P = *n_new, at most pv_ld) is known on the device only, so the
+// kernel resolves the span itself: E = J + P, a = max(E - n_frames, max(J - hist, 0)), used = E - a, of which min(used, P) are
+// provisional; it leaves them in *res.  A table launch: blockIdx.z = window.
+// n_new == nullptr: no provisional frames (P = 0; pv and pvmax are never read, pv_ld is 0), a window out of the history alone:
+// frames [first, first + n_frames) with J := first + n_frames.  The host has checked max(J' - hist, 0) <= first and J <= J' for the
+// speaker's count J', so n_frames <= hist and J - hist <= first: a = max(J - n_frames, max(J - hist, 0)) = first, used = n_frames.
+struct WindowOut { int64_t first_frame; int32_t n_used, n_provisional; float window_max; int32_t pad_; };
 struct WindowItem {
     const float* ring; const float* fmax;               // the speaker's rows of the history: [n_mels][hist], [hist]
-    void* out; float* wmax;                             // out [n_mels][ld] of the dtype; the maximum the clamp used
-    int64_t hist, ld, slot0;                            // slot0 = first frame mod hist
+    const float* pv; const float* pvmax;                // the speaker's provisional frames [n_mels][pv_ld] and their maxima [pv_ld]
+    const int32_t* n_new;                               // the speaker's count of the preview's round (HandoffAppend::n_new + k)
+    void* out; WindowOut* res;                          // out [n_mels][ld] of the dtype; the span (window_max only where used > 0)
+    int64_t hist, ld, J, pv_ld;                         // J: frames the pushes returned for the speaker
     int32_t n_frames, width, n_mels, f16;
 };
 constexpr int WINDOW_MULTI_MAX = 32;                    // (CSS_WINDOW_TABLE of the header)
 constexpr int WINDOW_ROWS = 8;                          // mel bands per block
 void launch_stream_windows(const WindowItem* e, int n, hipStream_t s);   // one launch; n <= WINDOW_MULTI_MAX
-
-// Windows that reach the present (include/css_mi355_present_window.h): at most n_frames frames counted back from the end of a
-// preview's provisional frames -- the ring's frames [a, J), then the last provisional ones -- under the same rule.  How many
-// frames the preview made (P = *n_new, at most pv_ld) is known on the device only, so the kernel resolves the span itself:
-// E = J + P, a = max(E - n_frames, max(J - hist, 0)), used = E - a, of which min(used, P) are provisional; it leaves them in *res.
-struct PresentWindowOut { int64_t first_frame; int32_t n_used, n_provisional; float window_max; int32_t pad_; };
-struct PresentWindowItem {
-    const float* ring; const float* fmax;               // the speaker's rows of the history: [n_mels][hist], [hist]
-    const float* pv; const float* pvmax;                // the speaker's provisional frames [n_mels][pv_ld] and their maxima [pv_ld]
-    const int32_t* n_new;                               // the speaker's count of the preview's round (HandoffAppend::n_new + k)
-    void* out; PresentWindowOut* res;                   // out [n_mels][ld] of the dtype; the span (window_max only where used > 0)
-    int64_t hist, ld, J, pv_ld;                         // J: frames the pushes returned for the speaker
-    int32_t n_frames, width, n_mels, f16;
-};
-void launch_stream_present_windows(const PresentWindowItem* e, int n, hipStream_t s);   // one launch; n <= WINDOW_MULTI_MAX
 
 // ------------------------------------------------------------------------------------------------
 // loss.hip -- validation loss of the training loop (train.py:411 _calc_loss): S x S base-loss sums + the noise term

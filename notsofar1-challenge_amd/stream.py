@@ -518,24 +518,29 @@ class CssStreamGroup:
                     s._preview_handoff_take()
         return [got.get(id(s)) for s in self.streams]
 
-    def windows(self, requests, width: int = 3000, dtype: str = "float16", out=None):
-        """Many encoder inputs in ONE css_stream_windows: ``requests`` are (stream, k) or (stream, k, first_frame, n_frames) with
-        the defaults of ``CssStream.window`` -> a torch tensor [B, n_mels, width] on the handle's device (``out``, or a slice of a
-        caller's tensor, if given).  All streams of the requests hand off the same n_mels.  ``window_launches`` holds the
-        kernel launches of the call, and every named stream's ``window_max`` the maximum of its last request."""
-        reqs = [tuple(r) + (None,) * (4 - len(r)) for r in requests]
+    def _window_requests(self, method, requests, fields, width, dtype, out):
+        """what ``windows`` and ``present_windows`` (``method``) do first: the request tuples padded with None to ``fields``,
+        checked, and the tensor the call writes -> (reqs, width, out, ld)"""
+        reqs = [tuple(r) + (None,) * (fields - len(r)) for r in requests]
         if not reqs:
             raise ValueError("no window requests")
         for s, *_ in reqs:
             if s not in self.streams:
                 raise ValueError("a stream that is not in this group")
             if s._hcfg is None or s.window_history is None:
-                raise ValueError("windows() needs streams opened with handoff= and window_history=")
+                raise ValueError(f"{method}() needs streams opened with handoff= and window_history=")
         n_mels = int(reqs[0][0]._hcfg.n_mels)
         if any(int(s._hcfg.n_mels) != n_mels for s, *_ in reqs):
-            raise ValueError("the streams of one windows() call hand off the same n_mels")
+            raise ValueError(f"the streams of one {method}() call hand off the same n_mels")
         width = int(width)
-        out, ld = _window_out(self._h, len(reqs), n_mels, width, dtype, out)
+        return (reqs, width) + _window_out(self._h, len(reqs), n_mels, width, dtype, out)
+
+    def windows(self, requests, width: int = 3000, dtype: str = "float16", out=None):
+        """Many encoder inputs in ONE css_stream_windows: ``requests`` are (stream, k) or (stream, k, first_frame, n_frames) with
+        the defaults of ``CssStream.window`` -> a torch tensor [B, n_mels, width] on the handle's device (``out``, or a slice of a
+        caller's tensor, if given).  All streams of the requests hand off the same n_mels.  ``window_launches`` holds the
+        kernel launches of the call, and every named stream's ``window_max`` the maximum of its last request."""
+        reqs, width, out, ld = self._window_requests("windows", requests, 4, width, dtype, out)
         items = (_lib.CssStreamWindow * len(reqs))()
         el = out.element_size()
         for i, (it, (s, k, first_frame, n_frames)) in enumerate(zip(items, reqs)):
@@ -561,19 +566,7 @@ class CssStreamGroup:
         every window of a stream whose prefix ``css_run`` refuses (spans row (-1, 0, 0), ``preview_handoff`` None), is left
         unwritten with a NaN maximum.  Every named stream gets ``preview_handoff`` / ``preview_first_sample`` as
         ``preview(handoff=True)`` sets them, and ``present_span`` / ``window_max`` of its last request."""
-        reqs = [tuple(r) + (None,) * (3 - len(r)) for r in requests]
-        if not reqs:
-            raise ValueError("no window requests")
-        for s, *_ in reqs:
-            if s not in self.streams:
-                raise ValueError("a stream that is not in this group")
-            if s._hcfg is None or s.window_history is None:
-                raise ValueError("present_windows() needs streams opened with handoff= and window_history=")
-        n_mels = int(reqs[0][0]._hcfg.n_mels)
-        if any(int(s._hcfg.n_mels) != n_mels for s, *_ in reqs):
-            raise ValueError("the streams of one present_windows() call hand off the same n_mels")
-        width = int(width)
-        out, ld = _window_out(self._h, len(reqs), n_mels, width, dtype, out)
+        reqs, width, out, ld = self._window_requests("present_windows", requests, 3, width, dtype, out)
         el = out.element_size()
         part = [s for s in self.streams if any(r[0] is s for r in reqs)]
         items = (_lib.CssStreamPresentItem * len(part))()

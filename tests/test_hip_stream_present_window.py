@@ -356,7 +356,9 @@ def test_the_stream_does_not_move(model):
 def test_grouped(model):
     """Three streams at different phases -- one before its first accepted preview, one with window_history = 96, one with 3000
     -- and 70 windows in ONE call: 3 window launches, the hand-off's launches of css_stream_preview_handoff_many on the same
-    items, every window its single-stream call's; the refused stream's windows and out fields stay."""
+    items, every window its single-stream call's; the refused stream's windows and out fields stay.  Then, on the stream with 96
+    frames of history, css_stream_present_windows (3 windows), css_stream_windows (40: two launches) and the first again -- the
+    two calls share one result staging: after each, every window is whisper_window of the host's frames and every out field the rule's."""
     import torch
     S, L = pkg("stream"), pkg("_lib")
     hcfg = dict(n_mels=80, pad_frames=8, drop_silence=True)
@@ -369,9 +371,13 @@ def test_grouped(model):
     large = S.CssStream(sep, cfg, handoff=hcfg, window_history=3000)
     y = np.ascontiguousarray(np.roll(x, 48000, axis=0))
     group = S.CssStreamGroup([early, small, large])
+    acc = [np.zeros((80, 0), np.float32) for _ in range(3)]   # the frames `small` has handed off
     group.push([x[:20000], x[:32000], y[:32000]])
+    acc = _grow(acc, small.handoff)
     group.push([None, x[32000:64000], y[32000:64000]])
+    acc = _grow(acc, small.handoff)
     group.push([None, x[64000:100000], y[64000:96000]])
+    acc = _grow(acc, small.handoff)
     group.push([None, None, y[96000:150000]])
     widths = (3000, 200, 101)
     specs = {early: [(k, 40, 45, "float16") for k in range(3)] + [(0, 1, 1, "float32")],
@@ -416,6 +422,38 @@ def test_grouped(model):
     for i, (s, k, m) in enumerate(reqs):
         single = s.present_window(k, m, 200, "float16")
         assert np.array_equal(host[1 + i], single.cpu().numpy()) and tuple(spans[i]) == s.present_span and maxima[i] == np.float32(s.window_max)
+    # the calls alternate on one stream, with different counts
+    first, end = small.window_range()
+    assert [int(e) for e in end] == [a.shape[1] for a in acc]
+    live = [k for k in range(3) if end[k] > first[k]]
+    assert live
+    plain = []
+    for i in range(40):
+        k = live[i % len(live)]
+        f, n = int(first[k]), int(end[k] - first[k])
+        a = f + i * 7 % n
+        m = 1 + i * 5 % (f + n - a)
+        plain.append((k, a, m, m + 5 * (i & 1), ("float16", "float32")[i >> 1 & 1]))
+    three = [(k, 50 + 40 * k, 131, ("float16", "float32")[k & 1]) for k in range(3)]
+    for call in ("present", "plain", "present"):
+        if call == "present":
+            r = _present(h, [(small, three)], 80)
+            assert r.rc == L.CSS_OK and r.items[0].ph.p.status == L.CSS_OK and r.launches == 1 == -(-3 // L.WINDOW_TABLE)
+            for spec, w, t in zip(three, r.tabs[0], r.outs[0]):
+                _check(S, t, w, acc[spec[0]], small.preview_handoff.mel[spec[0]], 96, spec)
+            continue
+        items = (L.CssStreamWindow * 40)()
+        outs = [torch.full((80, width), SENTINEL, dtype=getattr(torch, dtype), device="cuda") for _, _, _, width, dtype in plain]
+        for it, t, (k, a, m, width, dtype) in zip(items, outs, plain):
+            it.id, it.speaker, it.first_frame, it.n_frames, it.width = small.id, k, a, m, width
+            it.dtype, it.out_dev, it.ld, it.window_max = L.WINDOW_DTYPES[dtype], t.data_ptr(), width, -7.0
+        torch.cuda.synchronize()
+        launches = C.c_int32(-7)
+        assert h.lib.css_stream_windows(h.h, items, 40, C.byref(launches)) == L.CSS_OK and launches.value == 2 == -(-40 // L.WINDOW_TABLE)
+        for it, t, (k, a, m, width, dtype) in zip(items, outs, plain):
+            raw = acc[k][:, a:a + m]
+            assert np.array_equal(t.cpu().numpy(), S.whisper_window(raw, width, dtype)), (k, a, m, width, dtype)
+            assert it.window_max == raw.max() and (it.first_frame, it.n_frames) == (a, m)
     for s in (early, small, large):
         s.close()
     sep.close()
