@@ -3,14 +3,19 @@
 memory to separated waveforms in page-locked host memory; a session's PCIe legs run under its neighbours' kernels, and
 consecutive sessions share mask-estimator batches (up to max_batch_segments segments per batch).
 
-    python examples/session_queue.py [n_sessions]"""
+    python examples/session_queue.py [n_sessions] [--logmel]
+
+--logmel: every session also hands Whisper its input (css_run_enqueue_handoff): the kept sample ranges and the normalised
+log-mel of each separated stream, computed on the GPU behind the session's waveforms; one session takes no waveforms at all."""
 import importlib, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
 pkg = lambda n: importlib.import_module("notsofar1_challenge_amd." + n)
 css, _lib, sepmod, weights, synth = (pkg(n) for n in ("css", "_lib", "separator", "weights", "synth"))
 
-n_sessions = int(sys.argv[1]) if len(sys.argv) > 1 else 8
+logmel = "--logmel" in sys.argv[1:]
+args = [a for a in sys.argv[1:] if a != "--logmel"]
+n_sessions = int(args[0]) if args else 8
 desc = weights.ModelDesc.mc_v1()                                     # a real deployment: separator.load_css_model(dir)
 state = weights.apply_golden_recipe(weights.portable_state_dict(desc, 0))
 sep = sepmod.HipSeparator(state, None, device=0, max_batch_segments=128)
@@ -39,6 +44,19 @@ audio = sum(p.shape[0] for p, _ in sessions) / 16000.0
 print(f"{n_sessions} sessions, {audio:.0f} s of 7-channel audio: queued {1e3 * queued:.1f} ms ({audio / queued:.0f} x real time), "
       f"one call per session {1e3 * sync:.1f} ms ({audio / sync:.0f} x real time); same bits: "
       f"{all(np.array_equal(v, r) for v, r in zip(views, refs))}")
+if logmel:
+    t0 = time.perf_counter()
+    got = [h.run_enqueue_handoff(pcm, run_cfg, None if k == 0 else out, n_mels=80, pad_frames=8, drop_silence=True)
+           for k, (pcm, out) in enumerate(sessions)]
+    h.wait()                                                         # waveforms, ranges and log-mel are valid now
+    handed = time.perf_counter() - t0
+    for k, (view, ho) in enumerate(got[:3]):
+        for spk in range(3):
+            r = ho.ranges[spk]                                       # [n, 2] sample ranges of the meeting, in order: the time map
+            kept = int((r[:, 1] - r[:, 0]).sum())                    # frame j of ho.mel[spk] starts at concatenated sample 160 j
+            print(f"  session {k} stream {spk}: {len(r)} ranges, {kept / 16000.0:.1f} s kept, log-mel {ho.mel[spk].shape}")
+    print(f"with the hand-off: {1e3 * handed:.1f} ms ({audio / handed:.0f} x real time); waveforms the same bits: "
+          f"{all(np.array_equal(v, r) for (v, _), r in list(zip(got, refs))[1:])}")
 if os.environ.get("DEBUG"):
     for k, (v, r) in enumerate(zip(views, refs)):
         bad = np.flatnonzero((v != r).any(axis=0))

@@ -110,6 +110,12 @@ class CssStreamHandoffOut(C.Structure):
                 ("raw_max", C.c_void_p), ("n_activity", C.c_int64), ("first_activity_frame", C.c_int64)]
 
 
+class CssSessionHandoffOut(C.Structure):
+    """include/css_mi355_session_handoff.h: the caller's arrays of a session's hand-off (all S streams)"""
+    _fields_ = [("mel_host", C.c_void_p), ("cap_frames", C.c_int64), ("ranges_host", C.c_void_p), ("cap_ranges", C.c_int32),
+                ("n_frames", C.c_void_p), ("n_ranges", C.c_void_p)]
+
+
 class CssStreamPreviewHandoff(C.Structure):
     _fields_ = [("p", CssStreamPreview), ("ho", C.POINTER(CssStreamHandoffOut)), ("first_frame", C.c_void_p)]
 
@@ -335,6 +341,18 @@ SIGNATURES_FRONTEND = {
     "css_synthesis_tail_host": (C.c_int, [_P, C.POINTER(CssSynthesisTailDesc), _P, _P]),
     "css_pcm_edges_host": (C.c_int, [_P, C.POINTER(CssPcmEdgesDesc), _P, _P, _P]),
 }
+# the entry points include/css_mi355_session_handoff.h declares (kept ranges and log-mel of all streams of a session, found and
+# computed on the device; queued sessions that hand off), the ninth table load() applies
+SIGNATURES_SESSION_HANDOFF = {
+    "css_session_handoff_bounds": (C.c_int, [C.POINTER(CssModelDesc), C.POINTER(CssRunCfg), C.POINTER(CssStreamHandoffCfg), C.c_int64,
+                                             C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    "css_handoff_logmel_all": (C.c_int, [_P, _P, C.c_int64, C.POINTER(CssStreamHandoffCfg), C.POINTER(CssSessionHandoffOut)]),
+    "css_run_enqueue_handoff": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.POINTER(CssRunCfg), _P, C.c_int64,
+                                          C.POINTER(CssStreamHandoffCfg), C.POINTER(CssSessionHandoffOut)]),
+    "css_run_enqueue_pcm16_handoff": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.POINTER(CssRunCfg), _P, C.c_int64, _P,
+                                                C.POINTER(CssStreamHandoffCfg), C.POINTER(CssSessionHandoffOut)]),
+}
+SESSION_SCAN_CHUNK = 1024                        # CSS_SESSION_SCAN_CHUNK: the keep-scan kernel's step, in gate frames / sample blocks
 RESAMPLE_TILE = 256                              # output samples per block of the two resampling kernels (resample.hip RS_TILE)
 
 _lib: Optional[C.CDLL] = None
@@ -379,7 +397,7 @@ def load() -> C.CDLL:
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_RATE.items()) + list(SIGNATURES_PREVIEW.items()) +
                               list(SIGNATURES_PREVIEW_HANDOFF.items()) + list(SIGNATURES_ENCODER.items()) +
                               list(SIGNATURES_WINDOW.items()) + list(SIGNATURES_PRESENT.items()) +
-                              list(SIGNATURES_FRONTEND.items())):
+                              list(SIGNATURES_FRONTEND.items()) + list(SIGNATURES_SESSION_HANDOFF.items())):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -502,6 +520,45 @@ def stream_handoff_bounds(desc, run_cfg: RunCfg, hcfg: CssStreamHandoffCfg, n_sa
     if rc != CSS_OK:
         raise CssError(rc, "css_stream_handoff_bounds: bad configuration")
     return int(f.value), int(r.value), int(a.value)
+
+
+def session_handoff_bounds(desc, run_cfg: RunCfg, hcfg: CssStreamHandoffCfg, n_samples: int):
+    """css_session_handoff_bounds: (frames, ranges) per stream that suffice for the hand-off of a session of `n_samples`"""
+    f, r = C.c_int64(), C.c_int32()
+    rc = load().css_session_handoff_bounds(C.byref(make_desc(desc)), C.byref(run_cfg.c), C.byref(hcfg), int(n_samples), C.byref(f), C.byref(r))
+    if rc != CSS_OK:
+        raise CssError(rc, "css_session_handoff_bounds: bad configuration, or frames other than 512 / 256")
+    return int(f.value), int(r.value)
+
+
+class SessionHandoff:
+    """The arrays of one session's hand-off (css_mi355_session_handoff.h) and, once they are valid -- after wait() /
+    wait_sessions() for a queued session --, their trimmed views: ``mel[k]`` float32 [n_mels, n_frames[k]], ``ranges[k]`` int64
+    [n_ranges[k], 2] (the time map back to the meeting), ``n_frames``, ``n_ranges``.  pinned: page-locked arrays (what the queued
+    forms need).  cap_frames / cap_ranges: capacities beyond the bounds (tests)."""
+
+    def __init__(self, S: int, n_mels: int, frames: int, ranges: int, pinned: bool = True, fill=None):
+        make = pinned_empty if pinned else (lambda shape, dtype: np.empty(shape, dtype))
+        self.S, self.n_mels = int(S), int(n_mels)
+        self.mel_all = make((self.S, self.n_mels, max(int(frames), 1)), np.float32)
+        self.ranges_all = make((self.S, max(int(ranges), 1), 2), np.int64)
+        self.n_frames = make((self.S,), np.int64)
+        self.n_ranges = make((self.S,), np.int32)
+        if fill is not None:
+            self.mel_all[...] = fill
+            self.ranges_all[...] = int(fill)
+            self.n_frames[...] = int(fill)
+            self.n_ranges[...] = int(fill)
+        self.c = CssSessionHandoffOut(self.mel_all.ctypes.data, int(frames), self.ranges_all.ctypes.data, int(ranges),
+                                      self.n_frames.ctypes.data, self.n_ranges.ctypes.data)
+
+    @property
+    def mel(self):
+        return [self.mel_all[k, :, :int(self.n_frames[k])] for k in range(self.S)]
+
+    @property
+    def ranges(self):
+        return [self.ranges_all[k, :int(self.n_ranges[k])] for k in range(self.S)]
 
 
 def handoff_kept_ranges(act: np.ndarray, first_frame: int, n_known: int, pad_frames: int, a: int, b: int, n_out: int,
@@ -1066,6 +1123,64 @@ class Handle:
                                                   max_regions, C.byref(nreg)))
         del mel
         return flat[:n_mels * nfr.value].reshape(n_mels, nfr.value).copy(), regions[:nreg.value].copy()
+
+    def _session_handoff(self, cfg: RunCfg, n: int, n_mels, pad_frames, drop_silence, pinned=True):
+        hcfg = handoff_cfg(n_mels, pad_frames, drop_silence)
+        frames, ranges = session_handoff_bounds(self.desc, cfg, hcfg, n)
+        return hcfg, SessionHandoff(int(self.desc.num_spks), n_mels, frames, ranges, pinned=pinned)
+
+    def handoff_logmel_all(self, wav_ptr: int, wav_ld: int, n_mels: int = 80, pad_frames: int = 8, drop_silence: bool = True,
+                           out: Optional[SessionHandoff] = None) -> SessionHandoff:
+        """After run_device: kept ranges and log-mel of ALL streams (css_handoff_logmel_all) -- per stream, bit for bit,
+        what handoff_logmel returns, with the ranges found on the device.  `out`: a SessionHandoff to fill (any memory)."""
+        hcfg = handoff_cfg(n_mels, pad_frames, drop_silence)
+        if out is None:
+            p = self.get_plan()
+            TL = int(p.mix_frames)
+            out = SessionHandoff(int(self.desc.num_spks), n_mels, int(p.n_out) // 160,
+                                 (TL - 1) // (2 * int(pad_frames) + 3) + 1 if drop_silence else 1, pinned=False)
+        check(self.h, self.lib.css_handoff_logmel_all(self.h, C.c_void_p(wav_ptr), int(wav_ld), C.byref(hcfg), C.byref(out.c)))
+        return out
+
+    def run_enqueue_handoff(self, pcm: np.ndarray, cfg: RunCfg, out: Optional[np.ndarray], n_mels: int = 80, pad_frames: int = 8,
+                            drop_silence: bool = True, handoff: Optional[SessionHandoff] = None):
+        """run_enqueue plus the hand-off to Whisper (css_run_enqueue_handoff): behind the session's waveforms, on the device,
+        the kept ranges and the normalised log-mel of all streams.  `out` None: log-mel only, no waveform leaves the GPU.
+        Returns (view of `out` or None, SessionHandoff); both are valid after wait() / wait_sessions().  Not in "split_f16"."""
+        assert pcm.dtype == np.float32 and pcm.flags.c_contiguous and pcm.ndim == 2
+        n, c = pcm.shape
+        p = plan(self.desc, cfg, n)
+        if out is not None:
+            assert out.dtype == np.float32 and out.ndim == 2 and out.shape[0] == self.desc.num_spks and out.shape[1] >= p.n_out \
+                and out.strides[1] == 4
+        hcfg = handoff_cfg(n_mels, pad_frames, drop_silence)
+        ho = handoff if handoff is not None else self._session_handoff(cfg, n, n_mels, pad_frames, drop_silence)[1]
+        check(self.h, self.lib.css_run_enqueue_handoff(self.h, _np_ptr(pcm), n, c, C.byref(cfg.c), None if out is None else _np_ptr(out),
+                                                       0 if out is None else out.strides[0] // 4, C.byref(hcfg), C.byref(ho.c)))
+        self._queued_keep = getattr(self, "_queued_keep", []) + [(pcm, out, cfg, ho)]
+        return (None if out is None else out[:, :p.n_out]), ho
+
+    def run_enqueue_pcm16_handoff(self, planes, cfg: RunCfg, out16: np.ndarray, peaks: Optional[np.ndarray] = None, n_mels: int = 80,
+                                  pad_frames: int = 8, drop_silence: bool = True, handoff: Optional[SessionHandoff] = None):
+        """run_enqueue_pcm16 plus the hand-off (css_run_enqueue_pcm16_handoff): the log-mel is that of the float waveforms before
+        peak normalisation, i.e. what handoff_logmel sees.  Returns (view of `out16`, SessionHandoff)."""
+        n = planes[0].shape[0]
+        for p in planes:
+            assert p.dtype == np.int16 and p.ndim == 1 and p.shape[0] == n and p.flags.c_contiguous
+        c = len(planes)
+        pl = plan(self.desc, cfg, n)
+        S = int(self.desc.num_spks)
+        assert out16.dtype == np.int16 and out16.ndim == 2 and out16.shape[0] == S and out16.shape[1] >= pl.n_out and out16.strides[1] == 2
+        assert peaks is None or (peaks.dtype == np.float32 and peaks.shape == (S,) and peaks.flags.c_contiguous)
+        ptrs = (C.c_void_p * c)(*[p.ctypes.data for p in planes])
+        hcfg = handoff_cfg(n_mels, pad_frames, drop_silence)
+        ho = handoff if handoff is not None else self._session_handoff(cfg, n, n_mels, pad_frames, drop_silence)[1]
+        check(self.h, self.lib.css_run_enqueue_pcm16_handoff(self.h, ptrs, n, c, C.byref(cfg.c), out16.ctypes.data_as(C.c_void_p),
+                                                             out16.strides[0] // 2,
+                                                             peaks.ctypes.data_as(C.c_void_p) if peaks is not None else None,
+                                                             C.byref(hcfg), C.byref(ho.c)))
+        self._queued_keep = getattr(self, "_queued_keep", []) + [(planes, out16, peaks, cfg, ho)]
+        return out16[:, :pl.n_out], ho
 
     def resample(self, x, input_rate: int, fs: int = 16000) -> np.ndarray:
         """A recording at `input_rate` -> float32 [n_out, C] at `fs` on the device (css_resample_host): the samples a stream opened

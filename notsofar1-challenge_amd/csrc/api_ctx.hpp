@@ -140,7 +140,18 @@ struct SessState {
     int64_t mask_ld_v = 0;
 };
 
-// Where the samples of a pass come from and where its result goes (exactly one source, exactly one sink).
+// What css_run_enqueue_handoff / css_run_enqueue_pcm16_handoff ask for beside the waveforms (api_session_handoff.hip): the
+// caller's page-locked arrays by their DEVICE addresses -- the kernels of the hand-off store into them.
+struct SessHandoffReq {
+    bool on = false;
+    CssStreamHandoffCfg cfg{};
+    float* mel = nullptr; int64_t cap_frames = 0;       // [S][n_mels][cap_frames]
+    int64_t* ranges = nullptr; int32_t cap_ranges = 0;  // [S][cap_ranges][2]
+    int64_t* n_frames = nullptr; int32_t* n_ranges = nullptr;
+};
+
+// Where the samples of a pass come from and where its result goes (exactly one source; one sink, or -- a queued session that
+// only hands off -- none).
 struct RunIo {
     const float* pcm_host = nullptr;             // [n][C] float32 in host memory   (css_run)
     const float* pcm_dev = nullptr;              // [n][C] float32 in HBM           (css_run_device)
@@ -151,6 +162,7 @@ struct RunIo {
     float* peaks_host = nullptr;
     int64_t cap = 0;
     bool enqueue_only = false;                   // css_run_enqueue: return once everything is on the streams
+    const SessHandoffReq* ho = nullptr;          // a queued session that also hands off: behind the waveforms, on their stream
     // host to host: float PCM -> float waveforms (pcm, wav) or PCM16 planes -> PCM16 streams and their peaks (planes, wav16, peaks)
     static RunIo host(const float* pcm, const int16_t* const* planes, float* wav, int16_t* wav16, float* peaks, int64_t cap,
                       bool enqueue_only = false) {
@@ -196,6 +208,10 @@ struct css_ctx : SessState {
     // shared by the sessions of a handle: upload staging, the estimator's activations, the mask buffer, small tables
     std::vector<float> w_on_device;   // what segw holds (uploaded when a session's windows differ)
     DevBuf pcm_in, feat, hx, hu, ht, qkv, qkf, ctxb, masks, segw, stage, in16, pcm_f, enc, level, mel_tab, mel_work;
+    // the hand-off of queued sessions (api_session_handoff.hip): the DFT matrix with BOTH filterbanks (a queue may alternate
+    // between them, so neither is ever rebuilt), and one set of work buffers -- tails are serial on their stream
+    DevBuf sh_tab, sh_work;
+    PinnedBuf sh_pin;   // css_handoff_logmel_all into pageable arrays: the kernels' destination, copied out after the synchronise
     // sessions of a queued group other than the active one (run_group)
     static constexpr int MAX_GROUP = 8;
     std::vector<SessState> slots;
@@ -253,6 +269,7 @@ struct css_ctx : SessState {
         const float* pcm; int64_t n; int32_t n_ch; CssRunCfg cfg; float* wav; int64_t cap;
         std::vector<const int16_t*> planes; int16_t* wav16; float* peaks;
         float* wav_mapped;      // device address of the page-locked output (nullptr: pageable, or never looked up)
+        SessHandoffReq ho;      // css_run_enqueue*_handoff (wav may then be nullptr: log-mel only)
         std::vector<float> w;   // w_first | w_mid | w_last of cfg
         QueuedSession(const float* pcm_, const int16_t* const* planes_, int64_t n_, int32_t n_ch_, const CssRunCfg& c, float* wav_,
                       int16_t* wav16_, float* peaks_, int64_t cap_, float* mapped_)
@@ -274,7 +291,9 @@ struct css_ctx : SessState {
             return c;
         }
         RunIo io(bool enqueue_only) const {
-            return RunIo::host(pcm, pcm16() ? planes.data() : nullptr, wav, wav16, peaks, cap, enqueue_only);
+            RunIo io = RunIo::host(pcm, pcm16() ? planes.data() : nullptr, wav, wav16, peaks, cap, enqueue_only);
+            io.ho = ho.on ? &ho : nullptr;
+            return io;
         }
         // may the two share an estimator batch: one segmentation, the same three windows bit for bit
         bool groups_with(const QueuedSession& o) const {
@@ -421,6 +440,15 @@ int stream_open_count(const css_ctx* h);
 
 // ---- api_queue.hip
 hipEvent_t pool_event(css_ctx* h);
+void* mapped_host(const void* p);
+int enqueue_impl(css_handle_t h, const float* pcm_host, const int16_t* const* planes, int64_t n_samples, int32_t n_ch,
+                 const CssRunCfg* cfg, float* wav_host, int16_t* wav16, float* peaks, int64_t cap, const SessHandoffReq* ho = nullptr);
+
+// ---- api_session_handoff.hip
+// the handle's tables and work buffers for a session of this plan (before the first launch of the pass or group: ensure may wait)
+int session_handoff_prepare(css_ctx* h, const CssPlan& pl, const SessHandoffReq& r);
+// the five steps for the handle's current session on `st`, reading its gate bytes and the waveforms wav [S][wav_ld] in HBM
+int session_handoff_on(css_ctx* h, const float* wav, int64_t wav_ld, const SessHandoffReq& r, hipStream_t st);
 void reduce_profile(css_ctx* h);
 
 

@@ -441,6 +441,8 @@ static int run_pipeline(css_ctx* h, int64_t n, int32_t n_ch, const RunIo& io, bo
     HIPCHK(h, hipEventRecord(tail_done, h->tail_stream));
     HIPCHK(h, hipStreamWaitEvent(h->stream, tail_done, 0));
     if (io.wav16_host && (rc = encode_pcm16_out(h, (const float*)h->wav.p, io.wav16_host, io.cap, io.peaks_host, h->stream)) != CSS_OK) return rc;
+    // a queued session that also hands off (never an overlapping pass: run_once): its waveforms are whole in h->wav by now
+    if (io.ho && (rc = session_handoff_on(h, (const float*)h->wav.p, pl.n_out, *io.ho, h->stream)) != CSS_OK) return rc;
     // range check (split_f16.hpp): a split GEMM whose operand left the format's range raised this word
     HIPCHK(h, hipMemcpyAsync(h->range_flag_host.p, h->range_flag_dev.p, sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
     if (tails.out_done) HIPCHK(h, hipStreamWaitEvent(h->stream, tails.out_done, 0));
@@ -467,6 +469,9 @@ int run_once(css_handle_t h, int64_t n, int32_t n_ch, const CssRunCfg* cfg, cons
     // queued passes OVERLAP when the output is page-locked (see css_ctx::pass_no); otherwise they just queue up
     // (with the beamformer on the tail stream -- CSS_TUNE_MVDR_ON_LANES = 0 -- a tail also reads the spectra X, which the
     // next pass's transform overwrites: such passes queue up without overlapping)
+    // (a session that hands off keeps its waveforms in HBM and the hand-off's one set of work buffers to itself: alone in
+    // its pass -- more segments than a batch holds, pageable output -- it does not overlap with its neighbours)
+    if (io.ho) wav_mapped = nullptr;
     const bool piped = h->fft512 && io.enqueue_only && io.pcm_host && wav_mapped && h->tune[CSS_TUNE_MVDR_ON_LANES];
     if (!piped && !h->tune[CSS_TUNE_OUT_MAPPED]) wav_mapped = nullptr;
     if (io.enqueue_only && h->queued && h->last_piped != (int)piped) {
@@ -488,6 +493,7 @@ int run_once(css_handle_t h, int64_t n, int32_t n_ch, const CssRunCfg* cfg, cons
     if (rc != CSS_OK) return rc;
     const CssPlan& pl = h->plan;
     if (io.cap < pl.n_out) return fail(h, CSS_ERR_INVALID_ARG, "output buffer too small: need " + std::to_string(pl.n_out) + " samples per stream");
+    if (io.ho && (rc = session_handoff_prepare(h, pl, *io.ho)) != CSS_OK) return rc;
     h->ev_pool_used = 0;
     if (io.pcm_host) {
         const size_t need = ((size_t)n * n_ch * sizeof(float) + 255) / 256 * 256;
@@ -560,6 +566,7 @@ int run_group(css_handle_t h, const std::vector<css_ctx::QueuedSession>& grp) {
         pcm_off[(size_t)j] = (int64_t)pcm_bytes;
         pcm_bytes += ((size_t)q.n * q.n_ch * (q.pcm16() ? sizeof(int16_t) : sizeof(float)) + 255) / 256 * 256;
         if (q.wav16 && (rc = ensure(h, h->enc, (size_t)h->d.num_spks * h->plan.n_out * sizeof(int16_t) + 64)) != CSS_OK) return rc;
+        if (q.ho.on && (rc = session_handoff_prepare(h, h->plan, q.ho)) != CSS_OK) return rc;   // (before the group's first launch: ensure may wait)
     }
     const int T = grp[0].cfg.segment_frames, hop = grp[0].cfg.hop_frames;
     // a shared batch runs on at most TWO lanes: measured equal to three (profiles/r04_queue_group_ab.md), and it leaves the
@@ -699,7 +706,16 @@ int run_group(css_handle_t h, const std::vector<css_ctx::QueuedSession>& grp) {
         { CSS_PROF(CSS_PROF_OLA_STFT, ts); launch_ola_stft(sa, 0, TL, ts); }
         if (j == G - 1) hipEventRecord(h->ev[5], ts);
         istft_gemm_on(h, 0, TL, ts);
-        if (q.wav16) {
+        if (q.ho.on) {
+            // A session that also hands off: the waveforms stay in HBM -- never the zero-copy overlap-add -- and leave by copies
+            // (none with wav == nullptr); the hand-off follows on this stream, before the session counts as done.  h->wav is the
+            // session's own; the hand-off's work buffers are the handle's one set: tails are serial on this stream.
+            const int64_t n_out = h->plan.n_out;
+            wave_ola_on(h, 0, TL, 0, TL + 1, (float*)h->wav.p, n_out, 0, ts);
+            if (q.wav16 && (rc = encode_pcm16_out(h, (const float*)h->wav.p, q.wav16, q.cap, q.peaks, ts)) != CSS_OK) return rc;
+            if (q.wav && (rc = waveforms_out(h, (const float*)h->wav.p, n_out, q.wav, q.cap, 0, n_out, ts)) != CSS_OK) return rc;
+            if ((rc = session_handoff_on(h, (const float*)h->wav.p, n_out, q.ho, ts)) != CSS_OK) return rc;
+        } else if (q.wav16) {
             // css_run_pcm16's arithmetic, launch for launch
             const int64_t n_out = h->plan.n_out;
             if ((rc = ensure(h, h->wav, (size_t)S * n_out * sizeof(float))) != CSS_OK) return rc;
@@ -778,8 +794,8 @@ int css_run(css_handle_t h, const float* pcm_host, int64_t n_samples, int32_t n_
 
 // css_run_enqueue (float PCM -> float waveforms) and css_run_enqueue_pcm16 (PCM16 planes -> peak-normalised PCM16 streams): one
 // queue, one grouping rule; a session is one or the other (planes == nullptr: float)
-static int enqueue_impl(css_handle_t h, const float* pcm_host, const int16_t* const* planes, int64_t n_samples, int32_t n_ch,
-                        const CssRunCfg* cfg, float* wav_host, int16_t* wav16, float* peaks, int64_t cap) {
+int enqueue_impl(css_handle_t h, const float* pcm_host, const int16_t* const* planes, int64_t n_samples, int32_t n_ch,
+                 const CssRunCfg* cfg, float* wav_host, int16_t* wav16, float* peaks, int64_t cap, const SessHandoffReq* ho) {
     CssPlan pl{};
     int rc = check_run_args(h, n_samples, n_ch, cfg, &pl);
     if (rc != CSS_OK) return rc;
@@ -793,8 +809,11 @@ static int enqueue_impl(css_handle_t h, const float* pcm_host, const int16_t* co
     const void* out_key = wav16 ? (const void*)wav16 : (const void*)wav_host;
     if (h->mapped_key != out_key) { h->mapped_key = out_key; h->mapped_val = mapped_host(out_key); }
     float* mapped = (float*)h->mapped_val;   // (PCM16 output: only WHETHER it is page-locked matters -- it leaves by DMA)
-    const bool groupable = h->fft512 && h->group_limit > 1 && mapped && h->tune[CSS_TUNE_MVDR_ON_LANES] && pl.num_segments <= batch_cap(h, cfg->segment_frames);
+    // (a session that only hands off has no output buffer to be pageable)
+    const bool locked = mapped || (ho && !out_key);
+    const bool groupable = h->fft512 && h->group_limit > 1 && locked && h->tune[CSS_TUNE_MVDR_ON_LANES] && pl.num_segments <= batch_cap(h, cfg->segment_frames);
     css_ctx::QueuedSession q(pcm_host, planes, n_samples, n_ch, *cfg, wav_host, wav16, peaks, cap, mapped);
+    if (ho) q.ho = *ho;
     if (!h->fft512) {
         // Frame sizes other than 512 / 256 run the plain stage sequence to its end inside the call (run_once): nothing stays
         // queued, so css_wait would never look at the range word.  The pass therefore takes css_run's own rule here -- queued

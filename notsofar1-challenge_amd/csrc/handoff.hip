@@ -477,4 +477,175 @@ void launch_handoff_mel_multi(const HandoffMel* e, int n, int S, const float* sp
     }
 }
 
+// ---- queued sessions: ranges and counts found on the device ---------------------------------------------------------------------
+constexpr int SCAN_PER_THREAD = SESSION_SCAN_CHUNK / 256;
+static_assert(SCAN_PER_THREAD == 4, "a thread of the keep-scan owns one 32-bit word of gate bytes / four sample blocks");
+
+// Exclusive prefix sums of v over the block's 256 threads (x and y apiece), and the block's sums: a shuffle scan inside each
+// wave, the four waves' sums through LDS.  Every thread of the block calls it; sh is free again when it returns.
+__device__ __forceinline__ int2 session_block_scan(int2 v, int2 (&sh)[4], int2& total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int2 x = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int ax = __shfl_up(x.x, o), ay = __shfl_up(x.y, o);
+        if (lane >= o) { x.x += ax; x.y += ay; }
+    }
+    if (lane == 63) sh[wave] = x;
+    __syncthreads();
+    int2 before = make_int2(0, 0);
+    total = make_int2(0, 0);
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        if (w < wave) { before.x += sh[w].x; before.y += sh[w].y; }
+        total.x += sh[w].x; total.y += sh[w].y;
+    }
+    __syncthreads();
+    return make_int2(before.x + x.x - v.x, before.y + x.y - v.y);
+}
+
+// One block per speaker of the session.  Pass 1: psum[t] = active frames below t, for t = 0 .. TL, in chunks of
+// SESSION_SCAN_CHUNK frames with a carry; the chunks are laid over the 32-bit words of the gate row (a speaker's row starts at
+// k TL: any alignment), a thread takes one word as a whole where it lies inside the row and byte by byte at the row's two ends.
+// Pass 2: block q is kept iff psum says that a frame of [q - pad - 1, q + pad] is active; a prefix sum over the kept blocks and
+// over the run starts, again chunk by chunk, gives every run its index -- so the run table comes out in ascending order -- and
+// the samples kept before it.  A run's start and its end are written by the threads that own those blocks.
+__global__ __launch_bounds__(256) void session_keep_scan_kernel(SessionHandoff e) {
+    const int k = blockIdx.x, tid = threadIdx.x;
+    __shared__ int2 sh[4];
+    const int64_t TL = e.TL;
+    const uint8_t* __restrict__ gate = e.gate + (int64_t)k * TL;
+    int32_t* __restrict__ psum = e.psum + (int64_t)k * (TL + 1);
+    int2 total;
+    if (e.drop) {
+        const int64_t a = (int64_t)((uintptr_t)gate & 3);   // bytes between the word boundary below the row and the row
+        int carry = 0;
+        if (tid == 0) psum[0] = 0;
+        for (int64_t c0 = 0; c0 < a + TL; c0 += SESSION_SCAN_CHUNK) {
+            const int64_t u = c0 + (int64_t)tid * SCAN_PER_THREAD;   // this thread's word: row frames [u - a, u - a + 4)
+            int b[SCAN_PER_THREAD];
+            if (u >= a && u + SCAN_PER_THREAD <= a + TL) {
+                const uint32_t w = *reinterpret_cast<const uint32_t*>(gate + (u - a));
+#pragma unroll
+                for (int i = 0; i < SCAN_PER_THREAD; ++i) b[i] = ((w >> (8 * i)) & 0xffu) != 0;
+            } else {
+#pragma unroll
+                for (int i = 0; i < SCAN_PER_THREAD; ++i) {
+                    const int64_t t = u + i - a;
+                    b[i] = (t >= 0 && t < TL) ? gate[t] != 0 : 0;
+                }
+            }
+            const int2 ex = session_block_scan(make_int2(b[0] + b[1] + b[2] + b[3], 0), sh, total);
+            int run = carry + ex.x;
+#pragma unroll
+            for (int i = 0; i < SCAN_PER_THREAD; ++i) {
+                const int64_t t = u + i - a;
+                run += b[i];
+                if (t >= 0 && t < TL) psum[t + 1] = run;
+            }
+            carry += total.x;
+        }
+        __syncthreads();   // pass 2 reads what other threads of this block stored
+    }
+    const int64_t pad = e.pad;
+    auto kept = [&](int64_t q) -> int {   // blocks 0 .. TL; outside: not kept
+        if (q < 0 || q > TL) return 0;
+        if (!e.drop) return 1;
+        const int64_t lo = q - pad - 1 < 0 ? 0 : q - pad - 1, hi = q + pad < TL - 1 ? q + pad : TL - 1;
+        return psum[hi + 1] - psum[lo] > 0;
+    };
+    int64_t* __restrict__ regs = e.regs + (int64_t)k * e.cap_ranges * 2;
+    int64_t* __restrict__ offs = e.offs + (int64_t)k * e.cap_ranges;
+    int64_t* __restrict__ ranges_out = e.ranges_out + (int64_t)k * e.cap_ranges * 2;
+    int64_t blocks_before = 0;
+    int runs_before = 0;
+    for (int64_t c0 = 0; c0 <= TL; c0 += SESSION_SCAN_CHUNK) {
+        const int64_t q0 = c0 + (int64_t)tid * SCAN_PER_THREAD;
+        int f[SCAN_PER_THREAD + 2];   // kept flags of blocks q0 - 1 .. q0 + 4
+#pragma unroll
+        for (int i = 0; i < SCAN_PER_THREAD + 2; ++i) f[i] = kept(q0 - 1 + i);
+        int nk = 0, ns = 0;
+#pragma unroll
+        for (int i = 1; i <= SCAN_PER_THREAD; ++i) { nk += f[i]; ns += f[i] && !f[i - 1]; }
+        const int2 ex = session_block_scan(make_int2(nk, ns), sh, total);
+        int64_t blk = blocks_before + ex.x;
+        int r = runs_before + ex.y;   // runs that start below the block at hand
+#pragma unroll
+        for (int i = 1; i <= SCAN_PER_THREAD; ++i) {
+            const int64_t q = q0 + i - 1;
+            if (f[i] && !f[i - 1]) {
+                if (r < e.cap_ranges) { regs[2 * r] = q * 256; offs[r] = blk * 256; ranges_out[2 * r] = q * 256; }
+                ++r;
+            }
+            if (f[i] && !f[i + 1] && r - 1 < e.cap_ranges) { regs[2 * (r - 1) + 1] = (q + 1) * 256; ranges_out[2 * (r - 1) + 1] = (q + 1) * 256; }
+            blk += f[i];
+        }
+        blocks_before += total.x;
+        runs_before += total.y;
+    }
+    if (tid == 0) {
+        const int64_t n_act = blocks_before * 256, nfr = n_act / 160;   // whisper: 1 + n // hop frames, the last one dropped
+        e.st[k].A = n_act;
+        e.st[k].J = nfr;
+        e.st[k].gmax = (int)0x80808080;   // below every mapped finite value (launch_handoff_mel's reset)
+        e.n_new[k] = (int32_t)nfr;
+        e.n_ranges[k] = runs_before;
+        e.n_frames_out[k] = nfr;
+        e.n_ranges_out[k] = runs_before;
+    }
+}
+
+// handoff_gather_kernel's body for all speakers, the run count and the sample count read from what the keep-scan wrote:
+// operand floats [k per, (k + 1) per) are speaker k's; behind the last speaker's, 416 zeros (the product's last rows read them)
+__global__ __launch_bounds__(256) void session_gather_kernel(SessionHandoff e, const float* __restrict__ wavs, int64_t wav_ld,
+                                                             float* __restrict__ operand, int64_t per) {
+    const int k = blockIdx.y;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= per + (k == e.S - 1 ? MEL_K : 0)) return;
+    const int64_t n_act = e.st[k].A;
+    const int nr = e.n_ranges[k] < e.cap_ranges ? e.n_ranges[k] : e.cap_ranges;
+    const int64_t* __restrict__ regions = e.regs + (int64_t)k * e.cap_ranges * 2;
+    const int64_t* __restrict__ offs = e.offs + (int64_t)k * e.cap_ranges;
+    const float* __restrict__ wav = wavs + (int64_t)k * wav_ld;
+    float v = 0.f;
+    if (i < n_act + MEL_NFFT && n_act > 0 && nr > 0) {
+        int64_t j = i - MEL_NFFT / 2;
+        if (j < 0) j = -j;                                   // reflect (no edge repeat)
+        if (j >= n_act) j = 2 * (n_act - 1) - j;
+        j = j < 0 ? 0 : j;
+        int lo = 0, hi = nr - 1;
+        while (lo < hi) {                                    // last region with offs[r] <= j
+            const int mid = (lo + hi + 1) >> 1;
+            if (offs[mid] <= j) lo = mid; else hi = mid - 1;
+        }
+        v = wav[regions[2 * lo] + (j - offs[lo])];
+    }
+    operand[(int64_t)k * per + i] = v;
+}
+
+// handoff_norm_kernel's expression per speaker, over the columns below the speaker's frame count only
+__global__ __launch_bounds__(256) void session_norm_kernel(SessionHandoff e, const float* __restrict__ mel, int64_t mel_ld, int n_mels,
+                                                           float* __restrict__ out, int64_t out_ld) {
+    const int k = blockIdx.z, m = blockIdx.y;
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= e.st[k].J || j >= out_ld) return;
+    const int b = e.st[k].gmax;
+    const float mx = __int_as_float(b >= 0 ? b : b ^ 0x7fffffff);
+    const int64_t row = (int64_t)k * n_mels + m;
+    out[row * out_ld + j] = (fmaxf(mel[row * mel_ld + j], mx - 8.0f) + 4.0f) * 0.25f;
+}
+
+void launch_session_keep_scan(const SessionHandoff& e, hipStream_t s) {
+    hipLaunchKernelGGL(session_keep_scan_kernel, dim3(e.S), dim3(256), 0, s, e);
+}
+void launch_session_gather(const SessionHandoff& e, const float* wav, int64_t wav_ld, float* operand, int64_t rows, hipStream_t s) {
+    const int64_t per = rows * 160;
+    hipLaunchKernelGGL(session_gather_kernel, dim3((unsigned)((per + MEL_K + 255) / 256), e.S), dim3(256), 0, s, e, wav, wav_ld, operand, per);
+}
+void launch_session_norm(const SessionHandoff& e, const float* mel, int64_t mel_ld, int n_mels, float* out, int64_t out_ld, int64_t rows,
+                         hipStream_t s) {
+    if (rows <= 0) return;
+    hipLaunchKernelGGL(session_norm_kernel, dim3((unsigned)((rows + 255) / 256), n_mels, e.S), dim3(256), 0, s, e, mel, mel_ld, n_mels, out, out_ld);
+}
+
 }  // namespace css

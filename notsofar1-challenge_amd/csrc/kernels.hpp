@@ -239,6 +239,28 @@ constexpr int HANDOFF_MULTI_MAX = 16;
 void launch_handoff_append_multi(const HandoffAppend* e, int n, float* operand, hipStream_t s);
 void launch_handoff_mel_multi(const HandoffMel* e, int n, int S, const float* spec, int64_t ld, hipStream_t s);
 
+// The hand-off of QUEUED sessions (include/css_mi355_session_handoff.h, api_session_handoff.hip): all S streams of a finished
+// session, with no host decision between the steps.  The keep-scan kernel turns the gate bytes into the run table and the counts
+// in device memory (512 / 256 frames: block q of 256 samples is kept iff a frame of [q - pad - 1, q + pad] is active); the gather
+// and the normalisation read their counts from there and are launched over the host-known bounds; the product and the mel
+// kernel in between are the streams' (launch_gemm, launch_handoff_mel_multi with n_new = the frame counts).
+constexpr int SESSION_SCAN_CHUNK = 1024;      // gate frames / sample blocks per step of the keep-scan's prefix sums
+struct SessionHandoff {
+    const uint8_t* gate; int64_t TL;                    // the gate bytes [S][TL] (act_final)
+    int32_t pad, drop, S, cap_ranges;
+    int32_t* psum;                                      // scratch [S][TL + 1]: active frames below t
+    int64_t* regs; int64_t* offs;                       // out: run table [S][cap_ranges][2] sample ranges, [S][cap_ranges] samples before
+    HandoffState* st;                                   // out [S]: A = kept samples, J = frames, gmax = the reset maximum
+    int32_t* n_new; int32_t* n_ranges;                  // out [S] each: frames again (HandoffMel::n_new), runs
+    int64_t* ranges_out; int64_t* n_frames_out; int32_t* n_ranges_out;   // the caller's [S][cap_ranges][2], [S], [S] (device addresses)
+};
+void launch_session_keep_scan(const SessionHandoff& e, hipStream_t s);          // one block per speaker
+// operand rows [k rows, (k + 1) rows) of 160 floats: speaker k's kept samples, reflect-padded; zeros up to the operand's end + 416
+void launch_session_gather(const SessionHandoff& e, const float* wav, int64_t wav_ld, float* operand, int64_t rows, hipStream_t s);
+// out[(k n_mels + m) out_ld + j] = Whisper's normalisation of mel[(k n_mels + m) mel_ld + j], j < the speaker's frame count only
+void launch_session_norm(const SessionHandoff& e, const float* mel, int64_t mel_ld, int n_mels, float* out, int64_t out_ld, int64_t rows,
+                         hipStream_t s);
+
 // Whisper encoder windows (include/css_mi355_window.h, css_mi355_present_window.h): at most n_frames frames of one speaker counted
 // back from the end of a preview's provisional frames -- the ring's frames [a, J), then the last provisional ones -- clamped at their
 // own maximum - 8, (x + 4) / 4, padded to `width` columns with the value a frame of digital zeros takes, as float32 or float16 into
