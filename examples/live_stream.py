@@ -33,7 +33,13 @@ speaker, the last frames of the history followed by the preview's provisional fr
 (CssStream.present_window / CssStreamGroup.present_windows) -- an encoder input that ends at the microphone instead of up to
 3.6 s behind it, without the provisional frames going through the host.
 
+With --out-rate HZ [--out-pcm16] the final samples come back at the playback rate HZ, as float32 or (--out-pcm16) 16-bit PCM,
+resampled, scaled and rounded on the device (CssStream(output=dict(rate=HZ, dtype="int16"))): what a conference bridge that
+takes 48 kHz PCM16 and plays 48 kHz PCM16 needs, with nothing crossing PCIe at the model rate.  The previews stay float32 at
+the model rate.
+
     python examples/live_stream.py [--seconds 30] [--rooms N] [--logmel] [--pcm16] [--rate HZ] [--preview] [--window] [--present]
+                                   [--out-rate HZ] [--out-pcm16]
 """
 import argparse
 import os
@@ -123,7 +129,7 @@ def present_windows(group, streams, batch):
     return out, live
 
 
-def rooms(sep, n_rooms, seconds, fs, chunk, logmel=False, pcm16=False, rate=None, preview=False, window=False, present=False):
+def rooms(sep, n_rooms, seconds, fs, chunk, logmel=False, pcm16=False, rate=None, preview=False, window=False, present=False, output=None):
     mixes = [SYN.synth_meeting(seconds, 7, seed=1 + r)[0] for r in range(n_rooms)]
     if rate:
         mixes = [capture_at(m, fs, rate) for m in mixes]
@@ -131,7 +137,7 @@ def rooms(sep, n_rooms, seconds, fs, chunk, logmel=False, pcm16=False, rate=None
     elif pcm16:
         mixes = [capture(m) for m in mixes]
     streams = [STR.CssStream(sep, CSS.CssCfg(), fs=fs, num_channels=7, handoff=HANDOFF if logmel else None, input_rate=rate,
-                             window_history=3000 if window else None) for _ in mixes]
+                             window_history=3000 if window else None, output=output) for _ in mixes]
     group = STR.CssStreamGroup(streams)
     if window:
         import torch
@@ -166,7 +172,9 @@ def rooms(sep, n_rooms, seconds, fs, chunk, logmel=False, pcm16=False, rate=None
         for k, o in enumerate(s.finish()):
             room[k].append(o)
         s.close()
-    print("separated:", [[np.concatenate(x).shape[0] / fs for x in room] for room in outs], "s")
+    print("separated:", [[np.concatenate(x).shape[0] / (output["rate"] if output else fs) for x in room] for room in outs], "s")
+    if output:
+        print("samples the PCM16 clamp changed, per room:", [s_.output_clipped.tolist() for s_ in streams])
 
 
 def main():
@@ -179,15 +187,18 @@ def main():
     ap.add_argument("--rate", type=int, default=0, help="the source delivers int16 samples at this rate: CssStream(input_rate=HZ)")
     ap.add_argument("--window", action="store_true", help="after each tick, Whisper encoder windows per room and speaker in a torch tensor on the GPU")
     ap.add_argument("--present", action="store_true", help="after each tick, encoder windows that end at the present: the history and a preview's frames in one call")
+    ap.add_argument("--out-rate", type=int, default=0, help="the final samples come back at this rate, converted on the device: CssStream(output=dict(rate=HZ))")
+    ap.add_argument("--out-pcm16", action="store_true", help="... as int16 (gain 1, no peak normalisation); alone: int16 at the model rate")
     a = ap.parse_args()
     fs = 16000
     a.window = a.window or a.present
     a.logmel = a.logmel or a.window
     a.pcm16 = a.pcm16 or bool(a.rate)
+    output = dict(rate=a.out_rate or fs, dtype="int16" if a.out_pcm16 else "float32") if a.out_rate or a.out_pcm16 else None
     desc = W.ModelDesc.mc_v1()
     sep = SEP.HipSeparator(W.apply_golden_recipe(W.portable_state_dict(desc, 0)), None, device=0)
     if a.rooms > 1:
-        rooms(sep, a.rooms, a.seconds, fs, fs // 2, a.logmel, a.pcm16, a.rate or None, a.preview, a.window, a.present)
+        rooms(sep, a.rooms, a.seconds, fs, fs // 2, a.logmel, a.pcm16, a.rate or None, a.preview, a.window, a.present, output)
         sep.close()
         return
     mix = SYN.synth_meeting(a.seconds, 7, seed=1)[0]
@@ -199,7 +210,7 @@ def main():
     streams = [[] for _ in range(desc.num_spks)]
     mels = [[] for _ in range(desc.num_spks)]
     with STR.CssStream(sep, CSS.CssCfg(), fs=fs, num_channels=7, handoff=HANDOFF if a.logmel else None, input_rate=a.rate or None,
-                       window_history=3000 if a.window else None) as s:
+                       window_history=3000 if a.window else None, output=output) as s:
         if a.window:
             import torch
             batch = torch.empty((desc.num_spks, HANDOFF["n_mels"], 3000), dtype=torch.float16, device="cuda")
@@ -212,7 +223,7 @@ def main():
                 streams[k].append(o)
             inf = s.info()
             print(f"t={inf.n_pushed / fs:6.1f} s  final={inf.n_emitted / fs:6.1f} s  lag={(inf.n_pushed - inf.n_emitted) / fs:4.2f} s  "
-                  f"push {ms:6.2f} ms")
+                  f"push {ms:6.2f} ms" + (f"  {out[0].shape[0]} {out[0].dtype} samples at {output['rate']} Hz" if output else ""))
             if a.logmel:
                 print_handoff([s], fs)
                 for k, m in enumerate(s.handoff.mel):
@@ -240,7 +251,7 @@ def main():
                 windows = [STR.whisper_normalize(raw[:, i:i + 3000]) for i in range(0, raw.shape[1], 3000)]
                 print(f"speaker {k}: {raw.shape[1]} log-mel frames in {len(windows)} Whisper window(s)")
     wavs = [np.concatenate(x) for x in streams]
-    print("separated:", [w.shape[0] / fs for w in wavs], "s")
+    print("separated:", [w.shape[0] / (output["rate"] if output else fs) for w in wavs], "s")
     sep.close()
 
 

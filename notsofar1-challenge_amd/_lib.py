@@ -120,6 +120,17 @@ class CssStreamPreviewHandoff(C.Structure):
     _fields_ = [("p", CssStreamPreview), ("ho", C.POINTER(CssStreamHandoffOut)), ("first_frame", C.c_void_p)]
 
 
+class CssStreamOutputCfg(C.Structure):
+    """include/css_mi355_stream_out.h: the output format of a stream"""
+    _fields_ = [("up", C.c_int32), ("down", C.c_int32), ("pcm16", C.c_int32), ("gain", C.c_float)]
+
+
+class CssStreamOutputCounts(C.Structure):
+    _fields_ = [("n_written", C.c_int64), ("n_total", C.c_int64), ("n_clipped", C.c_void_p), ("peak_bits", C.c_void_p)]
+
+
+STREAM_OUTPUT_TABLE = 16                         # CSS_STREAM_OUTPUT_TABLE: streams per launch of the output kernel
+STREAM_OUTPUT_TILE = 1024                        # output samples per block of the output kernel (kernels.hpp SO_TILE)
 WINDOW_DTYPES = {"float32": 0, "float16": 1}     # CSS_WINDOW_F32, CSS_WINDOW_F16 (include/css_mi355_window.h)
 WINDOW_MAX_WIDTH = 3000                          # CSS_WINDOW_MAX_WIDTH
 WINDOW_TABLE = 32                                # CSS_WINDOW_TABLE: windows per launch of css_stream_windows
@@ -352,6 +363,15 @@ SIGNATURES_SESSION_HANDOFF = {
     "css_run_enqueue_pcm16_handoff": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.POINTER(CssRunCfg), _P, C.c_int64, _P,
                                                 C.POINTER(CssStreamHandoffCfg), C.POINTER(CssSessionHandoffOut)]),
 }
+# the entry points include/css_mi355_stream_out.h declares (final samples at the playback rate, float32 or PCM16), the tenth table
+# load() applies
+SIGNATURES_STREAM_OUT = {
+    "css_stream_set_output": (C.c_int, [_P, C.c_int32, C.POINTER(CssStreamOutputCfg)]),
+    "css_stream_output_bind": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.POINTER(CssStreamOutputCounts)]),
+    "css_stream_output_samples": (C.c_int, [C.POINTER(CssStreamOutputCfg), C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
+    "css_stream_output_peaks": (C.c_int, [_P, C.c_int32, _P]),
+    "css_stream_output_stats": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+}
 SESSION_SCAN_CHUNK = 1024                        # CSS_SESSION_SCAN_CHUNK: the keep-scan kernel's step, in gate frames / sample blocks
 RESAMPLE_TILE = 256                              # output samples per block of the two resampling kernels (resample.hip RS_TILE)
 
@@ -397,7 +417,8 @@ def load() -> C.CDLL:
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_RATE.items()) + list(SIGNATURES_PREVIEW.items()) +
                               list(SIGNATURES_PREVIEW_HANDOFF.items()) + list(SIGNATURES_ENCODER.items()) +
                               list(SIGNATURES_WINDOW.items()) + list(SIGNATURES_PRESENT.items()) +
-                              list(SIGNATURES_FRONTEND.items()) + list(SIGNATURES_SESSION_HANDOFF.items())):
+                              list(SIGNATURES_FRONTEND.items()) + list(SIGNATURES_SESSION_HANDOFF.items()) +
+                              list(SIGNATURES_STREAM_OUT.items())):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -506,6 +527,31 @@ def resample_taps(up: int, down: int) -> np.ndarray:
     if rc != CSS_OK:
         raise CssError(rc, f"css_resample_taps: the ratio {up} / {down} is not supported")
     return taps[:n.value]
+
+
+def stream_output_cfg(rate: int = 16000, dtype="float32", gain: float = 1.0, fs: int = 16000) -> CssStreamOutputCfg:
+    """The output format of a stream playing at `rate`: up / down = rate / fs in lowest terms, float32 or int16 samples"""
+    dt = np.dtype(dtype)
+    if dt not in (np.dtype(np.float32), np.dtype(np.int16)):
+        raise ValueError(f"output samples are float32 or int16, got {dt}")
+    down, up = rate_ratio(rate, fs)   # (rate_ratio gives fs / rate)
+    return CssStreamOutputCfg(up, down, int(dt == np.dtype(np.int16)), float(gain))
+
+
+def stream_output_samples(cfg: CssStreamOutputCfg, n_final_model: int, finished: bool = False) -> int:
+    """css_stream_output_samples: output samples written after `n_final_model` final model-rate samples"""
+    n = C.c_int64()
+    rc = load().css_stream_output_samples(C.byref(cfg), int(n_final_model), int(bool(finished)), C.byref(n))
+    if rc != CSS_OK:
+        raise CssError(rc, f"css_stream_output_samples: the ratio {cfg.up} / {cfg.down} is not supported, or a negative count")
+    return int(n.value)
+
+
+def pcm16_encode(y: np.ndarray, gain: float = 1.0):
+    """The numpy statement of the PCM16 output: float32 samples -> (int16 samples, the number of them the clamp changed)"""
+    v = np.asarray(y, np.float32) * np.float32(gain)
+    r = np.rint(v.astype(np.float64) * 32767.0)
+    return np.clip(r, -32768.0, 32767.0).astype(np.int16), int(np.count_nonzero((r < -32768.0) | (r > 32767.0)))
 
 
 def handoff_cfg(n_mels: int = 80, pad_frames: int = 8, drop_silence: bool = True) -> CssStreamHandoffCfg:
@@ -1210,6 +1256,12 @@ class Handle:
                                                  _np_ptr(out), m, C.byref(n_out)))
         assert n_out.value == m
         return out
+
+    def stream_output_stats(self):
+        """(launches of the output kernel, rounds with a stream that has an output format) of the last push / finish on this handle"""
+        a, b = C.c_int32(), C.c_int32()
+        check(self.h, self.lib.css_stream_output_stats(self.h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
 
     def stream_handoff_stats(self):
         """(hand-off launches, DFT products among them, operand frames) of the last stream call on this handle"""

@@ -343,6 +343,7 @@ struct css_ctx : SessState {
     FeatOpts feat_opts{};   // css_set_feature_options (css_create: the shipped configuration)
     void* streams[CSS_MAX_STREAMS] = {};   // css_stream_open: open streams (api_stream.hip StreamState), by id
     void* handoff = nullptr;   // api_stream.hip: what the hand-off of streams shares on this handle (HandoffCtx), made on first use
+    int32_t stream_out_launches = 0, stream_out_rounds = 0;   // api_stream.hip: the output kernel in the last push / finish call
     DevBuf stream_masks;   // api_stream.hip: the mask head's output for one estimator batch of streamed segments (never `masks`:
                            // the handle's own session keeps its bits between two pushes)
 

@@ -36,12 +36,20 @@
 // log-mel frames in a ring on the device: the mel launch of a committed round leaves them there.  css_stream_windows turns spans
 // of them into Whisper encoder inputs in the caller's device memory, css_stream_present_windows spans that end in a preview's
 // provisional frames: one kernel (handoff.hip stream_window_kernel), one table launch per WINDOW_MULTI_MAX windows (launch_windows).
+//
+// A stream with an output format (css_stream_set_output, include/css_mi355_stream_out.h) also writes the samples
+// that became final at the playback rate, as float32 or PCM16, into the buffer bound to it: ONE table launch per round
+// (resample.hip stream_output_kernel) between tail() and the downloads reads the round's final samples where tail() left them,
+// and the converted samples go from the stream's device staging to the caller's memory.  The float download is skipped when
+// the call's out_host is NULL.  Every stream keeps the running peak of its final samples: the kernel forms it for a stream with
+// an output format, the host from the downloaded samples for every other one (no launch, no copy is added to that path).
 #include "api_ctx.hpp"
 #include "../../include/css_mi355_rate.h"
 #include "../../include/css_mi355_preview.h"
 #include "../../include/css_mi355_preview_handoff.h"
 #include "../../include/css_mi355_window.h"
 #include "../../include/css_mi355_present_window.h"
+#include "../../include/css_mi355_stream_out.h"
 
 #include <climits>
 
@@ -99,9 +107,29 @@ struct RateStream {
     DevBuf stage, hist[2], tab;         // one piece as the caller laid it out (sized for float32); the carried inputs; the taps by phase
 };
 
+// Per stream with an output format (css_stream_set_output; resample.hip stream_output_kernel).  Nothing here is part of the
+// window.  The stream's n_emitted final samples have passed the kernel and all css_stream_output_samples(n_emitted) output samples
+// they make computable were written (n_total); hist[cur] holds final samples [n_emitted - H, n_emitted) per separated stream
+// (zeros before the recording's start).  The launch of a round writes the other generation and only a round that makes samples
+// final flips `cur`: a refused call and one that makes nothing final leave all of it alone.
+struct OutputCounters { unsigned long long clipped[SMAX]; unsigned int peak[SMAX]; };
+struct OutputStream {
+    CssStreamOutputCfg cfg{};
+    bool unity = false;
+    ResampleRatio r{};                  // (1 / 1: all zero but up = down = 1)
+    int H = 0;                          // carried samples per separated stream: ceil(2 half / up) + 1
+    int cur = 0;
+    DevBuf hist[2], tab, stage, ctr;    // the carried samples; the taps by phase; one round's output [S][stage_ld]; OutputCounters
+    int64_t stage_ld = 0, n_total = 0;
+    PinnedBuf pin;                      // the counters after a call
+    void* bound = nullptr; int64_t cap = 0; CssStreamOutputCounts* counts = nullptr;
+};
+
 struct StreamState {
     std::unique_ptr<HandoffStream> ho;
     std::unique_ptr<RateStream> rate;
+    std::unique_ptr<OutputStream> outp;
+    uint32_t peak_bits[SMAX] = {};  // max |w_k| over the n_emitted final samples, as float bits
     CssRunCfg cfg{};
     std::vector<float> w;          // the three windows (cfg.w_* point here)
     int n_ch = 0, T = 0, hop = 0, halo = 0;
@@ -141,6 +169,8 @@ void for_each_buffer(const StreamState* s, Fn fn) {
         for (const DevBuf* d : {&s->ho->gate, &s->ho->carry[0], &s->ho->carry[1], &s->ho->tail[0], &s->ho->tail[1], &s->ho->ring, &s->ho->fmax}) fn(*d);
     if (s->rate)
         for (const DevBuf* d : {&s->rate->stage, &s->rate->hist[0], &s->rate->hist[1], &s->rate->tab}) fn(*d);
+    if (s->outp)
+        for (const DevBuf* d : {&s->outp->hist[0], &s->outp->hist[1], &s->outp->tab, &s->outp->stage, &s->outp->ctr}) fn(*d);
 }
 
 int64_t device_bytes(const StreamState* s) {
@@ -390,6 +420,107 @@ int download(css_ctx* h, StreamState* s, int64_t n, float* out_host, int64_t cap
     HIPCHK(h, hipMemcpy2DAsync(out_host + at, (size_t)cap * sizeof(float), s->out.p, (size_t)n * sizeof(float), (size_t)n * sizeof(float),
                                (size_t)h->d.num_spks, hipMemcpyDeviceToHost, h->stream));
     return CSS_OK;
+}
+
+// ---- output format ---------------------------------------------------------------------------------------------------------
+// output samples written once `n_final` model-rate samples are final (finished: of the whole recording)
+int64_t output_count(const OutputStream* o, int64_t n_final, bool finished) {
+    return o->unity ? n_final : resample_count(o->r, n_final, finished);
+}
+size_t output_el(const OutputStream* o) { return o->cfg.pcm16 ? sizeof(int16_t) : sizeof(float); }
+// a row of the staging that holds what `n` final samples can make in one round (the resampler's lag released at finish included)
+int64_t output_stage_ld(const OutputStream* o, int64_t n) {
+    const int64_t most = o->unity ? n : (n * o->r.up + o->r.half) / o->r.down + 2;
+    return (most + 7) / 8 * 8;
+}
+
+// what a call that makes `need` more samples final must find bound to a stream with an output format
+int check_output_call(const StreamState* s, int64_t need, bool finished, std::string* why) {
+    const OutputStream* o = s->outp.get();
+    if (!o) return CSS_OK;
+    if (!o->bound) { *why = "the stream has an output format and nothing is bound (css_stream_output_bind)"; return CSS_ERR_STATE; }
+    if (o->cap < output_count(o, s->n_emitted + need, finished) - o->n_total) {
+        *why = "the bound output capacity is below what this call writes (css_stream_output_samples)";
+        return CSS_ERR_INVALID_ARG;
+    }
+    return CSS_OK;
+}
+
+// The entry of the round's output launch for a stream whose tail() left `n` new final samples per separated stream in s->out
+// (row pitch src_ld), `done` samples after the n_emitted of the call's start; flips the carried samples' generation.
+// *n_m: the output samples the round writes (at column 0 of the staging).
+int output_job(css_ctx* h, StreamState* s, int64_t done, int64_t n, int64_t src_ld, bool finished, StreamOutputJob* j, int64_t* n_m) {
+    OutputStream* o = s->outp.get();
+    const int S = h->d.num_spks;
+    const int64_t N0 = s->n_emitted + done, m0 = output_count(o, N0, false);
+    *n_m = output_count(o, N0 + n, finished) - m0;
+    const int64_t ld = output_stage_ld(o, n);
+    if (ld > o->stage_ld) {   // (finish can make more samples final than a round of a push)
+        const int rc = ensure(h, o->stage, (size_t)S * ld * output_el(o));
+        if (rc != CSS_OK) return rc;
+        o->stage_ld = ld;
+    }
+    *j = StreamOutputJob{};
+    j->src = (const float*)s->out.p; j->src_ld = src_ld; j->n = n;
+    j->N0 = N0; j->m0 = m0; j->n_m = *n_m;
+    j->up = o->r.up; j->down = o->r.down; j->half = o->r.half; j->P = o->r.P; j->P_ld = o->r.P_ld; j->tab = (const float*)o->tab.p;
+    j->pcm16 = o->cfg.pcm16; j->gain = o->cfg.gain;
+    j->dst = o->stage.p; j->dst_ld = o->stage_ld;
+    OutputCounters* c = (OutputCounters*)o->ctr.p;
+    j->peak = c->peak; j->clipped = c->clipped;
+    if (!o->unity) {
+        j->hist_in = (const float*)o->hist[o->cur].p; j->H = o->H;
+        if (!finished) { j->hist_out = (float*)o->hist[1 - o->cur].p; o->cur = 1 - o->cur; }
+    }
+    return CSS_OK;
+}
+
+// the round's `n_m` output samples from the staging to column `at` of the bound buffer
+int output_download(css_ctx* h, StreamState* s, int64_t n_m, int64_t at) {
+    OutputStream* o = s->outp.get();
+    if (n_m <= 0) return CSS_OK;
+    const size_t el = output_el(o);
+    HIPCHK(h, hipMemcpy2DAsync((char*)o->bound + (size_t)at * el, (size_t)o->cap * el, o->stage.p, (size_t)o->stage_ld * el, (size_t)n_m * el,
+                               (size_t)h->d.num_spks, hipMemcpyDeviceToHost, h->stream));
+    return CSS_OK;
+}
+
+// behind a call's last round: the counters to page-locked memory (read after the call's synchronise by output_report)
+int output_counters(css_ctx* h, StreamState* s) {
+    HIPCHK(h, hipMemcpyAsync(s->outp->pin.p, s->outp->ctr.p, sizeof(OutputCounters), hipMemcpyDeviceToHost, h->stream));
+    return CSS_OK;
+}
+void output_report(css_ctx* h, StreamState* s, int64_t written) {
+    OutputStream* o = s->outp.get();
+    const OutputCounters* c = o->pin.as<OutputCounters>();
+    o->n_total += written;
+    for (int k = 0; k < h->d.num_spks; ++k) s->peak_bits[k] = c->peak[k];
+    if (CssStreamOutputCounts* q = o->counts) {
+        q->n_written = written; q->n_total = o->n_total;
+        for (int k = 0; k < h->d.num_spks; ++k) { q->n_clipped[k] = (int64_t)c->clipped[k]; q->peak_bits[k] = c->peak[k]; }
+    }
+}
+// a call that moved nothing still reports (n_written = 0)
+void output_report_idle(css_ctx* h, StreamState* s) {
+    if (!s->outp || !s->outp->counts) return;
+    s->outp->counts->n_written = 0; s->outp->counts->n_total = s->outp->n_total;
+}
+
+// a stream without an output format: the running peak from the `n` samples per separated stream a call downloaded to out[S][cap].
+// fmaxf(m, |x|) from 0 as the kernels form it, on the bits: non-negative floats order like unsigned integers and a NaN, which
+// fmaxf never lets raise the peak, counts as 0 -- an integer maximum, which the compiler vectorises (the scan is bound by the
+// host's memory: about 0.3 ms per 1.15 M samples, a tick of 16 rooms)
+void host_peak(css_ctx* h, StreamState* s, const float* out, int64_t cap, int64_t n) {
+    for (int k = 0; k < h->d.num_spks; ++k) {
+        const int32_t* w = reinterpret_cast<const int32_t*>(out + (size_t)k * cap);
+        int32_t m = (int32_t)s->peak_bits[k];   // (|x| bits are below 2^31: signed compares, which every x86-64 has for vectors)
+        for (int64_t i = 0; i < n; ++i) {
+            const int32_t a = w[i] & 0x7fffffff;
+            const int32_t v = a > 0x7f800000 ? 0 : a;
+            m = v > m ? v : m;
+        }
+        s->peak_bits[k] = (uint32_t)m;
+    }
 }
 
 // ---- hand-off ----------------------------------------------------------------------------------------------------------
@@ -833,7 +964,7 @@ struct PushItem {
 };
 
 int push_items(css_ctx* h, const std::vector<PushItem>& items, bool pcm16, CssStreamGroupStats* stats) {
-    struct Item { StreamState* s; const PushItem* p; int64_t done, emitted, n, t_g1, t_g_before; bool planar; int64_t n_in; };
+    struct Item { StreamState* s; const PushItem* p; int64_t done, emitted, n, t_g1, t_g_before; bool planar; int64_t n_in, written; };
     std::vector<Item> its(items.size());
     for (size_t i = 0; i < items.size(); ++i) {
         const PushItem& p = items[i];
@@ -859,19 +990,25 @@ int push_items(css_ctx* h, const std::vector<PushItem>& items, bool pcm16, CssSt
         // (a rate stream: n_samples counts inputs; every check below is on the model-rate samples they make available)
         const int64_t n_after = model_samples_after(s, p.n_samples);
         const int64_t need = final_frames(n_after, s->T, s->hop, s->halo) * h->d.frame_hop - s->n_emitted;
-        if (need > 0 && (!p.out_host || p.cap < need))
+        // (a stream with an output format may leave the model-rate out_host out)
+        if (need > 0 && (p.out_host ? p.cap < need : !s->outp))
             return refuse(CSS_ERR_INVALID_ARG, "output capacity too small for the samples this push finalises");
         if (zero_weight_frames(s, s->t_st, segments_done(frames_of(n_after), s->T, s->hop) * s->hop))
             return refuse(CSS_ERR_ZERO_WEIGHT, "zero weights found. check hop_size, segment_size or m0, m1");
         const int hrc = check_handoff_call(h, s, n_after - s->n_pushed, &why);
         if (hrc != CSS_OK) return refuse(hrc, why);
-        its[i] = Item{s, &p, 0, 0, 0, 0, s->t_g, planar, 0};
+        const int orc = check_output_call(s, std::max<int64_t>(need, 0), false, &why);
+        if (orc != CSS_OK) return refuse(orc, why);
+        its[i] = Item{s, &p, 0, 0, 0, 0, s->t_g, planar, 0, 0};
     }
     if (stats) *stats = CssStreamGroupStats{};
+    h->stream_out_launches = h->stream_out_rounds = 0;
     handoff_begin_call(h);
     std::vector<HandoffJob> hj;
     std::vector<HandoffRec> recs;
     auto hand_out = [&]() {   // (a call that moved nothing still reports its empty hand-off)
+        for (size_t i = 0; i < its.size(); ++i)
+            if (its[i].written == 0) output_report_idle(h, its[i].s);
         for (size_t i = 0; i < its.size(); ++i)
             if (its[i].s->ho) {
                 const int hrc = handoff_collect(h, its[i].s, (int)i, its[i].t_g_before, recs, its[i].s->ho->m, its[i].s->ho->bound, true);
@@ -895,6 +1032,8 @@ int push_items(css_ctx* h, const std::vector<PushItem>& items, bool pcm16, CssSt
     std::vector<TailJob> tj;
     std::vector<StreamIngestPcm16> ing;
     std::vector<ResampleJob> rsj;
+    std::vector<StreamOutputJob> oj;
+    std::vector<int64_t> o_nm;
     for (size_t round = 0;; ++round) {
         act.clear();
         for (Item& it : its)
@@ -988,18 +1127,44 @@ int push_items(css_ctx* h, const std::vector<PushItem>& items, bool pcm16, CssSt
         for (Item* it : act)
             if (it->s->ho) hj.push_back(HandoffJob{it->s, (int)(it - its.data()), it->s->t_g, it->t_g1, (it->t_g1 - it->s->t_g) * hopS, false, 0});
         if ((rc = handoff_round(h, hj, round, &recs)) != CSS_OK) return rc;
+        // the streams with an output format whose tail() made samples final: one launch for all of them
+        oj.clear(); o_nm.clear();
+        for (Item* it : act) {
+            const int64_t n_new = (it->t_g1 - it->s->t_g) * hopS;
+            if (!it->s->outp || n_new <= 0) continue;
+            oj.emplace_back(); o_nm.push_back(0);
+            if ((rc = output_job(h, it->s, it->emitted, n_new, n_new, false, &oj.back(), &o_nm.back())) != CSS_OK) return rc;
+        }
+        if (!oj.empty()) {
+            if (!launch_stream_output_multi(oj.data(), (int)oj.size(), h->d.num_spks, h->stream, &h->stream_out_launches))
+                return fail(h, CSS_ERR_HIP, "the output kernel's LDS could not be reserved");
+            h->stream_out_rounds += 1;
+            HIPCHK(h, hipGetLastError());
+        }
+        size_t oi = 0;
         for (Item* it : act) {
             StreamState* s = it->s;
             const int64_t n_new = (it->t_g1 - s->t_g) * hopS;
-            if ((rc = download(h, s, n_new, it->p->out_host, it->p->cap, it->emitted)) != CSS_OK) return rc;
+            if (s->outp && n_new > 0) {
+                if ((rc = output_download(h, s, o_nm[oi], it->written)) != CSS_OK) return rc;
+                it->written += o_nm[oi++];
+            }
+            if (it->p->out_host && (rc = download(h, s, n_new, it->p->out_host, it->p->cap, it->emitted)) != CSS_OK) return rc;
             it->emitted += n_new;
             s->t_st = s->sd * s->hop;
             s->t_g = it->t_g1;
             it->done += it->n_in;
         }
     }
+    for (Item& it : its)
+        if (it.s->outp && it.emitted > 0 && (rc = output_counters(h, it.s)) != CSS_OK) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     for (Item& it : its) {
+        if (it.s->outp) {
+            if (it.emitted > 0) output_report(h, it.s, it.written);
+        } else if (it.emitted > 0) {
+            host_peak(h, it.s, it.p->out_host, it.p->cap, it.emitted);
+        }
         it.s->n_emitted += it.emitted;
         *it.p->n_out = it.emitted;
     }
@@ -1180,8 +1345,31 @@ int closing_pass(css_ctx* h, const std::vector<CloseJob>& jobs, bool commit, Css
         if ((rc = handoff_round(h, hj, 0, &recs, commit)) != CSS_OK) return rc;
         if (pc && pc->total && (rc = present_windows(h, jobs, recs, pc)) != CSS_OK) return rc;
     }
+    // finish of a stream with an output format: the rest of its samples, and the outputs that waited for inputs past the end
+    std::vector<int64_t> o_nm(jobs.size(), 0);
+    if (commit) {
+        h->stream_out_launches = h->stream_out_rounds = 0;
+        std::vector<StreamOutputJob> oj;
+        for (size_t i = 0; i < jobs.size(); ++i) {
+            StreamState* s = jobs[i].s;
+            if (!s->outp || jobs[i].need <= 0) continue;
+            oj.emplace_back();
+            if ((rc = output_job(h, s, 0, jobs[i].need, (jobs[i].p.mix_frames + 1 - s->t_g) * hopS, true, &oj.back(), &o_nm[i])) != CSS_OK) return rc;
+        }
+        if (!oj.empty()) {
+            if (!launch_stream_output_multi(oj.data(), (int)oj.size(), S, h->stream, &h->stream_out_launches))
+                return fail(h, CSS_ERR_HIP, "the output kernel's LDS could not be reserved");
+            h->stream_out_rounds += 1;
+            HIPCHK(h, hipGetLastError());
+        }
+        for (size_t i = 0; i < jobs.size(); ++i)
+            if (jobs[i].s->outp && jobs[i].need > 0) {
+                if ((rc = output_download(h, jobs[i].s, o_nm[i], 0)) != CSS_OK) return rc;
+                if ((rc = output_counters(h, jobs[i].s)) != CSS_OK) return rc;
+            }
+    }
     for (const CloseJob& j : jobs)
-        if ((rc = download(h, j.s, j.need, j.out_host, j.cap, 0)) != CSS_OK) return rc;
+        if (j.out_host && (rc = download(h, j.s, j.need, j.out_host, j.cap, 0)) != CSS_OK) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (!commit) {
         for (size_t i = 0; i < jobs.size(); ++i) {
@@ -1195,6 +1383,12 @@ int closing_pass(css_ctx* h, const std::vector<CloseJob>& jobs, bool commit, Css
     for (size_t i = 0; i < jobs.size(); ++i) {
         StreamState* s = jobs[i].s;
         if (s->ho && (rc = handoff_collect(h, s, (int)i, t_g_before[i], recs, s->ho->m, s->ho->bound, true)) != CSS_OK) return rc;
+        if (s->outp) {
+            if (jobs[i].need > 0) output_report(h, s, o_nm[i]);
+            else output_report_idle(h, s);
+        } else if (jobs[i].need > 0) {
+            host_peak(h, s, jobs[i].out_host, jobs[i].cap, jobs[i].need);
+        }
         s->n_pushed = jobs[i].n_total;
         s->K = std::max(s->K, frames_of(jobs[i].n_total));
         s->sd = jobs[i].p.num_segments; s->t_st = s->t_g = jobs[i].p.mix_frames;
@@ -1220,9 +1414,11 @@ int css_stream_finish(css_handle_t h, int32_t id, float* out_host, int64_t cap, 
     plan_impl(h->d, s->cfg, j.n_total, &j.p);
     if (j.p.zero_weight) return fail(h, CSS_ERR_ZERO_WEIGHT, "zero weights found. check hop_size, segment_size or m0, m1");
     j.need = j.p.n_out - s->n_emitted;
-    if (!out_host || cap < j.need) return fail(h, CSS_ERR_INVALID_ARG, "output capacity too small for the rest of the stream");
+    // (a stream with an output format may leave the model-rate out_host out)
+    if (out_host ? cap < j.need : !s->outp) return fail(h, CSS_ERR_INVALID_ARG, "output capacity too small for the rest of the stream");
     std::string why;
     if ((rc = check_handoff_call(h, s, -1, &why)) != CSS_OK) return fail(h, rc, why);
+    if ((rc = check_output_call(s, j.need, true, &why)) != CSS_OK) return fail(h, rc, why);
     if ((rc = closing_pass(h, {j}, true, nullptr)) != CSS_OK) return rc;
     *n_out = j.need;
     return CSS_OK;
@@ -1421,6 +1617,77 @@ int css_stream_set_rate(css_handle_t h, int32_t id, int32_t up, int32_t down) {
     if (rc != CSS_OK) return rc;
     if (e != hipSuccess) return fail(h, CSS_ERR_HIP, std::string("rate setup: ") + hipGetErrorString(e));
     s->rate = std::move(q);
+    return CSS_OK;
+}
+
+// ---- the output format of a stream (include/css_mi355_stream_out.h) --------------------------------------------------------------
+int css_stream_set_output(css_handle_t h, int32_t id, const CssStreamOutputCfg* cfg) {
+    StreamState* s = nullptr;
+    int rc = check_stream_call(h, id, &s);
+    if (rc != CSS_OK) return rc;
+    if (!cfg) return fail(h, CSS_ERR_INVALID_ARG, "null argument");
+    static_assert(STREAM_MULTI_MAX == CSS_STREAM_OUTPUT_TABLE, "the header states the table's size");
+    const bool unity = cfg->up == 1 && cfg->down == 1;
+    ResampleRatio r{1, 1, 0, 0, 0, 0};
+    if (!unity && (!resample_ratio(cfg->up, cfg->down, &r) || !stream_output_fits(r)))
+        return fail(h, CSS_ERR_INVALID_ARG, "output ratio: 1 / 1, or up != down in lowest terms, at most 128 taps per output sample and 16384 taps");
+    if (!std::isfinite(cfg->gain) || !(cfg->gain > 0.f)) return fail(h, CSS_ERR_INVALID_ARG, "the gain is finite and > 0");
+    if (s->outp) return fail(h, CSS_ERR_STATE, "this stream has an output format already");
+    if (s->n_pushed > 0 || s->finished || (s->rate && s->rate->n_in > 0))
+        return fail(h, CSS_ERR_STATE, "the output format is set before the stream's first sample");
+    HIPCHK(h, hipSetDevice(h->device));
+    const int S = h->d.num_spks;
+    std::unique_ptr<OutputStream> o(new OutputStream());
+    o->cfg = *cfg;
+    o->cfg.pcm16 = cfg->pcm16 ? 1 : 0;
+    o->unity = unity;
+    o->r = r;
+    // a round of a push makes at most as many samples final as the stream's output buffer holds per separated stream
+    o->stage_ld = output_stage_ld(o.get(), (int64_t)(s->out.cap / (sizeof(float) * S)));
+    rc = ensure(h, o->stage, (size_t)S * o->stage_ld * output_el(o.get()));
+    if (rc == CSS_OK) rc = ensure(h, o->ctr, sizeof(OutputCounters), true);
+    hipError_t e = o->pin.alloc(sizeof(OutputCounters));
+    if (rc == CSS_OK && e == hipSuccess && !unity) {
+        o->H = (2 * r.half + r.up - 1) / r.up + 1;
+        std::vector<float> taps((size_t)r.L), tab((size_t)r.up * r.P_ld);
+        resample_taps_f32(r, taps.data());
+        resample_phase_table(r, taps.data(), tab.data());
+        for (int b = 0; b < 2 && rc == CSS_OK; ++b) rc = ensure(h, o->hist[b], (size_t)S * o->H * sizeof(float), true);
+        if (rc == CSS_OK) rc = ensure(h, o->tab, tab.size() * sizeof(float));
+        if (rc == CSS_OK) e = hipMemcpyAsync(o->tab.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice, h->stream);
+    }
+    const hipError_t es = hipStreamSynchronize(h->stream);   // (the zero fills, and `tab` above leaves scope)
+    if (rc != CSS_OK) return rc;
+    if (e != hipSuccess || es != hipSuccess) return fail(h, CSS_ERR_HIP, std::string("output setup: ") + hipGetErrorString(e != hipSuccess ? e : es));
+    s->outp = std::move(o);
+    return CSS_OK;
+}
+
+int css_stream_output_bind(css_handle_t h, int32_t id, void* out_host, int64_t cap, CssStreamOutputCounts* counts) {
+    if (!h) return CSS_ERR_INVALID_ARG;
+    StreamState* s = get_stream(h, id);
+    if (!s) return fail(h, CSS_ERR_INVALID_ARG, "no open stream with this id");
+    if (!s->outp) return fail(h, CSS_ERR_STATE, "this stream has no output format (css_stream_set_output)");
+    if (out_host && (cap < 0 || !counts || !counts->n_clipped || !counts->peak_bits))
+        return fail(h, CSS_ERR_INVALID_ARG, "a buffer without counts, or counts without their arrays");
+    s->outp->bound = out_host;
+    s->outp->cap = out_host ? cap : 0;
+    s->outp->counts = out_host ? counts : nullptr;
+    return CSS_OK;
+}
+
+int css_stream_output_peaks(css_handle_t h, int32_t id, uint32_t* peak_bits) {
+    if (!h) return CSS_ERR_INVALID_ARG;
+    StreamState* s = get_stream(h, id);
+    if (!s || !peak_bits) return fail(h, CSS_ERR_INVALID_ARG, "no open stream with this id / null argument");
+    for (int k = 0; k < h->d.num_spks; ++k) peak_bits[k] = s->peak_bits[k];
+    return CSS_OK;
+}
+
+int css_stream_output_stats(css_handle_t h, int32_t* launches, int32_t* rounds) {
+    if (!h) return CSS_ERR_INVALID_ARG;
+    if (launches) *launches = h->stream_out_launches;
+    if (rounds) *rounds = h->stream_out_rounds;
     return CSS_OK;
 }
 

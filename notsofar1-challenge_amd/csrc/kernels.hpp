@@ -410,5 +410,24 @@ struct ResampleJob {
 };
 bool launch_stream_ingest_resample_multi(const ResampleJob* e, int n, hipStream_t s);   // false: the LDS could not be reserved
 bool launch_resample(const ResampleJob& e, hipStream_t s);
+// The output side of a stream (include/css_mi355_stream_out.h): the n final samples per separated stream a round made,
+// src [S][src_ld] (the recording's samples [N0, N0 + n)), -> outputs [m0, m0 + n_m) at the rate up / down, as float32 or as
+// int16 (__fmul_rn by gain, rint(double * 32767), clamp) at dst[k * dst_ld + (m - m0)] (rows 16-byte aligned).  Inputs
+// [N0 - H, N0) are hist_in [S][H]; every other input is zero.  With hist_out the last H inputs of [hist_in | src] go to
+// hist_out [S][H] (another buffer than hist_in).  up == down == 1: a copy / conversion, no taps, no span, no history.  Also
+// peak[k] = max(peak[k], max |src[k][:]| as float bits) and clipped[k] += samples of the round the clamp changed.
+constexpr int SO_TILE = 1024;   // output samples per block
+struct StreamOutputJob {
+    const float* src; int64_t src_ld, n;
+    const float* hist_in; float* hist_out; int H;
+    int64_t N0, m0, n_m;
+    int up, down, half, P, P_ld; const float* tab;
+    int pcm16; float gain;
+    void* dst; int64_t dst_ld;
+    unsigned int* peak; unsigned long long* clipped;
+};
+bool stream_output_fits(const ResampleRatio& r);   // the tile's LDS (taps, span, output tile) fits a workgroup
+// one launch per STREAM_MULTI_MAX entries (S separated streams each); false: the LDS could not be reserved
+bool launch_stream_output_multi(const StreamOutputJob* e, int n, int S, hipStream_t s, int* launches);
 
 }  // namespace css

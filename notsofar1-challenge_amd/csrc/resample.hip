@@ -15,8 +15,12 @@
 //                                   the streams' sample windows, and the inputs the next round still reads -> the other
 //                                   generation of the carried history
 //   resample_kernel                 a whole recording -> [n_out][C] (css_resample_host)
+//   stream_output_kernel            a table launch for the streams of a round that have an output format: [carried | the round's
+//                                   final samples] -> float32 or PCM16 at the playback rate (css_stream_set_output), the carried
+//                                   samples' other generation, the running peak and the clipped counts
 #include "api_ctx.hpp"
 #include "../../include/css_mi355_rate.h"
+#include "../../include/css_mi355_stream_out.h"
 
 #include <numeric>
 #include <type_traits>
@@ -219,6 +223,129 @@ __global__ __launch_bounds__(RS_TILE) void resample_kernel(ResampleJob e) {
     resample_tile<false>(e, (int64_t)blockIdx.x * RS_TILE, rs_lds);
 }
 
+// ---- the output side of a stream (include/css_mi355_stream_out.h; DESIGN.md 7b "Final samples at the playback rate") ----------
+// The twin of stream_ingest_resample_kernel: a table launch, blockIdx.z = entry (a stream), blockIdx.y = separated stream,
+// blockIdx.x = tile of SO_TILE output samples; block `tiles` of an entry writes the next generation of the carried samples and
+// blocks past it return at once.  A tile stages the taps and the span [carried | the round's final samples] of its speaker,
+// runs resample_sample per output sample (lane l of a pass takes output 256 pass + l), converts, and leaves through an output
+// tile in LDS so that the stores are 16 bytes per lane.
+// LDS banks (ds_read_b32: 32 banks, conflicts within a 32-lane half): consecutive lanes' first taps lie down / up of a sample
+// apart.  At the playback rates above the model's (3 / 1, 441 / 160, 2 / 1) that is less than one dword: a half reads at most
+// 32 down / up + 1 consecutive dwords, equal addresses broadcast, no conflict, and swz's padding dword only shifts them.  Below
+// it (1 / 2: a stride of 2 dwords folds lanes l and l + 16 onto one bank) swz moves the upper 16 lanes by one dword, as on the
+// input side.  The taps of a phase start at phase * P_ld: 3 rows at 3 / 1 (banks 0, 21, 10); at 441 / 160 the lanes' phases step
+// by 160 = 5 * 32, so whatever P_ld is the half's 32 lanes meet on the ~12 banks their wraps past 441 select (about 3 lanes per
+// bank, on one of the two reads per fmaf).
+struct StreamOutputTable { StreamOutputJob e[STREAM_MULTI_MAX]; };
+
+// floats of LDS before the output tile: the taps by phase and the span's row (nothing at 1 / 1), rounded to 16 bytes
+__host__ __device__ __forceinline__ int so_tile_at(int up, int down, int P, int P_ld) {
+    if (up == down) return 0;
+    const int span_max = (SO_TILE * down + up - 1) / up + P + 1;
+    return (up * P_ld + (span_max - 1 + ((span_max - 1) >> 5) + 1) + 3) & ~3;
+}
+
+__global__ __launch_bounds__(RS_TILE) void stream_output_kernel(StreamOutputTable tab) {
+    extern __shared__ __attribute__((aligned(16))) float rs_lds[];
+    __shared__ float w_peak[RS_TILE / 64];
+    __shared__ unsigned int w_clip[RS_TILE / 64];
+    const StreamOutputJob e = tab.e[blockIdx.z];
+    const int64_t tiles = (e.n_m + SO_TILE - 1) / SO_TILE;
+    const int64_t b = blockIdx.x;
+    if (b > tiles) return;
+    const int k = blockIdx.y, tid = threadIdx.x;
+    const float* __restrict__ src = e.src + (int64_t)k * e.src_ld;
+    // the running peak: the entry's tiles + 1 blocks of this speaker share the round's n samples
+    const int64_t per = (e.n + tiles) / (tiles + 1);
+    const int64_t lo = b * per < e.n ? b * per : e.n, hi = lo + per < e.n ? lo + per : e.n;
+    float m = 0.f;
+    for (int64_t i = lo + tid; i < hi; i += RS_TILE) m = fmaxf(m, fabsf(src[i]));
+    unsigned int clip = 0;
+    if (b == tiles) {
+        // the last H inputs of [carried | the round's samples] become the next round's carried history
+        if (e.hist_out)
+            for (int v = tid; v < e.H; v += RS_TILE) {
+                const int64_t s = e.n + v;
+                e.hist_out[(int64_t)k * e.H + v] = s < e.H ? e.hist_in[(int64_t)k * e.H + s] : src[s - e.H];
+            }
+    } else {
+        const bool unity = e.up == e.down;
+        const int up = e.up, down = e.down, P = e.P;
+        const int64_t t0 = b * SO_TILE;
+        const int nt = (int)(e.n_m - t0 < SO_TILE ? e.n_m - t0 : SO_TILE);
+        float* otile = rs_lds + so_tile_at(up, down, P, e.P_ld);
+        float* taps = rs_lds;
+        float* row = rs_lds + up * e.P_ld;
+        int rem0 = 0;
+        if (!unity) {
+            for (int v = tid; v < up * e.P_ld; v += RS_TILE) taps[v] = e.tab[v];
+            // the tile's first output: i_hi = num / up, phase = num % up; output t of the tile adds t * down to num
+            const int64_t num = (e.m0 + t0) * down + e.half;
+            const int64_t ihi0 = num / up;
+            rem0 = (int)(num - ihi0 * up);
+            const int span = (rem0 + (nt - 1) * down) / up + P;
+            // input i is element s = i - (N0 - H) of [carried (H) | the round's samples (n)]; zero before and behind
+            const int64_t s0 = ihi0 - (P - 1) - (e.N0 - e.H);
+            for (int p = tid; p < span; p += RS_TILE) {
+                const int64_t s = s0 + p;
+                float x = 0.f;
+                if (s >= 0 && s < e.H) x = e.hist_in[(int64_t)k * e.H + s];
+                else if (s >= e.H && s - e.H < e.n) x = src[s - e.H];
+                row[swz(p)] = x;
+            }
+            __syncthreads();
+        }
+        for (int t = tid; t < nt; t += RS_TILE) {
+            float y;
+            if (unity) {
+                y = src[t0 + t];
+            } else {
+                const int nu = rem0 + t * down;
+                const int a = nu / up;
+                y = resample_sample(row, a, taps + (nu - a * up) * e.P_ld, P);
+            }
+            if (e.pcm16) {
+                const double r = rint((double)__fmul_rn(y, e.gain) * 32767.0);
+                const double c = fmin(fmax(r, -32768.0), 32767.0);
+                clip += c != r ? 1u : 0u;
+                reinterpret_cast<int16_t*>(otile)[t] = (int16_t)c;
+            } else {
+                otile[t] = y;
+            }
+        }
+        __syncthreads();
+        // dst rows and tile starts are multiples of 16 bytes: whole vectors, then the tile's last elements one by one
+        if (e.pcm16) {
+            int16_t* d = static_cast<int16_t*>(e.dst) + (int64_t)k * e.dst_ld + t0;
+            const int nv = nt / 8;
+            for (int v = tid; v < nv; v += RS_TILE) reinterpret_cast<uint4*>(d)[v] = reinterpret_cast<const uint4*>(otile)[v];
+            for (int t = nv * 8 + tid; t < nt; t += RS_TILE) d[t] = reinterpret_cast<const int16_t*>(otile)[t];
+        } else {
+            float* d = static_cast<float*>(e.dst) + (int64_t)k * e.dst_ld + t0;
+            const int nv = nt / 4;
+            for (int v = tid; v < nv; v += RS_TILE) reinterpret_cast<uint4*>(d)[v] = reinterpret_cast<const uint4*>(otile)[v];
+            for (int t = nv * 4 + tid; t < nt; t += RS_TILE) d[t] = otile[t];
+        }
+    }
+    // one atomic of each kind per block, and only when it changes the word
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        m = fmaxf(m, __shfl_xor(m, o));
+        clip += __shfl_xor(clip, o);
+    }
+    if ((tid & 63) == 0) { w_peak[tid >> 6] = m; w_clip[tid >> 6] = clip; }
+    __syncthreads();
+    if (tid == 0) {
+        float bm = w_peak[0];
+        unsigned int bc = w_clip[0];
+        for (int w = 1; w < RS_TILE / 64; ++w) { bm = fmaxf(bm, w_peak[w]); bc += w_clip[w]; }
+        if (bm > __uint_as_float(__hip_atomic_load(e.peak + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) atomicMax(e.peak + k, __float_as_uint(bm));
+        if (bc) atomicAdd(e.clipped + k, (unsigned long long)bc);
+    }
+}
+
+size_t so_lds_bytes(int up, int down, int P, int P_ld) { return ((size_t)so_tile_at(up, down, P, P_ld) + SO_TILE) * sizeof(float); }
+
 size_t lds_bytes(const ResampleJob& e) {
     const int span_max = (RS_TILE * e.down + e.up - 1) / e.up + e.P + 1;
     const int row_ld = span_max - 1 + ((span_max - 1) >> 5) + 1;
@@ -255,6 +382,30 @@ bool launch_stream_ingest_resample_multi(const ResampleJob* e, int n, hipStream_
     return true;
 }
 
+bool stream_output_fits(const ResampleRatio& r) { return so_lds_bytes(r.up, r.down, r.P, r.P_ld) <= RS_LDS_MAX; }
+
+bool launch_stream_output_multi(const StreamOutputJob* e, int n, int S, hipStream_t s, int* launches) {
+    for (int i0 = 0; i0 < n; i0 += STREAM_MULTI_MAX) {
+        const int cnt = std::min(STREAM_MULTI_MAX, n - i0);
+        StreamOutputTable tab{};
+        int64_t most = 0;
+        size_t lds = 0;
+        for (int i = 0; i < cnt; ++i) {
+            const StreamOutputJob& j = e[i0 + i];
+            tab.e[i] = j;
+            most = std::max(most, (j.n_m + SO_TILE - 1) / SO_TILE + 1);
+            lds = std::max(lds, so_lds_bytes(j.up, j.down, j.P, j.P_ld));
+        }
+        if (lds > RS_LDS_MAX) return false;
+        if (lds > 65536 && hipFuncSetAttribute(reinterpret_cast<const void*>(stream_output_kernel),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+            return false;
+        hipLaunchKernelGGL(stream_output_kernel, dim3((unsigned)most, (unsigned)S, cnt), dim3(RS_TILE), lds, s, tab);
+        if (launches) ++*launches;
+    }
+    return true;
+}
+
 bool launch_resample(const ResampleJob& e, hipStream_t s) {
     const size_t lds = lds_bytes(e);
     if (lds > RS_LDS_MAX) return false;
@@ -274,6 +425,13 @@ int css_stream_rate_samples(int32_t up, int32_t down, int64_t n_in, int32_t fini
     if (!n_model || n_in < 0 || !resample_ratio(up, down, &r) || n_in > INT64_MAX / r.up) return CSS_ERR_INVALID_ARG;
     *n_model = resample_count(r, n_in, finished != 0);
     return CSS_OK;
+}
+
+// (include/css_mi355_stream_out.h)
+int css_stream_output_samples(const CssStreamOutputCfg* cfg, int64_t n_final_model, int32_t finished, int64_t* n) {
+    if (!cfg || !n || n_final_model < 0) return CSS_ERR_INVALID_ARG;
+    if (cfg->up == 1 && cfg->down == 1) { *n = n_final_model; return CSS_OK; }
+    return css_stream_rate_samples(cfg->up, cfg->down, n_final_model, finished, n);
 }
 
 int css_resample_taps(int32_t up, int32_t down, float* taps, int32_t cap, int32_t* n_taps) {

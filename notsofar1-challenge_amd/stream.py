@@ -45,6 +45,16 @@ include/css_mi355_present_window.h) are ``preview(handoff=True)`` and windows in
 ends at the present frame -- the history's final frames, then the preview's provisional ones, which never leave the device for
 this -- and ``present_span`` tells (first_frame, n_used, n_provisional).  ``whisper_window`` of the frames the pushes returned
 followed by ``preview_handoff.mel[k]``, bit for bit.
+
+``CssStream(..., output=dict(rate=48000, dtype="int16", gain=1 / 16))`` (css_stream_set_output, include/css_mi355_stream_out.h)
+gives the stream an output format: ``push`` / ``push_pcm16`` / ``finish`` and the grouped pushes then return the final samples at
+the playback rate -- ``handle.resample(css_run(x).T, fs, rate)`` of the whole recording, bit for bit, however the pushes were cut
+-- as float32, or as int16 through ``_lib.pcm16_encode``'s two lines (``gain``, round half to even, clamp; no peak
+normalisation), converted on the device into page-locked buffers; nothing crosses PCIe at the model rate unless
+``model_rate=True`` is among the options (``stream.model_rate`` then holds the call's float32 samples).  ``rate`` defaults to
+``fs`` (no rate change), ``dtype`` to float32, ``gain`` to 1.  ``output_clipped`` counts the samples the clamp changed,
+``output_peaks`` is max |w_k| over the final samples so far -- on every stream, with or without an output format; after ``finish``
+it is ``Handle.run_pcm16``'s peaks.  ``preview()`` stays float32 at the model rate.
 """
 from __future__ import annotations
 
@@ -144,11 +154,11 @@ class Handoff:
 
 class CssStream:
     """One stream on a ``HipSeparator``'s handle.  ``push(chunk)`` -> list of S float32 arrays (the newly final samples),
-    ``finish()`` -> the rest; use as a context manager (closes the stream).  ``handoff``: see the module text."""
+    ``finish()`` -> the rest; use as a context manager (closes the stream).  ``handoff``, ``output``: see the module text."""
 
     def __init__(self, separator: HipSeparator, cfg: Optional[CssCfg] = None, fs: int = 16000, num_channels: int = 7,
                  handoff: Optional[Mapping[str, object]] = None, input_rate: Optional[int] = None,
-                 window_history: Optional[int] = None):
+                 window_history: Optional[int] = None, output: Optional[Mapping[str, object]] = None):
         self.separator = separator
         self.cfg = cfg if cfg is not None else CssCfg()
         desc = separator.desc
@@ -174,6 +184,25 @@ class CssStream:
                 raise
             self.rate = (up, down)
             self.resampler_lag_samples = 10 * max(up, down) // up
+        # the output format (css_stream_set_output): what push / finish return then, and the counts bound with the buffer
+        self._ocfg = None
+        self.output_total = 0
+        self.model_rate: Optional[List[np.ndarray]] = None
+        if output is not None:
+            opts = dict(output)
+            self._o_model_rate = bool(opts.pop("model_rate", False))
+            try:
+                ocfg = _lib.stream_output_cfg(fs=fs, **opts)
+                _lib.check(self._h.h, self._h.lib.css_stream_set_output(self._h.h, self.id, C.byref(ocfg)))
+            except Exception:
+                self.close()
+                raise
+            self._ocfg = ocfg
+            self.output_rate = int(opts.get("rate", fs))
+            self._odtype = np.dtype(np.int16 if ocfg.pcm16 else np.float32)
+            self._oclip, self._opeak = np.zeros(self.num_spks, np.int64), np.zeros(self.num_spks, np.uint32)
+            self._ocounts = _lib.CssStreamOutputCounts(0, 0, self._oclip.ctypes.data, self._opeak.ctypes.data)
+            self._obuf = None
         self._out = np.empty((self.num_spks, 0), np.float32)
         self.handoff: Optional[Handoff] = None
         self.preview_handoff: Optional[Handoff] = None
@@ -257,6 +286,55 @@ class CssStream:
         """output samples per separated stream that are final after ``n_pushed`` pushed samples (input samples with ``input_rate``)"""
         return _lib.stream_final_samples(self.separator.desc, self._run_cfg, self._model_samples(n_pushed))
 
+    def output_samples(self, n_final: int, finished: bool = False) -> int:
+        """output-rate samples written once ``n_final`` model-rate samples are final -- ``final_samples(n_pushed)`` while the
+        stream is open -- or, ``finished``, by a finished stream that returned ``n_final`` (css_stream_output_samples)"""
+        if self._ocfg is None:
+            raise ValueError("output_samples() needs a stream opened with output=")
+        return _lib.stream_output_samples(self._ocfg, n_final, finished)
+
+    @property
+    def output_peaks(self) -> np.ndarray:
+        """float32 [S]: max |w_k| over the final model-rate samples so far (css_stream_output_peaks; any stream)"""
+        bits = np.zeros(self.num_spks, np.uint32)
+        _lib.check(self._h.h, self._h.lib.css_stream_output_peaks(self._h.h, self.id, bits.ctypes.data_as(C.c_void_p)))
+        return bits.view(np.float32)
+
+    @property
+    def output_clipped(self) -> np.ndarray:
+        """int64 [S]: output samples so far that the PCM16 clamp changed"""
+        if self._ocfg is None:
+            raise ValueError("output_clipped needs a stream opened with output=")
+        return self._oclip.copy()
+
+    def _output_bind(self, n_pushed: int, n_final: Optional[int] = None, finished: bool = False):
+        """binds a page-locked buffer that holds what a call writes after which ``n_pushed`` samples are pushed (``n_final`` final)"""
+        if self._ocfg is None:
+            return
+        if n_final is None:
+            n_final = self.final_samples(n_pushed)
+        need = _lib.stream_output_samples(self._ocfg, n_final, finished) - self.output_total
+        if self._obuf is None or self._obuf.shape[1] < need:
+            self._obuf = _lib.pinned_empty((self.num_spks, max(need, 1)), self._odtype)
+        _lib.check(self._h.h, self._h.lib.css_stream_output_bind(self._h.h, self.id, C.c_void_p(self._obuf.ctypes.data),
+                                                                 self._obuf.shape[1], C.byref(self._ocounts)))
+
+    def _model_out(self, cap: int):
+        """(array or None, pointer, capacity) for the model-rate samples of a call: nothing with an output format, unless asked for"""
+        if self._ocfg is not None and not self._o_model_rate:
+            return None, None, 0
+        out = self._buffer(cap)
+        return out, out.ctypes.data_as(C.c_void_p), out.shape[1]
+
+    def _returned(self, out, n_out: int) -> List[np.ndarray]:
+        """what a call returns: the model-rate samples, or with an output format those it wrote at the playback rate"""
+        got = None if out is None else [out[s, :n_out].copy() for s in range(self.num_spks)]
+        if self._ocfg is None:
+            return got
+        self.model_rate = got
+        self.output_total = int(self._ocounts.n_total)
+        return [self._obuf[s, :int(self._ocounts.n_written)].copy() for s in range(self.num_spks)]
+
     def _cap(self, n: int) -> int:
         """an output capacity that suffices for the next push of ``n`` samples"""
         return self._model_new(n) + self.latency_samples
@@ -277,40 +355,41 @@ class CssStream:
     def push(self, chunk) -> List[np.ndarray]:
         x = self._samples(chunk)
         n = x.shape[0]
-        out = self._buffer(self._cap(n))
+        out, ptr, cap = self._model_out(self._cap(n))
         n_out = C.c_int64(0)
         self._handoff_bind(n)
-        _lib.check(self._h.h, self._h.lib.css_stream_push(self._h.h, self.id, x.ctypes.data_as(C.c_void_p), n,
-                                                          out.ctypes.data_as(C.c_void_p), out.shape[1], C.byref(n_out)))
+        self._output_bind(self._n_in + n)
+        _lib.check(self._h.h, self._h.lib.css_stream_push(self._h.h, self.id, x.ctypes.data_as(C.c_void_p), n, ptr, cap, C.byref(n_out)))
         self._n_in += n
         self._handoff_take()
-        return [out[s, :n_out.value].copy() for s in range(self.num_spks)]
+        return self._returned(out, n_out.value)
 
     def push_pcm16(self, chunk) -> List[np.ndarray]:
         """``push`` for int16 samples [n, C] (interleaved, or the planar view ``planes.T``: ``pcm16_layout``): what ``push`` of
         ``chunk.astype(float32) / 32768`` returns, bit for bit; the samples are scaled and de-interleaved on the device."""
         x, ss, cs = pcm16_layout(chunk, self.num_channels)
         n = x.shape[0]
-        out = self._buffer(self._cap(n))
+        out, ptr, cap = self._model_out(self._cap(n))
         n_out = C.c_int64(0)
         self._handoff_bind(n)
-        _lib.check(self._h.h, self._h.lib.css_stream_push_pcm16(self._h.h, self.id, C.c_void_p(x.ctypes.data), n, ss, cs,
-                                                                out.ctypes.data_as(C.c_void_p), out.shape[1], C.byref(n_out)))
+        self._output_bind(self._n_in + n)
+        _lib.check(self._h.h, self._h.lib.css_stream_push_pcm16(self._h.h, self.id, C.c_void_p(x.ctypes.data), n, ss, cs, ptr, cap,
+                                                                C.byref(n_out)))
         self._n_in += n
         self._handoff_take()
-        return [out[s, :n_out.value].copy() for s in range(self.num_spks)]
+        return self._returned(out, n_out.value)
 
     def finish(self) -> List[np.ndarray]:
         inf = self.info()
         n_total = inf.n_pushed if self.rate is None else self._model_samples(self._n_in, True)
         rest = _lib.plan(self.separator.desc, self._run_cfg, n_total).n_out - inf.n_emitted
-        out = self._buffer(max(rest, 1))
+        out, ptr, cap = self._model_out(max(rest, 1))
         n_out = C.c_int64(0)
         self._handoff_bind(-1)
-        _lib.check(self._h.h, self._h.lib.css_stream_finish(self._h.h, self.id, out.ctypes.data_as(C.c_void_p), out.shape[1],
-                                                            C.byref(n_out)))
+        self._output_bind(0, inf.n_emitted + rest, True)
+        _lib.check(self._h.h, self._h.lib.css_stream_finish(self._h.h, self.id, ptr, cap, C.byref(n_out)))
         self._handoff_take()
-        return [out[s, :n_out.value].copy() for s in range(self.num_spks)]
+        return self._returned(out, n_out.value)
 
     def preview_samples(self, n_pushed: int):
         """(first, count): a preview after ``n_pushed`` pushed samples (input samples with ``input_rate``) returns samples
@@ -455,18 +534,19 @@ class CssStreamGroup:
         for it, (s, _) in zip(items, part):
             s._n_in += int(it.n_samples)
             s._handoff_take()
-        got = {id(s): [out[k, :it.n_out].copy() for k in range(s.num_spks)] for it, (s, _), out in zip(items, part, outs)}
-        return [got.get(id(s), [np.empty(0, np.float32) for _ in range(s.num_spks)]) for s in self.streams]
+        got = {id(s): s._returned(out, it.n_out) for it, (s, _), out in zip(items, part, outs)}
+        return [got.get(id(s), [np.empty(0, np.float32 if s._ocfg is None else s._odtype) for _ in range(s.num_spks)]) for s in self.streams]
 
     def push(self, chunks: Union[Mapping[CssStream, object], Sequence[object]]) -> List[List[np.ndarray]]:
         part = [(s, s._samples(c)) for s, c in zip(self.streams, self._per_stream(chunks)) if c is not None]
         items = (_lib.CssStreamPush * max(len(part), 1))()
         outs = []
         for it, (s, x) in zip(items, part):
-            out = s._buffer(s._cap(x.shape[0]))
+            out, _, cap = s._model_out(s._cap(x.shape[0]))
             outs.append(out)
+            s._output_bind(s._n_in + x.shape[0])
             it.id, it.pcm_host, it.n_samples = s.id, x.ctypes.data, x.shape[0]
-            it.out_host, it.cap, it.n_out = out.ctypes.data, out.shape[1], 0
+            it.out_host, it.cap, it.n_out = None if out is None else out.ctypes.data, cap, 0
             s._handoff_bind(x.shape[0])
         return self._call(self._h.lib.css_stream_push_many, items, part, outs)
 
@@ -476,10 +556,11 @@ class CssStreamGroup:
         items = (_lib.CssStreamPushPcm16 * max(len(part), 1))()
         outs = []
         for it, (s, (x, ss, cs)) in zip(items, part):
-            out = s._buffer(s._cap(x.shape[0]))
+            out, _, cap = s._model_out(s._cap(x.shape[0]))
             outs.append(out)
+            s._output_bind(s._n_in + x.shape[0])
             it.id, it.pcm16_host, it.n_samples, it.sample_stride, it.channel_stride = s.id, x.ctypes.data, x.shape[0], ss, cs
-            it.out_host, it.cap, it.n_out = out.ctypes.data, out.shape[1], 0
+            it.out_host, it.cap, it.n_out = None if out is None else out.ctypes.data, cap, 0
             s._handoff_bind(x.shape[0])
         return self._call(self._h.lib.css_stream_push_many_pcm16, items, part, outs)
 

@@ -45,6 +45,14 @@ css_stream_present_windows of all streams -- arm PH's preview and arm W's 3 floa
 and under one synchronise, the windows reaching over the preview's provisional frames to the present.  PH, W and PW follow one
 another inside every round, so they share clock and power state; at three rounds PW's windows are compared with whisper_window of
 the host's frames followed by the preview's, outside the clock (profiles/r16_stream_present_window.json).
+
+With --rate HZ --out-rate HZ2 [--out-pcm16] two groups of N streams take the same 16-bit recordings at HZ, one round of 1.5 s each
+per tick, in an order that alternates in blocks of rounds: (O) one css_stream_push_many_pcm16 on streams opened with
+output=dict(rate=HZ2, dtype=int16 or float32) and no model-rate out_host: the final samples come back at HZ2, converted on the
+device; (F) the same push on streams without an output format, followed by what a host does today with the float32 samples it
+gets: scipy.signal.resample_poly to HZ2 and, with --out-pcm16, the rounding to int16, per separated stream.  Arm O is compared
+with the definition (css_resample_host of css_run's waveforms, _lib.pcm16_encode), arm F's float32 samples with css_run; the
+bytes that cross PCIe per tick are counted for both (profiles/r20_stream_output.json).
 """
 import argparse
 import json
@@ -334,6 +342,131 @@ def group_bench(n_streams, out_path, seconds=60.0, round_s=1.5, block=5, passes=
     print(text)
 
 
+def output_bench(n_streams, out_path, rate, out_rate, out_pcm16, pinned=False, seconds=60.0, round_s=1.5, block=5, passes=2):
+    from scipy.signal import resample_poly
+    import notsofar1_challenge_amd._lib as LIB
+    import notsofar1_challenge_amd.css as CSS
+    import notsofar1_challenge_amd.separator as SEP
+    import notsofar1_challenge_amd.stream as STR
+    import notsofar1_challenge_amd.synth as SYN
+    import notsofar1_challenge_amd.weights as W
+    desc = W.ModelDesc.mc_v1()
+    st = W.apply_golden_recipe(W.portable_state_dict(desc, 0))
+    sep = SEP.HipSeparator(st, None, device=0, max_batch_segments=256)
+    cfg = CSS.CssCfg()
+    rc = CSS.make_run_cfg(cfg, FS, 7)
+    recs = [np.ascontiguousarray(SYN.synth_meeting(seconds, 7, seed=1000 + i)[0]) for i in range(n_streams)]
+    t = np.arange(int(round(seconds * rate))) * (float(FS) / rate)
+    at = np.arange(recs[0].shape[0])
+    q16 = [np.clip(np.rint(np.stack([np.interp(t, at, x[:, c]) for c in range(7)], axis=1) * 0.2 * 32768.0), -32768, 32767).astype(np.int16)
+           for x in recs]
+    recs = [sep.handle.resample(q, rate) if rate != FS else np.ascontiguousarray(q.astype(np.float32) / np.float32(32768.0)) for q in q16]
+    if pinned:
+        q16 = [LIB.pinned_copy(q) for q in q16]
+    sep.handle.run(recs[0][:FS * 10], rc)   # warm-up
+    refs = [sep.handle.run(x, rc).copy() for x in recs]
+    gain = 1.0
+    ocfg = LIB.stream_output_cfg(out_rate, "int16" if out_pcm16 else "float32", gain)
+    up, down = ocfg.up, ocfg.down
+
+    def definition(w):
+        y = w if up == down else np.ascontiguousarray(sep.handle.resample(w.T, FS, out_rate).T)
+        return np.stack([LIB.pcm16_encode(v, gain)[0] for v in y]) if out_pcm16 else y
+    want = [definition(w) for w in refs]
+    step = int(round_s * rate)
+    ms = {"O": [], "F": [], "F_push": []}
+    same = {"O": True, "F": True}
+    worst = 0.0   # arm F against the definition: float64 taps and sums against the float32 chain
+    launches = []
+
+    def host_convert(res):
+        out = []
+        for per_stream in res:
+            y = [v if up == down else resample_poly(v, up, down) for v in per_stream]
+            out.append([np.clip(np.rint(v.astype(np.float64) * gain * 32767.0), -32768, 32767).astype(np.int16) for v in y] if out_pcm16 else y)
+        return out
+
+    def one_pass(first, timed):
+        so = [STR.CssStream(sep, cfg, input_rate=rate if rate != FS else None,
+                            output=dict(rate=out_rate, dtype="int16" if out_pcm16 else "float32", gain=gain)) for _ in recs]
+        sf = [STR.CssStream(sep, cfg, input_rate=rate if rate != FS else None) for _ in recs]
+        go, gf = STR.CssStreamGroup(so), STR.CssStreamGroup(sf)
+        emo, emf = [0] * n_streams, [0] * n_streams
+        n_rounds = (q16[0].shape[0] + step - 1) // step if timed else 2 * block
+        for r in range(n_rounds):
+            chunks = [q[r * step:(r + 1) * step] for q in q16]
+            order = "OF" if (r // block + (first == "F")) % 2 == 0 else "FO"
+            for arm in order:
+                t0 = time.perf_counter()
+                if arm == "O":
+                    res_o = go.push_pcm16(chunks)
+                    dt = time.perf_counter() - t0
+                    launches.append(sep.handle.stream_output_stats())
+                else:
+                    res_f = gf.push_pcm16(chunks)
+                    dt_push = time.perf_counter() - t0
+                    conv = host_convert(res_f)
+                    dt = time.perf_counter() - t0
+                if timed:
+                    ms[arm].append(dt * 1e3)
+                    if arm == "F":
+                        ms["F_push"].append(dt_push * 1e3)
+            if not timed:
+                continue
+            for i in range(n_streams):
+                got = np.stack(res_o[i])
+                same["O"] = same["O"] and bool(np.array_equal(got, want[i][:, emo[i]:emo[i] + got.shape[1]]))
+                emo[i] += got.shape[1]
+                gf_ = np.stack(res_f[i])
+                same["F"] = same["F"] and bool(np.array_equal(gf_, refs[i][:, emf[i]:emf[i] + gf_.shape[1]]))
+                emf[i] += gf_.shape[1]
+        if timed:
+            for i in range(n_streams):
+                got = np.stack(so[i].finish())
+                same["O"] = same["O"] and bool(np.array_equal(got, want[i][:, emo[i]:])) and emo[i] + got.shape[1] == want[i].shape[1]
+                sf[i].finish()
+        dev = (so[0].info().device_bytes, sf[0].info().device_bytes)
+        for s in so + sf:
+            s.close()
+        return dev
+
+    one_pass("O", False)
+    dev = (0, 0)
+    for p in range(passes):
+        dev = one_pass("OF"[p % 2], True)
+    # one whole recording through the host's route, against the definition (in output LSB for int16, else absolute)
+    whole = host_convert([list(refs[0])])[0]
+    worst = float(np.abs(np.stack(whole).astype(np.float64) - want[0].astype(np.float64)).max())
+    per_tick_in = n_streams * step * 7 * 2
+    spk = 3 * n_streams
+    res = {"model": "mc_v1 (18 blocks, exact float32)", "cfg": "3 s / 1.5 s segments, defaults", "streams": n_streams, "meeting_s": seconds,
+           "round_s": round_s, "block_rounds": block, "passes": passes,
+           "input": "16-bit PCM at %d Hz, 0.2 of full scale (%s)" % (rate, "page-locked" if pinned else "pageable"),
+           "output": "%s at %d Hz, gain %g" % ("int16" if out_pcm16 else "float32", out_rate, gain),
+           "device_bytes_per_stream": {"O": int(dev[0]), "F": int(dev[1])},
+           "output_kernel_launches_and_rounds_per_call_max": [int(max(a for a, _ in launches)), int(max(b for _, b in launches))],
+           "pcie_bytes_per_tick": {"O": {"in": per_tick_in, "out": int(spk * round_s * out_rate * (2 if out_pcm16 else 4))},
+                                   "F": {"in": per_tick_in, "out": int(spk * round_s * FS * 4)}},
+           "host_route_max_abs_difference_from_the_definition": worst, "arms": {}}
+    for arm, what in (("O", "one css_stream_push_many_pcm16 per tick, streams with the output format, no model-rate out_host"),
+                      ("F", "the same push on streams without an output format + scipy.signal.resample_poly%s on the host for %d speaker streams"
+                       % (" and the int16 conversion" if out_pcm16 else "", spk)),
+                      ("F_push", "arm F's push alone")):
+        v = np.array(ms[arm])
+        res["arms"][arm] = {"what": what, "ticks": int(v.size), "tick_ms_p50": round(float(np.percentile(v, 50)), 3),
+                            "tick_ms_p10": round(float(np.percentile(v, 10)), 3), "tick_ms_p90": round(float(np.percentile(v, 90)), 3),
+                            "tick_ms_p99": round(float(np.percentile(v, 99)), 3)}
+        if arm in same:
+            res["arms"][arm]["bit_identical"] = same[arm]
+    res["p50_ratio_O_over_F"] = round(res["arms"]["O"]["tick_ms_p50"] / res["arms"]["F"]["tick_ms_p50"], 4)
+    sep.close()
+    text = json.dumps(res, indent=1)
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write(text + "\n")
+    print(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--minutes", type=float, nargs="+", default=[1.0, 10.0])
@@ -350,9 +483,14 @@ def main():
                     "css_stream_windows (arm W) and the host's route to the same windows (arm H); with --preview also one "
                     "css_stream_present_windows (arm PW)")
     ap.add_argument("--history", action="store_true", help="with --streams --handoff: streams keep a 3000-frame history; arm B alone")
+    ap.add_argument("--out-rate", type=int, default=0, help="with --streams --rate: arm O, streams with the output format at this rate, against arm F, "
+                    "plain streams + scipy.signal.resample_poly on the host")
+    ap.add_argument("--out-pcm16", action="store_true", help="with --out-rate: the output is int16 (the host's route converts too)")
     ap.add_argument("--passes", type=int, default=2, help="with --streams: timed passes over the recordings")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.streams and a.out_rate:
+        return output_bench(a.streams, a.out, a.rate or FS, a.out_rate, a.out_pcm16, pinned=a.pinned, passes=a.passes)
     if a.streams:
         return group_bench(a.streams, a.out, handoff=a.handoff, only_grouped=a.only_grouped, pcm16=a.pcm16, pinned=a.pinned, rate=a.rate,
                            preview=a.preview, passes=a.passes, window=a.window and a.handoff, history=a.history and a.handoff)
