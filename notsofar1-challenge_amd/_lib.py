@@ -198,6 +198,32 @@ class CssPcmEdgesDesc(C.Structure):
                [(n, C.c_int64) for n in ("n", "n_pad", "i_lo", "i_hi", "count", "out_ld", "in_elems", "out_elems")]
 
 
+class CssMvdrSet(C.Structure):                  # include/css_mi355_backend.h
+    _fields_ = [(n, C.c_int64) for n in ("seg_lo", "nseg", "scm_off", "bfw_off")]
+
+
+class CssMvdrDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("form", "C", "F", "S", "T", "hop", "nseg", "use_mvdr", "n_sets", "reserved")] + \
+               [(n, C.c_float) for n in ("mask_floor", "reserved_f")] + \
+               [(n, C.c_int64) for n in ("seg_lo", "stft_frames", "T_ld", "mask_ld", "x_floats", "mask_floats", "override_bytes",
+                                         "scm_doubles", "bfw_doubles", "sep_floats")] + \
+               [("sets", CssMvdrSet * 16)]
+
+
+class CssStitchSet(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("num_segments", "mask_off", "sep_off", "costs_off")]
+
+
+class CssStitchDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("form", "S", "F", "T", "hop", "loss", "input", "KIp", "y_split", "has_level", "dilation",
+                                         "erosion", "n_sets")] + \
+               [("level", C.c_uint32)] + \
+               [(n, C.c_float) for n in ("activity_th", "reserved_f")] + \
+               [(n, C.c_int64) for n in ("num_segments", "T_long", "mask_ld", "lo", "hi", "mask_floats", "sep_floats", "costs_doubles",
+                                         "perms_ints", "mask_st_floats", "activity_floats", "act_bytes", "y_floats")] + \
+               [("sets", CssStitchSet * 16)]
+
+
 class CssKernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("ms", C.c_float), ("launches", C.c_int32)]
 
@@ -372,6 +398,12 @@ SIGNATURES_STREAM_OUT = {
     "css_stream_output_peaks": (C.c_int, [_P, C.c_int32, _P]),
     "css_stream_output_stats": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
 }
+# the entry points include/css_mi355_backend.h declares (the kernels of csrc/mvdr.hip and csrc/stitch.hip on caller data), the
+# eleventh table load() applies
+SIGNATURES_BACKEND = {
+    "css_mvdr_host": (C.c_int, [_P, C.POINTER(CssMvdrDesc), _P, _P, _P, _P, _P, _P]),
+    "css_stitch_host": (C.c_int, [_P, C.POINTER(CssStitchDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+}
 SESSION_SCAN_CHUNK = 1024                        # CSS_SESSION_SCAN_CHUNK: the keep-scan kernel's step, in gate frames / sample blocks
 RESAMPLE_TILE = 256                              # output samples per block of the two resampling kernels (resample.hip RS_TILE)
 
@@ -418,7 +450,7 @@ def load() -> C.CDLL:
                               list(SIGNATURES_PREVIEW_HANDOFF.items()) + list(SIGNATURES_ENCODER.items()) +
                               list(SIGNATURES_WINDOW.items()) + list(SIGNATURES_PRESENT.items()) +
                               list(SIGNATURES_FRONTEND.items()) + list(SIGNATURES_SESSION_HANDOFF.items()) +
-                              list(SIGNATURES_STREAM_OUT.items())):
+                              list(SIGNATURES_STREAM_OUT.items()) + list(SIGNATURES_BACKEND.items())):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -1014,6 +1046,54 @@ class Handle:
         check(self.h, self.lib.css_pcm_edges_host(self.h, C.byref(d), _np_ptr(src), None if out is None else _np_ptr(out),
                                                   None if peak is None else _np_ptr(peak)))
         return out, peak
+
+    # ---- the kernels of csrc/mvdr.hip and csrc/stitch.hip on caller data (include/css_mi355_backend.h;
+    #      tests/test_hip_backend_kernels.py).  Arrays are the WHOLE allocations (None where a form takes none); the arrays a form
+    #      writes are copied first and returned as the launch left them.
+    def mvdr_host(self, form: int, *, X=None, masks=None, override=None, scm=None, bfw=None, sep=None, sets=(), **fields):
+        """launch_scm (0), launch_mvdr_solve (1), launch_mvdr_solve_multi (2; sets = (seg_lo, nseg, scm_off, bfw_off) each),
+        launch_beamform (3), launch_segment_power_norm (4) (css_mvdr_host); fields are the descriptor's.  Returns the array the
+        form writes: scm, bfw, sep, sep."""
+        arr = lambda a, t, own: None if a is None else (np.array(a, dtype=t).reshape(-1) if own else np.ascontiguousarray(a, dtype=t).reshape(-1))
+        X, masks, override = arr(X, np.float32, False), arr(masks, np.float32, False), arr(override, np.uint8, False)
+        scm, bfw, sep = arr(scm, np.float64, form == 0), arr(bfw, np.float64, form in (1, 2)), arr(sep, np.float32, form >= 3)
+        n = lambda a: 0 if a is None else a.size
+        d = CssMvdrDesc(form=int(form), n_sets=len(sets), x_floats=n(X), mask_floats=n(masks), override_bytes=n(override),
+                        scm_doubles=n(scm), bfw_doubles=n(bfw), sep_floats=n(sep),
+                        **{k: (float(v) if k == "mask_floor" else int(v)) for k, v in fields.items()})
+        for i, e in enumerate(sets):
+            d.sets[i] = CssMvdrSet(*(int(v) for v in e))
+        p = lambda a: None if a is None else _np_ptr(a)
+        check(self.h, self.lib.css_mvdr_host(self.h, C.byref(d), p(X), p(masks), p(override), p(scm), p(bfw), p(sep)))
+        return (scm, bfw, bfw, sep, sep)[int(form)]
+
+    def stitch_host(self, form: int, *, masks=None, sep=None, windows=None, costs=None, perms=None, mask_st=None, activity=None,
+                    act_b=None, act_tmp=None, act_final=None, Y=None, sets=(), level=None, **fields):
+        """launch_pit_costs (0), launch_pit_costs_multi (1; sets = (num_segments, mask_off, sep_off, costs_off) each),
+        launch_pit_scan (2), launch_ola_masks (3), launch_morphology (4), launch_ola_stft (5) (css_stitch_host); fields are the
+        descriptor's; level: None (absent) or the word.  Returns what the form writes: costs; costs; perms; (mask_st, activity,
+        act_b); (act_tmp, act_final); Y."""
+        arr = lambda a, t, own: None if a is None else (np.array(a, dtype=t).reshape(-1) if own else np.ascontiguousarray(a, dtype=t).reshape(-1))
+        masks, sep, windows = arr(masks, np.float32, False), arr(sep, np.float32, False), arr(windows, np.float32, False)
+        costs, perms = arr(costs, np.float64, form <= 1), arr(perms, np.int32, form == 2)
+        mask_st, activity, act_b = arr(mask_st, np.float32, True), arr(activity, np.float32, True), arr(act_b, np.uint8, form == 3)
+        act_tmp, act_final, Y = arr(act_tmp, np.uint8, True), arr(act_final, np.uint8, form == 4), arr(Y, np.float32, True)
+        n = lambda a: 0 if a is None else a.size
+        acts = [a.size for a in (act_b, act_tmp, act_final) if a is not None]
+        if len(set(acts)) > 1:
+            raise ValueError("act_b, act_tmp and act_final have one length")
+        if windows is not None and windows.size != 3 * int(fields["T"]):
+            raise ValueError("windows [3][T]")
+        d = CssStitchDesc(form=int(form), n_sets=len(sets), has_level=int(level is not None), level=int(level or 0),
+                          mask_floats=n(masks), sep_floats=n(sep), costs_doubles=n(costs), perms_ints=n(perms),
+                          mask_st_floats=n(mask_st), activity_floats=n(activity), act_bytes=acts[0] if acts else 0, y_floats=n(Y),
+                          **{k: (float(v) if k == "activity_th" else int(v)) for k, v in fields.items()})
+        for i, e in enumerate(sets):
+            d.sets[i] = CssStitchSet(*(int(v) for v in e))
+        p = lambda a: None if a is None else _np_ptr(a)
+        check(self.h, self.lib.css_stitch_host(self.h, C.byref(d), p(masks), p(sep), p(windows), p(costs), p(perms), p(mask_st),
+                                               p(activity), p(act_b), p(act_tmp), p(act_final), p(Y)))
+        return (costs, costs, perms, (mask_st, activity, act_b), (act_tmp, act_final), Y)[int(form)]
 
     # ---- RCCL through the C ABI (css_comm_*): what a host in another language would call
     def comm_init(self, unique_id: bytes, nranks: int, rank: int):

@@ -150,6 +150,24 @@ __device__ __forceinline__ float css_phase_of(float re, float im) {
     return (im == 0.f && re < 0.f) ? CSS_PHASE_NEG_REAL : atan2f(im, re);
 }
 
+// float32 product, sum and quotient that stay ONE rounding each, whatever follows them.  __fmul_rn / __fadd_rn / __fdiv_rn are a
+// plain * + / in this toolchain (__clang_hip_math.h without OCML_BASIC_ROUNDED_OPERATIONS) and carry the contraction of the
+// code around them: `__fadd_rn(v, __fmul_rn(w, m))` compiled to one FMA in the overlap-add kernels, whose sums then were not the
+// reference's `zeros += w * x` from the second contributor on.  An operation compiled with contraction off
+// cannot become half of an FMA.
+__device__ __forceinline__ float css_mul_rn(float x, float y) {
+#pragma clang fp contract(off)
+    return x * y;
+}
+__device__ __forceinline__ float css_add_rn(float x, float y) {
+#pragma clang fp contract(off)
+    return x + y;
+}
+__device__ __forceinline__ float css_div_rn(float x, float y) {
+#pragma clang fp contract(off)
+    return x / y;
+}
+
 // ------------------------------------------------------------------------------------------------
 // frontend.hip -- PCM layout, features, inverse-transform overlap-add
 // ------------------------------------------------------------------------------------------------
@@ -306,13 +324,22 @@ struct MvdrArgs {
     float mask_floor;
     int use_mvdr;
 };
+// PRECONDITIONS of the launches below (the paths guarantee them; css_mvdr_host, include/css_mi355_backend.h, refuses the rest):
+//   C == 7 for launch_scm, both solves and the MVDR beamformer (the packed 7 x 7 layout); use_mvdr == 0 reads microphone 0 alone
+//   1 <= S <= 3: scm_kernel sorts the frames of the S + 1 mask rows into FOUR lists, one per group of 16 lanes
+//   mask_ld >= (seg_lo + nseg) T; T_ld covers the last valid frame min(stft_frames, (seg_lo + nseg - 1) hop + T): frames from
+//   stft_frames on are never read
+//   an override byte is a winner index below S + 1, or 16 | bits with at least one of the bits 0 .. S set (a frame no mask wins
+//   would count towards no list and no plain sum)
 bool launch_scm(const MvdrArgs& a, hipStream_t s);   // false: the LDS of a long-segment launch could not be reserved
 void launch_mvdr_solve(const MvdrArgs& a, hipStream_t s);
 // the same for n sessions' argument sets in one launch (a queue group's sessions; each result is the per-session launch's)
 constexpr int MVDR_MULTI_MAX = 8;
 void launch_mvdr_solve_multi(const MvdrArgs* a, int n, hipStream_t s);
 void launch_beamform(const MvdrArgs& a, hipStream_t s);
-// optional power normalisation (css.py:233-247): scales sep of each segment in place
+// optional power normalisation (css.py:233-247): scales sep of each segment in place by the float64 gain, each value rounded to
+// float32 once.  A segment without a valid frame, or whose reference microphone and stream sum are both silent, has the gain
+// 0 / 0 of the reference's own formula: every value of it becomes NaN (the paths' segments all hold valid frames)
 void launch_segment_power_norm(const MvdrArgs& a, double* scratch, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------
@@ -333,6 +360,11 @@ struct StitchArgs {
     int y_split;               // Y rows as split-f16 GEMM operands (split_f16.hpp) instead of float32
     const unsigned int* level; // with y_split: the rows are scaled by level_gain(level) (split_f16.hpp); null = 1
 };
+// PRECONDITIONS of the launches below (css_stitch_host, include/css_mi355_backend.h, refuses the rest): 1 <= S <= 4 (SMAX);
+// 1 <= hop <= T, and hop < T for the costs (their mean divides by F (T - hop)); mask_ld >= num_segments T; every row of perms
+// that a launch reads is a permutation of 0 .. S - 1 (it indexes mask rows and spectra); T_long <= (num_segments - 1) hop + T:
+// every frame is covered by a segment (a frame none covers would be 0 / 0 in the masks); KIp >= 2 F, KIp % 32 == 0 with y_split;
+// launch_ola_stft's tile is 16 (2 F + 1) floats of dynamic LDS: F <= 511 without raising the kernel's limit.
 // scratch: pit_cost_scratch_bytes(total boundaries) bytes, indexed by absolute boundary
 size_t pit_cost_scratch_bytes(int64_t n_boundaries);
 void launch_pit_costs(const StitchArgs& a, int loss, int input, int64_t b_lo, int64_t b_hi, double* scratch, double* costs,

@@ -500,7 +500,8 @@ __global__ __launch_bounds__(256) void beamform_kernel(MvdrArgs a) {
             xi[c] = ok ? a.X[((int64_t)c * 2 * F + F + f) * a.T_ld + st + t] : 0.f;
         }
         for (int k = 0; k < S; ++k) {
-            float yr, yi;
+            const float m = fmaxf(a.masks[((int64_t)k * F + f) * a.mask_ld + seg * (int64_t)T + t], a.mask_floor);
+            float2* o = reinterpret_cast<float2*>(a.sep) + ((seg * S + k) * (int64_t)F + f) * T + t;
             if (a.use_mvdr) {
                 const double* w = a.bfw + ((seg * S + k) * (int64_t)F + f) * NC * 2;
                 double sr = 0.0, si = 0.0;
@@ -510,15 +511,13 @@ __global__ __launch_bounds__(256) void beamform_kernel(MvdrArgs a) {
                     sr += wr * xr[c] + wi * xi[c];
                     si += wr * xi[c] - wi * xr[c];
                 }
-                yr = (float)sr;
-                yi = (float)si;
+                // the mask product in float64 too and ONE rounding to float32: rounding y and then y m again left the value up to
+                // 2 x 2^-24 of it from the exact product; a float32 mask is exact in float64
+                const double md = (double)m;
+                *o = make_float2((float)(sr * md), (float)(si * md));
             } else {
-                yr = xr[0];
-                yi = xi[0];
+                *o = make_float2(xr[0] * m, xi[0] * m);
             }
-            const float m = fmaxf(a.masks[((int64_t)k * F + f) * a.mask_ld + seg * (int64_t)T + t], a.mask_floor);
-            float2* o = reinterpret_cast<float2*>(a.sep) + ((seg * S + k) * (int64_t)F + f) * T + t;
-            *o = make_float2(yr * m, yi * m);
         }
     }
 }
@@ -572,11 +571,13 @@ __global__ void segment_scale_kernel(MvdrArgs a, const double* __restrict__ scra
     const int64_t n = (int64_t)a.S * a.F * a.T;
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float g = (float)scratch[segl];
+    // the float64 gain and ONE rounding to float32 per value: a gain rounded to float32 and a float32 product after it left the
+    // value up to 2 x 2^-24 of it from sep g
+    const double g = scratch[segl];
     float2* p = reinterpret_cast<float2*>(a.sep) + seg * n + i;
     float2 v = *p;
-    v.x *= g;
-    v.y *= g;
+    v.x = (float)((double)v.x * g);
+    v.y = (float)((double)v.y * g);
     *p = v;
 }
 

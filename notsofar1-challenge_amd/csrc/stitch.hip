@@ -367,7 +367,7 @@ struct Covering {
         float ws = 0.f;
 #pragma unroll
         for (int i = 0; i < NC; ++i)
-            if (on[i]) ws = __fadd_rn(ws, w[i]);
+            if (on[i]) ws = css_add_rn(ws, w[i]);
         return ws;
     }
 };
@@ -377,7 +377,8 @@ struct Covering {
 //   mask_st[s][f][t] = (sum_i w_i[t - st_i] * mask_i[perm_i[s]][f][t - st_i]) / (sum_i w_i[t - st_i])
 //   activity[s][t]   = mean_f mask_st[s][f][t];   act_b = activity >= th
 // The float32 operation order of the reference (multiply, add in ascending segment order, divide) is
-// reproduced with explicit round-to-nearest intrinsics so no FMA contraction changes a bit.
+// reproduced with operations compiled with contraction off (kernels.hpp css_mul_rn / css_add_rn / css_div_rn), so no FMA
+// changes a bit.
 // Block = 16 frames x 16 frequency groups (a 60 s meeting is only 3749 frames: 64-frame blocks gave 177 blocks for
 // 256 CUs); lanes run over time (contiguous mask reads); the frequency mean is accumulated in float64 and the 16
 // partial sums are added in a fixed order.
@@ -395,16 +396,16 @@ __global__ __launch_bounds__(256) void ola_masks_kernel(StitchArgs a, int64_t t_
         if (active) {
             const int64_t s0 = first_seg(a, t), s1 = last_seg(a, t);
             float ws = 0.f;
-            for (int64_t seg = s0; seg <= s1; ++seg) ws = __fadd_rn(ws, seg_weight(a, seg, (int)(t - seg * a.hop)));
+            for (int64_t seg = s0; seg <= s1; ++seg) ws = css_add_rn(ws, seg_weight(a, seg, (int)(t - seg * a.hop)));
             float* out = a.mask_st + (int64_t)s * a.F * a.T_long + t;
             for (int f = fg; f < a.F; f += OM_FG) {
                 float v = 0.f;
                 for (int64_t seg = s0; seg <= s1; ++seg) {
                     const int tl = (int)(t - seg * a.hop);
                     const float m = a.masks[((int64_t)a.perms[seg * a.S + s] * a.F + f) * a.mask_ld + seg * a.T + tl];
-                    v = __fadd_rn(v, __fmul_rn(seg_weight(a, seg, tl), m));
+                    v = css_add_rn(v, css_mul_rn(seg_weight(a, seg, tl), m));
                 }
-                v = __fdiv_rn(v, ws);
+                v = css_div_rn(v, ws);
                 out[(int64_t)f * a.T_long] = v;
                 sum += (double)v;
             }
@@ -423,8 +424,8 @@ __global__ __launch_bounds__(256) void ola_masks_kernel(StitchArgs a, int64_t t_
                 float v = 0.f;
 #pragma unroll
                 for (int i = 0; i < NC; ++i)
-                    if (c.on[i]) v = __fadd_rn(v, __fmul_rn(c.w[i], mp[i][(int64_t)f * a.mask_ld]));
-                v = __fdiv_rn(v, wsum);
+                    if (c.on[i]) v = css_add_rn(v, css_mul_rn(c.w[i], mp[i][(int64_t)f * a.mask_ld]));
+                v = css_div_rn(v, wsum);
                 out[(int64_t)f * a.T_long] = v;
                 sum += (double)v;
             }
@@ -504,7 +505,7 @@ __global__ __launch_bounds__(256) void ola_stft_kernel(StitchArgs a, int64_t t_l
         float wsum = 0.f;
         if (active) {
             gs0 = first_seg(a, t); gs1 = last_seg(a, t);
-            for (int64_t seg = gs0; seg <= gs1; ++seg) wsum = __fadd_rn(wsum, seg_weight(a, seg, (int)(t - seg * a.hop)));
+            for (int64_t seg = gs0; seg <= gs1; ++seg) wsum = css_add_rn(wsum, seg_weight(a, seg, (int)(t - seg * a.hop)));
         }
         for (int f = fy; f < a.F; f += 16) {
             float re = 0.f, im = 0.f;
@@ -513,12 +514,12 @@ __global__ __launch_bounds__(256) void ola_stft_kernel(StitchArgs a, int64_t t_l
                     const int tl = (int)(t - seg * a.hop);
                     const float w = seg_weight(a, seg, tl);
                     const float2 v = sep[((seg * a.S + a.perms[seg * a.S + s]) * (int64_t)a.F + f) * a.T + tl];
-                    re = __fadd_rn(re, __fmul_rn(w, v.x));
-                    im = __fadd_rn(im, __fmul_rn(w, v.y));
+                    re = css_add_rn(re, css_mul_rn(w, v.x));
+                    im = css_add_rn(im, css_mul_rn(w, v.y));
                 }
                 if (gs1 >= gs0) {
-                    re = __fmul_rn(__fdiv_rn(re, wsum), gate);
-                    im = __fmul_rn(__fdiv_rn(im, wsum), gate);
+                    re = css_mul_rn(css_div_rn(re, wsum), gate);
+                    im = css_mul_rn(css_div_rn(im, wsum), gate);
                 }
             }
             tile[tx * TS + f] = re;
@@ -545,11 +546,11 @@ __global__ __launch_bounds__(256) void ola_stft_kernel(StitchArgs a, int64_t t_l
                 for (int i = 0; i < NC; ++i)
                     if (c.on[i]) {
                         const float2 v = pp[i][(int64_t)f * a.T];
-                        re = __fadd_rn(re, __fmul_rn(c.w[i], v.x));
-                        im = __fadd_rn(im, __fmul_rn(c.w[i], v.y));
+                        re = css_add_rn(re, css_mul_rn(c.w[i], v.x));
+                        im = css_add_rn(im, css_mul_rn(c.w[i], v.y));
                     }
-                re = __fmul_rn(__fdiv_rn(re, wsum), gate);
-                im = __fmul_rn(__fdiv_rn(im, wsum), gate);
+                re = css_mul_rn(css_div_rn(re, wsum), gate);
+                im = css_mul_rn(css_div_rn(im, wsum), gate);
             }
             tile[tx * TS + f] = re;
             tile[tx * TS + a.F + f] = im;
@@ -562,7 +563,10 @@ __global__ __launch_bounds__(256) void ola_stft_kernel(StitchArgs a, int64_t t_l
         float* out = a.Y + ((int64_t)s * a.T_long + t0 + r) * a.KIp;
         for (int j = threadIdx.x; j < a.KIp; j += 256) {
             const float v = j < 2 * a.F ? tile[r * TS + j] : 0.f;  // zero K padding
-            if (a.y_split) split_store(reinterpret_cast<_Float16*>(out), j, v * lvl);   // operand rows of the synthesis GEMM
+            // operand rows of the synthesis GEMM.  (+ 0.f: a gated frame holds -0 where the sum was negative, and whether the halves
+            // of -0 leave as -0 or +0 is otherwise the compiler's choice -- product and conversion fuse into an FMA with a +0 addend
+            // or they do not; +0 either way now, the bits the fused form has always written)
+            if (a.y_split) split_store(reinterpret_cast<_Float16*>(out), j, v * lvl + 0.f);
             else out[j] = v;
         }
     }

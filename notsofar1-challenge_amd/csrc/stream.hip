@@ -49,15 +49,15 @@ __device__ __forceinline__ void stream_activity_body(const StreamStitchArgs& a, 
         int64_t s0, s1;
         stream_cover(a, t, &s0, &s1);
         float ws = 0.f;
-        for (int64_t seg = s0; seg <= s1; ++seg) ws = __fadd_rn(ws, stream_seg_weight(a, seg, (int)(t - seg * a.hop)));
+        for (int64_t seg = s0; seg <= s1; ++seg) ws = css_add_rn(ws, stream_seg_weight(a, seg, (int)(t - seg * a.hop)));
         for (int f = fg; f < a.F; f += SA_FG) {
             float v = 0.f;
             for (int64_t seg = s0; seg <= s1; ++seg) {
                 const int tl = (int)(t - seg * a.hop);
                 const float m = a.masks[((int64_t)a.perms[seg * a.S + s] * a.F + f) * a.mask_ld + seg * a.T + tl];
-                v = __fadd_rn(v, __fmul_rn(stream_seg_weight(a, seg, tl), m));
+                v = css_add_rn(v, css_mul_rn(stream_seg_weight(a, seg, tl), m));
             }
-            sum += (double)__fdiv_rn(v, ws);
+            sum += (double)css_div_rn(v, ws);
         }
     }
     red[fg][lane] = sum;
@@ -117,7 +117,7 @@ __device__ __forceinline__ void stream_gate_ola_body(const StreamStitchArgs& a, 
     float wsum = 0.f;
     if (active) {
         stream_cover(a, t, &gs0, &gs1);
-        for (int64_t seg = gs0; seg <= gs1; ++seg) wsum = __fadd_rn(wsum, stream_seg_weight(a, seg, (int)(t - seg * a.hop)));
+        for (int64_t seg = gs0; seg <= gs1; ++seg) wsum = css_add_rn(wsum, stream_seg_weight(a, seg, (int)(t - seg * a.hop)));
     }
     for (int f = fy; f < a.F; f += 16) {
         float re = 0.f, im = 0.f;
@@ -126,12 +126,12 @@ __device__ __forceinline__ void stream_gate_ola_body(const StreamStitchArgs& a, 
                 const int tl = (int)(t - seg * a.hop);
                 const float w = stream_seg_weight(a, seg, tl);
                 const float2 v = sep[((seg * a.S + a.perms[seg * a.S + s]) * (int64_t)a.F + f) * a.T + tl];
-                re = __fadd_rn(re, __fmul_rn(w, v.x));
-                im = __fadd_rn(im, __fmul_rn(w, v.y));
+                re = css_add_rn(re, css_mul_rn(w, v.x));
+                im = css_add_rn(im, css_mul_rn(w, v.y));
             }
             if (gs1 >= gs0) {
-                re = __fmul_rn(__fdiv_rn(re, wsum), gate);
-                im = __fmul_rn(__fdiv_rn(im, wsum), gate);
+                re = css_mul_rn(css_div_rn(re, wsum), gate);
+                im = css_mul_rn(css_div_rn(im, wsum), gate);
             }
         }
         tile[tx * TS + f] = re;
