@@ -2,7 +2,7 @@
 // nothing here is exported on purpose.  css_ctx is the handle: the model, its streams and workspaces, and -- through SessState --
 // the session the stage entry points see.
 // Four owners hold what the library keeps on the GPU: DevBuf (device memory), PinnedBuf (page-locked host memory), Event (a
-// hipEvent_t) and std::unique_ptr (a stream's optional parts, api_stream.hip).  The rule is "members, not lists": a resource is a
+// hipEvent_t) and std::unique_ptr (a stream's optional parts, api_stream.hpp).  The rule is "members, not lists": a resource is a
 // member of the handle, of a stream or of one call's stack and is released with it; no function enumerates what to free.
 // HIP streams stay explicit (css_destroy): the handle's own may be the caller's, and the order of synchronise and destroy matters.
 #pragma once
@@ -178,6 +178,9 @@ struct RunIo {
     }
 };
 
+struct StreamState;   // api_stream.hpp: a streamed session and what its hand-off shares on a handle; owned through
+struct HandoffCtx;    // css_stream_close / stream_destroy_all (api_stream.hip), where the order of synchronise and delete matters
+
 struct css_ctx : SessState {
     CssModelDesc d{};
     int device = 0;
@@ -341,9 +344,9 @@ struct css_ctx : SessState {
     float prof_pair_ms = 0.f;
     int32_t prof_pairs = 0;
     FeatOpts feat_opts{};   // css_set_feature_options (css_create: the shipped configuration)
-    void* streams[CSS_MAX_STREAMS] = {};   // css_stream_open: open streams (api_stream.hip StreamState), by id
-    void* handoff = nullptr;   // api_stream.hip: what the hand-off of streams shares on this handle (HandoffCtx), made on first use
-    int32_t stream_out_launches = 0, stream_out_rounds = 0;   // api_stream.hip: the output kernel in the last push / finish call
+    StreamState* streams[CSS_MAX_STREAMS] = {};   // css_stream_open: open streams (api_stream.hpp), by id
+    HandoffCtx* handoff = nullptr;   // api_stream_handoff.hip: what the hand-off of streams shares on this handle, made on first use
+    int32_t stream_out_launches = 0, stream_out_rounds = 0;   // api_stream.hip stream_round: the output kernel in the last push / finish call
     DevBuf stream_masks;   // api_stream.hip: the mask head's output for one estimator batch of streamed segments (never `masks`:
                            // the handle's own session keeps its bits between two pushes)
 

@@ -221,7 +221,7 @@ void launch_handoff_gather(const float* wav, const int64_t* regions, const int64
                            int64_t total, hipStream_t s);
 void launch_handoff_mel(const float* spec, int64_t ld, int64_t nfr, const float* w, int n_mels, float* mel, int* gmax, hipStream_t s);
 
-// The hand-off of STREAMED sessions (api_stream.hip): per round of a push, the samples whose membership in the concatenation
+// The hand-off of STREAMED sessions (api_stream_handoff.hip): per round of a push, the samples whose membership in the concatenation
 // became decided are appended, the Whisper frames they complete are laid out as rows of ONE frame operand for all streams and
 // speakers of the round (one DFT product), and their raw log-mel values (no max - 8 clamp: that needs a maximum over a span
 // the consumer chooses) are written with the running maximum.  Table launches: blockIdx.z = entry (a stream), blockIdx.y =

@@ -270,6 +270,49 @@ def test_handoff_preview_and_model_rate_twins(env):
         assert np.array_equal(a[3], b[3]) and a[4] == b[4]
 
 
+def test_preview_with_handoff_on_a_stream_with_an_output_format(env):
+    """preview(handoff=True) after every push of a stream with the hand-off and an output format, beside a twin with the hand-off
+    alone (6 s, 2.0 s / 0.5 s segments): the same provisional samples and the same provisional hand-off; a preview writes nothing
+    at the playback rate, so the stream's outputs are the definition's"""
+    S, L = pkg("stream"), pkg("_lib")
+    x, w, y = env.rec("six"), env.w("six"), env.y("six", 48000)
+    sizes = [16000, 4000, 257, 24000]
+
+    def run(output):
+        outs, pvs = [], []
+        with S.CssStream(env.sep, env.cfg("six"), handoff=HANDOFF, output=output) as s:
+            n, i = 0, 0
+            while n < x.shape[0]:
+                k = min(sizes[i % len(sizes)], x.shape[0] - n)
+                outs.append(np.stack(s.push(x[n:n + k])))
+                n += k
+                i += 1
+                total = s.output_total if output else 0
+                try:
+                    pv = np.stack(s.preview(handoff=True))
+                    ho = s.preview_handoff
+                    pvs.append((s.preview_first_sample, pv, ho.mel, ho.ranges, ho.activity, ho.raw_max.copy(), ho.first_activity_frame,
+                                ho.first_frame.copy()))
+                except AssertionError as e:   # (css_run refuses a prefix of less than two segments)
+                    assert "zero weights" in str(e)
+                    pvs.append(None)
+                assert not output or s.output_total == total
+            outs.append(np.stack(s.finish()))
+        return np.concatenate(outs, axis=1), pvs
+
+    out_a, pv_a = run(dict(rate=48000, dtype="int16", gain=0.5))
+    out_b, pv_b = run(None)
+    assert np.array_equal(out_a, np.stack([L.pcm16_encode(y[k], 0.5)[0] for k in range(3)])) and np.array_equal(out_b, w)
+    assert len(pv_a) == len(pv_b) and any(p is not None for p in pv_a)
+    for a, b in zip(pv_a, pv_b):
+        assert (a is None) == (b is None)
+        if a is None:
+            continue
+        assert a[0] == b[0] and np.array_equal(a[1], b[1]) and np.array_equal(a[5], b[5]) and a[6] == b[6] and np.array_equal(a[7], b[7])
+        for k in range(3):
+            assert np.array_equal(a[2][k], b[2][k]) and np.array_equal(a[3][k], b[3][k]) and np.array_equal(a[4][k], b[4][k])
+
+
 # ---- 6. peaks ------------------------------------------------------------------------------------------------------------------
 def test_peaks_are_run_pcm16s(env):
     S = pkg("stream")
