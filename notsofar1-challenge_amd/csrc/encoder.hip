@@ -2,29 +2,29 @@
 // LayerNorm (+ReLU / +scalar GLU), the depthwise-conv module and relative-position attention.
 #include "kernels.hpp"
 #include "split_f16.hpp"
+#include "wave.hpp"
 
 namespace css {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
-// Sum over the 64 lanes, every lane gets the total: four DPP steps inside each row of 16 lanes (quad swaps, then
-// the 8- and 16-lane mirrors), then the four row totals through scalar registers.  No LDS: __shfl_xor compiles to
-// ds_bpermute, and the six dependent LDS round trips of a butterfly (~100 cycles each) were most of a LayerNorm row.
-template <int CTRL>
-__device__ __forceinline__ float dpp_addf(float v) {
-    return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float wave_sum(float v) {
-    v = dpp_addf<0xB1>(v);    // quad_perm [1,0,3,2]
-    v = dpp_addf<0x4E>(v);    // quad_perm [2,3,0,1]
-    v = dpp_addf<0x141>(v);   // row_half_mirror
-    v = dpp_addf<0x140>(v);   // row_mirror
-    const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0));
-    const float r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16));
-    const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32));
-    const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
-    return (r0 + r1) + (r2 + r3);
+// The row statistic of nn.LayerNorm (eps 1e-5) for a wave that holds a row of D = 256 * NV floats, NV float4 per lane: centres v
+// in place and returns 1 / sqrt(variance + eps).
+template <int NV>
+__device__ __forceinline__ float ln_centre(float4 (&v)[NV]) {
+    constexpr int D = 256 * NV;
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
+    const float mean = wave_sum_dpp(s) * (1.0f / D);
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        v[i].x -= mean; v[i].y -= mean; v[i].z -= mean; v[i].w -= mean;
+        q += (v[i].x * v[i].x + v[i].y * v[i].y) + (v[i].z * v[i].z + v[i].w * v[i].w);
+    }
+    return 1.0f / sqrtf(wave_sum_dpp(q) * (1.0f / D) + 1e-5f);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -49,20 +49,9 @@ __global__ __launch_bounds__(64 * LN_ROWS) void layernorm_kernel(const float* __
     const int lane = threadIdx.x & 63;
     const float4* xr = reinterpret_cast<const float4*>(x + (int64_t)row * D);
     float4 v[NV];
-    float s = 0.f;
 #pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        v[i] = xr[lane + 64 * i];
-        s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-    }
-    const float mean = wave_sum(s) * (1.0f / D);
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        v[i].x -= mean; v[i].y -= mean; v[i].z -= mean; v[i].w -= mean;
-        q += (v[i].x * v[i].x + v[i].y * v[i].y) + (v[i].z * v[i].z + v[i].w * v[i].w);
-    }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) * (1.0f / D) + 1e-5f);
+    for (int i = 0; i < NV; ++i) v[i] = xr[lane + 64 * i];
+    const float rstd = ln_centre(v);
     float p0 = 0.f, p1 = 0.f, p2 = 0.f, p3 = 0.f;
     if (MODE == 2) { p0 = pw[0]; p1 = pw[1]; p2 = pw[2]; p3 = pw[3]; }
     // y: float32 rows (may be null); ys: the same rows in the split-f16 GEMM operand format (may be null)
@@ -104,17 +93,7 @@ __global__ __launch_bounds__(64 * LN_ROWS) void layernorm2_kernel(const float* _
     for (int i = 0; i < NV; ++i) v[i] = xr[lane + 64 * i];
 #pragma unroll
     for (int pass = 0; pass < 2; ++pass) {
-        float s = 0.f;
-#pragma unroll
-        for (int i = 0; i < NV; ++i) s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-        const float mean = wave_sum(s) * (1.0f / D);
-        float q = 0.f;
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            v[i].x -= mean; v[i].y -= mean; v[i].z -= mean; v[i].w -= mean;
-            q += (v[i].x * v[i].x + v[i].y * v[i].y) + (v[i].z * v[i].z + v[i].w * v[i].w);
-        }
-        const float rstd = 1.0f / sqrtf(wave_sum(q) * (1.0f / D) + 1e-5f);
+        const float rstd = ln_centre(v);
         const float* w = pass ? w2 : w1;
         const float* b = pass ? b2 : b1;
         float* yo = pass ? z : y;
@@ -291,17 +270,7 @@ __global__ __launch_bounds__(256 * NV * HV) void conv_module_kernel(const float*
             for (int j = 0; j < NV; ++j) dst[lane + 64 * j] = make_float4(0.f, 0.f, 0.f, 0.f);
             continue;
         }
-        float s = 0.f;
-#pragma unroll
-        for (int j = 0; j < NV; ++j) s += (v[i][j].x + v[i][j].y) + (v[i][j].z + v[i][j].w);
-        const float mean = wave_sum(s) * (1.0f / D);
-        float q = 0.f;
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            v[i][j].x -= mean; v[i][j].y -= mean; v[i][j].z -= mean; v[i][j].w -= mean;
-            q += (v[i][j].x * v[i][j].x + v[i][j].y * v[i][j].y) + (v[i][j].z * v[i][j].z + v[i][j].w * v[i][j].w);
-        }
-        const float rstd = 1.0f / sqrtf(wave_sum(q) * (1.0f / D) + 1e-5f);
+        const float rstd = ln_centre(v[i]);
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
             const float4 g = reinterpret_cast<const float4*>(lnw)[lane + 64 * j];
@@ -346,22 +315,13 @@ __global__ __launch_bounds__(256 * NV * HV) void conv_module_kernel(const float*
     for (int j = wave; j < RUN && t0 + j < T; j += NW) {
         const int64_t row = (int64_t)seg * T + t0 + j;
         float4 r[NV];
-        float s = 0.f;
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             r[i] = reinterpret_cast<const float4*>(tile + j * D)[lane + 64 * i];
             reinterpret_cast<float4*>(x_out + row * D)[lane + 64 * i] = r[i];
-            s += (r[i].x + r[i].y) + (r[i].z + r[i].w);
         }
         if (!z && !zs) continue;
-        const float mean = wave_sum(s) * (1.0f / D);
-        float q = 0.f;
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            r[i].x -= mean; r[i].y -= mean; r[i].z -= mean; r[i].w -= mean;
-            q += (r[i].x * r[i].x + r[i].y * r[i].y) + (r[i].z * r[i].z + r[i].w * r[i].w);
-        }
-        const float rstd = 1.0f / sqrtf(wave_sum(q) * (1.0f / D) + 1e-5f);
+        const float rstd = ln_centre(r);
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             const float4 g = reinterpret_cast<const float4*>(ln2w)[lane + 64 * i];
@@ -817,9 +777,8 @@ __global__ __launch_bounds__(256) void relpos_attn_long_kernel(const float* __re
     // has nothing else to cover a chain of dependent multiply-adds.
     const int sub = tid & 3, kq = tid >> 2;
     auto quad_sum = [](float v) {
-        v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xf, 0xf, false));   // quad_perm [1,0,3,2]
-        v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xf, 0xf, false));   // quad_perm [2,3,0,1]
-        return v;
+        v = dpp_add<0xB1>(v);   // quad_perm [1,0,3,2]
+        return dpp_add<0x4E>(v);   // quad_perm [2,3,0,1]
     };
     auto load_row = [&](const float* rowp, float (&row)[16]) {
 #pragma unroll
@@ -880,11 +839,10 @@ __global__ __launch_bounds__(256) void relpos_attn_long_kernel(const float* __re
         float* row = ss + (size_t)i * T;
         float mx = -INFINITY;
         for (int j = lane; j < T; j += 64) mx = fmaxf(mx, row[j]);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+        mx = wave_max_shfl(mx);
         float sum = 0.f;
         for (int j = lane; j < T; j += 64) { const float e = expf(row[j] - mx); row[j] = e; sum += e; }
-        sum = wave_sum(sum);
+        sum = wave_sum_dpp(sum);
         const float inv = 1.0f / sum;
         for (int j = lane; j < T; j += 64) row[j] *= inv;
     }

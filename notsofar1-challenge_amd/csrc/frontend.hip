@@ -6,31 +6,13 @@
 
 #include "kernels.hpp"
 #include "split_f16.hpp"
+#include "wave.hpp"
 
 namespace css {
 
 bool css_force_long_path() {   // kernels.hpp
     static const bool on = [] { const char* e = getenv("CSS_FORCE_LONG_PATH"); return e && atoi(e) != 0; }();
     return on;
-}
-
-
-// sum over the 64 lanes (every lane gets the total): DPP inside the rows of 16, row totals through scalar registers
-// (no ds_bpermute round trips; see wave_sum in encoder.hip)
-template <int CTRL>
-__device__ __forceinline__ float dpp_addf_(float v) {
-    return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float wave_sum_f(float v) {
-    v = dpp_addf_<0xB1>(v);
-    v = dpp_addf_<0x4E>(v);
-    v = dpp_addf_<0x141>(v);
-    v = dpp_addf_<0x140>(v);
-    const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0));
-    const float r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16));
-    const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32));
-    const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
-    return (r0 + r1) + (r2 + r3);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -107,8 +89,7 @@ __global__ __launch_bounds__(256) void pcm_peak_kernel(const T* __restrict__ x, 
             const int64_t j = i < head ? i : head + nv * V + (i - head);
             m = fmaxf(m, fabsf((float)x[j]));
         }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    m = wave_max_shfl(m);
     // one atomic per BLOCK, and only when it can raise the peak: thousands of waves hitting one word cost ~11 ns each
     // (8192 of them made this 10 MB scan take 97 us)
     __shared__ float wmax[4];
@@ -142,8 +123,7 @@ __global__ __launch_bounds__(256) void peak_kernel(const float* __restrict__ wav
     const float* w = wav + (int64_t)s * n;
     float m = 0.f;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) m = fmaxf(m, fabsf(w[i]));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    m = wave_max_shfl(m);
     if ((threadIdx.x & 63) == 0) atomicMax(peak + s, __float_as_uint(m));
 }
 
@@ -274,8 +254,8 @@ __global__ __launch_bounds__(256) void features_kernel(const float* __restrict__
                 }
             }
         }
-        s0 = wave_sum_f(s0);
-        s1 = wave_sum_f(s1);
+        s0 = wave_sum_dpp(s0);
+        s1 = wave_sum_dpp(s1);
         if (m == 0) {
             if (o.mvn) {                                                 // feature.py:503-507
                 const float mean = s0 * invT;
@@ -285,7 +265,7 @@ __global__ __launch_bounds__(256) void features_kernel(const float* __restrict__
                     const int t = lane + 64 * i;
                     if (t < T) { a[i] -= mean; q += a[i] * a[i]; }
                 }
-                const float sd = sqrtf(wave_sum_f(q) / (float)(T - 1));
+                const float sd = sqrtf(wave_sum_dpp(q) / (float)(T - 1));
                 const float den = sd + CSS_EPS32;
 #pragma unroll
                 for (int i = 0; i < NT; ++i) {
@@ -310,7 +290,7 @@ __global__ __launch_bounds__(256) void features_kernel(const float* __restrict__
             const float yrm = s0 * invT, yim = s1 * invT;
             float shift = 0.f;
             if (o.ipd_norm && o.ipd_version == 2) shift = atan2f(yim, yrm);
-            if (o.ipd_norm && o.ipd_version == 3) shift = wave_sum_f(s2) * invT;
+            if (o.ipd_norm && o.ipd_version == 3) shift = wave_sum_dpp(s2) * invT;
 #pragma unroll
             for (int i = 0; i < NT; ++i) {
                 const int t = lane + 64 * i;
@@ -393,8 +373,8 @@ __global__ __launch_bounds__(64) void features_long_kernel(const float* __restri
         eval(t, a, b, d);
         s0 += a; s1 += b; s2 += d;
     }
-    s0 = wave_sum_f(s0);
-    s1 = wave_sum_f(s1);
+    s0 = wave_sum_dpp(s0);
+    s1 = wave_sum_dpp(s1);
     if (m == 0) {
         float mean = 0.f, den = 1.f;
         if (o.mvn) {                                                 // feature.py:503-507
@@ -406,7 +386,7 @@ __global__ __launch_bounds__(64) void features_long_kernel(const float* __restri
                 a -= mean;
                 q += a * a;
             }
-            den = sqrtf(wave_sum_f(q) / (float)(T - 1)) + CSS_EPS32;
+            den = sqrtf(wave_sum_dpp(q) / (float)(T - 1)) + CSS_EPS32;
         }
         for (int t = lane; t < T; t += 64) {
             float a, b, d;
@@ -417,7 +397,7 @@ __global__ __launch_bounds__(64) void features_long_kernel(const float* __restri
         const float yrm = s0 * invT, yim = s1 * invT;
         float shift = 0.f;
         if (o.ipd_norm && o.ipd_version == 2) shift = atan2f(yim, yrm);
-        if (o.ipd_norm && o.ipd_version == 3) shift = wave_sum_f(s2) * invT;
+        if (o.ipd_norm && o.ipd_version == 3) shift = wave_sum_dpp(s2) * invT;
         for (int t = lane; t < T; t += 64) {
             float a, b, d;
             eval(t, a, b, d);

@@ -15,6 +15,8 @@
 #include <hip/hip_fp16.h>
 
 #include "kernels.hpp"
+#include "table.hpp"
+#include "wave.hpp"
 
 namespace css {
 
@@ -119,8 +121,7 @@ __device__ __forceinline__ void handoff_mel_tile(MelTilePw& pw, const float* __r
             best = fmaxf(best, v);
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) best = fmaxf(best, __shfl_xor(best, o));
+    best = wave_max_shfl(best);
     if ((threadIdx.x & 63) == 0 && best > -INFINITY) {
         const int b = __float_as_int(best);
         atomicMax(gmax, b >= 0 ? b : b ^ 0x7fffffff);       // monotone map float -> int
@@ -156,9 +157,8 @@ void launch_handoff_mel(const float* spec, int64_t ld, int64_t nfr, const float*
 }
 
 // ---- streamed sessions ----------------------------------------------------------------------------------------------
-struct HandoffAppendTable { HandoffAppend e[HANDOFF_MULTI_MAX]; };
-struct HandoffMelTable { HandoffMel e[HANDOFF_MULTI_MAX]; };
-static_assert(sizeof(HandoffAppendTable) <= 4096 && sizeof(HandoffMelTable) <= 4096, "the tables travel by value as kernel arguments");
+struct HandoffAppendTable : Table<HandoffAppend, HANDOFF_MULTI_MAX> {};
+struct HandoffMelTable : Table<HandoffMel, HANDOFF_MULTI_MAX> {};
 
 // One block per (stream, speaker).  Block q of 256 samples is kept iff an active frame t has t - pad <= q <= t + pad + 1
 // (frame t spans blocks t and t + 1); every frame that can keep a block below D1 is gated-final.  The kept samples of
@@ -305,8 +305,7 @@ __global__ __launch_bounds__(256) void handoff_mel_multi_kernel(HandoffMelTable 
 }
 
 // ---- encoder windows: a span of the frame history, then a preview's provisional frames where the window reaches the present ----
-struct WindowTable { WindowItem e[WINDOW_MULTI_MAX]; };
-static_assert(sizeof(WindowTable) <= 4096, "the table travels by value as a kernel argument");
+struct WindowTable : Table<WindowItem, WINDOW_MULTI_MAX> {};
 
 template <typename T> struct WindowVec;
 template <> struct WindowVec<float> {
@@ -433,8 +432,7 @@ __global__ __launch_bounds__(256) void stream_window_kernel(WindowTable tab) {
             M = fmaxf(M, e.fmax[s]);
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) M = fmaxf(M, __shfl_xor(M, o));
+    M = wave_max_shfl(M);
     if (lane == 0) wm[wave] = M;
     __syncthreads();
     M = fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]));
@@ -449,32 +447,29 @@ __global__ __launch_bounds__(256) void stream_window_kernel(WindowTable tab) {
 }
 
 void launch_stream_windows(const WindowItem* e, int n, hipStream_t s) {
-    if (n <= 0) return;
-    WindowTable tab{};
-    int most = 1;
-    for (int i = 0; i < n; ++i) { tab.e[i] = e[i]; most = std::max(most, (int)e[i].n_mels); }
-    hipLaunchKernelGGL(stream_window_kernel, dim3((unsigned)((most + WINDOW_ROWS - 1) / WINDOW_ROWS), 1, n), dim3(256), 0, s, tab);
+    // (the caller chunks and counts the launches: more than one table here would be a launch it does not report)
+    for_each_table<WindowTable>(e, std::min(n, WINDOW_MULTI_MAX), [&](const WindowTable& tab, int cnt) {
+        const int most = table_max(tab, cnt, 1, [](const WindowItem& w) { return (int)w.n_mels; });
+        hipLaunchKernelGGL(stream_window_kernel, dim3((unsigned)((most + WINDOW_ROWS - 1) / WINDOW_ROWS), 1, cnt), dim3(256), 0, s, tab);
+        return true;
+    });
 }
 
 void launch_handoff_append_multi(const HandoffAppend* e, int n, float* operand, hipStream_t s) {
-    for (int i0 = 0; i0 < n; i0 += HANDOFF_MULTI_MAX) {
-        const int cnt = std::min(HANDOFF_MULTI_MAX, n - i0);
-        HandoffAppendTable tab{};
-        for (int i = 0; i < cnt; ++i) tab.e[i] = e[i0 + i];
-        hipLaunchKernelGGL(handoff_append_kernel, dim3(1, e[i0].S, cnt), dim3(256), 0, s, tab, operand);
-    }
+    for_each_table<HandoffAppendTable>(e, n, [&](const HandoffAppendTable& tab, int cnt) {
+        hipLaunchKernelGGL(handoff_append_kernel, dim3(1, tab.e[0].S, cnt), dim3(256), 0, s, tab, operand);
+        return true;
+    });
 }
 void launch_handoff_mel_multi(const HandoffMel* e, int n, int S, const float* spec, int64_t ld, hipStream_t s) {
-    for (int i0 = 0; i0 < n; i0 += HANDOFF_MULTI_MAX) {
-        const int cnt = std::min(HANDOFF_MULTI_MAX, n - i0);
-        HandoffMelTable tab{};
-        int64_t most = 1;
-        bool pvmax = false;
-        for (int i = 0; i < cnt; ++i) { tab.e[i] = e[i0 + i]; most = std::max(most, e[i0 + i].rows); pvmax = pvmax || e[i0 + i].pvmax; }
+    for_each_table<HandoffMelTable>(e, n, [&](const HandoffMelTable& tab, int cnt) {
+        const int64_t most = table_max(tab, cnt, (int64_t)1, [](const HandoffMel& m) { return m.rows; });
         const dim3 grid((unsigned)((most + MEL_TILE_FRAMES - 1) / MEL_TILE_FRAMES), S, cnt);
-        if (pvmax) hipLaunchKernelGGL(handoff_mel_multi_kernel<true>, grid, dim3(256), 0, s, tab, spec, ld);
+        if (table_max(tab, cnt, 0, [](const HandoffMel& m) { return m.pvmax ? 1 : 0; }))   // any entry with provisional maxima
+            hipLaunchKernelGGL(handoff_mel_multi_kernel<true>, grid, dim3(256), 0, s, tab, spec, ld);
         else hipLaunchKernelGGL(handoff_mel_multi_kernel<false>, grid, dim3(256), 0, s, tab, spec, ld);
-    }
+        return true;
+    });
 }
 
 // ---- queued sessions: ranges and counts found on the device ---------------------------------------------------------------------

@@ -2,6 +2,7 @@
 // train.py:529 eval_model calls it): per clip, the S x S matrix of mean base losses between every predicted speaker
 // output and every ground-truth speaker (the input of PitWrapper, losses.py:50-71) and the noise loss.
 #include "kernels.hpp"
+#include "wave.hpp"
 
 namespace css {
 
@@ -51,9 +52,7 @@ __global__ __launch_bounds__(256) void val_loss_kernel(const float* __restrict__
     }
 #pragma unroll
     for (int i = 0; i < 10; ++i) {
-        double v = acc[i];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+        const double v = wave_sum_shfl(acc[i]);
         if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][i] = v;
     }
     __syncthreads();

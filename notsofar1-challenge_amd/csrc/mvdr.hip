@@ -8,17 +8,13 @@
 #include <cstdlib>
 
 #include "kernels.hpp"
+#include "table.hpp"
+#include "wave.hpp"
 
 namespace css {
 
 constexpr int NC = 7;        // microphones of the NOTSOFAR array (utils/mic_array_model.py:4)
 constexpr int NPACK = 49;    // Hermitian 7x7: 7 real diagonal + 21 complex upper-triangle entries
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 __device__ __forceinline__ int valid_frames(int64_t stft_frames, int64_t seg, int hop, int T) {
     const int64_t tv = stft_frames - seg * (int64_t)hop;
@@ -42,29 +38,6 @@ __device__ __forceinline__ int valid_frames(int64_t stft_frames, int64_t seg, in
 // towards the plain sum only in the first one).  The 16 lanes' partial sums are combined by a four-step DPP
 // reduce-scatter and leave through LDS as 49 consecutive doubles per mask.
 // ------------------------------------------------------------------------------------------------
-template <int CTRL>
-__device__ __forceinline__ double dpp_add(double v) {
-    const int lo = __double2loint(v), hi = __double2hiint(v);
-    const int lo2 = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, false);
-    const int hi2 = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, false);
-    return v + __hiloint2double(hi2, lo2);
-}
-// the partner lane's value under DPP control CTRL
-template <int CTRL>
-__device__ __forceinline__ double dpp_get(double v) {
-    const int lo = __double2loint(v), hi = __double2hiint(v);
-    return __hiloint2double(__builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, false),
-                            __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, false));
-}
-// sum over the 16 lanes of a DPP row; every lane ends up with the total
-__device__ __forceinline__ double row16_sum(double v) {
-    v = dpp_add<0xB1>(v);    // quad_perm [1,0,3,2]
-    v = dpp_add<0x4E>(v);    // quad_perm [2,3,0,1]
-    v = dpp_add<0x141>(v);   // row_half_mirror: lane i <-> 7 - i
-    v = dpp_add<0x140>(v);   // row_mirror:      lane i <-> 15 - i
-    return v;
-}
-
 constexpr int SCM_WAVES = 2;   // bins per block
 
 template <int NI, int TS_ = NI * 64>   // 64-frame pieces of a segment: 4 (T <= 256) or 8 (T <= 512); TS_: the tile's row length
@@ -459,24 +432,19 @@ __device__ __forceinline__ void mvdr_solve_body(const MvdrArgs& a, const int64_t
     }
 }
 
-__global__ __launch_bounds__(64) void mvdr_solve_kernel(MvdrArgs a) { mvdr_solve_body(a, (int64_t)blockIdx.x * 64 + threadIdx.x); }
-// The sessions of a queue group in ONE launch (blockIdx.y = session): a thread is a chain of ~20 us whatever the launch
-// holds, and a 60 s meeting's 30 840 systems are 482 waves for 1 024 SIMDs -- three or six sessions still fit one round.
-struct MvdrMulti { MvdrArgs a[MVDR_MULTI_MAX]; };
-__global__ __launch_bounds__(64) void mvdr_solve_multi_kernel(MvdrMulti m) { mvdr_solve_body(m.a[blockIdx.y], (int64_t)blockIdx.x * 64 + threadIdx.x); }
+// The sessions of a queue group in ONE launch (a table launch, blockIdx.y = session; one session is a table of one): a thread is
+// a chain of ~20 us whatever the launch holds, and a 60 s meeting's 30 840 systems are 482 waves for 1 024 SIMDs -- three or six
+// sessions still fit one round.
+struct MvdrMulti : Table<MvdrArgs, MVDR_MULTI_MAX> {};
+__global__ __launch_bounds__(64) void mvdr_solve_multi_kernel(MvdrMulti m) { mvdr_solve_body(m.e[blockIdx.y], (int64_t)blockIdx.x * 64 + threadIdx.x); }
 
-void launch_mvdr_solve(const MvdrArgs& a, hipStream_t s) {
-    const int64_t total = (int64_t)a.nseg * a.S * a.F;
-    hipLaunchKernelGGL(mvdr_solve_kernel, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, s, a);
-}
+void launch_mvdr_solve(const MvdrArgs& a, hipStream_t s) { launch_mvdr_solve_multi(&a, 1, s); }
 void launch_mvdr_solve_multi(const MvdrArgs* a, int n, hipStream_t s) {
-    for (int i0 = 0; i0 < n; i0 += MVDR_MULTI_MAX) {
-        const int cnt = std::min(MVDR_MULTI_MAX, n - i0);
-        MvdrMulti m{};
-        int64_t most = 0;
-        for (int i = 0; i < cnt; ++i) { m.a[i] = a[i0 + i]; most = std::max<int64_t>(most, (int64_t)a[i0 + i].nseg * a[i0 + i].S * a[i0 + i].F); }
+    for_each_table<MvdrMulti>(a, n, [&](const MvdrMulti& m, int cnt) {
+        const int64_t most = table_max(m, cnt, (int64_t)0, [](const MvdrArgs& e) { return (int64_t)e.nseg * e.S * e.F; });
         if (most > 0) hipLaunchKernelGGL(mvdr_solve_multi_kernel, dim3((unsigned)((most + 63) / 64), cnt), dim3(64), 0, s, m);
-    }
+        return true;
+    });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -553,8 +521,8 @@ __global__ __launch_bounds__(256) void segment_energy_kernel(MvdrArgs a, double*
         }
         es += (double)sr * sr + (double)si * si;
     }
-    em = wave_sum_d(em);
-    es = wave_sum_d(es);
+    em = wave_sum_shfl(em);
+    es = wave_sum_shfl(es);
     const int wave = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) { red[0][wave] = em; red[1][wave] = es; }
     __syncthreads();

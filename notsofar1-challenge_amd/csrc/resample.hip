@@ -19,6 +19,8 @@
 //                                   final samples] -> float32 or PCM16 at the playback rate (css_stream_set_output), the carried
 //                                   samples' other generation, the running peak and the clipped counts
 #include "api_ctx.hpp"
+#include "table.hpp"
+#include "wave.hpp"
 #include "../../include/css_mi355_rate.h"
 #include "../../include/css_mi355_stream_out.h"
 
@@ -199,7 +201,7 @@ __device__ __forceinline__ void resample_tile(const ResampleJob& e, int64_t t0, 
     }
 }
 
-struct ResampleTable { ResampleJob e[STREAM_MULTI_MAX]; };
+struct ResampleTable : Table<ResampleJob, STREAM_MULTI_MAX> {};
 
 __global__ __launch_bounds__(RS_TILE) void stream_ingest_resample_kernel(ResampleTable tab) {
     extern __shared__ __attribute__((aligned(16))) float rs_lds[];
@@ -236,7 +238,7 @@ __global__ __launch_bounds__(RS_TILE) void resample_kernel(ResampleJob e) {
 // input side.  The taps of a phase start at phase * P_ld: 3 rows at 3 / 1 (banks 0, 21, 10); at 441 / 160 the lanes' phases step
 // by 160 = 5 * 32, so whatever P_ld is the half's 32 lanes meet on the ~12 banks their wraps past 441 select (about 3 lanes per
 // bank, on one of the two reads per fmaf).
-struct StreamOutputTable { StreamOutputJob e[STREAM_MULTI_MAX]; };
+struct StreamOutputTable : Table<StreamOutputJob, STREAM_MULTI_MAX> {};
 
 // floats of LDS before the output tile: the taps by phase and the span's row (nothing at 1 / 1), rounded to 16 bytes
 __host__ __device__ __forceinline__ int so_tile_at(int up, int down, int P, int P_ld) {
@@ -328,11 +330,8 @@ __global__ __launch_bounds__(RS_TILE) void stream_output_kernel(StreamOutputTabl
         }
     }
     // one atomic of each kind per block, and only when it changes the word
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        m = fmaxf(m, __shfl_xor(m, o));
-        clip += __shfl_xor(clip, o);
-    }
+    m = wave_max_shfl(m);
+    clip = wave_sum_shfl(clip);
     if ((tid & 63) == 0) { w_peak[tid >> 6] = m; w_clip[tid >> 6] = clip; }
     __syncthreads();
     if (tid == 0) {
@@ -363,47 +362,32 @@ bool resample_fits(const ResampleRatio& r, int C) {
 }
 
 bool launch_stream_ingest_resample_multi(const ResampleJob* e, int n, hipStream_t s) {
-    for (int i0 = 0; i0 < n; i0 += STREAM_MULTI_MAX) {
-        const int cnt = std::min(STREAM_MULTI_MAX, n - i0);
-        ResampleTable tab{};
-        int64_t most = 0;
-        size_t lds = 0;
-        for (int i = 0; i < cnt; ++i) {
-            tab.e[i] = e[i0 + i];
-            most = std::max(most, (e[i0 + i].n_m + RS_TILE - 1) / RS_TILE + 1);
-            lds = std::max(lds, lds_bytes(e[i0 + i]));
-        }
+    return for_each_table<ResampleTable>(e, n, [&](const ResampleTable& tab, int cnt) {
+        const int64_t most = table_max(tab, cnt, (int64_t)0, [](const ResampleJob& j) { return (j.n_m + RS_TILE - 1) / RS_TILE + 1; });
+        const size_t lds = table_max(tab, cnt, (size_t)0, [](const ResampleJob& j) { return lds_bytes(j); });
         if (lds > RS_LDS_MAX) return false;
         if (lds > 65536 && hipFuncSetAttribute(reinterpret_cast<const void*>(stream_ingest_resample_kernel),
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
             return false;
         hipLaunchKernelGGL(stream_ingest_resample_kernel, dim3((unsigned)most, 1, cnt), dim3(RS_TILE), lds, s, tab);
-    }
-    return true;
+        return true;
+    });
 }
 
 bool stream_output_fits(const ResampleRatio& r) { return so_lds_bytes(r.up, r.down, r.P, r.P_ld) <= RS_LDS_MAX; }
 
 bool launch_stream_output_multi(const StreamOutputJob* e, int n, int S, hipStream_t s, int* launches) {
-    for (int i0 = 0; i0 < n; i0 += STREAM_MULTI_MAX) {
-        const int cnt = std::min(STREAM_MULTI_MAX, n - i0);
-        StreamOutputTable tab{};
-        int64_t most = 0;
-        size_t lds = 0;
-        for (int i = 0; i < cnt; ++i) {
-            const StreamOutputJob& j = e[i0 + i];
-            tab.e[i] = j;
-            most = std::max(most, (j.n_m + SO_TILE - 1) / SO_TILE + 1);
-            lds = std::max(lds, so_lds_bytes(j.up, j.down, j.P, j.P_ld));
-        }
+    return for_each_table<StreamOutputTable>(e, n, [&](const StreamOutputTable& tab, int cnt) {
+        const int64_t most = table_max(tab, cnt, (int64_t)0, [](const StreamOutputJob& j) { return (j.n_m + SO_TILE - 1) / SO_TILE + 1; });
+        const size_t lds = table_max(tab, cnt, (size_t)0, [](const StreamOutputJob& j) { return so_lds_bytes(j.up, j.down, j.P, j.P_ld); });
         if (lds > RS_LDS_MAX) return false;
         if (lds > 65536 && hipFuncSetAttribute(reinterpret_cast<const void*>(stream_output_kernel),
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
             return false;
         hipLaunchKernelGGL(stream_output_kernel, dim3((unsigned)most, (unsigned)S, cnt), dim3(RS_TILE), lds, s, tab);
         if (launches) ++*launches;
-    }
-    return true;
+        return true;
+    });
 }
 
 bool launch_resample(const ResampleJob& e, hipStream_t s) {

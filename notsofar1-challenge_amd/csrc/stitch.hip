@@ -11,33 +11,11 @@
 #include "kernels.hpp"
 #include "lsap.hpp"
 #include "split_f16.hpp"
+#include "stitch_common.hpp"
+#include "table.hpp"
+#include "wave.hpp"
 
 namespace css {
-
-__device__ __forceinline__ double wave_sum_dd(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-// The same sum without LDS round trips (__shfl_xor compiles to ds_bpermute: six dependent ones per double and sum):
-// four DPP steps inside each row of 16 lanes, the four row totals through scalar registers.  Every lane gets the total.
-template <int CTRL>
-__device__ __forceinline__ double dpp_add_d(double v) {
-    const int lo = __double2loint(v), hi = __double2hiint(v);
-    return v + __hiloint2double(__builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, false),
-                                __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, false));
-}
-__device__ __forceinline__ double wave_sum_dpp(double v) {
-    v = dpp_add_d<0xB1>(v);    // quad_perm [1,0,3,2]
-    v = dpp_add_d<0x4E>(v);    // quad_perm [2,3,0,1]
-    v = dpp_add_d<0x141>(v);   // row_half_mirror
-    v = dpp_add_d<0x140>(v);   // row_mirror
-    const int lo = __double2loint(v), hi = __double2hiint(v);
-    double r[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) r[i] = __hiloint2double(__builtin_amdgcn_readlane(hi, 16 * i), __builtin_amdgcn_readlane(lo, 16 * i));
-    return (r[0] + r[1]) + (r[2] + r[3]);
-}
 
 // ------------------------------------------------------------------------------------------------
 // Raw PIT cost of boundary b (segments b | b+1):  cost[a][c] = mean_{F, overlap} loss(L_a - R_c)
@@ -131,35 +109,32 @@ __global__ __launch_bounds__(64) void pit_cost_final_kernel(const double* __rest
     pit_cost_final_body(partial, S, F, ov, b_lo, b_hi, costs, nch, (int64_t)blockIdx.x * 64 + threadIdx.x);
 }
 
-// All boundaries of the sessions of a queue group in one pair of launches (blockIdx.z / .y = session); every session keeps
-// its own chunk count, scratch and cost matrix, so each cost is the bit pattern the per-session launch gives.
-struct PitMulti { StitchArgs a[PIT_MULTI_MAX]; double* partial[PIT_MULTI_MAX]; double* costs[PIT_MULTI_MAX]; int loss, input; };
+// All boundaries of the sessions of a queue group in one pair of launches (a table launch, blockIdx.z / .y = session); every
+// session keeps its own chunk count, scratch and cost matrix, so each cost is the bit pattern the per-session launch gives.
+// (The per-session launch below keeps kernels of its own: as a table of one entry it made the grouped stream pushes, which
+// compute every stream's newest boundary with it, 0.4 ms per round of 16 streams slower -- profiles/r22_shared_device_code.json.)
+struct PitEntry { StitchArgs a; double* partial; double* costs; int loss, input; };
+struct PitMulti : Table<PitEntry, PIT_MULTI_MAX> {};
 __global__ __launch_bounds__(256) void pit_cost_multi_kernel(PitMulti m) {
-    const StitchArgs& a = m.a[blockIdx.z];
-    const int nch = pit_chunks(a.num_segments);
-    if ((int64_t)blockIdx.x >= a.num_segments - 1 || (int)blockIdx.y >= nch) return;
-    pit_cost_body(a, m.loss, m.input, blockIdx.x, blockIdx.y, nch, m.partial[blockIdx.z]);
+    const PitEntry& e = m.e[blockIdx.z];
+    const int nch = pit_chunks(e.a.num_segments);
+    if ((int64_t)blockIdx.x >= e.a.num_segments - 1 || (int)blockIdx.y >= nch) return;
+    pit_cost_body(e.a, e.loss, e.input, blockIdx.x, blockIdx.y, nch, e.partial);
 }
 __global__ __launch_bounds__(64) void pit_cost_final_multi_kernel(PitMulti m) {
-    const StitchArgs& a = m.a[blockIdx.y];
-    pit_cost_final_body(m.partial[blockIdx.y], a.S, a.F, a.T - a.hop, 0, a.num_segments - 1, m.costs[blockIdx.y], pit_chunks(a.num_segments),
+    const PitEntry& e = m.e[blockIdx.y];
+    pit_cost_final_body(e.partial, e.a.S, e.a.F, e.a.T - e.a.hop, 0, e.a.num_segments - 1, e.costs, pit_chunks(e.a.num_segments),
                         (int64_t)blockIdx.x * 64 + threadIdx.x);
 }
 void launch_pit_costs_multi(const StitchArgs* a, double* const* scratch, double* const* costs, int n, int loss, int input, hipStream_t s) {
-    for (int i0 = 0; i0 < n; i0 += PIT_MULTI_MAX) {
-        const int cnt = std::min(PIT_MULTI_MAX, n - i0);
-        PitMulti m{};
-        m.loss = loss; m.input = input;
-        int64_t nb = 0; int nch = 0;
-        for (int i = 0; i < cnt; ++i) {
-            m.a[i] = a[i0 + i]; m.partial[i] = scratch[i0 + i]; m.costs[i] = costs[i0 + i];
-            nb = std::max<int64_t>(nb, a[i0 + i].num_segments - 1);
-            nch = std::max(nch, pit_chunks(a[i0 + i].num_segments));
-        }
-        if (nb <= 0) continue;
+    for_each_table<PitMulti>(n, [&](int i) { return PitEntry{a[i], scratch[i], costs[i], loss, input}; }, [&](const PitMulti& m, int cnt) {
+        const int64_t nb = table_max(m, cnt, (int64_t)0, [](const PitEntry& e) { return e.a.num_segments - 1; });
+        const int nch = table_max(m, cnt, 0, [](const PitEntry& e) { return pit_chunks(e.a.num_segments); });
+        if (nb <= 0) return true;
         hipLaunchKernelGGL(pit_cost_multi_kernel, dim3((unsigned)nb, nch, cnt), dim3(256), 0, s, m);
-        hipLaunchKernelGGL(pit_cost_final_multi_kernel, dim3((unsigned)((nb * a[i0].S * a[i0].S + 63) / 64), cnt), dim3(64), 0, s, m);
-    }
+        hipLaunchKernelGGL(pit_cost_final_multi_kernel, dim3((unsigned)((nb * m.e[0].a.S * m.e[0].a.S + 63) / 64), cnt), dim3(64), 0, s, m);
+        return true;
+    });
 }
 
 size_t pit_cost_scratch_bytes(int64_t n_boundaries) { return (size_t)std::max<int64_t>(n_boundaries, 1) * PIT_CH * SMAX * SMAX * sizeof(double); }
@@ -319,31 +294,16 @@ void pit_scan_host(const double* costs, int64_t n_boundaries, int S, int32_t* pe
 // ------------------------------------------------------------------------------------------------
 // helpers shared by the two overlap-add kernels
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float seg_weight(const StitchArgs& a, int64_t seg, int tl) {
-    // css.py:258,290: segment 0 is built with is_first_seg, the last one with is_last_seg
-    const float* w = seg == 0 ? a.w_first : (seg == a.num_segments - 1 ? a.w_last : a.w_mid);
-    return w[tl];
-}
-
 // The segments covering frame t, in ascending segment order.  NC = ceil(T / hop) of them at most: two with the shipped
 // 3 s / 1.5 s configuration, up to four take the same code (the kernels are instantiated for NC = 2 and 4: slot i is
 // ALWAYS segment t / hop - (NC - 1) + i, present or not, so every index is a compile-time constant and nothing lives in
 // private scratch); denser segmentations (any hop >= 1 the reference accepts, css.py:144-171) take the NC = 0
-// instantiation, which walks first_seg(t) .. last_seg(t) per value.  The sums start from zero exactly as the reference's
+// instantiation: the general walk of stitch_common.hpp, which the stream kernels share.  The sums start from zero exactly as the reference's
 // `zeros += w * x` does (css.py:254-295): 0 + w x is w x, so the float32 operation order is the reference's.
 constexpr int MAXC = 4;
 __host__ __device__ inline int contributor_class(int T, int hop) {
     const int nc = (T + hop - 1) / hop;
     return nc <= 2 ? 2 : (nc <= MAXC ? MAXC : 0);
-}
-__device__ __forceinline__ int64_t first_seg(const StitchArgs& a, int64_t t) {
-    const int64_t lo = t - a.T + 1;
-    const int64_t s0 = lo <= 0 ? 0 : (lo + a.hop - 1) / a.hop;
-    return s0;
-}
-__device__ __forceinline__ int64_t last_seg(const StitchArgs& a, int64_t t) {
-    const int64_t s1 = t / a.hop;
-    return s1 < a.num_segments ? s1 : a.num_segments - 1;
 }
 template <int NC>
 struct Covering {
@@ -379,33 +339,24 @@ struct Covering {
 // The float32 operation order of the reference (multiply, add in ascending segment order, divide) is
 // reproduced with operations compiled with contraction off (kernels.hpp css_mul_rn / css_add_rn / css_div_rn), so no FMA
 // changes a bit.
-// Block = 16 frames x 16 frequency groups (a 60 s meeting is only 3749 frames: 64-frame blocks gave 177 blocks for
-// 256 CUs); lanes run over time (contiguous mask reads); the frequency mean is accumulated in float64 and the 16
-// partial sums are added in a fixed order.
+// Block = OLA_T frames x OLA_FG frequency groups; lanes run over time (contiguous mask reads); the frequency mean is
+// accumulated in float64 and the 16 partial sums are added in a fixed order (stitch_common.hpp ola_activity).
 // ------------------------------------------------------------------------------------------------
-constexpr int OM_T = 16, OM_FG = 16;
 template <int NC>
 __global__ __launch_bounds__(256) void ola_masks_kernel(StitchArgs a, int64_t t_lo, int64_t t_hi) {
-    __shared__ double red[OM_FG][OM_T];
     const int s = blockIdx.y;
-    const int lane = threadIdx.x & (OM_T - 1), fg = threadIdx.x / OM_T;
-    const int64_t t = t_lo + (int64_t)blockIdx.x * OM_T + lane;
+    const int lane = threadIdx.x & (OLA_T - 1), fg = threadIdx.x / OLA_T;
+    const int64_t t = t_lo + (int64_t)blockIdx.x * OLA_T + lane;
     const bool active = t < t_hi;
     double sum = 0.0;
     if constexpr (NC == 0) {
         if (active) {
-            const int64_t s0 = first_seg(a, t), s1 = last_seg(a, t);
-            float ws = 0.f;
-            for (int64_t seg = s0; seg <= s1; ++seg) ws = css_add_rn(ws, seg_weight(a, seg, (int)(t - seg * a.hop)));
+            int64_t s0, s1;
+            covering(a, t, &s0, &s1);
+            const float ws = ola_weight_sum(a, t, s0, s1);
             float* out = a.mask_st + (int64_t)s * a.F * a.T_long + t;
-            for (int f = fg; f < a.F; f += OM_FG) {
-                float v = 0.f;
-                for (int64_t seg = s0; seg <= s1; ++seg) {
-                    const int tl = (int)(t - seg * a.hop);
-                    const float m = a.masks[((int64_t)a.perms[seg * a.S + s] * a.F + f) * a.mask_ld + seg * a.T + tl];
-                    v = css_add_rn(v, css_mul_rn(seg_weight(a, seg, tl), m));
-                }
-                v = css_div_rn(v, ws);
+            for (int f = fg; f < a.F; f += OLA_FG) {
+                const float v = ola_mask_value(a, s, f, t, s0, s1, ws);
                 out[(int64_t)f * a.T_long] = v;
                 sum += (double)v;
             }
@@ -420,7 +371,7 @@ __global__ __launch_bounds__(256) void ola_masks_kernel(StitchArgs a, int64_t t_
             for (int i = 0; i < NC; ++i)
                 mp[i] = a.masks + (int64_t)(c.on[i] ? a.perms[c.seg[i] * a.S + s] : 0) * a.F * a.mask_ld + c.seg[i] * a.T + c.tl[i];
             float* out = a.mask_st + (int64_t)s * a.F * a.T_long + t;
-            for (int f = fg; f < a.F; f += OM_FG) {
+            for (int f = fg; f < a.F; f += OLA_FG) {
                 float v = 0.f;
 #pragma unroll
                 for (int i = 0; i < NC; ++i)
@@ -431,21 +382,15 @@ __global__ __launch_bounds__(256) void ola_masks_kernel(StitchArgs a, int64_t t_
             }
         }
     }
-    red[fg][lane] = sum;
-    __syncthreads();
-    if (fg == 0 && active) {
-        double tot = 0.0;
-#pragma unroll
-        for (int g = 0; g < OM_FG; ++g) tot += red[g][lane];
-        const float act = (float)(tot / (double)a.F);
+    ola_activity(sum, fg, lane, active, a.F, a.activity_th, [&](float act, uint8_t on) {
         a.activity[(int64_t)s * a.T_long + t] = act;
-        a.act_b[(int64_t)s * a.T_long + t] = act >= a.activity_th ? 1 : 0;
-    }
+        a.act_b[(int64_t)s * a.T_long + t] = on;
+    });
 }
 
 void launch_ola_masks(const StitchArgs& a, int64_t t_lo, int64_t t_hi, hipStream_t s) {
     if (t_hi <= t_lo) return;
-    const dim3 grid((unsigned)((t_hi - t_lo + OM_T - 1) / OM_T), a.S), block(OM_T * OM_FG);
+    const dim3 grid((unsigned)((t_hi - t_lo + OLA_T - 1) / OLA_T), a.S), block(OLA_T * OLA_FG);
     switch (contributor_class(a.T, a.hop)) {
         case 2: hipLaunchKernelGGL(ola_masks_kernel<2>, grid, block, 0, s, a, t_lo, t_hi); break;
         case 4: hipLaunchKernelGGL(ola_masks_kernel<4>, grid, block, 0, s, a, t_lo, t_hi); break;
@@ -484,18 +429,16 @@ void launch_morphology(const StitchArgs& a, int64_t t_lo, int64_t t_hi, hipStrea
 // ------------------------------------------------------------------------------------------------
 // Weighted overlap-add of the (permuted) separated spectra, activity gating (css.py:294,298,312) and
 // the hand-off layout of the synthesis GEMM: Y[s][t][0..F) = Re, [F..2F) = Im, zero padding to KIp.
-// Block = 16 frames of one stream; reads run over time (128-byte runs of float2), the tile is turned
+// Block = OLA_T frames of one stream; reads run over time (128-byte runs of float2), the tile is turned
 // through LDS so the writes run over the frequency axis.
 // ------------------------------------------------------------------------------------------------
-constexpr int OT = 16;
-
 template <int NC>
 __global__ __launch_bounds__(256) void ola_stft_kernel(StitchArgs a, int64_t t_lo, int64_t t_hi) {
-    extern __shared__ __attribute__((aligned(16))) float tile[];  // [OT][2F + 1] (odd stride: no bank conflicts)
+    extern __shared__ __attribute__((aligned(16))) float tile[];  // [OLA_T][2F + 1] (odd stride: no bank conflicts)
     const int TS = 2 * a.F + 1;
     const int s = blockIdx.y;
-    const int64_t t0 = t_lo + (int64_t)blockIdx.x * OT;
-    const int tx = threadIdx.x & (OT - 1), fy = threadIdx.x >> 4;  // 16 frames x 16 bins per pass
+    const int64_t t0 = t_lo + (int64_t)blockIdx.x * OLA_T;
+    const int tx = threadIdx.x & (OLA_T - 1), fy = threadIdx.x >> 4;  // 16 frames x 16 bins per pass
     const int64_t t = t0 + tx;
     const bool active = t < t_hi;
     const float2* sep = reinterpret_cast<const float2*>(a.sep);
@@ -504,26 +447,13 @@ __global__ __launch_bounds__(256) void ola_stft_kernel(StitchArgs a, int64_t t_l
         int64_t gs0 = 0, gs1 = -1;
         float wsum = 0.f;
         if (active) {
-            gs0 = first_seg(a, t); gs1 = last_seg(a, t);
-            for (int64_t seg = gs0; seg <= gs1; ++seg) wsum = css_add_rn(wsum, seg_weight(a, seg, (int)(t - seg * a.hop)));
+            covering(a, t, &gs0, &gs1);
+            wsum = ola_weight_sum(a, t, gs0, gs1);
         }
         for (int f = fy; f < a.F; f += 16) {
-            float re = 0.f, im = 0.f;
-            if (active) {
-                for (int64_t seg = gs0; seg <= gs1; ++seg) {
-                    const int tl = (int)(t - seg * a.hop);
-                    const float w = seg_weight(a, seg, tl);
-                    const float2 v = sep[((seg * a.S + a.perms[seg * a.S + s]) * (int64_t)a.F + f) * a.T + tl];
-                    re = css_add_rn(re, css_mul_rn(w, v.x));
-                    im = css_add_rn(im, css_mul_rn(w, v.y));
-                }
-                if (gs1 >= gs0) {
-                    re = css_mul_rn(css_div_rn(re, wsum), gate);
-                    im = css_mul_rn(css_div_rn(im, wsum), gate);
-                }
-            }
-            tile[tx * TS + f] = re;
-            tile[tx * TS + a.F + f] = im;
+            const float2 v = active ? ola_spec_value(a, s, f, t, gs0, gs1, wsum, gate) : make_float2(0.f, 0.f);
+            tile[tx * TS + f] = v.x;
+            tile[tx * TS + a.F + f] = v.y;
         }
     } else {
         Covering<NC> c;
@@ -558,7 +488,7 @@ __global__ __launch_bounds__(256) void ola_stft_kernel(StitchArgs a, int64_t t_l
     }
     __syncthreads();
     const float lvl = a.y_split ? level_gain(a.level) : 1.f;
-    for (int r = 0; r < OT; ++r) {
+    for (int r = 0; r < OLA_T; ++r) {
         if (t0 + r >= t_hi) break;
         float* out = a.Y + ((int64_t)s * a.T_long + t0 + r) * a.KIp;
         for (int j = threadIdx.x; j < a.KIp; j += 256) {
@@ -574,8 +504,8 @@ __global__ __launch_bounds__(256) void ola_stft_kernel(StitchArgs a, int64_t t_l
 
 void launch_ola_stft(const StitchArgs& a, int64_t t_lo, int64_t t_hi, hipStream_t s) {
     if (t_hi <= t_lo) return;
-    const size_t lds = (size_t)OT * (2 * a.F + 1) * sizeof(float);
-    const dim3 grid((unsigned)((t_hi - t_lo + OT - 1) / OT), a.S), block(256);
+    const size_t lds = (size_t)OLA_T * (2 * a.F + 1) * sizeof(float);
+    const dim3 grid((unsigned)((t_hi - t_lo + OLA_T - 1) / OLA_T), a.S), block(256);
     switch (contributor_class(a.T, a.hop)) {
         case 2: hipLaunchKernelGGL(ola_stft_kernel<2>, grid, block, lds, s, a, t_lo, t_hi); break;
         case 4: hipLaunchKernelGGL(ola_stft_kernel<4>, grid, block, lds, s, a, t_lo, t_hi); break;

@@ -2,12 +2,13 @@
 // bounded window of segment slots.  The offline kernels (stitch.hip) pick the first / last segment window from the local
 // segment index and the session's segment count, and gate over the whole recording; a stream knows neither its length
 // nor keeps its past.  These two kernels take a window base (global segment index of slot 0) and the global segment
-// count (INT64_MAX while the stream is open: no segment is the last one yet), and reproduce the float32 operation order of
-// ola_masks_kernel / morph_kernel / ola_stft_kernel exactly, so that every frame they produce is the offline frame bit for bit.
+// count (INT64_MAX while the stream is open: no segment is the last one yet).  Covering segments, weights, the overlap-add
+// walk and the frequency mean are the functions of stitch_common.hpp that ola_masks_kernel<0> / ola_stft_kernel<0> call, and
+// the gate reproduces morph_kernel, so that every frame they produce is the offline frame bit for bit.
 //   stream_activity_kernel   weighted overlap-add of the permuted masks, mean over frequency, threshold -> act_b
 //   stream_gate_ola_kernel   dilate / erode of act_b (left halo from earlier pushes), weighted overlap-add of the permuted
 //                            spectra, gating -> synthesis rows Y (and, for a stream with the hand-off on, the gate bytes)
-// Both are table launches (the idiom of mvdr_solve_multi_kernel): up to STREAM_MULTI_MAX streams' windows and frame ranges
+// Both are table launches (table.hpp): up to STREAM_MULTI_MAX streams' windows and frame ranges
 // by value, blockIdx.z selects the entry, blocks past an entry's range return at once.  One stream is a table of one entry,
 // so there is one copy of each body and one kernel for css_stream_push, css_stream_push_many and css_stream_finish.
 //   stream_scatter_masks_kernel   the mask columns of an estimator batch shared by several streams -> each stream's window
@@ -16,82 +17,50 @@
 #include <climits>
 
 #include "kernels.hpp"
+#include "stitch_common.hpp"
+#include "table.hpp"
 
 namespace css {
 
-__device__ __forceinline__ float stream_seg_weight(const StreamStitchArgs& a, int64_t seg, int tl) {
-    const int64_t g = a.seg_base + seg;   // css.py:258,290: first / last by the segment's place in the recording
-    const float* w = g == 0 ? a.w_first : (g == a.num_segments_global - 1 ? a.w_last : a.w_mid);
-    return w[tl];
-}
-// the segments of the window covering local frame t, ascending (as first_seg / last_seg of stitch.hip)
-__device__ __forceinline__ void stream_cover(const StreamStitchArgs& a, int64_t t, int64_t* s0, int64_t* s1) {
-    const int64_t lo = t - a.T + 1;
-    *s0 = lo <= 0 ? 0 : (lo + a.hop - 1) / a.hop;
-    const int64_t hi = t / a.hop;
-    *s1 = hi < a.num_slots ? hi : a.num_slots - 1;
-}
+struct StreamEntry { StreamStitchArgs a; StreamFrames r; };
+struct StreamMulti : Table<StreamEntry, STREAM_MULTI_MAX> {};
 
-// ola_masks_kernel's block shape and reduction order: 16 frames x 16 frequency groups, float64 partial sums per group,
-// the 16 groups added in a fixed order
-constexpr int SA_T = 16, SA_FG = 16;
-struct StreamMulti { StreamStitchArgs a[STREAM_MULTI_MAX]; StreamFrames r[STREAM_MULTI_MAX]; };
-static_assert(sizeof(StreamMulti) <= 4096, "the table travels by value as a kernel argument");
-
+// ola_masks_kernel<0> without the stitched masks themselves: only the activity bits leave
 __device__ __forceinline__ void stream_activity_body(const StreamStitchArgs& a, int64_t t_lo, int64_t t_hi) {
-    __shared__ double red[SA_FG][SA_T];
     const int s = blockIdx.y;
-    const int lane = threadIdx.x & (SA_T - 1), fg = threadIdx.x / SA_T;
-    const int64_t t = t_lo + (int64_t)blockIdx.x * SA_T + lane;
+    const int lane = threadIdx.x & (OLA_T - 1), fg = threadIdx.x / OLA_T;
+    const int64_t t = t_lo + (int64_t)blockIdx.x * OLA_T + lane;
     const bool active = t < t_hi;
     double sum = 0.0;
     if (active) {
         int64_t s0, s1;
-        stream_cover(a, t, &s0, &s1);
-        float ws = 0.f;
-        for (int64_t seg = s0; seg <= s1; ++seg) ws = css_add_rn(ws, stream_seg_weight(a, seg, (int)(t - seg * a.hop)));
-        for (int f = fg; f < a.F; f += SA_FG) {
-            float v = 0.f;
-            for (int64_t seg = s0; seg <= s1; ++seg) {
-                const int tl = (int)(t - seg * a.hop);
-                const float m = a.masks[((int64_t)a.perms[seg * a.S + s] * a.F + f) * a.mask_ld + seg * a.T + tl];
-                v = css_add_rn(v, css_mul_rn(stream_seg_weight(a, seg, tl), m));
-            }
-            sum += (double)css_div_rn(v, ws);
-        }
+        covering(a, t, &s0, &s1);
+        const float ws = ola_weight_sum(a, t, s0, s1);
+        for (int f = fg; f < a.F; f += OLA_FG) sum += (double)ola_mask_value(a, s, f, t, s0, s1, ws);
     }
-    red[fg][lane] = sum;
-    __syncthreads();
-    if (fg == 0 && active) {
-        double tot = 0.0;
-#pragma unroll
-        for (int g = 0; g < SA_FG; ++g) tot += red[g][lane];
-        const float act = (float)(tot / (double)a.F);
-        a.act_b[(int64_t)s * a.ld_frames + t] = act >= a.activity_th ? 1 : 0;
-    }
+    ola_activity(sum, fg, lane, active, a.F, a.activity_th, [&](float, uint8_t on) { a.act_b[(int64_t)s * a.ld_frames + t] = on; });
 }
 
 __global__ __launch_bounds__(256) void stream_activity_kernel(StreamMulti m) {
-    const StreamFrames r = m.r[blockIdx.z];
-    if (r.t_lo + (int64_t)blockIdx.x * SA_T >= r.t_hi) return;
-    stream_activity_body(m.a[blockIdx.z], r.t_lo, r.t_hi);
+    const StreamFrames r = m.e[blockIdx.z].r;
+    if (r.t_lo + (int64_t)blockIdx.x * OLA_T >= r.t_hi) return;
+    stream_activity_body(m.e[blockIdx.z].a, r.t_lo, r.t_hi);
 }
 
-// morph_kernel twice (dilate with zeros outside the recording, erode with ones outside it), then ola_stft_kernel's
-// overlap-add, division and gate, written as float32 synthesis rows.  Block = 16 frames of one stream.
-constexpr int SG_T = 16;
+// morph_kernel twice (dilate with zeros outside the recording, erode with ones outside it), then ola_stft_kernel<0>'s
+// overlap-add, division and gate, written as float32 synthesis rows.  Block = OLA_T frames of one stream.
 __device__ __forceinline__ void stream_gate_ola_body(const StreamStitchArgs& a, int64_t t_lo, int64_t t_hi) {
-    extern __shared__ __attribute__((aligned(16))) float tile[];   // [SG_T][2F + 1], then the dilated bits
+    extern __shared__ __attribute__((aligned(16))) float tile[];   // [OLA_T][2F + 1], then the dilated bits
     const int TS = 2 * a.F + 1;
-    uint8_t* dil = reinterpret_cast<uint8_t*>(tile + SG_T * TS);   // [SG_T + 2 E]
+    uint8_t* dil = reinterpret_cast<uint8_t*>(tile + OLA_T * TS);   // [OLA_T + 2 E]
     const int s = blockIdx.y;
-    const int64_t t0 = t_lo + (int64_t)blockIdx.x * SG_T;
-    const int tx = threadIdx.x & (SG_T - 1), fy = threadIdx.x >> 4;
+    const int64_t t0 = t_lo + (int64_t)blockIdx.x * OLA_T;
+    const int tx = threadIdx.x & (OLA_T - 1), fy = threadIdx.x >> 4;
     const int64_t t = t0 + tx;
     const bool active = t < t_hi;
     const uint8_t* row = a.act_b + (int64_t)s * a.ld_frames;
     const int64_t g_end = a.T_long_global - a.frame_base;   // local end of the recording (huge while the stream is open)
-    const int nd = SG_T + 2 * a.erosion;
+    const int nd = OLA_T + 2 * a.erosion;
     for (int i = threadIdx.x; i < nd; i += blockDim.x) {
         const int64_t u = t0 - a.erosion + i;
         uint8_t v = 0;
@@ -112,33 +81,19 @@ __device__ __forceinline__ void stream_gate_ola_body(const StreamStitchArgs& a, 
         }
     const float gate = active && keep ? 1.f : 0.f;
     if (a.gate_out && active && fy == 0) a.gate_out[(int64_t)s * a.gate_ld + ((t + a.frame_base) & a.gate_mask)] = keep;
-    const float2* sep = reinterpret_cast<const float2*>(a.sep);
     int64_t gs0 = 0, gs1 = -1;
     float wsum = 0.f;
     if (active) {
-        stream_cover(a, t, &gs0, &gs1);
-        for (int64_t seg = gs0; seg <= gs1; ++seg) wsum = css_add_rn(wsum, stream_seg_weight(a, seg, (int)(t - seg * a.hop)));
+        covering(a, t, &gs0, &gs1);
+        wsum = ola_weight_sum(a, t, gs0, gs1);
     }
     for (int f = fy; f < a.F; f += 16) {
-        float re = 0.f, im = 0.f;
-        if (active) {
-            for (int64_t seg = gs0; seg <= gs1; ++seg) {
-                const int tl = (int)(t - seg * a.hop);
-                const float w = stream_seg_weight(a, seg, tl);
-                const float2 v = sep[((seg * a.S + a.perms[seg * a.S + s]) * (int64_t)a.F + f) * a.T + tl];
-                re = css_add_rn(re, css_mul_rn(w, v.x));
-                im = css_add_rn(im, css_mul_rn(w, v.y));
-            }
-            if (gs1 >= gs0) {
-                re = css_mul_rn(css_div_rn(re, wsum), gate);
-                im = css_mul_rn(css_div_rn(im, wsum), gate);
-            }
-        }
-        tile[tx * TS + f] = re;
-        tile[tx * TS + a.F + f] = im;
+        const float2 v = active ? ola_spec_value(a, s, f, t, gs0, gs1, wsum, gate) : make_float2(0.f, 0.f);
+        tile[tx * TS + f] = v.x;
+        tile[tx * TS + a.F + f] = v.y;
     }
     __syncthreads();
-    for (int r = 0; r < SG_T; ++r) {
+    for (int r = 0; r < OLA_T; ++r) {
         if (t0 + r >= t_hi) break;
         float* out = a.Y + ((int64_t)s * a.ld_frames + t0 + r) * a.KIp;
         for (int j = threadIdx.x; j < a.KIp; j += 256) out[j] = j < 2 * a.F ? tile[r * TS + j] : 0.f;
@@ -146,9 +101,9 @@ __device__ __forceinline__ void stream_gate_ola_body(const StreamStitchArgs& a, 
 }
 
 __global__ __launch_bounds__(256) void stream_gate_ola_kernel(StreamMulti m) {
-    const StreamFrames r = m.r[blockIdx.z];
-    if (r.t_lo + (int64_t)blockIdx.x * SG_T >= r.t_hi) return;
-    stream_gate_ola_body(m.a[blockIdx.z], r.t_lo, r.t_hi);
+    const StreamFrames r = m.e[blockIdx.z].r;
+    if (r.t_lo + (int64_t)blockIdx.x * OLA_T >= r.t_hi) return;
+    stream_gate_ola_body(m.e[blockIdx.z].a, r.t_lo, r.t_hi);
 }
 
 // The mask head of a shared batch writes ONE matrix [rows][src_ld] (time fastest, batch segment c at column c T); stream e's
@@ -157,7 +112,7 @@ __global__ __launch_bounds__(256) void stream_gate_ola_kernel(StreamMulti m) {
 // aligned for more than one row in four: a wave copies one row with dword loads and stores, 64 consecutive floats per
 // access (256 contiguous bytes on both sides).  It is 0.77 MB per segment behind an estimator pass of milliseconds.
 constexpr int SC_ENTRIES = 16, SC_ROWS = 4;
-struct MaskScatterTable { MaskScatter e[SC_ENTRIES]; };
+struct MaskScatterTable : Table<MaskScatter, SC_ENTRIES> {};
 __global__ __launch_bounds__(64 * SC_ROWS) void stream_scatter_masks_kernel(const float* __restrict__ src, int64_t src_ld, int rows,
                                                                             MaskScatterTable tab) {
     const MaskScatter e = tab.e[blockIdx.y];
@@ -178,7 +133,7 @@ __global__ __launch_bounds__(64 * SC_ROWS) void stream_scatter_masks_kernel(cons
 // number of samples was pushed before), so the stores are dwords, 64 consecutive ones per wave, as in
 // stream_scatter_masks_kernel.
 constexpr int IN_THREADS = 256, IN_TILE_MAX = 1024, IN_LDS_MAX = 32768;
-struct StreamIngestTable { StreamIngestPcm16 e[STREAM_MULTI_MAX]; };
+struct StreamIngestTable : Table<StreamIngestPcm16, STREAM_MULTI_MAX> {};
 __global__ __launch_bounds__(IN_THREADS) void stream_ingest_pcm16_kernel(StreamIngestTable tab, int tile) {
     extern __shared__ __attribute__((aligned(16))) int16_t span[];   // [tile][C] of an interleaved entry
     const StreamIngestPcm16 e = tab.e[blockIdx.y];
@@ -209,46 +164,41 @@ __global__ __launch_bounds__(IN_THREADS) void stream_ingest_pcm16_kernel(StreamI
 }
 
 void launch_stream_ingest_pcm16_multi(const StreamIngestPcm16* e, int n, hipStream_t s) {
-    for (int i0 = 0; i0 < n; i0 += STREAM_MULTI_MAX) {
-        const int cnt = std::min(STREAM_MULTI_MAX, n - i0);
-        StreamIngestTable tab{};
-        int64_t most = 0;
-        int C = 1;
-        for (int i = 0; i < cnt; ++i) { tab.e[i] = e[i0 + i]; most = std::max(most, e[i0 + i].n); C = std::max(C, e[i0 + i].C); }
+    for_each_table<StreamIngestTable>(e, n, [&](const StreamIngestTable& tab, int cnt) {
+        const int64_t most = table_max(tab, cnt, (int64_t)0, [](const StreamIngestPcm16& p) { return p.n; });
+        const int C = table_max(tab, cnt, 1, [](const StreamIngestPcm16& p) { return p.C; });
         // the largest multiple of 64 samples whose interleaved span fits IN_LDS_MAX (at least 64: C is 1 or 7 here)
         const int tile = std::max(64, std::min(IN_TILE_MAX, IN_LDS_MAX / (2 * C) / 64 * 64));
         if (most > 0)
             hipLaunchKernelGGL(stream_ingest_pcm16_kernel, dim3((unsigned)((most + tile - 1) / tile), cnt), dim3(IN_THREADS),
                                (size_t)tile * C * sizeof(int16_t), s, tab, tile);
-    }
+        return true;
+    });
+}
+
+static int64_t most_frames(const StreamMulti& m, int cnt) {
+    return table_max(m, cnt, (int64_t)0, [](const StreamEntry& e) { return e.r.t_hi - e.r.t_lo; });
 }
 
 void launch_stream_activity_multi(const StreamStitchArgs* a, const StreamFrames* r, int n, hipStream_t s) {
-    for (int i0 = 0; i0 < n; i0 += STREAM_MULTI_MAX) {
-        const int cnt = std::min(STREAM_MULTI_MAX, n - i0);
-        StreamMulti m{};
-        int64_t most = 0;
-        for (int i = 0; i < cnt; ++i) { m.a[i] = a[i0 + i]; m.r[i] = r[i0 + i]; most = std::max(most, r[i0 + i].t_hi - r[i0 + i].t_lo); }
+    for_each_table<StreamMulti>(n, [&](int i) { return StreamEntry{a[i], r[i]}; }, [&](const StreamMulti& m, int cnt) {
+        const int64_t most = most_frames(m, cnt);
         if (most > 0)
-            hipLaunchKernelGGL(stream_activity_kernel, dim3((unsigned)((most + SA_T - 1) / SA_T), a[i0].S, cnt), dim3(SA_T * SA_FG), 0, s, m);
-    }
+            hipLaunchKernelGGL(stream_activity_kernel, dim3((unsigned)((most + OLA_T - 1) / OLA_T), m.e[0].a.S, cnt), dim3(OLA_T * OLA_FG), 0, s, m);
+        return true;
+    });
 }
 
 void launch_stream_gate_ola_multi(const StreamStitchArgs* a, const StreamFrames* r, int n, hipStream_t s) {
-    for (int i0 = 0; i0 < n; i0 += STREAM_MULTI_MAX) {
-        const int cnt = std::min(STREAM_MULTI_MAX, n - i0);
-        StreamMulti m{};
-        int64_t most = 0;
-        int erosion = 0;   // the dynamic LDS of the launch is the largest entry's
-        for (int i = 0; i < cnt; ++i) {
-            m.a[i] = a[i0 + i]; m.r[i] = r[i0 + i];
-            most = std::max(most, r[i0 + i].t_hi - r[i0 + i].t_lo);
-            erosion = std::max(erosion, a[i0 + i].erosion);
-        }
-        const size_t lds = (size_t)SG_T * (2 * a[i0].F + 1) * sizeof(float) + (size_t)SG_T + 2 * (size_t)erosion;
+    for_each_table<StreamMulti>(n, [&](int i) { return StreamEntry{a[i], r[i]}; }, [&](const StreamMulti& m, int cnt) {
+        const int64_t most = most_frames(m, cnt);
+        // the dynamic LDS of the launch is the largest entry's
+        const int erosion = table_max(m, cnt, 0, [](const StreamEntry& e) { return e.a.erosion; });
+        const size_t lds = (size_t)OLA_T * (2 * m.e[0].a.F + 1) * sizeof(float) + (size_t)OLA_T + 2 * (size_t)erosion;
         if (most > 0)
-            hipLaunchKernelGGL(stream_gate_ola_kernel, dim3((unsigned)((most + SG_T - 1) / SG_T), a[i0].S, cnt), dim3(256), lds, s, m);
-    }
+            hipLaunchKernelGGL(stream_gate_ola_kernel, dim3((unsigned)((most + OLA_T - 1) / OLA_T), m.e[0].a.S, cnt), dim3(256), lds, s, m);
+        return true;
+    });
 }
 
 void launch_stream_activity(const StreamStitchArgs& a, int64_t t_lo, int64_t t_hi, hipStream_t s) {
@@ -261,13 +211,11 @@ void launch_stream_gate_ola(const StreamStitchArgs& a, int64_t t_lo, int64_t t_h
 }
 
 void launch_stream_scatter_masks(const float* src, int64_t src_ld, int rows, const MaskScatter* e, int n, hipStream_t s) {
-    for (int i0 = 0; i0 < n; i0 += SC_ENTRIES) {
-        const int cnt = std::min(SC_ENTRIES, n - i0);
-        MaskScatterTable tab{};
-        for (int i = 0; i < cnt; ++i) tab.e[i] = e[i0 + i];
+    for_each_table<MaskScatterTable>(e, n, [&](const MaskScatterTable& tab, int cnt) {
         hipLaunchKernelGGL(stream_scatter_masks_kernel, dim3((unsigned)((rows + SC_ROWS - 1) / SC_ROWS), cnt), dim3(64 * SC_ROWS), 0, s,
                            src, src_ld, rows, tab);
-    }
+        return true;
+    });
 }
 
 }  // namespace css

@@ -62,7 +62,7 @@ def test_stream_is_bit_identical_to_css_run_multichannel(mc_state, mix60):
     sep.close()
 
 
-@pytest.mark.parametrize("knob", ["sc", "normalize", "sep_mse", "th03", "sqrt_hann", "seg2", "seg10"])
+@pytest.mark.parametrize("knob", ["sc", "normalize", "sep_mse", "th03", "sqrt_hann", "seg2", "seg10", "dense"])
 def test_stream_knobs_and_models(knob, mc_state, sc_state, mix60):
     CSS = pkg("css")
     x = (mix60[0] if mix60.ndim == 3 else mix60)[:16000 * 24]
@@ -81,6 +81,9 @@ def test_stream_knobs_and_models(knob, mc_state, sc_state, mix60):
     elif knob == "seg10":
         cfg.segment_size_sec, cfg.hop_size_sec = 10.0, 5.0
         x = (mix60[0] if mix60.ndim == 3 else mix60)[:16000 * 40]
+    elif knob == "dense":   # six contributors per frame (186 frames, hop 37): the general overlap-add walk on both sides
+        cfg.segment_size_sec, cfg.hop_size_sec = 3.0, 0.6
+        x = x[:16000 * 12]
     sep = _sep(state)
     if knob == "sqrt_hann":
         sep.handle.set_analysis_window("sqrt_hann")

@@ -14,7 +14,7 @@ import pandas as pd
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 o = sys.argv[1]
-NAMES = {"deinterleave_kernel": "deinterleave", "stft_fft_kernel": "stft", "features_kernel": "features", "scm_kernel": "scm", "mvdr_solve": "mvdr_solve",
+NAMES = {"deinterleave_kernel": "deinterleave", "stft_fft_kernel": "stft", "features_kernel": "features", "scm_kernel": "scm", "mvdr_solve_multi_kernel": "mvdr_solve",
          "beamform_kernel": "beamform", "ola_masks_kernel": "ola_masks", "ola_stft_kernel": "ola_stft", "wave_ola_kernel": "wave_ola", "pit_cost_kernel": "pit"}
 
 
