@@ -7,8 +7,8 @@
 //     two waves per SIMD, both from ONE block: they run the same 32 MFMAs between the same barriers, and the pipe idles
 //     while both store the next slab, meet and wait for their first operand reads (a slab takes 2 680 cycles for 2 048 of
 //     MFMA issue with one wave per SIMD, tools/gemm_f32_bench.hip).  Here a wave owns 32 COLUMNS of the block's tile and all
-//     of its rows (TM row tiles of 32: at most 64 accumulator registers), the slab is 16 deep and double buffered
-//     (2 x (128 + 128) rows x 20 floats = 40 960 B: exactly a quarter of the CU's 160 KB), and the kernel is held to
+//     of its rows (TM row tiles of 32: at most 64 accumulator registers), the slab is 16 deep (short tiles: deeper, below) and
+//     double buffered (2 x (128 + 128) rows x 20 floats = 40 960 B: exactly a quarter of the CU's 160 KB), and the kernel is held to
 //     128 registers (__launch_bounds__(256, 4)) -- four waves per SIMD from four blocks that fill each other's bubbles.
 //     The kernels of the fast epilogue -- every Linear layer's -- fit that without spilling (hipcc -Rpass-analysis=
 //     kernel-resource-usage: no scratch; tests/test_gemm_f32_registers.py) because the host picks the epilogue kind: the
@@ -23,6 +23,14 @@
 //     the epilogue's residual reads and result writes, the next tile's cold first slab -- fall into the other blocks'
 //     K loops instead of all CUs leaving the matrix pipe idle together (one round of equal tiles: 25 us of a 116 us
 //     launch was prologue + epilogue, fitted over K).
+//   * The SLAB DEPTH belongs to the tile (round 10): what a wave pays per slab -- the wait for the next slab's loads, the LDS
+//     store, the block barrier, the first operand read behind it -- is the same for every tile height, the MFMAs it buys are
+//     8 per row unit and 16 k.  With the weights as register fragments and the fast epilogue (every Linear layer) a 32-row tile
+//     takes slabs 64 deep and a 64- or 96-row tile 32 deep (f32_max_depth; the deepest that divides K), 32 MFMAs per wave and
+//     barrier like the 128-row tile (48 at 96 rows); the A loads of a thread are whole 16-byte pieces of 256- / 128-byte row
+//     runs, the weight fragments a ring of one register set: each chunk's but the last's is requested a slab ahead, behind the
+//     last MFMA that read its registers, the last chunk's at the top of its own slab (f32_tile says why).  Same order of the
+//     MFMAs over k, same bits (tests/test_hip_gemm_f32_slab_depth.py).
 //   * Operands arrive by buffer loads (rows past M / N read zeros: no clamped row pointers, one offset register per
 //     operand); the epilogue requests a tile's residual values one 32 x 32 tile ahead (the first under the last slab's
 //     MFMAs) and writes 16-byte row pieces after a turn through a wave-private LDS patch.
@@ -35,8 +43,8 @@ namespace css {
 
 namespace {
 
-constexpr int F_BK = 16;                     // slab depth
-constexpr int F_LD = 20;                     // LDS row stride in floats: 5 * row mod 16 is a bijection -> conflict-free ds_read_b128
+constexpr int F_BK = 16;                     // slab depth of the tallest tile (and of every tile whose B operand goes through LDS)
+constexpr int F_LD = 20;                     // its LDS row stride in floats (depth + 4: see f32_tile)
 constexpr int F_BUF = (128 + BN) * F_LD;     // floats per slab buffer (A region sized for the tallest tile)
 constexpr int F_PATCH_LD = 36;
 
@@ -50,28 +58,76 @@ __device__ __forceinline__ float epi_value(float acc, float bn, float bm, int ac
     return v;
 }
 
+#ifndef F32_DMA
+#define F32_DMA 0   // 1: global -> LDS by the DMA path (buffer_load ... lds), unpadded 64-byte LDS rows with an XOR swizzle
+#endif
+#ifndef F32_SPREAD
+#define F32_SPREAD 1   // the next slab's global loads one per two MFMA groups of this slab instead of as a burst in front of it
+#endif
+#ifndef F32_DEEP
+#define F32_DEEP 1   // 0 (tools, A/B): every tile with 16-deep slabs, as before round 10
+#endif
+#ifndef F32_DEEP_TM1
+#define F32_DEEP_TM1 64   // slab depth of the 32-row tiles (tools: 16, 32)
+#endif
+#ifndef F32_DEEP_TM2
+#define F32_DEEP_TM2 32   // of the 64-row tiles (tools: 16)
+#endif
+#ifndef F32_DEEP_TM3
+#define F32_DEEP_TM3 32   // of the 96-row tiles (tools: 16)
+#endif
+// The deepest slab a tile of TM units may take (round 10).  What a wave pays per slab -- the wait for the global loads, the LDS
+// store, the block barrier, the first operand read -- does not depend on the tile's height, but the MFMAs it buys do: 8 TM per
+// 16 k.  So the short tiles take deeper slabs, 32 MFMAs per wave and barrier like the 128-row tile: 64 k for 32 rows, 32 k for
+// 64 rows -- and 32 k for 96 rows too (48 MFMAs: spill-free, and faster in tools/gemm_f32_bench.hip and in the pipeline,
+// profiles/r10_gemm_f32_slab_depth.md).  Only the kernels with the weights as register fragments (BD) can: their slab buffers' B
+// half is free.  A deep A slab of 32 x 68 or 64 x 36 floats fits the 128 x 20 floats of a buffer's A half; the 96 x 36 = 3 456
+// floats of the 96-row tile run on into the unused B half (f32_tile's static_assert holds a BD slab to the whole buffer).  The order
+// of the MFMAs over k does not change, so no bit does.  (The DMA path of the tools keeps its unpadded 16-float rows, and a deep
+// slab's weight ring needs the spread loads: depth 16 only for F32_DMA and for F32_SPREAD = 0.)
+constexpr int f32_max_depth(int tm, bool bd) {
+    return (!bd || !F32_DEEP || !F32_SPREAD || F32_DMA) ? 16 : tm == 1 ? F32_DEEP_TM1 : tm == 2 ? F32_DEEP_TM2 : tm == 3 ? F32_DEEP_TM3 : 16;
+}
+
 // BD: the B operand is a static weight in FRAGMENT order (launch_f32_fragments: float4 index ((j K/8 + kc) 64 + lane) holds
 // W[32 j + (lane & 31)][8 kc + 4 (lane >> 5) .. + 3], i.e. what lane `lane` feeds to the four MFMAs of chunk kc for column
 // tile j): it goes global -> registers as one coalesced 1 KiB load per wave and chunk -- no LDS store, no LDS read, half the
 // slab buffer -- because every memory instruction of this loop costs matrix issue time.
 // FAST: the fast epilogue (below), chosen on the host (f32_fast_epilogue): its launches run a kernel with no general-epilogue code.
-template <int TM, bool BD, bool FAST>
+// DK: the slab depth (16, 32, 64; a divisor of K -- f32_tile_any picks it per launch).  LDS rows are DK + 4 floats: DK / 4 + 1 is
+// odd, and the 16 lanes a ds_read_b128 serves together hold rows of 16 different residues mod 16, so they read 16 different
+// bank quads (as 20 = 16 + 4 did); a staging store's 8 lanes hold 8 consecutive pieces of one row for DK >= 32.
+template <int TM, bool BD, bool FAST, int DK>
 __device__ __forceinline__ void f32_tile(const GemmArgs& g, const float* __restrict__ A, const float* __restrict__ B,
                                          float* __restrict__ C, const int m0, const int n0, float* __restrict__ lds) {
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 31, h = lane >> 5;
+    // (the thread's index behind a compiler barrier: what every tile form derives from it -- staging rows, LDS addresses -- is
+    // otherwise formed once in front of the tile walk, for all forms, and held in registers the K loops do not have)
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    const int lane = tid & 63, w = tid >> 6, c = lane & 31, h = lane >> 5;
     const int M = g.M, N = g.N;
+    int gK = g.K;
+    int64_t glda = g.lda;
+    if constexpr (FAST) asm volatile("" : "+s"(gK), "+s"(glda));   // (as ldc and ldr below: slab counts, extents and pass strides per tile)
     constexpr int BM = 32 * TM;
-    constexpr int NPA = (BM + 63) / 64;      // staging passes over the A tile (64 rows x 16 floats per pass)
-    // ---- staging: thread -> (row srow + 64 i, floats sk .. sk + 3) of the slab
-    const int srow = tid >> 2, sk = (tid & 3) * 4;
+    constexpr int LD = DK + 4;               // LDS row stride in floats
+    constexpr int PPR = DK / 4;              // 16-byte pieces of a row's part of the slab: consecutive threads, one row piece each
+    constexpr int RPP = 256 / PPR;           // rows per staging pass
+    constexpr int NPA = (BM + RPP - 1) / RPP;   // staging passes over the A tile
+    constexpr int NCH = DK / 8;              // 8-k chunks (four MFMAs per row tile each) of a slab
+    static_assert(DK == 16 || (BD && (DK == 32 || DK == 64)), "deep slabs: the weights-as-fragments kernels only");
+    static_assert(BM * LD <= (BD ? F_BUF : 128 * F_LD), "the A slab must fit its buffer");
+    static_assert(!F32_DMA || DK == 16, "the DMA path stages 16-float rows");
+    // ---- staging: thread -> (row srow + RPP i, floats sk .. sk + 3) of the slab
+    const int srow = tid / PPR, sk = (tid % PPR) * 4;
     // (rows may overlap -- the analysis transform of an arbitrary frame size hands the recording's frames over as rows with
     // stride hop < K: the extent is the last row's end, not rows x stride)
-    const int64_t extA = (int64_t)(M - 1) * g.lda + (g.lda > g.K ? g.lda : g.K), extB = (int64_t)(N - 1) * g.ldb + (g.ldb > g.K ? g.ldb : g.K);
+    const int64_t extA = (int64_t)(M - 1) * glda + (glda > gK ? glda : gK), extB = (int64_t)(N - 1) * g.ldb + (g.ldb > gK ? g.ldb : gK);
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(A), 0, (int)(extA * 4), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(B), 0, (int)((BD ? (int64_t)((N + 31) / 32 * 32) * g.K : extB) * 4), 0x00020000);
-    const int voA = (int)(((int64_t)(m0 + srow) * g.lda + sk) * 4), voB = (int)(((int64_t)(n0 + srow) * g.ldb + sk) * 4);
-    const int passA = (int)(64 * g.lda * 4), passB = (int)(64 * g.ldb * 4);
-    const bool a1_on = (BM % 64 == 0) || srow < BM % 64;   // the last A pass of an odd TM covers 32 rows only
+    const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(B), 0, (int)((BD ? (int64_t)((N + 31) / 32 * 32) * gK : extB) * 4), 0x00020000);
+    const int voA = (int)(((int64_t)(m0 + srow) * glda + sk) * 4), voB = (int)(((int64_t)(n0 + srow) * g.ldb + sk) * 4);
+    const int passA = (int)(RPP * glda * 4), passB = (int)(64 * g.ldb * 4);   // (B through LDS: DK = 16, 64 rows per pass)
+    const bool a1_on = (BM % RPP == 0) || srow < BM % RPP;   // the last A pass may cover fewer rows (DK = 16: 32 of 64 for an odd TM)
 #ifndef F32_TOOLS
 #define F32_TOOLS 0   // tools/gemm_f32_bench.hip only (-DF32_TOOLS=1): the block census below (GemmArgs::narrow_epilogue == 77 turns
                       // GemmArgs::range_flag into a census buffer).  The library never compiles that path: range_flag there is ONE word.
@@ -81,9 +137,6 @@ __device__ __forceinline__ void f32_tile(const GemmArgs& g, const float* __restr
 #endif
 #ifndef F32_FAST_EPILOGUE
 #define F32_FAST_EPILOGUE 1   // 0: the general epilogue for every launch (A/B, tools)
-#endif
-#ifndef F32_SPREAD
-#define F32_SPREAD 1   // the next slab's global loads one per two MFMA groups of this slab instead of as a burst in front of it
 #endif
 #ifndef F32_TRANSPOSED
 #define F32_TRANSPOSED 0   // 1: the MFMA operands swapped (weights first): the accumulators hold the tile TRANSPOSED -- lane = token row,
@@ -104,16 +157,15 @@ __device__ __forceinline__ void f32_tile(const GemmArgs& g, const float* __restr
 #else
 #define F32_AFTER_STORE(o)
 #endif
-#ifndef F32_DMA
-#define F32_DMA 0   // 1: global -> LDS by the DMA path (buffer_load ... lds), unpadded 64-byte LDS rows with an XOR swizzle
-#endif
 #if F32_DMA
     // LDS row r (16 floats = four 16-byte slots) holds its k segment s in slot s ^ ((r >> 2) & 3): the 16 lanes of a
     // ds_read_b128 group then hit 16 distinct bank quads.  The DMA writes lane l's 16 bytes at base + 16 l, so lane l
     // (row l >> 2 of its wave's 16 rows, slot l & 3) FETCHES segment (l & 3) ^ ((row >> 2) & 3).
     constexpr int D_BUF = (128 + BN) * 16;
+    f32x4 wc[NCH] = {}, wn[NCH] = {};   // (never loaded: launch_gemm_f32 refuses fragment-ordered weights in a DMA build)
+    const int vw = 0;
     const int dseg = ((tid & 3) ^ ((tid >> 4) & 3)) * 4;
-    const int dvoA = (int)(((int64_t)(m0 + srow) * g.lda + dseg) * 4), dvoB = (int)(((int64_t)(n0 + srow) * g.ldb + dseg) * 4);
+    const int dvoA = (int)(((int64_t)(m0 + srow) * glda + dseg) * 4), dvoB = (int)(((int64_t)(n0 + srow) * g.ldb + dseg) * 4);
     const bool a1_wave = (BM % 64 == 0) || w < (BM % 64) / 16;   // (wave-uniform: a wave covers 16 rows of a pass)
     typedef __attribute__((address_space(3))) void lds_void;
 #define F32_GLOAD(k0, buf)                                                                                       \
@@ -129,8 +181,15 @@ __device__ __forceinline__ void f32_tile(const GemmArgs& g, const float* __restr
 #define F32_SPREAD 0
 #else
     f32x4 ra[NPA], rb[2];
-    f32x4 wc[2], wn[2];   // BD: this slab's / the next slab's weight fragments (two chunks of 8 k each)
-    const int vw = (int)((((int64_t)(n0 / 32 + w) * (g.K / 8)) * 64 + lane) * 16);
+    // BD: this slab's / the next slab's weight fragments (NCH chunks of 8 k each).  A deep slab keeps ONE set, wc, as a ring:
+    // chunk ch's fragment of the next slab is requested into wc[ch] behind the chunk's last MFMA, a whole slab ahead of its use
+    // -- no second set (64 registers at depth 64) and no copies.  The LAST chunk's fragment is requested at the top of its own
+    // slab instead (4 NCH - 4 MFMA groups ahead of its use): a load behind the slab's last MFMA is a load the compiler may place
+    // in front of that MFMA -- nothing in the block uses the MFMA's result --, and then the fragment needs other registers than
+    // the ones the MFMA still reads: the ring turns into a shift with copies and a vmcnt(0) at every slab's head (seen in the
+    // depth-64 body).  So wc[NCH - 1] is not carried from slab to slab at all.
+    f32x4 wc[NCH], wn[DK == 16 ? NCH : 1];
+    const int vw = (int)((((int64_t)(n0 / 32 + w) * (gK / 8)) * 64 + lane) * 16);
 #define F32_GLOAD(k0, buf)                                                                                       \
     _Pragma("unroll") for (int i = 0; i < NPA; ++i) {                                                            \
         if (i + 1 < NPA || a1_on) ra[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, voA, (k0) * 4 + i * passA, 0)); \
@@ -139,40 +198,43 @@ __device__ __forceinline__ void f32_tile(const GemmArgs& g, const float* __restr
         _Pragma("unroll") for (int i = 0; i < 2; ++i)                                                            \
             rb[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsB, voB, (k0) * 4 + i * passB, 0)); \
     } else {                                                                                                     \
-        wn[0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsB, vw, ((k0) / 8) * 1024, 0)); \
-        wn[1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsB, vw, ((k0) / 8 + 1) * 1024, 0)); \
+        _Pragma("unroll") for (int i = 0; i < (DK == 16 ? NCH : NCH - 1); ++i) {   /* (deep: the last chunk's at its slab's top) */ \
+            const f32x4 w_ = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsB, vw, ((k0) / 8 + i) * 1024, 0)); \
+            if constexpr (DK == 16) wn[i] = w_; else wc[i] = w_;                                                 \
+        }                                                                                                        \
     }
-    // load j of the next slab (A passes first, then the two B / weight pieces): F32_SPREAD issues them one per two MFMA groups
+    // load j of the next slab (A passes first, then the B / weight pieces): F32_SPREAD issues them one per two MFMA groups (deep
+    // slabs: the A passes one per group from the slab's first, each weight piece behind its chunk)
 #define F32_GLOAD1(k0, j)                                                                                        \
     {                                                                                                            \
         if ((j) < NPA) {                                                                                         \
             if ((j) + 1 < NPA || a1_on) ra[(j) < NPA ? (j) : 0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, voA, (k0) * 4 + (j) * passA, 0)); \
-        } else if ((j) < NPA + 2) {                                                                              \
-            if constexpr (!BD) rb[(j) - NPA] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsB, voB, (k0) * 4 + ((j) - NPA) * passB, 0)); \
-            else wn[(j) - NPA] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsB, vw, ((k0) / 8 + (j) - NPA) * 1024, 0)); \
+        } else if ((j) < NPA + (BD ? NCH : 2)) {                                                                 \
+            if constexpr (!BD) rb[((j) - NPA) & 1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsB, voB, (k0) * 4 + ((j) - NPA) * passB, 0)); \
+            else wn[DK == 16 ? ((j) - NPA) & 1 : 0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsB, vw, ((k0) / 8 + (j) - NPA) * 1024, 0)); \
         }                                                                                                        \
     }
 #define F32_LSTORE(buf)                                                                                          \
     {                                                                                                            \
-        float* as_ = lds + (buf) * F_BUF + srow * F_LD + sk;                                                     \
+        float* as_ = lds + (buf) * F_BUF + srow * LD + sk;                                                       \
         _Pragma("unroll") for (int i = 0; i < NPA; ++i) {                                                        \
-            if (i + 1 < NPA || a1_on) *reinterpret_cast<f32x4*>(as_ + i * 64 * F_LD) = ra[i];                    \
+            if (i + 1 < NPA || a1_on) *reinterpret_cast<f32x4*>(as_ + i * RPP * LD) = ra[i];                     \
         }                                                                                                        \
         if constexpr (!BD) {                                                                                     \
-            _Pragma("unroll") for (int i = 0; i < 2; ++i) *reinterpret_cast<f32x4*>(as_ + (128 + i * 64) * F_LD) = rb[i]; \
+            _Pragma("unroll") for (int i = 0; i < 2; ++i) *reinterpret_cast<f32x4*>(as_ + (128 + i * 64) * LD) = rb[i]; \
         }                                                                                                        \
     }
 #endif
     f32x16 acc[TM];
 #pragma unroll
     for (int i = 0; i < TM; ++i) acc[i] = f32x16{0};
-    const int nk = g.K / F_BK;
+    const int nk = gK / DK;
 #if F32_PROBE
     const unsigned long long t_in_ = (w == 0) ? __builtin_readcyclecounter() : 0;
 #endif
     F32_GLOAD(0, 0)
     F32_LSTORE(0)
-    if constexpr (BD) { wc[0] = wn[0]; wc[1] = wn[1]; }
+    if constexpr (BD && DK == 16) { wc[0] = wn[0]; wc[1] = wn[1]; }
     __syncthreads();
 #if F32_DMA
     constexpr int S_BUF = D_BUF, S_LD = 16;
@@ -180,8 +242,8 @@ __device__ __forceinline__ void f32_tile(const GemmArgs& g, const float* __restr
     const int aoff = c * 16, boff = (128 + 32 * w + c) * 16;
 #define F32_SLOT(ch) (((8 * (ch) + 4 * h)) ^ sw4)
 #else
-    constexpr int S_BUF = F_BUF, S_LD = F_LD;
-    const int aoff = c * F_LD + 4 * h, boff = (128 + 32 * w + c) * F_LD + 4 * h;
+    constexpr int S_BUF = F_BUF, S_LD = LD;
+    const int aoff = c * LD + 4 * h, boff = (128 + 32 * w + c) * LD + 4 * h;
 #define F32_SLOT(ch) (8 * (ch))
 #endif
     // epilogue operands: lane -> rows (lane >> 3) + 8 j of each 32 x 32 tile, columns n .. n + 3
@@ -189,7 +251,10 @@ __device__ __forceinline__ void f32_tile(const GemmArgs& g, const float* __restr
     const float* __restrict__ res = g.residual;
     const int act = g.act;
     const bool bias_m = bias && g.bias_along_m, bias_n = bias && !g.bias_along_m, has_res = res != nullptr;
-    const int64_t ldc = g.ldc, ldr = g.ldr;
+    int64_t ldc = g.ldc, ldr = g.ldr;
+    // (behind a compiler barrier: otherwise every row multiple of ldc and ldr that the epilogues of all tile forms use is formed in
+    // front of the tile walk and held in scalar registers through it -- with the deep forms' bodies more than there are)
+    if constexpr (FAST) asm volatile("" : "+s"(ldc), "+s"(ldr));
     const float alpha = g.alpha;
     // (the general epilogue's 16-byte pieces; the fast one always has them)
     const bool wide = FAST || ((ldc % 4 == 0) && (N % 4 == 0) && ((reinterpret_cast<uintptr_t>(C) & 15) == 0) &&
@@ -247,30 +312,61 @@ __device__ __forceinline__ void f32_tile(const GemmArgs& g, const float* __restr
 #define F32_ABLATE 0   // tools: timing probes (wrong results): 1 no slab barrier, 2 no global loads / LDS stores, 4 no LDS operand reads; 8 (right results): accumulators in AGPRs
 #endif
     f32x4 abl_a = {1.f, 2.f, 3.f, (float)lane}, abl_b = {0.5f, 0.25f, (float)w, 1.f};
+#define F32_MFMA(i, av, bv)                                                                                      \
+    {                                                                                                            \
+        if (F32_ABLATE & 8) asm volatile("v_mfma_f32_32x32x2_f32 %0, %1, %2, %0" : "+a"(acc[i]) : "v"(av), "v"(bv)); \
+        else if (F32_TRANSPOSED) acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(bv, av, acc[i], 0, 0, 0);         \
+        else acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[i], 0, 0, 0);                             \
+    }
+    // A deep slab (DK > 16, weights in registers) reads chunk ch + 1's A fragments in front of chunk ch's MFMAs: the slab's
+    // NCH operand reads cost one exposed LDS latency, the first, instead of one each.
 #define F32_COMPUTE(buf)                                                                                         \
     {                                                                                                            \
         const float* as = lds + (buf) * S_BUF + aoff;                                                            \
         const float* bs = lds + (buf) * S_BUF + boff;                                                            \
-        _Pragma("unroll") for (int ch = 0; ch < 2; ++ch) {                                                       \
-            f32x4 b = abl_b;                                                                                     \
-            if constexpr (BD) b = wc[ch];                                                                        \
-            else if (!(F32_ABLATE & 4)) b = *reinterpret_cast<const f32x4*>(bs + F32_SLOT(ch));                  \
-            f32x4 a[TM];                                                                                         \
-            _Pragma("unroll") for (int i = 0; i < TM; ++i) {                                                     \
-                a[i] = abl_a;                                                                                    \
-                if (!(F32_ABLATE & 4)) a[i] = *reinterpret_cast<const f32x4*>(as + i * 32 * S_LD + F32_SLOT(ch)); \
-            }                                                                                                    \
-            __builtin_amdgcn_sched_barrier(0);                                                                   \
-            _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                                      \
-                if (F32_SPREAD && spread_k0 >= 0 && !(e & 1)) { F32_GLOAD1(spread_k0, ch * 2 + (e >> 1)) __builtin_amdgcn_sched_barrier(0); } \
+        if constexpr (DK == 16) {                                                                                \
+            _Pragma("unroll") for (int ch = 0; ch < 2; ++ch) {                                                   \
+                f32x4 b = abl_b;                                                                                 \
+                if constexpr (BD) b = wc[ch];                                                                    \
+                else if (!(F32_ABLATE & 4)) b = *reinterpret_cast<const f32x4*>(bs + F32_SLOT(ch));              \
+                f32x4 a[TM];                                                                                     \
                 _Pragma("unroll") for (int i = 0; i < TM; ++i) {                                                 \
-                    if (F32_ABLATE & 8) asm volatile("v_mfma_f32_32x32x2_f32 %0, %1, %2, %0" : "+a"(acc[i]) : "v"(a[i][e]), "v"(b[e])); \
-                    else if (F32_TRANSPOSED) acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[e], a[i][e], acc[i], 0, 0, 0); \
-                    else acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i][e], b[e], acc[i], 0, 0, 0);          \
+                    a[i] = abl_a;                                                                                \
+                    if (!(F32_ABLATE & 4)) a[i] = *reinterpret_cast<const f32x4*>(as + i * 32 * S_LD + F32_SLOT(ch)); \
                 }                                                                                                \
-                if (F32_SPREAD && spread_k0 >= 0) __builtin_amdgcn_sched_barrier(0);                             \
+                __builtin_amdgcn_sched_barrier(0);                                                               \
+                _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                                  \
+                    if (F32_SPREAD && spread_k0 >= 0 && !(e & 1)) { F32_GLOAD1(spread_k0, ch * 2 + (e >> 1)) __builtin_amdgcn_sched_barrier(0); } \
+                    _Pragma("unroll") for (int i = 0; i < TM; ++i) F32_MFMA(i, a[i][e], b[e])                    \
+                    if (F32_SPREAD && spread_k0 >= 0) __builtin_amdgcn_sched_barrier(0);                         \
+                }                                                                                                \
+                __builtin_amdgcn_sched_barrier(0);                                                               \
             }                                                                                                    \
-            __builtin_amdgcn_sched_barrier(0);                                                                   \
+        } else {                                                                                                 \
+            wc[NCH - 1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsB, vw, (cur_k0 / 8 + NCH - 1) * 1024, 0)); \
+            f32x4 a[2][TM];                                                                                      \
+            _Pragma("unroll") for (int i = 0; i < TM; ++i) {                                                     \
+                a[0][i] = abl_a;                                                                                 \
+                if (!(F32_ABLATE & 4)) a[0][i] = *reinterpret_cast<const f32x4*>(as + i * 32 * S_LD);            \
+            }                                                                                                    \
+            _Pragma("unroll") for (int ch = 0; ch < NCH; ++ch) {                                                 \
+                if (ch + 1 < NCH) {                                                                              \
+                    _Pragma("unroll") for (int i = 0; i < TM; ++i) {                                             \
+                        a[(ch + 1) & 1][i] = abl_a;                                                              \
+                        if (!(F32_ABLATE & 4)) a[(ch + 1) & 1][i] = *reinterpret_cast<const f32x4*>(as + i * 32 * S_LD + 8 * (ch + 1)); \
+                    }                                                                                            \
+                }                                                                                                \
+                __builtin_amdgcn_sched_barrier(0);                                                               \
+                _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                                  \
+                    if (spread_k0 >= 0 && ch * 4 + e < NPA) { F32_GLOAD1(spread_k0, ch * 4 + e) __builtin_amdgcn_sched_barrier(0); } \
+                    _Pragma("unroll") for (int i = 0; i < TM; ++i) F32_MFMA(i, a[ch & 1][i][e], wc[ch][e])       \
+                    if (spread_k0 >= 0) __builtin_amdgcn_sched_barrier(0);                                       \
+                }                                                                                                \
+                if (spread_k0 >= 0 && ch + 1 < NCH) {                                                            \
+                    wc[ch] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsB, vw, (spread_k0 / 8 + ch) * 1024, 0)); \
+                }                                                                                                \
+                __builtin_amdgcn_sched_barrier(0);                                                               \
+            }                                                                                                    \
         }                                                                                                        \
     }
     // slabs 0 .. nk - 2: the next slab travels global -> registers under this slab's MFMAs, then registers -> LDS
@@ -282,19 +378,20 @@ __device__ __forceinline__ void f32_tile(const GemmArgs& g, const float* __restr
 #else
 #define F32_CLK(var)
 #endif
-    int spread_k0 = -1;
+    int spread_k0 = -1, cur_k0 = 0;   // (k of the next slab while its loads are spread under this one's MFMAs; k of this slab)
     for (int kt = 0; kt + 1 < nk; ++kt) {
 #if F32_PROBE
         unsigned long long t0_ = 0, t1_ = 0, t2_ = 0, t3_ = 0;
 #endif
         F32_CLK(t0_)
-        if (F32_SPREAD) spread_k0 = (kt + 1) * F_BK;
-        else if (!(F32_ABLATE & 2)) { F32_GLOAD((kt + 1) * F_BK, (kt + 1) & 1) }
+        cur_k0 = kt * DK;
+        if (F32_SPREAD) spread_k0 = (kt + 1) * DK;
+        else if (!(F32_ABLATE & 2)) { F32_GLOAD((kt + 1) * DK, (kt + 1) & 1) }
         __builtin_amdgcn_sched_barrier(0);   // (the compiler otherwise sinks the loads below the MFMAs, next to their LDS stores)
         F32_COMPUTE(kt & 1)
         F32_CLK(t1_)
         if (!(F32_ABLATE & 2)) { F32_LSTORE((kt + 1) & 1) }
-        if constexpr (BD) { wc[0] = wn[0]; wc[1] = wn[1]; }
+        if constexpr (BD && DK == 16) { wc[0] = wn[0]; wc[1] = wn[1]; }
         F32_CLK(t2_)
         if (!(F32_ABLATE & 1)) __syncthreads();
         F32_CLK(t3_)
@@ -327,9 +424,11 @@ __device__ __forceinline__ void f32_tile(const GemmArgs& g, const float* __restr
         else prefetch(0, 0, lane_);
     }
     spread_k0 = -1;
+    cur_k0 = (nk - 1) * DK;
     F32_COMPUTE((nk - 1) & 1)
     __syncthreads();
 #undef F32_COMPUTE
+#undef F32_MFMA
 #undef F32_SLOT
 #undef F32_GLOAD
 #undef F32_GLOAD1
@@ -469,6 +568,25 @@ __device__ __forceinline__ void f32_tile(const GemmArgs& g, const float* __restr
 #undef F32_EPILOGUE_PROBE
 }
 
+// A tile of TM units at the deepest slab its height may take (f32_max_depth) that divides K -- no remainder slabs: K = 512 and
+// 1 024 take 64, the embedding's 1 824 takes 32, any other multiple of 16 takes 16.
+// (Every entry point of the library takes K % 32 == 0 only, so through the library heights 1 - 3 always run deep: their depth-16
+// bodies in gemm_f32_kernel<true, true> -- three of its eight tile bodies -- are reached by direct callers of
+// launch_gemm with K = 16 (2 n + 1) alone, and no pytest case runs them; tools/gemm_f32_bench.hip's bit check does, built
+// with -DF32_DEEP=0.)
+template <int TM, bool BD, bool FAST>
+__device__ __forceinline__ void f32_tile_any(const GemmArgs& g, const float* __restrict__ A, const float* __restrict__ B,
+                                             float* __restrict__ C, const int m0, const int n0, float* __restrict__ lds) {
+    constexpr int D = f32_max_depth(TM, BD && FAST);   // (the general epilogue's kernels have no registers for a deep body)
+    if constexpr (D >= 64) {
+        if (g.K % 64 == 0) return f32_tile<TM, BD, FAST, 64>(g, A, B, C, m0, n0, lds);
+    }
+    if constexpr (D >= 32) {
+        if (g.K % 32 == 0) return f32_tile<TM, BD, FAST, 32>(g, A, B, C, m0, n0, lds);
+    }
+    f32_tile<TM, BD, FAST, 16>(g, A, B, C, m0, n0, lds);
+}
+
 }  // namespace
 
 // The work of a launch as a line of units (32 rows x 128 columns): index = (batch entry * tiles_n + column panel) * u + row
@@ -510,10 +628,10 @@ __global__ __launch_bounds__(256, 4) void gemm_f32_kernel(GemmArgs g, F32Plan p)
         if (!first) __syncthreads();   // the previous tile's epilogue patches lie over the slab buffers
         first = false;
         switch (tm) {
-            case 1: f32_tile<1, BD, FAST>(g, A, B, C, 32 * r, tn * BN, lds); break;
-            case 2: f32_tile<2, BD, FAST>(g, A, B, C, 32 * r, tn * BN, lds); break;
-            case 3: f32_tile<3, BD, FAST>(g, A, B, C, 32 * r, tn * BN, lds); break;
-            default: f32_tile<4, BD, FAST>(g, A, B, C, 32 * r, tn * BN, lds); break;
+            case 1: f32_tile_any<1, BD, FAST>(g, A, B, C, 32 * r, tn * BN, lds); break;
+            case 2: f32_tile_any<2, BD, FAST>(g, A, B, C, 32 * r, tn * BN, lds); break;
+            case 3: f32_tile_any<3, BD, FAST>(g, A, B, C, 32 * r, tn * BN, lds); break;
+            default: f32_tile_any<4, BD, FAST>(g, A, B, C, 32 * r, tn * BN, lds); break;
         }
         pos += tm;
         want = p.max_tm;
@@ -547,6 +665,9 @@ bool launch_gemm_f32(const GemmArgs& g, hipStream_t s, int forced_tm) {
     if (g.K <= 0 || g.K % F_BK) return false;
     const int64_t lim = (int64_t)1 << 31;
     if ((((int64_t)g.M + 128) * g.lda + g.K) * 4 >= lim || (((int64_t)g.N + 128) * g.ldb + g.K) * 4 >= lim) return false;
+#if F32_DMA
+    if (g.b_frag32) return false;   // (the DMA path stages a row-major B: the caller's B_rows fallback, or a loud refusal)
+#endif
     if (g.b_frag32 && (g.N % 32 || g.K % 16 || g.batch != 1 || ((int64_t)g.N * g.K * 4 >= lim))) return false;
     if ((g.lda % 4) || (!g.b_frag32 && (g.ldb % 4)) || (reinterpret_cast<uintptr_t>(g.A) & 15) || (reinterpret_cast<uintptr_t>(g.B) & 15)) return false;   // 16-byte operand loads
     constexpr int NCU = 256;

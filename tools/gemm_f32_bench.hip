@@ -36,7 +36,15 @@ int main(int argc, char** argv) {
     Shape shapes[] = {{512, 512, "attn-out", 1}, {1024, 512, "ffn-up", 0}, {512, 1024, "ffn-down", 1}, {1536, 512, "qkv", 0}, {512, 1824, "embed", 0}};
     int Ms[] = {7440, 22320, 22320, 22320, 29760};
     if (getenv("GEMM_BENCH_M")) Ms[1] = atoi(getenv("GEMM_BENCH_M"));   // the second height of the table (the headline's shared batch: 44640)
-    const int layouts[] = {8, 1, 13, 12, 0};   // round-4 kernel (8 waves) | gemm_f32.hip (tiles up to 128 rows) | up to 96 | up to 64
+    int layouts[8] = {8, 1, 13, 12, 0};   // round-4 kernel (8 waves) | gemm_f32.hip (tiles up to 128 rows) | up to 96 | up to 64
+    int nlay = 5;
+    if (const char* e = getenv("GEMM_BENCH_LAYOUTS")) {   // e.g. 8,1,11,12,13,14 (the first one is the reference for the bits); at most 7
+        nlay = 0;
+        for (const char* q = e; *q && nlay < 7; ) { layouts[nlay++] = atoi(q); while (*q && *q != ',') ++q; if (*q) ++q; }
+        layouts[nlay] = 0;
+    }
+    const int reps = getenv("GEMM_BENCH_REPS") ? std::max(1, atoi(getenv("GEMM_BENCH_REPS"))) : 1;   // repeats of the timed loop: median, (min .. max)
+    if (getenv("GEMM_BENCH_M0")) Ms[0] = atoi(getenv("GEMM_BENCH_M0"));
     const size_t maxA = (size_t)44640 * 2048, maxB = (size_t)2048 * 1824, maxC = (size_t)44640 * 2048;
     float *A, *B, *C, *R;
     hipMalloc(&A, maxA * 4); hipMalloc(&B, maxB * 4 + 4096); hipMalloc(&C, maxC * 4); hipMalloc(&R, maxC * 4);
@@ -58,7 +66,7 @@ int main(int argc, char** argv) {
             printf("mfma_f32_32x32x2 rate: %3d blocks x %d waves: %.1f us, %.1f TFLOP/s\n", blocks, threads / 64, ms * 1e3, n * 4096 / (ms * 1e-3) / 1e12);
         }
     }
-    {   // census of the persistent blocks of one launch: start / end (100 MHz wall clock), shader cycles, physical CU
+    if (!getenv("GEMM_BENCH_NO_CENSUS")) {   // census of the persistent blocks of one launch: start / end (100 MHz wall clock), shader cycles, physical CU
         unsigned long long* dbg; hipMalloc(&dbg, 1024 * 96);   // [1024][4] census + [1024][4] slab-clock sums of wave 0 (builds with -DF32_PROBE=1)
         float* Bfc = nullptr; hipMalloc(&Bfc, maxB * 4 + 4096);
         // (GEMM_BENCH_M: the estimator's five Linear shapes at that height with their bias / residual, as the timing table runs them)
@@ -116,7 +124,7 @@ int main(int argc, char** argv) {
             if (!Bf) hipMalloc(&Bf, maxB * 4 + 4096);
             const bool fragw = getenv("GEMM_BENCH_FRAG") != nullptr;
             if (fragw) launch_f32_fragments(B, sh.K, Bf, sh.N, sh.K, st);
-            for (int layout : layouts) {
+            for (int lx = 0; lx < nlay; ++lx) { const int layout = layouts[lx];
                 GemmArgs g{};
                 g.A = A; g.lda = sh.K; g.B = B; g.ldb = sh.K; g.C = C; g.ldc = sh.N; g.M = M; g.N = sh.N; g.K = sh.K; g.batch = 1; g.alpha = 1.f;
                 if (fragw && layout != 8) { g.B = Bf; g.b_frag32 = 1; }
@@ -124,13 +132,20 @@ int main(int argc, char** argv) {
                 if (sh.mode == 1) { g.residual = R; g.ldr = sh.N; g.alpha = 0.5f; }
                 g.layout = layout;
                 for (int i = 0; i < 2; ++i) launch_gemm(g, st);
-                hipEventRecord(e0, st);
                 const int it = 10;
-                for (int i = 0; i < it; ++i) launch_gemm(g, st);
-                hipEventRecord(e1, st); hipEventSynchronize(e1);
-                float ms; hipEventElapsedTime(&ms, e0, e1);
-                const double fl = 2.0 * M * sh.N * sh.K, us = 1e3 * ms / it;
-                printf("  L%-2d %7.1f us %5.1f TF %.3f |", layout, us, fl / (us * 1e-6) / 1e12, fl / (us * 1e-6) / 1e12 / 157.3);
+                std::vector<double> rus;
+                for (int rep = 0; rep < reps; ++rep) {
+                    hipEventRecord(e0, st);
+                    for (int i = 0; i < it; ++i) launch_gemm(g, st);
+                    hipEventRecord(e1, st); hipEventSynchronize(e1);
+                    float ms; hipEventElapsedTime(&ms, e0, e1);
+                    rus.push_back(1e3 * ms / it);
+                }
+                std::sort(rus.begin(), rus.end());
+                const double fl = 2.0 * M * sh.N * sh.K, us = rus[rus.size() / 2];
+                printf("  L%-2d %7.1f us", layout, us);
+                if (reps > 1) printf(" (%.1f .. %.1f)", rus.front(), rus.back());
+                printf(" %5.1f TF %.3f |", fl / (us * 1e-6) / 1e12, fl / (us * 1e-6) / 1e12 / 157.3);
                 {   // every layout must give the bits of the first one
                     static std::vector<float> ref, got;
                     const size_t ne = (size_t)M * sh.N;
@@ -153,7 +168,7 @@ int main(int argc, char** argv) {
         {   // the mask head: weights [1028][512] are the A operand, the tokens B; row bias + sigmoid; tokens fastest
             printf("%-9s M=%6d N=%5d K=%5d :", "head", 1028, M, 512);
             int li = 0;
-            for (int layout : layouts) {
+            for (int lx = 0; lx < nlay; ++lx) { const int layout = layouts[lx];
                 GemmArgs g{};
                 g.A = B; g.lda = 512; g.B = A; g.ldb = 512; g.C = C; g.ldc = M; g.M = 1028; g.N = M; g.K = 512; g.batch = 1; g.alpha = 1.f;
                 g.bias = R; g.bias_along_m = 1; g.act = ACT_SIGMOID; g.m_fastest = 1; g.layout = layout;
@@ -178,7 +193,7 @@ int main(int argc, char** argv) {
         // the estimator's launch mix: embed x 1, (ffn-up, ffn-down) x 36, (qkv, attn-out) x 18
         const double fl_mix = 2.0 * M * (512.0 * 1824 + 36 * 2 * 512.0 * 1024 + 18 * (1536.0 * 512 + 512.0 * 512));
         printf("   => estimator mix at M=%d:", M);
-        for (int li = 0; li < 4; ++li) printf("  L%-2d %8.1f us  frac %.3f |", layouts[li], tot[mi][li], fl_mix / (tot[mi][li] * 1e-6) / 1e12 / 157.3);
+        for (int li = 0; li < nlay; ++li) printf("  L%-2d %8.1f us  frac %.3f |", layouts[li], tot[mi][li], fl_mix / (tot[mi][li] * 1e-6) / 1e12 / 157.3);
         printf("\n");
     }
     return 0;
