@@ -115,7 +115,9 @@ __device__ __forceinline__ void handoff_mel_tile(MelTilePw& pw, const float* __r
         float acc = 0.f;
         const float* wm = w + (size_t)m * MEL_BINS;
         for (int f = 0; f < MEL_BINS; ++f) acc = fmaf(wm[f], pw[f][tj], acc);
-        const float v = log10f(fmaxf(acc, 1e-10f));
+        // At the floor the value is -10.0f itself: the device library's log10f(1e-10f) lies one ulp below it, and Whisper's
+        // features of silence are -1.5, the value the encoder windows pad with.  (A NaN sum compares false: the floor, as fmaxf gave.)
+        const float v = acc > 1e-10f ? log10f(acc) : -10.0f;
         if (j0 + tj < nfr) {
             mel[(int64_t)m * mel_ld + j0 + tj] = v;
             best = fmaxf(best, v);
