@@ -63,7 +63,7 @@ typedef enum css_status {
 /* Architecture of the mask estimator.  Mirrors the dataclasses of
  * css/training/conformer_wrapper.py:11-48 (ExtractorCfg / ConformerCfg / NnetCfg). */
 typedef struct CssModelDesc {
-    int32_t num_mics;        /* 7 (multi-channel) or 1 (single-channel)                 */
+    int32_t num_mics;        /* 1 (single-channel) or 2 .. 8 (MVDR; 7: the NOTSOFAR array) */
     int32_t num_bins;        /* F = frame_len/2 + 1 = 257                               */
     int32_t in_features;     /* 1799 = F*(1 + 6 IPD pairs), or 257                      */
     int32_t attention_dim;   /* D = 512                                                 */
@@ -145,7 +145,7 @@ typedef enum css_buffer {
     CSS_BUF_X = 0,          /* float  [C][2F][T_ld]                  (see css_buffer_dims)          */
     CSS_BUF_FEATURES = 1,   /* float  [batch tokens][K_pad]          last processed batch           */
     CSS_BUF_MASKS = 2,      /* float  [(S+1)F][num_segments*T_seg]                                  */
-    CSS_BUF_SCM = 3,        /* double [segments][S+1][F][49]                                        */
+    CSS_BUF_SCM = 3,        /* double [segments][S+1][F][C C]: packed Hermitian, 49 at 7 microphones */
     CSS_BUF_BFW = 4,        /* double [segments][S][F][C][2]                                        */
     CSS_BUF_SEP = 5,        /* float  [segments][S][F][T_seg][2]                                    */
     CSS_BUF_PIT_COST = 6,   /* double [segments-1][S*S]  raw (unpermuted) costs                     */

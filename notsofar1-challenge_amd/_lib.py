@@ -210,6 +210,14 @@ class CssMvdrDesc(C.Structure):
                [("sets", CssMvdrSet * 16)]
 
 
+class CssMvdrArraySet(C.Structure):             # include/css_mi355_array.h (the members of CssMvdrSet / CssMvdrDesc)
+    _fields_ = list(CssMvdrSet._fields_)
+
+
+class CssMvdrArrayDesc(C.Structure):
+    _fields_ = list(CssMvdrDesc._fields_[:-1]) + [("sets", CssMvdrArraySet * 16)]
+
+
 class CssStitchSet(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("num_segments", "mask_off", "sep_off", "costs_off")]
 
@@ -404,6 +412,12 @@ SIGNATURES_BACKEND = {
     "css_mvdr_host": (C.c_int, [_P, C.POINTER(CssMvdrDesc), _P, _P, _P, _P, _P, _P]),
     "css_stitch_host": (C.c_int, [_P, C.POINTER(CssStitchDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
+# the entry point include/css_mi355_array.h declares (the MVDR kernels of 2 .. 8 microphones on caller data), the twelfth table
+# load() applies (named ARRAY_...: tests/test_backend_reference.py counts the module's SIGNATURES... tables)
+ARRAY_SIGNATURES = {
+    "css_mvdr_array_host": (C.c_int, [_P, C.POINTER(CssMvdrArrayDesc), _P, _P, _P, _P, _P, _P]),
+}
+ARRAY_MIN_MICS, ARRAY_MAX_MICS = 2, 8            # CSS_ARRAY_MIN_MICS, CSS_ARRAY_MAX_MICS
 SESSION_SCAN_CHUNK = 1024                        # CSS_SESSION_SCAN_CHUNK: the keep-scan kernel's step, in gate frames / sample blocks
 RESAMPLE_TILE = 256                              # output samples per block of the two resampling kernels (resample.hip RS_TILE)
 
@@ -450,7 +464,8 @@ def load() -> C.CDLL:
                               list(SIGNATURES_PREVIEW_HANDOFF.items()) + list(SIGNATURES_ENCODER.items()) +
                               list(SIGNATURES_WINDOW.items()) + list(SIGNATURES_PRESENT.items()) +
                               list(SIGNATURES_FRONTEND.items()) + list(SIGNATURES_SESSION_HANDOFF.items()) +
-                              list(SIGNATURES_STREAM_OUT.items()) + list(SIGNATURES_BACKEND.items())):
+                              list(SIGNATURES_STREAM_OUT.items()) + list(SIGNATURES_BACKEND.items()) +
+                              list(ARRAY_SIGNATURES.items())):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -1050,21 +1065,31 @@ class Handle:
     # ---- the kernels of csrc/mvdr.hip and csrc/stitch.hip on caller data (include/css_mi355_backend.h;
     #      tests/test_hip_backend_kernels.py).  Arrays are the WHOLE allocations (None where a form takes none); the arrays a form
     #      writes are copied first and returned as the launch left them.
-    def mvdr_host(self, form: int, *, X=None, masks=None, override=None, scm=None, bfw=None, sep=None, sets=(), **fields):
+    def mvdr_host(self, form: int, **kw):
         """launch_scm (0), launch_mvdr_solve (1), launch_mvdr_solve_multi (2; sets = (seg_lo, nseg, scm_off, bfw_off) each),
         launch_beamform (3), launch_segment_power_norm (4) (css_mvdr_host); fields are the descriptor's.  Returns the array the
         form writes: scm, bfw, sep, sep."""
+        return self._mvdr_host(self.lib.css_mvdr_host, CssMvdrDesc, CssMvdrSet, form, **kw)
+
+    def mvdr_array_host(self, form: int, **kw):
+        """css_mvdr_array_host (include/css_mi355_array.h): forms 0 .. 3 of mvdr_host for C = 2 .. 8 microphones; scm is
+        [segments][S + 1][F][C C], bfw [segments][S][F][C][2]."""
+        if not 0 <= int(form) <= 3:
+            raise ValueError("css_mvdr_array_host has the forms 0 .. 3")
+        return self._mvdr_host(self.lib.css_mvdr_array_host, CssMvdrArrayDesc, CssMvdrArraySet, form, **kw)
+
+    def _mvdr_host(self, entry, Desc, Set, form: int, *, X=None, masks=None, override=None, scm=None, bfw=None, sep=None, sets=(), **fields):
         arr = lambda a, t, own: None if a is None else (np.array(a, dtype=t).reshape(-1) if own else np.ascontiguousarray(a, dtype=t).reshape(-1))
         X, masks, override = arr(X, np.float32, False), arr(masks, np.float32, False), arr(override, np.uint8, False)
         scm, bfw, sep = arr(scm, np.float64, form == 0), arr(bfw, np.float64, form in (1, 2)), arr(sep, np.float32, form >= 3)
         n = lambda a: 0 if a is None else a.size
-        d = CssMvdrDesc(form=int(form), n_sets=len(sets), x_floats=n(X), mask_floats=n(masks), override_bytes=n(override),
-                        scm_doubles=n(scm), bfw_doubles=n(bfw), sep_floats=n(sep),
-                        **{k: (float(v) if k == "mask_floor" else int(v)) for k, v in fields.items()})
+        d = Desc(form=int(form), n_sets=len(sets), x_floats=n(X), mask_floats=n(masks), override_bytes=n(override),
+                 scm_doubles=n(scm), bfw_doubles=n(bfw), sep_floats=n(sep),
+                 **{k: (float(v) if k == "mask_floor" else int(v)) for k, v in fields.items()})
         for i, e in enumerate(sets):
-            d.sets[i] = CssMvdrSet(*(int(v) for v in e))
+            d.sets[i] = Set(*(int(v) for v in e))
         p = lambda a: None if a is None else _np_ptr(a)
-        check(self.h, self.lib.css_mvdr_host(self.h, C.byref(d), p(X), p(masks), p(override), p(scm), p(bfw), p(sep)))
+        check(self.h, entry(self.h, C.byref(d), p(X), p(masks), p(override), p(scm), p(bfw), p(sep)))
         return (scm, bfw, bfw, sep, sep)[int(form)]
 
     def stitch_host(self, form: int, *, masks=None, sep=None, windows=None, costs=None, perms=None, mask_st=None, activity=None,

@@ -5,6 +5,7 @@
 
 #include "api_ctx.hpp"
 #include "../../include/css_mi355_backend.h"
+#include "../../include/css_mi355_array.h"
 
 using namespace css;
 
@@ -31,23 +32,26 @@ inline bool is_permutation(const int32_t* p, int S) {
     return true;
 }
 
-}  // namespace
-
-extern "C" {
-
-int css_mvdr_host(css_handle_t h, const CssMvdrDesc* d, const float* X, const float* masks, const uint8_t* wta_override,
-                  double* scm, double* bfw, float* sep) {
+// css_mvdr_host (ARRAY = false: the 7-microphone kernels and the power normalisation, forms 0 .. 4) and css_mvdr_array_host
+// (ARRAY = true: every microphone count of mvdr.hip, forms 0 .. 3): one body, the descriptors have the same members
+static_assert(CSS_ARRAY_MAX_SETS == CSS_BACKEND_MAX_SETS && sizeof(CssMvdrArrayDesc) == sizeof(CssMvdrDesc), "one body, one layout");
+template <bool ARRAY, class Desc>
+int mvdr_host_impl(css_handle_t h, const Desc* d, const float* X, const float* masks, const uint8_t* wta_override,
+                   double* scm, double* bfw, float* sep) {
     CSS_DRAIN(h);
     if (!h) return CSS_ERR_INVALID_ARG;
-    auto bad = [&](const char* what) { return fail(h, CSS_ERR_INVALID_ARG, std::string("css_mvdr_host: ") + what); };
+    const char* const name = ARRAY ? "css_mvdr_array_host: " : "css_mvdr_host: ";
+    auto bad = [&](const char* what) { return fail(h, CSS_ERR_INVALID_ARG, std::string(name) + what); };
     if (!d) return bad("null argument");
     const int form = d->form, C = d->C, F = d->F, S = d->S, T = d->T, hop = d->hop;
-    if (form < 0 || form > 4) return bad("form must be 0 .. 4");
+    if (ARRAY ? (form < 0 || form > 3) : (form < 0 || form > 4)) return bad(ARRAY ? "form must be 0 .. 3" : "form must be 0 .. 4");
     const bool need_x = form == 0 || form == 3 || form == 4, need_m = form == 0 || form == 3;
     const bool need_scm = form <= 2, need_bfw = form == 1 || form == 2 || (form == 3 && d->use_mvdr), need_sep = form >= 3;
     if ((need_x && !X) || (need_m && !masks) || (need_scm && !scm) || (need_bfw && !bfw) || (need_sep && !sep)) return bad("null argument");
     if (d->use_mvdr < 0 || d->use_mvdr > 1) return bad("use_mvdr is 0 or 1");
-    if ((form <= 2 || d->use_mvdr) ? C != 7 : (C < 1 || C > 64)) return bad("C must be 7 for the covariances, the solve and the MVDR beamformer (1 .. 64 otherwise)");
+    if (ARRAY) {
+        if (C < 2 || C > 8) return bad("C must be 2 .. 8");
+    } else if ((form <= 2 || d->use_mvdr) ? C != 7 : (C < 1 || C > 64)) return bad("C must be 7 for the covariances, the solve and the MVDR beamformer (1 .. 64 otherwise)");
     if (S < 1 || S > 3) return bad("S must be 1 .. 3 (S + 1 mask rows in four lane groups)");
     if (F < 1 || F > 4096 || T < 1 || T > 65535 || hop < 1 || hop > (1 << 20)) return bad("F 1 .. 4096, T 1 .. 65535, hop >= 1");
     const int nm = S + 1;
@@ -76,14 +80,14 @@ int css_mvdr_host(css_handle_t h, const CssMvdrDesc* d, const float* X, const fl
             if (!(v < nm || (v >= 16 && v < 32 && (v & ((1 << nm) - 1))))) return bad("an override byte is neither a winner index below S + 1 nor 16 | bits with a bit below S + 1");
         }
     }
-    const int64_t scm_per = (int64_t)nm * F * 49, bfw_per = (int64_t)S * F * 14, sep_per = (int64_t)S * F * T * 2;
+    const int64_t scm_per = (int64_t)nm * F * C * C, bfw_per = (int64_t)S * F * 2 * C, sep_per = (int64_t)S * F * T * 2;
     if (need_scm && (d->scm_doubles < 1 || d->scm_doubles > HOST_CAP)) return bad("scm_doubles: 1 .. 2^28");
     if (need_bfw && (d->bfw_doubles < 1 || d->bfw_doubles > HOST_CAP)) return bad("bfw_doubles: 1 .. 2^28");
     if (need_sep && (d->sep_floats < 1 || d->sep_floats > HOST_CAP)) return bad("sep_floats: 1 .. 2^28");
     if (form == 2) {
         if (d->n_sets < 1 || d->n_sets > CSS_BACKEND_MAX_SETS) return bad("n_sets must be 1 .. 16");
         for (int i = 0; i < d->n_sets; ++i) {
-            const CssMvdrSet& s = d->sets[i];
+            const auto& s = d->sets[i];
             if (s.nseg < 1 || s.nseg > 4096 || s.seg_lo < 0 || s.seg_lo > (1 << 20) || s.scm_off < 0 || s.bfw_off < 0) return bad("a set: nseg 1 .. 4096, seg_lo >= 0, offsets >= 0");
             if (s.scm_off > HOST_CAP || s.scm_off + (s.seg_lo + s.nseg) * scm_per > d->scm_doubles) return bad("a set's covariances lie outside scm");
             if (s.bfw_off > HOST_CAP || s.bfw_off + (s.seg_lo + s.nseg) * bfw_per > d->bfw_doubles) return bad("a set's weights lie outside bfw");
@@ -123,7 +127,7 @@ int css_mvdr_host(css_handle_t h, const CssMvdrDesc* d, const float* X, const fl
     a.mask_floor = d->mask_floor; a.use_mvdr = d->use_mvdr;
     switch (form) {
     case 0:
-        if (!launch_scm(a, st)) return fail(h, CSS_ERR_HIP, "css_mvdr_host: the covariance kernel's LDS could not be reserved");
+        if (!launch_scm(a, st)) return fail(h, CSS_ERR_HIP, std::string(name) + "the covariance kernel's LDS could not be reserved");
         break;
     case 1: launch_mvdr_solve(a, st); break;
     case 2: {
@@ -144,6 +148,20 @@ int css_mvdr_host(css_handle_t h, const CssMvdrDesc* d, const float* X, const fl
     HIPCHK(h, hipStreamSynchronize(st));
     HIPCHK(h, hipGetLastError());
     return CSS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int css_mvdr_host(css_handle_t h, const CssMvdrDesc* d, const float* X, const float* masks, const uint8_t* wta_override,
+                  double* scm, double* bfw, float* sep) {
+    return mvdr_host_impl<false>(h, d, X, masks, wta_override, scm, bfw, sep);
+}
+
+int css_mvdr_array_host(css_handle_t h, const CssMvdrArrayDesc* d, const float* X, const float* masks, const uint8_t* wta_override,
+                        double* scm, double* bfw, float* sep) {
+    return mvdr_host_impl<true>(h, d, X, masks, wta_override, scm, bfw, sep);
 }
 
 int css_stitch_host(css_handle_t h, const CssStitchDesc* d, const float* masks, const float* sep, const float* windows,

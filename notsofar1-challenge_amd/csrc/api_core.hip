@@ -67,7 +67,8 @@ int64_t bind_weights(const CssModelDesc& d, const float* base, Weights* w) {
 }
 
 const char* validate_desc(const CssModelDesc& d) {
-    if (d.num_mics != 1 && d.num_mics != 7) return "num_mics must be 1 or 7";
+    // 1: the single-channel models; 2 .. 8: the MVDR kernels' instantiations (mvdr.hip; 7 is the NOTSOFAR array)
+    if (d.num_mics < 1 || d.num_mics > 8) return "num_mics must be 1 .. 8";
     // init_kernel (feature.py:19-45): N FFT points (frame_len rounded up to a power of two, or frame_len itself), N/2 + 1 bins, a
     // window of frame_len samples, any hop.  frame_len 512 / hop 256 takes the FFT kernel and every pipelined schedule; other
     // sizes take the DFT-matrix product and the plain stage sequence
@@ -987,8 +988,8 @@ static int buffer_info(css_ctx* h, int which, DevBuf** buf, int64_t dims[4], int
                 return fail(h, CSS_ERR_STATE, "the masks of a session that shared a queued estimator batch are columns of the group's "
                                               "buffer: not addressable as CSS_BUF_MASKS (css_write_buffer re-homes them)");
             *buf = &h->masks; dims[0] = (int64_t)(S + 1) * F; dims[1] = nseg * T; break;
-        case CSS_BUF_SCM: *buf = &h->scm; dims[0] = nseg; dims[1] = S + 1; dims[2] = F; dims[3] = 49; *elem = 8; break;
-        case CSS_BUF_BFW: *buf = &h->bfw; dims[0] = nseg; dims[1] = S; dims[2] = F; dims[3] = 14; *elem = 8; break;
+        case CSS_BUF_SCM: *buf = &h->scm; dims[0] = nseg; dims[1] = S + 1; dims[2] = F; dims[3] = (int64_t)h->n_ch * h->n_ch; *elem = 8; break;   // packed Hermitian C x C (49 at 7 microphones)
+        case CSS_BUF_BFW: *buf = &h->bfw; dims[0] = nseg; dims[1] = S; dims[2] = F; dims[3] = 2 * (int64_t)h->n_ch; *elem = 8; break;
         case CSS_BUF_SEP: *buf = &h->sep; dims[0] = nseg; dims[1] = S; dims[2] = F; dims[3] = (int64_t)T * 2; break;
         case CSS_BUF_PIT_COST: *buf = &h->costs; dims[0] = std::max<int64_t>(nseg - 1, 0); dims[1] = S * S; *elem = 8; break;
         case CSS_BUF_PERMS: *buf = &h->perms; dims[0] = nseg; dims[1] = S; break;

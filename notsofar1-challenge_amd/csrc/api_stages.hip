@@ -65,8 +65,8 @@ int begin_impl(css_handle_t h, int64_t n_samples, int32_t n_ch, const CssRunCfg*
     h->ph_valid = false;
     if ((rc = ensure_activations(h, std::min<int64_t>(h->max_batch, nseg), T)) != CSS_OK) return rc;
     ENS(masks, (size_t)(S + 1) * F * nseg * T * sizeof(float))
-    ENS(scm, (size_t)nseg * (S + 1) * F * 49 * sizeof(double))
-    ENS(bfw, (size_t)nseg * S * F * 7 * 2 * sizeof(double))
+    ENS(scm, (size_t)nseg * (S + 1) * F * n_ch * n_ch * sizeof(double))   // packed Hermitian C x C per (segment, mask, bin)
+    ENS(bfw, (size_t)nseg * S * F * n_ch * 2 * sizeof(double))
     ENS(sep, (size_t)nseg * S * F * T * 2 * sizeof(float))
     ENS(costs, (size_t)std::max<int64_t>(nseg - 1, 1) * S * S * sizeof(double))
     ENS(pit_part, pit_cost_scratch_bytes(nseg - 1))

@@ -471,8 +471,8 @@ int css_stream_open(css_handle_t h, const CssRunCfg* cfg, int32_t n_ch, int32_t*
         if ((rc = alloc(s->act_b[b], (size_t)S * s->WF)) != CSS_OK) break;
         if ((rc = alloc(s->G[b], (size_t)S * s->WF * N * sizeof(float))) != CSS_OK) break;
     }
-    if (rc == CSS_OK) rc = alloc(s->scm, (size_t)s->SC * (S + 1) * F * 49 * sizeof(double));
-    if (rc == CSS_OK) rc = alloc(s->bfw, (size_t)s->SC * S * F * 7 * 2 * sizeof(double));
+    if (rc == CSS_OK) rc = alloc(s->scm, (size_t)s->SC * (S + 1) * F * s->n_ch * s->n_ch * sizeof(double));
+    if (rc == CSS_OK) rc = alloc(s->bfw, (size_t)s->SC * S * F * s->n_ch * 2 * sizeof(double));
     if (rc == CSS_OK) rc = alloc(s->pnorm, (size_t)s->SC * sizeof(double));
     if (rc == CSS_OK) rc = alloc(s->costs, (size_t)(s->SC + 1) * S * S * sizeof(double));
     if (rc == CSS_OK) rc = alloc(s->pit_part, pit_cost_scratch_bytes(s->SC));

@@ -318,14 +318,15 @@ struct MvdrArgs {
     int S; int T; int hop;
     int64_t seg_lo; int nseg;
     const uint8_t* wta_override;           // nullptr or [segments][F][T]
-    double* scm;                           // [segments][S+1][F][49]
+    double* scm;                           // [segments][S+1][F][C C]: packed Hermitian, C real diagonal entries, then (Re, Im) of (c, d), c < d, row by row
     double* bfw;                           // [segments][S][F][C][2]
     float* sep;                            // [segments][S][F][T][2]
     float mask_floor;
     int use_mvdr;
 };
 // PRECONDITIONS of the launches below (the paths guarantee them; css_mvdr_host, include/css_mi355_backend.h, refuses the rest):
-//   C == 7 for launch_scm, both solves and the MVDR beamformer (the packed 7 x 7 layout); use_mvdr == 0 reads microphone 0 alone
+//   2 <= C <= 8 for launch_scm, both solves and the MVDR beamformer (one instantiation per C of the packed C x C layout; the sets
+//   of a multi-session solve share one C); use_mvdr == 0 reads microphone 0 alone
 //   1 <= S <= 3: scm_kernel sorts the frames of the S + 1 mask rows into FOUR lists, one per group of 16 lanes
 //   mask_ld >= (seg_lo + nseg) T; T_ld covers the last valid frame min(stft_frames, (seg_lo + nseg - 1) hop + T): frames from
 //   stft_frames on are never read

@@ -1,7 +1,7 @@
 // Mask-based MVDR beamformer of one segment (css/css_with_conformer/utils/mvdr_util.py):
 //   make_wta (:50) -> get_mask_scm (:58) -> calc_bfcoeffs (:69) -> get_bf (:78), then the floored mask
 //   multiplication of css/css.py:222-227.
-// The 7x7 spatial covariance matrices are accumulated and solved in float64 (the reference does
+// The C x C spatial covariance matrices (C = 2 .. 8 microphones; the reference: 7) are accumulated and solved in float64 (the reference does
 // this in complex64, which leaves it ~2e-5 from the exact answer; float64 keeps our
 // own distance from the exact answer negligible, so the distance to the reference is the reference's).
 #include <algorithm>
@@ -13,8 +13,13 @@
 
 namespace css {
 
-constexpr int NC = 7;        // microphones of the NOTSOFAR array (utils/mic_array_model.py:4)
-constexpr int NPACK = 49;    // Hermitian 7x7: 7 real diagonal + 21 complex upper-triangle entries
+// Every kernel below is a template over NC, the number of microphones (2 .. 8; 7 is the NOTSOFAR array,
+// utils/mic_array_model.py:4, and its instantiations are the kernels this file held before the template).
+// Packed Hermitian NC x NC: NC real diagonal entries, then (Re, Im) of (c, d), c < d, row by row: NC * NC doubles.
+// the walk of scm_kernel keeps 2 * ceil(NC * NC / passes) doubles per lane: 98 at NC = 7; at NC = 8 one pass would be 128
+// doubles (every VGPR of the lane before the frame's 16 values, the addresses and the exchange), so the list is walked twice,
+// 32 entries at a time
+template <int NC> constexpr int scm_passes() { return NC * NC > 49 ? 2 : 1; }
 
 __device__ __forceinline__ int valid_frames(int64_t stft_frames, int64_t seg, int hop, int T) {
     const int64_t tv = stft_frames - seg * (int64_t)hop;
@@ -27,22 +32,26 @@ __device__ __forceinline__ int valid_frames(int64_t stft_frames, int64_t seg, in
 //              else 1e-10                                            (mvdr_util.py:50-55)
 //   Phi_k[f] = sum_t w_k[f,t] x[f,t] x[f,t]^H  (+ 1e-15 I)            (mvdr_util.py:61-65)
 //
-// One wave per (segment, bin).  The 14 Re / Im plane rows and the mask rows of the bin are read ONCE, as whole
+// One wave per (segment, bin).  The 2 NC Re / Im plane rows (14 at NC = 7) and the mask rows of the bin are read ONCE, as whole
 // contiguous rows, into a wave-private LDS tile (the four masks used to re-read the planes 64 bytes at a time).  A frame
 // has one winner, so
-//   Phi_k = sum_{t: k wins} (m_k - 1e-10) P_t  +  1e-10 sum_t P_t,        P_t = x_t x_t^H  (7 real + 21 complex entries)
+//   Phi_k = sum_{t: k wins} (m_k - 1e-10) P_t  +  1e-10 sum_t P_t,        P_t = x_t x_t^H  (NC real + NC (NC - 1) / 2 complex entries: 7 + 21)
 // and the outer product of a frame is formed once, for its winner, instead of once per mask: the frames are sorted by
 // winner into four lists (wave ballots), the 16 lanes of group k walk list k -- every lane busy on every step, a third
 // of the float64 work of the mask-major loop -- and keep two accumulator sets, the weighted sum and the plain sum; the
 // plain sums of the four groups add up to sum_t P_t (a frame with tied winners is in each of their lists, but counts
 // towards the plain sum only in the first one).  The 16 lanes' partial sums are combined by a four-step DPP
-// reduce-scatter and leave through LDS as 49 consecutive doubles per mask.
+// reduce-scatter and leave through LDS as NC * NC consecutive doubles per mask (49 at NC = 7).
 // ------------------------------------------------------------------------------------------------
 constexpr int SCM_WAVES = 2;   // bins per block
 
-template <int NI, int TS_ = NI * 64>   // 64-frame pieces of a segment: 4 (T <= 256) or 8 (T <= 512); TS_: the tile's row length
+template <int NC, int NI, int TS_ = NI * 64>   // 64-frame pieces of a segment: 4 (T <= 256) or 8 (T <= 512); TS_: the tile's row length
 __global__ __launch_bounds__(64 * SCM_WAVES) void scm_kernel(MvdrArgs a) {
     extern __shared__ __attribute__((aligned(16))) float scm_lds[];
+    constexpr int NPACK = NC * NC, NPASS = scm_passes<NC>(), E = (NPACK + NPASS - 1) / NPASS;   // E: packed entries per pass
+    constexpr int H1 = (E + 1) / 2, H2 = (H1 + 1) / 2, H3 = (H2 + 1) / 2;                       // values a lane keeps after each exchange
+    constexpr int NR = 2 * NC;                                                                  // plane rows of the tile
+    static_assert(NPASS == 1 || (NC % 2 == 0 && E % 2 == 0 && NPASS * E == NPACK), "a (Re, Im) pair lies in one pass");
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;   // (wave-uniform for the compiler: the rows' buffer descriptors live in scalar registers)
     const int k = lane >> 4, l16 = lane & 15;
     const int f = blockIdx.x * SCM_WAVES + wave, segl = blockIdx.y;
@@ -52,14 +61,14 @@ __global__ __launch_bounds__(64 * SCM_WAVES) void scm_kernel(MvdrArgs a) {
     if (f >= F) return;   // (whole waves; no block-wide barrier below)
     const int tv = valid_frames(a.stft_frames, seg, a.hop, T);
     const int64_t st = seg * (int64_t)a.hop;
-    // wave-private tile: x[14][TS] (rows c: Re, 7 + c: Im), m[4][TS], TS = NI * 64 (whole 64-frame pieces, so that a piece is
+    // wave-private tile: x[2 NC][TS] (rows c: Re, NC + c: Im; 14 rows at NC = 7), m[4][TS], TS = NI * 64 (whole 64-frame pieces, so that a piece is
     // stored without a lane mask), then the four frame lists (uint16) and 4 x 98 doubles
     // (TS_ = 192 for the shipped 3 s segments, with the group totals laid over the tile -- dead by then: 15.4 KB per wave, ten
     // waves per CU instead of eight.  The launch is 10 280 waves: 5.02 rounds of 2 048 slots are six rounds, 4.02 of 2 560 five.)
     constexpr int TS = TS_;
-    constexpr bool TOT_OVER_TILE = TS_ < NI * 64;
-    float* xs = scm_lds + (size_t)wave * ((14 + 4) * TS + 2 * TS + (TOT_OVER_TILE ? 0 : 4 * 2 * NPACK * 2));
-    float* ms = xs + 14 * TS;
+    constexpr bool TOT_OVER_TILE = TS_ < NI * 64 && NPASS == 1;   // (a second pass still reads the tile)
+    float* xs = scm_lds + (size_t)wave * ((NR + 4) * TS + 2 * TS + (TOT_OVER_TILE ? 0 : 4 * 2 * NPACK * 2));
+    float* ms = xs + NR * TS;
     unsigned short* lists = reinterpret_cast<unsigned short*>(ms + 4 * TS);    // [4][TS]
     double* tot = reinterpret_cast<double*>(TOT_OVER_TILE ? xs : ms + 4 * TS + 2 * TS);   // [4][2 * NPACK] group totals (8-byte aligned)
     // ---- the bin's rows, contiguous along time: every load of the 18 rows is in flight before the first LDS store
@@ -83,7 +92,7 @@ __global__ __launch_bounds__(64 * SCM_WAVES) void scm_kernel(MvdrArgs a) {
         for (int r = 0; r < 2 * NC + 4; ++r)
 #pragma unroll
             for (int i = 0; i < NI; ++i)
-                if (64 * i < tv) xs[r * TS + lane + 64 * i] = v[r][i];   // rows 14 .. 17 are the mask rows (ms = xs + 14 TS)
+                if (64 * i < tv) xs[r * TS + lane + 64 * i] = v[r][i];   // rows 2 NC .. 2 NC + 3 are the mask rows (ms = xs + 2 NC TS)
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -116,99 +125,21 @@ __global__ __launch_bounds__(64 * SCM_WAVES) void scm_kernel(MvdrArgs a) {
     __builtin_amdgcn_wave_barrier();
     // ---- group k walks its list.  Two accumulator sets per lane: the weighted sum and the plain sum -- held CROSSWISE in
     // the two halves of the group (lanes 0..7: acc = weighted, pl = plain; lanes 8..15: acc = plain, pl = weighted), so that
-    // the first step of the reduce-scatter below needs no selects: every lane keeps `acc` and receives its partner's `pl`
-    double acc[NPACK], pl[NPACK];
-#pragma unroll
-    for (int i = 0; i < NPACK; ++i) { acc[i] = 0.0; pl[i] = 0.0; }
-    const int nk = k == 0 ? cnt[0] : (k == 1 ? cnt[1] : (k == 2 ? cnt[2] : cnt[3]));
-    const bool upper = l16 >= 8;
-    for (int i = l16; i < nk; i += 16) {
-        const unsigned e = lists[k * TS + i];
-        const int t = e & 0x7fff;
-        const double first_ = (e & 0x8000) ? 1.0 : 0.0;
-        const double w_ = (double)ms[k * TS + t] - 1e-10;
-        const double w = upper ? first_ : w_, first = upper ? w_ : first_;   // (names as in the lower half)
-        double xr[NC], xi[NC];
-#pragma unroll
-        for (int c = 0; c < NC; ++c) { xr[c] = (double)xs[c * TS + t]; xi[c] = (double)xs[(NC + c) * TS + t]; }
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const double p = xr[c] * xr[c] + xi[c] * xi[c];
-            acc[c] += w * p;
-            pl[c] += first * p;
-        }
-        int p = NC;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-#pragma unroll
-            for (int d = c + 1; d < NC; ++d) {
-                const double pr = xr[c] * xr[d] + xi[c] * xi[d];      // Re x_c conj(x_d)
-                const double pi = xi[c] * xr[d] - xr[c] * xi[d];      // Im
-                acc[p] += w * pr; pl[p] += first * pr;
-                acc[p + 1] += w * pi; pl[p + 1] += first * pi;
-                p += 2;
-            }
-        }
-    }
-    // ---- reduce-scatter over the group's 16 lanes: four DPP exchanges, each halving the number of values a lane keeps
-    // (summing all 98 values into all 16 lanes cost 4 x 98 exchanges and 16 copies of every total; this costs
-    // 49 + 25 + 13 + 7 and leaves each total in one lane).  A lane keeps the lower or upper half of its values by one bit
-    // of its position; its partner keeps the other half and sends the half this lane keeps.
-    // value list: acc[0..48] then pl[0..48]; after the steps lane l holds the totals of original indices
-    //   j + 49 b0 + 25 b1 + 13 b2 + 7 b3,  j = 0..6,  b0 = l16 >= 8, b1 = (l16 & 7) >= 4, b2 = bit 1, b3 = bit 0
-    double v1[49], v2[25], v3[13], v4[7];
-    {
-        // partner: 15 - l16 (row_mirror), in the other half: its `pl` is what this lane's `acc` is (see above)
-#pragma unroll
-        for (int j = 0; j < 49; ++j) v1[j] = acc[j] + dpp_get<0x140>(pl[j]);
-    }
-    {
-        const bool up = (l16 & 7) >= 4;      // partner: 7 - (l16 & 7) inside the half row (row_half_mirror)
-#pragma unroll
-        for (int j = 0; j < 25; ++j) {
-            const double lo = v1[j], hi = j + 25 < 49 ? v1[j + 25] : 0.0;
-            const double keep = up ? hi : lo, send = up ? lo : hi;
-            v2[j] = keep + dpp_get<0x141>(send);
-        }
-    }
-    {
-        const bool up = (l16 & 2) != 0;      // partner: l16 ^ 2 (quad_perm [2,3,0,1])
-#pragma unroll
-        for (int j = 0; j < 13; ++j) {
-            const double lo = v2[j], hi = j + 13 < 25 ? v2[j + 13] : 0.0;
-            const double keep = up ? hi : lo, send = up ? lo : hi;
-            v3[j] = keep + dpp_get<0x4E>(send);
-        }
-    }
-    {
-        const bool up = (l16 & 1) != 0;      // partner: l16 ^ 1 (quad_perm [1,0,3,2])
-#pragma unroll
-        for (int j = 0; j < 7; ++j) {
-            const double lo = v3[j], hi = j + 7 < 13 ? v3[j + 7] : 0.0;
-            const double keep = up ? hi : lo, send = up ? lo : hi;
-            v4[j] = keep + dpp_get<0xB1>(send);
-        }
-    }
-    // the totals meet in LDS: tot[k][0..48] weighted sums, tot[k][49..97] plain sums
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    {
-        const int base = (l16 >= 8 ? 49 : 0);
-        const int o1 = ((l16 & 7) >= 4 ? 25 : 0), o2 = ((l16 & 2) ? 13 : 0), o3 = ((l16 & 1) ? 7 : 0);
-#pragma unroll
-        for (int j = 0; j < 7; ++j) {
-            // position inside the 49-value half after steps 2..4; slots past a half's end were padding (zero sums)
-            const int q3 = j + o3, q2 = q3 + o2, q1 = q2 + o1;
-            const bool real = q3 < 13 && q2 < 25 && q1 < 49;
-            if (real) tot[k * 98 + base + q1] = v4[j];
-        }
+    // the first step of the reduce-scatter below needs no selects: every lane keeps `acc` and receives its partner's `pl`.
+    // A pass holds the packed entries [LO, LO + E): all of them at NC <= 7; at NC = 8 the list is walked twice, 32 entries each
+    // (the frame's 16 values and its weight are read from LDS again, the float64 work is done once)
+    constexpr int LO = 0;
+#include "scm_walk.inc"
+    if constexpr (NPASS > 1) {
+        constexpr int LO = E;
+#include "scm_walk.inc"
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    // ---- Phi_k = weighted + 1e-10 * (sum of the four plain sums) (+ 1e-15 on the diagonal), 49 consecutive doubles per mask
+    // ---- Phi_k = weighted + 1e-10 * (sum of the four plain sums) (+ 1e-15 on the diagonal), NPACK consecutive doubles per mask
     for (int e = lane; e < nm * NPACK; e += 64) {
         const int kk = e / NPACK, i = e - kk * NPACK;
-        double v = tot[kk * 98 + i] + 1e-10 * ((tot[49 + i] + tot[98 + 49 + i]) + (tot[2 * 98 + 49 + i] + tot[3 * 98 + 49 + i]));
+        double v = tot[kk * (2 * NPACK) + i] + 1e-10 * ((tot[NPACK + i] + tot[2 * NPACK + NPACK + i]) + (tot[2 * (2 * NPACK) + NPACK + i] + tot[3 * (2 * NPACK) + NPACK + i]));
         if (i < NC) v += 1e-15;  // Ri += 1e-15 * I   (mvdr_util.py:63-65)
         a.scm[((seg * nm + kk) * (int64_t)F + f) * NPACK + i] = v;
     }
@@ -222,7 +153,10 @@ __global__ __launch_bounds__(64 * SCM_WAVES) void scm_kernel(MvdrArgs a) {
 // ------------------------------------------------------------------------------------------------
 constexpr int SCM_LONG_CH = 128;
 
+template <int NC>
 __global__ __launch_bounds__(256) void scm_long_kernel(MvdrArgs a) {
+    constexpr int NPACK = NC * NC;
+    static_assert(4 * NPACK <= 256, "thread (k, e): four masks of NC * NC entries in one block");
     __shared__ float xs[2 * NC][SCM_LONG_CH];
     __shared__ double ws[4][SCM_LONG_CH];      // (m_k - 1e-10) where mask k wins the frame, else 0
     const int f = blockIdx.x, segl = blockIdx.y;
@@ -242,7 +176,7 @@ __global__ __launch_bounds__(256) void scm_long_kernel(MvdrArgs a) {
         for (int s_ = 0; s_ < NC - 2; ++s_) if (p >= NC - 1 - c) { p -= NC - 1 - c; ++c; }
         d = c + 1 + p;
     }
-    const bool owner = k < nm;   // 4 x 49 = 196 of the 256 threads own an entry
+    const bool owner = k < nm;   // 4 x 49 = 196 of the 256 threads own an entry at NC = 7, all 256 at NC = 8
     double acc = 0.0, plain = 0.0;
     for (int t0 = 0; t0 < tv; t0 += SCM_LONG_CH) {
         const int n = min(SCM_LONG_CH, tv - t0);
@@ -284,28 +218,52 @@ __global__ __launch_bounds__(256) void scm_long_kernel(MvdrArgs a) {
     }
 }
 
-bool launch_scm(const MvdrArgs& a, hipStream_t s) {
+// the launches switch on MvdrArgs::C: one instantiation per microphone count (C outside 2 .. 8 is the caller's error: no launch)
+#define CSS_MVDR_DISPATCH(C_, CALL) \
+    switch (C_) {                   \
+    case 2: { CALL(2); } break;     \
+    case 3: { CALL(3); } break;     \
+    case 4: { CALL(4); } break;     \
+    case 5: { CALL(5); } break;     \
+    case 6: { CALL(6); } break;     \
+    case 7: { CALL(7); } break;     \
+    case 8: { CALL(8); } break;     \
+    default: break;                 \
+    }
+
+template <int NC>
+static bool launch_scm_c(const MvdrArgs& a, hipStream_t s) {
+    constexpr int NPACK = NC * NC;
     if (a.T > 512 || css_force_long_path()) {
-        hipLaunchKernelGGL(scm_long_kernel, dim3(a.F, a.nseg), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(scm_long_kernel<NC>, dim3(a.F, a.nseg), dim3(256), 0, s, a);
         return true;
     }
-    // per wave: 18 rows of TS floats, 4 lists of TS uint16 (= 2 TS floats), 4 x 98 doubles; TS = 256 or 512
+    // per wave: 2 NC + 4 rows of TS floats (18 at NC = 7), 4 lists of TS uint16 (= 2 TS floats), 4 x 2 NPACK doubles; TS = 256 or 512
     const int TS = a.T <= 256 ? 256 : 512;
-    const size_t per_wave = ((size_t)(14 + 4) * TS + 2 * TS + 4 * 2 * NPACK * 2) * sizeof(float);
+    const size_t per_wave = ((size_t)(2 * NC + 4) * TS + 2 * TS + 4 * 2 * NPACK * 2) * sizeof(float);
     const dim3 grid((a.F + SCM_WAVES - 1) / SCM_WAVES, a.nseg), block(64 * SCM_WAVES);
-    if (a.T <= 192) {   // (A/B on one box: 90.2 -> 74.5 us per 40 segments)
-        hipLaunchKernelGGL((scm_kernel<4, 192>), grid, block, (size_t)(20 * 192) * sizeof(float) * SCM_WAVES, s, a);
+    if (a.T <= 192) {   // (A/B on one box at NC = 7: 90.2 -> 74.5 us per 40 segments)
+        // the group totals lie over the tile where one pass walks it (20 rows of 192 floats at NC = 7), behind it with two passes
+        const size_t tile = (size_t)(2 * NC + 6) * 192 * sizeof(float) + (scm_passes<NC>() > 1 ? (size_t)4 * 2 * NPACK * sizeof(double) : 0);
+        hipLaunchKernelGGL((scm_kernel<NC, 4, 192>), grid, block, tile * SCM_WAVES, s, a);
     } else if (a.T <= 256) {
-        hipLaunchKernelGGL(scm_kernel<4>, grid, block, per_wave * SCM_WAVES, s, a);
-    } else {   // up to 8 s segments: 82 KB of LDS per block
+        hipLaunchKernelGGL((scm_kernel<NC, 4>), grid, block, per_wave * SCM_WAVES, s, a);
+    } else {   // up to 8 s segments: 82 KB of LDS per block at NC = 7, 98 KB at NC = 8
         // (the attribute is per device: set on every launch -- a host-side table lookup -- not behind a process-wide flag
         // that a second device, or a second thread's first launch, would miss; stft.hip does the same)
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(scm_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize,
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(scm_kernel<NC, 8>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)(per_wave * SCM_WAVES)) != hipSuccess)
             return false;
-        hipLaunchKernelGGL(scm_kernel<8>, grid, block, per_wave * SCM_WAVES, s, a);
+        hipLaunchKernelGGL((scm_kernel<NC, 8>), grid, block, per_wave * SCM_WAVES, s, a);
     }
     return true;
+}
+
+bool launch_scm(const MvdrArgs& a, hipStream_t s) {
+#define CSS_CALL(N) return launch_scm_c<N>(a, s)
+    CSS_MVDR_DISPATCH(a.C, CSS_CALL)
+#undef CSS_CALL
+    return false;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -313,7 +271,7 @@ bool launch_scm(const MvdrArgs& a, hipStream_t s) {
 //   Z = solve(Phi_n, Phi_i);  W = Z[:, 0] / (trace(Z) [+ 1e-15 at bin 0 only])
 // One thread per (segment, speaker, bin): complex LU with partial pivoting (the algorithm behind
 // numpy.linalg.solve / LAPACK gesv; pivot = max |re|+|im| like i?amax) held entirely in registers --
-// row exchanges are predicated swaps so every index is a compile-time constant -- then the seven
+// row exchanges are predicated swaps so every index is a compile-time constant -- then the NC
 // right-hand-side columns are pushed through one at a time (only column 0 and the trace are needed).
 // ------------------------------------------------------------------------------------------------
 struct cplx { double re, im; };
@@ -329,6 +287,7 @@ __device__ __forceinline__ void cswap_if(bool p, cplx& a, cplx& b) {
     b.re = p ? ta.re : tb.re; b.im = p ? ta.im : tb.im;
 }
 // element (r, c) of a packed Hermitian matrix
+template <int NC>
 __device__ __forceinline__ cplx herm_at(const double* __restrict__ m, int r, int c) {
     if (r == c) return {m[r], 0.0};
     const int lo = r < c ? r : c, hi = r < c ? c : r;
@@ -336,7 +295,9 @@ __device__ __forceinline__ cplx herm_at(const double* __restrict__ m, int r, int
     return {m[p], r < c ? m[p + 1] : -m[p + 1]};
 }
 
+template <int NC>
 __device__ __forceinline__ void mvdr_solve_body(const MvdrArgs& a, const int64_t gid) {
+    constexpr int NPACK = NC * NC;
     const int F = a.F, S = a.S, nm = S + 1;
     const int64_t total = (int64_t)a.nseg * S * F;
     if (gid >= total) return;
@@ -359,7 +320,7 @@ __device__ __forceinline__ void mvdr_solve_body(const MvdrArgs& a, const int64_t
         for (int r = 0; r < NC; ++r)
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
-                const cplx v = herm_at(m, r, c);
+                const cplx v = herm_at<NC>(m, r, c);
                 A[r][c].re += v.re;
                 A[r][c].im += v.im;
             }
@@ -399,7 +360,7 @@ __device__ __forceinline__ void mvdr_solve_body(const MvdrArgs& a, const int64_t
     for (int col = 0; col < NC; ++col) {
         cplx z[NC];
 #pragma unroll
-        for (int r = 0; r < NC; ++r) z[r] = herm_at(ms, r, col);
+        for (int r = 0; r < NC; ++r) z[r] = herm_at<NC>(ms, r, col);
 #pragma unroll
         for (int p = 0; p < NC; ++p)
 #pragma unroll
@@ -436,13 +397,17 @@ __device__ __forceinline__ void mvdr_solve_body(const MvdrArgs& a, const int64_t
 // a chain of ~20 us whatever the launch holds, and a 60 s meeting's 30 840 systems are 482 waves for 1 024 SIMDs -- three or six
 // sessions still fit one round.
 struct MvdrMulti : Table<MvdrArgs, MVDR_MULTI_MAX> {};
-__global__ __launch_bounds__(64) void mvdr_solve_multi_kernel(MvdrMulti m) { mvdr_solve_body(m.e[blockIdx.y], (int64_t)blockIdx.x * 64 + threadIdx.x); }
+template <int NC>
+__global__ __launch_bounds__(64) void mvdr_solve_multi_kernel(MvdrMulti m) { mvdr_solve_body<NC>(m.e[blockIdx.y], (int64_t)blockIdx.x * 64 + threadIdx.x); }
 
 void launch_mvdr_solve(const MvdrArgs& a, hipStream_t s) { launch_mvdr_solve_multi(&a, 1, s); }
 void launch_mvdr_solve_multi(const MvdrArgs* a, int n, hipStream_t s) {
     for_each_table<MvdrMulti>(a, n, [&](const MvdrMulti& m, int cnt) {
         const int64_t most = table_max(m, cnt, (int64_t)0, [](const MvdrArgs& e) { return (int64_t)e.nseg * e.S * e.F; });
-        if (most > 0) hipLaunchKernelGGL(mvdr_solve_multi_kernel, dim3((unsigned)((most + 63) / 64), cnt), dim3(64), 0, s, m);
+        // (the sets of a launch are sessions of one handle: one model, one microphone count)
+#define CSS_CALL(N) hipLaunchKernelGGL(mvdr_solve_multi_kernel<N>, dim3((unsigned)((most + 63) / 64), cnt), dim3(64), 0, s, m)
+        if (most > 0) CSS_MVDR_DISPATCH(m.e[0].C, CSS_CALL)
+#undef CSS_CALL
         return true;
     });
 }
@@ -453,6 +418,7 @@ void launch_mvdr_solve_multi(const MvdrArgs* a, int n, hipStream_t s) {
 // mc_mvdr = False) the masked signal is the reference microphone 0 (css.py:204,220).
 // Block = (bin, segment), threads run over time.
 // ------------------------------------------------------------------------------------------------
+template <int NC>
 __global__ __launch_bounds__(256) void beamform_kernel(MvdrArgs a) {
     const int f = blockIdx.x, segl = blockIdx.y;
     const int64_t seg = a.seg_lo + segl;
@@ -494,7 +460,11 @@ void launch_beamform(const MvdrArgs& a, hipStream_t s) {
     // as many waves as the segment has 64-frame pieces (3 s segments: 186 frames on 192 threads instead of 256; ten blocks
     // per CU instead of eight -- 40 x 257 blocks are 4.02 rounds of 2 560 slots instead of 5.02 of 2 048: 50.3 -> 47.3 us)
     const int threads = std::min(256, (a.T + 63) / 64 * 64);
-    hipLaunchKernelGGL(beamform_kernel, dim3(a.F, a.nseg), dim3(threads), 0, s, a);
+    // (without MVDR the kernel reads microphone 0 alone, whatever C is: the NC = 7 instantiation, as before the template)
+#define CSS_CALL(N) hipLaunchKernelGGL(beamform_kernel<N>, dim3(a.F, a.nseg), dim3(threads), 0, s, a)
+    if (!a.use_mvdr) { CSS_CALL(7); return; }
+    CSS_MVDR_DISPATCH(a.C, CSS_CALL)
+#undef CSS_CALL
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -20,7 +20,7 @@ import numpy as np
 
 from . import _lib
 from .separator import HipSeparator, load_css_model
-from .wavio import NUM_MICS_MC, load_audio, read_wav_pcm16, write_pcm16_samples, write_wav
+from .wavio import check_mic_count, load_audio, read_wav_pcm16, write_pcm16_samples, write_wav
 
 _LOG = logging.getLogger('css')
 
@@ -132,7 +132,7 @@ def separate_and_stitch(speech_mix: np.ndarray, separator, fs: int, device, cfg:
     """Applies speech separation in block-online fashion (css/css.py:110-338).
 
     Args:
-        speech_mix: long-form input [Batch, Nsamples, Channels] float32 (Channels == 1 or 7).
+        speech_mix: long-form input [Batch, Nsamples, Channels] float32 (Channels == the model's num_mics: 1 .. 8).
         separator: a ``HipSeparator`` (see separator.py).
         fs: sample rate.
         device: GPU to run on (torch.device / 'cuda:N' / int).
@@ -188,7 +188,7 @@ def _stage_separator(num_mics: int, num_spks: int, device) -> HipSeparator:
         bins = 257
         desc = ModelDesc(num_mics=num_mics, num_bins=bins, in_features=bins * (1 + (num_mics - 1 if num_mics > 1 else 0)),
                          attention_dim=256, attention_heads=4, linear_units=256, num_blocks=1, num_spks=num_spks)
-        sep = _STAGE_SEPARATORS[key] = HipSeparator(portable_state_dict(desc, 0), None, device=device)
+        sep = _STAGE_SEPARATORS[key] = HipSeparator(portable_state_dict(desc, 0), None, device=device, num_mics=num_mics)
         assert (sep.desc.num_mics, sep.desc.num_spks) == (num_mics, num_spks)
     return sep
 
@@ -349,7 +349,7 @@ def css_inference(out_dir: str, models_dir: str, session, cfg: CssCfg, fetch_fro
         raw = None if cfg.slice_audio_for_debug else [read_wav_pcm16(p) for p in session.wav_file_names]
         same_shape = raw and all(r is not None for r in raw) and len({(r[0].shape[0], r[1]) for r in raw}) == 1
         if same_shape:
-            assert len(raw) == (NUM_MICS_MC if session.is_mc else 1), f'expecting {NUM_MICS_MC} microphones'
+            check_mic_count(len(raw), bool(session.is_mc))
             sr, mixture, streams, encoded = _separate_pcm16_session(separator, raw, cfg, device)
         else:
             sr, mixture, streams, encoded = _separate_float_session(separator, session, cfg, device)

@@ -3,7 +3,7 @@
 
 The reference iterates the sessions of ``all_session_df`` one by one in a single process
 (``inference.py:59-63``: "sessions are independent by challenge rule"), reloads the checkpoint for every
-session (``css.py:85``) and, per session, reads 7 wav files, separates, writes 4 (``css.py:51-107``).  Here
+session (``css.py:85``) and, per session, reads one wav file per microphone (7 in the reference), separates, writes 4 (``css.py:51-107``).  Here
 
 * a rank takes every ``world``-th session (the scheme of the reference's unused ``DDPRowIterator``,
   ``utils/torch_utils.py:48-99``) -- dev-set-1 has 106 multi-channel sessions of ~6 min, which shard better
@@ -37,7 +37,7 @@ import numpy as np
 from . import _lib
 from .css import CssCfg, _SessionOutput, css_inference, make_run_cfg
 from .separator import _device_index, load_css_model
-from .wavio import NUM_MICS_MC, probe_wav_pcm16, read_pcm16_payload_into, write_pcm16_samples, write_wav
+from .wavio import check_mic_count, probe_wav_pcm16, read_pcm16_payload_into, write_pcm16_samples, write_wav
 
 _LOG = logging.getLogger('css')
 
@@ -96,7 +96,7 @@ def _decode_session(pos, session, where, cfg: CssCfg, pool: _PinnedPool) -> _Loa
     if not same:                       # float / multi-channel / 24-bit files, the debug slice: css_inference's own float path
         ld.fallback = True
         return ld
-    assert len(probes) == (NUM_MICS_MC if session.is_mc else 1), f'expecting {NUM_MICS_MC} microphones'
+    check_mic_count(len(probes), bool(session.is_mc))
     n, c = probes[0][0], len(probes)
     ld.sr = probes[0][1]
     ld.block = pool.take(n * c * 2)

@@ -77,8 +77,9 @@ def feature_options(e: ExtractorCfg) -> dict:
                 ipd_cos=e.ipd_cos, pairs=ipd_pairs(e.ipd_index))
 
 
-def desc_from_cfg(cfg: ConformerCssCfg) -> ModelDesc:
-    """ConformerCssCfg -> the C ABI's model descriptor.  The spectral and IPD options of ExtractorCfg
+def desc_from_cfg(cfg: ConformerCssCfg, num_mics: Optional[int] = None) -> ModelDesc:
+    """ConformerCssCfg -> the C ABI's model descriptor.  `num_mics`: the array's microphone count (1 .. 8, above every IPD pair
+    index); None keeps the default, the 7-microphone NOTSOFAR array whenever the pairs fit it.  The spectral and IPD options of ExtractorCfg
     (`log_spectrogram`, `mvn_spectrogram`, `ipd_index`, `ipd_mean_normalize`, `ipd_mean_normalize_version`, `ipd_cos`) are
     all implemented (css_set_feature_options), and so are both analysis windows init_kernel builds, 'hann' and 'sqrt_hann'
     (css_set_analysis_window; feature.py:24-36).  `frame_len` / `frame_hop` / `round_pow_of_two` (init_kernel,
@@ -102,8 +103,13 @@ def desc_from_cfg(cfg: ConformerCssCfg) -> ModelDesc:
         raise NotImplementedError("at most 16 IPD pairs")
     if e.ipd_mean_normalize and e.ipd_mean_normalize_version not in (1, 2, 3):
         raise RuntimeError(f"expect ipd_mean_normalization version 1, 2 or 3, got {e.ipd_mean_normalize_version}")  # feature.py:228-231
-    num_mics = (max(max(p) for p in pairs) + 1) if pairs else 1
-    num_mics = 7 if pairs and num_mics <= 7 else num_mics        # the NOTSOFAR array (mic_array_model.py:4)
+    need_mics = (max(max(p) for p in pairs) + 1) if pairs else 1
+    if num_mics is None:
+        num_mics = 7 if pairs and need_mics <= 7 else need_mics    # the NOTSOFAR array (mic_array_model.py:4)
+    elif not 1 <= int(num_mics) <= 8 or int(num_mics) < need_mics or (int(num_mics) == 1) != (not pairs):
+        raise ValueError(f"num_mics={num_mics}: must be 1 .. 8, exceed every IPD pair index (largest: {need_mics - 1}) and be 1 "
+                         f"exactly when there are no pairs")
+    num_mics = int(num_mics)
     bins = n_fft // 2 + 1
     assert n.in_features == bins * (1 + len(pairs)), \
         f"in_features={n.in_features} does not match {bins} bins x (1 + {len(pairs)} IPD pairs)"
@@ -147,12 +153,14 @@ class HipSeparator:
     "split_f16" is the explicit opt-in to 22-bit operands on the f16 matrix cores (about twice the throughput)."""
 
     def __init__(self, state_dict: Dict[str, "np.ndarray"], cfg: Optional[ConformerCssCfg] = None,
-                 device=0, max_batch_segments: int = 64, stream: int = 0, linear_mode: str = "exact_f32"):
+                 device=0, max_batch_segments: int = 64, stream: int = 0, linear_mode: str = "exact_f32",
+                 num_mics: Optional[int] = None):
         if linear_mode not in ("exact_f32", "split_f16"):
             raise ValueError(f"linear_mode must be 'exact_f32' or 'split_f16', got {linear_mode!r}")
         st = {k: (v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v))
               for k, v in strip_module_prefix(state_dict).items()}
-        desc = desc_from_cfg(cfg) if cfg is not None else None
+        # num_mics: the array's microphone count where it is not the default (7 for a model with IPD blocks, else 1)
+        desc = desc_from_cfg(cfg, num_mics) if cfg is not None else (ModelDesc.from_state_dict(st, num_mics) if num_mics is not None else None)
         self.blob, self.desc = pack_blob(st, desc)
         self.cfg = cfg
         self.training = False

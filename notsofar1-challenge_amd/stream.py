@@ -156,13 +156,13 @@ class CssStream:
     """One stream on a ``HipSeparator``'s handle.  ``push(chunk)`` -> list of S float32 arrays (the newly final samples),
     ``finish()`` -> the rest; use as a context manager (closes the stream).  ``handoff``, ``output``: see the module text."""
 
-    def __init__(self, separator: HipSeparator, cfg: Optional[CssCfg] = None, fs: int = 16000, num_channels: int = 7,
+    def __init__(self, separator: HipSeparator, cfg: Optional[CssCfg] = None, fs: int = 16000, num_channels: Optional[int] = None,
                  handoff: Optional[Mapping[str, object]] = None, input_rate: Optional[int] = None,
                  window_history: Optional[int] = None, output: Optional[Mapping[str, object]] = None):
         self.separator = separator
         self.cfg = cfg if cfg is not None else CssCfg()
         desc = separator.desc
-        self.num_channels = int(num_channels)
+        self.num_channels = int(desc.num_mics if num_channels is None else num_channels)   # (another count: CSS_ERR_SHAPE at css_stream_open)
         self.num_spks = int(desc.num_spks)
         self._run_cfg = make_run_cfg(self.cfg, fs, self.num_channels, desc.frame_len, desc.frame_hop)
         self._h = separator.handle

@@ -18,6 +18,16 @@ from typing import List, Tuple
 import numpy as np
 
 NUM_MICS_MC = 7  # utils/mic_array_model.py:4 multichannel_mic_pos_xyz_cm() has 7 rows
+MAX_MICS = 8     # the MVDR kernels' largest array (csrc/mvdr.hip); a multi-channel session lists 2 .. 8 wav files
+
+
+def check_mic_count(n_files: int, is_mc: bool) -> None:
+    """A session lists one wav file per microphone: one for a single-channel session, 2 .. 8 (the reference: 7) for a
+    multi-channel one.  That the count is the model's is checked where the model is known (CSS_ERR_SHAPE)."""
+    if is_mc:
+        assert 2 <= n_files <= MAX_MICS, f'expecting 2 .. {MAX_MICS} microphones ({NUM_MICS_MC} for the NOTSOFAR array), got {n_files}'
+    else:
+        assert n_files == 1, f'expecting 1 microphone, got {n_files}'
 
 
 def read_wav(path) -> Tuple[np.ndarray, int]:
@@ -151,10 +161,10 @@ def write_pcm16(path, samps: np.ndarray, sr: int) -> None:
 def load_audio(wav_file_names: List, is_mc: bool) -> Tuple[np.ndarray, int]:
     """css/helpers.py:40-65: -> (mix_wav float32 [Batch=1, n_samples, n_channels], sr)."""
     if is_mc:
-        assert len(wav_file_names) == NUM_MICS_MC, f'expecting {NUM_MICS_MC} microphones'
+        check_mic_count(len(wav_file_names), True)
         audio, srs = zip(*[read_wav(p) for p in wav_file_names])
         mix_wav = np.stack(audio, axis=-1)[np.newaxis, ...]
-        assert mix_wav.ndim == 3 and mix_wav.shape[2] in (1, 7)
+        assert mix_wav.ndim == 3 and 2 <= mix_wav.shape[2] <= MAX_MICS
         sr = srs[0]
     else:
         assert len(wav_file_names) == 1

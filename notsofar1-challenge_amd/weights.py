@@ -61,7 +61,9 @@ class ModelDesc:
         return cls(num_mics=1, in_features=257)
 
     @classmethod
-    def from_state_dict(cls, state: Dict[str, np.ndarray]) -> "ModelDesc":
+    def from_state_dict(cls, state: Dict[str, np.ndarray], num_mics: int = None) -> "ModelDesc":
+        """The descriptor a checkpoint implies.  A state dict does not say how many microphones its IPD pairs index: a model
+        with IPD blocks is taken for the 7-microphone NOTSOFAR array unless `num_mics` (2 .. 8) says otherwise."""
         st = strip_module_prefix(state)
         emb = st[PREFIX + "conformer.embed.0.weight"]
         pe = st[PREFIX + "conformer.pos_emb.pe_k.weight"]
@@ -71,7 +73,12 @@ class ModelDesc:
             blocks += 1
         nb = 257
         nout = st[PREFIX + "linear.weight"].shape[0]
-        return cls(num_mics=7 if emb.shape[1] > nb else 1, num_bins=nb, in_features=emb.shape[1],
+        implied = 7 if emb.shape[1] > nb else 1
+        if num_mics is None:
+            num_mics = implied
+        elif not 1 <= int(num_mics) <= 8 or (int(num_mics) == 1) != (implied == 1):
+            raise ValueError(f"num_mics={num_mics}: 2 .. 8 for a model with IPD blocks (in_features {emb.shape[1]} > {nb}), 1 for one without")
+        return cls(num_mics=int(num_mics), num_bins=nb, in_features=emb.shape[1],
                    attention_dim=d, attention_heads=d // pe.shape[1],
                    linear_units=st[PREFIX + "conformer.encoders.0.feed_forward_in.net.0.weight"].shape[0],
                    num_blocks=blocks,
