@@ -129,6 +129,10 @@ class CssStreamOutputCounts(C.Structure):
     _fields_ = [("n_written", C.c_int64), ("n_total", C.c_int64), ("n_clipped", C.c_void_p), ("peak_bits", C.c_void_p)]
 
 
+class CssSessionRate(C.Structure):              # include/css_mi355_session_rate.h
+    _fields_ = [("in_up", C.c_int32), ("in_down", C.c_int32), ("out_up", C.c_int32), ("out_down", C.c_int32)]
+
+
 STREAM_OUTPUT_TABLE = 16                         # CSS_STREAM_OUTPUT_TABLE: streams per launch of the output kernel
 STREAM_OUTPUT_TILE = 1024                        # output samples per block of the output kernel (kernels.hpp SO_TILE)
 WINDOW_DTYPES = {"float32": 0, "float16": 1}     # CSS_WINDOW_F32, CSS_WINDOW_F16 (include/css_mi355_window.h)
@@ -417,6 +421,18 @@ SIGNATURES_BACKEND = {
 ARRAY_SIGNATURES = {
     "css_mvdr_array_host": (C.c_int, [_P, C.POINTER(CssMvdrArrayDesc), _P, _P, _P, _P, _P, _P]),
 }
+# the entry points include/css_mi355_session_rate.h declares (whole sessions at the capture rate, both wav edges resampled on the
+# device), the thirteenth table load() applies (named SESSION_RATE_...: the same count in tests/test_backend_reference.py)
+SESSION_RATE_SIGNATURES = {
+    "css_session_rate_samples": (C.c_int, [C.POINTER(CssModelDesc), C.POINTER(CssRunCfg), C.POINTER(CssSessionRate), C.c_int64,
+                                           C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "css_run_rate": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.POINTER(CssRunCfg), C.POINTER(CssSessionRate), _P, C.c_int64]),
+    "css_run_pcm16_rate": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.POINTER(CssRunCfg), C.POINTER(CssSessionRate), _P, C.c_int64, _P]),
+    "css_run_enqueue_rate": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.POINTER(CssRunCfg), C.POINTER(CssSessionRate), _P, C.c_int64]),
+    "css_run_enqueue_pcm16_rate": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.POINTER(CssRunCfg), C.POINTER(CssSessionRate), _P, C.c_int64,
+                                             _P]),
+    "css_session_rate_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+}
 ARRAY_MIN_MICS, ARRAY_MAX_MICS = 2, 8            # CSS_ARRAY_MIN_MICS, CSS_ARRAY_MAX_MICS
 SESSION_SCAN_CHUNK = 1024                        # CSS_SESSION_SCAN_CHUNK: the keep-scan kernel's step, in gate frames / sample blocks
 RESAMPLE_TILE = 256                              # output samples per block of the two resampling kernels (resample.hip RS_TILE)
@@ -465,7 +481,7 @@ def load() -> C.CDLL:
                               list(SIGNATURES_WINDOW.items()) + list(SIGNATURES_PRESENT.items()) +
                               list(SIGNATURES_FRONTEND.items()) + list(SIGNATURES_SESSION_HANDOFF.items()) +
                               list(SIGNATURES_STREAM_OUT.items()) + list(SIGNATURES_BACKEND.items()) +
-                              list(ARRAY_SIGNATURES.items())):
+                              list(ARRAY_SIGNATURES.items()) + list(SESSION_RATE_SIGNATURES.items())):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -574,6 +590,24 @@ def resample_taps(up: int, down: int) -> np.ndarray:
     if rc != CSS_OK:
         raise CssError(rc, f"css_resample_taps: the ratio {up} / {down} is not supported")
     return taps[:n.value]
+
+
+def session_rate(input_rate: Optional[int] = None, output_rate: Optional[int] = None, fs: int = 16000) -> CssSessionRate:
+    """The two ratios of a session whose files are at `input_rate` and whose streams are wanted at `output_rate` (None: the
+    model's rate `fs` on that side): 48000 in, 16000 out -> 1 / 3 and 1 / 1; 48000 in and out -> 1 / 3 and 3 / 1"""
+    in_up, in_down = (1, 1) if input_rate is None else rate_ratio(input_rate, fs)
+    out_down, out_up = (1, 1) if output_rate is None else rate_ratio(output_rate, fs)   # (rate_ratio gives fs / rate)
+    return CssSessionRate(in_up, in_down, out_up, out_down)
+
+
+def session_rate_samples(desc, run_cfg: RunCfg, rate: CssSessionRate, n_in: int):
+    """css_session_rate_samples: (n_model, n_out_model, n_out) of a recording of `n_in` capture-rate samples"""
+    a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+    rc = load().css_session_rate_samples(C.byref(make_desc(desc)), C.byref(run_cfg.c), C.byref(rate), int(n_in), C.byref(a), C.byref(b), C.byref(c))
+    if rc != CSS_OK:
+        raise CssError(rc, f"css_session_rate_samples: the ratios {rate.in_up} / {rate.in_down}, {rate.out_up} / {rate.out_down} are not "
+                           f"supported, or {n_in} samples are outside [1, 2^40] or too few for this configuration")
+    return int(a.value), int(b.value), int(c.value)
 
 
 def stream_output_cfg(rate: int = 16000, dtype="float32", gain: float = 1.0, fs: int = 16000) -> CssStreamOutputCfg:
@@ -856,6 +890,81 @@ class Handle:
         check(self.h, self.lib.css_run_enqueue_pcm16(self.h, ptrs, n, c, C.byref(cfg.c), out16.ctypes.data_as(C.c_void_p), out16.strides[0] // 2,
                                                      peaks.ctypes.data_as(C.c_void_p) if peaks is not None else None))
         return out16[:, :pl.n_out]
+
+    # ---- whole sessions at the capture rate (include/css_mi355_session_rate.h)
+    def session_rate_samples(self, cfg: RunCfg, rate: CssSessionRate, n_in: int):
+        """(n_model, n_out_model, n_out) of a recording of `n_in` capture-rate samples on this handle's model"""
+        return session_rate_samples(self.desc, cfg, rate, n_in)
+
+    def _rate_float_args(self, pcm, cfg, rate, out):
+        assert pcm.dtype == np.float32 and pcm.flags.c_contiguous and pcm.ndim == 2
+        n, c = pcm.shape
+        n_out = self.session_rate_samples(cfg, rate, n)[2]
+        S = int(self.desc.num_spks)
+        if out is None:
+            out = np.empty((S, n_out), dtype=np.float32)
+        assert out.dtype == np.float32 and out.ndim == 2 and out.shape[0] == S and out.shape[1] >= n_out and out.strides[1] == 4
+        return n, c, n_out, out
+
+    def _rate_pcm16_args(self, planes, cfg, rate, out16, peaks):
+        n = planes[0].shape[0]
+        for p in planes:
+            assert p.dtype == np.int16 and p.ndim == 1 and p.shape[0] == n and p.flags.c_contiguous
+        n_out = self.session_rate_samples(cfg, rate, n)[2]
+        S = int(self.desc.num_spks)
+        if out16 is None:
+            out16 = np.empty((S, n_out), dtype=np.int16)
+        if peaks is None:
+            peaks = np.empty((S,), dtype=np.float32)
+        assert out16.dtype == np.int16 and out16.ndim == 2 and out16.shape[0] == S and out16.shape[1] >= n_out and out16.strides[1] == 2
+        assert peaks.dtype == np.float32 and peaks.shape == (S,) and peaks.flags.c_contiguous
+        ptrs = (C.c_void_p * len(planes))(*[p.ctypes.data for p in planes])
+        return n, len(planes), n_out, out16, peaks, ptrs
+
+    def run_rate(self, pcm: np.ndarray, cfg: RunCfg, rate: CssSessionRate, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """css_run_rate: pcm [n_in, C] float32 at the capture rate -> wav [S, n_out] float32 at the output rate.  `cfg` is the
+        configuration at the MODEL's rate (make_run_cfg(cfg, 16000, ...))."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.float32)
+        n, c, n_out, out = self._rate_float_args(pcm, cfg, rate, out)
+        check(self.h, self.lib.css_run_rate(self.h, _np_ptr(pcm), n, c, C.byref(cfg.c), C.byref(rate), _np_ptr(out), out.strides[0] // 4))
+        return out[:, :n_out]
+
+    def run_pcm16_rate(self, planes, cfg: RunCfg, rate: CssSessionRate):
+        """css_run_pcm16_rate: C mono int16 planes at the capture rate -> (int16 [S, n_out] peak-normalised at the output rate,
+        float32 [S] peaks of the streams at that rate)."""
+        planes = [np.ascontiguousarray(p, dtype=np.int16) for p in planes]
+        n, c, n_out, out16, peaks, ptrs = self._rate_pcm16_args(planes, cfg, rate, None, None)
+        check(self.h, self.lib.css_run_pcm16_rate(self.h, ptrs, n, c, C.byref(cfg.c), C.byref(rate), out16.ctypes.data_as(C.c_void_p),
+                                                  out16.strides[0] // 2, peaks.ctypes.data_as(C.c_void_p)))
+        return out16[:, :n_out], peaks
+
+    def run_enqueue_rate(self, pcm: np.ndarray, cfg: RunCfg, rate: CssSessionRate, out: np.ndarray) -> np.ndarray:
+        """run_rate as a queued session (css_run_enqueue_rate): run_enqueue's lifetime rules; returns the view of `out` that
+        wait() makes valid."""
+        n, c, n_out, out = self._rate_float_args(pcm, cfg, rate, out)
+        self._queued_keep = getattr(self, "_queued_keep", []) + [(pcm, out, cfg, rate)]
+        check(self.h, self.lib.css_run_enqueue_rate(self.h, _np_ptr(pcm), n, c, C.byref(cfg.c), C.byref(rate), _np_ptr(out),
+                                                    out.strides[0] // 4))
+        return out[:, :n_out]
+
+    def run_enqueue_pcm16_rate(self, planes, cfg: RunCfg, rate: CssSessionRate, out16: np.ndarray,
+                               peaks: Optional[np.ndarray] = None) -> np.ndarray:
+        """run_pcm16_rate as a queued session (css_run_enqueue_pcm16_rate): run_enqueue_pcm16's lifetime rules; returns the view
+        of `out16` that wait() makes valid."""
+        assert out16 is not None
+        keep_peaks = peaks
+        n, c, n_out, out16, peaks, ptrs = self._rate_pcm16_args(planes, cfg, rate, out16, peaks)
+        self._queued_keep = getattr(self, "_queued_keep", []) + [(planes, out16, peaks, cfg, rate)]
+        check(self.h, self.lib.css_run_enqueue_pcm16_rate(self.h, ptrs, n, c, C.byref(cfg.c), C.byref(rate), out16.ctypes.data_as(C.c_void_p),
+                                                          out16.strides[0] // 2,
+                                                          peaks.ctypes.data_as(C.c_void_p) if keep_peaks is not None else None))
+        return out16[:, :n_out]
+
+    def session_rate_stats(self):
+        """(launches of the ingest kernel, launches of the output kernel, rate sessions) on this handle since it was created"""
+        a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+        check(self.h, self.lib.css_session_rate_stats(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        return int(a.value), int(b.value), int(c.value)
 
     def timings(self) -> dict:
         t = CssTimings()

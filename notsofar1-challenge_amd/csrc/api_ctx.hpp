@@ -150,6 +150,17 @@ struct SessHandoffReq {
     int64_t* n_frames = nullptr; int32_t* n_ranges = nullptr;
 };
 
+// What css_run*_rate ask for beside the session (api_session_rate.hip): the two ratios with their device tables, the counts, and --
+// with an output ratio -- where the streams at the output rate go.  Such a session's RunIo / QueuedSession has no sink of its
+// own (wav == wav16 == nullptr, cap = the model-rate n_out): its waveforms stay in HBM and leave through session_output_on.
+struct SessRate {
+    bool on = false, in_on = false, out_on = false;   // a rate session; its input / output side has a ratio other than 1 / 1
+    ResampleRatio in{}, out{};
+    const float* in_tab = nullptr; const float* out_tab = nullptr;   // the phase tables on the device (css_ctx::rate_tabs)
+    int64_t n_in = 0, n_out = 0;   // capture-rate samples per channel; output-rate samples per stream
+    float* wav = nullptr; int16_t* wav16 = nullptr; float* peaks = nullptr; int64_t cap = 0;   // (out_on) the caller's [S][cap], peaks [S]
+};
+
 // Where the samples of a pass come from and where its result goes (exactly one source; one sink, or -- a queued session that
 // only hands off -- none).
 struct RunIo {
@@ -163,6 +174,8 @@ struct RunIo {
     int64_t cap = 0;
     bool enqueue_only = false;                   // css_run_enqueue: return once everything is on the streams
     const SessHandoffReq* ho = nullptr;          // a queued session that also hands off: behind the waveforms, on their stream
+    const SessRate* rate = nullptr;              // a rate session: with in_on, pcm_host / planes_host are at the capture rate (rate->n_in samples)
+    bool level_done = false;                     // pcm_dev: the recording's level is already in the level word (the ingest kernel wrote it)
     // host to host: float PCM -> float waveforms (pcm, wav) or PCM16 planes -> PCM16 streams and their peaks (planes, wav16, peaks)
     static RunIo host(const float* pcm, const int16_t* const* planes, float* wav, int16_t* wav16, float* peaks, int64_t cap,
                       bool enqueue_only = false) {
@@ -273,6 +286,7 @@ struct css_ctx : SessState {
         std::vector<const int16_t*> planes; int16_t* wav16; float* peaks;
         float* wav_mapped;      // device address of the page-locked output (nullptr: pageable, or never looked up)
         SessHandoffReq ho;      // css_run_enqueue*_handoff (wav may then be nullptr: log-mel only)
+        SessRate rate;          // css_run*_rate: n is the MODEL-rate count, pcm / planes hold rate.n_in capture-rate samples
         std::vector<float> w;   // w_first | w_mid | w_last of cfg
         QueuedSession(const float* pcm_, const int16_t* const* planes_, int64_t n_, int32_t n_ch_, const CssRunCfg& c, float* wav_,
                       int16_t* wav16_, float* peaks_, int64_t cap_, float* mapped_)
@@ -296,6 +310,7 @@ struct css_ctx : SessState {
         RunIo io(bool enqueue_only) const {
             RunIo io = RunIo::host(pcm, pcm16() ? planes.data() : nullptr, wav, wav16, peaks, cap, enqueue_only);
             io.ho = ho.on ? &ho : nullptr;
+            io.rate = rate.on ? &rate : nullptr;
             return io;
         }
         // may the two share an estimator batch: one segmentation, the same three windows bit for bit
@@ -347,6 +362,13 @@ struct css_ctx : SessState {
     StreamState* streams[CSS_MAX_STREAMS] = {};   // css_stream_open: open streams (api_stream.hpp), by id
     HandoffCtx* handoff = nullptr;   // api_stream_handoff.hip: what the hand-off of streams shares on this handle, made on first use
     int32_t stream_out_launches = 0, stream_out_rounds = 0;   // api_stream.hip stream_round: the output kernel in the last push / finish call
+    // css_run*_rate (api_session_rate.hip): the phase tables of the ratios met so far (never rebuilt, never moved: queued sessions
+    // hold their addresses), the output edge's buffers (level words | float rows | PCM16 rows; tails are serial on their stream),
+    // and the running counts of css_session_rate_stats
+    struct RateTab { int up, down; DevBuf tab; };
+    std::vector<std::unique_ptr<RateTab>> rate_tabs;
+    DevBuf rate_out;
+    int64_t rate_ingest_launches = 0, rate_output_launches = 0, rate_sessions = 0;
     DevBuf stream_masks;   // api_stream.hip: the mask head's output for one estimator batch of streamed segments (never `masks`:
                            // the handle's own session keeps its bits between two pushes)
 
@@ -446,7 +468,24 @@ int stream_open_count(const css_ctx* h);
 hipEvent_t pool_event(css_ctx* h);
 void* mapped_host(const void* p);
 int enqueue_impl(css_handle_t h, const float* pcm_host, const int16_t* const* planes, int64_t n_samples, int32_t n_ch,
-                 const CssRunCfg* cfg, float* wav_host, int16_t* wav16, float* peaks, int64_t cap, const SessHandoffReq* ho = nullptr);
+                 const CssRunCfg* cfg, float* wav_host, int16_t* wav16, float* peaks, int64_t cap, const SessHandoffReq* ho = nullptr,
+                 const SessRate* rate = nullptr);
+int run_impl(css_handle_t h, int64_t n, int32_t n_ch, const CssRunCfg* cfg, const RunIo& io);
+int waveforms_out(css_ctx* h, const float* src, int64_t src_ld, float* wav, int64_t cap, int64_t a, int64_t b, hipStream_t st);
+
+// ---- api_session_rate.hip
+// a rate session's view of its own sink: the caller's arrays move into q.rate when the output side has a ratio
+void session_rate_adopt(css_ctx::QueuedSession& q, const SessRate& rate, int64_t n_out_model);
+// the output edge's buffers for a session of this rate (before the first launch of the pass or group: ensure may wait)
+int session_rate_prepare(css_ctx* h, const SessRate& r);
+// bytes of the capture-rate recording, and the whole ingest of ONE session on `st`: upload to `staging`, the kernel -> dst
+size_t session_rate_capture_bytes(const SessRate& r, int n_ch, bool pcm16);
+int session_rate_upload(css_ctx* h, const SessRate& r, const float* pcm, const int16_t* const* planes, int n_ch, void* staging, hipStream_t st);
+SessionIngestJob session_rate_job(const SessRate& r, bool pcm16, int n_ch, const void* staging, float* dst, int64_t n_model, int64_t n_peak,
+                                  unsigned int* level);
+int session_rate_ingest(css_ctx* h, const SessionIngestJob* jobs, int n, hipStream_t st);
+// the output edge of the handle's current session on `st`: wav [S][wav_ld] in HBM -> the caller's arrays at the output rate
+int session_output_on(css_ctx* h, const float* wav, int64_t wav_ld, const SessRate& r, hipStream_t st);
 
 // ---- api_session_handoff.hip
 // the handle's tables and work buffers for a session of this plan (before the first launch of the pass or group: ensure may wait)

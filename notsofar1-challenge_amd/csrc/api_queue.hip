@@ -160,7 +160,7 @@ static int encode_pcm16_out(css_ctx* h, const float* src, int16_t* wav16, int64_
 }
 
 // samples [a, b) of the float waveforms `src` [S][src_ld] to the caller's [S][cap], stream by stream
-static int waveforms_out(css_ctx* h, const float* src, int64_t src_ld, float* wav, int64_t cap, int64_t a, int64_t b, hipStream_t st) {
+int waveforms_out(css_ctx* h, const float* src, int64_t src_ld, float* wav, int64_t cap, int64_t a, int64_t b, hipStream_t st) {
     for (int sp = 0; sp < h->d.num_spks; ++sp)
         HIPCHK(h, hipMemcpyAsync(wav + (size_t)sp * cap + a, src + (size_t)sp * src_ld + a, (size_t)(b - a) * sizeof(float), hipMemcpyDeviceToHost, st));
     return CSS_OK;
@@ -184,7 +184,7 @@ static int run_plain(css_ctx* h, int64_t n, int32_t n_ch, const RunIo& io, HostC
         hipEventRecord(h->ev[2], h->stream);
         h->stft_done = true;
     } else {
-        launch_pcm_peak_f32(h->pcm_src, peak_len(h, 0, n) * n_ch, h->peak_dev, h->stream);
+        if (!io.level_done) launch_pcm_peak_f32(h->pcm_src, peak_len(h, 0, n) * n_ch, h->peak_dev, h->stream);
         if ((rc = css_stage_stft(h)) != CSS_OK) return rc;
     }
     if ((rc = css_stage_masknet(h, 0, nseg)) != CSS_OK) return rc;
@@ -201,6 +201,7 @@ static int run_plain(css_ctx* h, int64_t n, int32_t n_ch, const RunIo& io, HostC
     if ((rc = istft_impl(h, 0, TL, 0, TL - 1 + h->ovl, dst, dst_ld, 0, h->stream)) != CSS_OK) return rc;
     if (io.wav16_host && (rc = encode_pcm16_out(h, dst, io.wav16_host, io.cap, io.peaks_host, h->stream)) != CSS_OK) return rc;
     if (io.wav_host && (rc = waveforms_out(h, dst, dst_ld, io.wav_host, io.cap, 0, pl.n_out, h->stream)) != CSS_OK) return rc;
+    if (io.rate && io.rate->out_on && (rc = session_output_on(h, dst, dst_ld, *io.rate, h->stream)) != CSS_OK) return rc;
     HIPCHK(h, hipMemcpyAsync(h->range_flag_host.p, h->range_flag_dev.p, sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
     hipEventRecord(h->ev[7], h->stream);
     return sync_and_time(h, t0, true);
@@ -375,7 +376,7 @@ static int run_pipeline(css_ctx* h, int64_t n, int32_t n_ch, const RunIo& io, bo
         hipEvent_t level = pool_event(h);
         HIPCHK(h, hipEventRecord(level, h->copy_stream));
         HIPCHK(h, hipStreamWaitEvent(h->tail_stream, level, 0));
-    } else {
+    } else if (!io.level_done) {
         launch_pcm_peak_f32(h->pcm_src, peak_len(h, 0, n) * n_ch, h->peak_dev, h->tail_stream);
     }
     if ((rc = zero_short_planes(h, h->stream)) != CSS_OK) return rc;
@@ -443,6 +444,8 @@ static int run_pipeline(css_ctx* h, int64_t n, int32_t n_ch, const RunIo& io, bo
     if (io.wav16_host && (rc = encode_pcm16_out(h, (const float*)h->wav.p, io.wav16_host, io.cap, io.peaks_host, h->stream)) != CSS_OK) return rc;
     // a queued session that also hands off (never an overlapping pass: run_once): its waveforms are whole in h->wav by now
     if (io.ho && (rc = session_handoff_on(h, (const float*)h->wav.p, pl.n_out, *io.ho, h->stream)) != CSS_OK) return rc;
+    // a rate session with an output ratio (never an overlapping pass either): its waveforms are whole in h->wav, the output edge follows
+    if (io.rate && io.rate->out_on && (rc = session_output_on(h, (const float*)h->wav.p, pl.n_out, *io.rate, h->stream)) != CSS_OK) return rc;
     // range check (split_f16.hpp): a split GEMM whose operand left the format's range raised this word
     HIPCHK(h, hipMemcpyAsync(h->range_flag_host.p, h->range_flag_dev.p, sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
     if (tails.out_done) HIPCHK(h, hipStreamWaitEvent(h->stream, tails.out_done, 0));
@@ -456,10 +459,15 @@ static int run_pipeline(css_ctx* h, int64_t n, int32_t n_ch, const RunIo& io, bo
     return sync_and_time(h, t0, false);
 }
 
-int run_once(css_handle_t h, int64_t n, int32_t n_ch, const CssRunCfg* cfg, const RunIo& io) {
+int run_once(css_handle_t h, int64_t n, int32_t n_ch, const CssRunCfg* cfg, const RunIo& io_in) {
     int rc;
     if (!h) return CSS_ERR_INVALID_ARG;
     const auto host_t0 = std::chrono::steady_clock::now();
+    // A rate session alone in its pass (css_run*_rate, or a queued one without company): its recording is converted on the handle's
+    // stream in front of everything else, and the pass runs on the model-rate samples in HBM -- never as an overlapping pass.
+    RunIo io = io_in;
+    const bool ingest = io.rate && io.rate->in_on;
+    if (ingest) { io.pcm_host = nullptr; io.planes_host = nullptr; }
     // page-locked output (css_host_alloc): its device address, for the zero-copy output path
     float* wav_mapped = nullptr;
     if (io.wav_host && (h->tune[CSS_TUNE_OUT_MAPPED] || io.enqueue_only)) {
@@ -503,9 +511,22 @@ int run_once(css_handle_t h, int64_t n, int32_t n_ch, const CssRunCfg* cfg, cons
         if ((rc = ensure(h, h->in16, (size_t)n * n_ch * sizeof(int16_t))) != CSS_OK) return rc;
         for (int c = 0; c < n_ch; ++c)
             if (!io.planes_host[c]) return fail(h, CSS_ERR_INVALID_ARG, "null channel plane");
+    } else if (ingest) {
+        const bool pcm16 = io_in.planes_host != nullptr;
+        const size_t model_b = ((size_t)n * n_ch * sizeof(float) + 255) / 256 * 256;
+        if ((rc = ensure(h, h->pcm_in, model_b + session_rate_capture_bytes(*io.rate, n_ch, pcm16))) != CSS_OK) return rc;
+        float* model = (float*)h->pcm_in.p;
+        void* staging = (char*)h->pcm_in.p + model_b;
+        if ((rc = session_rate_upload(h, *io.rate, io_in.pcm_host, io_in.planes_host, n_ch, staging, h->stream)) != CSS_OK) return rc;
+        const SessionIngestJob job = session_rate_job(*io.rate, pcm16, n_ch, staging, model, n, peak_len(h, 0, n), h->peak_dev);
+        if ((rc = session_rate_ingest(h, &job, 1, h->stream)) != CSS_OK) return rc;
+        h->pcm_src = model;
+        io.pcm_dev = model;
+        io.level_done = true;
     } else {
         h->pcm_src = io.pcm_dev;
     }
+    if (io.rate && (rc = session_rate_prepare(h, *io.rate)) != CSS_OK) return rc;
     if (io.wav16_host && (rc = ensure(h, h->enc, (size_t)h->d.num_spks * pl.n_out * sizeof(int16_t) + 64)) != CSS_OK) return rc;
     hipEventRecord(h->ev[1], h->stream);
     hipEventRecord(h->ev[2], h->stream);   // the analysis transform is part of the lanes' chains (CssTimings.stft = 0)
@@ -548,7 +569,8 @@ int run_group(css_handle_t h, const std::vector<css_ctx::QueuedSession>& grp) {
     if ((int)h->slots.size() < G - 1) h->slots.resize((size_t)(G - 1));
     const int S = h->d.num_spks, F = h->d.num_bins;
     // ---- the sessions: plans, buffers
-    std::vector<int64_t> off((size_t)G), pcm_off((size_t)G);
+    std::vector<int64_t> off((size_t)G), pcm_off((size_t)G), cap_off((size_t)G);
+    bool any_ingest = false;
     int64_t total = 0;
     size_t pcm_bytes = 0;
     for (int j = 0; j < G; ++j) {
@@ -564,7 +586,15 @@ int run_group(css_handle_t h, const std::vector<css_ctx::QueuedSession>& grp) {
         off[(size_t)j] = total;
         total += h->plan.num_segments;
         pcm_off[(size_t)j] = (int64_t)pcm_bytes;
-        pcm_bytes += ((size_t)q.n * q.n_ch * (q.pcm16() ? sizeof(int16_t) : sizeof(float)) + 255) / 256 * 256;
+        if (q.rate.in_on) {   // the model-rate floats the ingest kernel writes, and behind them the recording as it was captured
+            pcm_bytes += ((size_t)q.n * q.n_ch * sizeof(float) + 255) / 256 * 256;
+            cap_off[(size_t)j] = (int64_t)pcm_bytes;
+            pcm_bytes += (session_rate_capture_bytes(q.rate, q.n_ch, q.pcm16()) + 255) / 256 * 256;
+            any_ingest = true;
+        } else {
+            pcm_bytes += ((size_t)q.n * q.n_ch * (q.pcm16() ? sizeof(int16_t) : sizeof(float)) + 255) / 256 * 256;
+        }
+        if (q.rate.on && (rc = session_rate_prepare(h, q.rate)) != CSS_OK) return rc;
         if (q.wav16 && (rc = ensure(h, h->enc, (size_t)h->d.num_spks * h->plan.n_out * sizeof(int16_t) + 64)) != CSS_OK) return rc;
         if (q.ho.on && (rc = session_handoff_prepare(h, h->plan, q.ho)) != CSS_OK) return rc;   // (before the group's first launch: ensure may wait)
     }
@@ -582,7 +612,7 @@ int run_group(css_handle_t h, const std::vector<css_ctx::QueuedSession>& grp) {
     for (int j = 0; j < G; ++j) {
         Active act(h, j, G);
         h->pcm_src = (const float*)(pcm_base + pcm_off[(size_t)j]);
-        h->src16 = grp[(size_t)j].pcm16();
+        h->src16 = grp[(size_t)j].pcm16() && !grp[(size_t)j].rate.in_on;   // (a rate session is a float session behind its ingest)
         h->masks_v = (float*)h->masks.p + off[(size_t)j] * T;
         h->mask_ld_v = total * T;
         gs[(size_t)j] = GroupSess{(const float*)h->X.p, h->T_ld, h->plan.stft_frames, off[(size_t)j], (int)h->plan.num_segments,
@@ -600,10 +630,26 @@ int run_group(css_handle_t h, const std::vector<css_ctx::QueuedSession>& grp) {
     // ---- copy stream: every session's samples as one piece, its level scanned and its analysis transform behind it --
     // all of it beside the PREVIOUS pass's estimator (the host runs passes ahead), so that the main stream carries nothing
     // but estimators, back to back
+    if (any_ingest) {
+        // the rate sessions first: their recordings as they were captured, then ONE launch that converts all of them into their
+        // slots and writes their levels (no peak scan for them below)
+        std::vector<SessionIngestJob> jobs;
+        for (int j = 0; j < G; ++j) {
+            const css_ctx::QueuedSession& q = grp[(size_t)j];
+            if (!q.rate.in_on) continue;
+            Active act(h, j, G);
+            void* staging = const_cast<char*>(pcm_base) + cap_off[(size_t)j];
+            if ((rc = session_rate_upload(h, q.rate, q.pcm, q.pcm16() ? q.planes.data() : nullptr, q.n_ch, staging, h->copy_stream)) != CSS_OK) return rc;
+            jobs.push_back(session_rate_job(q.rate, q.pcm16(), q.n_ch, staging, const_cast<float*>(h->pcm_src), q.n, peak_len(h, 0, q.n), h->peak_dev));
+        }
+        if ((rc = session_rate_ingest(h, jobs.data(), (int)jobs.size(), h->copy_stream)) != CSS_OK) return rc;
+    }
     for (int j = 0; j < G; ++j) {
         Active act(h, j, G);
         const css_ctx::QueuedSession& q = grp[(size_t)j];
-        if (h->src16) {   // the session's mono PCM16 planes, half the PCIe bytes (css_run_enqueue_pcm16)
+        if (q.rate.in_on) {
+            // (converted above)
+        } else if (h->src16) {   // the session's mono PCM16 planes, half the PCIe bytes (css_run_enqueue_pcm16)
             if ((rc = planes_up(h, q.planes.data(), (int16_t*)const_cast<float*>(h->pcm_src), q.n, q.n_ch, h->copy_stream)) != CSS_OK) return rc;
         } else {
             HIPCHK(h, hipMemcpyAsync(const_cast<float*>(h->pcm_src), q.pcm, (size_t)q.n * q.n_ch * sizeof(float), hipMemcpyHostToDevice,
@@ -706,7 +752,13 @@ int run_group(css_handle_t h, const std::vector<css_ctx::QueuedSession>& grp) {
         { CSS_PROF(CSS_PROF_OLA_STFT, ts); launch_ola_stft(sa, 0, TL, ts); }
         if (j == G - 1) hipEventRecord(h->ev[5], ts);
         istft_gemm_on(h, 0, TL, ts);
-        if (q.ho.on) {
+        if (q.rate.out_on) {
+            // A session with an output ratio: the waveforms stay in HBM, as a hand-off session's do, and the output edge follows on
+            // this stream before the session counts as done
+            const int64_t n_out = h->plan.n_out;
+            wave_ola_on(h, 0, TL, 0, TL + 1, (float*)h->wav.p, n_out, 0, ts);
+            if ((rc = session_output_on(h, (const float*)h->wav.p, n_out, q.rate, ts)) != CSS_OK) return rc;
+        } else if (q.ho.on) {
             // A session that also hands off: the waveforms stay in HBM -- never the zero-copy overlap-add -- and leave by copies
             // (none with wav == nullptr); the hand-off follows on this stream, before the session counts as done.  h->wav is the
             // session's own; the hand-off's work buffers are the handle's one set: tails are serial on this stream.
@@ -795,11 +847,13 @@ int css_run(css_handle_t h, const float* pcm_host, int64_t n_samples, int32_t n_
 // css_run_enqueue (float PCM -> float waveforms) and css_run_enqueue_pcm16 (PCM16 planes -> peak-normalised PCM16 streams): one
 // queue, one grouping rule; a session is one or the other (planes == nullptr: float)
 int enqueue_impl(css_handle_t h, const float* pcm_host, const int16_t* const* planes, int64_t n_samples, int32_t n_ch,
-                 const CssRunCfg* cfg, float* wav_host, int16_t* wav16, float* peaks, int64_t cap, const SessHandoffReq* ho) {
+                 const CssRunCfg* cfg, float* wav_host, int16_t* wav16, float* peaks, int64_t cap, const SessHandoffReq* ho,
+                 const SessRate* rate) {
     CssPlan pl{};
     int rc = check_run_args(h, n_samples, n_ch, cfg, &pl);
     if (rc != CSS_OK) return rc;
-    if (cap < pl.n_out) return fail(h, CSS_ERR_INVALID_ARG, "output buffer too small: need " + std::to_string(pl.n_out) + " samples per stream");
+    // (a rate session: n_samples counts model-rate samples, and cap was checked against the output-rate count)
+    if (!rate && cap < pl.n_out) return fail(h, CSS_ERR_INVALID_ARG, "output buffer too small: need " + std::to_string(pl.n_out) + " samples per stream");
     if (planes)
         for (int c = 0; c < n_ch; ++c)
             if (!planes[c]) return fail(h, CSS_ERR_INVALID_ARG, "null channel plane");
@@ -814,6 +868,7 @@ int enqueue_impl(css_handle_t h, const float* pcm_host, const int16_t* const* pl
     const bool groupable = h->fft512 && h->group_limit > 1 && locked && h->tune[CSS_TUNE_MVDR_ON_LANES] && pl.num_segments <= batch_cap(h, cfg->segment_frames);
     css_ctx::QueuedSession q(pcm_host, planes, n_samples, n_ch, *cfg, wav_host, wav16, peaks, cap, mapped);
     if (ho) q.ho = *ho;
+    if (rate) { session_rate_adopt(q, *rate, pl.n_out); h->rate_sessions += 1; }
     if (!h->fft512) {
         // Frame sizes other than 512 / 256 run the plain stage sequence to its end inside the call (run_once): nothing stays
         // queued, so css_wait would never look at the range word.  The pass therefore takes css_run's own rule here -- queued

@@ -127,13 +127,13 @@ __global__ __launch_bounds__(256) void peak_kernel(const float* __restrict__ wav
     if ((threadIdx.x & 63) == 0) atomicMax(peak + s, __float_as_uint(m));
 }
 
-__global__ void encode_pcm16_kernel(const float* __restrict__ wav, int64_t n, const unsigned int* __restrict__ peak,
+__global__ void encode_pcm16_kernel(const float* __restrict__ wav, int64_t wav_ld, int64_t n, const unsigned int* __restrict__ peak,
                                     int16_t* __restrict__ out, int64_t out_ld) {
     const int s = blockIdx.y;
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float den = __fadd_rn(__uint_as_float(peak[s]), 1e-7f);
-    const float y = __fdiv_rn(__fmul_rn(wav[(int64_t)s * n + i], 0.99f), den);
+    const float y = __fdiv_rn(__fmul_rn(wav[(int64_t)s * wav_ld + i], 0.99f), den);
     double v = rint((double)y * 32767.0);
     v = fmin(fmax(v, -32768.0), 32767.0);
     out[(int64_t)s * out_ld + i] = (int16_t)v;
@@ -144,7 +144,13 @@ void launch_encode_pcm16(const float* wav, int S, int64_t n, unsigned int* peak_
     if (n <= 0) return;
     hipMemsetAsync(peak_bits, 0, (size_t)S * sizeof(unsigned int), s);
     hipLaunchKernelGGL(peak_kernel, dim3(256, S), dim3(256), 0, s, wav, n, peak_bits);
-    hipLaunchKernelGGL(encode_pcm16_kernel, dim3((unsigned)((n + 255) / 256), S), dim3(256), 0, s, wav, n, peak_bits, out, out_ld);
+    hipLaunchKernelGGL(encode_pcm16_kernel, dim3((unsigned)((n + 255) / 256), S), dim3(256), 0, s, wav, n, n, peak_bits, out, out_ld);
+}
+
+void launch_encode_pcm16_with_peaks(const float* wav, int64_t wav_ld, int S, int64_t n, const unsigned int* peak_bits, int16_t* out,
+                                    int64_t out_ld, hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(encode_pcm16_kernel, dim3((unsigned)((n + 255) / 256), S), dim3(256), 0, s, wav, wav_ld, n, peak_bits, out, out_ld);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -185,6 +185,9 @@ void launch_pcm16_to_channel_major(const int16_t* planes, float* pcm_cm, int64_t
                                    int64_t i_hi, hipStream_t s);
 void launch_encode_pcm16(const float* wav, int S, int64_t n, unsigned int* peak_bits, int16_t* out, int64_t out_ld,
                          hipStream_t s);
+// the second of its two steps alone: rows wav [S][wav_ld] with their peaks already in peak_bits (the session output kernel's)
+void launch_encode_pcm16_with_peaks(const float* wav, int64_t wav_ld, int S, int64_t n, const unsigned int* peak_bits, int16_t* out,
+                                    int64_t out_ld, hipStream_t s);
 // features for segments [seg_lo, seg_lo + nseg): X planes -> feat [nseg*T][Kp] (bias/scale folded); float32 rows
 // or split-f16 rows (split_f16.hpp; the padding columns are never written and must be zero)
 // Segments beyond 512 frames (8 s) take kernels written for any length (features_long_kernel, relpos_attn_long_kernel,
@@ -462,5 +465,22 @@ struct StreamOutputJob {
 bool stream_output_fits(const ResampleRatio& r);   // the tile's LDS (taps, span, output tile) fits a workgroup
 // one launch per STREAM_MULTI_MAX entries (S separated streams each); false: the LDS could not be reserved
 bool launch_stream_output_multi(const StreamOutputJob* e, int n, int S, hipStream_t s, int* launches);
+// The two wav edges of whole sessions at the capture rate (include/css_mi355_session_rate.h).
+// Ingest: a table launch over the rate sessions of a queue group -- entry r is launch_resample's job (the whole recording ->
+// dst [n_m][C], the session's slot of the sample buffer), and *level = max(*level, max |dst[m][:]| over m < n_peak) as float
+// bits: the word launch_pcm_peak_f32 makes of those samples.
+constexpr int SESSION_RATE_TABLE = 8;   // css_ctx::MAX_GROUP
+struct SessionIngestJob { ResampleJob r; int64_t n_peak; unsigned int* level; };
+bool session_ingest_fits(const ResampleRatio& r, int C);
+bool launch_session_ingest_multi(const SessionIngestJob* e, int n, hipStream_t s, int* launches);   // false: the LDS could not be reserved
+// Output: rows src [S][src_ld] of n model-rate samples -> dst [S][dst_ld] float32, n_m samples per row at up / down (dst and
+// dst_ld multiples of 16 bytes), and peak[k] = max(peak[k], max |dst[k][:]|) as float bits.
+struct SessionOutputJob {
+    const float* src; int64_t src_ld, n, n_m;
+    int up, down, half, P, P_ld; const float* tab;
+    float* dst; int64_t dst_ld;
+    unsigned int* peak;
+};
+bool launch_session_output(const SessionOutputJob& e, int S, hipStream_t s);   // false: the LDS could not be reserved
 
 }  // namespace css

@@ -15,6 +15,8 @@
 //                                   the streams' sample windows, and the inputs the next round still reads -> the other
 //                                   generation of the carried history
 //   resample_kernel                 a whole recording -> [n_out][C] (css_resample_host)
+//   session_ingest_resample_kernel  a table launch for the rate sessions of a queue group: recordings -> [n_model][C] and their
+//                                   levels (css_run*_rate); session_output_kernel: a session's waveforms -> the output rate
 //   stream_output_kernel            a table launch for the streams of a round that have an output format: [carried | the round's
 //                                   final samples] -> float32 or PCM16 at the playback rate (css_stream_set_output), the carried
 //                                   samples' other generation, the running peak and the clipped counts
@@ -155,8 +157,9 @@ __device__ __forceinline__ void piece_to_lds(const ResampleJob& e, int64_t j0, i
 
 // Outputs [m0 + t0, m0 + t0 + RS_TILE) of entry e, all channels: the taps and the span of inputs they read into LDS (float,
 // channel-major), then 64 consecutive outputs per wave and channel.  STREAM: dst[c * dst_ld + (m - m0)]; else dst[m * C + c].
-template <bool STREAM>
-__device__ __forceinline__ void resample_tile(const ResampleJob& e, int64_t t0, float* lds) {
+// PEAK: returns the thread's max |y| over its outputs m < n_peak, all channels (0 otherwise).
+template <bool STREAM, bool PEAK = false>
+__device__ __forceinline__ float resample_tile(const ResampleJob& e, int64_t t0, float* lds, int64_t n_peak = 0) {
     const int C = e.C, P = e.P, up = e.up, down = e.down;
     const int nt = (int)(e.n_m - t0 < RS_TILE ? e.n_m - t0 : RS_TILE);
     const int span_max = (RS_TILE * down + up - 1) / up + P + 1;
@@ -190,15 +193,19 @@ __device__ __forceinline__ void resample_tile(const ResampleJob& e, int64_t t0, 
     }
     __syncthreads();
     const int t = threadIdx.x;
-    if (t >= nt) return;
+    float pk = 0.0f;
+    if (t >= nt) return pk;
     const int nu = rem0 + t * down;
     const int a = nu / up;
     const float* tp = tab + (nu - a * up) * e.P_ld;
+    const bool scanned = PEAK && e.m0 + t0 + t < n_peak;
     for (int c = 0; c < C; ++c) {
         const float y = resample_sample(xs + c * row_ld, a, tp, P);
         if (STREAM) e.dst[(int64_t)c * e.dst_ld + t0 + t] = y;
         else e.dst[(e.m0 + t0 + t) * C + c] = y;
+        if (scanned) pk = fmaxf(pk, fabsf(y));
     }
+    return pk;
 }
 
 struct ResampleTable : Table<ResampleJob, STREAM_MULTI_MAX> {};
@@ -343,6 +350,82 @@ __global__ __launch_bounds__(RS_TILE) void stream_output_kernel(StreamOutputTabl
     }
 }
 
+// ---- whole sessions at the capture rate (include/css_mi355_session_rate.h; DESIGN.md 7 "N1 / N2 at the capture rate") ---------------------------------------
+// The ingest edge: resample_kernel as a table launch, blockIdx.z = a rate session of the queue group, blockIdx.x = tile of RS_TILE
+// model-rate samples of all channels; blocks past a session's last tile return at once.  The tile's outputs also give the
+// recording's level: the block's max |y| over the samples launch_pcm_peak_f32 would scan, one atomicMax per block and only when
+// it raises the word -- a maximum, so the word does not depend on the order.
+struct SessionIngestTable : Table<SessionIngestJob, SESSION_RATE_TABLE> {};
+
+// the block's maximum of m into *word (float bits of a non-negative value), by thread 0; w [RS_TILE / 64] is LDS
+__device__ __forceinline__ void block_peak_to(float m, float* w, unsigned int* word) {
+    const int tid = threadIdx.x;
+    m = wave_max_shfl(m);
+    if ((tid & 63) == 0) w[tid >> 6] = m;
+    __syncthreads();
+    if (tid == 0) {
+        float bm = w[0];
+        for (int i = 1; i < RS_TILE / 64; ++i) bm = fmaxf(bm, w[i]);
+        if (bm > __uint_as_float(__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) atomicMax(word, __float_as_uint(bm));
+    }
+}
+
+__global__ __launch_bounds__(RS_TILE) void session_ingest_resample_kernel(SessionIngestTable tab) {
+    extern __shared__ __attribute__((aligned(16))) float rs_lds[];
+    __shared__ float w_peak[RS_TILE / 64];
+    const SessionIngestJob e = tab.e[blockIdx.z];
+    const int64_t t0 = (int64_t)blockIdx.x * RS_TILE;
+    if (t0 >= e.r.n_m) return;
+    const float m = resample_tile<false, true>(e.r, t0, rs_lds, e.n_peak);
+    block_peak_to(m, w_peak, e.level);
+}
+
+// The output edge of ONE session: blockIdx.y = separated stream, blockIdx.x = tile of SO_TILE output samples.  stream_output_kernel
+// without the carried history, the sample formats and the clip counts: a tile stages the taps and its span of waveform row k
+// (zeros before sample 0 and behind sample n - 1), lane l of a pass takes output 256 pass + l, and the tile leaves through LDS so
+// that the stores are 16 bytes per lane.  The LDS bank argument is stream_output_kernel's (same layout, same swz).  The peak is
+// that of the OUTPUT samples (write_wav normalises what it writes), one atomicMax per block.
+__global__ __launch_bounds__(RS_TILE) void session_output_kernel(SessionOutputJob e) {
+    extern __shared__ __attribute__((aligned(16))) float rs_lds[];
+    __shared__ float w_peak[RS_TILE / 64];
+    const int k = blockIdx.y, tid = threadIdx.x;
+    const int up = e.up, down = e.down, P = e.P;
+    const int64_t t0 = (int64_t)blockIdx.x * SO_TILE;
+    if (t0 >= e.n_m) return;
+    const int nt = (int)(e.n_m - t0 < SO_TILE ? e.n_m - t0 : SO_TILE);
+    const float* __restrict__ src = e.src + (int64_t)k * e.src_ld;
+    float* taps = rs_lds;
+    float* row = rs_lds + up * e.P_ld;
+    float* otile = rs_lds + so_tile_at(up, down, P, e.P_ld);
+    for (int v = tid; v < up * e.P_ld; v += RS_TILE) taps[v] = e.tab[v];
+    // the tile's first output: i_hi = num / up, phase = num % up; output t of the tile adds t * down to num
+    const int64_t num = t0 * down + e.half;
+    const int64_t ihi0 = num / up;
+    const int rem0 = (int)(num - ihi0 * up);
+    const int span = (rem0 + (nt - 1) * down) / up + P;
+    const int64_t s0 = ihi0 - (P - 1);
+    for (int p = tid; p < span; p += RS_TILE) {
+        const int64_t s = s0 + p;
+        row[swz(p)] = (s >= 0 && s < e.n) ? src[s] : 0.f;
+    }
+    __syncthreads();
+    float m = 0.f;
+    for (int t = tid; t < nt; t += RS_TILE) {
+        const int nu = rem0 + t * down;
+        const int a = nu / up;
+        const float y = resample_sample(row, a, taps + (nu - a * up) * e.P_ld, P);
+        otile[t] = y;
+        m = fmaxf(m, fabsf(y));
+    }
+    __syncthreads();
+    // dst rows and tile starts are multiples of 16 bytes: whole vectors, then the tile's last elements one by one
+    float* d = e.dst + (int64_t)k * e.dst_ld + t0;
+    const int nv = nt / 4;
+    for (int v = tid; v < nv; v += RS_TILE) reinterpret_cast<uint4*>(d)[v] = reinterpret_cast<const uint4*>(otile)[v];
+    for (int t = nv * 4 + tid; t < nt; t += RS_TILE) d[t] = otile[t];
+    block_peak_to(m, w_peak, e.peak + k);
+}
+
 size_t so_lds_bytes(int up, int down, int P, int P_ld) { return ((size_t)so_tile_at(up, down, P, P_ld) + SO_TILE) * sizeof(float); }
 
 size_t lds_bytes(const ResampleJob& e) {
@@ -388,6 +471,42 @@ bool launch_stream_output_multi(const StreamOutputJob* e, int n, int S, hipStrea
         if (launches) ++*launches;
         return true;
     });
+}
+
+// (both session kernels keep a few static LDS words beside the dynamic tile)
+constexpr size_t SESSION_LDS_STATIC = 64;
+
+bool session_ingest_fits(const ResampleRatio& r, int C) {
+    ResampleJob e{};
+    e.up = r.up; e.down = r.down; e.P = r.P; e.P_ld = r.P_ld; e.C = C;
+    return lds_bytes(e) + SESSION_LDS_STATIC <= RS_LDS_MAX;
+}
+
+bool launch_session_ingest_multi(const SessionIngestJob* e, int n, hipStream_t s, int* launches) {
+    return for_each_table<SessionIngestTable>(e, n, [&](const SessionIngestTable& tab, int cnt) {
+        const int64_t most = table_max(tab, cnt, (int64_t)1, [](const SessionIngestJob& j) { return (j.r.n_m + RS_TILE - 1) / RS_TILE; });
+        const size_t lds = table_max(tab, cnt, (size_t)0, [](const SessionIngestJob& j) { return lds_bytes(j.r); });
+        if (lds + SESSION_LDS_STATIC > RS_LDS_MAX) return false;
+        if (lds > 65536 - SESSION_LDS_STATIC &&
+            hipFuncSetAttribute(reinterpret_cast<const void*>(session_ingest_resample_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)lds) != hipSuccess)
+            return false;
+        hipLaunchKernelGGL(session_ingest_resample_kernel, dim3((unsigned)most, 1, cnt), dim3(RS_TILE), lds, s, tab);
+        if (launches) ++*launches;
+        return true;
+    });
+}
+
+bool launch_session_output(const SessionOutputJob& e, int S, hipStream_t s) {
+    const size_t lds = so_lds_bytes(e.up, e.down, e.P, e.P_ld);
+    if (lds + SESSION_LDS_STATIC > RS_LDS_MAX) return false;
+    if (lds > 65536 - SESSION_LDS_STATIC &&
+        hipFuncSetAttribute(reinterpret_cast<const void*>(session_output_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
+            hipSuccess)
+        return false;
+    if (e.n_m > 0)
+        hipLaunchKernelGGL(session_output_kernel, dim3((unsigned)((e.n_m + SO_TILE - 1) / SO_TILE), (unsigned)S), dim3(RS_TILE), lds, s, e);
+    return true;
 }
 
 bool launch_resample(const ResampleJob& e, hipStream_t s) {

@@ -305,26 +305,53 @@ class _SessionOutput:
         return self.directory / f"sep_stream{i}.wav"
 
 
-def _separate_pcm16_session(separator, raw, cfg: CssCfg, device):
-    """The device-side wav edges: raw int16 planes up, peak-normalised PCM16 streams down."""
+def session_rates(sr: int, model_rate=None, output_rate=None):
+    """What the two keywords of css_inference / css_sessions mean for files at `sr`: (the model's rate, the rate of
+    sep_stream{i}.wav, the CssSessionRate of the rate calls or None when neither side converts).  ``model_rate=None``: the
+    files' rate is taken as the model's (the reference's behaviour); ``output_rate``: None = the model's rate, "input" = the
+    files' rate, or a rate in Hz."""
+    fs = int(sr) if model_rate is None else int(model_rate)
+    out_sr = fs if output_rate is None else (int(sr) if output_rate == "input" else int(output_rate))
+    if fs == int(sr) and out_sr == fs:
+        return fs, out_sr, None
+    return fs, out_sr, _lib.session_rate(None if fs == int(sr) else int(sr), None if out_sr == fs else out_sr, fs)
+
+
+def _separate_pcm16_session(separator, raw, cfg: CssCfg, device, model_rate=None, output_rate=None):
+    """The device-side wav edges: raw int16 planes up, peak-normalised PCM16 streams down -- with a
+    model or output rate other than the files', both edges also resample on the device (css_run_pcm16_rate)."""
     sr = raw[0][1]
+    fs, out_sr, rate = session_rates(sr, model_rate, output_rate)
     separator.to(device)
     desc = separator.desc
-    run_cfg = make_run_cfg(cfg, sr, len(raw), desc.frame_len, desc.frame_hop)
-    pcm16, _ = separator.handle.run_pcm16([r[0] for r in raw], run_cfg)
+    run_cfg = make_run_cfg(cfg, fs, len(raw), desc.frame_len, desc.frame_hop)
+    if rate is None:
+        pcm16, _ = separator.handle.run_pcm16([r[0] for r in raw], run_cfg)
+    else:
+        pcm16, _ = separator.handle.run_pcm16_rate([r[0] for r in raw], run_cfg, rate)
     mixture = raw[0][0].astype(np.float32) / np.float32(32768.0)
-    return sr, mixture, [pcm16[i] for i in range(pcm16.shape[0])], True
+    return sr, out_sr, mixture, [pcm16[i] for i in range(pcm16.shape[0])], True
 
 
-def _separate_float_session(separator, session, cfg: CssCfg, device):
+def _separate_float_session(separator, session, cfg: CssCfg, device, model_rate=None, output_rate=None):
     mixwav, sr = load_audio(session.wav_file_names, is_mc=session.is_mc)
     if cfg.slice_audio_for_debug:
         mixwav = mixwav[:, sr * 20:sr * 30, :]
-    wavs, _ = separate_and_stitch(mixwav, separator, sr, device, cfg, return_side_info=False)
-    return sr, mixwav[0, :, 0], wavs, False
+    fs, out_sr, rate = session_rates(sr, model_rate, output_rate)
+    if rate is None:
+        wavs, _ = separate_and_stitch(mixwav, separator, sr, device, cfg, return_side_info=False)
+    else:   # the float rate call (css_run_rate); cfg in seconds becomes frames at the model's rate
+        assert isinstance(separator, HipSeparator), "model_rate / output_rate need the HIP separator"
+        separator.to(device)
+        desc = separator.desc
+        run_cfg = make_run_cfg(cfg, fs, mixwav.shape[2], desc.frame_len, desc.frame_hop)
+        wav = separator.handle.run_rate(mixwav[0], run_cfg, rate)
+        wavs = [wav[k] for k in range(desc.num_spks)]
+    return sr, out_sr, mixwav[0, :, 0], wavs, False
 
 
-def css_inference(out_dir: str, models_dir: str, session, cfg: CssCfg, fetch_from_cache: bool, separator=None):
+def css_inference(out_dir: str, models_dir: str, session, cfg: CssCfg, fetch_from_cache: bool, separator=None,
+                  model_rate: Optional[int] = None, output_rate=None):
     """Applies CSS to one session row: the counterpart of css/css.py:51-107, same arguments, same files
     (``out_dir/css_inference/<session_id>/{input_mixture,sep_stream0..}.wav``), same returned Series (a copy of the
     session with ``sep_wav_file_names``).
@@ -332,7 +359,12 @@ def css_inference(out_dir: str, models_dir: str, session, cfg: CssCfg, fetch_fro
     ``separator``: a model already resident on the GPU (the session loop of pipeline.py keeps one per model kind); by
     default the checkpoint under ``models_dir`` is loaded for this call and released afterwards, as the reference does.
     Mono 16-bit PCM inputs -- what the NOTSOFAR recordings are -- take the device-side wav edges: int16 over PCIe,
-    scaling, peak normalisation and PCM16 encoding on the GPU."""
+    scaling, peak normalisation and PCM16 encoding on the GPU.
+
+    ``model_rate``: None takes the files' rate for the model's, as the reference does; ``16000`` converts files at another
+    supported rate (96 / 48 / 44.1 / 32 / 24 / 22.05 / 8 kHz) to the model's rate on the device, and the configuration's seconds
+    become frames at that rate.  ``output_rate``: None writes ``sep_stream{i}.wav`` at the model's rate, ``"input"`` at the
+    files' rate, an integer at that rate.  ``input_mixture.wav`` stays channel 0 as read, at the files' rate."""
     _LOG.info("Running CSS (Continuous Speech Separation)")
     result = session.copy()
     where = _SessionOutput.plan(out_dir, session, cfg, fetch_from_cache)
@@ -350,9 +382,9 @@ def css_inference(out_dir: str, models_dir: str, session, cfg: CssCfg, fetch_fro
         same_shape = raw and all(r is not None for r in raw) and len({(r[0].shape[0], r[1]) for r in raw}) == 1
         if same_shape:
             check_mic_count(len(raw), bool(session.is_mc))
-            sr, mixture, streams, encoded = _separate_pcm16_session(separator, raw, cfg, device)
+            sr, out_sr, mixture, streams, encoded = _separate_pcm16_session(separator, raw, cfg, device, model_rate, output_rate)
         else:
-            sr, mixture, streams, encoded = _separate_float_session(separator, session, cfg, device)
+            sr, out_sr, mixture, streams, encoded = _separate_float_session(separator, session, cfg, device, model_rate, output_rate)
     finally:
         if owned:
             separator.close()
@@ -363,9 +395,9 @@ def css_inference(out_dir: str, models_dir: str, session, cfg: CssCfg, fetch_fro
         path = where.stream_path(i)
         _LOG.info(f"CSS: saving separated wav to {path}")
         if encoded:
-            write_pcm16_samples(path, samples, sr)
+            write_pcm16_samples(path, samples, out_sr)
         else:
-            write_wav(path, samps=samples, sr=sr)
+            write_wav(path, samps=samples, sr=out_sr)
         names.append(str(path))
     result['sep_wav_file_names'] = names
     return result

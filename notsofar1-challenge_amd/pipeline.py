@@ -35,7 +35,7 @@ from typing import Dict, List, Optional
 import numpy as np
 
 from . import _lib
-from .css import CssCfg, _SessionOutput, css_inference, make_run_cfg
+from .css import CssCfg, _SessionOutput, css_inference, make_run_cfg, session_rates
 from .separator import _device_index, load_css_model
 from .wavio import check_mic_count, probe_wav_pcm16, read_pcm16_payload_into, write_pcm16_samples, write_wav
 
@@ -84,7 +84,7 @@ _POOL = _PinnedPool()   # process-wide: a second css_sessions call (or a long on
 
 class _Loaded:
     """One session decoded for the queue: its mono PCM16 planes in ONE page-locked block ([C][n] int16)."""
-    __slots__ = ("pos", "session", "where", "sr", "block", "planes", "out_block", "out16", "peaks", "fallback", "mixture_written")
+    __slots__ = ("pos", "session", "where", "sr", "out_sr", "block", "planes", "out_block", "out16", "peaks", "fallback", "mixture_written")
 
 
 def _decode_session(pos, session, where, cfg: CssCfg, pool: _PinnedPool) -> _Loaded:
@@ -121,7 +121,7 @@ def _write_session(ld: _Loaded, n_out: int, pool: _PinnedPool) -> List[str]:
     for i in range(ld.out16.shape[0]):
         path = ld.where.stream_path(i)
         _LOG.info(f"CSS: saving separated wav to {path}")
-        write_pcm16_samples(path, ld.out16[i, :n_out], ld.sr)
+        write_pcm16_samples(path, ld.out16[i, :n_out], ld.out_sr)
         names.append(str(path))
     if ld.mixture_written is not None:
         ld.mixture_written.result()          # (it reads channel 0 from the block that goes back to the pool here)
@@ -134,7 +134,8 @@ def _write_session(ld: _Loaded, n_out: int, pool: _PinnedPool) -> List[str]:
 def css_sessions(out_dir: str, models_dir: str, sessions_df, cfg: CssCfg, fetch_from_cache: bool = False,
                  rank: Optional[int] = None, world: Optional[int] = None, device=None,
                  queue_depth: int = 12, io_threads: int = 4, max_batch_segments: int = 256, linear_mode: str = "exact_f32",
-                 separators: Optional[Dict[bool, object]] = None, stats: Optional[dict] = None):
+                 separators: Optional[Dict[bool, object]] = None, stats: Optional[dict] = None,
+                 model_rate: Optional[int] = None, output_rate=None):
     """Run CSS on the sessions this rank owns; returns a DataFrame with those rows plus
     ``sep_wav_file_names`` -- every row is exactly what ``css_inference`` returns for it (css/css.py:51-107).
 
@@ -146,7 +147,11 @@ def css_sessions(out_dir: str, models_dir: str, sessions_df, cfg: CssCfg, fetch_
     to it); ``linear_mode``: see ``HipSeparator`` (default: the reference's float32 operand precision); ``separators``:
     models already resident on the GPU, ``{is_mc: HipSeparator}`` -- they are used instead of ``models_dir`` and NOT closed
     (a caller that runs the loop repeatedly, e.g. ``bench.py``'s ``sessions_from_files`` leg); ``stats``: a dict that receives
-    where the loop's wall time went (seconds: until the first session was on the queue, inside css_wait, after the last css_wait)."""
+    where the loop's wall time went (seconds: until the first session was on the queue, inside css_wait, after the last css_wait);
+    ``model_rate`` / ``output_rate``: see ``css_inference`` -- None / None is the reference's behaviour (the files' rate is taken as
+    the model's); with ``model_rate=16000`` sessions whose files are at another supported rate go through the queue's rate calls
+    (css_run_enqueue_pcm16_rate: both wav edges resampled on the device), and ``output_rate="input"`` writes the streams at the
+    files' rate."""
     import dataclasses
     import pandas as pd
     rank, world = _rank_world(rank, world)
@@ -185,7 +190,7 @@ def css_sessions(out_dir: str, models_dir: str, sessions_df, cfg: CssCfg, fetch_
             session = sessions_df.iloc[pos]
             where = _SessionOutput.plan(out_dir, session, cfg, fetch_from_cache)
             if where.shortcut is not None:
-                rows[pos] = css_inference(out_dir, models_dir, session, cfg, fetch_from_cache)
+                rows[pos] = css_inference(out_dir, models_dir, session, cfg, fetch_from_cache, model_rate=model_rate, output_rate=output_rate)
             else:
                 work.append((pos, session, where))
         ahead = max(2 * int(queue_depth), 2)
@@ -239,7 +244,8 @@ def css_sessions(out_dir: str, models_dir: str, sessions_df, cfg: CssCfg, fetch_
             if ld.fallback:
                 close_window()
                 _LOG.info(f"CSS [{rank}/{world}] session {ld.session.session_id} (float path)")
-                rows[ld.pos] = css_inference(out_dir, models_dir, ld.session, cfg, fetch_from_cache, separator=model_for(kind))
+                rows[ld.pos] = css_inference(out_dir, models_dir, ld.session, cfg, fetch_from_cache, separator=model_for(kind),
+                                             model_rate=model_rate, output_rate=output_rate)
                 k += 1
                 continue
             sep = model_for(kind)
@@ -248,14 +254,21 @@ def css_sessions(out_dir: str, models_dir: str, sessions_df, cfg: CssCfg, fetch_
                 cur = sep
             sep.to(device)
             h, desc = sep.handle, sep.desc
-            run_cfg = make_run_cfg(cfg, ld.sr, len(ld.planes), desc.frame_len, desc.frame_hop)
-            n_out = int(_lib.plan(desc, run_cfg, ld.planes[0].shape[0]).n_out)
+            fs, ld.out_sr, rate = session_rates(ld.sr, model_rate, output_rate)
+            run_cfg = make_run_cfg(cfg, fs, len(ld.planes), desc.frame_len, desc.frame_hop)
+            if rate is None:
+                n_out = int(_lib.plan(desc, run_cfg, ld.planes[0].shape[0]).n_out)
+            else:
+                n_out = h.session_rate_samples(run_cfg, rate, ld.planes[0].shape[0])[2]
             S = int(desc.num_spks)
             ld.out_block = pool.take(S * n_out * 2 + 64)
             ld.out16 = ld.out_block[64:64 + S * n_out * 2].view(np.int16).reshape(S, n_out)
             ld.peaks = ld.out_block[:4 * S].view(np.float32)
             _LOG.info(f"CSS [{rank}/{world}] session {ld.session.session_id}")
-            h.run_enqueue_pcm16(ld.planes, run_cfg, ld.out16, ld.peaks)
+            if rate is None:
+                h.run_enqueue_pcm16(ld.planes, run_cfg, ld.out16, ld.peaks)
+            else:
+                h.run_enqueue_pcm16_rate(ld.planes, run_cfg, rate, ld.out16, ld.peaks)
             ld.mixture_written = io.submit(_write_mixture, ld)
             if not t_first:
                 t_first = time.perf_counter() - t_start
