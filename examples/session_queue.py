@@ -3,18 +3,20 @@
 memory to separated waveforms in page-locked host memory; a session's PCIe legs run under its neighbours' kernels, and
 consecutive sessions share mask-estimator batches (up to max_batch_segments segments per batch).
 
-    python examples/session_queue.py [n_sessions] [--logmel]
+    python examples/session_queue.py [n_sessions] [--logmel [--windows]]
 
 --logmel: every session also hands Whisper its input (css_run_enqueue_handoff): the kept sample ranges and the normalised
-log-mel of each separated stream, computed on the GPU behind the session's waveforms; one session takes no waveforms at all."""
+log-mel of each separated stream, computed on the GPU behind the session's waveforms; one session takes no waveforms at all.
+--windows (with --logmel): the log-mel never leaves the GPU (css_run_enqueue_windows with mel_host = NULL): every session leaves
+Whisper's float16 encoder inputs [S, windows, 80, 3000] and the whole padded log-mel for seek-based decoding in torch tensors."""
 import importlib, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
 pkg = lambda n: importlib.import_module("notsofar1_challenge_amd." + n)
 css, _lib, sepmod, weights, synth = (pkg(n) for n in ("css", "_lib", "separator", "weights", "synth"))
 
-logmel = "--logmel" in sys.argv[1:]
-args = [a for a in sys.argv[1:] if a != "--logmel"]
+logmel, windows = "--logmel" in sys.argv[1:], "--windows" in sys.argv[1:]
+args = [a for a in sys.argv[1:] if a not in ("--logmel", "--windows")]
 n_sessions = int(args[0]) if args else 8
 desc = weights.ModelDesc.mc_v1()                                     # a real deployment: separator.load_css_model(dir)
 state = weights.apply_golden_recipe(weights.portable_state_dict(desc, 0))
@@ -44,7 +46,23 @@ audio = sum(p.shape[0] for p, _ in sessions) / 16000.0
 print(f"{n_sessions} sessions, {audio:.0f} s of 7-channel audio: queued {1e3 * queued:.1f} ms ({audio / queued:.0f} x real time), "
       f"one call per session {1e3 * sync:.1f} ms ({audio / sync:.0f} x real time); same bits: "
       f"{all(np.array_equal(v, r) for v, r in zip(views, refs))}")
-if logmel:
+if logmel and windows:
+    import torch
+    torch.zeros(1, device="cuda")                                    # (torch's own start-up on the GPU stays out of the timing)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    got = [h.run_enqueue_windows(pcm, run_cfg, None if k == 0 else out, width=3000, stride=3000, dtype="float16", mel_host=False, seek=True)
+           for k, (pcm, out) in enumerate(sessions)]
+    h.wait()                                                         # waveforms, ranges, counts and the tensors are valid now
+    handed = time.perf_counter() - t0
+    for k, (view, ho, win) in enumerate(got[:3]):
+        for spk in range(3):
+            n = int(win.n_windows[spk])                              # encoder inputs win.windows[spk, :n]; win.mel[spk][:, seek:seek + 3000]
+            print(f"  session {k} stream {spk}: {int(ho.n_frames[spk])} frames in {n} windows {tuple(win.windows[spk, :n].shape)} "
+                  f"{win.windows.dtype}, on {win.windows.device}; clamp at {float(win.window_max[spk]):.3f}")
+    print(f"with encoder windows on the device: {1e3 * handed:.1f} ms ({audio / handed:.0f} x real time); waveforms the same bits: "
+          f"{all(np.array_equal(v, r) for (v, _, _), r in list(zip(got, refs))[1:])}")
+elif logmel:
     t0 = time.perf_counter()
     got = [h.run_enqueue_handoff(pcm, run_cfg, None if k == 0 else out, n_mels=80, pad_frames=8, drop_silence=True)
            for k, (pcm, out) in enumerate(sessions)]

@@ -116,6 +116,13 @@ class CssSessionHandoffOut(C.Structure):
                 ("n_frames", C.c_void_p), ("n_ranges", C.c_void_p)]
 
 
+class CssSessionWindows(C.Structure):
+    """include/css_mi355_session_window.h: the encoder windows of a session, in the caller's device memory"""
+    _fields_ = [("width", C.c_int32), ("stride", C.c_int32), ("dtype", C.c_int32), ("reserved", C.c_int32),
+                ("windows_dev", C.c_void_p), ("ld", C.c_int64), ("cap_windows", C.c_int64), ("mel_dev", C.c_void_p),
+                ("mel_ld", C.c_int64), ("n_windows", C.c_void_p), ("window_max", C.c_void_p)]
+
+
 class CssStreamPreviewHandoff(C.Structure):
     _fields_ = [("p", CssStreamPreview), ("ho", C.POINTER(CssStreamHandoffOut)), ("first_frame", C.c_void_p)]
 
@@ -433,6 +440,17 @@ SESSION_RATE_SIGNATURES = {
                                              _P]),
     "css_session_rate_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
 }
+# the entry points include/css_mi355_session_window.h declares (encoder windows of whole sessions, written on the device), the
+# fourteenth table load() applies (named ..._BINDINGS: tests count the module's SIGNATURES... and ..._SIGNATURES tables)
+_SW_TAIL = [C.POINTER(CssStreamHandoffCfg), C.POINTER(CssSessionHandoffOut), C.POINTER(CssSessionWindows)]
+SESSION_WINDOW_BINDINGS = {
+    "css_session_window_bounds": (C.c_int, [C.POINTER(CssModelDesc), C.POINTER(CssRunCfg), C.POINTER(CssStreamHandoffCfg), C.c_int32,
+                                            C.c_int32, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "css_handoff_windows_all": (C.c_int, [_P, _P, C.c_int64] + _SW_TAIL),
+    "css_run_enqueue_windows": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.POINTER(CssRunCfg), _P, C.c_int64] + _SW_TAIL),
+    "css_run_enqueue_pcm16_windows": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.POINTER(CssRunCfg), _P, C.c_int64, _P] + _SW_TAIL),
+    "css_session_window_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+}
 ARRAY_MIN_MICS, ARRAY_MAX_MICS = 2, 8            # CSS_ARRAY_MIN_MICS, CSS_ARRAY_MAX_MICS
 SESSION_SCAN_CHUNK = 1024                        # CSS_SESSION_SCAN_CHUNK: the keep-scan kernel's step, in gate frames / sample blocks
 RESAMPLE_TILE = 256                              # output samples per block of the two resampling kernels (resample.hip RS_TILE)
@@ -481,7 +499,8 @@ def load() -> C.CDLL:
                               list(SIGNATURES_WINDOW.items()) + list(SIGNATURES_PRESENT.items()) +
                               list(SIGNATURES_FRONTEND.items()) + list(SIGNATURES_SESSION_HANDOFF.items()) +
                               list(SIGNATURES_STREAM_OUT.items()) + list(SIGNATURES_BACKEND.items()) +
-                              list(ARRAY_SIGNATURES.items()) + list(SESSION_RATE_SIGNATURES.items())):
+                              list(ARRAY_SIGNATURES.items()) + list(SESSION_RATE_SIGNATURES.items()) +
+                              list(SESSION_WINDOW_BINDINGS.items())):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -686,6 +705,73 @@ class SessionHandoff:
     @property
     def ranges(self):
         return [self.ranges_all[k, :int(self.n_ranges[k])] for k in range(self.S)]
+
+
+def session_window_bounds(desc, run_cfg: RunCfg, hcfg: CssStreamHandoffCfg, width: int, stride: int, n_samples: int):
+    """css_session_window_bounds: (frames, ranges, windows) per stream that suffice for a window session of `n_samples`"""
+    f, r, w = C.c_int64(), C.c_int32(), C.c_int64()
+    rc = load().css_session_window_bounds(C.byref(make_desc(desc)), C.byref(run_cfg.c), C.byref(hcfg), int(width), int(stride),
+                                          int(n_samples), C.byref(f), C.byref(r), C.byref(w))
+    if rc != CSS_OK:
+        raise CssError(rc, "css_session_window_bounds: bad configuration, width outside 1 .. 3000 or stride outside 1 .. width")
+    return int(f.value), int(r.value), int(w.value)
+
+
+class SessionWindows:
+    """The encoder windows of one session (css_mi355_session_window.h): the struct, the two page-locked count arrays and the
+    torch tensors the kernel writes.  ``windows``: the caller's CUDA tensor [S, W, n_mels, >= width] of the dtype (dense but for
+    the row pitch) or, with None, a new one of W = cap_windows; False: no windows.  ``mel``: likewise [S, n_mels, mel_ld] for the
+    whole padded log-mel, True for a new one of mel_ld columns, None / False for none.  After wait() / wait_sessions():
+    ``n_windows[k]``, ``window_max[k]``, and window w of speaker k is ``windows[k, w, :, :width]``."""
+
+    def __init__(self, device: int, S: int, n_mels: int, width: int, stride: int, dtype="float16", cap_windows: int = 0, windows=None,
+                 mel=None, mel_ld: int = 0, pinned: bool = True, fill=None):
+        import torch
+        from .stream import _window_out
+        if dtype not in WINDOW_DTYPES:
+            raise ValueError(f"windows are float32 or float16, got {dtype!r}")
+        dt = getattr(torch, dtype)
+        self.S, self.n_mels, self.width, self.stride, self.dtype = int(S), int(n_mels), int(width), int(stride), dtype
+        make = pinned_empty if pinned else (lambda shape, d: np.empty(shape, d))
+        self.n_windows = make((self.S,), np.int32)
+        self.window_max = make((self.S,), np.float32)
+        if fill is not None:
+            self.n_windows[...] = int(fill)
+            self.window_max[...] = fill
+
+        class _Dev:   # (what _window_out asks of a handle)
+            pass
+        dev = _Dev()
+        dev.device = int(device)
+        ld = 0
+        if windows is None:
+            W = max(int(cap_windows), 1)
+            windows = _window_out(dev, self.S * W, self.n_mels, self.width, dtype, None)[0].view(self.S, W, self.n_mels, self.width)
+        if windows is False:
+            windows = None
+        if windows is not None:
+            W = int(windows.shape[1]) if windows.dim() == 4 else 0
+            ld = windows.stride(2) if windows.dim() == 4 else 0
+            if (windows.dtype != dt or not windows.is_cuda or (windows.device.index or 0) != dev.device or windows.dim() != 4 or
+                    windows.shape[0] != self.S or windows.shape[2] != self.n_mels or windows.shape[3] < self.width or
+                    windows.stride(3) != 1 or ld < self.width or windows.stride(1) != self.n_mels * ld or
+                    windows.stride(0) != W * self.n_mels * ld):
+                raise ValueError(f"windows: a {dtype} tensor [{self.S}, W, {self.n_mels}, >= {self.width}] on cuda:{dev.device}, dense "
+                                 f"but for the row pitch")
+            cap_windows = W
+        if mel is True:
+            mel = torch.empty((self.S, self.n_mels, max(int(mel_ld), 1)), dtype=dt, device=f"cuda:{dev.device}")
+        if mel is False:
+            mel = None
+        if mel is not None:
+            if (mel.dtype != dt or not mel.is_cuda or (mel.device.index or 0) != dev.device or mel.dim() != 3 or
+                    mel.shape[0] != self.S or mel.shape[1] != self.n_mels or not mel.is_contiguous()):
+                raise ValueError(f"mel: a contiguous {dtype} tensor [{self.S}, {self.n_mels}, mel_ld] on cuda:{dev.device}")
+            mel_ld = int(mel.shape[2])
+        self.windows, self.mel = windows, mel
+        self.c = CssSessionWindows(self.width, self.stride, WINDOW_DTYPES[dtype], 0, windows.data_ptr() if windows is not None else None,
+                                   int(ld), int(cap_windows) if windows is not None else 0, mel.data_ptr() if mel is not None else None,
+                                   int(mel_ld) if mel is not None else 0, self.n_windows.ctypes.data, self.window_max.ctypes.data)
 
 
 def handoff_kept_ranges(act: np.ndarray, first_frame: int, n_known: int, pad_frames: int, a: int, b: int, n_out: int,
@@ -1441,6 +1527,100 @@ class Handle:
                                                              C.byref(hcfg), C.byref(ho.c)))
         self._queued_keep = getattr(self, "_queued_keep", []) + [(planes, out16, peaks, cfg, ho)]
         return out16[:, :pl.n_out], ho
+
+    # ---- encoder windows of whole sessions (include/css_mi355_session_window.h) ----
+    def session_window_bounds(self, cfg: RunCfg, n: int, width: int = 3000, stride: int = 3000, n_mels: int = 80, pad_frames: int = 8,
+                              drop_silence: bool = True):
+        """(frames, ranges, windows) per stream that suffice for a window session of `n` samples"""
+        return session_window_bounds(self.desc, cfg, handoff_cfg(n_mels, pad_frames, drop_silence), width, stride, n)
+
+    def _session_windows(self, frames, ranges, nw, hcfg, width, stride, dtype, mel_host, seek, handoff, windows, pinned=True,
+                         torch_sync=True):
+        """the hand-off arrays and the window description for the bounds (frames, ranges, nw), made where the caller gave none ->
+        (SessionHandoff, the CssSessionHandoffOut to pass, SessionWindows).  mel_host False: the struct's mel_host is NULL (the
+        SessionHandoff's mel_all is not written); seek: also the whole log-mel, frames + 3000 columns a row."""
+        S = int(self.desc.num_spks)
+        if handoff is None:
+            handoff = SessionHandoff(S, hcfg.n_mels, frames if mel_host else 1, ranges, pinned=pinned)
+        c = CssSessionHandoffOut(handoff.c.mel_host if mel_host else None, handoff.c.cap_frames if mel_host else 0,
+                                 handoff.c.ranges_host, handoff.c.cap_ranges, handoff.c.n_frames, handoff.c.n_ranges)
+        if windows is None:
+            windows = SessionWindows(self.device, S, hcfg.n_mels, width, stride, dtype, cap_windows=nw, mel=bool(seek),
+                                     mel_ld=frames + WINDOW_MAX_WIDTH, pinned=pinned)
+        if torch_sync:
+            import torch
+            torch.cuda.current_stream(self.device).synchronize()   # the caller's tensors: nothing of torch's still writes them
+        return handoff, c, windows
+
+    def handoff_windows_all(self, wav_ptr: int, wav_ld: int, width: int = 3000, stride: int = 3000, dtype="float16", n_mels: int = 80,
+                            pad_frames: int = 8, drop_silence: bool = True, mel_host: bool = True, seek: bool = False,
+                            out: Optional[SessionHandoff] = None, windows: Optional[SessionWindows] = None):
+        """After run_device: handoff_logmel_all plus the encoder windows on the device (css_handoff_windows_all) ->
+        (SessionHandoff, SessionWindows).  mel_host False: no log-mel goes to the host (``mel_all`` is not written)."""
+        hcfg = handoff_cfg(n_mels, pad_frames, drop_silence)
+        p = self.get_plan()
+        frames = int(p.n_out) // 160
+        ranges = (int(p.mix_frames) - 1) // (2 * int(pad_frames) + 3) + 1 if drop_silence else 1
+        ho, c, win = self._session_windows(frames, ranges, -(-frames // max(int(stride), 1)), hcfg, width, stride, dtype, mel_host, seek,
+                                           out, windows, pinned=False)
+        check(self.h, self.lib.css_handoff_windows_all(self.h, C.c_void_p(wav_ptr), int(wav_ld), C.byref(hcfg), C.byref(c), C.byref(win.c)))
+        return ho, win
+
+    def run_enqueue_windows(self, pcm: np.ndarray, cfg: RunCfg, out: Optional[np.ndarray], width: int = 3000, stride: int = 3000,
+                            dtype="float16", n_mels: int = 80, pad_frames: int = 8, drop_silence: bool = True, mel_host: bool = True,
+                            seek: bool = False, handoff: Optional[SessionHandoff] = None, windows: Optional[SessionWindows] = None,
+                            torch_sync: bool = True):
+        """run_enqueue_handoff plus the encoder windows, written on the device behind the session's log-mel
+        (css_run_enqueue_windows).  Returns (view of `out` or None, SessionHandoff, SessionWindows), valid after wait() /
+        wait_sessions().  mel_host False: no log-mel crosses PCIe; seek: also the whole padded log-mel (``windows.mel``).
+        torch's current stream is synchronised before the enqueue, so that nothing of torch's still writes the tensors; on the
+        legacy default stream that waits for the handle's main stream too (DESIGN.md section 7 N4 has the cost) -- a caller whose
+        tensors are idle passes torch_sync=False."""
+        assert pcm.dtype == np.float32 and pcm.flags.c_contiguous and pcm.ndim == 2
+        n, c = pcm.shape
+        p = plan(self.desc, cfg, n)
+        if out is not None:
+            assert out.dtype == np.float32 and out.ndim == 2 and out.shape[0] == self.desc.num_spks and out.shape[1] >= p.n_out \
+                and out.strides[1] == 4
+        hcfg = handoff_cfg(n_mels, pad_frames, drop_silence)
+        ho, hc, win = self._session_windows(*session_window_bounds(self.desc, cfg, hcfg, width, stride, n), hcfg, width, stride, dtype,
+                                            mel_host, seek, handoff, windows, torch_sync=torch_sync)
+        check(self.h, self.lib.css_run_enqueue_windows(self.h, _np_ptr(pcm), n, c, C.byref(cfg.c), None if out is None else _np_ptr(out),
+                                                       0 if out is None else out.strides[0] // 4, C.byref(hcfg), C.byref(hc),
+                                                       C.byref(win.c)))
+        self._queued_keep = getattr(self, "_queued_keep", []) + [(pcm, out, cfg, ho, win)]
+        return (None if out is None else out[:, :p.n_out]), ho, win
+
+    def run_enqueue_pcm16_windows(self, planes, cfg: RunCfg, out16: np.ndarray, peaks: Optional[np.ndarray] = None, width: int = 3000,
+                                  stride: int = 3000, dtype="float16", n_mels: int = 80, pad_frames: int = 8, drop_silence: bool = True,
+                                  mel_host: bool = True, seek: bool = False, handoff: Optional[SessionHandoff] = None,
+                                  windows: Optional[SessionWindows] = None, torch_sync: bool = True):
+        """run_enqueue_pcm16_handoff plus the encoder windows (css_run_enqueue_pcm16_windows): windows of the float waveforms
+        before peak normalisation.  Returns (view of `out16`, SessionHandoff, SessionWindows)."""
+        n = planes[0].shape[0]
+        for p in planes:
+            assert p.dtype == np.int16 and p.ndim == 1 and p.shape[0] == n and p.flags.c_contiguous
+        c = len(planes)
+        pl = plan(self.desc, cfg, n)
+        S = int(self.desc.num_spks)
+        assert out16.dtype == np.int16 and out16.ndim == 2 and out16.shape[0] == S and out16.shape[1] >= pl.n_out and out16.strides[1] == 2
+        assert peaks is None or (peaks.dtype == np.float32 and peaks.shape == (S,) and peaks.flags.c_contiguous)
+        ptrs = (C.c_void_p * c)(*[p.ctypes.data for p in planes])
+        hcfg = handoff_cfg(n_mels, pad_frames, drop_silence)
+        ho, hc, win = self._session_windows(*session_window_bounds(self.desc, cfg, hcfg, width, stride, n), hcfg, width, stride, dtype,
+                                            mel_host, seek, handoff, windows, torch_sync=torch_sync)
+        check(self.h, self.lib.css_run_enqueue_pcm16_windows(self.h, ptrs, n, c, C.byref(cfg.c), out16.ctypes.data_as(C.c_void_p),
+                                                             out16.strides[0] // 2,
+                                                             peaks.ctypes.data_as(C.c_void_p) if peaks is not None else None,
+                                                             C.byref(hcfg), C.byref(hc), C.byref(win.c)))
+        self._queued_keep = getattr(self, "_queued_keep", []) + [(planes, out16, peaks, cfg, ho, win)]
+        return out16[:, :pl.n_out], ho, win
+
+    def session_window_stats(self):
+        """(launches of the window kernel, sessions that asked for windows) on this handle so far"""
+        a, b = C.c_int64(), C.c_int64()
+        check(self.h, self.lib.css_session_window_stats(self.h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
 
     def resample(self, x, input_rate: int, fs: int = 16000) -> np.ndarray:
         """A recording at `input_rate` -> float32 [n_out, C] at `fs` on the device (css_resample_host): the samples a stream opened

@@ -142,10 +142,20 @@ struct SessState {
 
 // What css_run_enqueue_handoff / css_run_enqueue_pcm16_handoff ask for beside the waveforms (api_session_handoff.hip): the
 // caller's page-locked arrays by their DEVICE addresses -- the kernels of the hand-off store into them.
+// The encoder windows a session asks for on top (api_session_window.hip, include/css_mi355_session_window.h): the caller's device
+// memory, and its two count arrays by their DEVICE addresses.
+struct SessWindowReq {
+    bool on = false;
+    int32_t width = 0, stride = 0, f16 = 0;
+    void* windows = nullptr; int64_t ld = 0, cap_windows = 0;   // [S][cap_windows][n_mels][ld], or null
+    void* whole = nullptr; int64_t whole_ld = 0;                // [S][n_mels][whole_ld], or null
+    int32_t* n_windows = nullptr; float* window_max = nullptr;  // [S] each
+};
 struct SessHandoffReq {
     bool on = false;
     CssStreamHandoffCfg cfg{};
-    float* mel = nullptr; int64_t cap_frames = 0;       // [S][n_mels][cap_frames]
+    float* mel = nullptr; int64_t cap_frames = 0;       // [S][n_mels][cap_frames]; null (a window session may): no log-mel to the host
+    SessWindowReq win;
     int64_t* ranges = nullptr; int32_t cap_ranges = 0;  // [S][cap_ranges][2]
     int64_t* n_frames = nullptr; int32_t* n_ranges = nullptr;
 };
@@ -369,6 +379,7 @@ struct css_ctx : SessState {
     std::vector<std::unique_ptr<RateTab>> rate_tabs;
     DevBuf rate_out;
     int64_t rate_ingest_launches = 0, rate_output_launches = 0, rate_sessions = 0;
+    int64_t window_launches = 0, window_sessions = 0;   // css_session_window_stats: launches of the window kernel, sessions that asked for windows
     DevBuf stream_masks;   // api_stream.hip: the mask head's output for one estimator batch of streamed segments (never `masks`:
                            // the handle's own session keeps its bits between two pushes)
 
@@ -492,6 +503,16 @@ int session_output_on(css_ctx* h, const float* wav, int64_t wav_ld, const SessRa
 int session_handoff_prepare(css_ctx* h, const CssPlan& pl, const SessHandoffReq& r);
 // the five steps for the handle's current session on `st`, reading its gate bytes and the waveforms wav [S][wav_ld] in HBM
 int session_handoff_on(css_ctx* h, const float* wav, int64_t wav_ld, const SessHandoffReq& r, hipStream_t st);
+// The checks and the body of the two kinds of entry points, shared with api_session_window.hip (mel_optional: out->mel_host may
+// be NULL).  *_check refuse what the header says, with nothing allocated, queued or written; on CSS_OK *frames is the session's
+// frame bound.  session_handoff_all_run: `win` holds HOST addresses of its count arrays (pageable ones are staged like `out`'s).
+struct CssSessionHandoffOut;   // include/css_mi355_session_handoff.h
+int session_handoff_enqueue_check(css_ctx* h, int64_t n_samples, int32_t n_ch, const CssRunCfg* cfg, const CssStreamHandoffCfg* hcfg,
+                                  const CssSessionHandoffOut* out, bool mel_optional, SessHandoffReq* req, int64_t* n_out, int64_t* frames);
+int session_handoff_all_check(css_ctx* h, const float* wav_dev, int64_t wav_ld, const CssStreamHandoffCfg* hcfg,
+                              const CssSessionHandoffOut* out, bool mel_optional, int64_t* frames);
+int session_handoff_all_run(css_ctx* h, const float* wav_dev, int64_t wav_ld, const CssStreamHandoffCfg* hcfg, CssSessionHandoffOut* out,
+                            const SessWindowReq* win);
 void reduce_profile(css_ctx* h);
 
 

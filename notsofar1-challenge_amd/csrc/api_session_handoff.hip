@@ -5,7 +5,8 @@
 // handoff_mel_multi_kernel<false>: its frame counts come from device memory), normalisation (columns below the count only,
 // stored straight into the caller's page-locked arrays).  Bit for bit css_handoff_logmel's values per stream: the gather is a
 // copy, the product's elements do not depend on N, handoff_mel_tile is the one place of re re + im im and log10f, the maximum is
-// an order-free atomicMax, and the normalisation is handoff_norm_kernel's expression.
+// an order-free atomicMax, and the normalisation is handoff_norm_kernel's expression.  A window session (api_session_window.hip)
+// adds a sixth step, the encoder windows out of the raw mel rows, and may leave out the fifth (mel_host == NULL).
 #include "api_ctx.hpp"
 #include "../../include/css_mi355_session_handoff.h"
 
@@ -58,12 +59,16 @@ SessHandoffReq make_req(const CssStreamHandoffCfg& c, void* const dev[4], int64_
     return r;
 }
 
-bool out_complete(const CssSessionHandoffOut* o) { return o && o->mel_host && o->ranges_host && o->n_frames && o->n_ranges; }
+bool out_complete(const CssSessionHandoffOut* o, bool mel_optional) {
+    return o && (o->mel_host || mel_optional) && o->ranges_host && o->n_frames && o->n_ranges;
+}
+}  // namespace
 
-// what the two queued entry points check alike; on CSS_OK `req` is the request and `n_out` the session's samples per stream
-int check_enqueue(css_ctx* h, int64_t n_samples, int32_t n_ch, const CssRunCfg* cfg, const CssStreamHandoffCfg* hcfg,
-                  const CssSessionHandoffOut* out, SessHandoffReq* req, int64_t* n_out) {
-    if (!hcfg || !out_complete(out)) return fail(h, CSS_ERR_INVALID_ARG, "null argument");
+// what the queued entry points check alike; on CSS_OK `req` is the request, `n_out` the session's samples per stream and
+// `frames` its frame bound
+int session_handoff_enqueue_check(css_ctx* h, int64_t n_samples, int32_t n_ch, const CssRunCfg* cfg, const CssStreamHandoffCfg* hcfg,
+                                  const CssSessionHandoffOut* out, bool mel_optional, SessHandoffReq* req, int64_t* n_out, int64_t* frames) {
+    if (!hcfg || !out_complete(out, mel_optional)) return fail(h, CSS_ERR_INVALID_ARG, "null argument");
     if (h->split) return fail(h, CSS_ERR_STATE, "CSS_LINEAR_SPLIT_F16: css_wait may repeat a queued session, a hand-off session cannot be repeated");
     if (!h->fft512) return fail(h, CSS_ERR_INVALID_ARG, "the session hand-off needs frames of 512 samples at hop 256");
     if (!handoff_cfg_ok(hcfg)) return fail(h, CSS_ERR_INVALID_ARG, "n_mels must be 80 or 128, pad_frames in [0, 4096]");
@@ -71,17 +76,18 @@ int check_enqueue(css_ctx* h, int64_t n_samples, int32_t n_ch, const CssRunCfg* 
     int rc = check_run_args(h, n_samples, n_ch, cfg, &pl);
     if (rc != CSS_OK) return rc;
     const Bounds b = session_bounds(pl, *hcfg);
-    if (out->cap_frames < b.frames || out->cap_ranges < b.ranges)
+    if ((out->mel_host && out->cap_frames < b.frames) || out->cap_ranges < b.ranges)
         return fail(h, CSS_ERR_INVALID_ARG, "hand-off capacities below css_session_handoff_bounds: need " + std::to_string(b.frames) +
                                                 " frames, " + std::to_string(b.ranges) + " ranges");
-    void* dev[4] = {mapped_host(out->mel_host), mapped_host(out->ranges_host), mapped_host(out->n_frames), mapped_host(out->n_ranges)};
-    for (void* p : dev)
-        if (!p) return fail(h, CSS_ERR_INVALID_ARG, "the hand-off arrays of a queued session must be page-locked (css_host_alloc)");
-    *req = make_req(*hcfg, dev, out->cap_frames, out->cap_ranges);
+    void* dev[4] = {out->mel_host ? mapped_host(out->mel_host) : nullptr, mapped_host(out->ranges_host), mapped_host(out->n_frames),
+                    mapped_host(out->n_ranges)};
+    for (int i = out->mel_host ? 0 : 1; i < 4; ++i)
+        if (!dev[i]) return fail(h, CSS_ERR_INVALID_ARG, "the hand-off arrays of a queued session must be page-locked (css_host_alloc)");
+    *req = make_req(*hcfg, dev, out->mel_host ? out->cap_frames : 0, out->cap_ranges);
     *n_out = pl.n_out;
+    *frames = b.frames;
     return CSS_OK;
 }
-}  // namespace
 
 int session_handoff_prepare(css_ctx* h, const CssPlan& pl, const SessHandoffReq& r) {
     int rc;
@@ -121,7 +127,20 @@ int session_handoff_on(css_ctx* h, const float* wav, int64_t wav_ld, const SessH
     HandoffMel me{0, L.rows, e.n_new, e.st, dftm + SH_DFT_F + (r.cfg.n_mels == 80 ? 0 : SH_MEL80_F), r.cfg.n_mels, mel, L.rows,
                   nullptr, nullptr, 0, nullptr};
     launch_handoff_mel_multi(&me, 1, S, spec, L.ld, st);
-    launch_session_norm(e, mel, L.rows, r.cfg.n_mels, r.mel, r.cap_frames, L.rows - 3, st);
+    if (r.mel) launch_session_norm(e, mel, L.rows, r.cfg.n_mels, r.mel, r.cap_frames, L.rows - 3, st);
+    if (r.win.on) {   // the encoder windows, out of the raw rows before the next session reuses them
+        const SessWindowReq& w = r.win;
+        SessionWindows sw{};
+        sw.st = e.st; sw.mel = mel; sw.mel_ld = L.rows; sw.max_frames = L.rows - 3;
+        sw.S = S; sw.n_mels = r.cfg.n_mels; sw.width = w.width; sw.stride = w.stride; sw.f16 = w.f16;
+        sw.win = w.windows; sw.ld = w.ld; sw.cap_windows = w.cap_windows;
+        sw.n_win_jobs = w.windows ? (sw.max_frames + w.stride - 1) / w.stride : 0;
+        sw.whole = w.whole; sw.whole_ld = w.whole_ld;
+        sw.n_whole_jobs = w.whole ? (w.whole_ld + SESSION_WINDOW_CHUNK - 1) / SESSION_WINDOW_CHUNK : 0;
+        sw.n_windows_out = w.n_windows; sw.window_max_out = w.window_max;
+        launch_session_windows(sw, st);
+        h->window_launches += 1;
+    }
     HIPCHK(h, hipGetLastError());
     return CSS_OK;
 }
@@ -139,38 +158,58 @@ int css_session_handoff_bounds(const CssModelDesc* desc, const CssRunCfg* cfg, c
     return CSS_OK;
 }
 
-int css_handoff_logmel_all(css_handle_t h, const float* wav_dev, int64_t wav_ld, const CssStreamHandoffCfg* hcfg,
-                           CssSessionHandoffOut* out) {
+int session_handoff_all_check(css_ctx* h, const float* wav_dev, int64_t wav_ld, const CssStreamHandoffCfg* hcfg,
+                              const CssSessionHandoffOut* out, bool mel_optional, int64_t* frames) {
     CSS_DRAIN(h);
     int rc = check_session(h);
     if (rc) return rc;
-    if (!wav_dev || !hcfg || !out_complete(out)) return fail(h, CSS_ERR_INVALID_ARG, "null argument");
+    if (!wav_dev || !hcfg || !out_complete(out, mel_optional)) return fail(h, CSS_ERR_INVALID_ARG, "null argument");
     if (!h->fft512) return fail(h, CSS_ERR_INVALID_ARG, "the session hand-off needs frames of 512 samples at hop 256");
     if (!handoff_cfg_ok(hcfg)) return fail(h, CSS_ERR_INVALID_ARG, "n_mels must be 80 or 128, pad_frames in [0, 4096]");
     if (!h->perms_done) return fail(h, CSS_ERR_STATE, "no finished pass in this session");
     if (wav_ld < h->plan.n_out) return fail(h, CSS_ERR_INVALID_ARG, "wav_ld shorter than the streams");
-    const int S = h->d.num_spks, nm = hcfg->n_mels;
     const Bounds b = session_bounds(h->plan, *hcfg);
-    if (out->cap_frames < b.frames || out->cap_ranges < b.ranges)
+    if ((out->mel_host && out->cap_frames < b.frames) || out->cap_ranges < b.ranges)
         return fail(h, CSS_ERR_INVALID_ARG, "hand-off capacities below css_session_handoff_bounds: need " + std::to_string(b.frames) +
                                                 " frames, " + std::to_string(b.ranges) + " ranges");
+    *frames = b.frames;
+    return CSS_OK;
+}
+
+int session_handoff_all_run(css_ctx* h, const float* wav_dev, int64_t wav_ld, const CssStreamHandoffCfg* hcfg, CssSessionHandoffOut* out,
+                            const SessWindowReq* win) {
+    int rc;
+    const int S = h->d.num_spks, nm = hcfg->n_mels;
+    const Bounds b = session_bounds(h->plan, *hcfg);
+    const bool has_mel = out->mel_host != nullptr;
     HIPCHK(h, hipSetDevice(h->device));
     // page-locked arrays take the kernels' stores themselves; pageable ones get them through a page-locked staging block of
     // the bounds' size, copied out -- the written parts only -- after the synchronise
-    void* dev[4] = {mapped_host(out->mel_host), mapped_host(out->ranges_host), mapped_host(out->n_frames), mapped_host(out->n_ranges)};
-    const bool direct = dev[0] && dev[1] && dev[2] && dev[3];
+    void* dev[4] = {has_mel ? mapped_host(out->mel_host) : nullptr, mapped_host(out->ranges_host), mapped_host(out->n_frames),
+                    mapped_host(out->n_ranges)};
+    void* wdev[2] = {win ? mapped_host(win->n_windows) : nullptr, win ? mapped_host(win->window_max) : nullptr};
+    const bool direct = (dev[0] || !has_mel) && dev[1] && dev[2] && dev[3] && (!win || (wdev[0] && wdev[1]));
     const int64_t fr_ld = std::max<int64_t>(b.frames, 1);
-    const size_t mel_b = (size_t)S * nm * fr_ld * sizeof(float), reg_b = (size_t)S * b.ranges * 2 * sizeof(int64_t);
+    const size_t mel_b = has_mel ? (size_t)S * nm * fr_ld * sizeof(float) : 0, reg_b = (size_t)S * b.ranges * 2 * sizeof(int64_t);
+    const size_t cnt_b = (size_t)S * (sizeof(int64_t) + sizeof(int32_t));   // n_frames | n_ranges, then (a window call) n_windows | window_max
     SessHandoffReq req;
     if (direct) {
-        req = make_req(*hcfg, dev, out->cap_frames, out->cap_ranges);
+        req = make_req(*hcfg, dev, has_mel ? out->cap_frames : 0, out->cap_ranges);
     } else {
-        const size_t need = mel_b + reg_b + (size_t)S * (sizeof(int64_t) + sizeof(int32_t)) + 64;
+        const size_t need = mel_b + reg_b + cnt_b + (size_t)S * (sizeof(int32_t) + sizeof(float)) + 64;
         if (h->sh_pin.cap < need) HIPCHK(h, h->sh_pin.alloc(need));
         char* p = (char*)mapped_host(h->sh_pin.p);
         if (!p) return fail(h, CSS_ERR_HIP, "the staging block has no device address");
-        void* stage[4] = {p, p + mel_b, p + mel_b + reg_b, p + mel_b + reg_b + (size_t)S * sizeof(int64_t)};
-        req = make_req(*hcfg, stage, fr_ld, b.ranges);
+        void* stage[4] = {has_mel ? p : nullptr, p + mel_b, p + mel_b + reg_b, p + mel_b + reg_b + (size_t)S * sizeof(int64_t)};
+        req = make_req(*hcfg, stage, has_mel ? fr_ld : 0, b.ranges);
+        wdev[0] = p + mel_b + reg_b + cnt_b;
+        wdev[1] = p + mel_b + reg_b + cnt_b + (size_t)S * sizeof(int32_t);
+    }
+    if (win) {
+        req.win = *win;
+        req.win.on = true;
+        req.win.n_windows = (int32_t*)wdev[0];
+        req.win.window_max = (float*)wdev[1];
     }
     if ((rc = session_handoff_prepare(h, h->plan, req)) != CSS_OK) return rc;
     if ((rc = session_handoff_on(h, wav_dev, wav_ld, req, h->stream)) != CSS_OK) return rc;
@@ -185,21 +224,32 @@ int css_handoff_logmel_all(css_handle_t h, const float* wav_dev, int64_t wav_ld,
         for (int k = 0; k < S; ++k) {
             out->n_frames[k] = nf[k];
             out->n_ranges[k] = nr[k];
-            for (int m = 0; m < nm && nf[k] > 0; ++m)
+            for (int m = 0; m < nm && nf[k] > 0 && has_mel; ++m)
                 std::memcpy(out->mel_host + ((size_t)k * nm + m) * out->cap_frames, mel + ((size_t)k * nm + m) * fr_ld, (size_t)nf[k] * sizeof(float));
             if (nr[k] > 0)
                 std::memcpy(out->ranges_host + (size_t)k * out->cap_ranges * 2, reg + (size_t)k * b.ranges * 2, (size_t)nr[k] * 2 * sizeof(int64_t));
         }
+        if (win) {
+            std::memcpy(win->n_windows, p + mel_b + reg_b + cnt_b, (size_t)S * sizeof(int32_t));
+            std::memcpy(win->window_max, p + mel_b + reg_b + cnt_b + (size_t)S * sizeof(int32_t), (size_t)S * sizeof(float));
+        }
     }
     return CSS_OK;
+}
+
+int css_handoff_logmel_all(css_handle_t h, const float* wav_dev, int64_t wav_ld, const CssStreamHandoffCfg* hcfg,
+                           CssSessionHandoffOut* out) {
+    int64_t frames = 0;
+    const int rc = session_handoff_all_check(h, wav_dev, wav_ld, hcfg, out, false, &frames);
+    return rc != CSS_OK ? rc : session_handoff_all_run(h, wav_dev, wav_ld, hcfg, out, nullptr);
 }
 
 int css_run_enqueue_handoff(css_handle_t h, const float* pcm_host, int64_t n_samples, int32_t n_ch, const CssRunCfg* cfg,
                             float* wav_host, int64_t cap, const CssStreamHandoffCfg* hcfg, CssSessionHandoffOut* out) {
     if (!h || !pcm_host) return fail(h, CSS_ERR_INVALID_ARG, "null argument");
     SessHandoffReq req;
-    int64_t n_out = 0;
-    const int rc = check_enqueue(h, n_samples, n_ch, cfg, hcfg, out, &req, &n_out);
+    int64_t n_out = 0, frames = 0;
+    const int rc = session_handoff_enqueue_check(h, n_samples, n_ch, cfg, hcfg, out, false, &req, &n_out, &frames);
     if (rc != CSS_OK) return rc;
     return enqueue_impl(h, pcm_host, nullptr, n_samples, n_ch, cfg, wav_host, nullptr, nullptr, wav_host ? cap : n_out, &req);
 }
@@ -209,8 +259,8 @@ int css_run_enqueue_pcm16_handoff(css_handle_t h, const int16_t* const* planes_h
                                   const CssStreamHandoffCfg* hcfg, CssSessionHandoffOut* out) {
     if (!h || !planes_host || !wav_pcm16_host || n_samples < 1 || n_ch < 1) return fail(h, CSS_ERR_INVALID_ARG, "bad argument");
     SessHandoffReq req;
-    int64_t n_out = 0;
-    const int rc = check_enqueue(h, n_samples, n_ch, cfg, hcfg, out, &req, &n_out);
+    int64_t n_out = 0, frames = 0;
+    const int rc = session_handoff_enqueue_check(h, n_samples, n_ch, cfg, hcfg, out, false, &req, &n_out, &frames);
     if (rc != CSS_OK) return rc;
     return enqueue_impl(h, nullptr, planes_host, n_samples, n_ch, cfg, nullptr, wav_pcm16_host, peaks_host, cap, &req);
 }

@@ -632,6 +632,71 @@ __global__ __launch_bounds__(256) void session_norm_kernel(SessionHandoff e, con
     out[row * out_ld + j] = (fmaxf(mel[row * mel_ld + j], mx - 8.0f) + 4.0f) * 0.25f;
 }
 
+// One row of one job of the window kernel below: dst[c] for c < wd is the normalised raw frame row[s0 + c] where c < n and `fill`
+// behind.  Written as window_row writes a row: scalar stores up to dst's first 16-byte boundary, 16-byte stores from there, scalar
+// stores behind the last whole one.  A 16-byte group wholly below n is read through window_load16 (a window starts at any frame,
+// so the source has any alignment); the group that holds frame n - 1 and a source at the row's two ends are taken frame by frame.
+template <typename T>
+__device__ __forceinline__ void session_window_row(const float* __restrict__ row, int64_t row_len, int64_t s0, int64_t n, int64_t wd,
+                                                   T* __restrict__ dst, float lo, float fill, int lane) {
+    constexpr int V = WindowVec<T>::V;
+    auto norm = [&](float raw) { return (fmaxf(raw, lo) + 4.0f) * 0.25f; };   // session_norm_kernel's expression
+    auto one = [&](int64_t c) { return c < n ? norm(row[s0 + c]) : fill; };
+    const int64_t to_boundary = (int64_t)(((16 - ((uintptr_t)dst & 15)) & 15) / sizeof(T));
+    const int64_t head = to_boundary < wd ? to_boundary : wd;
+    const int64_t nvec = (wd - head) / V, tail = head + nvec * V;
+    for (int64_t c = lane; c < head; c += 64) WindowVec<T>::store(dst + c, one(c));
+    for (int64_t c = tail + lane; c < wd; c += 64) WindowVec<T>::store(dst + c, one(c));
+    for (int64_t g = lane; g < nvec; g += 64) {
+        const int64_t c = head + g * V;
+        float v[V];
+        if (c + V <= n && window_load16<V>(row, s0 + c, row_len, v)) {
+#pragma unroll
+            for (int i = 0; i < V; ++i) v[i] = norm(v[i]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < V; ++i) v[i] = one(c + i);
+        }
+        WindowVec<T>::store16(dst + c, v);
+    }
+}
+
+// The encoder windows and the whole log-mel of a queued session (kernels.hpp SessionWindows): a block has one job of one speaker,
+// a wave one band of it.  The frame count and the maximum are the keep-scan's and the mel kernel's words in device memory; the
+// grid covers the host's bounds, and what lies beyond the counts leaves at once.  No LDS, no barrier.
+__global__ __launch_bounds__(256) void session_window_kernel(SessionWindows e) {
+    const int k = blockIdx.z, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int m = blockIdx.y * SESSION_WINDOW_ROWS + wave;
+    const int64_t job = blockIdx.x;
+    const int64_t J = e.st[k].J < e.max_frames ? e.st[k].J : e.max_frames;
+    const int b = e.st[k].gmax;
+    const float mx = __int_as_float(b >= 0 ? b : b ^ 0x7fffffff);
+    if (job == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
+        e.n_windows_out[k] = (int32_t)((J + e.stride - 1) / e.stride);
+        e.window_max_out[k] = mx;
+    }
+    if (J <= 0 || m >= e.n_mels) return;
+    const float lo = mx - 8.0f, fill = (fmaxf(-10.0f, lo) + 4.0f) * 0.25f;
+    const float* __restrict__ row = e.mel + ((int64_t)k * e.n_mels + m) * e.mel_ld;
+    int64_t s0, n, wd, at;   // the job's first frame, frames, columns, and its first element in the output
+    if (job < e.n_win_jobs) {
+        s0 = job * e.stride;
+        n = J - s0 < e.width ? J - s0 : e.width;
+        if (n < 1) return;
+        wd = e.width;
+        at = (((int64_t)k * e.cap_windows + job) * e.n_mels + m) * e.ld;
+    } else {
+        s0 = (job - e.n_win_jobs) * SESSION_WINDOW_CHUNK;
+        wd = e.whole_ld - s0 < SESSION_WINDOW_CHUNK ? e.whole_ld - s0 : SESSION_WINDOW_CHUNK;
+        n = J - s0 < wd ? J - s0 : wd;
+        n = n < 0 ? 0 : n;
+        at = ((int64_t)k * e.n_mels + m) * e.whole_ld + s0;
+    }
+    void* out = job < e.n_win_jobs ? e.win : e.whole;
+    if (e.f16) session_window_row<__half>(row, e.mel_ld, s0, n, wd, (__half*)out + at, lo, fill, lane);
+    else session_window_row<float>(row, e.mel_ld, s0, n, wd, (float*)out + at, lo, fill, lane);
+}
+
 void launch_session_keep_scan(const SessionHandoff& e, hipStream_t s) {
     hipLaunchKernelGGL(session_keep_scan_kernel, dim3(e.S), dim3(256), 0, s, e);
 }
@@ -643,6 +708,13 @@ void launch_session_norm(const SessionHandoff& e, const float* mel, int64_t mel_
                          hipStream_t s) {
     if (rows <= 0) return;
     hipLaunchKernelGGL(session_norm_kernel, dim3((unsigned)((rows + 255) / 256), n_mels, e.S), dim3(256), 0, s, e, mel, mel_ld, n_mels, out, out_ld);
+}
+void launch_session_windows(const SessionWindows& e, hipStream_t s) {
+    static_assert(SESSION_WINDOW_ROWS == 4 && SESSION_WINDOW_CHUNK % 8 == 0, "a wave per band; chunks of whole 16-byte groups");
+    const int64_t jobs = e.n_win_jobs + e.n_whole_jobs;
+    if (jobs < 1) return;
+    hipLaunchKernelGGL(session_window_kernel, dim3((unsigned)jobs, (unsigned)((e.n_mels + SESSION_WINDOW_ROWS - 1) / SESSION_WINDOW_ROWS), e.S),
+                       dim3(256), 0, s, e);
 }
 
 }  // namespace css

@@ -282,6 +282,24 @@ void launch_session_gather(const SessionHandoff& e, const float* wav, int64_t wa
 void launch_session_norm(const SessionHandoff& e, const float* mel, int64_t mel_ld, int n_mels, float* out, int64_t out_ld, int64_t rows,
                          hipStream_t s);
 
+// Encoder windows of a QUEUED session (include/css_mi355_session_window.h, api_session_window.hip): one launch behind the mel
+// kernel, reading the raw rows mel [S][n_mels][mel_ld] and the counts st[k].J / st[k].gmax from device memory.  A block has one
+// JOB of one speaker and SESSION_WINDOW_ROWS bands (one wave per band).  Jobs 0 .. n_win_jobs - 1 are windows: window w holds the
+// frames from w stride, n = min(width, J - w stride) of them, and leaves at once when n < 1.  The jobs behind them are chunks of
+// SESSION_WINDOW_CHUNK columns of the whole log-mel row (`whole`, every column below whole_ld: the frames, then the fill); they
+// leave when J == 0.  Session normalisation: clamp at gmax - 8, (x + 4) / 4, fill = what -10 takes under it.
+constexpr int SESSION_WINDOW_ROWS = 4;
+constexpr int SESSION_WINDOW_CHUNK = 4096;              // (a multiple of the 16-byte store: chunks keep the row's alignment)
+struct SessionWindows {
+    const HandoffState* st; const float* mel; int64_t mel_ld, max_frames;   // J is taken as at most max_frames (the host's bound)
+    int32_t S, n_mels, width, stride, f16;
+    int64_t n_win_jobs, n_whole_jobs;                   // the grid's jobs: ceil(max_frames / stride) or 0; ceil(whole_ld / CHUNK) or 0
+    void* win; int64_t ld, cap_windows;                 // [S][cap_windows][n_mels][ld] of the dtype, or null
+    void* whole; int64_t whole_ld;                      // [S][n_mels][whole_ld] of the dtype, or null
+    int32_t* n_windows_out; float* window_max_out;      // the caller's [S] each (device addresses)
+};
+void launch_session_windows(const SessionWindows& e, hipStream_t s);
+
 // Whisper encoder windows (include/css_mi355_window.h, css_mi355_present_window.h): at most n_frames frames of one speaker counted
 // back from the end of a preview's provisional frames -- the ring's frames [a, J), then the last provisional ones -- clamped at their
 // own maximum - 8, (x + 4) / 4, padded to `width` columns with the value a frame of digital zeros takes, as float32 or float16 into

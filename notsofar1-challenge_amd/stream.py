@@ -95,6 +95,32 @@ def whisper_window(raw: np.ndarray, width: int = 3000, dtype="float16") -> np.nd
     return out.astype(dt)
 
 
+def session_window_fill(M) -> np.float32:
+    """what a frame of digital zeros (log10(1e-10) = -10) takes under a clamp at the maximum M: (max(-10, M - 8) + 4) / 4 in float32"""
+    return (np.maximum(np.float32(-10.0), np.float32(M) - np.float32(8.0)) + np.float32(4.0)) * np.float32(0.25)
+
+
+def session_windows(mel: np.ndarray, M, width: int = 3000, stride: int = 3000, dtype="float16") -> np.ndarray:
+    """The numpy statement of css_run_enqueue_windows for one speaker: ``mel`` [n_mels, J] is the session hand-off's normalised
+    log-mel and ``M`` the maximum its clamp used -> [ceil(J / stride), n_mels, width].  Window w holds columns
+    ``mel[:, w * stride : w * stride + width]``; the columns behind them hold ``session_window_fill(M)``; float16 is ``astype`` of
+    the float32 values.  (One window over raw frames: ``session_windows(whisper_normalize(raw), raw.max(), width, width)[0]`` is
+    ``whisper_window(raw, width)``.)"""
+    mel = np.asarray(mel, dtype=np.float32)
+    dt = np.dtype(dtype)
+    if dt not in (np.dtype(np.float32), np.dtype(np.float16)):
+        raise ValueError(f"windows are float32 or float16, got {dt}")
+    if mel.ndim != 2 or not 1 <= width <= 3000 or not 1 <= stride <= width:
+        raise ValueError(f"expected [n_mels, J] frames, width in 1 .. 3000 and stride in 1 .. width, got {mel.shape}, {width}, {stride}")
+    J = mel.shape[1]
+    n = -(-J // int(stride))
+    out = np.full((n, mel.shape[0], int(width)), session_window_fill(M), np.float32)
+    for w in range(n):
+        part = mel[:, w * stride:w * stride + width]
+        out[w, :, :part.shape[1]] = part
+    return out.astype(dt)
+
+
 def _torch():
     import torch
     return torch

@@ -10,7 +10,15 @@ Arms, alternated inside one process (P A B C P A B C ...), the host clock around
 Every arm's outputs are compared for bit equality at the sizes timed (waveforms of P, A, B; log-mel and ranges of A, B, C).
 
     python tools/queue_handoff_bench.py [--sessions 24] [--rounds 5] [--json OUT]
-    --trace-arm B --rounds 1     one arm only, for a separate kernel-trace run of the profiler"""
+    --trace-arm B --rounds 1     one arm only, for a separate kernel-trace run of the profiler
+
+--windows: the encoder windows of include/css_mi355_session_window.h instead (float16, width = stride = 3000), arms H P W W0:
+  H   run_enqueue_handoff x N, wait (arm B above): the floor
+  P   the route without that header: H, then per session stream.session_windows in numpy and torch.from_numpy(...).cuda()
+  W   run_enqueue_windows x N with the log-mel to the host as well, wait
+  W0  the same with mel_host = NULL: no log-mel crosses PCIe
+  W0n W0 with torch_sync=False: without the synchronise of torch's current stream before every enqueue
+Windows of P, W and W0 are compared for bit equality.  --trace-arm W0 --rounds 1: one arm only, for a kernel-trace run."""
 import argparse
 import importlib
 import json
@@ -33,7 +41,8 @@ def main():
     ap.add_argument("--seconds", type=float, default=60.0)
     ap.add_argument("--distinct", type=int, default=4, help="distinct recordings the sessions cycle through")
     ap.add_argument("--max-batch", type=int, default=256)
-    ap.add_argument("--trace-arm", default=None, choices=("P", "A", "B", "C"))
+    ap.add_argument("--trace-arm", default=None, choices=("P", "A", "B", "C", "H", "W", "W0", "W0n"))
+    ap.add_argument("--windows", action="store_true", help="the encoder-window arms H P W W0")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     import torch
@@ -50,6 +59,8 @@ def main():
     n_out = int(L.plan(desc, run_cfg, n).n_out)
     frames, ranges = L.session_handoff_bounds(desc, run_cfg, L.handoff_cfg(**HANDOFF), n)
     pcm = [recs[i % a.distinct] for i in range(N)]
+    if a.windows:
+        return window_arms(a, sep, run_cfg, pcm, n, n_out)
     wavs = {arm: [L.pinned_empty((S, n_out), np.float32) for _ in range(N)] for arm in "PAB"}
     hos = {arm: [L.SessionHandoff(S, nm, frames, ranges) for _ in range(N)] for arm in "BC"}
     dev_pcm = [torch.from_numpy(np.asarray(r)).cuda() for r in recs]
@@ -107,6 +118,95 @@ def main():
         out["B_over_A"] = med["B"] / med["A"]
         out["B_minus_P_ms"] = med["B"] - med["P"]
         out["C_minus_P_ms"] = med["C"] - med["P"]
+    print(json.dumps(out))
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(out, f, indent=1)
+    sep.close()
+
+
+def window_arms(a, sep, run_cfg, pcm, n, n_out):
+    import torch
+    L, ST = pkg("_lib"), pkg("stream")
+    h, desc, N = sep.handle, sep.desc, a.sessions
+    S, nm, width = int(desc.num_spks), HANDOFF["n_mels"], 3000
+    frames, ranges, nw = L.session_window_bounds(desc, run_cfg, L.handoff_cfg(**HANDOFF), width, width, n)
+    wavs = {arm: [L.pinned_empty((S, n_out), np.float32) for _ in range(N)] for arm in ("H", "W", "W0", "W0n")}
+    hos = {arm: [L.SessionHandoff(S, nm, frames, ranges) for _ in range(N)] for arm in ("H", "W", "W0", "W0n")}
+    wins = {arm: [L.SessionWindows(0, S, nm, width, width, "float16", cap_windows=nw) for _ in range(N)] for arm in ("W", "W0", "W0n")}
+    up_p = [None] * N
+
+    def arm_h():
+        for i in range(N):
+            h.run_enqueue_handoff(pcm[i], run_cfg, wavs["H"][i], handoff=hos["H"][i], **HANDOFF)
+        h.wait()
+
+    def arm_p():
+        arm_h()
+        for i in range(N):
+            ho, per = hos["H"][i], []
+            for k in range(S):
+                # (the host never learns M_k; the fill follows from the largest normalised value, (M + 4) / 4 -> M)
+                mel = ho.mel[k]
+                M = np.float32(mel.max()) * np.float32(4.0) - np.float32(4.0) if mel.shape[1] else np.float32(0)
+                w = ST.session_windows(mel, M, width, width, "float16")
+                per.append(np.concatenate([w, np.zeros((nw - w.shape[0], nm, width), np.float16)]))
+            up_p[i] = torch.from_numpy(np.stack(per)).cuda()
+        torch.cuda.synchronize()
+
+    def arm_w(arm):
+        for i in range(N):
+            h.run_enqueue_windows(pcm[i], run_cfg, wavs[arm][i], width, width, "float16", mel_host=arm == "W", handoff=hos[arm][i],
+                                  windows=wins[arm][i], torch_sync=arm != "W0n", **HANDOFF)
+        h.wait()
+
+    arms = {"H": arm_h, "P": arm_p, "W": lambda: arm_w("W"), "W0": lambda: arm_w("W0"), "W0n": lambda: arm_w("W0n")}
+    order = [a.trace_arm] if a.trace_arm else ["H", "P", "W", "W0", "W0n"]
+    for arm in order:
+        arms[arm]()
+    times = {arm: [] for arm in order}
+    for _ in range(a.rounds):
+        for arm in order:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            arms[arm]()
+            times[arm].append((time.perf_counter() - t0) * 1e3 / N)
+    equal = None
+    if not a.trace_arm:
+        equal = True
+        for i in range(N):
+            for k in range(S):
+                nk = int(wins["W"][i].n_windows[k])
+                ref = up_p[i][k, :nk].cpu().numpy()
+                equal = equal and nk == int(wins["W0"][i].n_windows[k]) == -(-int(hos["H"][i].n_frames[k]) // width)
+                got = {arm: wins[arm][i].windows[k, :nk].cpu().numpy() for arm in ("W", "W0", "W0n")}
+                equal = equal and np.array_equal(got["W"], got["W0"]) and np.array_equal(got["W"], got["W0n"])
+                for w in range(nk):   # (P's fill comes from a maximum recovered in float32: the frames are compared, not the padding)
+                    nv = min(width, int(hos["H"][i].n_frames[k]) - w * width)
+                    equal = equal and np.array_equal(got["W"][w, :, :nv], ref[w, :, :nv])
+                equal = equal and np.array_equal(hos["W"][i].mel[k], hos["H"][i].mel[k])
+            equal = equal and all(np.array_equal(wavs[arm][i], wavs["H"][i]) for arm in ("W", "W0", "W0n"))
+    src = hos[order[-1] if order[-1] != "P" else "H"]
+    mean_frames = float(np.mean([int(src[i].n_frames[k]) for i in range(N) for k in range(S)]))
+    mean_windows = float(np.mean([-(-int(src[i].n_frames[k]) // width) for i in range(N) for k in range(S)]))
+    up, wav_b, mel_b = n * 7 * 4, S * n_out * 4, S * nm * mean_frames * 4
+    win_b = S * mean_windows * nm * width * 2
+    small = S * (ranges * 16 + 12)
+    out = dict(workload=f"{a.seconds:g} s x 7 channels, mc_v1, activity_th 0.3, {N} sessions per window, {a.rounds} windows per arm, "
+                        f"{a.distinct} distinct recordings, hand-off {HANDOFF}, float16 windows of width = stride = {width}",
+               ms_per_session={arm: dict(median=float(np.median(t)), min=float(np.min(t)), max=float(np.max(t)), all=[round(v, 4) for v in t])
+                               for arm, t in times.items()},
+               outputs_bit_equal=equal, mean_kept_frames_per_stream=mean_frames, mean_windows_per_stream=mean_windows,
+               frame_bound=frames, window_bound=nw, window_bytes_written_per_session=win_b,
+               pcie_bytes_per_session=dict(H=up + wav_b + mel_b + small, P=up + wav_b + mel_b + small + S * nw * nm * width * 2,
+                                           W=up + wav_b + mel_b + small + S * 8, W0=up + wav_b + small + S * 8, W0n=up + wav_b + small + S * 8))
+    if not a.trace_arm:
+        med = {arm: out["ms_per_session"][arm]["median"] for arm in order}
+        out["W0_minus_H_ms"] = med["W0"] - med["H"]
+        out["W0n_minus_H_ms"] = med["W0n"] - med["H"]
+        out["W_minus_H_ms"] = med["W"] - med["H"]
+        out["P_minus_H_ms"] = med["P"] - med["H"]
+        out["H_spread_ms"] = out["ms_per_session"]["H"]["max"] - out["ms_per_session"]["H"]["min"]
     print(json.dumps(out))
     if a.json:
         with open(a.json, "w") as f:
