@@ -209,6 +209,20 @@ class CssPcmEdgesDesc(C.Structure):
                [(n, C.c_int64) for n in ("n", "n_pad", "i_lo", "i_hi", "count", "out_ld", "in_elems", "out_elems")]
 
 
+class CssRateIngestJob(C.Structure):            # include/css_mi355_rate_kernels.h
+    _fields_ = [(n, C.c_int32) for n in ("up", "down", "C", "is_int16", "src_offset", "H", "dst_col", "has_hist_out")] + \
+               [("level_before", C.c_uint32), ("level_after", C.c_uint32)] + \
+               [(n, C.c_int64) for n in ("plane_ld", "n", "N0", "m0", "n_m", "dst_ld", "n_peak", "src_elems", "hist_elems", "dst_floats")] + \
+               [(n, C.c_void_p) for n in ("src", "hist_in", "hist_out", "dst")]
+
+
+class CssRateOutputJob(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("up", "down", "H", "pcm16", "has_hist_out", "reserved")] + \
+               [("gain", C.c_float), ("reserved_f", C.c_float)] + \
+               [(n, C.c_int64) for n in ("src_ld", "n", "N0", "m0", "n_m", "dst_ld", "src_floats", "hist_elems", "dst_elems")] + \
+               [(n, C.c_void_p) for n in ("src", "hist_in", "hist_out", "dst", "peak", "clipped")]
+
+
 class CssMvdrSet(C.Structure):                  # include/css_mi355_backend.h
     _fields_ = [(n, C.c_int64) for n in ("seg_lo", "nseg", "scm_off", "bfw_off")]
 
@@ -451,6 +465,13 @@ SESSION_WINDOW_BINDINGS = {
     "css_run_enqueue_pcm16_windows": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.POINTER(CssRunCfg), _P, C.c_int64, _P] + _SW_TAIL),
     "css_session_window_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
 }
+# the entry points include/css_mi355_rate_kernels.h declares (the table and session kernels of csrc/resample.hip on caller data), the
+# fifteenth table load() applies (a ..._BINDINGS table, as the one above)
+RATE_KERNEL_BINDINGS = {
+    "css_rate_ingest_host": (C.c_int, [_P, C.c_int32, C.POINTER(CssRateIngestJob), C.c_int32]),
+    "css_rate_output_host": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(CssRateOutputJob), C.c_int32]),
+}
+RATE_KERNEL_JOBS = 64                            # CSS_RATE_KERNEL_JOBS
 ARRAY_MIN_MICS, ARRAY_MAX_MICS = 2, 8            # CSS_ARRAY_MIN_MICS, CSS_ARRAY_MAX_MICS
 SESSION_SCAN_CHUNK = 1024                        # CSS_SESSION_SCAN_CHUNK: the keep-scan kernel's step, in gate frames / sample blocks
 RESAMPLE_TILE = 256                              # output samples per block of the two resampling kernels (resample.hip RS_TILE)
@@ -500,7 +521,7 @@ def load() -> C.CDLL:
                               list(SIGNATURES_FRONTEND.items()) + list(SIGNATURES_SESSION_HANDOFF.items()) +
                               list(SIGNATURES_STREAM_OUT.items()) + list(SIGNATURES_BACKEND.items()) +
                               list(ARRAY_SIGNATURES.items()) + list(SESSION_RATE_SIGNATURES.items()) +
-                              list(SESSION_WINDOW_BINDINGS.items())):
+                              list(SESSION_WINDOW_BINDINGS.items()) + list(RATE_KERNEL_BINDINGS.items())):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -1256,6 +1277,77 @@ class Handle:
         check(self.h, self.lib.css_pcm_edges_host(self.h, C.byref(d), _np_ptr(src), None if out is None else _np_ptr(out),
                                                   None if peak is None else _np_ptr(peak)))
         return out, peak
+
+    # ---- the table and session kernels of csrc/resample.hip on caller data (include/css_mi355_rate_kernels.h;
+    #      tests/test_hip_rate_kernels.py).  A job is a dict of the descriptor's fields; its arrays are the WHOLE allocations and
+    #      the ones a launch writes are copied first and returned as the launch left them.
+    def rate_ingest(self, form: int, jobs):
+        """launch_stream_ingest_resample_multi (0) / launch_session_ingest_multi (1) (css_rate_ingest_host).  Per job: src (int16 or
+        float32), hist_in, dst, hist_out (None: not passed) and the scalar fields.  Returns [(dst, hist_out, level_after)]."""
+        tab = (CssRateIngestJob * len(jobs))()
+        keep = []
+        for d, j in zip(tab, jobs):
+            j = dict(j)
+            src = np.ascontiguousarray(j.pop("src")).reshape(-1)
+            if src.dtype not in (np.int16, np.float32):
+                raise ValueError("src is int16 or float32")
+            hin = j.pop("hist_in", None)
+            hin = np.zeros(0, np.float32) if hin is None else np.ascontiguousarray(hin, dtype=np.float32).reshape(-1)
+            hout = j.pop("hist_out", None)
+            hout = None if hout is None else np.ascontiguousarray(hout, dtype=np.float32).reshape(-1).copy()
+            dst = np.ascontiguousarray(j.pop("dst"), dtype=np.float32).reshape(-1).copy()
+            if hout is not None and hout.size != hin.size:
+                raise ValueError("hist_out has hist_in's size")
+            for k, v in j.items():
+                setattr(d, k, int(v))
+            d.is_int16, d.has_hist_out = int(src.dtype == np.int16), int(hout is not None)
+            d.src_elems, d.hist_elems, d.dst_floats = src.size, hin.size, dst.size
+            d.src, d.hist_in, d.dst = src.ctypes.data, hin.ctypes.data, dst.ctypes.data
+            d.hist_out = None if hout is None else hout.ctypes.data
+            keep.append((src, hin, hout, dst))
+        rc = self.lib.css_rate_ingest_host(self.h, int(form), tab, len(jobs))
+        return self._rate_left(rc, [(k[3], k[2], int(d.level_after)) for d, k in zip(tab, keep)])
+
+    def rate_output(self, form: int, S: int, jobs):
+        """launch_stream_output_multi (0) / launch_session_output (1) (css_rate_output_host).  Per job: src, hist_in, dst (float32, or
+        int16 with pcm16), hist_out (None: not passed), peak [S] uint32, clipped [S] uint64 and the scalar fields.
+        Returns [(dst, hist_out, peak, clipped)]."""
+        tab = (CssRateOutputJob * len(jobs))()
+        keep = []
+        for d, j in zip(tab, jobs):
+            j = dict(j)
+            src = np.ascontiguousarray(j.pop("src"), dtype=np.float32).reshape(-1)
+            hin = j.pop("hist_in", None)
+            hin = np.zeros(0, np.float32) if hin is None else np.ascontiguousarray(hin, dtype=np.float32).reshape(-1)
+            hout = j.pop("hist_out", None)
+            hout = None if hout is None else np.ascontiguousarray(hout, dtype=np.float32).reshape(-1).copy()
+            dst = np.ascontiguousarray(j.pop("dst")).reshape(-1).copy()
+            peak = np.ascontiguousarray(j.pop("peak", np.zeros(S, np.uint32)), dtype=np.uint32).reshape(-1).copy()
+            clipped = np.ascontiguousarray(j.pop("clipped", np.zeros(S, np.uint64)), dtype=np.uint64).reshape(-1).copy()
+            pcm16 = int(j.get("pcm16", 0))
+            if dst.dtype != (np.int16 if pcm16 else np.float32) or peak.size != S or clipped.size != S:
+                raise ValueError("dst is int16 with pcm16, float32 without; peak and clipped [S]")
+            if hout is not None and hout.size != hin.size:
+                raise ValueError("hist_out has hist_in's size")
+            d.gain = float(j.pop("gain", 1.0))
+            for k, v in j.items():
+                setattr(d, k, int(v))
+            d.has_hist_out = int(hout is not None)
+            d.src_floats, d.hist_elems, d.dst_elems = src.size, hin.size, dst.size
+            d.src, d.hist_in, d.dst, d.peak, d.clipped = src.ctypes.data, hin.ctypes.data, dst.ctypes.data, peak.ctypes.data, clipped.ctypes.data
+            d.hist_out = None if hout is None else hout.ctypes.data
+            keep.append((src, hin, hout, dst, peak, clipped))
+        rc = self.lib.css_rate_output_host(self.h, int(form), int(S), tab, len(jobs))
+        return self._rate_left(rc, [(k[3], k[2], k[4], k[5]) for k in keep])
+
+    def _rate_left(self, rc, left):
+        """`left` after a call that succeeded; a refused call raises CssError with `left` (the arrays as the call left them) on it"""
+        try:
+            check(self.h, rc)
+        except CssError as e:
+            e.left = left
+            raise
+        return left
 
     # ---- the kernels of csrc/mvdr.hip and csrc/stitch.hip on caller data (include/css_mi355_backend.h;
     #      tests/test_hip_backend_kernels.py).  Arrays are the WHOLE allocations (None where a form takes none); the arrays a form

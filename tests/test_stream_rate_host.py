@@ -15,7 +15,8 @@ import pytest
 from conftest import ROOT, pkg
 
 CSRC = os.path.join(ROOT, "notsofar1-challenge_amd", "csrc")
-RATIOS = ((1, 3), (1, 2), (2, 1), (2, 3), (160, 441), (1, 6), (320, 441))
+RATIOS = ((1, 3), (1, 2), (2, 1), (2, 3), (160, 441), (1, 6), (320, 441),      # the capture rates,
+          (3, 1), (441, 160), (3, 2), (441, 320), (6, 1), (819, 818))           # the playback rates and the rule's edge
 NAMES = ("css_stream_set_rate", "css_stream_rate_samples", "css_resample_taps", "css_resample_host")
 
 
