@@ -223,6 +223,55 @@ class CssRateOutputJob(C.Structure):
                [(n, C.c_void_p) for n in ("src", "hist_in", "hist_out", "dst", "peak", "clipped")]
 
 
+class CssKArray(C.Structure):                   # include/css_mi355_stream_kernels.h
+    _fields_ = [("p", C.c_void_p), ("elems", C.c_int64)]
+
+
+class CssStreamTailJob(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("S", "F", "T", "hop", "KIp", "dilation", "erosion", "has_ring")] + \
+               [("activity_th", C.c_float), ("reserved_f", C.c_float)] + \
+               [(n, C.c_int64) for n in ("num_slots", "seg_base", "frame_base", "num_segments_global", "T_long_global", "mask_ld",
+                                         "ld_frames", "gate_ld", "t_lo", "t_hi")] + \
+               [(n, CssKArray) for n in ("masks", "sep", "perms", "w_first", "w_mid", "w_last", "act_b", "Y", "ring")]
+
+
+class CssStreamScatterJob(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("dst_off", "dst_ld", "src_col", "n_cols")] + [("dst", CssKArray)]
+
+
+class CssStreamIngestJob(C.Structure):
+    _fields_ = [("C", C.c_int32), ("dst_col", C.c_int32)] + [(n, C.c_int64) for n in ("plane_ld", "n", "dst_ld")] + \
+               [("src", CssKArray), ("dst", CssKArray)]
+
+
+class CssStreamAppendJob(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("pad", "drop", "closing", "S", "preview", "reserved")] + \
+               [(n, C.c_int64) for n in ("gate_ld", "out_ld", "out_base", "carry_ld", "t_g0", "t_g1", "D0", "D1", "row0", "rows")] + \
+               [(n, CssKArray) for n in ("gate", "out", "carry_in", "carry_out", "tail_in", "tail_out", "st", "st_out", "act_out", "n_new")]
+
+
+class CssStreamMelJob(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n_mels", "has_ring", "has_pvmax", "reserved")] + \
+               [(n, C.c_int64) for n in ("row0", "rows", "hist", "mel_ld")] + \
+               [(n, CssKArray) for n in ("n_new", "st", "mel", "ring", "fmax", "pvmax")]
+
+
+# a state row of the streamed hand-off (csrc/kernels.hpp HandoffState)
+HANDOFF_STATE = np.dtype([("A", "<i8"), ("J", "<i8"), ("gmax", "<i4"), ("pad", "<i4")])
+# per descriptor: the arrays a launch only reads, and the arrays it may write (copied first, returned as the launch left them)
+STREAM_KERNEL_ARRAYS = {
+    "CssStreamTailJob": ((("masks", np.float32), ("sep", np.float32), ("perms", np.int32), ("w_first", np.float32), ("w_mid", np.float32),
+                          ("w_last", np.float32)), (("act_b", np.uint8), ("Y", np.float32), ("ring", np.uint8))),
+    "CssStreamScatterJob": ((), (("dst", np.float32),)),
+    "CssStreamIngestJob": ((("src", np.int16),), (("dst", np.float32),)),
+    "CssStreamAppendJob": ((("gate", np.uint8), ("out", np.float32), ("carry_in", np.float32), ("tail_in", np.float32)),
+                           (("carry_out", np.float32), ("tail_out", np.float32), ("st", HANDOFF_STATE), ("st_out", HANDOFF_STATE),
+                            ("act_out", np.uint8), ("n_new", np.int32))),
+    "CssStreamMelJob": ((("n_new", np.int32),), (("st", HANDOFF_STATE), ("mel", np.float32), ("ring", np.float32), ("fmax", np.float32),
+                                                  ("pvmax", np.float32))),
+}
+
+
 class CssMvdrSet(C.Structure):                  # include/css_mi355_backend.h
     _fields_ = [(n, C.c_int64) for n in ("seg_lo", "nseg", "scm_off", "bfw_off")]
 
@@ -472,6 +521,16 @@ RATE_KERNEL_BINDINGS = {
     "css_rate_output_host": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(CssRateOutputJob), C.c_int32]),
 }
 RATE_KERNEL_JOBS = 64                            # CSS_RATE_KERNEL_JOBS
+# the entry points include/css_mi355_stream_kernels.h declares (the kernels of csrc/stream.hip and the streamed part of
+# csrc/handoff.hip on caller data), the sixteenth table load() applies (a ..._BINDINGS table, as the two above)
+STREAM_KERNEL_BINDINGS = {
+    "css_stream_tail_host": (C.c_int, [_P, C.c_int32, C.POINTER(CssStreamTailJob), C.c_int32]),
+    "css_stream_scatter_host": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int32, C.POINTER(CssStreamScatterJob), C.c_int32]),
+    "css_stream_ingest_host": (C.c_int, [_P, C.POINTER(CssStreamIngestJob), C.c_int32]),
+    "css_stream_append_host": (C.c_int, [_P, C.POINTER(CssStreamAppendJob), C.c_int32, _P, C.c_int64]),
+    "css_stream_mel_host": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.c_int64, C.POINTER(CssStreamMelJob), C.c_int32]),
+}
+STREAM_KERNEL_JOBS = 64                          # CSS_STREAM_KERNEL_JOBS
 ARRAY_MIN_MICS, ARRAY_MAX_MICS = 2, 8            # CSS_ARRAY_MIN_MICS, CSS_ARRAY_MAX_MICS
 SESSION_SCAN_CHUNK = 1024                        # CSS_SESSION_SCAN_CHUNK: the keep-scan kernel's step, in gate frames / sample blocks
 RESAMPLE_TILE = 256                              # output samples per block of the two resampling kernels (resample.hip RS_TILE)
@@ -521,7 +580,8 @@ def load() -> C.CDLL:
                               list(SIGNATURES_FRONTEND.items()) + list(SIGNATURES_SESSION_HANDOFF.items()) +
                               list(SIGNATURES_STREAM_OUT.items()) + list(SIGNATURES_BACKEND.items()) +
                               list(ARRAY_SIGNATURES.items()) + list(SESSION_RATE_SIGNATURES.items()) +
-                              list(SESSION_WINDOW_BINDINGS.items()) + list(RATE_KERNEL_BINDINGS.items())):
+                              list(SESSION_WINDOW_BINDINGS.items()) + list(RATE_KERNEL_BINDINGS.items()) +
+                              list(STREAM_KERNEL_BINDINGS.items())):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -1348,6 +1408,70 @@ class Handle:
             e.left = left
             raise
         return left
+
+    # ---- the kernels of csrc/stream.hip and the streamed part of csrc/handoff.hip on caller data
+    #      (include/css_mi355_stream_kernels.h; tests/test_hip_stream_kernels.py).  A job is a dict of the descriptor's scalar fields
+    #      and its arrays (the WHOLE allocations; None or absent: not passed); the arrays a launch may write are copied first, and
+    #      every call returns one dict per job with them as the launch left them.
+    def _stream_kernel_table(self, kind, jobs):
+        ins, outs = STREAM_KERNEL_ARRAYS[kind.__name__]
+        tab = (kind * len(jobs))()
+        keep, left = [], []
+        for d, j in zip(tab, jobs):
+            j = dict(j)
+            got = {}
+            for (name, dtype), out in [(f, False) for f in ins] + [(f, True) for f in outs]:
+                a = j.pop(name, None)
+                if a is None:
+                    continue
+                a = np.ascontiguousarray(a, dtype=dtype).reshape(-1)
+                a = a.copy() if out else a
+                getattr(d, name).p, getattr(d, name).elems = a.ctypes.data, a.size
+                keep.append(a)
+                if out:
+                    got[name] = a
+            for k, v in j.items():
+                setattr(d, k, float(v) if k == "activity_th" else int(v))
+            left.append(got)
+        return tab, keep, left
+
+    def stream_tail(self, form: int, jobs):
+        """launch_stream_activity_multi (0) / launch_stream_gate_ola_multi (1) (css_stream_tail_host) -> [{act_b, Y, ring}]"""
+        tab, keep, left = self._stream_kernel_table(CssStreamTailJob, jobs)
+        for d in tab:
+            d.has_ring = int(bool(d.ring.p))
+        return self._rate_left(self.lib.css_stream_tail_host(self.h, int(form), tab, len(jobs)), left)
+
+    def stream_scatter(self, src, src_ld: int, rows: int, jobs):
+        """launch_stream_scatter_masks (css_stream_scatter_host) of src [rows][src_ld] -> [{dst}]"""
+        src = np.ascontiguousarray(src, dtype=np.float32).reshape(-1)
+        tab, keep, left = self._stream_kernel_table(CssStreamScatterJob, jobs)
+        return self._rate_left(self.lib.css_stream_scatter_host(self.h, _np_ptr(src), src.size, int(src_ld), int(rows), tab, len(jobs)), left)
+
+    def stream_ingest(self, jobs):
+        """launch_stream_ingest_pcm16_multi (css_stream_ingest_host) -> [{dst}]"""
+        tab, keep, left = self._stream_kernel_table(CssStreamIngestJob, jobs)
+        return self._rate_left(self.lib.css_stream_ingest_host(self.h, tab, len(jobs)), left)
+
+    def stream_append(self, jobs, operand):
+        """launch_handoff_append_multi (css_stream_append_host); a job with st_out is a preview's.  -> ([{carry_out, tail_out, st,
+        st_out, act_out, n_new, rows, row0}], operand as the launch left it)"""
+        operand = np.ascontiguousarray(operand, dtype=np.float32).reshape(-1).copy()
+        tab, keep, left = self._stream_kernel_table(CssStreamAppendJob, jobs)
+        for d in tab:
+            d.preview = int(bool(d.st_out.p))
+        rc = self.lib.css_stream_append_host(self.h, tab, len(jobs), _np_ptr(operand), operand.size)
+        for d, got in zip(tab, left):
+            got["rows"], got["row0"] = int(d.rows), int(d.row0)
+        return self._rate_left(rc, (left, operand))
+
+    def stream_mel(self, S: int, spec, ld: int, jobs):
+        """launch_handoff_mel_multi (css_stream_mel_host) on spec [402][ld] -> [{st, mel, ring, fmax, pvmax}]"""
+        spec = np.ascontiguousarray(spec, dtype=np.float32).reshape(-1)
+        tab, keep, left = self._stream_kernel_table(CssStreamMelJob, jobs)
+        for d in tab:
+            d.has_ring, d.has_pvmax = int(bool(d.ring.p)), int(bool(d.pvmax.p))
+        return self._rate_left(self.lib.css_stream_mel_host(self.h, int(S), _np_ptr(spec), spec.size, int(ld), tab, len(jobs)), left)
 
     # ---- the kernels of csrc/mvdr.hip and csrc/stitch.hip on caller data (include/css_mi355_backend.h;
     #      tests/test_hip_backend_kernels.py).  Arrays are the WHOLE allocations (None where a form takes none); the arrays a form

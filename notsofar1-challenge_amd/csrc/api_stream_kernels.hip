@@ -1,0 +1,355 @@
+// include/css_mi355_stream_kernels.h: the kernels of stream.hip and the streamed part of handoff.hip on caller data, one entry per
+// launcher (unit tests of the kernels; the companion of api_rate_kernels.hip).  Every entry checks first, then stages in
+// h->stage, makes the ONE launcher call the path makes, downloads every allocation a launch could have written and synchronises.
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "api_ctx.hpp"
+#include "stitch_common.hpp"   // (OLA_T: the gate kernel's block of frames)
+#include "../../include/css_mi355_stream_kernels.h"
+
+using namespace css;
+
+namespace {
+
+constexpr int64_t HOST_CAP = (int64_t)1 << 28;   // elements per array
+constexpr int64_t POS_MAX = (int64_t)1 << 40;    // frame and sample positions of a recording
+
+// Byte offsets into h->stage: every region starts on 256 bytes and has 256 bytes of room on both sides.  Arrays are registered
+// before the allocation, then uploaded whole; those marked `out` come back whole.
+struct Stager {
+    struct Slot { size_t at, bytes; void* host; bool out; };
+    size_t bytes = 256;
+    std::vector<Slot> slots;
+    size_t take(const CssKArray& a, size_t el, bool out) {
+        const size_t n = (size_t)a.elems * el, at = bytes;
+        bytes += (n + 255) / 256 * 256 + 256;
+        slots.push_back(Slot{at, n, a.p, out});
+        return at;
+    }
+    size_t take_raw(void* host, size_t n, bool out) { return take(CssKArray{host, (int64_t)n}, 1, out); }
+    hipError_t upload(char* base, hipStream_t st) const {
+        for (const Slot& s : slots)
+            if (s.bytes > 0)
+                if (hipError_t e = hipMemcpyAsync(base + s.at, s.host, s.bytes, hipMemcpyHostToDevice, st)) return e;
+        return hipStreamSynchronize(st);   // (the sources are pageable host memory of this call)
+    }
+    hipError_t download(char* base, hipStream_t st) const {
+        for (const Slot& s : slots)
+            if (s.out && s.bytes > 0)
+                if (hipError_t e = hipMemcpyAsync(s.host, base + s.at, s.bytes, hipMemcpyDeviceToHost, st)) return e;
+        return hipStreamSynchronize(st);
+    }
+};
+
+bool arr_ok(const CssKArray& a, int64_t need) { return a.elems >= need && a.elems >= 0 && a.elems <= HOST_CAP && (a.elems == 0 || a.p); }
+bool pow2(int64_t v) { return v > 0 && (v & (v - 1)) == 0; }
+bool pos_ok(int64_t v) { return v >= 0 && v <= POS_MAX; }
+
+int stage_and_upload(css_ctx* h, const Stager& sg, char** base) {
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc;
+    if ((rc = ensure(h, h->stage, sg.bytes)) != CSS_OK) return rc;
+    *base = (char*)h->stage.p;
+    HIPCHK(h, sg.upload(*base, h->stream));
+    return CSS_OK;
+}
+int download_all(css_ctx* h, const Stager& sg, char* base) {
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, sg.download(base, h->stream));
+    HIPCHK(h, hipGetLastError());
+    return CSS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int css_stream_tail_host(css_handle_t h, int32_t form, CssStreamTailJob* jobs, int32_t n_jobs) {
+    CSS_DRAIN(h);
+    if (!h) return CSS_ERR_INVALID_ARG;
+    auto bad = [&](const char* what) { return fail(h, CSS_ERR_INVALID_ARG, std::string("css_stream_tail_host: ") + what); };
+    if (!jobs) return bad("null argument");
+    if (form < 0 || form > 1) return bad("form must be 0 (activity) or 1 (gate and overlap-add)");
+    if (n_jobs < 1 || n_jobs > CSS_STREAM_KERNEL_JOBS) return bad("1 .. 64 jobs");
+    int max_erosion = 0;
+    for (int i = 0; i < n_jobs; ++i) max_erosion = std::max(max_erosion, std::min(jobs[i].erosion, 4096));
+    for (int i = 0; i < n_jobs; ++i) {
+        const CssStreamTailJob& j = jobs[i];
+        if (j.S < 1 || j.S > 4) return bad("S must be 1 .. 4");
+        if (j.F < 1 || j.F > 1024 || j.T < 1 || j.T > 4096) return bad("F must be 1 .. 1024 and T 1 .. 4096");
+        if (j.hop < 1 || j.hop > j.T) return bad("hop must be 1 .. T");
+        if (j.S != jobs[0].S || j.F != jobs[0].F) return bad("the jobs of one call share S and F");
+        if (form == 1 && (size_t)OLA_T * (2 * j.F + 1) * sizeof(float) + OLA_T + 2 * (size_t)max_erosion > 65536)
+            return bad("the gate launch's LDS, 64 (2 F + 1) + 16 + 2 (the largest erosion) bytes, exceeds 64 KiB");
+        if (j.KIp < 2 * j.F || j.KIp > 4096) return bad("KIp must cover 2 F (and be at most 4096)");
+        if (j.dilation < 0 || j.dilation > 4096 || j.erosion < 0 || j.erosion > 4096) return bad("dilation and erosion must be 0 .. 4096");
+        if (j.has_ring < 0 || j.has_ring > 1 || (j.has_ring && !pow2(j.gate_ld))) return bad("gate_ld must be a power of two");
+        if (j.num_slots < 0 || j.num_slots > (1 << 20) || !pos_ok(j.seg_base) || !pos_ok(j.frame_base))
+            return bad("num_slots, seg_base and frame_base must not be negative");
+        if (j.num_segments_global < j.seg_base + j.num_slots) return bad("num_segments_global below seg_base + num_slots");
+        if (j.mask_ld < j.num_slots * j.T || j.mask_ld > HOST_CAP) return bad("mask_ld must cover num_slots T");
+        if (j.ld_frames < 1 || j.ld_frames > (1 << 24)) return bad("ld_frames must be 1 .. 2^24");
+        if (j.t_lo < 0 || j.t_hi < j.t_lo || j.t_hi > j.ld_frames) return bad("the range must lie in [0, ld_frames]");
+        if (j.T_long_global < j.frame_base || j.t_hi > j.T_long_global - j.frame_base) return bad("the range ends past T_long_global");
+        if (!arr_ok(j.masks, (int64_t)j.S * j.F * j.mask_ld) || !arr_ok(j.sep, j.num_slots * j.S * j.F * j.T * 2) ||
+            !arr_ok(j.perms, j.num_slots * j.S) || !arr_ok(j.w_first, j.T) || !arr_ok(j.w_mid, j.T) || !arr_ok(j.w_last, j.T) ||
+            !arr_ok(j.act_b, (int64_t)j.S * j.ld_frames) || !arr_ok(j.Y, (int64_t)j.S * j.ld_frames * j.KIp) ||
+            (j.has_ring && !arr_ok(j.ring, (int64_t)j.S * j.gate_ld)))
+            return bad("an array is null or shorter than its description");
+        const int32_t* perms = (const int32_t*)j.perms.p;
+        for (int64_t q = 0; q < j.num_slots * j.S; ++q)
+            if (perms[q] < 0 || perms[q] >= j.S) return bad("a permutation entry outside 0 .. S - 1");
+        if (form == 1 && j.t_hi > j.t_lo) {
+            const int64_t halo = (int64_t)j.erosion + j.dilation;
+            const int64_t g_end = j.T_long_global - j.frame_base;
+            const int64_t lo = std::max(j.t_lo - halo, -j.frame_base), hi = std::min(j.t_hi - 1 + halo, g_end - 1);
+            if (lo < 0) return bad("the gate reads act_b below local frame 0 (t_lo < erosion + dilation with frame_base > 0)");
+            if (hi >= j.ld_frames) return bad("the gate of the range's last frame reads act_b past ld_frames");
+        }
+    }
+    Stager sg;
+    struct At { size_t masks, sep, perms, w0, w1, w2, act, Y, ring; };
+    std::vector<At> at((size_t)n_jobs);
+    for (int i = 0; i < n_jobs; ++i) {
+        CssStreamTailJob& j = jobs[i];
+        At& a = at[(size_t)i];
+        a.masks = sg.take(j.masks, 4, false); a.sep = sg.take(j.sep, 4, false); a.perms = sg.take(j.perms, 4, false);
+        a.w0 = sg.take(j.w_first, 4, false); a.w1 = sg.take(j.w_mid, 4, false); a.w2 = sg.take(j.w_last, 4, false);
+        a.act = sg.take(j.act_b, 1, true); a.Y = sg.take(j.Y, 4, true);
+        a.ring = j.has_ring ? sg.take(j.ring, 1, true) : 0;
+    }
+    char* base = nullptr;
+    int rc;
+    if ((rc = stage_and_upload(h, sg, &base)) != CSS_OK) return rc;
+    std::vector<StreamStitchArgs> sa((size_t)n_jobs);
+    std::vector<StreamFrames> fr((size_t)n_jobs);
+    for (int i = 0; i < n_jobs; ++i) {
+        const CssStreamTailJob& j = jobs[i];
+        const At& a = at[(size_t)i];
+        StreamStitchArgs& e = sa[(size_t)i];
+        e = StreamStitchArgs{};
+        e.masks = (const float*)(base + a.masks); e.mask_ld = j.mask_ld;
+        e.sep = (const float*)(base + a.sep); e.perms = (const int32_t*)(base + a.perms);
+        e.S = j.S; e.F = j.F; e.T = j.T; e.hop = j.hop;
+        e.num_slots = j.num_slots; e.seg_base = j.seg_base; e.frame_base = j.frame_base;
+        e.num_segments_global = j.num_segments_global; e.T_long_global = j.T_long_global;
+        e.w_first = (const float*)(base + a.w0); e.w_mid = (const float*)(base + a.w1); e.w_last = (const float*)(base + a.w2);
+        e.act_b = (uint8_t*)(base + a.act); e.Y = (float*)(base + a.Y); e.KIp = j.KIp; e.ld_frames = j.ld_frames;
+        e.activity_th = j.activity_th; e.dilation = j.dilation; e.erosion = j.erosion;
+        if (j.has_ring) { e.gate_out = (uint8_t*)(base + a.ring); e.gate_ld = j.gate_ld; e.gate_mask = j.gate_ld - 1; }
+        fr[(size_t)i] = StreamFrames{j.t_lo, j.t_hi};
+    }
+    if (form == 0) launch_stream_activity_multi(sa.data(), fr.data(), n_jobs, h->stream);
+    else launch_stream_gate_ola_multi(sa.data(), fr.data(), n_jobs, h->stream);
+    return download_all(h, sg, base);
+}
+
+int css_stream_scatter_host(css_handle_t h, const float* src, int64_t src_elems, int64_t src_ld, int32_t rows, CssStreamScatterJob* jobs,
+                            int32_t n_jobs) {
+    CSS_DRAIN(h);
+    if (!h) return CSS_ERR_INVALID_ARG;
+    auto bad = [&](const char* what) { return fail(h, CSS_ERR_INVALID_ARG, std::string("css_stream_scatter_host: ") + what); };
+    if (!jobs || !src) return bad("null argument");
+    if (n_jobs < 1 || n_jobs > CSS_STREAM_KERNEL_JOBS) return bad("1 .. 64 jobs");
+    if (rows < 1 || rows > 65536) return bad("rows must be 1 .. 65536");
+    if (src_ld < 1 || src_ld > HOST_CAP || src_elems > HOST_CAP || src_elems < (int64_t)rows * src_ld) return bad("src is shorter than [rows][src_ld]");
+    for (int i = 0; i < n_jobs; ++i) {
+        const CssStreamScatterJob& j = jobs[i];
+        if (j.src_col < 0 || j.n_cols < 0 || j.src_col + j.n_cols > src_ld) return bad("the columns must lie in [0, src_ld]");
+        if (j.dst_ld < j.n_cols || j.dst_ld > HOST_CAP) return bad("dst_ld must cover n_cols");
+        if (j.dst_off < 0 || j.dst_off > 63) return bad("dst_off must be 0 .. 63");
+        if (!arr_ok(j.dst, j.dst_off + (int64_t)(rows - 1) * j.dst_ld + j.n_cols) || !j.dst.p) return bad("dst is null or shorter than its description");
+    }
+    Stager sg;
+    const size_t src_at = sg.take_raw((void*)src, (size_t)src_elems * 4, false);
+    std::vector<size_t> at((size_t)n_jobs);
+    for (int i = 0; i < n_jobs; ++i) at[(size_t)i] = sg.take(jobs[i].dst, 4, true);
+    char* base = nullptr;
+    int rc;
+    if ((rc = stage_and_upload(h, sg, &base)) != CSS_OK) return rc;
+    std::vector<MaskScatter> ms((size_t)n_jobs);
+    for (int i = 0; i < n_jobs; ++i)
+        ms[(size_t)i] = MaskScatter{(float*)(base + at[(size_t)i]) + jobs[i].dst_off, jobs[i].dst_ld, jobs[i].src_col, jobs[i].n_cols};
+    launch_stream_scatter_masks((const float*)(base + src_at), src_ld, rows, ms.data(), n_jobs, h->stream);
+    return download_all(h, sg, base);
+}
+
+int css_stream_ingest_host(css_handle_t h, CssStreamIngestJob* jobs, int32_t n_jobs) {
+    CSS_DRAIN(h);
+    if (!h) return CSS_ERR_INVALID_ARG;
+    auto bad = [&](const char* what) { return fail(h, CSS_ERR_INVALID_ARG, std::string("css_stream_ingest_host: ") + what); };
+    if (!jobs) return bad("null argument");
+    if (n_jobs < 1 || n_jobs > CSS_STREAM_KERNEL_JOBS) return bad("1 .. 64 jobs");
+    for (int i = 0; i < n_jobs; ++i) {
+        const CssStreamIngestJob& j = jobs[i];
+        if (j.C < 1 || j.C > 64) return bad("C must be 1 .. 64");
+        if (j.C != jobs[0].C) return bad("the jobs of one call share C");
+        if (j.n < 0 || j.n > ((int64_t)1 << 24)) return bad("n must be 0 .. 2^24");
+        if (j.plane_ld < 0 || (j.plane_ld > 0 && j.plane_ld < j.n) || j.plane_ld > HOST_CAP) return bad("plane_ld must be 0 (interleaved) or cover n");
+        if (j.dst_col < 0 || j.dst_col > 3) return bad("dst_col must be 0 .. 3");
+        if (j.dst_ld < j.dst_col + j.n || j.dst_ld > HOST_CAP) return bad("dst_ld must cover dst_col + n");
+        const int64_t src_need = j.n == 0 ? 0 : (j.plane_ld > 0 ? (int64_t)(j.C - 1) * j.plane_ld + j.n : j.n * j.C);
+        if (!arr_ok(j.src, src_need)) return bad("src is null or shorter than its description");
+        if (!arr_ok(j.dst, j.dst_col + (int64_t)(j.C - 1) * j.dst_ld + j.n) || !j.dst.p) return bad("dst is null or shorter than its description");
+    }
+    Stager sg;
+    std::vector<size_t> src_at((size_t)n_jobs), dst_at((size_t)n_jobs);
+    for (int i = 0; i < n_jobs; ++i) {
+        src_at[(size_t)i] = sg.take(jobs[i].src, 2, false);
+        dst_at[(size_t)i] = sg.take(jobs[i].dst, 4, true);
+    }
+    char* base = nullptr;
+    int rc;
+    if ((rc = stage_and_upload(h, sg, &base)) != CSS_OK) return rc;
+    std::vector<StreamIngestPcm16> in((size_t)n_jobs);
+    for (int i = 0; i < n_jobs; ++i) {
+        const CssStreamIngestJob& j = jobs[i];
+        in[(size_t)i] = StreamIngestPcm16{(const int16_t*)(base + src_at[(size_t)i]), j.plane_ld, j.n, j.C,
+                                          (float*)(base + dst_at[(size_t)i]) + j.dst_col, j.dst_ld};
+    }
+    launch_stream_ingest_pcm16_multi(in.data(), n_jobs, h->stream);
+    return download_all(h, sg, base);
+}
+
+int css_stream_append_host(css_handle_t h, CssStreamAppendJob* jobs, int32_t n_jobs, float* operand, int64_t operand_floats) {
+    CSS_DRAIN(h);
+    if (!h) return CSS_ERR_INVALID_ARG;
+    auto bad = [&](const char* what) { return fail(h, CSS_ERR_INVALID_ARG, std::string("css_stream_append_host: ") + what); };
+    if (!jobs || !operand) return bad("null argument");
+    if (n_jobs < 1 || n_jobs > CSS_STREAM_KERNEL_JOBS) return bad("1 .. 64 jobs");
+    static_assert(sizeof(HandoffState) == 24, "the header states the state row");
+    int64_t rows_total = 0;
+    std::vector<int64_t> rows((size_t)n_jobs), row0((size_t)n_jobs);
+    for (int i = 0; i < n_jobs; ++i) {
+        const CssStreamAppendJob& j = jobs[i];
+        if (j.S < 1 || j.S > 4 || j.S != jobs[0].S) return bad("S must be 1 .. 4, the same for all jobs");
+        if (j.pad < 0 || j.pad > 4096) return bad("pad must be 0 .. 4096");
+        if (j.drop < 0 || j.drop > 1 || j.closing < 0 || j.closing > 1 || j.preview < 0 || j.preview > 1) return bad("drop, closing and preview are 0 or 1");
+        if (!pow2(j.gate_ld) || j.gate_ld > HOST_CAP) return bad("gate_ld must be a power of two");
+        if (!pos_ok(j.t_g0) || !pos_ok(j.t_g1) || j.t_g1 < j.t_g0) return bad("t_g1 < t_g0 (or a negative frame count)");
+        if (!pos_ok(j.D0) || !pos_ok(j.D1) || j.D1 < j.D0) return bad("D1 < D0 (or a negative sample count)");
+        if (j.D0 % 256) return bad("D0 must be a multiple of 256");
+        if (j.D1 - j.D0 > ((int64_t)1 << 24)) return bad("D1 - D0 above 2^24");
+        if (!pos_ok(j.out_base) || j.out_ld < 0 || j.out_ld > HOST_CAP || j.carry_ld < 0 || j.carry_ld > HOST_CAP)
+            return bad("out_base, out_ld and carry_ld must not be negative");
+        const int64_t end = std::max(j.D1, 256 * j.t_g1);
+        if (end > j.out_base && end - j.out_base > j.out_ld) return bad("out_ld does not reach the round's last sample");
+        if (std::min(j.out_base, end) - j.D0 > j.carry_ld) return bad("out_base - D0 > carry_ld");
+        if (256 * j.t_g1 - j.D1 > j.carry_ld) return bad("the undecided samples behind D1 do not fit carry_ld");
+        if (!j.closing && j.drop && j.D1 > 256 * std::max<int64_t>(j.t_g1 - j.pad, 0)) return bad("an open round decides blocks whose frames are not gated-final");
+        const int64_t look = j.drop ? std::min(j.t_g0, std::max<int64_t>(j.D0 / 256 - j.pad - 1, 0)) : j.t_g0;
+        if (j.t_g1 - look > j.gate_ld) return bad("the ring is shorter than the frames the round reads");
+        if (!arr_ok(j.gate, (int64_t)j.S * j.gate_ld) || !arr_ok(j.out, (int64_t)j.S * j.out_ld) || !arr_ok(j.carry_in, (int64_t)j.S * j.carry_ld) ||
+            !arr_ok(j.carry_out, (int64_t)j.S * j.carry_ld) || !arr_ok(j.tail_in, (int64_t)j.S * HANDOFF_TAIL_LD) ||
+            !arr_ok(j.tail_out, (int64_t)j.S * HANDOFF_TAIL_LD) || !arr_ok(j.st, j.S) || (j.preview && !arr_ok(j.st_out, j.S)) ||
+            !arr_ok(j.act_out, (int64_t)j.S * (j.t_g1 - j.t_g0)) || !arr_ok(j.n_new, j.S) || !j.st.p || !j.n_new.p || (j.preview && !j.st_out.p))
+            return bad("an array is null or shorter than its description");
+        if (j.carry_out.p && j.carry_out.p == j.carry_in.p) return bad("carry_out must be another array than carry_in");
+        if (j.tail_out.p == j.tail_in.p) return bad("tail_out must be another array than tail_in");
+        const HandoffState* st = (const HandoffState*)j.st.p;
+        for (int k = 0; k < j.S; ++k)
+            if (st[k].A < 0 || st[k].J != (st[k].A >= 201 ? (st[k].A - 200) / 160 + 1 : 0)) return bad("a state row is not a state of an open stream");
+        rows[(size_t)i] = (j.D1 - j.D0 + 200) / 160 + 2 + 3;   // handoff_rows (api_stream_handoff.hip)
+        row0[(size_t)i] = rows_total;
+        rows_total += rows[(size_t)i] * j.S;
+    }
+    if (operand_floats != rows_total * 160 + 1024) return bad("operand must hold (sum of S rows) 160 + 1024 floats");
+    Stager sg;
+    struct At { size_t gate, out, cin, cout, tin, tout, st, sto, act, nn; };
+    std::vector<At> at((size_t)n_jobs);
+    const size_t op_at = sg.take_raw(operand, (size_t)operand_floats * 4, true);
+    for (int i = 0; i < n_jobs; ++i) {
+        CssStreamAppendJob& j = jobs[i];
+        At& a = at[(size_t)i];
+        a.gate = sg.take(j.gate, 1, false); a.out = sg.take(j.out, 4, false); a.cin = sg.take(j.carry_in, 4, false);
+        a.cout = sg.take(j.carry_out, 4, true); a.tin = sg.take(j.tail_in, 4, false); a.tout = sg.take(j.tail_out, 4, true);
+        a.st = sg.take(j.st, sizeof(HandoffState), true);
+        a.sto = j.preview ? sg.take(j.st_out, sizeof(HandoffState), true) : a.st;
+        a.act = sg.take(j.act_out, 1, true); a.nn = sg.take(j.n_new, 4, true);
+    }
+    char* base = nullptr;
+    int rc;
+    if ((rc = stage_and_upload(h, sg, &base)) != CSS_OK) return rc;
+    std::vector<HandoffAppend> ap((size_t)n_jobs);
+    for (int i = 0; i < n_jobs; ++i) {
+        CssStreamAppendJob& j = jobs[i];
+        const At& a = at[(size_t)i];
+        HandoffAppend& e = ap[(size_t)i];
+        e = HandoffAppend{};
+        e.gate = (const uint8_t*)(base + a.gate); e.gate_ld = j.gate_ld; e.gate_mask = j.gate_ld - 1;
+        e.out = (const float*)(base + a.out); e.out_ld = j.out_ld; e.out_base = j.out_base;
+        e.carry_in = (const float*)(base + a.cin); e.carry_out = (float*)(base + a.cout); e.carry_ld = j.carry_ld;
+        e.tail_in = (const float*)(base + a.tin); e.tail_out = (float*)(base + a.tout);
+        e.st = (const HandoffState*)(base + a.st); e.st_out = (HandoffState*)(base + a.sto);
+        e.t_g0 = j.t_g0; e.t_g1 = j.t_g1; e.D0 = j.D0; e.D1 = j.D1;
+        e.pad = j.pad; e.drop = j.drop; e.closing = j.closing; e.S = j.S;
+        e.row0 = j.row0 = row0[(size_t)i]; e.rows = j.rows = rows[(size_t)i];
+        e.act_out = (uint8_t*)(base + a.act); e.n_new = (int32_t*)(base + a.nn);
+    }
+    launch_handoff_append_multi(ap.data(), n_jobs, (float*)(base + op_at), h->stream);
+    return download_all(h, sg, base);
+}
+
+int css_stream_mel_host(css_handle_t h, int32_t S, const float* spec, int64_t spec_elems, int64_t ld, CssStreamMelJob* jobs, int32_t n_jobs) {
+    CSS_DRAIN(h);
+    if (!h) return CSS_ERR_INVALID_ARG;
+    auto bad = [&](const char* what) { return fail(h, CSS_ERR_INVALID_ARG, std::string("css_stream_mel_host: ") + what); };
+    if (!jobs || !spec) return bad("null argument");
+    if (n_jobs < 1 || n_jobs > CSS_STREAM_KERNEL_JOBS) return bad("1 .. 64 jobs");
+    if (S < 1 || S > 4) return bad("S must be 1 .. 4");
+    if (ld < 1 || ld > HOST_CAP / 402 || spec_elems < 402 * ld || spec_elems > HOST_CAP) return bad("spec is shorter than [402][ld]");
+    for (int i = 0; i < n_jobs; ++i) {
+        const CssStreamMelJob& j = jobs[i];
+        if (j.n_mels != 80 && j.n_mels != 128) return bad("n_mels must be 80 or 128");
+        if (j.row0 < 0 || j.rows < 1 || j.rows > (1 << 20) || j.row0 + (int64_t)S * j.rows > ld) return bad("row0 + S rows must lie in [0, ld]");
+        if (j.mel_ld < j.rows || j.mel_ld > HOST_CAP) return bad("mel_ld must cover rows");
+        if (j.has_ring < 0 || j.has_ring > 1 || j.has_pvmax < 0 || j.has_pvmax > 1 || (j.has_ring && j.has_pvmax)) return bad("has_ring and has_pvmax are 0 or 1, not both");
+        if (j.has_ring && (j.hist < 1 || j.hist > HOST_CAP)) return bad("hist must be at least 1");
+        if (!arr_ok(j.n_new, S) || !arr_ok(j.st, S) || !arr_ok(j.mel, (int64_t)S * j.n_mels * j.mel_ld) || !j.n_new.p || !j.st.p || !j.mel.p ||
+            (j.has_ring && (!arr_ok(j.ring, (int64_t)S * j.n_mels * j.hist) || !arr_ok(j.fmax, (int64_t)S * j.hist) || !j.ring.p || !j.fmax.p)) ||
+            (j.has_pvmax && (!arr_ok(j.pvmax, (int64_t)S * j.rows) || !j.pvmax.p)))
+            return bad("an array is null or shorter than its description");
+        const int32_t* nn = (const int32_t*)j.n_new.p;
+        const HandoffState* st = (const HandoffState*)j.st.p;
+        for (int k = 0; k < S; ++k) {
+            if (nn[k] < 0) return bad("n_new must not be negative");
+            if (j.has_ring && st[k].J < nn[k]) return bad("a frame count J below n_new");
+        }
+    }
+    std::vector<float> w80((size_t)80 * 201), w128((size_t)128 * 201);
+    handoff_build_mel(w80.data(), 80);
+    handoff_build_mel(w128.data(), 128);
+    Stager sg;
+    const size_t spec_at = sg.take_raw((void*)spec, (size_t)spec_elems * 4, false);
+    const size_t w80_at = sg.take_raw(w80.data(), w80.size() * 4, false), w128_at = sg.take_raw(w128.data(), w128.size() * 4, false);
+    struct At { size_t nn, st, mel, ring, fmax, pv; };
+    std::vector<At> at((size_t)n_jobs);
+    for (int i = 0; i < n_jobs; ++i) {
+        CssStreamMelJob& j = jobs[i];
+        At& a = at[(size_t)i];
+        a.nn = sg.take(j.n_new, 4, false); a.st = sg.take(j.st, sizeof(HandoffState), true); a.mel = sg.take(j.mel, 4, true);
+        a.ring = j.has_ring ? sg.take(j.ring, 4, true) : 0; a.fmax = j.has_ring ? sg.take(j.fmax, 4, true) : 0;
+        a.pv = j.has_pvmax ? sg.take(j.pvmax, 4, true) : 0;
+    }
+    char* base = nullptr;
+    int rc;
+    if ((rc = stage_and_upload(h, sg, &base)) != CSS_OK) return rc;
+    std::vector<HandoffMel> me((size_t)n_jobs);
+    for (int i = 0; i < n_jobs; ++i) {
+        const CssStreamMelJob& j = jobs[i];
+        const At& a = at[(size_t)i];
+        HandoffMel& e = me[(size_t)i];
+        e = HandoffMel{};
+        e.row0 = j.row0; e.rows = j.rows; e.n_new = (const int32_t*)(base + a.nn); e.st = (HandoffState*)(base + a.st);
+        e.w = (const float*)(base + (j.n_mels == 80 ? w80_at : w128_at)); e.n_mels = j.n_mels;
+        e.mel = (float*)(base + a.mel); e.mel_ld = j.mel_ld;
+        if (j.has_ring) { e.ring = (float*)(base + a.ring); e.fmax = (float*)(base + a.fmax); e.hist = j.hist; }
+        if (j.has_pvmax) e.pvmax = (float*)(base + a.pv);
+    }
+    launch_handoff_mel_multi(me.data(), n_jobs, S, (const float*)(base + spec_at), ld, h->stream);
+    return download_all(h, sg, base);
+}
+
+}  // extern "C"

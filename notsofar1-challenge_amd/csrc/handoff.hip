@@ -233,7 +233,9 @@ __global__ __launch_bounds__(256) void handoff_append_kernel(HandoffAppendTable 
     __syncthreads();
     const int64_t tail1 = J1 > 0 ? 160 * J1 - 200 : 0;
     float* __restrict__ tail_out = e.tail_out + (int64_t)k * HANDOFF_TAIL_LD;
-    for (int64_t c = tail1 + tid; c < A1 && c - tail1 < HANDOFF_TAIL_LD; c += 256) tail_out[c - tail1] = concat(c);
+    // (J1 == 1: tail1 is -40 and the first 40 floats stand for samples before the concatenation: nothing reads them, and there is
+    //  nothing to read for them -- with J0 == 0 concat(c < 0) would be tail_in[-40 ..], below the speaker's row)
+    for (int64_t c = tail1 + tid; c < A1 && c - tail1 < HANDOFF_TAIL_LD; c += 256) tail_out[c - tail1] = c < 0 ? 0.f : concat(c);
     // ---- the samples still undecided, for the next round; the gate bytes of the round; the counts
     const int64_t end = e.t_g1 * HOP;
     float* __restrict__ carry_out = e.carry_out + (int64_t)k * e.carry_ld;

@@ -66,7 +66,8 @@ __device__ __forceinline__ void stream_gate_ola_body(const StreamStitchArgs& a, 
         uint8_t v = 0;
         if (u + a.frame_base >= 0 && u < g_end)
             for (int64_t w = u - a.dilation; w <= u + a.dilation; ++w) {
-                const uint8_t x = (w + a.frame_base < 0 || w >= g_end) ? 0 : row[w];
+                // (w >= ld_frames: only lanes at or above t_hi get there -- the block dilates whole -- and the row ends at ld_frames)
+                const uint8_t x = (w + a.frame_base < 0 || w >= g_end || w >= a.ld_frames) ? 0 : row[w];
                 v = v | x;
             }
         dil[i] = v;

@@ -34,7 +34,7 @@ def test_header_library_and_binding_agree():
     declared = re.findall(r"\bint\s+(css_\w+)\s*\(", text)
     assert sorted(declared) == sorted(NAMES) == sorted(L.RATE_KERNEL_BINDINGS)
     tables = {n: getattr(L, n) for n in dir(L) if n.startswith("SIGNATURES") or n.endswith("_SIGNATURES") or n.endswith("_BINDINGS")}
-    assert len(tables) == 15
+    assert len(tables) == 16
     for n, t in tables.items():
         assert n == "RATE_KERNEL_BINDINGS" or not set(L.RATE_KERNEL_BINDINGS) & set(t), n
     for f in os.listdir(os.path.join(ROOT, "include")):
@@ -47,7 +47,7 @@ def test_header_library_and_binding_agree():
         restype, argtypes = L.RATE_KERNEL_BINDINGS[name]
         fn = getattr(lib, name)   # (AttributeError: the library does not export it)
         assert restype is C.c_int and len(argtypes) == len(params), name
-        assert fn.restype is C.c_int and list(fn.argtypes) == list(argtypes)       # load() applied the fifteenth table
+        assert fn.restype is C.c_int and list(fn.argtypes) == list(argtypes)       # load() applied the fifteenth of its sixteen tables
     kinds = {"int32_t": C.c_int32, "int64_t": C.c_int64, "uint32_t": C.c_uint32, "float": C.c_float}
     for desc in DESCS:   # the header's fields in the header's order, with the header's types; every pointer is a void pointer
         body = re.search(rf"typedef struct {desc} \{{(.*?)\}} {desc};", text, flags=re.S).group(1)
