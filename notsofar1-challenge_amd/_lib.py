@@ -272,6 +272,53 @@ STREAM_KERNEL_ARRAYS = {
 }
 
 
+class CssSessionScanJob(C.Structure):           # include/css_mi355_handoff_kernels.h
+    _fields_ = [(n, C.c_int32) for n in ("S", "pad", "drop", "cap_ranges", "gate_off", "reserved")] + [("TL", C.c_int64)] + \
+               [(n, CssKArray) for n in ("gate", "psum", "regs", "offs", "st", "n_new", "n_ranges", "ranges_out", "n_frames_out",
+                                         "n_ranges_out")]
+
+
+class CssSessionGatherJob(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("S", "cap_ranges", "wav_off", "reserved")] + [(n, C.c_int64) for n in ("wav_ld", "rows")] + \
+               [(n, CssKArray) for n in ("regs", "offs", "st", "n_ranges", "wav", "operand")]
+
+
+class CssSessionNormJob(C.Structure):
+    _fields_ = [("S", C.c_int32), ("n_mels", C.c_int32)] + [(n, C.c_int64) for n in ("mel_ld", "out_ld", "rows")] + \
+               [(n, CssKArray) for n in ("st", "mel", "out")]
+
+
+class CssSessionWindowsJob(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("S", "n_mels", "width", "stride", "f16", "has_win", "has_whole", "win_off", "whole_off",
+                                         "mel_off")] + \
+               [(n, C.c_int64) for n in ("mel_ld", "max_frames", "ld", "cap_windows", "whole_ld", "n_win_jobs", "n_whole_jobs")] + \
+               [(n, CssKArray) for n in ("st", "mel", "win", "whole", "n_windows_out", "window_max_out")]
+
+
+class CssStreamWindowJob(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n_frames", "width", "n_mels", "f16", "has_pv", "ring_off", "pv_off", "out_off")] + \
+               [(n, C.c_int64) for n in ("hist", "ld", "J", "pv_ld")] + \
+               [(n, CssKArray) for n in ("ring", "fmax", "pv", "pvmax", "n_new", "out")]
+
+
+# a result row of the window kernel (csrc/kernels.hpp WindowOut)
+WINDOW_OUT = np.dtype([("first_frame", "<i8"), ("n_used", "<i4"), ("n_provisional", "<i4"), ("window_max", "<f4"), ("pad", "<i4")])
+# per descriptor, as STREAM_KERNEL_ARRAYS: the arrays a launch only reads, and those it may write.  None: float32, or float16 (as
+# uint16 words) where the descriptor's f16 is set
+HANDOFF_KERNEL_ARRAYS = {
+    "CssSessionScanJob": ((("gate", np.uint8),), (("psum", np.int32), ("regs", np.int64), ("offs", np.int64), ("st", HANDOFF_STATE),
+                                                  ("n_new", np.int32), ("n_ranges", np.int32), ("ranges_out", np.int64),
+                                                  ("n_frames_out", np.int64), ("n_ranges_out", np.int32))),
+    "CssSessionGatherJob": ((("regs", np.int64), ("offs", np.int64), ("st", HANDOFF_STATE), ("n_ranges", np.int32), ("wav", np.float32)),
+                            (("operand", np.float32),)),
+    "CssSessionNormJob": ((("st", HANDOFF_STATE), ("mel", np.float32)), (("out", np.float32),)),
+    "CssSessionWindowsJob": ((("st", HANDOFF_STATE), ("mel", np.float32)),
+                             (("win", None), ("whole", None), ("n_windows_out", np.int32), ("window_max_out", np.float32))),
+    "CssStreamWindowJob": ((("ring", np.float32), ("fmax", np.float32), ("pv", np.float32), ("pvmax", np.float32), ("n_new", np.int32)),
+                           (("out", None),)),
+}
+
+
 class CssMvdrSet(C.Structure):                  # include/css_mi355_backend.h
     _fields_ = [(n, C.c_int64) for n in ("seg_lo", "nseg", "scm_off", "bfw_off")]
 
@@ -531,6 +578,16 @@ STREAM_KERNEL_BINDINGS = {
     "css_stream_mel_host": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.c_int64, C.POINTER(CssStreamMelJob), C.c_int32]),
 }
 STREAM_KERNEL_JOBS = 64                          # CSS_STREAM_KERNEL_JOBS
+# the entry points include/css_mi355_handoff_kernels.h declares (the window kernels and the queued sessions' hand-off kernels of
+# csrc/handoff.hip on caller data), the seventeenth table load() applies (a ..._BINDINGS table, as the three above)
+HANDOFF_KERNEL_BINDINGS = {
+    "css_session_scan_host": (C.c_int, [_P, C.POINTER(CssSessionScanJob)]),
+    "css_session_gather_host": (C.c_int, [_P, C.POINTER(CssSessionGatherJob)]),
+    "css_session_norm_host": (C.c_int, [_P, C.POINTER(CssSessionNormJob)]),
+    "css_session_windows_host": (C.c_int, [_P, C.POINTER(CssSessionWindowsJob)]),
+    "css_stream_windows_host": (C.c_int, [_P, C.POINTER(CssStreamWindowJob), C.c_int32, _P, C.c_int64]),
+}
+WINDOW_KERNEL_ITEMS = 64                         # CSS_WINDOW_KERNEL_ITEMS
 ARRAY_MIN_MICS, ARRAY_MAX_MICS = 2, 8            # CSS_ARRAY_MIN_MICS, CSS_ARRAY_MAX_MICS
 SESSION_SCAN_CHUNK = 1024                        # CSS_SESSION_SCAN_CHUNK: the keep-scan kernel's step, in gate frames / sample blocks
 RESAMPLE_TILE = 256                              # output samples per block of the two resampling kernels (resample.hip RS_TILE)
@@ -581,7 +638,7 @@ def load() -> C.CDLL:
                               list(SIGNATURES_STREAM_OUT.items()) + list(SIGNATURES_BACKEND.items()) +
                               list(ARRAY_SIGNATURES.items()) + list(SESSION_RATE_SIGNATURES.items()) +
                               list(SESSION_WINDOW_BINDINGS.items()) + list(RATE_KERNEL_BINDINGS.items()) +
-                              list(STREAM_KERNEL_BINDINGS.items())):
+                              list(STREAM_KERNEL_BINDINGS.items()) + list(HANDOFF_KERNEL_BINDINGS.items())):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -1413,8 +1470,8 @@ class Handle:
     #      (include/css_mi355_stream_kernels.h; tests/test_hip_stream_kernels.py).  A job is a dict of the descriptor's scalar fields
     #      and its arrays (the WHOLE allocations; None or absent: not passed); the arrays a launch may write are copied first, and
     #      every call returns one dict per job with them as the launch left them.
-    def _stream_kernel_table(self, kind, jobs):
-        ins, outs = STREAM_KERNEL_ARRAYS[kind.__name__]
+    def _stream_kernel_table(self, kind, jobs, arrays=None):
+        ins, outs = (arrays or STREAM_KERNEL_ARRAYS)[kind.__name__]
         tab = (kind * len(jobs))()
         keep, left = [], []
         for d, j in zip(tab, jobs):
@@ -1424,6 +1481,8 @@ class Handle:
                 a = j.pop(name, None)
                 if a is None:
                     continue
+                if dtype is None:   # (float32, or float16 words: the job's f16 says which)
+                    dtype = np.uint16 if int(j.get("f16", 0)) else np.float32
                 a = np.ascontiguousarray(a, dtype=dtype).reshape(-1)
                 a = a.copy() if out else a
                 getattr(d, name).p, getattr(d, name).elems = a.ctypes.data, a.size
@@ -1472,6 +1531,43 @@ class Handle:
         for d in tab:
             d.has_ring, d.has_pvmax = int(bool(d.ring.p)), int(bool(d.pvmax.p))
         return self._rate_left(self.lib.css_stream_mel_host(self.h, int(S), _np_ptr(spec), spec.size, int(ld), tab, len(jobs)), left)
+
+    # ---- the window kernels and the queued sessions' hand-off kernels of csrc/handoff.hip on caller data
+    #      (include/css_mi355_handoff_kernels.h; tests/test_hip_window_kernels.py).  A job is a dict as above; an array with an
+    #      element offset field is the WHOLE allocation, the offset's elements in front included.
+    def _handoff_kernel(self, entry, kind, job):
+        tab, keep, left = self._stream_kernel_table(kind, [job], HANDOFF_KERNEL_ARRAYS)
+        return tab, self._rate_left(entry(self.h, tab), left)[0]
+
+    def session_scan(self, job):
+        """launch_session_keep_scan (css_session_scan_host) -> {psum, regs, offs, st, n_new, n_ranges, ranges_out, n_frames_out,
+        n_ranges_out}"""
+        return self._handoff_kernel(self.lib.css_session_scan_host, CssSessionScanJob, job)[1]
+
+    def session_gather(self, job):
+        """launch_session_gather (css_session_gather_host) -> {operand}"""
+        return self._handoff_kernel(self.lib.css_session_gather_host, CssSessionGatherJob, job)[1]
+
+    def session_norm(self, job):
+        """launch_session_norm (css_session_norm_host) -> {out}"""
+        return self._handoff_kernel(self.lib.css_session_norm_host, CssSessionNormJob, job)[1]
+
+    def session_windows(self, job):
+        """launch_session_windows (css_session_windows_host); win / whole are float32, or uint16 words of float16 with f16
+        -> {win, whole, n_windows_out, window_max_out, n_win_jobs, n_whole_jobs}"""
+        job = dict(job, has_win=int(job.get("win") is not None), has_whole=int(job.get("whole") is not None))
+        tab, keep, left = self._stream_kernel_table(CssSessionWindowsJob, [job], HANDOFF_KERNEL_ARRAYS)
+        rc = self.lib.css_session_windows_host(self.h, tab)
+        left[0]["n_win_jobs"], left[0]["n_whole_jobs"] = int(tab[0].n_win_jobs), int(tab[0].n_whole_jobs)
+        return self._rate_left(rc, left)[0]
+
+    def stream_windows(self, items, res):
+        """launch_stream_windows per 32 items (css_stream_windows_host); res: WINDOW_OUT rows, item i takes row i
+        -> ([{out}], res as the launches left it)"""
+        res = np.array(res, dtype=WINDOW_OUT).reshape(-1)
+        items = [dict(j, has_pv=int(j.get("pv") is not None)) for j in items]
+        tab, keep, left = self._stream_kernel_table(CssStreamWindowJob, items, HANDOFF_KERNEL_ARRAYS)
+        return self._rate_left(self.lib.css_stream_windows_host(self.h, tab, len(items), _np_ptr(res), res.size), (left, res))
 
     # ---- the kernels of csrc/mvdr.hip and csrc/stitch.hip on caller data (include/css_mi355_backend.h;
     #      tests/test_hip_backend_kernels.py).  Arrays are the WHOLE allocations (None where a form takes none); the arrays a form

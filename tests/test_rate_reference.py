@@ -34,7 +34,7 @@ def test_header_library_and_binding_agree():
     declared = re.findall(r"\bint\s+(css_\w+)\s*\(", text)
     assert sorted(declared) == sorted(NAMES) == sorted(L.RATE_KERNEL_BINDINGS)
     tables = {n: getattr(L, n) for n in dir(L) if n.startswith("SIGNATURES") or n.endswith("_SIGNATURES") or n.endswith("_BINDINGS")}
-    assert len(tables) == 16
+    assert len(tables) == 17
     for n, t in tables.items():
         assert n == "RATE_KERNEL_BINDINGS" or not set(L.RATE_KERNEL_BINDINGS) & set(t), n
     for f in os.listdir(os.path.join(ROOT, "include")):

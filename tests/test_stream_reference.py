@@ -35,11 +35,14 @@ def test_header_library_and_binding_agree():
     for n in dir(L):
         if (n.startswith("SIGNATURES") or n.endswith("_SIGNATURES") or n.endswith("_BINDINGS")) and n != "STREAM_KERNEL_BINDINGS":
             assert not set(L.STREAM_KERNEL_BINDINGS) & set(getattr(L, n)), n
-    assert len([n for n in dir(L) if n.startswith("SIGNATURES") or n.endswith("_SIGNATURES") or n.endswith("_BINDINGS")]) == 16
+    assert len([n for n in dir(L) if n.startswith("SIGNATURES") or n.endswith("_SIGNATURES") or n.endswith("_BINDINGS")]) == 17
     for f in os.listdir(os.path.join(ROOT, "include")):
         if f != HEADER:
             other = open(os.path.join(ROOT, "include", f)).read()
             for name in NAMES + DESCS:
+                if name == "CssKArray" and f == "css_mi355_handoff_kernels.h":    # (its companion includes this header and uses the type)
+                    assert f'#include "{HEADER}"' in other and "typedef struct CssKArray" not in other
+                    continue
                 assert not re.search(rf"\b{name}\b", other), f"{name} belongs to {HEADER} alone"
     for name in NAMES:
         params = re.search(rf"\b{name}\s*\((.*?)\)\s*;", text, flags=re.S).group(1).split(",")
