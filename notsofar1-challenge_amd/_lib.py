@@ -650,6 +650,22 @@ def _np_ptr(a: np.ndarray):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _flat(a, dtype=np.float32, copy=False):
+    """`a` as a flat contiguous array of `dtype` (with `copy`: one of its own, which a launch may write); None stays None."""
+    if a is None:
+        return None
+    a = np.ascontiguousarray(a, dtype=dtype).reshape(-1)
+    return a.copy() if copy else a
+
+
+def _ptr(a):
+    return None if a is None else _np_ptr(a)
+
+
+def _size(a) -> int:
+    return 0 if a is None else a.size
+
+
 def check(handle, rc: int):
     if rc != CSS_OK:
         text = load().css_last_error(handle).decode("utf-8", "replace")
@@ -1286,16 +1302,15 @@ class Handle:
                   z=None, ys=None):
         """One LayerNorm launch (css_layernorm_host; the header describes the forms).  x, y, z, ys are the WHOLE flat float32
         allocations (None: the launch does not get that pointer).  Returns (x, y, z, ys) as the launch left them."""
-        flat = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float32).reshape(-1).copy()
-        x, y, z, ys = flat(x), flat(y), flat(z), flat(ys)
-        w, b, w2, b2 = flat(w), flat(b), flat(w2), flat(b2)
+        x, y, z, ys = (_flat(a, copy=True) for a in (x, y, z, ys))
+        w, b, w2, b2 = _flat(w), _flat(b), _flat(w2), _flat(b2)
         outs = [a.size for a in (y, z, ys) if a is not None]
         if len(set(outs)) > 1:
             raise ValueError("y, z and ys are allocations of one length")
         d = CssLayerNormDesc(form=int(form), rows=int(rows), D=int(D), inplace=int(bool(inplace)), x_floats=x.size,
                              out_floats=outs[0] if outs else 0)
-        ptr = lambda a: None if a is None else _np_ptr(a)
-        check(self.h, self.lib.css_layernorm_host(self.h, C.byref(d), ptr(x), ptr(w), ptr(b), ptr(w2), ptr(b2), ptr(y), ptr(z), ptr(ys)))
+        check(self.h, self.lib.css_layernorm_host(self.h, C.byref(d), _ptr(x), _ptr(w), _ptr(b), _ptr(w2), _ptr(b2), _ptr(y), _ptr(z),
+                                                  _ptr(ys)))
         return x, y, z, ys
 
     def conv_module(self, form: int, x: np.ndarray, nseg: int, T: int, D: int, taps: int, ln_w, ln_b, pw, dw_wt, dw_b, bn_alpha,
@@ -1303,9 +1318,8 @@ class Handle:
         """The conv module, fused (form 0) or as its two-kernel fallback in place (form 1) (css_conv_module_host).  Returns
         (launched, x, x_out, z, zs): whole allocations as the launches left them; launched is False when the fused kernel does
         not cover (D, taps) or the device refused its LDS."""
-        flat = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float32).reshape(-1).copy()
-        x, x_out, z, zs = flat(x), flat(x_out), flat(z), flat(zs)
-        ops = [flat(a) for a in (ln_w, ln_b, pw, dw_wt, dw_b, bn_alpha, bn_beta, ln2_w, ln2_b)]
+        x, x_out, z, zs = (_flat(a, copy=True) for a in (x, x_out, z, zs))
+        ops = [_flat(a) for a in (ln_w, ln_b, pw, dw_wt, dw_b, bn_alpha, bn_beta, ln2_w, ln2_b)]
         outs = [a.size for a in (x_out, z, zs) if a is not None]
         if len(set(outs)) > 1:
             raise ValueError("x_out, z and zs are allocations of one length")
@@ -1313,9 +1327,8 @@ class Handle:
             raise ValueError("pw [6], dw_wt [taps][D], every other operand [D]")
         d = CssConvModuleDesc(form=int(form), nseg=int(nseg), T=int(T), D=int(D), taps=int(taps), x_floats=x.size,
                               out_floats=outs[0] if outs else 0)
-        ptr = lambda a: None if a is None else _np_ptr(a)
         launched = C.c_int32(-1)
-        check(self.h, self.lib.css_conv_module_host(self.h, C.byref(d), ptr(x), *[ptr(a) for a in ops], ptr(x_out), ptr(z), ptr(zs),
+        check(self.h, self.lib.css_conv_module_host(self.h, C.byref(d), _ptr(x), *[_ptr(a) for a in ops], _ptr(x_out), _ptr(z), _ptr(zs),
                                                     C.byref(launched)))
         return bool(launched.value), x, x_out, z, zs
 
@@ -1324,8 +1337,7 @@ class Handle:
         """QKV product + relative-position attention (css_attention_host; mode 0 exact float32, 1 split-f16, 2 any length).
         Returns (qkv, ctx): the allocations of nseg * T + slack_rows rows of 3 D / D floats as the launches left them; every
         float they did not write holds `canary`."""
-        flat = lambda a: np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
-        x, w, bias, pe = flat(x), flat(w), flat(bias), flat(pe)
+        x, w, bias, pe = _flat(x), _flat(w), _flat(bias), _flat(pe)
         K = w.size // (3 * D)
         rows = nseg * T + int(slack_rows)
         qkv = np.empty(rows * 3 * D, np.float32)
@@ -1344,34 +1356,30 @@ class Handle:
     def analysis(self, x: np.ndarray, C_: int, x_stride: int, t_lo: int, t_hi: int, row_ld: int, out: np.ndarray, *, offset: int = 0,
                  window: int = 0, phase=None):
         """launch_stft_fft (css_analysis_host).  Returns (out, phase)."""
-        flat = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float32).reshape(-1).copy()
-        x, out, phase = np.ascontiguousarray(x, dtype=np.float32).reshape(-1), flat(out), flat(phase)
+        x, out, phase = _flat(x), _flat(out, copy=True), _flat(phase, copy=True)
         d = CssAnalysisDesc(C=int(C_), t_lo=int(t_lo), t_hi=int(t_hi), offset=int(offset), window=int(window),
                             want_phase=int(phase is not None), x_stride=int(x_stride), row_ld=int(row_ld), x_floats=x.size,
-                            out_floats=out.size, phase_floats=0 if phase is None else phase.size)
-        check(self.h, self.lib.css_analysis_host(self.h, C.byref(d), _np_ptr(x), _np_ptr(out), None if phase is None else _np_ptr(phase)))
+                            out_floats=out.size, phase_floats=_size(phase))
+        check(self.h, self.lib.css_analysis_host(self.h, C.byref(d), _np_ptr(x), _np_ptr(out), _ptr(phase)))
         return out, phase
 
     def features_host(self, X: np.ndarray, C_: int, F: int, T_ld: int, stft_frames: int, seg_lo: int, nseg: int, T: int, hop: int,
                       Kp: int, cfg: "CssFeatureCfg", in_bias, in_scale, feat: np.ndarray, *, split_out: int = 0, PH=None):
         """launch_features (css_features_host).  Returns feat."""
-        f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
-        X, in_bias, in_scale, feat = f32(X), f32(in_bias), f32(in_scale), f32(feat).copy()
-        PH = None if PH is None else f32(PH)
+        X, in_bias, in_scale, feat, PH = _flat(X), _flat(in_bias), _flat(in_scale), _flat(feat, copy=True), _flat(PH)
         d = CssFeaturesDesc(C=int(C_), F=int(F), nseg=int(nseg), T=int(T), hop=int(hop), Kp=int(Kp), split_out=int(split_out),
                             T_ld=int(T_ld), stft_frames=int(stft_frames), seg_lo=int(seg_lo), x_floats=X.size,
-                            ph_floats=0 if PH is None else PH.size, feat_floats=feat.size, cfg=cfg)
+                            ph_floats=_size(PH), feat_floats=feat.size, cfg=cfg)
         if in_bias.size != F * (1 + cfg.num_pairs) or in_scale.size != in_bias.size:
             raise ValueError("in_bias, in_scale [F (1 + pairs)]")
-        check(self.h, self.lib.css_features_host(self.h, C.byref(d), _np_ptr(X), None if PH is None else _np_ptr(PH), _np_ptr(in_bias),
+        check(self.h, self.lib.css_features_host(self.h, C.byref(d), _np_ptr(X), _ptr(PH), _np_ptr(in_bias),
                                                  _np_ptr(in_scale), _np_ptr(feat)))
         return feat
 
     def synthesis_tail(self, form: int, src: np.ndarray, out: np.ndarray, *, t_lo=(), t_hi=(), level=None, **fields):
         """launch_wave_ola (0), launch_join_shards (1), launch_planes_to_rows (2) (css_synthesis_tail_host); fields are the
         descriptor's.  level: None (absent) or the word.  Returns out."""
-        src = np.ascontiguousarray(src, dtype=np.float32).reshape(-1)
-        out = np.ascontiguousarray(out, dtype=np.float32).reshape(-1).copy()
+        src, out = _flat(src), _flat(out, copy=True)
         d = CssSynthesisTailDesc(form=int(form), has_level=int(level is not None), level=int(level or 0), in_floats=src.size,
                                  out_floats=out.size, **{k: int(v) for k, v in fields.items()})
         for k, (lo, hi) in enumerate(zip(t_lo, t_hi)):
@@ -1586,17 +1594,14 @@ class Handle:
         return self._mvdr_host(self.lib.css_mvdr_array_host, CssMvdrArrayDesc, CssMvdrArraySet, form, **kw)
 
     def _mvdr_host(self, entry, Desc, Set, form: int, *, X=None, masks=None, override=None, scm=None, bfw=None, sep=None, sets=(), **fields):
-        arr = lambda a, t, own: None if a is None else (np.array(a, dtype=t).reshape(-1) if own else np.ascontiguousarray(a, dtype=t).reshape(-1))
-        X, masks, override = arr(X, np.float32, False), arr(masks, np.float32, False), arr(override, np.uint8, False)
-        scm, bfw, sep = arr(scm, np.float64, form == 0), arr(bfw, np.float64, form in (1, 2)), arr(sep, np.float32, form >= 3)
-        n = lambda a: 0 if a is None else a.size
-        d = Desc(form=int(form), n_sets=len(sets), x_floats=n(X), mask_floats=n(masks), override_bytes=n(override),
-                 scm_doubles=n(scm), bfw_doubles=n(bfw), sep_floats=n(sep),
+        X, masks, override = _flat(X), _flat(masks), _flat(override, np.uint8)
+        scm, bfw, sep = _flat(scm, np.float64, form == 0), _flat(bfw, np.float64, form in (1, 2)), _flat(sep, np.float32, form >= 3)
+        d = Desc(form=int(form), n_sets=len(sets), x_floats=_size(X), mask_floats=_size(masks), override_bytes=_size(override),
+                 scm_doubles=_size(scm), bfw_doubles=_size(bfw), sep_floats=_size(sep),
                  **{k: (float(v) if k == "mask_floor" else int(v)) for k, v in fields.items()})
         for i, e in enumerate(sets):
             d.sets[i] = Set(*(int(v) for v in e))
-        p = lambda a: None if a is None else _np_ptr(a)
-        check(self.h, entry(self.h, C.byref(d), p(X), p(masks), p(override), p(scm), p(bfw), p(sep)))
+        check(self.h, entry(self.h, C.byref(d), _ptr(X), _ptr(masks), _ptr(override), _ptr(scm), _ptr(bfw), _ptr(sep)))
         return (scm, bfw, bfw, sep, sep)[int(form)]
 
     def stitch_host(self, form: int, *, masks=None, sep=None, windows=None, costs=None, perms=None, mask_st=None, activity=None,
@@ -1605,26 +1610,24 @@ class Handle:
         launch_pit_scan (2), launch_ola_masks (3), launch_morphology (4), launch_ola_stft (5) (css_stitch_host); fields are the
         descriptor's; level: None (absent) or the word.  Returns what the form writes: costs; costs; perms; (mask_st, activity,
         act_b); (act_tmp, act_final); Y."""
-        arr = lambda a, t, own: None if a is None else (np.array(a, dtype=t).reshape(-1) if own else np.ascontiguousarray(a, dtype=t).reshape(-1))
-        masks, sep, windows = arr(masks, np.float32, False), arr(sep, np.float32, False), arr(windows, np.float32, False)
-        costs, perms = arr(costs, np.float64, form <= 1), arr(perms, np.int32, form == 2)
-        mask_st, activity, act_b = arr(mask_st, np.float32, True), arr(activity, np.float32, True), arr(act_b, np.uint8, form == 3)
-        act_tmp, act_final, Y = arr(act_tmp, np.uint8, True), arr(act_final, np.uint8, form == 4), arr(Y, np.float32, True)
-        n = lambda a: 0 if a is None else a.size
+        masks, sep, windows = _flat(masks), _flat(sep), _flat(windows)
+        costs, perms = _flat(costs, np.float64, form <= 1), _flat(perms, np.int32, form == 2)
+        mask_st, activity, act_b = _flat(mask_st, copy=True), _flat(activity, copy=True), _flat(act_b, np.uint8, form == 3)
+        act_tmp, act_final, Y = _flat(act_tmp, np.uint8, True), _flat(act_final, np.uint8, form == 4), _flat(Y, copy=True)
         acts = [a.size for a in (act_b, act_tmp, act_final) if a is not None]
         if len(set(acts)) > 1:
             raise ValueError("act_b, act_tmp and act_final have one length")
         if windows is not None and windows.size != 3 * int(fields["T"]):
             raise ValueError("windows [3][T]")
         d = CssStitchDesc(form=int(form), n_sets=len(sets), has_level=int(level is not None), level=int(level or 0),
-                          mask_floats=n(masks), sep_floats=n(sep), costs_doubles=n(costs), perms_ints=n(perms),
-                          mask_st_floats=n(mask_st), activity_floats=n(activity), act_bytes=acts[0] if acts else 0, y_floats=n(Y),
+                          mask_floats=_size(masks), sep_floats=_size(sep), costs_doubles=_size(costs), perms_ints=_size(perms),
+                          mask_st_floats=_size(mask_st), activity_floats=_size(activity), act_bytes=acts[0] if acts else 0,
+                          y_floats=_size(Y),
                           **{k: (float(v) if k == "activity_th" else int(v)) for k, v in fields.items()})
         for i, e in enumerate(sets):
             d.sets[i] = CssStitchSet(*(int(v) for v in e))
-        p = lambda a: None if a is None else _np_ptr(a)
-        check(self.h, self.lib.css_stitch_host(self.h, C.byref(d), p(masks), p(sep), p(windows), p(costs), p(perms), p(mask_st),
-                                               p(activity), p(act_b), p(act_tmp), p(act_final), p(Y)))
+        check(self.h, self.lib.css_stitch_host(self.h, C.byref(d), _ptr(masks), _ptr(sep), _ptr(windows), _ptr(costs), _ptr(perms),
+                                               _ptr(mask_st), _ptr(activity), _ptr(act_b), _ptr(act_tmp), _ptr(act_final), _ptr(Y)))
         return (costs, costs, perms, (mask_st, activity, act_b), (act_tmp, act_final), Y)[int(form)]
 
     # ---- RCCL through the C ABI (css_comm_*): what a host in another language would call

@@ -4,24 +4,14 @@
 #include <vector>
 
 #include "api_ctx.hpp"
+#include "api_kernel_stage.hpp"   // (Stager, stage_and_upload, download_all)
 #include "../../include/css_mi355_backend.h"
 #include "../../include/css_mi355_array.h"
 
 using namespace css;
+using namespace css::kstage;
 
 namespace {
-
-constexpr int64_t HOST_CAP = (int64_t)1 << 28;   // elements per array: far below the kernels' 32-bit grids
-
-// a staging area cut into regions that each start on 256 bytes
-struct Stage {
-    size_t bytes = 0;
-    size_t take(int64_t n, size_t elem) {
-        const size_t at = bytes;
-        bytes += ((size_t)std::max<int64_t>(n, 0) * elem + 255) / 256 * 256;
-        return at;
-    }
-};
 
 inline bool is_permutation(const int32_t* p, int S) {
     unsigned seen = 0;
@@ -98,32 +88,27 @@ int mvdr_host_impl(css_handle_t h, const Desc* d, const float* X, const float* m
         if (need_sep && d->sep_floats < segs * sep_per) return bad("sep is shorter than its description");
     }
 
-    HIPCHK(h, hipSetDevice(h->device));
-    Stage sg;
-    const size_t o_x = sg.take(need_x ? d->x_floats : 0, 4), o_m = sg.take(need_m ? d->mask_floats : 0, 4);
-    const size_t o_ov = sg.take(form == 0 && wta_override ? d->override_bytes : 0, 1);
-    const size_t o_scm = sg.take(need_scm ? d->scm_doubles : 0, 8), o_bfw = sg.take(need_bfw ? d->bfw_doubles : 0, 8);
-    const size_t o_sep = sg.take(need_sep ? d->sep_floats : 0, 4), o_scr = sg.take(form == 4 ? d->nseg : 0, 8);
+    // an array a form does not take is absent, whatever the caller passed; each form brings back what its launch writes
+    Stager sg;
+    const size_t o_x = sg.arr(need_x ? X : nullptr, d->x_floats, 4, UP), o_m = sg.arr(need_m ? masks : nullptr, d->mask_floats, 4, UP);
+    const size_t o_ov = sg.arr(form == 0 ? wta_override : nullptr, d->override_bytes, 1, UP);
+    const size_t o_scm = sg.arr(need_scm ? scm : nullptr, d->scm_doubles, 8, form == 0 ? UP | DOWN : UP);
+    const size_t o_bfw = sg.arr(need_bfw ? bfw : nullptr, d->bfw_doubles, 8, form == 1 || form == 2 ? UP | DOWN : UP);
+    const size_t o_sep = sg.arr(need_sep ? sep : nullptr, d->sep_floats, 4, UP | DOWN);
+    const size_t o_scr = sg.scratch(form == 4 ? d->nseg : 0, 8);
+    char* base = nullptr;
     int rc;
-    if ((rc = ensure(h, h->stage, sg.bytes + 256)) != CSS_OK) return rc;
-    char* base = (char*)h->stage.p;
+    if ((rc = stage_and_upload(h, sg, &base)) != CSS_OK) return rc;
     hipStream_t st = h->stream;
-    if (need_x) HIPCHK(h, hipMemcpyAsync(base + o_x, X, (size_t)d->x_floats * 4, hipMemcpyHostToDevice, st));
-    if (need_m) HIPCHK(h, hipMemcpyAsync(base + o_m, masks, (size_t)d->mask_floats * 4, hipMemcpyHostToDevice, st));
-    if (form == 0 && wta_override) HIPCHK(h, hipMemcpyAsync(base + o_ov, wta_override, (size_t)d->override_bytes, hipMemcpyHostToDevice, st));
-    if (need_scm) HIPCHK(h, hipMemcpyAsync(base + o_scm, scm, (size_t)d->scm_doubles * 8, hipMemcpyHostToDevice, st));
-    if (need_bfw) HIPCHK(h, hipMemcpyAsync(base + o_bfw, bfw, (size_t)d->bfw_doubles * 8, hipMemcpyHostToDevice, st));
-    if (need_sep) HIPCHK(h, hipMemcpyAsync(base + o_sep, sep, (size_t)d->sep_floats * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipStreamSynchronize(st));   // (the arrays may be pageable host memory of the caller)
 
     MvdrArgs a{};
-    a.X = need_x ? (const float*)(base + o_x) : nullptr; a.T_ld = d->T_ld; a.stft_frames = d->stft_frames; a.C = C; a.F = F;
-    a.masks = need_m ? (const float*)(base + o_m) : nullptr; a.mask_ld = d->mask_ld;
+    a.X = Stager::dev<const float>(base, o_x); a.T_ld = d->T_ld; a.stft_frames = d->stft_frames; a.C = C; a.F = F;
+    a.masks = Stager::dev<const float>(base, o_m); a.mask_ld = d->mask_ld;
     a.S = S; a.T = T; a.hop = hop; a.seg_lo = d->seg_lo; a.nseg = d->nseg;
-    a.wta_override = form == 0 && wta_override ? (const uint8_t*)(base + o_ov) : nullptr;
-    a.scm = need_scm ? (double*)(base + o_scm) : nullptr;
-    a.bfw = need_bfw ? (double*)(base + o_bfw) : nullptr;
-    a.sep = need_sep ? (float*)(base + o_sep) : nullptr;
+    a.wta_override = Stager::dev<const uint8_t>(base, o_ov);
+    a.scm = Stager::dev<double>(base, o_scm);
+    a.bfw = Stager::dev<double>(base, o_bfw);
+    a.sep = Stager::dev<float>(base, o_sep);
     a.mask_floor = d->mask_floor; a.use_mvdr = d->use_mvdr;
     switch (form) {
     case 0:
@@ -140,14 +125,9 @@ int mvdr_host_impl(css_handle_t h, const Desc* d, const float* X, const float* m
         break;
     }
     case 3: launch_beamform(a, st); break;
-    default: launch_segment_power_norm(a, (double*)(base + o_scr), st); break;
+    default: launch_segment_power_norm(a, Stager::dev<double>(base, o_scr), st); break;
     }
-    if (form == 0) HIPCHK(h, hipMemcpyAsync(scm, base + o_scm, (size_t)d->scm_doubles * 8, hipMemcpyDeviceToHost, st));
-    if (form == 1 || form == 2) HIPCHK(h, hipMemcpyAsync(bfw, base + o_bfw, (size_t)d->bfw_doubles * 8, hipMemcpyDeviceToHost, st));
-    if (form >= 3) HIPCHK(h, hipMemcpyAsync(sep, base + o_sep, (size_t)d->sep_floats * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    HIPCHK(h, hipGetLastError());
-    return CSS_OK;
+    return download_all(h, sg, base);
 }
 
 }  // namespace
@@ -242,48 +222,38 @@ int css_stitch_host(css_handle_t h, const CssStitchDesc* d, const float* masks, 
         }
     }
 
-    HIPCHK(h, hipSetDevice(h->device));
-    Stage sg;
-    const size_t o_m = sg.take(need_m ? d->mask_floats : 0, 4), o_sep = sg.take(need_sep ? d->sep_floats : 0, 4);
-    const size_t o_w = sg.take(need_w ? 3 * (int64_t)T : 0, 4), o_c = sg.take(need_costs ? d->costs_doubles : 0, 8);
-    const size_t o_p = sg.take(need_perms ? d->perms_ints : 0, 4), o_st = sg.take(need_st ? d->mask_st_floats : 0, 4);
-    const size_t o_a = sg.take(need_st ? d->activity_floats : 0, 4), o_b = sg.take(need_b ? d->act_bytes : 0, 1);
-    const size_t o_t = sg.take(need_tmp ? d->act_bytes : 0, 1), o_f = sg.take(need_fin ? d->act_bytes : 0, 1);
-    const size_t o_y = sg.take(need_y ? d->y_floats : 0, 4), o_lv = sg.take(1, 4);
-    const size_t o_scr = sg.take(is_cost ? (int64_t)pit_cost_scratch_bytes(total_b) : 0, 1);
-    int rc;
-    if ((rc = ensure(h, h->stage, sg.bytes + 256)) != CSS_OK) return rc;
-    char* base = (char*)h->stage.p;
-    hipStream_t st = h->stream;
+    // an array a form does not take is absent, whatever the caller passed; each form brings back what its launch writes
     const uint32_t level = d->level;
-    auto up = [&](size_t off, const void* src, int64_t n, size_t elem) { return hipMemcpyAsync(base + off, src, (size_t)n * elem, hipMemcpyHostToDevice, st); };
-    auto down = [&](void* dst, size_t off, int64_t n, size_t elem) { return hipMemcpyAsync(dst, base + off, (size_t)n * elem, hipMemcpyDeviceToHost, st); };
-    if (need_m) HIPCHK(h, up(o_m, masks, d->mask_floats, 4));
-    if (need_sep) HIPCHK(h, up(o_sep, sep, d->sep_floats, 4));
-    if (need_w) HIPCHK(h, up(o_w, windows, 3 * (int64_t)T, 4));
-    if (need_costs) HIPCHK(h, up(o_c, costs, d->costs_doubles, 8));
-    if (need_perms) HIPCHK(h, up(o_p, perms, d->perms_ints, 4));
-    if (need_st) { HIPCHK(h, up(o_st, mask_st, d->mask_st_floats, 4)); HIPCHK(h, up(o_a, activity, d->activity_floats, 4)); }
-    if (need_b) HIPCHK(h, up(o_b, act_b, d->act_bytes, 1));
-    if (need_tmp) HIPCHK(h, up(o_t, act_tmp, d->act_bytes, 1));
-    if (need_fin) HIPCHK(h, up(o_f, act_final, d->act_bytes, 1));
-    if (need_y) HIPCHK(h, up(o_y, Y, d->y_floats, 4));
-    HIPCHK(h, up(o_lv, &level, 1, 4));
-    HIPCHK(h, hipStreamSynchronize(st));   // (the arrays may be pageable host memory of the caller)
+    Stager sg;
+    const size_t o_m = sg.arr(need_m ? masks : nullptr, d->mask_floats, 4, UP), o_sep = sg.arr(need_sep ? sep : nullptr, d->sep_floats, 4, UP);
+    const size_t o_w = sg.arr(need_w ? windows : nullptr, 3 * (int64_t)T, 4, UP);
+    const size_t o_c = sg.arr(need_costs ? costs : nullptr, d->costs_doubles, 8, is_cost ? UP | DOWN : UP);
+    const size_t o_p = sg.arr(need_perms ? perms : nullptr, d->perms_ints, 4, form == 2 ? UP | DOWN : UP);
+    const size_t o_st = sg.arr(need_st ? mask_st : nullptr, d->mask_st_floats, 4, UP | DOWN);
+    const size_t o_a = sg.arr(need_st ? activity : nullptr, d->activity_floats, 4, UP | DOWN);
+    const size_t o_b = sg.arr(need_b ? act_b : nullptr, d->act_bytes, 1, form == 3 ? UP | DOWN : UP);
+    const size_t o_t = sg.arr(need_tmp ? act_tmp : nullptr, d->act_bytes, 1, UP | DOWN);
+    const size_t o_f = sg.arr(need_fin ? act_final : nullptr, d->act_bytes, 1, form == 4 ? UP | DOWN : UP);
+    const size_t o_y = sg.arr(need_y ? Y : nullptr, d->y_floats, 4, UP | DOWN), o_lv = sg.arr(&level, 1, 4, UP);
+    const size_t o_scr = sg.scratch(is_cost ? (int64_t)pit_cost_scratch_bytes(total_b) : 0, 1);
+    char* base = nullptr;
+    int rc;
+    if ((rc = stage_and_upload(h, sg, &base)) != CSS_OK) return rc;
+    hipStream_t st = h->stream;
 
     StitchArgs a{};
-    a.masks = need_m ? (const float*)(base + o_m) : nullptr; a.mask_ld = d->mask_ld;
-    a.sep = need_sep ? (const float*)(base + o_sep) : nullptr;
+    a.masks = Stager::dev<const float>(base, o_m); a.mask_ld = d->mask_ld;
+    a.sep = Stager::dev<const float>(base, o_sep);
     a.S = S; a.F = F; a.T = T; a.hop = hop; a.num_segments = NS; a.T_long = TL;
-    if (need_w) { a.w_first = (const float*)(base + o_w); a.w_mid = a.w_first + T; a.w_last = a.w_mid + T; }
-    a.perms = need_perms ? (const int32_t*)(base + o_p) : nullptr;
-    a.mask_st = need_st ? (float*)(base + o_st) : nullptr; a.activity = need_st ? (float*)(base + o_a) : nullptr;
-    a.act_b = need_b ? (uint8_t*)(base + o_b) : nullptr; a.act_tmp = need_tmp ? (uint8_t*)(base + o_t) : nullptr;
-    a.act_final = need_fin ? (uint8_t*)(base + o_f) : nullptr;
+    if (need_w) { a.w_first = Stager::dev<const float>(base, o_w); a.w_mid = a.w_first + T; a.w_last = a.w_mid + T; }
+    a.perms = Stager::dev<const int32_t>(base, o_p);
+    a.mask_st = Stager::dev<float>(base, o_st); a.activity = Stager::dev<float>(base, o_a);
+    a.act_b = Stager::dev<uint8_t>(base, o_b); a.act_tmp = Stager::dev<uint8_t>(base, o_t);
+    a.act_final = Stager::dev<uint8_t>(base, o_f);
     a.activity_th = d->activity_th; a.dilation = d->dilation; a.erosion = d->erosion;
-    a.Y = need_y ? (float*)(base + o_y) : nullptr; a.KIp = d->KIp; a.y_split = d->y_split;
-    a.level = form == 5 && d->has_level ? (const unsigned int*)(base + o_lv) : nullptr;
-    double* cd = need_costs ? (double*)(base + o_c) : nullptr;
+    a.Y = Stager::dev<float>(base, o_y); a.KIp = d->KIp; a.y_split = d->y_split;
+    a.level = form == 5 && d->has_level ? Stager::dev<const unsigned int>(base, o_lv) : nullptr;
+    double* cd = Stager::dev<double>(base, o_c);
     switch (form) {
     case 0: launch_pit_costs(a, d->loss, d->input, lo, hi, (double*)(base + o_scr), cd, st); break;
     case 1: {
@@ -306,17 +276,7 @@ int css_stitch_host(css_handle_t h, const CssStitchDesc* d, const float* masks, 
     case 4: launch_morphology(a, lo, hi, st); break;
     default: launch_ola_stft(a, lo, hi, st); break;
     }
-    if (is_cost) HIPCHK(h, down(costs, o_c, d->costs_doubles, 8));
-    if (form == 2) HIPCHK(h, down(perms, o_p, d->perms_ints, 4));
-    if (form == 3) {
-        HIPCHK(h, down(mask_st, o_st, d->mask_st_floats, 4)); HIPCHK(h, down(activity, o_a, d->activity_floats, 4));
-        HIPCHK(h, down(act_b, o_b, d->act_bytes, 1));
-    }
-    if (form == 4) { HIPCHK(h, down(act_tmp, o_t, d->act_bytes, 1)); HIPCHK(h, down(act_final, o_f, d->act_bytes, 1)); }
-    if (form == 5) HIPCHK(h, down(Y, o_y, d->y_floats, 4));
-    HIPCHK(h, hipStreamSynchronize(st));
-    HIPCHK(h, hipGetLastError());
-    return CSS_OK;
+    return download_all(h, sg, base);
 }
 
 }  // extern "C"

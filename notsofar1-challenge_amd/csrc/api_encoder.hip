@@ -2,15 +2,13 @@
 // the companion of css_gemm_host).  Every entry checks first, then stages in h->stage, launches exactly what masknet_lane
 // (api_stages.hip) launches, downloads every allocation a launch could have written and synchronises.
 #include "api_ctx.hpp"
+#include "api_kernel_stage.hpp"   // (Stager, stage_and_upload, download_all)
 #include "../../include/css_mi355_encoder.h"
 
 using namespace css;
+using namespace css::kstage;
 
 namespace {
-
-constexpr int64_t HOST_CAP = (int64_t)1 << 28;   // floats per array: far below the kernels' 32-bit buffer offsets
-
-inline size_t pad64(int64_t n) { return (size_t)((n + 63) / 64 * 64); }   // every staged region starts on 256 bytes
 
 bool ln_width(int D) { return D >= 256 && D <= 1024 && D % 256 == 0; }
 
@@ -38,38 +36,22 @@ int css_layernorm_host(css_handle_t h, const CssLayerNormDesc* d, float* x, cons
     if (form == 3 && (!w2 || !b2 || (!y && !inplace))) return bad("form 3: w2, b2 and y or inplace");
     if (form <= 1 && (w2 || b2)) return bad("forms 0 and 1 take no second weights");
 
-    HIPCHK(h, hipSetDevice(h->device));
-    const size_t f_x = pad64(d->x_floats), f_o = pad64(d->out_floats), f_w = pad64(D);
+    Stager sg;
+    const size_t o_x = sg.arr(x, d->x_floats, 4, UP | DOWN);
+    const size_t o_y = sg.arr(y, d->out_floats, 4, UP | DOWN), o_z = sg.arr(z, d->out_floats, 4, UP | DOWN);
+    const size_t o_s = sg.arr(ys, d->out_floats, 4, UP | DOWN);
+    const size_t o_w = sg.arr(w, D, 4, UP), o_b = sg.arr(b, D, 4, UP);
+    const size_t o_w2 = sg.arr(w2, form == 2 ? 6 : D, 4, UP), o_b2 = sg.arr(b2, D, 4, UP);
+    char* base = nullptr;
     int rc;
-    if ((rc = ensure(h, h->stage, (f_x + 3 * f_o + 4 * f_w) * sizeof(float))) != CSS_OK) return rc;
-    float* xd = (float*)h->stage.p;
-    float* yd = xd + f_x;
-    float* zd = yd + f_o;
-    float* sd = zd + f_o;
-    float* wd = sd + f_o;
-    float* bd = wd + f_w;
-    float* w2d = bd + f_w;
-    float* b2d = w2d + f_w;
+    if ((rc = stage_and_upload(h, sg, &base)) != CSS_OK) return rc;
+    auto at = [&](size_t o) { return Stager::dev<float>(base, o); };   // (null for an absent array)
     hipStream_t st = h->stream;
-    HIPCHK(h, hipMemcpyAsync(xd, x, (size_t)d->x_floats * sizeof(float), hipMemcpyHostToDevice, st));
-    if (y) HIPCHK(h, hipMemcpyAsync(yd, y, (size_t)d->out_floats * sizeof(float), hipMemcpyHostToDevice, st));
-    if (z) HIPCHK(h, hipMemcpyAsync(zd, z, (size_t)d->out_floats * sizeof(float), hipMemcpyHostToDevice, st));
-    if (ys) HIPCHK(h, hipMemcpyAsync(sd, ys, (size_t)d->out_floats * sizeof(float), hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(wd, w, (size_t)D * sizeof(float), hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(bd, b, (size_t)D * sizeof(float), hipMemcpyHostToDevice, st));
-    if (w2) HIPCHK(h, hipMemcpyAsync(w2d, w2, (size_t)(form == 2 ? 6 : D) * sizeof(float), hipMemcpyHostToDevice, st));
-    if (b2) HIPCHK(h, hipMemcpyAsync(b2d, b2, (size_t)D * sizeof(float), hipMemcpyHostToDevice, st));
-    float* yo = inplace ? xd : (y ? yd : nullptr);
-    if (form <= 1) launch_layernorm(xd, yo, ys ? sd : nullptr, wd, bd, rows, D, form, st);
-    else if (form == 2) launch_ln_glu(xd, yd, wd, bd, w2d, rows, D, st);
-    else launch_layernorm2(xd, yo, wd, bd, z ? zd : nullptr, ys ? sd : nullptr, w2d, b2d, rows, D, st);
-    HIPCHK(h, hipMemcpyAsync(x, xd, (size_t)d->x_floats * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (y) HIPCHK(h, hipMemcpyAsync(y, yd, (size_t)d->out_floats * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (z) HIPCHK(h, hipMemcpyAsync(z, zd, (size_t)d->out_floats * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (ys) HIPCHK(h, hipMemcpyAsync(ys, sd, (size_t)d->out_floats * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    HIPCHK(h, hipGetLastError());
-    return CSS_OK;
+    float *xd = at(o_x), *yd = at(o_y), *yo = inplace ? xd : yd;
+    if (form <= 1) launch_layernorm(xd, yo, at(o_s), at(o_w), at(o_b), rows, D, form, st);
+    else if (form == 2) launch_ln_glu(xd, yd, at(o_w), at(o_b), at(o_w2), rows, D, st);
+    else launch_layernorm2(xd, yo, at(o_w), at(o_b), at(o_z), at(o_s), at(o_w2), at(o_b2), rows, D, st);
+    return download_all(h, sg, base);
 }
 
 int css_conv_module_host(css_handle_t h, const CssConvModuleDesc* d, float* x, const float* ln_w, const float* ln_b,
@@ -91,54 +73,28 @@ int css_conv_module_host(css_handle_t h, const CssConvModuleDesc* d, float* x, c
     if (form == 0 && (z || zs) && (!ln2_w || !ln2_b)) return bad("z / zs need ln2_w and ln2_b");
     if (form == 1 && (x_out || z || zs)) return bad("form 1 works in place: x_out, z and zs must be NULL");
 
-    HIPCHK(h, hipSetDevice(h->device));
-    const size_t f_x = pad64(d->x_floats), f_o = pad64(d->out_floats), f_w = pad64(D), f_t = pad64((int64_t)taps * D), f_u = pad64(need);
+    Stager sg;
+    const size_t o_x = sg.arr(x, d->x_floats, 4, UP | DOWN), o_o = sg.arr(x_out, d->out_floats, 4, UP | DOWN);
+    const size_t o_z = sg.arr(z, d->out_floats, 4, UP | DOWN), o_s = sg.arr(zs, d->out_floats, 4, UP | DOWN);
+    const size_t o_u = sg.scratch(form == 1 ? need : 0, 4);   // form 1: the GLU rows between the two kernels
+    const size_t o_lnw = sg.arr(ln_w, D, 4, UP), o_lnb = sg.arr(ln_b, D, 4, UP), o_dwb = sg.arr(dw_b, D, 4, UP);
+    const size_t o_al = sg.arr(bn_alpha, D, 4, UP), o_be = sg.arr(bn_beta, D, 4, UP);
+    const size_t o_l2w = sg.arr(ln2_w, D, 4, UP), o_l2b = sg.arr(ln2_b, D, 4, UP);
+    const size_t o_wt = sg.arr(dw_wt, (int64_t)taps * D, 4, UP), o_pw = sg.arr(pw, 6, 4, UP);
+    char* base = nullptr;
     int rc;
-    if ((rc = ensure(h, h->stage, (f_x + 3 * f_o + f_u + 7 * f_w + f_t + 64) * sizeof(float))) != CSS_OK) return rc;
-    float* xd = (float*)h->stage.p;
-    float* od = xd + f_x;
-    float* zd = od + f_o;
-    float* sd = zd + f_o;
-    float* ud = sd + f_o;            // form 1: the GLU rows between the two kernels
-    float* lnwd = ud + f_u;
-    float* lnbd = lnwd + f_w;
-    float* dwbd = lnbd + f_w;
-    float* ald = dwbd + f_w;
-    float* bed = ald + f_w;
-    float* l2wd = bed + f_w;
-    float* l2bd = l2wd + f_w;
-    float* wtd = l2bd + f_w;
-    float* pwd = wtd + f_t;
+    if ((rc = stage_and_upload(h, sg, &base)) != CSS_OK) return rc;
+    auto at = [&](size_t o) { return Stager::dev<float>(base, o); };   // (null for an absent array)
     hipStream_t st = h->stream;
-    const size_t xb = (size_t)d->x_floats * sizeof(float), ob = (size_t)d->out_floats * sizeof(float), wb = (size_t)D * sizeof(float);
-    HIPCHK(h, hipMemcpyAsync(xd, x, xb, hipMemcpyHostToDevice, st));
-    if (x_out) HIPCHK(h, hipMemcpyAsync(od, x_out, ob, hipMemcpyHostToDevice, st));
-    if (z) HIPCHK(h, hipMemcpyAsync(zd, z, ob, hipMemcpyHostToDevice, st));
-    if (zs) HIPCHK(h, hipMemcpyAsync(sd, zs, ob, hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(lnwd, ln_w, wb, hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(lnbd, ln_b, wb, hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(dwbd, dw_b, wb, hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(ald, bn_alpha, wb, hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(bed, bn_beta, wb, hipMemcpyHostToDevice, st));
-    if (ln2_w) HIPCHK(h, hipMemcpyAsync(l2wd, ln2_w, wb, hipMemcpyHostToDevice, st));
-    if (ln2_b) HIPCHK(h, hipMemcpyAsync(l2bd, ln2_b, wb, hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(wtd, dw_wt, (size_t)taps * D * sizeof(float), hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(pwd, pw, 6 * sizeof(float), hipMemcpyHostToDevice, st));
     if (form == 0) {
-        *launched = launch_conv_module(xd, od, lnwd, lnbd, pwd, wtd, dwbd, ald, bed, l2wd, l2bd, z ? zd : nullptr, zs ? sd : nullptr,
-                                       nseg, T, D, taps, st) ? 1 : 0;
+        *launched = launch_conv_module(at(o_x), at(o_o), at(o_lnw), at(o_lnb), at(o_pw), at(o_wt), at(o_dwb), at(o_al), at(o_be), at(o_l2w),
+                                       at(o_l2b), at(o_z), at(o_s), nseg, T, D, taps, st) ? 1 : 0;
     } else {
-        launch_ln_glu(xd, ud, lnwd, lnbd, pwd, nseg * T, D, st);
-        launch_dwconv(ud, xd, wtd, dwbd, ald, bed, pwd, nseg, T, D, taps, st);
+        launch_ln_glu(at(o_x), at(o_u), at(o_lnw), at(o_lnb), at(o_pw), nseg * T, D, st);
+        launch_dwconv(at(o_u), at(o_x), at(o_wt), at(o_dwb), at(o_al), at(o_be), at(o_pw), nseg, T, D, taps, st);
         *launched = 1;
     }
-    HIPCHK(h, hipMemcpyAsync(x, xd, xb, hipMemcpyDeviceToHost, st));
-    if (x_out) HIPCHK(h, hipMemcpyAsync(x_out, od, ob, hipMemcpyDeviceToHost, st));
-    if (z) HIPCHK(h, hipMemcpyAsync(z, zd, ob, hipMemcpyDeviceToHost, st));
-    if (zs) HIPCHK(h, hipMemcpyAsync(zs, sd, ob, hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    HIPCHK(h, hipGetLastError());
-    return CSS_OK;
+    return download_all(h, sg, base);
 }
 
 int css_attention_host(css_handle_t h, const CssAttentionDesc* d, const float* x, const float* w, const float* bias,
@@ -167,34 +123,25 @@ int css_attention_host(css_handle_t h, const CssAttentionDesc* d, const float* x
         if (((size_t)64 + (size_t)T) * sizeof(float) > 150 * 1024) return bad("mode 2: a segment of more than ~ 38 000 frames");
     }
 
-    HIPCHK(h, hipSetDevice(h->device));
     const int N = 3 * D;
     const int64_t qkf_n = mode == 1 ? qk_fragment_floats(nseg, T, H) : 0;
     const int64_t pef_n = mode != 2 ? (int64_t)pe_fragment_tiles(T) * 2048 : 0;
-    const size_t f_x = pad64(M * K), f_w = pad64((int64_t)N * K), f_b = pad64(N), f_pe = pad64((int64_t)2 * maxlen * 64);
-    const size_t f_q = pad64(d->qkv_floats), f_c = pad64(d->ctx_floats), f_qf = pad64(qkf_n), f_pf = pad64(pef_n);
+    Stager sg;
+    const int64_t pe_n = (int64_t)2 * maxlen * 64;
+    const size_t o_x = sg.arr(x, M * K, 4, UP), o_xs = sg.scratch(M * K, 4);                     // x, x split
+    const size_t o_w = sg.arr(w, (int64_t)N * K, 4, UP), o_wc = sg.scratch((int64_t)N * K, 4);   // w, w converted
+    const size_t o_b = sg.arr(bias, N, 4, UP);
+    const size_t o_pe = sg.arr(pe, pe_n, 4, UP), o_pes = sg.scratch(pe_n, 4);                    // pe, pe split
+    // the outputs start as the caller's canary, not as the caller's arrays
+    const size_t o_q = sg.filled(d->qkv_floats, d->canary, qkv), o_c = sg.filled(d->ctx_floats, d->canary, ctx);
+    const size_t o_qf = sg.filled(qkf_n, d->canary, nullptr), o_pf = sg.scratch(pef_n, 4);       // fragments
+    char* base = nullptr;
     int rc;
-    //           x, x split   w, w converted   bias  pe, pe split   qkv   ctx   fragments
-    if ((rc = ensure(h, h->stage, (2 * f_x + 2 * f_w + f_b + 2 * f_pe + f_q + f_c + f_qf + f_pf) * sizeof(float))) != CSS_OK) return rc;
-    float* xd = (float*)h->stage.p;
-    float* xs = xd + f_x;
-    float* wd = xs + f_x;
-    float* wc = wd + f_w;
-    float* bd = wc + f_w;
-    float* ped = bd + f_b;
-    float* pes = ped + f_pe;
-    float* qd = pes + f_pe;
-    float* cd = qd + f_q;
-    float* qkf = cd + f_c;
-    float* pef = qkf + f_qf;
+    if ((rc = stage_and_upload(h, sg, &base)) != CSS_OK) return rc;
+    auto at = [&](size_t o) { return Stager::dev<float>(base, o); };
+    float *xd = at(o_x), *xs = at(o_xs), *wd = at(o_w), *wc = at(o_wc), *bd = at(o_b), *ped = at(o_pe), *pes = at(o_pes);
+    float *qd = at(o_q), *cd = at(o_c), *qkf = at(o_qf), *pef = at(o_pf);
     hipStream_t st = h->stream;
-    HIPCHK(h, hipMemcpyAsync(xd, x, (size_t)M * K * sizeof(float), hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(wd, w, (size_t)N * K * sizeof(float), hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(bd, bias, (size_t)N * sizeof(float), hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(ped, pe, (size_t)2 * maxlen * 64 * sizeof(float), hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)qd, (int)d->canary, (size_t)d->qkv_floats, st));
-    HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)cd, (int)d->canary, (size_t)d->ctx_floats, st));
-    if (qkf_n) HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)qkf, (int)d->canary, (size_t)qkf_n, st));
 
     // the QKV product as masknet_lane's lin() describes it
     GemmArgs g = linear(xd, K, wd, K, bd, qd, N, (int)M, N, K, ACT_NONE);
@@ -217,11 +164,7 @@ int css_attention_host(css_handle_t h, const CssAttentionDesc* d, const float* x
         launch_pe_fragments(mode == 1 ? pes : ped, pef, T, maxlen, mode, st);
         launch_relpos_attention(qd, mode == 1 ? qkf : nullptr, pef, cd, nseg, T, D, H, maxlen, mode, mode, st);
     }
-    HIPCHK(h, hipMemcpyAsync(qkv, qd, (size_t)d->qkv_floats * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(ctx, cd, (size_t)d->ctx_floats * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    HIPCHK(h, hipGetLastError());
-    return CSS_OK;
+    return download_all(h, sg, base);
 }
 
 }  // extern "C"

@@ -4,17 +4,11 @@
 #include <vector>
 
 #include "api_ctx.hpp"
+#include "api_kernel_stage.hpp"   // (Stager, stage_and_upload, download_all)
 #include "../../include/css_mi355_frontend.h"
 
 using namespace css;
-
-namespace {
-
-constexpr int64_t HOST_CAP = (int64_t)1 << 28;   // elements per array: far below the kernels' 32-bit grids
-
-inline size_t pad64(int64_t n) { return (size_t)((n + 63) / 64 * 64); }   // every staged region starts on 256 bytes
-
-}  // namespace
+using namespace css::kstage;
 
 extern "C" {
 
@@ -39,30 +33,19 @@ int css_analysis_host(css_handle_t h, const CssAnalysisDesc* d, const float* x, 
     if (phase && (d->phase_floats < off + (int64_t)C * 257 * row_ld || d->phase_floats > HOST_CAP))
         return bad("phase is shorter than its description");
 
-    HIPCHK(h, hipSetDevice(h->device));
     std::vector<float> tab(stft_table_floats());
     stft_build_tables(tab.data(), d->window);
-    const size_t f_x = pad64(d->x_floats), f_o = pad64(d->out_floats), f_p = pad64(phase ? d->phase_floats : 0), f_t = pad64((int64_t)tab.size());
+    Stager sg;
+    const size_t o_x = sg.arr(x, d->x_floats, 4, UP), o_o = sg.arr(out, d->out_floats, 4, UP | DOWN);
+    const size_t o_p = sg.arr(phase, d->phase_floats, 4, UP | DOWN), o_t = sg.arr(tab.data(), (int64_t)tab.size(), 4, UP);
+    char* base = nullptr;
     int rc;
-    if ((rc = ensure(h, h->stage, (f_x + f_o + f_p + f_t) * sizeof(float))) != CSS_OK) return rc;
-    float* xd = (float*)h->stage.p;
-    float* od = xd + f_x;
-    float* pd = od + f_o;
-    float* td = pd + f_p;
-    hipStream_t st = h->stream;
-    HIPCHK(h, hipMemcpyAsync(xd, x, (size_t)d->x_floats * sizeof(float), hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(od, out, (size_t)d->out_floats * sizeof(float), hipMemcpyHostToDevice, st));
-    if (phase) HIPCHK(h, hipMemcpyAsync(pd, phase, (size_t)d->phase_floats * sizeof(float), hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(td, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipStreamSynchronize(st));   // (tab is pageable host memory of this call)
+    if ((rc = stage_and_upload(h, sg, &base)) != CSS_OK) return rc;
+    auto at = [&](size_t o) { return Stager::dev<float>(base, o); };   // (null for an absent array)
     // the phase base carries the plane base's offset: launch_stft_fft decides float4 against scalar stores on `out` alone
-    if (!launch_stft_fft(xd, xs, C, t_lo, t_hi, td, od + off, row_ld, st, phase ? pd + off : nullptr))
+    if (!launch_stft_fft(at(o_x), xs, C, t_lo, t_hi, at(o_t), at(o_o) + off, row_ld, h->stream, phase ? at(o_p) + off : nullptr))
         return fail(h, CSS_ERR_HIP, "css_analysis_host: the kernel's LDS could not be reserved");
-    HIPCHK(h, hipMemcpyAsync(out, od, (size_t)d->out_floats * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (phase) HIPCHK(h, hipMemcpyAsync(phase, pd, (size_t)d->phase_floats * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    HIPCHK(h, hipGetLastError());
-    return CSS_OK;
+    return download_all(h, sg, base);
 }
 
 int css_features_host(css_handle_t h, const CssFeaturesDesc* d, const float* X, const float* PH, const float* in_bias,
@@ -96,26 +79,17 @@ int css_features_host(css_handle_t h, const CssFeaturesDesc* d, const float* X, 
     o.ipd_version = c.ipd_mean_normalize_version; o.ipd_cos = c.ipd_cos != 0; o.num_pairs = c.num_pairs;
     for (int p = 0; p < c.num_pairs; ++p) { o.pair_l[p] = (unsigned char)c.pair_l[p]; o.pair_r[p] = (unsigned char)c.pair_r[p]; }
 
-    HIPCHK(h, hipSetDevice(h->device));
-    const size_t f_x = pad64(d->x_floats), f_p = pad64(PH ? d->ph_floats : 0), f_c = pad64(cols), f_f = pad64(d->feat_floats);
+    Stager sg;
+    const size_t o_x = sg.arr(X, d->x_floats, 4, UP), o_p = sg.arr(PH, d->ph_floats, 4, UP);
+    const size_t o_b = sg.arr(in_bias, cols, 4, UP), o_s = sg.arr(in_scale, cols, 4, UP);
+    const size_t o_f = sg.arr(feat, d->feat_floats, 4, UP | DOWN);
+    char* base = nullptr;
     int rc;
-    if ((rc = ensure(h, h->stage, (f_x + f_p + 2 * f_c + f_f) * sizeof(float))) != CSS_OK) return rc;
-    float* xd = (float*)h->stage.p;
-    float* pd = xd + f_x;
-    float* bd = pd + f_p;
-    float* sd = bd + f_c;
-    float* fd = sd + f_c;
-    hipStream_t st = h->stream;
-    HIPCHK(h, hipMemcpyAsync(xd, X, (size_t)d->x_floats * sizeof(float), hipMemcpyHostToDevice, st));
-    if (PH) HIPCHK(h, hipMemcpyAsync(pd, PH, (size_t)d->ph_floats * sizeof(float), hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(bd, in_bias, (size_t)cols * sizeof(float), hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(sd, in_scale, (size_t)cols * sizeof(float), hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(fd, feat, (size_t)d->feat_floats * sizeof(float), hipMemcpyHostToDevice, st));
-    launch_features(xd, d->T_ld, d->stft_frames, C, F, fd, Kp, bd, sd, d->seg_lo, nseg, T, hop, d->split_out, o, st, PH ? pd : nullptr);
-    HIPCHK(h, hipMemcpyAsync(feat, fd, (size_t)d->feat_floats * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    HIPCHK(h, hipGetLastError());
-    return CSS_OK;
+    if ((rc = stage_and_upload(h, sg, &base)) != CSS_OK) return rc;
+    auto at = [&](size_t o) { return Stager::dev<float>(base, o); };   // (null for an absent array)
+    launch_features(at(o_x), d->T_ld, d->stft_frames, C, F, at(o_f), Kp, at(o_b), at(o_s), d->seg_lo, nseg, T, hop, d->split_out, o, h->stream,
+                    at(o_p));
+    return download_all(h, sg, base);
 }
 
 int css_synthesis_tail_host(css_handle_t h, const CssSynthesisTailDesc* d, const float* in, float* out) {
@@ -153,19 +127,16 @@ int css_synthesis_tail_host(css_handle_t h, const CssSynthesisTailDesc* d, const
         if (d->out_floats < (int64_t)d->B * d->T_frames * d->KIp) return bad("form 2: rows is shorter than its description");
     }
 
-    HIPCHK(h, hipSetDevice(h->device));
-    const size_t f_i = pad64(d->in_floats), f_o = pad64(d->out_floats);
-    int rc;
-    if ((rc = ensure(h, h->stage, (f_i + f_o + 64) * sizeof(float))) != CSS_OK) return rc;
-    float* id = (float*)h->stage.p;
-    float* od = id + f_i;
-    unsigned int* lv = reinterpret_cast<unsigned int*>(od + f_o);
-    hipStream_t st = h->stream;
     const uint32_t level = d->level;
-    HIPCHK(h, hipMemcpyAsync(id, in, (size_t)d->in_floats * sizeof(float), hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(od, out, (size_t)d->out_floats * sizeof(float), hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(lv, &level, sizeof(level), hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipStreamSynchronize(st));
+    Stager sg;
+    const size_t o_i = sg.arr(in, d->in_floats, 4, UP), o_o = sg.arr(out, d->out_floats, 4, UP | DOWN), o_lv = sg.arr(&level, 1, 4, UP);
+    char* base = nullptr;
+    int rc;
+    if ((rc = stage_and_upload(h, sg, &base)) != CSS_OK) return rc;
+    const float* id = Stager::dev<float>(base, o_i);
+    float* od = Stager::dev<float>(base, o_o);
+    unsigned int* lv = Stager::dev<unsigned int>(base, o_lv);
+    hipStream_t st = h->stream;
     if (form == 0)
         launch_wave_ola(id, od, d->B, d->T_frames, d->hop, d->L, d->q_lo, d->q_hi, d->f_lo, d->f_hi, d->out_ld, d->out_q0,
                         d->has_level ? lv : nullptr, st);
@@ -173,10 +144,7 @@ int css_synthesis_tail_host(css_handle_t h, const CssSynthesisTailDesc* d, const
         launch_join_shards(id, d->ld, d->t_lo, d->t_hi, d->world, d->S, d->hop, d->n_out, od, d->out_ld, st);
     else
         launch_planes_to_rows(id, od, d->B, d->F2, d->T_frames, d->KIp, st);
-    HIPCHK(h, hipMemcpyAsync(out, od, (size_t)d->out_floats * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    HIPCHK(h, hipGetLastError());
-    return CSS_OK;
+    return download_all(h, sg, base);
 }
 
 int css_pcm_edges_host(css_handle_t h, const CssPcmEdgesDesc* d, const void* in, void* out, uint32_t* peak) {
@@ -217,20 +185,18 @@ int css_pcm_edges_host(css_handle_t h, const CssPcmEdgesDesc* d, const void* in,
         out_size = sizeof(int16_t);
     }
 
-    HIPCHK(h, hipSetDevice(h->device));
-    const size_t b_i = pad64(d->in_elems) * sizeof(float), b_o = pad64(is_peak ? 0 : d->out_elems) * sizeof(float);
     const size_t n_pk = form == 5 ? (size_t)S : 1;
-    int rc;
-    if ((rc = ensure(h, h->stage, b_i + b_o + pad64((int64_t)n_pk) * sizeof(float))) != CSS_OK) return rc;
-    char* id = (char*)h->stage.p;
-    char* od = id + b_i;
-    unsigned int* pk = reinterpret_cast<unsigned int*>(od + b_o);
-    hipStream_t st = h->stream;
     const uint32_t before = d->peak_before;
-    HIPCHK(h, hipMemcpyAsync(id, in, (size_t)d->in_elems * in_size, hipMemcpyHostToDevice, st));
-    if (!is_peak) HIPCHK(h, hipMemcpyAsync(od, out, (size_t)d->out_elems * out_size, hipMemcpyHostToDevice, st));
-    if (is_peak) HIPCHK(h, hipMemcpyAsync(pk, &before, sizeof(before), hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipStreamSynchronize(st));
+    Stager sg;
+    const size_t o_i = sg.arr(in, d->in_elems, in_size, UP), o_o = sg.arr(out, d->out_elems, out_size, UP | DOWN);
+    // the peak words: forms 3 and 4 start from peak_before, form 5 writes every one; all return them where the caller asks
+    const size_t o_pk = sg.region(n_pk * sizeof(unsigned int), is_peak ? &before : nullptr, peak);
+    char* base = nullptr;
+    int rc;
+    if ((rc = stage_and_upload(h, sg, &base)) != CSS_OK) return rc;
+    char *id = base + o_i, *od = Stager::dev<char>(base, o_o);
+    unsigned int* pk = Stager::dev<unsigned int>(base, o_pk);
+    hipStream_t st = h->stream;
     switch (form) {
     case 0: launch_deinterleave((const float*)id, (float*)od, n, C, d->n_pad, d->i_lo, d->i_hi, d->split_out, st); break;
     case 1: launch_pcm16_to_float((const int16_t*)id, (float*)od, n, C, st); break;
@@ -239,11 +205,7 @@ int css_pcm_edges_host(css_handle_t h, const CssPcmEdgesDesc* d, const void* in,
     case 4: launch_pcm_peak_i16((const int16_t*)id + d->src_offset, d->count, pk, st); break;
     default: launch_encode_pcm16((const float*)id, S, n, pk, (int16_t*)od, d->out_ld, st); break;
     }
-    if (!is_peak) HIPCHK(h, hipMemcpyAsync(out, od, (size_t)d->out_elems * out_size, hipMemcpyDeviceToHost, st));
-    if (peak) HIPCHK(h, hipMemcpyAsync(peak, pk, n_pk * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    HIPCHK(h, hipGetLastError());
-    return CSS_OK;
+    return download_all(h, sg, base);
 }
 
 }  // extern "C"

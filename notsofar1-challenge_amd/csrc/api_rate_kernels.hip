@@ -5,25 +5,16 @@
 #include <vector>
 
 #include "api_ctx.hpp"
+#include "api_kernel_stage.hpp"   // (Stager, stage_and_upload, download_all)
 #include "../../include/css_mi355_rate_kernels.h"
 
 using namespace css;
+using namespace css::kstage;
 
 namespace {
 
-constexpr int64_t HOST_CAP = (int64_t)1 << 28;   // elements per array
 constexpr int64_t COUNT_MAX = (int64_t)1 << 40;  // sample counts and positions: their products with `down` stay far inside int64
 constexpr int64_t N_M_MAX = (int64_t)1 << 24;    // outputs per job: the grids stay small
-
-// byte offsets into h->stage: every region starts on 256 bytes and has 256 bytes of room behind it
-struct Stage {
-    size_t bytes = 0;
-    size_t take(size_t n) {
-        const size_t at = bytes;
-        bytes += (n + 255) / 256 * 256 + 256;
-        return at;
-    }
-};
 
 bool in_range(int64_t v) { return v >= 0 && v <= COUNT_MAX; }
 
@@ -80,22 +71,24 @@ int css_rate_ingest_host(css_handle_t h, int32_t form, CssRateIngestJob* jobs, i
     struct At { size_t tab, src, hin, hout, dst, level; };
     std::vector<At> at((size_t)n_jobs);
     std::vector<std::vector<float>> tabs((size_t)n_jobs);
-    Stage st_;
+    Stager sg;
     for (int i = 0; i < n_jobs; ++i) {
-        const CssRateIngestJob& j = jobs[i];
+        CssRateIngestJob& j = jobs[i];
+        At& a = at[(size_t)i];
         const size_t el = j.is_int16 ? sizeof(int16_t) : sizeof(float);
+        float* const ho = j.has_hist_out ? j.hist_out : nullptr;
         tabs[(size_t)i] = phase_table(rr[(size_t)i]);
-        at[(size_t)i].tab = st_.take(tabs[(size_t)i].size() * sizeof(float));
-        at[(size_t)i].src = st_.take((size_t)(j.src_offset + j.src_elems) * el);
-        at[(size_t)i].hin = st_.take((size_t)j.hist_elems * sizeof(float));
-        at[(size_t)i].hout = st_.take((size_t)j.hist_elems * sizeof(float));
-        at[(size_t)i].dst = st_.take((size_t)j.dst_floats * sizeof(float));
-        at[(size_t)i].level = st_.take(sizeof(unsigned int));
+        // (regions, not arr(): a job's launch is handed every one of these, an empty history included)
+        a.tab = sg.region(tabs[(size_t)i].size() * sizeof(float), tabs[(size_t)i].data(), nullptr);
+        a.src = sg.region((size_t)j.src_elems * el, j.src, nullptr, (size_t)j.src_offset * el);
+        a.hin = sg.region((size_t)j.hist_elems * sizeof(float), j.hist_in, nullptr);
+        a.hout = sg.region((size_t)j.hist_elems * sizeof(float), ho, ho);
+        a.dst = sg.region((size_t)j.dst_floats * sizeof(float), j.dst, j.dst);
+        a.level = sg.region(sizeof(uint32_t), &j.level_before, &j.level_after);
     }
-    HIPCHK(h, hipSetDevice(h->device));
+    char* base = nullptr;
     int rc;
-    if ((rc = ensure(h, h->stage, st_.bytes)) != CSS_OK) return rc;
-    char* base = (char*)h->stage.p;
+    if ((rc = stage_and_upload(h, sg, &base)) != CSS_OK) return rc;
     hipStream_t st = h->stream;
     std::vector<ResampleJob> rj((size_t)n_jobs);
     std::vector<SessionIngestJob> sj((size_t)n_jobs);
@@ -105,14 +98,6 @@ int css_rate_ingest_host(css_handle_t h, int32_t form, CssRateIngestJob* jobs, i
         const ResampleRatio& r = rr[(size_t)i];
         const size_t el = j.is_int16 ? sizeof(int16_t) : sizeof(float);
         char* src_d = base + a.src + (size_t)j.src_offset * el;
-        HIPCHK(h, hipMemcpyAsync(base + a.tab, tabs[(size_t)i].data(), tabs[(size_t)i].size() * sizeof(float), hipMemcpyHostToDevice, st));
-        if (j.src_elems > 0) HIPCHK(h, hipMemcpyAsync(src_d, j.src, (size_t)j.src_elems * el, hipMemcpyHostToDevice, st));
-        if (j.hist_elems > 0 && j.hist_in)
-            HIPCHK(h, hipMemcpyAsync(base + a.hin, j.hist_in, (size_t)j.hist_elems * sizeof(float), hipMemcpyHostToDevice, st));
-        if (j.has_hist_out && j.hist_elems > 0)
-            HIPCHK(h, hipMemcpyAsync(base + a.hout, j.hist_out, (size_t)j.hist_elems * sizeof(float), hipMemcpyHostToDevice, st));
-        HIPCHK(h, hipMemcpyAsync(base + a.dst, j.dst, (size_t)j.dst_floats * sizeof(float), hipMemcpyHostToDevice, st));
-        HIPCHK(h, hipMemcpyAsync(base + a.level, &j.level_before, sizeof(uint32_t), hipMemcpyHostToDevice, st));
         ResampleJob& e = rj[(size_t)i];
         e = ResampleJob{};
         e.src = src_d; e.is_i16 = j.is_int16 ? 1 : 0; e.plane_ld = j.plane_ld; e.n = j.n;
@@ -122,25 +107,13 @@ int css_rate_ingest_host(css_handle_t h, int32_t form, CssRateIngestJob* jobs, i
         e.C = j.C; e.dst = (float*)(base + a.dst) + j.dst_col; e.dst_ld = j.dst_ld;
         sj[(size_t)i] = SessionIngestJob{e, j.n_peak, (unsigned int*)(base + a.level)};
     }
-    HIPCHK(h, hipStreamSynchronize(st));   // (the tables are pageable host memory of this call)
     const bool ok = form == 0 ? launch_stream_ingest_resample_multi(rj.data(), n_jobs, st)
                               : launch_session_ingest_multi(sj.data(), n_jobs, st, nullptr);
     if (!ok) {
         hipStreamSynchronize(st);
         return fail(h, CSS_ERR_HIP, "css_rate_ingest_host: the kernel's LDS could not be reserved");
     }
-    HIPCHK(h, hipGetLastError());
-    for (int i = 0; i < n_jobs; ++i) {
-        CssRateIngestJob& j = jobs[i];
-        const At& a = at[(size_t)i];
-        HIPCHK(h, hipMemcpyAsync(j.dst, base + a.dst, (size_t)j.dst_floats * sizeof(float), hipMemcpyDeviceToHost, st));
-        if (j.has_hist_out && j.hist_elems > 0)
-            HIPCHK(h, hipMemcpyAsync(j.hist_out, base + a.hout, (size_t)j.hist_elems * sizeof(float), hipMemcpyDeviceToHost, st));
-        HIPCHK(h, hipMemcpyAsync(&j.level_after, base + a.level, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    }
-    HIPCHK(h, hipStreamSynchronize(st));
-    HIPCHK(h, hipGetLastError());
-    return CSS_OK;
+    return download_all(h, sg, base);
 }
 
 int css_rate_output_host(css_handle_t h, int32_t form, int32_t S, CssRateOutputJob* jobs, int32_t n_jobs) {
@@ -182,39 +155,31 @@ int css_rate_output_host(css_handle_t h, int32_t form, int32_t S, CssRateOutputJ
     struct At { size_t tab, src, hin, hout, dst, peak, clip; };
     std::vector<At> at((size_t)n_jobs);
     std::vector<std::vector<float>> tabs((size_t)n_jobs);
-    Stage st_;
+    Stager sg;
     for (int i = 0; i < n_jobs; ++i) {
         const CssRateOutputJob& j = jobs[i];
+        At& a = at[(size_t)i];
+        float* const ho = j.has_hist_out ? j.hist_out : nullptr;
+        uint64_t* const cl = form == 0 ? j.clipped : nullptr;
         if (rr[(size_t)i].L > 0) tabs[(size_t)i] = phase_table(rr[(size_t)i]);
-        at[(size_t)i].tab = st_.take(tabs[(size_t)i].size() * sizeof(float));
-        at[(size_t)i].src = st_.take((size_t)j.src_floats * sizeof(float));
-        at[(size_t)i].hin = st_.take((size_t)j.hist_elems * sizeof(float));
-        at[(size_t)i].hout = st_.take((size_t)j.hist_elems * sizeof(float));
-        at[(size_t)i].dst = st_.take((size_t)j.dst_elems * (j.pcm16 ? sizeof(int16_t) : sizeof(float)));
-        at[(size_t)i].peak = st_.take((size_t)S * sizeof(uint32_t));
-        at[(size_t)i].clip = st_.take((size_t)S * sizeof(uint64_t));
+        // (regions, not arr(): a job's launch is handed every one of these but an empty table)
+        a.tab = sg.region(tabs[(size_t)i].size() * sizeof(float), tabs[(size_t)i].data(), nullptr);
+        a.src = sg.region((size_t)j.src_floats * sizeof(float), j.src, nullptr);
+        a.hin = sg.region((size_t)j.hist_elems * sizeof(float), j.hist_in, nullptr);
+        a.hout = sg.region((size_t)j.hist_elems * sizeof(float), ho, ho);
+        a.dst = sg.region((size_t)j.dst_elems * (j.pcm16 ? sizeof(int16_t) : sizeof(float)), j.dst, j.dst);
+        a.peak = sg.region((size_t)S * sizeof(uint32_t), j.peak, j.peak);
+        a.clip = sg.region((size_t)S * sizeof(uint64_t), cl, cl);
     }
-    HIPCHK(h, hipSetDevice(h->device));
+    char* base = nullptr;
     int rc;
-    if ((rc = ensure(h, h->stage, st_.bytes)) != CSS_OK) return rc;
-    char* base = (char*)h->stage.p;
+    if ((rc = stage_and_upload(h, sg, &base)) != CSS_OK) return rc;
     hipStream_t st = h->stream;
     std::vector<StreamOutputJob> oj((size_t)n_jobs);
     for (int i = 0; i < n_jobs; ++i) {
         const CssRateOutputJob& j = jobs[i];
         const At& a = at[(size_t)i];
         const ResampleRatio& r = rr[(size_t)i];
-        const size_t el = j.pcm16 ? sizeof(int16_t) : sizeof(float);
-        if (!tabs[(size_t)i].empty())
-            HIPCHK(h, hipMemcpyAsync(base + a.tab, tabs[(size_t)i].data(), tabs[(size_t)i].size() * sizeof(float), hipMemcpyHostToDevice, st));
-        HIPCHK(h, hipMemcpyAsync(base + a.src, j.src, (size_t)j.src_floats * sizeof(float), hipMemcpyHostToDevice, st));
-        if (j.hist_elems > 0 && j.hist_in)
-            HIPCHK(h, hipMemcpyAsync(base + a.hin, j.hist_in, (size_t)j.hist_elems * sizeof(float), hipMemcpyHostToDevice, st));
-        if (j.has_hist_out && j.hist_elems > 0)
-            HIPCHK(h, hipMemcpyAsync(base + a.hout, j.hist_out, (size_t)j.hist_elems * sizeof(float), hipMemcpyHostToDevice, st));
-        HIPCHK(h, hipMemcpyAsync(base + a.dst, j.dst, (size_t)j.dst_elems * el, hipMemcpyHostToDevice, st));
-        HIPCHK(h, hipMemcpyAsync(base + a.peak, j.peak, (size_t)S * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        if (form == 0) HIPCHK(h, hipMemcpyAsync(base + a.clip, j.clipped, (size_t)S * sizeof(uint64_t), hipMemcpyHostToDevice, st));
         StreamOutputJob& e = oj[(size_t)i];
         e = StreamOutputJob{};
         e.src = (const float*)(base + a.src); e.src_ld = j.src_ld; e.n = j.n;
@@ -226,7 +191,6 @@ int css_rate_output_host(css_handle_t h, int32_t form, int32_t S, CssRateOutputJ
         e.dst = base + a.dst; e.dst_ld = j.dst_ld;
         e.peak = (unsigned int*)(base + a.peak); e.clipped = (unsigned long long*)(base + a.clip);
     }
-    HIPCHK(h, hipStreamSynchronize(st));   // (the tables are pageable host memory of this call)
     bool ok;
     if (form == 0) {
         ok = launch_stream_output_multi(oj.data(), n_jobs, S, st, nullptr);
@@ -242,20 +206,7 @@ int css_rate_output_host(css_handle_t h, int32_t form, int32_t S, CssRateOutputJ
         hipStreamSynchronize(st);
         return fail(h, CSS_ERR_HIP, "css_rate_output_host: the kernel's LDS could not be reserved");
     }
-    HIPCHK(h, hipGetLastError());
-    for (int i = 0; i < n_jobs; ++i) {
-        CssRateOutputJob& j = jobs[i];
-        const At& a = at[(size_t)i];
-        const size_t el = j.pcm16 ? sizeof(int16_t) : sizeof(float);
-        HIPCHK(h, hipMemcpyAsync(j.dst, base + a.dst, (size_t)j.dst_elems * el, hipMemcpyDeviceToHost, st));
-        if (j.has_hist_out && j.hist_elems > 0)
-            HIPCHK(h, hipMemcpyAsync(j.hist_out, base + a.hout, (size_t)j.hist_elems * sizeof(float), hipMemcpyDeviceToHost, st));
-        HIPCHK(h, hipMemcpyAsync(j.peak, base + a.peak, (size_t)S * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        if (form == 0) HIPCHK(h, hipMemcpyAsync(j.clipped, base + a.clip, (size_t)S * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    }
-    HIPCHK(h, hipStreamSynchronize(st));
-    HIPCHK(h, hipGetLastError());
-    return CSS_OK;
+    return download_all(h, sg, base);
 }
 
 }  // extern "C"
