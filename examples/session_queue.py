@@ -3,20 +3,22 @@
 memory to separated waveforms in page-locked host memory; a session's PCIe legs run under its neighbours' kernels, and
 consecutive sessions share mask-estimator batches (up to max_batch_segments segments per batch).
 
-    python examples/session_queue.py [n_sessions] [--logmel [--windows]]
+    python examples/session_queue.py [n_sessions] [--logmel [--windows]] [--nemo]
 
 --logmel: every session also hands Whisper its input (css_run_enqueue_handoff): the kept sample ranges and the normalised
 log-mel of each separated stream, computed on the GPU behind the session's waveforms; one session takes no waveforms at all.
 --windows (with --logmel): the log-mel never leaves the GPU (css_run_enqueue_windows with mel_host = NULL): every session leaves
-Whisper's float16 encoder inputs [S, windows, 80, 3000] and the whole padded log-mel for seek-based decoding in torch tensors."""
+Whisper's float16 encoder inputs [S, windows, 80, 3000] and the whole padded log-mel for seek-based decoding in torch tensors.
+--nemo: every session hands a NeMo host its input instead (css_run_enqueue_nemo): the kept ranges and NeMo's log-mel features
+(pre-emphasis 0.97, symmetric Hann in a 512-point transform, ln(x + 2^-24), per-band normalisation) of each separated stream."""
 import importlib, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
 pkg = lambda n: importlib.import_module("notsofar1_challenge_amd." + n)
 css, _lib, sepmod, weights, synth = (pkg(n) for n in ("css", "_lib", "separator", "weights", "synth"))
 
-logmel, windows = "--logmel" in sys.argv[1:], "--windows" in sys.argv[1:]
-args = [a for a in sys.argv[1:] if a not in ("--logmel", "--windows")]
+logmel, windows, nemo = "--logmel" in sys.argv[1:], "--windows" in sys.argv[1:], "--nemo" in sys.argv[1:]
+args = [a for a in sys.argv[1:] if a not in ("--logmel", "--windows", "--nemo")]
 n_sessions = int(args[0]) if args else 8
 desc = weights.ModelDesc.mc_v1()                                     # a real deployment: separator.load_css_model(dir)
 state = weights.apply_golden_recipe(weights.portable_state_dict(desc, 0))
@@ -74,6 +76,19 @@ elif logmel:
             kept = int((r[:, 1] - r[:, 0]).sum())                    # frame j of ho.mel[spk] starts at concatenated sample 160 j
             print(f"  session {k} stream {spk}: {len(r)} ranges, {kept / 16000.0:.1f} s kept, log-mel {ho.mel[spk].shape}")
     print(f"with the hand-off: {1e3 * handed:.1f} ms ({audio / handed:.0f} x real time); waveforms the same bits: "
+          f"{all(np.array_equal(v, r) for (v, _), r in list(zip(got, refs))[1:])}")
+if nemo:
+    t0 = time.perf_counter()
+    got = [h.run_enqueue_nemo(pcm, run_cfg, None if k == 0 else out, n_mels=80, pad_frames=8, drop_silence=True, preemphasis=0.97,
+                              normalize=True) for k, (pcm, out) in enumerate(sessions)]
+    h.wait()                                                         # waveforms, ranges, features and statistics are valid now
+    handed = time.perf_counter() - t0
+    for k, (view, ho) in enumerate(got[:3]):
+        for spk in range(3):
+            r = ho.ranges[spk]                                       # frame j of ho.mel[spk] is centred on concatenated sample 160 j
+            print(f"  session {k} stream {spk}: {len(r)} ranges, features {ho.mel[spk].shape}, "
+                  f"raw mean {float(ho.mean[spk].mean()):.2f}" if int(ho.n_frames[spk]) else f"  session {k} stream {spk}: silent")
+    print(f"with the NeMo hand-off: {1e3 * handed:.1f} ms ({audio / handed:.0f} x real time); waveforms the same bits: "
           f"{all(np.array_equal(v, r) for (v, _), r in list(zip(got, refs))[1:])}")
 if os.environ.get("DEBUG"):
     for k, (v, r) in enumerate(zip(views, refs)):

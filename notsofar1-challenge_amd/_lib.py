@@ -319,6 +319,31 @@ HANDOFF_KERNEL_ARRAYS = {
 }
 
 
+class CssNemoCfg(C.Structure):                  # include/css_mi355_nemo_handoff.h
+    _fields_ = [("n_mels", C.c_int32), ("pad_frames", C.c_int32), ("drop_silence", C.c_int32), ("preemphasis", C.c_float),
+                ("normalize", C.c_int32)]
+
+
+class CssNemoOut(C.Structure):
+    _fields_ = [("mel_host", C.c_void_p), ("cap_frames", C.c_int64), ("ranges_host", C.c_void_p), ("cap_ranges", C.c_int32),
+                ("n_frames", C.c_void_p), ("n_ranges", C.c_void_p), ("mean_host", C.c_void_p), ("std_host", C.c_void_p)]
+
+
+class CssNemoArray(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("elems", C.c_int64)]
+
+
+class CssNemoKernelsJob(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("S", "n_mels", "normalize", "cap_ranges", "wav_off")] + [("preemphasis", C.c_float)] + \
+               [(n, C.c_int64) for n in ("wav_ld", "rows", "raw_ld", "out_ld")] + \
+               [(n, CssNemoArray) for n in ("wav", "regs", "offs", "st", "n_ranges", "operand", "raw", "mean", "stdv", "out")]
+
+
+# the arrays of CssNemoKernelsJob: those the launches only read, and those they write (returned as the launches left them)
+NEMO_KERNEL_ARRAYS = ((("wav", np.float32), ("regs", np.int64), ("offs", np.int64), ("st", HANDOFF_STATE), ("n_ranges", np.int32)),
+                      (("operand", np.float32), ("raw", np.float32), ("mean", np.float32), ("stdv", np.float32), ("out", np.float32)))
+
+
 class CssMvdrSet(C.Structure):                  # include/css_mi355_backend.h
     _fields_ = [(n, C.c_int64) for n in ("seg_lo", "nseg", "scm_off", "bfw_off")]
 
@@ -587,6 +612,19 @@ HANDOFF_KERNEL_BINDINGS = {
     "css_session_windows_host": (C.c_int, [_P, C.POINTER(CssSessionWindowsJob)]),
     "css_stream_windows_host": (C.c_int, [_P, C.POINTER(CssStreamWindowJob), C.c_int32, _P, C.c_int64]),
 }
+# the entry points include/css_mi355_nemo_handoff.h declares (kept ranges and NeMo log-mel features of all streams of a session,
+# on the device; queued sessions that hand off to NeMo hosts; the kernels of csrc/nemo.hip on caller data), the eighteenth table
+# load() applies (named ..._ABI: tests count the module's SIGNATURES..., ..._SIGNATURES and ..._BINDINGS tables)
+NEMO_HANDOFF_ABI = {
+    "css_nemo_handoff_bounds": (C.c_int, [C.POINTER(CssModelDesc), C.POINTER(CssRunCfg), C.POINTER(CssNemoCfg), C.c_int64,
+                                          C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    "css_handoff_nemo_all": (C.c_int, [_P, _P, C.c_int64, C.POINTER(CssNemoCfg), C.POINTER(CssNemoOut)]),
+    "css_run_enqueue_nemo": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.POINTER(CssRunCfg), _P, C.c_int64, C.POINTER(CssNemoCfg),
+                                       C.POINTER(CssNemoOut)]),
+    "css_run_enqueue_pcm16_nemo": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.POINTER(CssRunCfg), _P, C.c_int64, _P,
+                                             C.POINTER(CssNemoCfg), C.POINTER(CssNemoOut)]),
+    "css_nemo_kernels_host": (C.c_int, [_P, C.POINTER(CssNemoKernelsJob)]),
+}
 WINDOW_KERNEL_ITEMS = 64                         # CSS_WINDOW_KERNEL_ITEMS
 ARRAY_MIN_MICS, ARRAY_MAX_MICS = 2, 8            # CSS_ARRAY_MIN_MICS, CSS_ARRAY_MAX_MICS
 SESSION_SCAN_CHUNK = 1024                        # CSS_SESSION_SCAN_CHUNK: the keep-scan kernel's step, in gate frames / sample blocks
@@ -638,7 +676,8 @@ def load() -> C.CDLL:
                               list(SIGNATURES_STREAM_OUT.items()) + list(SIGNATURES_BACKEND.items()) +
                               list(ARRAY_SIGNATURES.items()) + list(SESSION_RATE_SIGNATURES.items()) +
                               list(SESSION_WINDOW_BINDINGS.items()) + list(RATE_KERNEL_BINDINGS.items()) +
-                              list(STREAM_KERNEL_BINDINGS.items()) + list(HANDOFF_KERNEL_BINDINGS.items())):
+                              list(STREAM_KERNEL_BINDINGS.items()) + list(HANDOFF_KERNEL_BINDINGS.items()) +
+                              list(NEMO_HANDOFF_ABI.items())):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -851,6 +890,56 @@ class SessionHandoff:
             self.n_ranges[...] = int(fill)
         self.c = CssSessionHandoffOut(self.mel_all.ctypes.data, int(frames), self.ranges_all.ctypes.data, int(ranges),
                                       self.n_frames.ctypes.data, self.n_ranges.ctypes.data)
+
+    @property
+    def mel(self):
+        return [self.mel_all[k, :, :int(self.n_frames[k])] for k in range(self.S)]
+
+    @property
+    def ranges(self):
+        return [self.ranges_all[k, :int(self.n_ranges[k])] for k in range(self.S)]
+
+
+def nemo_cfg(n_mels: int = 80, pad_frames: int = 8, drop_silence: bool = True, preemphasis: float = 0.97,
+             normalize: bool = True) -> CssNemoCfg:
+    return CssNemoCfg(int(n_mels), int(pad_frames), int(bool(drop_silence)), float(preemphasis), int(bool(normalize)))
+
+
+def nemo_handoff_bounds(desc, run_cfg: RunCfg, ncfg: CssNemoCfg, n_samples: int):
+    """css_nemo_handoff_bounds: (frames, ranges) per stream that suffice for the NeMo hand-off of a session of `n_samples`"""
+    f, r = C.c_int64(), C.c_int32()
+    rc = load().css_nemo_handoff_bounds(C.byref(make_desc(desc)), C.byref(run_cfg.c), C.byref(ncfg), int(n_samples), C.byref(f), C.byref(r))
+    if rc != CSS_OK:
+        raise CssError(rc, "css_nemo_handoff_bounds: bad configuration, or frames other than 512 / 256")
+    return int(f.value), int(r.value)
+
+
+class NemoHandoff:
+    """The arrays of one session's hand-off to a NeMo host (css_mi355_nemo_handoff.h) and, once they are valid -- after wait() /
+    wait_sessions() for a queued session --, their trimmed views: ``mel[k]`` float32 [n_mels, n_frames[k]] (normalised per band,
+    or the raw ln values with normalize off), ``ranges[k]`` int64 [n_ranges[k], 2] (the time map back to the meeting),
+    ``n_frames``, ``n_ranges``, and with ``stats`` ``mean`` / ``std`` float32 [S, n_mels] of the raw values (rows of speakers
+    with a frame).  pinned: page-locked arrays (what the queued forms need)."""
+
+    def __init__(self, S: int, n_mels: int, frames: int, ranges: int, pinned: bool = True, fill=None, stats: bool = True):
+        make = pinned_empty if pinned else (lambda shape, dtype: np.empty(shape, dtype))
+        self.S, self.n_mels = int(S), int(n_mels)
+        self.mel_all = make((self.S, self.n_mels, max(int(frames), 1)), np.float32)
+        self.ranges_all = make((self.S, max(int(ranges), 1), 2), np.int64)
+        self.n_frames = make((self.S,), np.int64)
+        self.n_ranges = make((self.S,), np.int32)
+        self.mean = make((self.S, self.n_mels), np.float32) if stats else None
+        self.std = make((self.S, self.n_mels), np.float32) if stats else None
+        if fill is not None:
+            self.mel_all[...] = fill
+            self.ranges_all[...] = int(fill)
+            self.n_frames[...] = int(fill)
+            self.n_ranges[...] = int(fill)
+            if stats:
+                self.mean[...] = fill
+                self.std[...] = fill
+        self.c = CssNemoOut(self.mel_all.ctypes.data, int(frames), self.ranges_all.ctypes.data, int(ranges), self.n_frames.ctypes.data,
+                            self.n_ranges.ctypes.data, self.mean.ctypes.data if stats else None, self.std.ctypes.data if stats else None)
 
     @property
     def mel(self):
@@ -1842,6 +1931,90 @@ class Handle:
                                                              C.byref(hcfg), C.byref(ho.c)))
         self._queued_keep = getattr(self, "_queued_keep", []) + [(planes, out16, peaks, cfg, ho)]
         return out16[:, :pl.n_out], ho
+
+    # ---- the hand-off to NeMo hosts (include/css_mi355_nemo_handoff.h) ----
+    def _nemo_handoff(self, cfg: RunCfg, n: int, ncfg: CssNemoCfg, pinned=True):
+        frames, ranges = nemo_handoff_bounds(self.desc, cfg, ncfg, n)
+        return NemoHandoff(int(self.desc.num_spks), int(ncfg.n_mels), frames, ranges, pinned=pinned)
+
+    def handoff_nemo_all(self, wav_ptr: int, wav_ld: int, n_mels: int = 80, pad_frames: int = 8, drop_silence: bool = True,
+                         preemphasis: float = 0.97, normalize: bool = True, out: Optional[NemoHandoff] = None) -> NemoHandoff:
+        """After run_device: kept ranges and NeMo log-mel features of ALL streams (css_handoff_nemo_all).  `out`: a NemoHandoff
+        to fill (any memory)."""
+        ncfg = nemo_cfg(n_mels, pad_frames, drop_silence, preemphasis, normalize)
+        if out is None:
+            p = self.get_plan()
+            TL = int(p.mix_frames)
+            out = NemoHandoff(int(self.desc.num_spks), n_mels, int(p.n_out) // 160,
+                              (TL - 1) // (2 * int(pad_frames) + 3) + 1 if drop_silence else 1, pinned=False)
+        check(self.h, self.lib.css_handoff_nemo_all(self.h, C.c_void_p(wav_ptr), int(wav_ld), C.byref(ncfg), C.byref(out.c)))
+        return out
+
+    def run_enqueue_nemo(self, pcm: np.ndarray, cfg: RunCfg, out: Optional[np.ndarray], n_mels: int = 80, pad_frames: int = 8,
+                         drop_silence: bool = True, preemphasis: float = 0.97, normalize: bool = True,
+                         handoff: Optional[NemoHandoff] = None):
+        """run_enqueue plus the hand-off to a NeMo host (css_run_enqueue_nemo): behind the session's waveforms, on the device, the
+        kept ranges and NeMo's log-mel features of all streams (``stream.nemo_features`` states them).  `out` None: features only,
+        no waveform leaves the GPU.  Returns (view of `out` or None, NemoHandoff); both are valid after wait() /
+        wait_sessions().  Not in "split_f16"."""
+        assert pcm.dtype == np.float32 and pcm.flags.c_contiguous and pcm.ndim == 2
+        n, c = pcm.shape
+        p = plan(self.desc, cfg, n)
+        if out is not None:
+            assert out.dtype == np.float32 and out.ndim == 2 and out.shape[0] == self.desc.num_spks and out.shape[1] >= p.n_out \
+                and out.strides[1] == 4
+        ncfg = nemo_cfg(n_mels, pad_frames, drop_silence, preemphasis, normalize)
+        ho = handoff if handoff is not None else self._nemo_handoff(cfg, n, ncfg)
+        check(self.h, self.lib.css_run_enqueue_nemo(self.h, _np_ptr(pcm), n, c, C.byref(cfg.c), None if out is None else _np_ptr(out),
+                                                    0 if out is None else out.strides[0] // 4, C.byref(ncfg), C.byref(ho.c)))
+        self._queued_keep = getattr(self, "_queued_keep", []) + [(pcm, out, cfg, ho)]
+        return (None if out is None else out[:, :p.n_out]), ho
+
+    def run_enqueue_pcm16_nemo(self, planes, cfg: RunCfg, out16: Optional[np.ndarray], peaks: Optional[np.ndarray] = None,
+                               n_mels: int = 80, pad_frames: int = 8, drop_silence: bool = True, preemphasis: float = 0.97,
+                               normalize: bool = True, handoff: Optional[NemoHandoff] = None):
+        """run_enqueue_pcm16 plus the hand-off to a NeMo host (css_run_enqueue_pcm16_nemo): the features are those of the float
+        waveforms before peak normalisation.  `out16` None: features only.  Returns (view of `out16` or None, NemoHandoff)."""
+        n = planes[0].shape[0]
+        for p in planes:
+            assert p.dtype == np.int16 and p.ndim == 1 and p.shape[0] == n and p.flags.c_contiguous
+        c = len(planes)
+        pl = plan(self.desc, cfg, n)
+        S = int(self.desc.num_spks)
+        if out16 is not None:
+            assert out16.dtype == np.int16 and out16.ndim == 2 and out16.shape[0] == S and out16.shape[1] >= pl.n_out and out16.strides[1] == 2
+        assert peaks is None or (peaks.dtype == np.float32 and peaks.shape == (S,) and peaks.flags.c_contiguous)
+        ptrs = (C.c_void_p * c)(*[p.ctypes.data for p in planes])
+        ncfg = nemo_cfg(n_mels, pad_frames, drop_silence, preemphasis, normalize)
+        ho = handoff if handoff is not None else self._nemo_handoff(cfg, n, ncfg)
+        check(self.h, self.lib.css_run_enqueue_pcm16_nemo(self.h, ptrs, n, c, C.byref(cfg.c),
+                                                          None if out16 is None else out16.ctypes.data_as(C.c_void_p),
+                                                          0 if out16 is None else out16.strides[0] // 2,
+                                                          peaks.ctypes.data_as(C.c_void_p) if peaks is not None else None,
+                                                          C.byref(ncfg), C.byref(ho.c)))
+        self._queued_keep = getattr(self, "_queued_keep", []) + [(planes, out16, peaks, cfg, ho)]
+        return (None if out16 is None else out16[:, :pl.n_out]), ho
+
+    def nemo_kernels(self, job):
+        """The kernels of csrc/nemo.hip on caller data (css_nemo_kernels_host): gather, the product, mel, statistics and
+        normalisation as the path launches them.  A job is a dict of the descriptor's scalar fields and its arrays (the WHOLE
+        allocations); the arrays the launches write are copied first -> {operand, raw, mean, stdv, out} as the launches left them."""
+        j = dict(job)
+        d = CssNemoKernelsJob()
+        keep, left = [], {}
+        for (name, dtype), out in [(f, False) for f in NEMO_KERNEL_ARRAYS[0]] + [(f, True) for f in NEMO_KERNEL_ARRAYS[1]]:
+            a = j.pop(name, None)
+            if a is None:
+                continue
+            a = np.ascontiguousarray(a, dtype=dtype).reshape(-1)
+            a = a.copy() if out else a
+            getattr(d, name).p, getattr(d, name).elems = a.ctypes.data, a.size
+            keep.append(a)
+            if out:
+                left[name] = a
+        for k, v in j.items():
+            setattr(d, k, float(v) if k == "preemphasis" else int(v))
+        return self._rate_left(self.lib.css_nemo_kernels_host(self.h, C.byref(d)), left)
 
     # ---- encoder windows of whole sessions (include/css_mi355_session_window.h) ----
     def session_window_bounds(self, cfg: RunCfg, n: int, width: int = 3000, stride: int = 3000, n_mels: int = 80, pad_frames: int = 8,

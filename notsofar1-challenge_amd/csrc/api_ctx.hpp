@@ -151,9 +151,18 @@ struct SessWindowReq {
     void* whole = nullptr; int64_t whole_ld = 0;                // [S][n_mels][whole_ld], or null
     int32_t* n_windows = nullptr; float* window_max = nullptr;  // [S] each
 };
+// The other tail of a hand-off session (api_nemo_handoff.hip, include/css_mi355_nemo_handoff.h): NeMo's features in place of
+// Whisper's.  The ranges and the counts stay SessHandoffReq's; `mel` / `cap_frames` there are unused, and win is off.
+struct SessNemoReq {
+    bool on = false;
+    float preemph = 0.f; int32_t normalize = 1;
+    float* mel = nullptr; int64_t cap_frames = 0;       // [S][n_mels][cap_frames]
+    float* mean = nullptr; float* stdv = nullptr;       // [S][n_mels] each, or null
+};
 struct SessHandoffReq {
     bool on = false;
     CssStreamHandoffCfg cfg{};
+    SessNemoReq nemo;
     float* mel = nullptr; int64_t cap_frames = 0;       // [S][n_mels][cap_frames]; null (a window session may): no log-mel to the host
     SessWindowReq win;
     int64_t* ranges = nullptr; int32_t cap_ranges = 0;  // [S][cap_ranges][2]
@@ -237,6 +246,7 @@ struct css_ctx : SessState {
     // the hand-off of queued sessions (api_session_handoff.hip): the DFT matrix with BOTH filterbanks (a queue may alternate
     // between them, so neither is ever rebuilt), and one set of work buffers -- tails are serial on their stream
     DevBuf sh_tab, sh_work;
+    DevBuf nemo_tab;    // a NeMo session's tables (api_nemo_handoff.hip): the [514][512] analysis matrix and both banks at 257 bins
     PinnedBuf sh_pin;   // css_handoff_logmel_all into pageable arrays: the kernels' destination, copied out after the synchronise
     // sessions of a queued group other than the active one (run_group)
     static constexpr int MAX_GROUP = 8;
@@ -513,6 +523,9 @@ int session_handoff_all_check(css_ctx* h, const float* wav_dev, int64_t wav_ld, 
                               const CssSessionHandoffOut* out, bool mel_optional, int64_t* frames);
 int session_handoff_all_run(css_ctx* h, const float* wav_dev, int64_t wav_ld, const CssStreamHandoffCfg* hcfg, CssSessionHandoffOut* out,
                             const SessWindowReq* win);
+// ---- api_nemo_handoff.hip: session_handoff_prepare / session_handoff_on hand a request with nemo.on over to these
+int nemo_handoff_prepare(css_ctx* h, const CssPlan& pl, const SessHandoffReq& r);
+int nemo_handoff_on(css_ctx* h, const float* wav, int64_t wav_ld, const SessHandoffReq& r, hipStream_t st);
 void reduce_profile(css_ctx* h);
 
 

@@ -90,6 +90,7 @@ int session_handoff_enqueue_check(css_ctx* h, int64_t n_samples, int32_t n_ch, c
 }
 
 int session_handoff_prepare(css_ctx* h, const CssPlan& pl, const SessHandoffReq& r) {
+    if (r.nemo.on) return nemo_handoff_prepare(h, pl, r);   // (a session has one format)
     int rc;
     if (!h->sh_tab.p) {
         std::vector<float> t(SH_DFT_F + SH_MEL80_F + SH_MEL128_F, 0.f);
@@ -103,6 +104,7 @@ int session_handoff_prepare(css_ctx* h, const CssPlan& pl, const SessHandoffReq&
 }
 
 int session_handoff_on(css_ctx* h, const float* wav, int64_t wav_ld, const SessHandoffReq& r, hipStream_t st) {
+    if (r.nemo.on) return nemo_handoff_on(h, wav, wav_ld, r, st);
     const int S = h->d.num_spks;
     const Layout L = layout(S, h->plan, r);
     if (!h->sh_tab.p || h->sh_work.cap < L.bytes) return fail(h, CSS_ERR_STATE, "internal: the session hand-off was not prepared");

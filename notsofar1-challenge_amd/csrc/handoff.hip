@@ -48,19 +48,20 @@ static double mel_to_hz(double m) {
     const double f_sp = 200.0 / 3.0, min_log_hz = 1000.0, min_log_mel = min_log_hz / f_sp, logstep = std::log(6.4) / 27.0;
     return m >= min_log_mel ? min_log_hz * std::exp(logstep * (m - min_log_mel)) : f_sp * m;
 }
-// librosa.filters.mel(sr=16000, n_fft=400, n_mels) (slaney scale and normalisation), float32 [n_mels][201]
-void handoff_build_mel(float* w, int n_mels) {
+// librosa.filters.mel(sr=16000, n_fft=2 (bins - 1), n_mels) (slaney scale and normalisation), float32 [n_mels][bins]: 201 bins
+// for Whisper's 400-point transform, 257 for the 512-point one of nemo.hip
+void handoff_build_mel(float* w, int n_mels, int bins) {
     const double sr = 16000.0;
     std::vector<double> mel_f(n_mels + 2);
     const double lo = hz_to_mel(0.0), hi = hz_to_mel(sr / 2);
     for (int i = 0; i < n_mels + 2; ++i) mel_f[i] = mel_to_hz(lo + (hi - lo) * i / (n_mels + 1));
     for (int i = 0; i < n_mels; ++i) {
         const double enorm = 2.0 / (mel_f[i + 2] - mel_f[i]);
-        for (int f = 0; f < MEL_BINS; ++f) {
-            const double hz = sr / 2 * f / (MEL_BINS - 1);
+        for (int f = 0; f < bins; ++f) {
+            const double hz = sr / 2 * f / (bins - 1);
             const double lower = (hz - mel_f[i]) / (mel_f[i + 1] - mel_f[i]);
             const double upper = (mel_f[i + 2] - hz) / (mel_f[i + 2] - mel_f[i + 1]);
-            w[(size_t)i * MEL_BINS + f] = (float)(std::fmax(0.0, std::fmin(lower, upper)) * enorm);
+            w[(size_t)i * bins + f] = (float)(std::fmax(0.0, std::fmin(lower, upper)) * enorm);
         }
     }
 }

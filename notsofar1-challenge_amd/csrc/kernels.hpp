@@ -219,7 +219,7 @@ void launch_planes_to_rows(const float* planes, float* rows, int B, int F2, int6
 // handoff.hip -- active regions of a separated stream -> Whisper log-mel features on the device
 // ------------------------------------------------------------------------------------------------
 void handoff_build_dft(float* m);                 // [402][416]
-void handoff_build_mel(float* w, int n_mels);     // [n_mels][201]
+void handoff_build_mel(float* w, int n_mels, int bins = 201);   // [n_mels][bins]: the slaney bank over bins - 1 equal steps up to 8 kHz
 void launch_handoff_gather(const float* wav, const int64_t* regions, const int64_t* offs, int nr, int64_t n_act, float* out,
                            int64_t total, hipStream_t s);
 void launch_handoff_mel(const float* spec, int64_t ld, int64_t nfr, const float* w, int n_mels, float* mel, int* gmax, hipStream_t s);
@@ -321,6 +321,32 @@ struct WindowItem {
 constexpr int WINDOW_MULTI_MAX = 32;                    // (CSS_WINDOW_TABLE of the header)
 constexpr int WINDOW_ROWS = 8;                          // mel bands per block
 void launch_stream_windows(const WindowItem* e, int n, hipStream_t s);   // one launch; n <= WINDOW_MULTI_MAX
+
+// ------------------------------------------------------------------------------------------------
+// nemo.hip -- the kept ranges of the separated streams -> NeMo's log-mel features on the device (DESIGN.md 7 "N4 for NeMo hosts")
+// ------------------------------------------------------------------------------------------------
+// Behind the keep-scan of a queued session (launch_session_keep_scan: run table, offsets, st[k].A kept samples, st[k].J = A / 160
+// frames), with no host decision between the steps: gather (all speakers, pre-emphasis across the seams, zero pads), the product
+// (launch_gemm on the [514][512] analysis matrix, exact float32), mel (raw ln rows), statistics, normalisation.  A speaker owns
+// `rows` operand rows of 160 floats -- frame j is the 512 floats from row j -- and rows - 4 is the bound of its frame count.
+constexpr int NEMO_NFFT = 512, NEMO_BINS = 257, NEMO_WIN = 400, NEMO_WIN_OFF = 56, NEMO_HOP = 160;
+constexpr float NEMO_LOG_GUARD = 5.9604644775390625e-8f;   // 2^-24
+constexpr float NEMO_STD_EPS = 1e-5f;
+void nemo_build_dft(float* m);                    // [514][512], window folded in
+struct NemoFeatures {
+    const HandoffState* st; int32_t S, n_mels, normalize, pad_;
+    int64_t rows;                                       // operand rows per speaker; the frame count is taken as at most rows - 4
+    const float* w;                                     // the bank [n_mels][257]
+    float* raw; int64_t raw_ld;                         // [S][n_mels][raw_ld]: ln(mel + 2^-24), frames below the count
+    float* mean; float* stdv;                           // [S][n_mels] each, written where the count is at least 1
+    float* mean_out; float* std_out;                    // the caller's [S][n_mels] (device addresses), or null
+    float* out; int64_t out_ld;                         // the caller's [S][n_mels][out_ld] (device address): frames below the count only
+};
+// operand rows [k rows, (k + 1) rows) of 160 floats: 256 zeros, speaker k's pre-emphasised kept samples, zeros; zeros up to the operand's end + 512
+void launch_nemo_gather(const SessionHandoff& e, const float* wav, int64_t wav_ld, float* operand, int64_t rows, float preemph, hipStream_t s);
+void launch_nemo_mel(const NemoFeatures& e, const float* spec, int64_t ld, hipStream_t s);   // spec [514][ld], speaker k's frames at columns k rows ..
+void launch_nemo_stats(const NemoFeatures& e, hipStream_t s);                                // one block per (band, speaker)
+void launch_nemo_norm(const NemoFeatures& e, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------
 // loss.hip -- validation loss of the training loop (train.py:411 _calc_loss): S x S base-loss sums + the noise term

@@ -79,6 +79,61 @@ def whisper_normalize(raw: np.ndarray, raw_max: Optional[float] = None) -> np.nd
     return (np.maximum(raw, mx - np.float32(8.0)) + np.float32(4.0)) * np.float32(0.25)
 
 
+_NEMO_TABLES: dict = {}
+
+
+def nemo_tables(n_mels: int):
+    """The two float32 tables of the NeMo hand-off (csrc/nemo.hip): the analysis matrix [514, 512] -- rows f: cos, 257 + f: -sin of
+    2 pi f n / 512, times the symmetric 400-point Hann window (a float32 value) at offset 56 -- and the slaney mel bank
+    [n_mels, 257] over 0 .. 8 kHz, both from float64 formulas rounded once."""
+    if n_mels not in _NEMO_TABLES:
+        f, n = np.arange(257)[:, None], np.arange(512)[None, :]
+        w = np.zeros(512)
+        w[56:456] = (0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(400) / 399.0)).astype(np.float32)
+        a = 2.0 * np.pi * ((f * n) % 512) / 512.0
+        A = (np.concatenate([np.cos(a), -np.sin(a)]) * w[None, :]).astype(np.float32)
+        f_sp, min_log_hz, logstep = 200.0 / 3.0, 1000.0, np.log(6.4) / 27.0
+        min_log_mel = min_log_hz / f_sp
+        mel2hz = lambda m: np.where(m >= min_log_mel, min_log_hz * np.exp(logstep * (m - min_log_mel)), f_sp * m)
+        mel_f = mel2hz(np.linspace(0.0, min_log_mel + np.log(8000.0 / min_log_hz) / logstep, n_mels + 2))
+        fft_f = np.linspace(0.0, 8000.0, 257)
+        W = np.zeros((n_mels, 257))
+        for i in range(n_mels):
+            lower = (fft_f - mel_f[i]) / (mel_f[i + 1] - mel_f[i])
+            upper = (mel_f[i + 2] - fft_f) / (mel_f[i + 2] - mel_f[i + 1])
+            W[i] = np.maximum(0.0, np.minimum(lower, upper)) * (2.0 / (mel_f[i + 2] - mel_f[i]))
+        _NEMO_TABLES[n_mels] = (A, W.astype(np.float32))
+    return _NEMO_TABLES[n_mels]
+
+
+def nemo_features(x: np.ndarray, n_mels: int = 80, preemphasis: float = 0.97, normalize: bool = True) -> np.ndarray:
+    """The numpy statement, in float32, of what ``Handle.run_enqueue_nemo`` hands to a NeMo host for one stream: ``x`` is the
+    concatenation of the stream's kept ranges -> float32 [n_mels, len(x) // 160].  NeMo's AudioToMelSpectrogramPreprocessor
+    (published as transformers' ParakeetFeatureExtractor): pre-emphasis ``y[c] = x[c] - p x[c - 1]``, 256 zeros on both sides,
+    frames of 512 at hop 160 under a symmetric 400-point Hann window at offset 56, power spectrum, slaney mel bank at 257 bins,
+    ``ln(mel + 2^-24)``, and with ``normalize`` per band ``(v - mean) / (std + 1e-5)`` with the unbiased std over the frames (0
+    for a single frame).  The device sums in another order: its values agree within the bound of tests/nemo_reference.py, not
+    bit for bit."""
+    x = np.asarray(x, dtype=np.float32).reshape(-1)
+    L = len(x) // 160
+    if L == 0:
+        return np.zeros((n_mels, 0), np.float32)
+    y = x.copy()
+    if preemphasis:
+        y[1:] = x[1:] - np.float32(preemphasis) * x[:-1]
+    A, W = nemo_tables(n_mels)
+    padded = np.concatenate([np.zeros(256, np.float32), y, np.zeros(256, np.float32)])
+    frames = np.lib.stride_tricks.sliding_window_view(padded, 512)[::160][:L].T              # [512, L]
+    spec = A @ frames
+    power = spec[:257] * spec[:257] + spec[257:] * spec[257:]
+    raw = np.log((W @ power).astype(np.float32) + np.float32(2.0 ** -24)).astype(np.float32)
+    if not normalize:
+        return raw
+    mean = raw.astype(np.float64).mean(axis=1)
+    std = np.sqrt(((raw - mean[:, None]) ** 2).sum(axis=1) / (L - 1)) if L > 1 else np.zeros(n_mels)
+    return (raw - mean.astype(np.float32)[:, None]) / (std.astype(np.float32)[:, None] + np.float32(1e-5))
+
+
 def whisper_window(raw: np.ndarray, width: int = 3000, dtype="float16") -> np.ndarray:
     """The numpy statement of css_stream_windows: raw log-mel frames [n_mels, n] of one span -> [n_mels, width].  Columns < n are
     ``whisper_normalize(raw)``, clamped at the span's own maximum M; the columns behind them hold what a frame of digital zeros

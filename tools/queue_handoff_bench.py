@@ -18,7 +18,15 @@ Every arm's outputs are compared for bit equality at the sizes timed (waveforms 
   W   run_enqueue_windows x N with the log-mel to the host as well, wait
   W0  the same with mel_host = NULL: no log-mel crosses PCIe
   W0n W0 with torch_sync=False: without the synchronise of torch's current stream before every enqueue
-Windows of P, W and W0 are compared for bit equality.  --trace-arm W0 --rounds 1: one arm only, for a kernel-trace run."""
+Windows of P, W and W0 are compared for bit equality.  --trace-arm W0 --rounds 1: one arm only, for a kernel-trace run.
+
+--nemo: the hand-off to NeMo hosts of include/css_mi355_nemo_handoff.h (80 bands, the whole streams: drop_silence = 0, so that
+every arm makes the features of the same samples), arms A B C D:
+  A   the route without that header: run_enqueue x N, wait, then per stream the torch CPU rendering of the published definition
+  B   run_enqueue_nemo x N with wav_host = NULL (features only), wait
+  C   run_enqueue_handoff x N with wav_host = NULL (Whisper's features), wait: for scale
+  D   the plain queue: run_enqueue x N, wait
+B's features are compared with A's (float32 against float32: the largest difference is reported, not asserted)."""
 import argparse
 import importlib
 import json
@@ -41,8 +49,9 @@ def main():
     ap.add_argument("--seconds", type=float, default=60.0)
     ap.add_argument("--distinct", type=int, default=4, help="distinct recordings the sessions cycle through")
     ap.add_argument("--max-batch", type=int, default=256)
-    ap.add_argument("--trace-arm", default=None, choices=("P", "A", "B", "C", "H", "W", "W0", "W0n"))
+    ap.add_argument("--trace-arm", default=None, choices=("P", "A", "B", "C", "D", "H", "W", "W0", "W0n"))
     ap.add_argument("--windows", action="store_true", help="the encoder-window arms H P W W0")
+    ap.add_argument("--nemo", action="store_true", help="the NeMo hand-off arms A B C D")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     import torch
@@ -61,6 +70,8 @@ def main():
     pcm = [recs[i % a.distinct] for i in range(N)]
     if a.windows:
         return window_arms(a, sep, run_cfg, pcm, n, n_out)
+    if a.nemo:
+        return nemo_arms(a, sep, run_cfg, pcm, n, n_out)
     wavs = {arm: [L.pinned_empty((S, n_out), np.float32) for _ in range(N)] for arm in "PAB"}
     hos = {arm: [L.SessionHandoff(S, nm, frames, ranges) for _ in range(N)] for arm in "BC"}
     dev_pcm = [torch.from_numpy(np.asarray(r)).cuda() for r in recs]
@@ -207,6 +218,86 @@ def window_arms(a, sep, run_cfg, pcm, n, n_out):
         out["W_minus_H_ms"] = med["W"] - med["H"]
         out["P_minus_H_ms"] = med["P"] - med["H"]
         out["H_spread_ms"] = out["ms_per_session"]["H"]["max"] - out["ms_per_session"]["H"]["min"]
+    print(json.dumps(out))
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(out, f, indent=1)
+    sep.close()
+
+
+def nemo_arms(a, sep, run_cfg, pcm, n, n_out):
+    import torch
+    L, ST = pkg("_lib"), pkg("stream")
+    h, desc, N = sep.handle, sep.desc, a.sessions
+    S, nm = int(desc.num_spks), 80
+    ncfg = dict(n_mels=nm, pad_frames=8, drop_silence=False, preemphasis=0.97, normalize=True)
+    wcfg = dict(n_mels=nm, pad_frames=8, drop_silence=False)
+    frames, ranges = L.nemo_handoff_bounds(desc, run_cfg, L.nemo_cfg(**ncfg), n)
+    wavs = {arm: [L.pinned_empty((S, n_out), np.float32) for _ in range(N)] for arm in "AD"}
+    nemo = [L.NemoHandoff(S, nm, frames, ranges) for _ in range(N)]
+    whisper = [L.SessionHandoff(S, nm, frames, ranges) for _ in range(N)]
+    bank = torch.from_numpy(ST.nemo_tables(nm)[1])
+    window = torch.hann_window(400, periodic=False)
+    feats_a = [None] * N
+
+    def rendering(x):
+        """the published class body (transformers' ParakeetFeatureExtractor) for one utterance, torch on the CPU, float32"""
+        w = torch.from_numpy(x)[None, :]
+        w = torch.cat([w[:, :1], w[:, 1:] - 0.97 * w[:, :-1]], dim=1)
+        stft = torch.stft(w, 512, hop_length=160, win_length=400, window=window, return_complex=True, pad_mode="constant")
+        mel = torch.log(bank @ torch.view_as_real(stft).pow(2).sum(-1) + 2 ** -24)[0, :, :x.shape[0] // 160]
+        mean = mel.mean(dim=1, keepdim=True)
+        std = torch.sqrt(((mel - mean) ** 2).sum(dim=1, keepdim=True) / (mel.shape[1] - 1))
+        return ((mel - mean) / (std + 1e-5)).numpy()
+
+    def arm_plain(out):
+        for i in range(N):
+            h.run_enqueue(pcm[i], run_cfg, out[i])
+        h.wait()
+
+    def arm_a():
+        arm_plain(wavs["A"])
+        for i in range(N):
+            feats_a[i] = [rendering(wavs["A"][i][k]) for k in range(S)]
+
+    def arm_b():
+        for i in range(N):
+            h.run_enqueue_nemo(pcm[i], run_cfg, None, handoff=nemo[i], **ncfg)
+        h.wait()
+
+    def arm_c():
+        for i in range(N):
+            h.run_enqueue_handoff(pcm[i], run_cfg, None, handoff=whisper[i], **wcfg)
+        h.wait()
+
+    arms = {"A": arm_a, "B": arm_b, "C": arm_c, "D": lambda: arm_plain(wavs["D"])}
+    order = [a.trace_arm] if a.trace_arm else list("ABCD")
+    for arm in order:                                        # warm-up: every buffer at its final size
+        arms[arm]()
+    times = {arm: [] for arm in order}
+    for _ in range(a.rounds):
+        for arm in order:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            arms[arm]()
+            times[arm].append((time.perf_counter() - t0) * 1e3 / N)
+    diff = None
+    if not a.trace_arm:
+        diff = max(float(np.abs(nemo[i].mel[k] - feats_a[i][k]).max()) for i in range(N) for k in range(S))
+        assert all(np.array_equal(wavs["A"][i], wavs["D"][i]) for i in range(N))
+    up, wav_b, mel_b = n * 7 * 4, S * n_out * 4, S * nm * frames * 4
+    out = dict(workload=f"{a.seconds:g} s x 7 channels, mc_v1, activity_th 0.3, {N} sessions per window, {a.rounds} windows per arm, "
+                        f"{a.distinct} distinct recordings, NeMo hand-off {ncfg}",
+               ms_per_session={arm: dict(median=float(np.median(t)), min=float(np.min(t)), max=float(np.max(t)), all=[round(v, 4) for v in t])
+                               for arm, t in times.items()},
+               max_abs_B_minus_A=diff, frames_per_stream=frames,
+               pcie_bytes_per_session=dict(A=up + wav_b, B=up + mel_b, C=up + mel_b, D=up + wav_b))
+    if not a.trace_arm:
+        med = {arm: out["ms_per_session"][arm]["median"] for arm in order}
+        out["B_minus_D_ms"] = med["B"] - med["D"]
+        out["A_minus_D_ms"] = med["A"] - med["D"]
+        out["C_minus_D_ms"] = med["C"] - med["D"]
+        out["D_spread_ms"] = out["ms_per_session"]["D"]["max"] - out["ms_per_session"]["D"]["min"]
     print(json.dumps(out))
     if a.json:
         with open(a.json, "w") as f:
