@@ -38,8 +38,13 @@ resampled, scaled and rounded on the device (CssStream(output=dict(rate=HZ, dtyp
 takes 48 kHz PCM16 and plays 48 kHz PCM16 needs, with nothing crossing PCIe at the model rate.  The previews stay float32 at
 the model rate.
 
-    python examples/live_stream.py [--seconds 30] [--rooms N] [--logmel] [--pcm16] [--rate HZ] [--preview] [--window] [--present]
-                                   [--out-rate HZ] [--out-pcm16]
+With --nemo every stream has the NeMo hand-off on instead (CssStream(nemo=...), include/css_mi355_stream_nemo.h): each tick also
+returns, per room and speaker, the raw NeMo frames ln(mel + 2^-24) that became complete and the kept ranges -- what a cache-aware
+streaming FastConformer, a streaming diarizer or a frame-level VAD on the same GPU takes (they normalise per short window
+themselves, or not at all).  A stream has one format: --nemo does not go with --logmel, --window or --present; a plain --preview does.
+
+    python examples/live_stream.py [--seconds 30] [--rooms N] [--logmel | --nemo] [--pcm16] [--rate HZ] [--preview] [--window]
+                                   [--present] [--out-rate HZ] [--out-pcm16]
 """
 import argparse
 import os
@@ -58,6 +63,7 @@ import notsofar1_challenge_amd.weights as W        # noqa: E402
 
 
 HANDOFF = dict(n_mels=80, pad_frames=8, drop_silence=True)
+NEMO = dict(n_mels=80, pad_frames=8, drop_silence=True, preemphasis=0.97)
 
 
 def print_handoff(streams, fs):
@@ -65,6 +71,14 @@ def print_handoff(streams, fs):
     for r, s in enumerate(streams):
         h = s.handoff
         per = [f"{m.shape[1]:4d} fr {float((g[:, 1] - g[:, 0]).sum()) / fs:5.2f} s" for m, g in zip(h.mel, h.ranges)]
+        print(f"    room {r}: " + " | ".join(per))
+
+
+def print_nemo(streams, fs):
+    """per room and speaker: NeMo frames of this tick (from which frame of the concatenation on) and kept seconds"""
+    for r, s in enumerate(streams):
+        h = s.nemo
+        per = [f"{m.shape[1]:4d} fr from {int(f0):5d} {float((g[:, 1] - g[:, 0]).sum()) / fs:5.2f} s" for m, g, f0 in zip(h.mel, h.ranges, h.first_frame)]
         print(f"    room {r}: " + " | ".join(per))
 
 
@@ -129,7 +143,8 @@ def present_windows(group, streams, batch):
     return out, live
 
 
-def rooms(sep, n_rooms, seconds, fs, chunk, logmel=False, pcm16=False, rate=None, preview=False, window=False, present=False, output=None):
+def rooms(sep, n_rooms, seconds, fs, chunk, logmel=False, pcm16=False, rate=None, preview=False, window=False, present=False, output=None,
+          nemo=False):
     mixes = [SYN.synth_meeting(seconds, 7, seed=1 + r)[0] for r in range(n_rooms)]
     if rate:
         mixes = [capture_at(m, fs, rate) for m in mixes]
@@ -137,7 +152,7 @@ def rooms(sep, n_rooms, seconds, fs, chunk, logmel=False, pcm16=False, rate=None
     elif pcm16:
         mixes = [capture(m) for m in mixes]
     streams = [STR.CssStream(sep, CSS.CssCfg(), fs=fs, num_channels=7, handoff=HANDOFF if logmel else None, input_rate=rate,
-                             window_history=3000 if window else None, output=output) for _ in mixes]
+                             window_history=3000 if window else None, output=output, nemo=NEMO if nemo else None) for _ in mixes]
     group = STR.CssStreamGroup(streams)
     if window:
         import torch
@@ -156,6 +171,8 @@ def rooms(sep, n_rooms, seconds, fs, chunk, logmel=False, pcm16=False, rate=None
               f"estimator batches {group.stats.estimator_batches} ({group.stats.estimator_segments} segments)")
         if logmel:
             print_handoff(streams, fs)
+        if nemo:
+            print_nemo(streams, fs)   # -> the streaming encoder's next chunk: torch.from_numpy(s.nemo.mel[k])[None]
         if preview:
             t = time.perf_counter()
             pv = group.preview(handoff=logmel)
@@ -182,6 +199,7 @@ def main():
     ap.add_argument("--seconds", type=float, default=30.0)
     ap.add_argument("--rooms", type=int, default=1, help="meetings fed tick by tick through one CssStreamGroup")
     ap.add_argument("--logmel", action="store_true", help="also return Whisper log-mel frames and kept ranges with every tick")
+    ap.add_argument("--nemo", action="store_true", help="also return raw NeMo log-mel frames and kept ranges with every tick (not with --logmel)")
     ap.add_argument("--pcm16", action="store_true", help="the source delivers int16 samples: push_pcm16 instead of push")
     ap.add_argument("--preview", action="store_true", help="after each tick's push, also fetch the provisional tail (preview)")
     ap.add_argument("--rate", type=int, default=0, help="the source delivers int16 samples at this rate: CssStream(input_rate=HZ)")
@@ -193,12 +211,14 @@ def main():
     fs = 16000
     a.window = a.window or a.present
     a.logmel = a.logmel or a.window
+    if a.nemo and a.logmel:
+        ap.error("--nemo is a hand-off format of its own: not with --logmel, --window or --present")
     a.pcm16 = a.pcm16 or bool(a.rate)
     output = dict(rate=a.out_rate or fs, dtype="int16" if a.out_pcm16 else "float32") if a.out_rate or a.out_pcm16 else None
     desc = W.ModelDesc.mc_v1()
     sep = SEP.HipSeparator(W.apply_golden_recipe(W.portable_state_dict(desc, 0)), None, device=0)
     if a.rooms > 1:
-        rooms(sep, a.rooms, a.seconds, fs, fs // 2, a.logmel, a.pcm16, a.rate or None, a.preview, a.window, a.present, output)
+        rooms(sep, a.rooms, a.seconds, fs, fs // 2, a.logmel, a.pcm16, a.rate or None, a.preview, a.window, a.present, output, a.nemo)
         sep.close()
         return
     mix = SYN.synth_meeting(a.seconds, 7, seed=1)[0]
@@ -210,7 +230,7 @@ def main():
     streams = [[] for _ in range(desc.num_spks)]
     mels = [[] for _ in range(desc.num_spks)]
     with STR.CssStream(sep, CSS.CssCfg(), fs=fs, num_channels=7, handoff=HANDOFF if a.logmel else None, input_rate=a.rate or None,
-                       window_history=3000 if a.window else None, output=output) as s:
+                       window_history=3000 if a.window else None, output=output, nemo=NEMO if a.nemo else None) as s:
         if a.window:
             import torch
             batch = torch.empty((desc.num_spks, HANDOFF["n_mels"], 3000), dtype=torch.float16, device="cuda")
@@ -228,6 +248,10 @@ def main():
                 print_handoff([s], fs)
                 for k, m in enumerate(s.handoff.mel):
                     mels[k].append(m)
+            if a.nemo:
+                print_nemo([s], fs)
+                for k, m in enumerate(s.nemo.mel):
+                    mels[k].append(m)
             if a.preview:
                 try:
                     count = s.preview(handoff=a.logmel)[0].shape[0]
@@ -242,6 +266,11 @@ def main():
                 present_windows(STR.CssStreamGroup([s]), [s], batch)
         for k, o in enumerate(s.finish()):
             streams[k].append(o)
+        if a.nemo:
+            for k, m in enumerate(s.nemo.mel):
+                mels[k].append(m)
+            for k in range(desc.num_spks):
+                print(f"speaker {k}: {np.concatenate(mels[k], axis=1).shape[1]} NeMo frames in all")
         if a.logmel:
             for k, m in enumerate(s.handoff.mel):
                 mels[k].append(m)

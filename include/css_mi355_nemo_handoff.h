@@ -23,7 +23,7 @@
  *      normalize == 0: the raw ln values (a diarizer host normalises per embedding window itself: NeMo's speaker models
  *      normalise per segment).
  *
- * Frames of 512 samples at hop 256 only.  Out of scope: streamed sessions, encoder-style windows, float16 output, rate
+ * Frames of 512 samples at hop 256 only.  Streamed sessions: css_mi355_stream_nemo.h.  Out of scope: encoder-style windows, float16 output, rate
  * sessions, other frame geometries, CSS_LINEAR_SPLIT_F16 (CSS_ERR_STATE), and NeMo's pad_to / dither, which are host and
  * training concerns.  A session has one format, Whisper's or this one, not both. */
 #ifndef CSS_MI355_NEMO_HANDOFF_H

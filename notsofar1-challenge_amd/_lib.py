@@ -256,6 +256,26 @@ class CssStreamMelJob(C.Structure):
                [(n, CssKArray) for n in ("n_new", "st", "mel", "ring", "fmax", "pvmax")]
 
 
+class CssStreamNemoCfg(C.Structure):            # include/css_mi355_stream_nemo.h
+    _fields_ = [("n_mels", C.c_int32), ("pad_frames", C.c_int32), ("drop_silence", C.c_int32), ("preemphasis", C.c_float)]
+
+
+class CssStreamNemoArray(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("elems", C.c_int64)]
+
+
+class CssStreamNemoAppendJob(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("pad", "drop", "closing", "S")] + [("preemphasis", C.c_float), ("reserved", C.c_int32)] + \
+               [(n, C.c_int64) for n in ("gate_ld", "out_ld", "out_base", "carry_ld", "t_g0", "t_g1", "D0", "D1", "row0", "rows")] + \
+               [(n, CssStreamNemoArray) for n in ("gate", "out", "carry_in", "carry_out", "tail_in", "tail_out", "st", "act_out", "n_new",
+                                                  "xlast_in", "xlast_out")]
+
+
+class CssStreamNemoMelJob(C.Structure):
+    _fields_ = [("n_mels", C.c_int32), ("reserved", C.c_int32)] + [(n, C.c_int64) for n in ("row0", "rows", "mel_ld")] + \
+               [("n_new", CssStreamNemoArray), ("mel", CssStreamNemoArray)]
+
+
 # a state row of the streamed hand-off (csrc/kernels.hpp HandoffState)
 HANDOFF_STATE = np.dtype([("A", "<i8"), ("J", "<i8"), ("gmax", "<i4"), ("pad", "<i4")])
 # per descriptor: the arrays a launch only reads, and the arrays it may write (copied first, returned as the launch left them)
@@ -269,6 +289,14 @@ STREAM_KERNEL_ARRAYS = {
                             ("act_out", np.uint8), ("n_new", np.int32))),
     "CssStreamMelJob": ((("n_new", np.int32),), (("st", HANDOFF_STATE), ("mel", np.float32), ("ring", np.float32), ("fmax", np.float32),
                                                   ("pvmax", np.float32))),
+}
+# the same for the two kernel entries of include/css_mi355_stream_nemo.h
+STREAM_NEMO_ARRAYS = {
+    "CssStreamNemoAppendJob": ((("gate", np.uint8), ("out", np.float32), ("carry_in", np.float32), ("tail_in", np.float32),
+                                ("xlast_in", np.float32)),
+                               (("carry_out", np.float32), ("tail_out", np.float32), ("st", HANDOFF_STATE), ("act_out", np.uint8),
+                                ("n_new", np.int32), ("xlast_out", np.float32))),
+    "CssStreamNemoMelJob": ((("n_new", np.int32),), (("mel", np.float32),)),
 }
 
 
@@ -625,6 +653,16 @@ NEMO_HANDOFF_ABI = {
                                              C.POINTER(CssNemoCfg), C.POINTER(CssNemoOut)]),
     "css_nemo_kernels_host": (C.c_int, [_P, C.POINTER(CssNemoKernelsJob)]),
 }
+# include/css_mi355_stream_nemo.h (a table of its own, as NEMO_HANDOFF_ABI)
+STREAM_NEMO_ABI = {
+    "css_stream_nemo_open": (C.c_int, [_P, C.c_int32, C.POINTER(CssStreamNemoCfg)]),
+    "css_stream_nemo_bounds": (C.c_int, [C.POINTER(CssModelDesc), C.POINTER(CssRunCfg), C.POINTER(CssStreamNemoCfg), C.c_int64,
+                                         C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "css_stream_nemo_final_frames": (C.c_int, [C.POINTER(CssModelDesc), C.POINTER(CssRunCfg), C.POINTER(CssStreamNemoCfg), C.c_int64,
+                                               C.POINTER(C.c_int64)]),
+    "css_stream_nemo_append_host": (C.c_int, [_P, C.POINTER(CssStreamNemoAppendJob), C.c_int32, _P, C.c_int64]),
+    "css_stream_nemo_mel_host": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.c_int64, C.POINTER(CssStreamNemoMelJob), C.c_int32]),
+}
 WINDOW_KERNEL_ITEMS = 64                         # CSS_WINDOW_KERNEL_ITEMS
 ARRAY_MIN_MICS, ARRAY_MAX_MICS = 2, 8            # CSS_ARRAY_MIN_MICS, CSS_ARRAY_MAX_MICS
 SESSION_SCAN_CHUNK = 1024                        # CSS_SESSION_SCAN_CHUNK: the keep-scan kernel's step, in gate frames / sample blocks
@@ -677,7 +715,7 @@ def load() -> C.CDLL:
                               list(ARRAY_SIGNATURES.items()) + list(SESSION_RATE_SIGNATURES.items()) +
                               list(SESSION_WINDOW_BINDINGS.items()) + list(RATE_KERNEL_BINDINGS.items()) +
                               list(STREAM_KERNEL_BINDINGS.items()) + list(HANDOFF_KERNEL_BINDINGS.items()) +
-                              list(NEMO_HANDOFF_ABI.items())):
+                              list(NEMO_HANDOFF_ABI.items()) + list(STREAM_NEMO_ABI.items())):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -1031,6 +1069,29 @@ def handoff_kept_ranges(act: np.ndarray, first_frame: int, n_known: int, pad_fra
     if rc != CSS_OK:
         raise CssError(rc, "css_handoff_kept_ranges: bad argument, a missing frame or too little room")
     return buf[:n.value].copy()
+
+
+def stream_nemo_cfg(n_mels: int = 80, pad_frames: int = 8, drop_silence: bool = True, preemphasis: float = 0.97) -> CssStreamNemoCfg:
+    return CssStreamNemoCfg(int(n_mels), int(pad_frames), int(bool(drop_silence)), float(preemphasis))
+
+
+def stream_nemo_bounds(desc, run_cfg: RunCfg, ncfg: CssStreamNemoCfg, n_samples: int):
+    """css_stream_nemo_bounds: (frames, ranges, gate frames) that suffice for a push of `n_samples` (-1: finish)"""
+    f, r, a = C.c_int64(), C.c_int32(), C.c_int64()
+    rc = load().css_stream_nemo_bounds(C.byref(make_desc(desc)), C.byref(run_cfg.c), C.byref(ncfg), int(n_samples),
+                                       C.byref(f), C.byref(r), C.byref(a))
+    if rc != CSS_OK:
+        raise CssError(rc, "css_stream_nemo_bounds: bad configuration")
+    return int(f.value), int(r.value), int(a.value)
+
+
+def stream_nemo_final_frames(desc, run_cfg: RunCfg, ncfg: CssStreamNemoCfg, n_pushed: int) -> int:
+    """css_stream_nemo_final_frames (drop_silence = 0 only): NeMo frames that are final after `n_pushed` samples"""
+    n = C.c_int64()
+    rc = load().css_stream_nemo_final_frames(C.byref(make_desc(desc)), C.byref(run_cfg.c), C.byref(ncfg), int(n_pushed), C.byref(n))
+    if rc != CSS_OK:
+        raise CssError(rc, "css_stream_nemo_final_frames: bad configuration, or drop_silence is on")
+    return int(n.value)
 
 
 def stream_handoff_final_frames(desc, run_cfg: RunCfg, hcfg: CssStreamHandoffCfg, n_pushed: int) -> int:
@@ -1628,6 +1689,26 @@ class Handle:
         for d in tab:
             d.has_ring, d.has_pvmax = int(bool(d.ring.p)), int(bool(d.pvmax.p))
         return self._rate_left(self.lib.css_stream_mel_host(self.h, int(S), _np_ptr(spec), spec.size, int(ld), tab, len(jobs)), left)
+
+    def stream_nemo_append(self, jobs, operand):
+        """launch_nemo_append_multi (css_stream_nemo_append_host): ``stream_append``'s jobs with ``preemphasis``, ``xlast_in`` and
+        ``xlast_out``, tails of y[160 J - 256, A).  -> ([{carry_out, tail_out, st, act_out, n_new, xlast_out, rows, row0}], operand)"""
+        operand = np.ascontiguousarray(operand, dtype=np.float32).reshape(-1).copy()
+        jobs = [dict(j) for j in jobs]
+        pre = [float(j.pop("preemphasis", 0.0)) for j in jobs]
+        tab, keep, left = self._stream_kernel_table(CssStreamNemoAppendJob, jobs, STREAM_NEMO_ARRAYS)
+        for d, p in zip(tab, pre):
+            d.preemphasis = p
+        rc = self.lib.css_stream_nemo_append_host(self.h, tab, len(jobs), _np_ptr(operand), operand.size)
+        for d, got in zip(tab, left):
+            got["rows"], got["row0"] = int(d.rows), int(d.row0)
+        return self._rate_left(rc, (left, operand))
+
+    def stream_nemo_mel(self, S: int, spec, ld: int, jobs):
+        """launch_nemo_mel_multi (css_stream_nemo_mel_host) on spec [514][ld] -> [{mel}]"""
+        spec = np.ascontiguousarray(spec, dtype=np.float32).reshape(-1)
+        tab, keep, left = self._stream_kernel_table(CssStreamNemoMelJob, jobs, STREAM_NEMO_ARRAYS)
+        return self._rate_left(self.lib.css_stream_nemo_mel_host(self.h, int(S), _np_ptr(spec), spec.size, int(ld), tab, len(jobs)), left)
 
     # ---- the window kernels and the queued sessions' hand-off kernels of csrc/handoff.hip on caller data
     #      (include/css_mi355_handoff_kernels.h; tests/test_hip_window_kernels.py).  A job is a dict as above; an array with an

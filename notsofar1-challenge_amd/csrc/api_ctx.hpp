@@ -526,6 +526,9 @@ int session_handoff_all_run(css_ctx* h, const float* wav_dev, int64_t wav_ld, co
 // ---- api_nemo_handoff.hip: session_handoff_prepare / session_handoff_on hand a request with nemo.on over to these
 int nemo_handoff_prepare(css_ctx* h, const CssPlan& pl, const SessHandoffReq& r);
 int nemo_handoff_on(css_ctx* h, const float* wav, int64_t wav_ld, const SessHandoffReq& r, hipStream_t st);
+// css_ctx::nemo_tab, built on first use, and the bank of n_mels (80 / 128) in it; the matrix is at its start
+int nemo_ensure_tables(css_ctx* h);
+const float* nemo_bank(const css_ctx* h, int n_mels);
 void reduce_profile(css_ctx* h);
 
 

@@ -76,19 +76,6 @@ SessHandoffReq make_req(const CssNemoCfg& c, void* const dev[6], int64_t cap_fra
 
 bool out_complete(const CssNemoOut* o) { return o && o->mel_host && o->ranges_host && o->n_frames && o->n_ranges; }
 
-int ensure_tables(css_ctx* h) {
-    if (h->nemo_tab.p) return CSS_OK;
-    std::vector<float> t(NM_DFT_F + NM_MEL80_F + NM_MEL128_F, 0.f);
-    nemo_build_dft(t.data());
-    handoff_build_mel(t.data() + NM_DFT_F, 80, NEMO_BINS);
-    handoff_build_mel(t.data() + NM_DFT_F + NM_MEL80_F, 128, NEMO_BINS);
-    int rc;
-    if ((rc = ensure(h, h->nemo_tab, t.size() * sizeof(float))) != CSS_OK) return rc;
-    HIPCHK(h, hipMemcpy(h->nemo_tab.p, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));   // (nothing reads it yet)
-    return CSS_OK;
-}
-const float* bank(const css_ctx* h, int n_mels) { return (const float*)h->nemo_tab.p + NM_DFT_F + (n_mels == 80 ? 0 : NM_MEL80_F); }
-
 // steps two to six on `st`: e holds the run table and the counts, f the rest
 void features_on(css_ctx* h, const SessionHandoff& e, NemoFeatures f, const float* wav, int64_t wav_ld, float* operand, float* spec, int64_t ld,
                  float preemph, hipStream_t st) {
@@ -97,7 +84,7 @@ void features_on(css_ctx* h, const SessionHandoff& e, NemoFeatures f, const floa
     g.A = (const float*)h->nemo_tab.p; g.lda = NEMO_NFFT; g.B = operand; g.ldb = NEMO_HOP; g.C = spec; g.ldc = ld;
     g.M = 2 * NEMO_BINS; g.N = (int)(f.rows * e.S); g.K = NEMO_NFFT; g.batch = 1; g.alpha = 1.f;
     launch_gemm(g, st);                                     // exact float32 matrix cores
-    f.w = bank(h, f.n_mels);
+    f.w = nemo_bank(h, f.n_mels);
     launch_nemo_mel(f, spec, ld, st);
     launch_nemo_stats(f, st);
     launch_nemo_norm(f, st);
@@ -127,9 +114,22 @@ int enqueue_check(css_ctx* h, int64_t n_samples, int32_t n_ch, const CssRunCfg* 
 }
 }  // namespace
 
+int nemo_ensure_tables(css_ctx* h) {
+    if (h->nemo_tab.p) return CSS_OK;
+    std::vector<float> t(NM_DFT_F + NM_MEL80_F + NM_MEL128_F, 0.f);
+    nemo_build_dft(t.data());
+    handoff_build_mel(t.data() + NM_DFT_F, 80, NEMO_BINS);
+    handoff_build_mel(t.data() + NM_DFT_F + NM_MEL80_F, 128, NEMO_BINS);
+    int rc;
+    if ((rc = ensure(h, h->nemo_tab, t.size() * sizeof(float))) != CSS_OK) return rc;
+    HIPCHK(h, hipMemcpy(h->nemo_tab.p, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));   // (nothing reads it yet)
+    return CSS_OK;
+}
+const float* nemo_bank(const css_ctx* h, int n_mels) { return (const float*)h->nemo_tab.p + NM_DFT_F + (n_mels == 80 ? 0 : NM_MEL80_F); }
+
 int nemo_handoff_prepare(css_ctx* h, const CssPlan& pl, const SessHandoffReq& r) {
     int rc;
-    if ((rc = ensure_tables(h)) != CSS_OK) return rc;
+    if ((rc = nemo_ensure_tables(h)) != CSS_OK) return rc;
     return ensure(h, h->sh_work, layout(h->d.num_spks, pl, r.cfg.n_mels, r.cap_ranges).bytes);
 }
 
@@ -308,7 +308,7 @@ int css_nemo_kernels_host(css_handle_t h, CssNemoKernelsJob* job) {
     }
     int rc;
     HIPCHK(h, hipSetDevice(h->device));
-    if ((rc = ensure_tables(h)) != CSS_OK) return rc;
+    if ((rc = nemo_ensure_tables(h)) != CSS_OK) return rc;
     const int64_t ld = (j.rows * S + 3) / 4 * 4;
     Stager sg;
     const size_t a_regs = sg.take(regs, 8, false), a_offs = sg.take(offs, 8, false), a_st = sg.take(st, sizeof(HandoffState), false),

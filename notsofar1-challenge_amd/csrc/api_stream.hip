@@ -35,7 +35,8 @@ void for_each_buffer(const StreamState* s, Fn fn) {
         for (const DevBuf* d : {&s->pcm[b], &s->X[b], &s->masks[b], &s->sep[b], &s->perms[b], &s->act_b[b], &s->G[b]}) fn(*d);
     for (const DevBuf* d : {&s->scm, &s->bfw, &s->pnorm, &s->costs, &s->pit_part, &s->Y, &s->out, &s->segw, &s->pcm16_stage}) fn(*d);
     if (s->ho)
-        for (const DevBuf* d : {&s->ho->gate, &s->ho->carry[0], &s->ho->carry[1], &s->ho->tail[0], &s->ho->tail[1], &s->ho->ring, &s->ho->fmax}) fn(*d);
+        for (const DevBuf* d : {&s->ho->gate, &s->ho->carry[0], &s->ho->carry[1], &s->ho->tail[0], &s->ho->tail[1], &s->ho->ring, &s->ho->fmax,
+                                &s->ho->xlast[0], &s->ho->xlast[1]}) fn(*d);
     if (s->rate)
         for (const DevBuf* d : {&s->rate->stage, &s->rate->hist[0], &s->rate->hist[1], &s->rate->tab}) fn(*d);
     if (s->outp)
@@ -805,6 +806,7 @@ int preview_items(css_ctx* h, const std::vector<PreviewItem>& items, CssStreamGr
         CloseJob j{s, CssPlan{}, closing_samples(s), p.out_host, p.cap, 0};
         if (CssStreamHandoffOut* ho = items[(size_t)i].ho) {
             if (!s->ho) return refuse(CSS_ERR_STATE, "the hand-off of this stream is off (css_stream_handoff_open)");
+            if (s->ho->nemo) return refuse(CSS_ERR_STATE, "a preview with hand-off of a NeMo stream is not supported (css_stream_preview works)");
             if (!items[(size_t)i].first_frame) return refuse(CSS_ERR_INVALID_ARG, "hand-off outputs without first_frame");
             const int hrc = check_handoff_out(s, ho, -1, &why);   // a preview is a finish at this moment
             if (hrc != CSS_OK) return refuse(hrc, why);
@@ -812,6 +814,7 @@ int preview_items(css_ctx* h, const std::vector<PreviewItem>& items, CssStreamGr
         }
         if (items[(size_t)i].present) {
             const PreviewItem& it = items[(size_t)i];
+            if (s->ho && s->ho->nemo) return refuse(CSS_ERR_STATE, "windows up to the present of a NeMo stream are not supported");
             if (!s->ho || !s->ho->hist_frames) return refuse(CSS_ERR_STATE, "the stream has no frame history (css_stream_window_open)");
             if (it.n_windows < 0 || (it.n_windows > 0 && (!it.windows || !it.ho)))
                 return refuse(CSS_ERR_INVALID_ARG, "n_windows < 0, or windows without `windows` or without hand-off outputs (ph.ho)");

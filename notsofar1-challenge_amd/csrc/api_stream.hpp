@@ -9,6 +9,7 @@
 #include "../../include/css_mi355_window.h"
 #include "../../include/css_mi355_present_window.h"
 #include "../../include/css_mi355_stream_out.h"
+#include "../../include/css_mi355_stream_nemo.h"
 
 #include <climits>
 
@@ -36,6 +37,12 @@ struct HandoffStream {
     // j mod hist_frames, and their maxima over the bands [S][hist_frames]; one generation, written by committed rounds only
     DevBuf ring, fmax;
     int64_t hist_frames = 0;
+    // the NeMo format (css_stream_nemo_open, include/css_mi355_stream_nemo.h): everything above but the history serves it as it
+    // serves Whisper's (cfg holds n_mels, pad_frames, drop_silence; tail at NEMO_TAIL_LD); the last kept sample per speaker
+    // travels in two generations beside carry and tail
+    bool nemo = false;
+    float preemph = 0.f;
+    DevBuf xlast[2];
 };
 
 // Per handle, made when the first stream switches the hand-off on.
@@ -46,6 +53,9 @@ struct HandoffCtx {
     DevBuf present; PinnedBuf present_pin;   // css_stream_windows / css_stream_present_windows: a WindowOut per window of one call, and its staging
     int32_t launches = 0, products = 0;
     int64_t frames = 0;
+    // the same for the NeMo streams of a round (their own operand, spectra, results and staging: a round may have both formats)
+    DevBuf nemo_operand, nemo_spec, nemo_res;
+    std::vector<PinnedBuf> nemo_pinned;
 };
 
 // Per stream with a rate ratio (css_stream_set_rate; resample.hip).  Nothing here is part of the window: the rebase never touches

@@ -2,6 +2,8 @@
 // bits, the kept sample ranges and the raw Whisper log-mel frames that became final.  The step sits between tail() and the
 // downloads of a round: three launches for all streams of the round (handoff.hip: append, ONE DFT product, mel), results
 // into page-locked staging under the call's final synchronise, where the host trims them into the caller's buffers.
+// The NeMo format (css_stream_nemo_*; include/css_mi355_stream_nemo.h) is the same step with nemo_stream.hip's kernels and the
+// offline NeMo path's tables: raw ln(mel + 2^-24) frames instead, no running maximum, no previews with hand-off, no history.
 // A hand-off stream with a frame history (css_stream_window_open, include/css_mi355_window.h) also keeps its last raw
 // log-mel frames in a ring on the device: the mel launch of a committed round leaves them there.  css_stream_windows turns spans
 // of them into Whisper encoder inputs in the caller's device memory, css_stream_present_windows spans that end in a preview's
@@ -16,12 +18,15 @@ constexpr size_t HO_DFT_F = (size_t)402 * 416, HO_MEL80_F = (size_t)80 * 201, HO
 // fewer than T + halo + pad + 2 blocks (t_g >= K - T - halo, n_out = (max(K, T) + 1) blocks).  J frames need 160 J + 40
 // samples, so a call that appends dn samples completes at most dn / 160 + 1 frames -- (dn + 200) / 160 + 1 at finish, which
 // also emits the frames the trailing reflection completes.  Two ranges of a call have a dropped block between them.
+// The NeMo format (include/css_mi355_stream_nemo.h) differs in `lead`, the samples of the next hop a frame waits for: Whisper's
+// frame j reads concatenated samples below 160 j + 200 (+ 1: the reflection), NeMo's below 160 j + 256.
+constexpr int64_t WHISPER_LEAD = 200, NEMO_LEAD = NEMO_NFFT / 2;
 struct HandoffNeed { int64_t frames; int32_t ranges; int64_t activity; };
-static HandoffNeed handoff_need(int T, int hop, int halo, const CssStreamHandoffCfg& c, int64_t n_samples) {
+static HandoffNeed handoff_need(int T, int hop, int halo, const CssStreamHandoffCfg& c, int64_t n_samples, int64_t lead = WHISPER_LEAD) {
     const int pad = c.drop_silence ? c.pad_frames : 0;
     const int64_t blocks = n_samples < 0 ? (int64_t)T + hop + halo + pad + 3 : n_samples / 256 + 1 + hop;
     HandoffNeed n;
-    n.frames = (blocks * 256 + 200) / 160 + 2;
+    n.frames = (blocks * 256 + lead) / 160 + 2;
     n.ranges = c.drop_silence ? (int32_t)std::min<int64_t>(blocks / 2 + 1, INT32_MAX) : 1;
     n.activity = blocks;
     return n;
@@ -29,6 +34,13 @@ static HandoffNeed handoff_need(int T, int hop, int halo, const CssStreamHandoff
 // frames of the operand a round reserves for one speaker that appends at most dn samples: the frames it can complete, the
 // rows the last frame's 416 columns reach into, and the gap to the next owner
 static int64_t handoff_rows(int64_t dn) { return (dn + 200) / 160 + 2 + 3; }
+// the same for NeMo's 512 columns (api_stream_kernels.hip states it again for the kernel entry)
+static int64_t nemo_rows(int64_t dn) { return (dn + NEMO_LEAD) / NEMO_HOP + 2 + 4; }
+// frames of a concatenation of A samples: of a finished stream, or complete while it is open
+static int64_t frames_complete(bool nemo, bool closing, int64_t A) {
+    if (closing) return A / 160;
+    return nemo ? (A >= NEMO_LEAD ? (A - NEMO_LEAD) / NEMO_HOP + 1 : 0) : (A >= 201 ? (A - 200) / 160 + 1 : 0);
+}
 
 static int check_handoff_cfg(const CssStreamHandoffCfg* c) {
     if (!c || (c->n_mels != 80 && c->n_mels != 128) || c->pad_frames < 0 || c->pad_frames > 4096) return CSS_ERR_INVALID_ARG;
@@ -37,8 +49,8 @@ static int check_handoff_cfg(const CssStreamHandoffCfg* c) {
 
 // what a call must find in the hand-off outputs `o` of a stream with the hand-off on
 int check_handoff_out(const StreamState* s, const CssStreamHandoffOut* o, int64_t n_samples, std::string* why) {
-    const HandoffNeed n = handoff_need(s->T, s->hop, s->halo, s->ho->cfg, n_samples);
-    if (!o->mel_host || !o->ranges_host || !o->n_frames || !o->n_ranges || !o->raw_max || o->cap_frames < n.frames ||
+    const HandoffNeed n = handoff_need(s->T, s->hop, s->halo, s->ho->cfg, n_samples, s->ho->nemo ? NEMO_LEAD : WHISPER_LEAD);
+    if (!o->mel_host || !o->ranges_host || !o->n_frames || !o->n_ranges || (!o->raw_max && !s->ho->nemo) || o->cap_frames < n.frames ||
         o->cap_ranges < n.ranges || (o->activity_host && o->cap_activity < n.activity)) {
         *why = "hand-off capacities below css_stream_handoff_bounds for this call";
         return CSS_ERR_INVALID_ARG;
@@ -62,12 +74,19 @@ void handoff_begin_call(css_ctx* h) {
 // A stream's share (RoundJob::handoff): frames [t_g, t_hi) became gated-final, the output buffer holds (q_hi - t_g) hop samples per
 // speaker from sample t_g * hop on.  A preview's round with windows up to the present (n_windows) also leaves the maxima over the
 // bands of the frames it makes (pvmax).
-int handoff_round(css_ctx* h, const std::vector<RoundJob>& all, size_t round, std::vector<HandoffRec>* recs, bool commit) {
+// One format's streams of the round: Whisper's (handoff.hip) or, `nemo`, NeMo's (nemo_stream.hip) -- the same three steps on the
+// format's own operand, spectra, results and staging.
+static int handoff_round_format(css_ctx* h, const std::vector<RoundJob>& all, size_t round, std::vector<HandoffRec>* recs, bool commit, bool nemo) {
     HandoffCtx* c = h->handoff;
     std::vector<RoundJob> jobs;
     for (const RoundJob& j : all)
-        if (j.handoff && j.s->ho && (j.t_hi > j.s->t_g || j.closing)) jobs.push_back(j);
+        if (j.handoff && j.s->ho && j.s->ho->nemo == nemo && (j.t_hi > j.s->t_g || j.closing)) jobs.push_back(j);
     if (jobs.empty() || !c) return CSS_OK;
+    DevBuf& operand = nemo ? c->nemo_operand : c->operand;
+    DevBuf& spec = nemo ? c->nemo_spec : c->spec;
+    DevBuf& res = nemo ? c->nemo_res : c->res;
+    std::vector<PinnedBuf>& pinned = nemo ? c->nemo_pinned : c->pinned;
+    const int spec_rows = nemo ? 2 * NEMO_BINS : 402;
     const int S = h->d.num_spks, hopS = h->d.frame_hop;
     const size_t n = jobs.size();
     std::vector<HandoffAppend> ap(n);
@@ -88,7 +107,7 @@ int handoff_round(css_ctx* h, const std::vector<RoundJob>& all, size_t round, st
         a.tail_in = (const float*)o->tail[o->cur].p; a.tail_out = (float*)o->tail[1 - o->cur].p;
         a.t_g0 = t_g0; a.t_g1 = j.t_hi; a.D0 = o->D; a.D1 = D1;
         a.pad = o->pad; a.drop = o->cfg.drop_silence ? 1 : 0; a.closing = j.closing ? 1 : 0; a.S = S;
-        a.rows = handoff_rows(D1 - o->D); a.row0 = rows_total;
+        a.rows = nemo ? nemo_rows(D1 - o->D) : handoff_rows(D1 - o->D); a.row0 = rows_total;
         rows_total += a.rows * S;
         act_off[i] = res_b; res_b = al(res_b + (size_t)S * (size_t)(j.t_hi - t_g0));
         new_off[i] = res_b; res_b = al(res_b + (size_t)S * sizeof(int32_t));
@@ -98,16 +117,18 @@ int handoff_round(css_ctx* h, const std::vector<RoundJob>& all, size_t round, st
     const size_t state_b = (size_t)CSS_MAX_STREAMS * SMAX * sizeof(HandoffState);
     const int64_t ld = (rows_total + 3) / 4 * 4;
     int rc;
-    // The product reads 416 columns from every row; columns 400 .. 415 meet zeros of the matrix, so what they read only has to
-    // be finite.  The append kernel rewrites ALL rows of every owner each round, the floats behind the last row are zeros
+    // The product reads 416 columns from every row (NeMo: 512); columns 400 .. 415 meet zeros of the matrix, so what they read only
+    // has to be finite.  The append kernel rewrites ALL rows of every owner each round, the floats behind the last row are zeros
     // from the allocation or finite values an earlier, larger round left there.
-    if ((rc = ensure(h, c->operand, ((size_t)rows_total * 160 + 1024) * sizeof(float), true)) != CSS_OK) return rc;
-    if ((rc = ensure(h, c->spec, (size_t)402 * ld * sizeof(float))) != CSS_OK) return rc;
-    if ((rc = ensure(h, c->res, res_b)) != CSS_OK) return rc;
-    if (c->pinned.size() <= round) c->pinned.resize(round + 1);
-    PinnedBuf& pin = c->pinned[round];
+    if ((rc = ensure(h, operand, ((size_t)rows_total * 160 + 1024) * sizeof(float), true)) != CSS_OK) return rc;
+    if ((rc = ensure(h, spec, (size_t)spec_rows * ld * sizeof(float))) != CSS_OK) return rc;
+    if ((rc = ensure(h, res, res_b)) != CSS_OK) return rc;
+    if (pinned.size() <= round) pinned.resize(round + 1);
+    PinnedBuf& pin = pinned[round];
     if (pin.cap < res_b + state_b) HIPCHK(h, pin.alloc(res_b + state_b));
-    const float* dftm = (const float*)c->tab.p;
+    const float* dftm = (const float*)(nemo ? h->nemo_tab.p : c->tab.p);
+    std::vector<NemoAppend> nap(nemo ? n : 0);
+    std::vector<NemoMel> nme(nemo ? n : 0);
     for (size_t i = 0; i < n; ++i) {
         const RoundJob& j = jobs[i];
         HandoffStream* o = j.s->ho.get();
@@ -116,12 +137,19 @@ int handoff_round(css_ctx* h, const std::vector<RoundJob>& all, size_t round, st
         ap[i].st = (const HandoffState*)c->state.p + (size_t)id * SMAX;
         HandoffState* st = (HandoffState*)(commit ? c->state.p : c->state_pv.p) + (size_t)id * SMAX;
         ap[i].st_out = st;
-        ap[i].act_out = (uint8_t*)c->res.p + act_off[i];
-        ap[i].n_new = (int32_t*)((char*)c->res.p + new_off[i]);
-        me[i] = HandoffMel{ap[i].row0, ap[i].rows, ap[i].n_new, st, dftm + HO_DFT_F + (o->cfg.n_mels == 80 ? 0 : HO_MEL80_F), o->cfg.n_mels,
-                           (float*)((char*)c->res.p + mel_off[i]), ap[i].rows, nullptr, nullptr, 0};
-        if (commit && o->hist_frames) { me[i].ring = (float*)o->ring.p; me[i].fmax = (float*)o->fmax.p; me[i].hist = o->hist_frames; }
-        if (j.n_windows > 0 && !commit) me[i].pvmax = (float*)((char*)c->res.p + pvm_off[i]);
+        ap[i].act_out = (uint8_t*)res.p + act_off[i];
+        ap[i].n_new = (int32_t*)((char*)res.p + new_off[i]);
+        if (nemo) {
+            nap[i] = NemoAppend{ap[i], (const float*)o->xlast[o->cur].p, (float*)o->xlast[1 - o->cur].p, o->preemph, 0};
+            nme[i] = NemoMel{ap[i].row0, ap[i].rows, ap[i].n_new, nemo_bank(h, o->cfg.n_mels), (float*)((char*)res.p + mel_off[i]), ap[i].rows,
+                             o->cfg.n_mels, 0};
+            me[i].mel = nme[i].mel;
+        } else {
+            me[i] = HandoffMel{ap[i].row0, ap[i].rows, ap[i].n_new, st, dftm + HO_DFT_F + (o->cfg.n_mels == 80 ? 0 : HO_MEL80_F), o->cfg.n_mels,
+                               (float*)((char*)res.p + mel_off[i]), ap[i].rows, nullptr, nullptr, 0};
+            if (commit && o->hist_frames) { me[i].ring = (float*)o->ring.p; me[i].fmax = (float*)o->fmax.p; me[i].hist = o->hist_frames; }
+            if (j.n_windows > 0 && !commit) me[i].pvmax = (float*)((char*)res.p + pvm_off[i]);
+        }
         HandoffRec r{};
         r.s = j.s; r.item = j.item; r.t_g0 = ap[i].t_g0; r.t_g1 = ap[i].t_g1; r.D0 = ap[i].D0; r.D1 = ap[i].D1; r.n_out = j.n_out; r.closing = j.closing;
         r.act = (const uint8_t*)pin.p + act_off[i];
@@ -136,18 +164,25 @@ int handoff_round(css_ctx* h, const std::vector<RoundJob>& all, size_t round, st
             o->cur = 1 - o->cur;
         }
     }
-    launch_handoff_append_multi(ap.data(), (int)n, (float*)c->operand.p, h->stream);
+    if (nemo) launch_nemo_append_multi(nap.data(), (int)n, (float*)operand.p, h->stream);
+    else launch_handoff_append_multi(ap.data(), (int)n, (float*)operand.p, h->stream);
     GemmArgs g{};
-    g.A = dftm; g.lda = 416; g.B = (const float*)c->operand.p; g.ldb = 160; g.C = (float*)c->spec.p; g.ldc = ld;
-    g.M = 402; g.N = (int)rows_total; g.K = 416; g.batch = 1; g.alpha = 1.f;
-    launch_gemm(g, h->stream);
-    launch_handoff_mel_multi(me.data(), (int)n, S, (const float*)c->spec.p, ld, h->stream);
+    g.A = dftm; g.lda = nemo ? NEMO_NFFT : 416; g.B = (const float*)operand.p; g.ldb = 160; g.C = (float*)spec.p; g.ldc = ld;
+    g.M = spec_rows; g.N = (int)rows_total; g.K = nemo ? NEMO_NFFT : 416; g.batch = 1; g.alpha = 1.f;
+    launch_gemm(g, h->stream);   // (exact float32: a k-ordered chain per element, whatever the product's shape)
+    if (nemo) launch_nemo_mel_multi(nme.data(), (int)n, S, (const float*)spec.p, ld, h->stream);
+    else launch_handoff_mel_multi(me.data(), (int)n, S, (const float*)spec.p, ld, h->stream);
     const int tables = (int)((n + HANDOFF_MULTI_MAX - 1) / HANDOFF_MULTI_MAX);
     c->launches += 2 * tables + 1; c->products += 1; c->frames += rows_total;
-    HIPCHK(h, hipMemcpyAsync(pin.p, c->res.p, res_b, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(pin.p, res.p, res_b, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipMemcpyAsync((char*)pin.p + res_b, commit ? c->state.p : c->state_pv.p, state_b, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipGetLastError());
     return CSS_OK;
+}
+
+int handoff_round(css_ctx* h, const std::vector<RoundJob>& all, size_t round, std::vector<HandoffRec>* recs, bool commit) {
+    const int rc = handoff_round_format(h, all, round, recs, commit, false);
+    return rc != CSS_OK ? rc : handoff_round_format(h, all, round, recs, commit, true);
 }
 
 // After the call's synchronise: the rounds' results of ONE stream, in order, trimmed into `out`, on the mirrors `mir`: the
@@ -183,7 +218,7 @@ int handoff_collect(css_ctx* h, StreamState* s, int item, int64_t t_g_before, co
             for (size_t i = before; i + 1 < g.size(); i += 2) added += g[i + 1] - g[i];
             if (before) added += g[before - 1] - last_end;
             const int64_t A1 = mir.A[(size_t)k] + added;
-            const int64_t J1 = r.closing ? A1 / 160 : (A1 >= 201 ? (A1 - 200) / 160 + 1 : 0);
+            const int64_t J1 = frames_complete(o->nemo, r.closing, A1);
             const int64_t nj = J1 - mir.J[(size_t)k];
             // internal consistency, not refusals: a stream that has moved already ends here (only css_stream_close is left)
             if (nj != r.n_new[k] || r.st[k].A != A1 || r.st[k].J != J1) {
@@ -201,6 +236,7 @@ int handoff_collect(css_ctx* h, StreamState* s, int item, int64_t t_g_before, co
                             r.mel + ((size_t)k * nm + m) * r.mel_ld, (size_t)nj * sizeof(float));
             nfr[(size_t)k] += nj;
             mir.A[(size_t)k] = A1; mir.J[(size_t)k] = J1;
+            if (o->nemo) continue;   // (no running maximum: raw_max is never written)
             const int b = r.st[k].gmax;
             const int bits = b >= 0 ? b : b ^ 0x7fffffff;
             std::memcpy(&mir.raw_max[(size_t)k], &bits, sizeof(float));
@@ -218,7 +254,7 @@ int handoff_collect(css_ctx* h, StreamState* s, int item, int64_t t_g_before, co
         std::memcpy(out->ranges_host + (size_t)k * out->cap_ranges * 2, g.data(), g.size() * sizeof(int64_t));
         out->n_ranges[k] = (int32_t)(g.size() / 2);
         out->n_frames[k] = nfr[(size_t)k];
-        out->raw_max[k] = mir.raw_max[(size_t)k];
+        if (!o->nemo) out->raw_max[k] = mir.raw_max[(size_t)k];
     }
     out->n_activity = n_act;
     out->first_activity_frame = t_g_before;
@@ -324,13 +360,13 @@ int css_stream_handoff_final_frames(const CssModelDesc* desc, const CssRunCfg* c
     return CSS_OK;
 }
 
-int css_stream_handoff_open(css_handle_t h, int32_t id, const CssStreamHandoffCfg* cfg) {
-    StreamState* s = nullptr;
-    int rc = check_stream_call(h, id, &s);
-    if (rc != CSS_OK) return rc;
-    if (check_handoff_cfg(cfg) != CSS_OK) return fail(h, CSS_ERR_INVALID_ARG, "n_mels is 80 or 128, pad_frames 0 .. 4096");
+// What both formats' open calls do once the configuration is accepted: the handle's shared part on first use (the state rows; the
+// format's tables), the stream's buffers, its state rows and mirrors.  nemo: the pre-emphasis coefficient, else null.
+static int open_handoff(css_ctx* h, StreamState* s, int32_t id, const CssStreamHandoffCfg* cfg, const float* nemo) {
+    int rc;
     if (s->ho) return fail(h, CSS_ERR_STATE, "the hand-off of this stream is on already");
-    if (s->n_pushed > 0 || s->finished) return fail(h, CSS_ERR_STATE, "the hand-off is switched on before the stream's first sample");
+    if (s->n_pushed > 0 || s->finished || (nemo && s->rate && s->rate->n_in > 0))
+        return fail(h, CSS_ERR_STATE, "the hand-off is switched on before the stream's first sample");
     HIPCHK(h, hipSetDevice(h->device));
     const int S = h->d.num_spks;
     HandoffCtx* c = h->handoff;
@@ -338,13 +374,17 @@ int css_stream_handoff_open(css_handle_t h, int32_t id, const CssStreamHandoffCf
         c = new HandoffCtx();
         h->handoff = c;
     }
-    if (!c->tab.p || !c->state.p || !c->state_pv.p) {
+    if (!c->state.p || !c->state_pv.p) {
+        if ((rc = ensure(h, c->state, (size_t)CSS_MAX_STREAMS * SMAX * sizeof(HandoffState), true)) != CSS_OK) return rc;
+        if ((rc = ensure(h, c->state_pv, (size_t)CSS_MAX_STREAMS * SMAX * sizeof(HandoffState), true)) != CSS_OK) return rc;
+    }
+    if (nemo) {
+        if ((rc = nemo_ensure_tables(h)) != CSS_OK) return rc;
+    } else if (!c->tab.p) {
         std::vector<float> t(HO_DFT_F + HO_MEL80_F + HO_MEL128_F, 0.f);
         handoff_build_dft(t.data());
         handoff_build_mel(t.data() + HO_DFT_F, 80);
         handoff_build_mel(t.data() + HO_DFT_F + HO_MEL80_F, 128);
-        if ((rc = ensure(h, c->state, (size_t)CSS_MAX_STREAMS * SMAX * sizeof(HandoffState), true)) != CSS_OK) return rc;
-        if ((rc = ensure(h, c->state_pv, (size_t)CSS_MAX_STREAMS * SMAX * sizeof(HandoffState), true)) != CSS_OK) return rc;
         if ((rc = ensure(h, c->tab, t.size() * sizeof(float))) != CSS_OK) return rc;
         HIPCHK(h, hipMemcpy(c->tab.p, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));
     }
@@ -352,6 +392,9 @@ int css_stream_handoff_open(css_handle_t h, int32_t id, const CssStreamHandoffCf
     o->cfg = *cfg;
     o->cfg.drop_silence = cfg->drop_silence ? 1 : 0;
     o->pad = o->cfg.drop_silence ? cfg->pad_frames : 0;
+    o->nemo = nemo != nullptr;
+    o->preemph = nemo ? *nemo : 0.f;
+    static_assert(NEMO_TAIL_LD == HANDOFF_TAIL_LD, "one allocation size serves both tails (each kernel indexes by its own constant)");
     // the ring holds a round's frames (at most the window) and the 2 pad + 2 frames before them that can keep its blocks
     int64_t ring = 64;
     while (ring < s->WF + 2 * (int64_t)o->pad + 8) ring *= 2;
@@ -360,7 +403,8 @@ int css_stream_handoff_open(css_handle_t h, int32_t id, const CssStreamHandoffCf
     rc = ensure(h, o->gate, (size_t)S * ring, true);
     for (int b = 0; b < 2 && rc == CSS_OK; ++b) {
         rc = ensure(h, o->carry[b], (size_t)S * o->carry_ld * sizeof(float), true);
-        if (rc == CSS_OK) rc = ensure(h, o->tail[b], (size_t)S * HANDOFF_TAIL_LD * sizeof(float), true);
+        if (rc == CSS_OK) rc = ensure(h, o->tail[b], (size_t)S * (nemo ? NEMO_TAIL_LD : HANDOFF_TAIL_LD) * sizeof(float), true);
+        if (rc == CSS_OK && nemo) rc = ensure(h, o->xlast[b], (size_t)SMAX * sizeof(float), true);
     }
     std::vector<HandoffState> init((size_t)SMAX, HandoffState{0, 0, HANDOFF_GMAX_NONE, 0});
     hipError_t e = hipSuccess;
@@ -374,6 +418,54 @@ int css_stream_handoff_open(css_handle_t h, int32_t id, const CssStreamHandoffCf
     o->m.A.assign((size_t)S, 0); o->m.J.assign((size_t)S, 0);
     o->m.raw_max.assign((size_t)S, -INFINITY);
     s->ho = std::move(o);
+    return CSS_OK;
+}
+
+int css_stream_handoff_open(css_handle_t h, int32_t id, const CssStreamHandoffCfg* cfg) {
+    StreamState* s = nullptr;
+    const int rc = check_stream_call(h, id, &s);
+    if (rc != CSS_OK) return rc;
+    if (check_handoff_cfg(cfg) != CSS_OK) return fail(h, CSS_ERR_INVALID_ARG, "n_mels is 80 or 128, pad_frames 0 .. 4096");
+    return open_handoff(h, s, id, cfg, nullptr);
+}
+
+// ---- the NeMo format (include/css_mi355_stream_nemo.h) ------------------------------------------------------------------------
+static bool nemo_cfg_ok(const CssStreamNemoCfg* c, CssStreamHandoffCfg* as) {
+    if (!c || !std::isfinite(c->preemphasis) || c->preemphasis < 0.f || c->preemphasis >= 1.f) return false;
+    *as = CssStreamHandoffCfg{c->n_mels, c->pad_frames, c->drop_silence};
+    return check_handoff_cfg(as) == CSS_OK;
+}
+
+int css_stream_nemo_open(css_handle_t h, int32_t id, const CssStreamNemoCfg* cfg) {
+    StreamState* s = nullptr;
+    const int rc = check_stream_call(h, id, &s);
+    if (rc != CSS_OK) return rc;
+    CssStreamHandoffCfg as{};
+    if (!nemo_cfg_ok(cfg, &as)) return fail(h, CSS_ERR_INVALID_ARG, "n_mels is 80 or 128, pad_frames 0 .. 4096, preemphasis finite in [0, 1)");
+    if (h->split) return fail(h, CSS_ERR_STATE, "streams run in CSS_LINEAR_EXACT_F32 only");
+    return open_handoff(h, s, id, &as, &cfg->preemphasis);
+}
+
+int css_stream_nemo_bounds(const CssModelDesc* desc, const CssRunCfg* cfg, const CssStreamNemoCfg* ncfg, int64_t n_samples,
+                           int64_t* frames, int32_t* ranges, int64_t* activity) {
+    CssStreamHandoffCfg as{};
+    if (!desc || !frames || !ranges || !activity || n_samples < -1 || !nemo_cfg_ok(ncfg, &as)) return CSS_ERR_INVALID_ARG;
+    const int rc = check_stream_cfg(*desc, cfg);
+    if (rc != CSS_OK) return rc;
+    const HandoffNeed n = handoff_need(cfg->segment_frames, cfg->hop_frames, cfg->dilation_frames + cfg->erosion_frames, as, n_samples, NEMO_LEAD);
+    *frames = n.frames; *ranges = n.ranges; *activity = n.activity;
+    return CSS_OK;
+}
+
+int css_stream_nemo_final_frames(const CssModelDesc* desc, const CssRunCfg* cfg, const CssStreamNemoCfg* ncfg, int64_t n_pushed,
+                                 int64_t* n_frames) {
+    CssStreamHandoffCfg as{};
+    if (!desc || !n_frames || n_pushed < 0 || !nemo_cfg_ok(ncfg, &as)) return CSS_ERR_INVALID_ARG;
+    const int rc = check_stream_cfg(*desc, cfg);
+    if (rc != CSS_OK) return rc;
+    if (as.drop_silence) return CSS_ERR_INVALID_ARG;   // with the gate in play the count depends on the audio
+    const int64_t fin = final_frames(n_pushed, cfg->segment_frames, cfg->hop_frames, cfg->dilation_frames + cfg->erosion_frames) * desc->frame_hop;
+    *n_frames = frames_complete(true, false, fin);
     return CSS_OK;
 }
 
@@ -402,6 +494,7 @@ int css_stream_window_open(css_handle_t h, int32_t id, int32_t history_frames) {
     if (rc != CSS_OK) return rc;
     if (history_frames < 32 || history_frames > (1 << 20)) return fail(h, CSS_ERR_INVALID_ARG, "history_frames is 32 .. 2^20");
     if (!s->ho) return fail(h, CSS_ERR_STATE, "the hand-off of this stream is off (css_stream_handoff_open)");
+    if (s->ho->nemo) return fail(h, CSS_ERR_STATE, "a NeMo stream has no frame history: encoder windows are Whisper's");
     if (s->ho->hist_frames) return fail(h, CSS_ERR_STATE, "this stream has a frame history already");
     if (s->n_pushed > 0 || s->finished || (s->rate && s->rate->n_in > 0))
         return fail(h, CSS_ERR_STATE, "the frame history is switched on before the stream's first sample");

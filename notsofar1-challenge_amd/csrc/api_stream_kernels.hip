@@ -9,6 +9,7 @@
 #include "api_kernel_stage.hpp"   // (Stager, arr_ok, stage_and_upload, download_all)
 #include "stitch_common.hpp"   // (OLA_T: the gate kernel's block of frames)
 #include "../../include/css_mi355_stream_kernels.h"
+#include "../../include/css_mi355_stream_nemo.h"
 
 using namespace css;
 using namespace css::kstage;
@@ -19,6 +20,106 @@ constexpr int64_t POS_MAX = (int64_t)1 << 40;    // frame and sample positions o
 
 bool pow2(int64_t v) { return v > 0 && (v & (v - 1)) == 0; }
 bool pos_ok(int64_t v) { return v >= 0 && v <= POS_MAX; }
+static_assert(sizeof(CssStreamNemoArray) == sizeof(CssKArray), "the stager's array descriptor");
+CssKArray ka(const CssStreamNemoArray& a) { return CssKArray{a.p, a.elems}; }
+
+// Both append entries: job i is job(i); nemo(i), where the call is css_stream_nemo_append_host, its NeMo part (else null).
+template <class Job, class Nemo>
+int append_host(css_ctx* h, const char* who, Job job, Nemo nemo, bool is_nemo, int32_t n_jobs, float* operand, int64_t operand_floats) {
+    auto bad = [&](const char* what) { return fail(h, CSS_ERR_INVALID_ARG, std::string(who) + ": " + what); };
+    if (!operand) return bad("null argument");
+    if (n_jobs < 1 || n_jobs > CSS_STREAM_KERNEL_JOBS) return bad("1 .. 64 jobs");
+    static_assert(sizeof(HandoffState) == 24, "the header states the state row");
+    static_assert(NEMO_TAIL_LD == HANDOFF_TAIL_LD, "the headers state 512 floats for both tails");
+    int64_t rows_total = 0;
+    std::vector<int64_t> rows((size_t)n_jobs), row0((size_t)n_jobs);
+    for (int i = 0; i < n_jobs; ++i) {
+        const CssStreamAppendJob& j = job(i);
+        if (j.S < 1 || j.S > 4 || j.S != job(0).S) return bad("S must be 1 .. 4, the same for all jobs");
+        if (j.pad < 0 || j.pad > 4096) return bad("pad must be 0 .. 4096");
+        if (j.drop < 0 || j.drop > 1 || j.closing < 0 || j.closing > 1 || j.preview < 0 || j.preview > 1) return bad("drop, closing and preview are 0 or 1");
+        if (!pow2(j.gate_ld) || j.gate_ld > HOST_CAP) return bad("gate_ld must be a power of two");
+        if (!pos_ok(j.t_g0) || !pos_ok(j.t_g1) || j.t_g1 < j.t_g0) return bad("t_g1 < t_g0 (or a negative frame count)");
+        if (!pos_ok(j.D0) || !pos_ok(j.D1) || j.D1 < j.D0) return bad("D1 < D0 (or a negative sample count)");
+        if (j.D0 % 256) return bad("D0 must be a multiple of 256");
+        if (j.D1 - j.D0 > ((int64_t)1 << 24)) return bad("D1 - D0 above 2^24");
+        if (!pos_ok(j.out_base) || j.out_ld < 0 || j.out_ld > HOST_CAP || j.carry_ld < 0 || j.carry_ld > HOST_CAP)
+            return bad("out_base, out_ld and carry_ld must not be negative");
+        const int64_t end = std::max(j.D1, 256 * j.t_g1);
+        if (end > j.out_base && end - j.out_base > j.out_ld) return bad("out_ld does not reach the round's last sample");
+        if (std::min(j.out_base, end) - j.D0 > j.carry_ld) return bad("out_base - D0 > carry_ld");
+        if (256 * j.t_g1 - j.D1 > j.carry_ld) return bad("the undecided samples behind D1 do not fit carry_ld");
+        if (!j.closing && j.drop && j.D1 > 256 * std::max<int64_t>(j.t_g1 - j.pad, 0)) return bad("an open round decides blocks whose frames are not gated-final");
+        const int64_t look = j.drop ? std::min(j.t_g0, std::max<int64_t>(j.D0 / 256 - j.pad - 1, 0)) : j.t_g0;
+        if (j.t_g1 - look > j.gate_ld) return bad("the ring is shorter than the frames the round reads");
+        if (!arr_ok(j.gate, (int64_t)j.S * j.gate_ld) || !arr_ok(j.out, (int64_t)j.S * j.out_ld) || !arr_ok(j.carry_in, (int64_t)j.S * j.carry_ld) ||
+            !arr_ok(j.carry_out, (int64_t)j.S * j.carry_ld) || !arr_ok(j.tail_in, (int64_t)j.S * HANDOFF_TAIL_LD) ||
+            !arr_ok(j.tail_out, (int64_t)j.S * HANDOFF_TAIL_LD) || !arr_ok(j.st, j.S) || (j.preview && !arr_ok(j.st_out, j.S)) ||
+            !arr_ok(j.act_out, (int64_t)j.S * (j.t_g1 - j.t_g0)) || !arr_ok(j.n_new, j.S) || !j.st.p || !j.n_new.p || (j.preview && !j.st_out.p))
+            return bad("an array is null or shorter than its description");
+        if (j.carry_out.p && j.carry_out.p == j.carry_in.p) return bad("carry_out must be another array than carry_in");
+        if (j.tail_out.p == j.tail_in.p) return bad("tail_out must be another array than tail_in");
+        const HandoffState* st = (const HandoffState*)j.st.p;
+        for (int k = 0; k < j.S; ++k)
+            if (st[k].A < 0 || st[k].A > POS_MAX ||
+                st[k].J != (is_nemo ? (st[k].A >= 256 ? (st[k].A - 256) / 160 + 1 : 0) : (st[k].A >= 201 ? (st[k].A - 200) / 160 + 1 : 0)))
+                return bad("a state row is not a state of an open stream");
+        if (is_nemo) {
+            const CssStreamNemoAppendJob& nj = *nemo(i);
+            if (j.preview) return bad("a NeMo round is never a preview's");
+            if (!std::isfinite(nj.preemphasis) || nj.preemphasis < 0.f || nj.preemphasis >= 1.f) return bad("preemphasis must be finite, at least 0 and below 1");
+            if (!arr_ok(ka(nj.xlast_in), j.S) || !arr_ok(ka(nj.xlast_out), j.S) || !nj.xlast_in.p || !nj.xlast_out.p) return bad("an array is null or shorter than its description");
+            if (nj.xlast_in.p == nj.xlast_out.p) return bad("xlast_out must be another array than xlast_in");
+        }
+        // handoff_rows / nemo_rows (api_stream_handoff.hip)
+        rows[(size_t)i] = is_nemo ? (j.D1 - j.D0 + 256) / 160 + 2 + 4 : (j.D1 - j.D0 + 200) / 160 + 2 + 3;
+        row0[(size_t)i] = rows_total;
+        rows_total += rows[(size_t)i] * j.S;
+    }
+    if (operand_floats != rows_total * 160 + 1024) return bad("operand must hold (sum of S rows) 160 + 1024 floats");
+    Stager sg;
+    struct At { size_t gate, out, cin, cout, tin, tout, st, sto, act, nn, xin, xout; };
+    std::vector<At> at((size_t)n_jobs);
+    const size_t op_at = sg.take_raw(operand, (size_t)operand_floats * 4, true);
+    for (int i = 0; i < n_jobs; ++i) {
+        CssStreamAppendJob& j = job(i);
+        At& a = at[(size_t)i];
+        a.gate = sg.take(j.gate, 1, false); a.out = sg.take(j.out, 4, false); a.cin = sg.take(j.carry_in, 4, false);
+        a.cout = sg.take(j.carry_out, 4, true); a.tin = sg.take(j.tail_in, 4, false); a.tout = sg.take(j.tail_out, 4, true);
+        a.st = sg.take(j.st, sizeof(HandoffState), true);
+        a.sto = j.preview ? sg.take(j.st_out, sizeof(HandoffState), true) : a.st;
+        a.act = sg.take(j.act_out, 1, true); a.nn = sg.take(j.n_new, 4, true);
+        if (is_nemo) { a.xin = sg.take(ka(nemo(i)->xlast_in), 4, false); a.xout = sg.take(ka(nemo(i)->xlast_out), 4, true); }
+    }
+    char* base = nullptr;
+    int rc;
+    if ((rc = stage_and_upload(h, sg, &base)) != CSS_OK) return rc;
+    std::vector<HandoffAppend> ap((size_t)n_jobs);
+    for (int i = 0; i < n_jobs; ++i) {
+        CssStreamAppendJob& j = job(i);
+        const At& a = at[(size_t)i];
+        HandoffAppend& e = ap[(size_t)i];
+        e = HandoffAppend{};
+        e.gate = (const uint8_t*)(base + a.gate); e.gate_ld = j.gate_ld; e.gate_mask = j.gate_ld - 1;
+        e.out = (const float*)(base + a.out); e.out_ld = j.out_ld; e.out_base = j.out_base;
+        e.carry_in = (const float*)(base + a.cin); e.carry_out = (float*)(base + a.cout); e.carry_ld = j.carry_ld;
+        e.tail_in = (const float*)(base + a.tin); e.tail_out = (float*)(base + a.tout);
+        e.st = (const HandoffState*)(base + a.st); e.st_out = (HandoffState*)(base + a.sto);
+        e.t_g0 = j.t_g0; e.t_g1 = j.t_g1; e.D0 = j.D0; e.D1 = j.D1;
+        e.pad = j.pad; e.drop = j.drop; e.closing = j.closing; e.S = j.S;
+        e.row0 = j.row0 = row0[(size_t)i]; e.rows = j.rows = rows[(size_t)i];
+        e.act_out = (uint8_t*)(base + a.act); e.n_new = (int32_t*)(base + a.nn);
+    }
+    if (is_nemo) {
+        std::vector<NemoAppend> nap((size_t)n_jobs);
+        for (int i = 0; i < n_jobs; ++i)
+            nap[(size_t)i] = NemoAppend{ap[(size_t)i], (const float*)(base + at[(size_t)i].xin), (float*)(base + at[(size_t)i].xout), nemo(i)->preemphasis, 0};
+        launch_nemo_append_multi(nap.data(), n_jobs, (float*)(base + op_at), h->stream);
+    } else {
+        launch_handoff_append_multi(ap.data(), n_jobs, (float*)(base + op_at), h->stream);
+    }
+    return download_all(h, sg, base);
+}
 
 }  // namespace
 
@@ -174,80 +275,27 @@ int css_stream_ingest_host(css_handle_t h, CssStreamIngestJob* jobs, int32_t n_j
 int css_stream_append_host(css_handle_t h, CssStreamAppendJob* jobs, int32_t n_jobs, float* operand, int64_t operand_floats) {
     CSS_DRAIN(h);
     if (!h) return CSS_ERR_INVALID_ARG;
-    auto bad = [&](const char* what) { return fail(h, CSS_ERR_INVALID_ARG, std::string("css_stream_append_host: ") + what); };
-    if (!jobs || !operand) return bad("null argument");
-    if (n_jobs < 1 || n_jobs > CSS_STREAM_KERNEL_JOBS) return bad("1 .. 64 jobs");
-    static_assert(sizeof(HandoffState) == 24, "the header states the state row");
-    int64_t rows_total = 0;
-    std::vector<int64_t> rows((size_t)n_jobs), row0((size_t)n_jobs);
+    if (!jobs) return fail(h, CSS_ERR_INVALID_ARG, "css_stream_append_host: null argument");
+    return append_host(h, "css_stream_append_host", [&](int i) -> CssStreamAppendJob& { return jobs[i]; },
+                       [](int) -> const CssStreamNemoAppendJob* { return nullptr; }, false, n_jobs, operand, operand_floats);
+}
+
+int css_stream_nemo_append_host(css_handle_t h, CssStreamNemoAppendJob* jobs, int32_t n_jobs, float* operand, int64_t operand_floats) {
+    CSS_DRAIN(h);
+    if (!h) return CSS_ERR_INVALID_ARG;
+    if (!jobs) return fail(h, CSS_ERR_INVALID_ARG, "css_stream_nemo_append_host: null argument");
+    if (n_jobs < 1 || n_jobs > CSS_STREAM_KERNEL_JOBS) return fail(h, CSS_ERR_INVALID_ARG, "css_stream_nemo_append_host: 1 .. 64 jobs");
+    std::vector<CssStreamAppendJob> as((size_t)n_jobs);   // the Whisper entry's job of each: one set of checks, one staging
     for (int i = 0; i < n_jobs; ++i) {
-        const CssStreamAppendJob& j = jobs[i];
-        if (j.S < 1 || j.S > 4 || j.S != jobs[0].S) return bad("S must be 1 .. 4, the same for all jobs");
-        if (j.pad < 0 || j.pad > 4096) return bad("pad must be 0 .. 4096");
-        if (j.drop < 0 || j.drop > 1 || j.closing < 0 || j.closing > 1 || j.preview < 0 || j.preview > 1) return bad("drop, closing and preview are 0 or 1");
-        if (!pow2(j.gate_ld) || j.gate_ld > HOST_CAP) return bad("gate_ld must be a power of two");
-        if (!pos_ok(j.t_g0) || !pos_ok(j.t_g1) || j.t_g1 < j.t_g0) return bad("t_g1 < t_g0 (or a negative frame count)");
-        if (!pos_ok(j.D0) || !pos_ok(j.D1) || j.D1 < j.D0) return bad("D1 < D0 (or a negative sample count)");
-        if (j.D0 % 256) return bad("D0 must be a multiple of 256");
-        if (j.D1 - j.D0 > ((int64_t)1 << 24)) return bad("D1 - D0 above 2^24");
-        if (!pos_ok(j.out_base) || j.out_ld < 0 || j.out_ld > HOST_CAP || j.carry_ld < 0 || j.carry_ld > HOST_CAP)
-            return bad("out_base, out_ld and carry_ld must not be negative");
-        const int64_t end = std::max(j.D1, 256 * j.t_g1);
-        if (end > j.out_base && end - j.out_base > j.out_ld) return bad("out_ld does not reach the round's last sample");
-        if (std::min(j.out_base, end) - j.D0 > j.carry_ld) return bad("out_base - D0 > carry_ld");
-        if (256 * j.t_g1 - j.D1 > j.carry_ld) return bad("the undecided samples behind D1 do not fit carry_ld");
-        if (!j.closing && j.drop && j.D1 > 256 * std::max<int64_t>(j.t_g1 - j.pad, 0)) return bad("an open round decides blocks whose frames are not gated-final");
-        const int64_t look = j.drop ? std::min(j.t_g0, std::max<int64_t>(j.D0 / 256 - j.pad - 1, 0)) : j.t_g0;
-        if (j.t_g1 - look > j.gate_ld) return bad("the ring is shorter than the frames the round reads");
-        if (!arr_ok(j.gate, (int64_t)j.S * j.gate_ld) || !arr_ok(j.out, (int64_t)j.S * j.out_ld) || !arr_ok(j.carry_in, (int64_t)j.S * j.carry_ld) ||
-            !arr_ok(j.carry_out, (int64_t)j.S * j.carry_ld) || !arr_ok(j.tail_in, (int64_t)j.S * HANDOFF_TAIL_LD) ||
-            !arr_ok(j.tail_out, (int64_t)j.S * HANDOFF_TAIL_LD) || !arr_ok(j.st, j.S) || (j.preview && !arr_ok(j.st_out, j.S)) ||
-            !arr_ok(j.act_out, (int64_t)j.S * (j.t_g1 - j.t_g0)) || !arr_ok(j.n_new, j.S) || !j.st.p || !j.n_new.p || (j.preview && !j.st_out.p))
-            return bad("an array is null or shorter than its description");
-        if (j.carry_out.p && j.carry_out.p == j.carry_in.p) return bad("carry_out must be another array than carry_in");
-        if (j.tail_out.p == j.tail_in.p) return bad("tail_out must be another array than tail_in");
-        const HandoffState* st = (const HandoffState*)j.st.p;
-        for (int k = 0; k < j.S; ++k)
-            if (st[k].A < 0 || st[k].J != (st[k].A >= 201 ? (st[k].A - 200) / 160 + 1 : 0)) return bad("a state row is not a state of an open stream");
-        rows[(size_t)i] = (j.D1 - j.D0 + 200) / 160 + 2 + 3;   // handoff_rows (api_stream_handoff.hip)
-        row0[(size_t)i] = rows_total;
-        rows_total += rows[(size_t)i] * j.S;
+        const CssStreamNemoAppendJob& j = jobs[i];
+        as[(size_t)i] = CssStreamAppendJob{j.pad, j.drop, j.closing, j.S, 0, 0, j.gate_ld, j.out_ld, j.out_base, j.carry_ld, j.t_g0, j.t_g1, j.D0, j.D1,
+                                           0, 0, ka(j.gate), ka(j.out), ka(j.carry_in), ka(j.carry_out), ka(j.tail_in), ka(j.tail_out), ka(j.st),
+                                           CssKArray{nullptr, 0}, ka(j.act_out), ka(j.n_new)};
     }
-    if (operand_floats != rows_total * 160 + 1024) return bad("operand must hold (sum of S rows) 160 + 1024 floats");
-    Stager sg;
-    struct At { size_t gate, out, cin, cout, tin, tout, st, sto, act, nn; };
-    std::vector<At> at((size_t)n_jobs);
-    const size_t op_at = sg.take_raw(operand, (size_t)operand_floats * 4, true);
-    for (int i = 0; i < n_jobs; ++i) {
-        CssStreamAppendJob& j = jobs[i];
-        At& a = at[(size_t)i];
-        a.gate = sg.take(j.gate, 1, false); a.out = sg.take(j.out, 4, false); a.cin = sg.take(j.carry_in, 4, false);
-        a.cout = sg.take(j.carry_out, 4, true); a.tin = sg.take(j.tail_in, 4, false); a.tout = sg.take(j.tail_out, 4, true);
-        a.st = sg.take(j.st, sizeof(HandoffState), true);
-        a.sto = j.preview ? sg.take(j.st_out, sizeof(HandoffState), true) : a.st;
-        a.act = sg.take(j.act_out, 1, true); a.nn = sg.take(j.n_new, 4, true);
-    }
-    char* base = nullptr;
-    int rc;
-    if ((rc = stage_and_upload(h, sg, &base)) != CSS_OK) return rc;
-    std::vector<HandoffAppend> ap((size_t)n_jobs);
-    for (int i = 0; i < n_jobs; ++i) {
-        CssStreamAppendJob& j = jobs[i];
-        const At& a = at[(size_t)i];
-        HandoffAppend& e = ap[(size_t)i];
-        e = HandoffAppend{};
-        e.gate = (const uint8_t*)(base + a.gate); e.gate_ld = j.gate_ld; e.gate_mask = j.gate_ld - 1;
-        e.out = (const float*)(base + a.out); e.out_ld = j.out_ld; e.out_base = j.out_base;
-        e.carry_in = (const float*)(base + a.cin); e.carry_out = (float*)(base + a.cout); e.carry_ld = j.carry_ld;
-        e.tail_in = (const float*)(base + a.tin); e.tail_out = (float*)(base + a.tout);
-        e.st = (const HandoffState*)(base + a.st); e.st_out = (HandoffState*)(base + a.sto);
-        e.t_g0 = j.t_g0; e.t_g1 = j.t_g1; e.D0 = j.D0; e.D1 = j.D1;
-        e.pad = j.pad; e.drop = j.drop; e.closing = j.closing; e.S = j.S;
-        e.row0 = j.row0 = row0[(size_t)i]; e.rows = j.rows = rows[(size_t)i];
-        e.act_out = (uint8_t*)(base + a.act); e.n_new = (int32_t*)(base + a.nn);
-    }
-    launch_handoff_append_multi(ap.data(), n_jobs, (float*)(base + op_at), h->stream);
-    return download_all(h, sg, base);
+    const int rc = append_host(h, "css_stream_nemo_append_host", [&](int i) -> CssStreamAppendJob& { return as[(size_t)i]; },
+                               [&](int i) -> const CssStreamNemoAppendJob* { return &jobs[i]; }, true, n_jobs, operand, operand_floats);
+    for (int i = 0; i < n_jobs; ++i) { jobs[i].row0 = as[(size_t)i].row0; jobs[i].rows = as[(size_t)i].rows; }
+    return rc;
 }
 
 int css_stream_mel_host(css_handle_t h, int32_t S, const float* spec, int64_t spec_elems, int64_t ld, CssStreamMelJob* jobs, int32_t n_jobs) {
@@ -307,6 +355,44 @@ int css_stream_mel_host(css_handle_t h, int32_t S, const float* spec, int64_t sp
         if (j.has_pvmax) e.pvmax = (float*)(base + a.pv);
     }
     launch_handoff_mel_multi(me.data(), n_jobs, S, (const float*)(base + spec_at), ld, h->stream);
+    return download_all(h, sg, base);
+}
+
+int css_stream_nemo_mel_host(css_handle_t h, int32_t S, const float* spec, int64_t spec_elems, int64_t ld, CssStreamNemoMelJob* jobs,
+                             int32_t n_jobs) {
+    CSS_DRAIN(h);
+    if (!h) return CSS_ERR_INVALID_ARG;
+    auto bad = [&](const char* what) { return fail(h, CSS_ERR_INVALID_ARG, std::string("css_stream_nemo_mel_host: ") + what); };
+    if (!jobs || !spec) return bad("null argument");
+    if (n_jobs < 1 || n_jobs > CSS_STREAM_KERNEL_JOBS) return bad("1 .. 64 jobs");
+    if (S < 1 || S > 4) return bad("S must be 1 .. 4");
+    constexpr int64_t SPEC_ROWS = 2 * NEMO_BINS;
+    if (ld < 1 || ld > HOST_CAP / SPEC_ROWS || spec_elems < SPEC_ROWS * ld || spec_elems > HOST_CAP) return bad("spec is shorter than [514][ld]");
+    for (int i = 0; i < n_jobs; ++i) {
+        const CssStreamNemoMelJob& j = jobs[i];
+        if (j.n_mels != 80 && j.n_mels != 128) return bad("n_mels must be 80 or 128");
+        if (j.row0 < 0 || j.rows < 1 || j.rows > (1 << 20) || j.row0 + (int64_t)S * j.rows > ld) return bad("row0 + S rows must lie in [0, ld]");
+        if (j.mel_ld < j.rows || j.mel_ld > HOST_CAP) return bad("mel_ld must cover rows");
+        if (!arr_ok(ka(j.n_new), S) || !arr_ok(ka(j.mel), (int64_t)S * j.n_mels * j.mel_ld) || !j.n_new.p || !j.mel.p) return bad("an array is null or shorter than its description");
+        for (int k = 0; k < S; ++k)
+            if (((const int32_t*)j.n_new.p)[k] < 0) return bad("n_new must not be negative");
+    }
+    int rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    if ((rc = nemo_ensure_tables(h)) != CSS_OK) return rc;
+    Stager sg;
+    const size_t spec_at = sg.take_raw((void*)spec, (size_t)spec_elems * 4, false);
+    std::vector<size_t> nn_at((size_t)n_jobs), mel_at((size_t)n_jobs);
+    for (int i = 0; i < n_jobs; ++i) { nn_at[(size_t)i] = sg.take(ka(jobs[i].n_new), 4, false); mel_at[(size_t)i] = sg.take(ka(jobs[i].mel), 4, true); }
+    char* base = nullptr;
+    if ((rc = stage_and_upload(h, sg, &base)) != CSS_OK) return rc;
+    std::vector<NemoMel> me((size_t)n_jobs);
+    for (int i = 0; i < n_jobs; ++i) {
+        const CssStreamNemoMelJob& j = jobs[i];
+        me[(size_t)i] = NemoMel{j.row0, j.rows, (const int32_t*)(base + nn_at[(size_t)i]), nemo_bank(h, j.n_mels), (float*)(base + mel_at[(size_t)i]), j.mel_ld,
+                                j.n_mels, 0};
+    }
+    launch_nemo_mel_multi(me.data(), n_jobs, S, (const float*)(base + spec_at), ld, h->stream);
     return download_all(h, sg, base);
 }
 

@@ -348,6 +348,29 @@ void launch_nemo_mel(const NemoFeatures& e, const float* spec, int64_t ld, hipSt
 void launch_nemo_stats(const NemoFeatures& e, hipStream_t s);                                // one block per (band, speaker)
 void launch_nemo_norm(const NemoFeatures& e, hipStream_t s);
 
+// The NeMo hand-off of STREAMED sessions (include/css_mi355_stream_nemo.h, api_stream_handoff.hip; DESIGN.md 7b "The NeMo hand-off
+// of a stream"): the Whisper stream hand-off's round -- append, ONE product, mel -- with NeMo's operand.  The append entry is the
+// Whisper one (same gate ring, decided samples, carry, counts, gate bytes) with three differences: the samples are pre-emphasised
+// while they are compacted (the predecessor of a sample is the kept sample before it, across seams and across rounds: x_last is
+// carried per speaker), the tail is y[160 J - 256, A) at its own leading dimension, and what lies outside [0, A) is zero instead
+// of a reflection.  Operand column x of a speaker's rows is y[160 J0 - 256 + x]; frame j is complete once A >= 160 j + 256, so
+// every emitted row is the offline gather's row (nemo_gather_kernel), float for float.  a.st_out[k].gmax is left alone.
+constexpr int NEMO_TAIL_LD = 512;                       // floats per speaker of the tail (A - (160 J - 256) < 512 are used)
+struct NemoAppend {
+    HandoffAppend a;                                    // tail_in / tail_out: [S][NEMO_TAIL_LD]
+    const float* xlast_in; float* xlast_out;            // [S]: the last kept sample x[A - 1] before / after the round (unread while A == 0)
+    float preemph; int32_t pad_;
+};
+struct NemoMel {
+    int64_t row0, rows;                                 // the entry's columns of the spectra (NemoAppend::a.row0, rows)
+    const int32_t* n_new;                               // [S]: frames the append completed
+    const float* w;                                     // the bank [n_mels][257]
+    float* mel; int64_t mel_ld;                         // out [S][n_mels][mel_ld]: ln(mel + 2^-24)
+    int32_t n_mels, pad_;
+};
+void launch_nemo_append_multi(const NemoAppend* e, int n, float* operand, hipStream_t s);   // tables of HANDOFF_MULTI_MAX
+void launch_nemo_mel_multi(const NemoMel* e, int n, int S, const float* spec, int64_t ld, hipStream_t s);
+
 // ------------------------------------------------------------------------------------------------
 // loss.hip -- validation loss of the training loop (train.py:411 _calc_loss): S x S base-loss sums + the noise term
 // ------------------------------------------------------------------------------------------------

@@ -18,6 +18,14 @@ view ``planes.T`` of C mono recordings -- moves it to the device as int16 and sc
 call -- raw Whisper log-mel frames, the kept sample ranges and the gate bits per separated stream (``Handoff``).  All calls'
 frames of a finished stream, through ``whisper_normalize``, are ``Handle.handoff_logmel`` of the whole recording, bit for bit.
 
+``CssStream(..., nemo=dict(n_mels=80, pad_frames=8, drop_silence=True, preemphasis=0.97))`` switches the NeMo hand-off on instead
+(css_stream_nemo_open, include/css_mi355_stream_nemo.h): after every ``push`` / ``push_pcm16`` / ``finish`` / grouped push,
+``stream.nemo`` holds what became final in that call -- the raw NeMo frames ``ln(mel + 2^-24)`` that became complete (frame j once
+160 j + 256 kept samples are appended; ``finish`` emits the rest), the kept ranges and the gate bits by the Whisper hand-off's
+rules (``Handoff``; ``raw_max`` is None).  All calls' frames of a finished stream are
+``Handle.handoff_nemo_all(..., normalize=False).mel[k]`` of the whole recording, bit for bit.  A stream has one format:
+``nemo=`` with ``handoff=`` or ``window_history=`` raises ValueError.
+
 ``CssStream(..., input_rate=48000)`` takes its pushes at the capture rate (css_stream_set_rate): ``push`` and ``push_pcm16`` move the
 samples to the device as they were captured and the rate conversion to the model's ``fs`` -- ``scipy.signal.resample_poly``'s
 default filter, in float32 -- is part of the ingest kernel.  A finished stream returned ``css_run`` of
@@ -239,7 +247,10 @@ class CssStream:
 
     def __init__(self, separator: HipSeparator, cfg: Optional[CssCfg] = None, fs: int = 16000, num_channels: Optional[int] = None,
                  handoff: Optional[Mapping[str, object]] = None, input_rate: Optional[int] = None,
-                 window_history: Optional[int] = None, output: Optional[Mapping[str, object]] = None):
+                 window_history: Optional[int] = None, output: Optional[Mapping[str, object]] = None,
+                 nemo: Optional[Mapping[str, object]] = None):
+        if nemo is not None and (handoff is not None or window_history is not None):
+            raise ValueError("nemo= is a hand-off format of its own: not together with handoff= or window_history=")
         self.separator = separator
         self.cfg = cfg if cfg is not None else CssCfg()
         desc = separator.desc
@@ -290,10 +301,17 @@ class CssStream:
         self._pv = None
         self.preview_first_sample = 0
         self._hcfg = None
-        if handoff is not None:
-            self._hcfg = _lib.handoff_cfg(**dict(handoff))
+        self.nemo: Optional[Handoff] = None
+        self._ncfg = None
+        if handoff is not None or nemo is not None:
             try:
-                _lib.check(self._h.h, self._h.lib.css_stream_handoff_open(self._h.h, self.id, C.byref(self._hcfg)))
+                if nemo is not None:
+                    self._ncfg = _lib.stream_nemo_cfg(**dict(nemo))
+                    self._hcfg = _lib.handoff_cfg(self._ncfg.n_mels, self._ncfg.pad_frames, self._ncfg.drop_silence)
+                    _lib.check(self._h.h, self._h.lib.css_stream_nemo_open(self._h.h, self.id, C.byref(self._ncfg)))
+                else:
+                    self._hcfg = _lib.handoff_cfg(**dict(handoff))
+                    _lib.check(self._h.h, self._h.lib.css_stream_handoff_open(self._h.h, self.id, C.byref(self._hcfg)))
             except Exception:
                 self.close()
                 raise
@@ -301,6 +319,7 @@ class CssStream:
             self._ho_caps = (0, 0, 0)
             S = self.num_spks
             self._ho_n = (np.zeros(S, np.int64), np.zeros(S, np.int32), np.zeros(S, np.float32))
+            self._nemo_frames = np.zeros(S, np.int64)   # (frames returned so far: Handoff.first_frame of the next call)
         self.window_history = None
         self.window_max = None
         self.present_span = None
@@ -325,10 +344,24 @@ class CssStream:
     def handoff_bounds(self, n_samples: int):
         """(frames, ranges, gate frames) the next push of ``n_samples`` (-1: finish) needs room for"""
         n = self._model_new(n_samples) if n_samples >= 0 else n_samples
+        if self._ncfg is not None:
+            return _lib.stream_nemo_bounds(self.separator.desc, self._run_cfg, self._ncfg, n)
         return _lib.stream_handoff_bounds(self.separator.desc, self._run_cfg, self._hcfg, n)
 
     def handoff_final_frames(self, n_pushed: int) -> int:
         return _lib.stream_handoff_final_frames(self.separator.desc, self._run_cfg, self._hcfg, self._model_samples(n_pushed))
+
+    def nemo_bounds(self, n_samples: int):
+        """(frames, ranges, gate frames) the next push of ``n_samples`` (-1: finish) of a stream opened with ``nemo=`` needs room for"""
+        if self._ncfg is None:
+            raise ValueError("nemo_bounds() needs a stream opened with nemo=")
+        return self.handoff_bounds(n_samples)
+
+    def nemo_final_frames(self, n_pushed: int) -> int:
+        """NeMo frames that are final after ``n_pushed`` pushed samples (``drop_silence=False`` only)"""
+        if self._ncfg is None:
+            raise ValueError("nemo_final_frames() needs a stream opened with nemo=")
+        return _lib.stream_nemo_final_frames(self.separator.desc, self._run_cfg, self._ncfg, self._model_samples(n_pushed))
 
     def _handoff_bind(self, n_samples: int):
         """binds buffers that suffice for a call with ``n_samples`` (kept while they are large enough)"""
@@ -355,8 +388,15 @@ class CssStream:
         nf, nr, mx = self._ho_n
         na = int(self._ho.n_activity)
         S = range(self.num_spks)
-        self.handoff = Handoff([self._ho_mel[k, :, :nf[k]].copy() for k in S], [self._ho_ranges[k, :nr[k]].copy() for k in S],
-                               [self._ho_act[k, :na].copy() for k in S], mx.copy(), int(self._ho.first_activity_frame))
+        got = Handoff([self._ho_mel[k, :, :nf[k]].copy() for k in S], [self._ho_ranges[k, :nr[k]].copy() for k in S],
+                      [self._ho_act[k, :na].copy() for k in S], mx.copy(), int(self._ho.first_activity_frame))
+        if self._ncfg is None:
+            self.handoff = got
+            return
+        # (a NeMo stream: no running maximum; mel[k] starts at frame first_frame[k] of k's concatenation)
+        got.raw_max, got.first_frame = None, self._nemo_frames.copy()
+        self._nemo_frames += nf
+        self.nemo = got
 
     def info(self) -> _lib.CssStreamInfo:
         inf = _lib.CssStreamInfo()
@@ -509,7 +549,7 @@ class CssStream:
         what ``css_run`` of the prefix raises (with the default windows: the reference's assert until more than one segment
         was pushed).  ``handoff=True`` (css_stream_preview_handoff; a stream opened with ``handoff=``, else ValueError) also
         sets ``preview_handoff`` to the hand-off outputs ``finish`` would return now; ``handoff`` stays the last push's."""
-        if handoff and self._hcfg is None:
+        if handoff and (self._hcfg is None or self._ncfg is not None):
             raise ValueError("preview(handoff=True) needs a stream opened with handoff=")
         out = np.empty((self.num_spks, max(self.latency_samples, 1)), np.float32)
         n_out, first = C.c_int64(0), C.c_int64(0)
@@ -661,7 +701,7 @@ class CssStreamGroup:
             outs.append(out)
             p = it.p if handoff else it
             p.id, p.out_host, p.cap = s.id, out.ctypes.data, out.shape[1]
-            if handoff and s._hcfg is not None:
+            if handoff and s._hcfg is not None and s._ncfg is None:
                 ho, first_frame = s._preview_handoff_out()
                 it.ho, it.first_frame = C.pointer(ho), first_frame.ctypes.data
         stats = _lib.CssStreamGroupStats()
@@ -676,7 +716,7 @@ class CssStreamGroup:
             if p.status == _lib.CSS_OK:
                 s.preview_first_sample = int(p.first_sample)
                 got[id(s)] = [out[k, :p.n_out].copy() for k in range(s.num_spks)]
-                if handoff and s._hcfg is not None:
+                if handoff and s._hcfg is not None and s._ncfg is None:
                     s._preview_handoff_take()
         return [got.get(id(s)) for s in self.streams]
 

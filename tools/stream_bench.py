@@ -53,6 +53,11 @@ device; (F) the same push on streams without an output format, followed by what 
 gets: scipy.signal.resample_poly to HZ2 and, with --out-pcm16, the rounding to int16, per separated stream.  Arm O is compared
 with the definition (css_resample_host of css_run's waveforms, _lib.pcm16_encode), arm F's float32 samples with css_run; the
 bytes that cross PCIe per tick are counted for both (profiles/r20_stream_output.json).
+
+With --nemo (with --streams) four arms run, each in a fresh process of its own and alternated: the plain grouped tick, the same
+with the Whisper hand-off, with the NeMo hand-off (CssStream(nemo=...), include/css_mi355_stream_nemo.h), and the host's route --
+the plain tick, then stream.nemo_features of every returned piece on the CPU.  --parent-library PATH adds the plain and the
+Whisper arm on an earlier build of the library, between this one's (profiles/r27_stream_nemo.json).
 """
 import argparse
 import json
@@ -342,6 +347,130 @@ def group_bench(n_streams, out_path, seconds=60.0, round_s=1.5, block=5, passes=
     print(text)
 
 
+NEMO = dict(n_mels=80, pad_frames=8, drop_silence=True, preemphasis=0.97)
+NEMO_ARMS = {"plain": "one css_stream_push_many per tick, no hand-off",
+             "whisper": "the same, every stream with the Whisper hand-off (80 bands, pad 8, drop silence)",
+             "nemo": "the same, every stream with the NeMo hand-off (80 bands, pad 8, drop silence, p = 0.97)",
+             "host": "the plain tick, then the raw NeMo features of every returned piece on the CPU (numpy float32 on BLAS: host_nemo_features)"}
+
+
+def host_nemo_features(tables, x, p):
+    """what a host computes per returned piece: stream.nemo_features(x, normalize=False)'s arithmetic with the frames laid out
+    contiguously, so that both products run on BLAS (the package's own statement multiplies a strided view)"""
+    A, Wm = tables
+    L = len(x) // 160
+    if L == 0:
+        return np.zeros((Wm.shape[0], 0), np.float32)
+    y = x.copy()
+    if p:
+        y[1:] = x[1:] - np.float32(p) * x[:-1]
+    padded = np.concatenate([np.zeros(256, np.float32), y, np.zeros(256, np.float32)])
+    frames = np.ascontiguousarray(np.lib.stride_tricks.sliding_window_view(padded, 512)[::160][:L].T)
+    spec = A @ frames
+    power = spec[:257] * spec[:257] + spec[257:] * spec[257:]
+    return np.log(Wm @ power + np.float32(2.0 ** -24))
+
+
+def nemo_arm(arm, n_streams, seconds=60.0, round_s=1.5, passes=2):
+    """One arm of --nemo in this process (the library is CSS_MI355_LIBRARY's, or the tree's): a warm-up pass, then `passes` timed
+    passes of grouped ticks over `n_streams` meetings; prints one JSON line {"arm", "tick_ms": [...], "bit_identical", ...}."""
+    import notsofar1_challenge_amd._lib as LIB
+    if os.environ.get("CSS_MI355_LIBRARY"):
+        LIB.STREAM_NEMO_ABI.clear()   # (an earlier build of the library: it has no NeMo stream entries, and no arm on it asks for one)
+    import notsofar1_challenge_amd.css as CSS
+    import notsofar1_challenge_amd.separator as SEP
+    import notsofar1_challenge_amd.stream as STR
+    import notsofar1_challenge_amd.synth as SYN
+    import notsofar1_challenge_amd.weights as W
+    desc = W.ModelDesc.mc_v1()
+    sep = SEP.HipSeparator(W.apply_golden_recipe(W.portable_state_dict(desc, 0)), None, device=0, max_batch_segments=256)
+    cfg = CSS.CssCfg()
+    rc = CSS.make_run_cfg(cfg, FS, 7)
+    recs = [np.ascontiguousarray(SYN.synth_meeting(seconds, 7, seed=1000 + i)[0]) for i in range(n_streams)]
+    sep.handle.run(recs[0][:FS * 10], rc)   # warm-up
+    refs = [sep.handle.run(x, rc).copy() for x in recs]
+    step = int(round_s * FS)
+    tables = STR.nemo_tables(NEMO["n_mels"])
+    ms, same, frames = [], True, []
+    for p in range(passes + 1):
+        kw = dict(handoff=HANDOFF) if arm == "whisper" else dict(nemo=NEMO) if arm == "nemo" else {}
+        streams = [STR.CssStream(sep, cfg, **kw) for _ in recs]
+        group = STR.CssStreamGroup(streams)
+        em = [0] * n_streams
+        for r in range((recs[0].shape[0] + step - 1) // step):
+            chunks = [x[r * step:(r + 1) * step] for x in recs]
+            t = time.perf_counter()
+            res = group.push(chunks)
+            if arm == "host":
+                feats = [host_nemo_features(tables, w, NEMO["preemphasis"]) for got in res for w in got]
+            dt = time.perf_counter() - t
+            if p > 0:
+                ms.append(dt * 1e3)
+                if arm == "host":
+                    frames.append(sum(f.shape[1] for f in feats))
+                elif arm != "plain":
+                    frames.append(sum(m.shape[1] for s in streams for m in (s.nemo if arm == "nemo" else s.handoff).mel))
+            for i, got in enumerate(res):
+                got = np.stack(got)
+                same = same and bool(np.array_equal(got, refs[i][:, em[i]:em[i] + got.shape[1]]))
+                em[i] += got.shape[1]
+        for i, s in enumerate(streams):
+            got = np.stack(s.finish())
+            same = same and bool(np.array_equal(got, refs[i][:, em[i]:])) and em[i] + got.shape[1] == refs[i].shape[1]
+            s.close()
+    stats = list(sep.handle.stream_handoff_stats())
+    sep.close()
+    print("NEMO_ARM " + json.dumps({"arm": arm, "library": os.environ.get("CSS_MI355_LIBRARY") or "this", "tick_ms": [round(v, 4) for v in ms],
+                                    "bit_identical": same, "frames_per_tick_median": float(np.median(frames)) if frames else 0.0,
+                                    "launches_products_frames_last_call": stats}))
+
+
+def nemo_bench(n_streams, out_path, parent_library, repeats=3, passes=2):
+    """--nemo: every arm in a fresh process of its own, one after the other and alternated -- the parent commit's library (plain,
+    Whisper) between this commit's arms -- `repeats` times; per arm the tick's p50 of every repeat, their median [min, max]."""
+    import subprocess
+    order = [("plain", True), ("plain", False), ("whisper", True), ("whisper", False), ("nemo", False), ("host", False)]
+    if not parent_library:
+        order = [o for o in order if not o[1]]
+    got = {}
+    for rep in range(repeats):
+        for arm, parent in (order if rep % 2 == 0 else order[::-1]):
+            env = dict(os.environ)
+            env.pop("CSS_MI355_LIBRARY", None)
+            if parent:
+                env["CSS_MI355_LIBRARY"] = os.path.abspath(parent_library)
+            out = subprocess.run([sys.executable, os.path.abspath(__file__), "--nemo-arm", arm, "--streams", str(n_streams), "--passes", str(passes)],
+                                 env=env, capture_output=True, text=True, timeout=900)
+            if out.returncode != 0:   # (a child that failed ends the measurement: nothing more is started on the GPU)
+                sys.stderr.write(out.stdout[-2000:] + out.stderr[-4000:])
+                raise SystemExit(f"arm {arm} ({'parent' if parent else 'this'}) ended with {out.returncode}")
+            line = [l for l in out.stdout.splitlines() if l.startswith("NEMO_ARM ")][-1]
+            got.setdefault(("parent " if parent else "this ") + arm, []).append(json.loads(line[len("NEMO_ARM "):]))
+    res = {"what": "tools/stream_bench.py --nemo --streams %d: 60 s meetings, mc_v1 (18 blocks, exact float32), 1.5 s grouped ticks, every arm in a "
+                   "process of its own, arms alternated in one job, %d repeats of %d timed passes" % (n_streams, repeats, passes),
+           "hand-offs": {"whisper": HANDOFF, "nemo": NEMO}, "arms": {}}
+    for name, runs in got.items():
+        p50 = [float(np.percentile(np.array(r["tick_ms"]), 50)) for r in runs]
+        res["arms"][name] = {"what": NEMO_ARMS[name.split()[1]], "tick_ms_p50_per_repeat": [round(v, 3) for v in p50],
+                             "tick_ms_median": round(float(np.median(p50)), 3), "tick_ms_min": round(min(p50), 3), "tick_ms_max": round(max(p50), 3),
+                             "ticks_per_repeat": len(runs[0]["tick_ms"]), "bit_identical": all(r["bit_identical"] for r in runs),
+                             "frames_per_tick_median": runs[0]["frames_per_tick_median"],
+                             "launches_products_frames_last_call": runs[0]["launches_products_frames_last_call"]}
+    a = res["arms"]
+    med = lambda k: a[k]["tick_ms_median"]
+    res["extra_over_plain_ms"] = {k: round(med("this " + k) - med("this plain"), 3) for k in ("whisper", "nemo", "host")}
+    if parent_library:
+        for k in ("plain", "whisper"):
+            pr = a["parent " + k]
+            res["this_minus_parent_" + k + "_ms"] = round(med("this " + k) - med("parent " + k), 3)
+            res["parent_" + k + "_spread_ms"] = round(pr["tick_ms_max"] - pr["tick_ms_min"], 3)
+    text = json.dumps(res, indent=1)
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write(text + "\n")
+    print(text)
+
+
 def output_bench(n_streams, out_path, rate, out_rate, out_pcm16, pinned=False, seconds=60.0, round_s=1.5, block=5, passes=2):
     from scipy.signal import resample_poly
     import notsofar1_challenge_amd._lib as LIB
@@ -487,8 +616,16 @@ def main():
                     "plain streams + scipy.signal.resample_poly on the host")
     ap.add_argument("--out-pcm16", action="store_true", help="with --out-rate: the output is int16 (the host's route converts too)")
     ap.add_argument("--passes", type=int, default=2, help="with --streams: timed passes over the recordings")
+    ap.add_argument("--nemo", action="store_true", help="with --streams: plain, Whisper hand-off, NeMo hand-off and the host's route, each arm in a process "
+                    "of its own, alternated (profiles/r27_stream_nemo.json)")
+    ap.add_argument("--parent-library", default=None, help="with --nemo: an earlier build of the library; its plain and Whisper arms run between this one's")
+    ap.add_argument("--nemo-arm", default=None, choices=sorted(NEMO_ARMS), help="one arm of --nemo in this process (what --nemo starts)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.streams and a.nemo_arm:
+        return nemo_arm(a.nemo_arm, a.streams, passes=a.passes)
+    if a.streams and a.nemo:
+        return nemo_bench(a.streams, a.out, a.parent_library, passes=a.passes)
     if a.streams and a.out_rate:
         return output_bench(a.streams, a.out, a.rate or FS, a.out_rate, a.out_pcm16, pinned=a.pinned, passes=a.passes)
     if a.streams:
