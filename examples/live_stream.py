@@ -43,8 +43,14 @@ returns, per room and speaker, the raw NeMo frames ln(mel + 2^-24) that became c
 streaming FastConformer, a streaming diarizer or a frame-level VAD on the same GPU takes (they normalise per short window
 themselves, or not at all).  A stream has one format: --nemo does not go with --logmel, --window or --present; a plain --preview does.
 
-    python examples/live_stream.py [--seconds 30] [--rooms N] [--logmel | --nemo] [--pcm16] [--rate HZ] [--preview] [--window]
-                                   [--present] [--out-rate HZ] [--out-pcm16]
+With --nemo --chunks the streams also keep their last 1024 NeMo frames on the device (CssStream(nemo_history=1024),
+include/css_mi355_nemo_chunk.h) and after every tick ONE call writes, per room and speaker, two chunks into torch tensors on the
+GPU: the raw [80, 70 + 14] frames a cache-aware streaming FastConformer step takes (pre-encode cache + chunk) and a 4 s buffer
+normalised per feature over the buffer, float16 -- what FrameBatchASR, a streaming diarizer or a frame-level VAD takes -- without
+the frames crossing PCIe again (CssStream.nemo_chunk / CssStreamGroup.nemo_chunks).
+
+    python examples/live_stream.py [--seconds 30] [--rooms N] [--logmel | --nemo [--chunks]] [--pcm16] [--rate HZ] [--preview]
+                                   [--window] [--present] [--out-rate HZ] [--out-pcm16]
 """
 import argparse
 import os
@@ -143,8 +149,27 @@ def present_windows(group, streams, batch):
     return out, live
 
 
+def nemo_chunks(group, streams, step, buffered):
+    """one css_stream_nemo_chunks per kind for every (room, speaker) that holds enough frames: the raw step input [B, 80, 84] of a
+    cache-aware encoder into `step`, and the last 4 s normalised per feature over the buffer, float16 [B, 80, 400], into `buffered`"""
+    for what, width, normalize, batch in (("raw step inputs", step.shape[2], None, step), ("per-feature buffers", buffered.shape[2], "per_feature", buffered)):
+        reqs = [(s, k, None, width) for s in streams for k in range(s.num_spks) if s.nemo_history_range()[1][k] >= width]
+        if not reqs:
+            print(f"    no {what} yet")
+            continue
+        t = time.perf_counter()
+        out = group.nemo_chunks(reqs, width, normalize, str(batch.dtype).split(".")[1], out=batch[:len(reqs)])
+        ms = (time.perf_counter() - t) * 1e3
+        print(f"    {len(reqs)} {what} {tuple(out.shape)} {out.dtype} on {out.device} in {ms:5.2f} ms, {group.window_launches} launch(es)")
+
+
+def chunk_batches(n, n_mels):
+    import torch
+    return (torch.empty((n, n_mels, 70 + 14), dtype=torch.float32, device="cuda"), torch.empty((n, n_mels, 400), dtype=torch.float16, device="cuda"))
+
+
 def rooms(sep, n_rooms, seconds, fs, chunk, logmel=False, pcm16=False, rate=None, preview=False, window=False, present=False, output=None,
-          nemo=False):
+          nemo=False, chunks=False):
     mixes = [SYN.synth_meeting(seconds, 7, seed=1 + r)[0] for r in range(n_rooms)]
     if rate:
         mixes = [capture_at(m, fs, rate) for m in mixes]
@@ -152,8 +177,11 @@ def rooms(sep, n_rooms, seconds, fs, chunk, logmel=False, pcm16=False, rate=None
     elif pcm16:
         mixes = [capture(m) for m in mixes]
     streams = [STR.CssStream(sep, CSS.CssCfg(), fs=fs, num_channels=7, handoff=HANDOFF if logmel else None, input_rate=rate,
-                             window_history=3000 if window else None, output=output, nemo=NEMO if nemo else None) for _ in mixes]
+                             window_history=3000 if window else None, output=output, nemo=NEMO if nemo else None,
+                             nemo_history=1024 if chunks else None) for _ in mixes]
     group = STR.CssStreamGroup(streams)
+    if chunks:
+        step, buffered = chunk_batches(n_rooms * sep.desc.num_spks, NEMO["n_mels"])
     if window:
         import torch
         batch = torch.empty((n_rooms * sep.desc.num_spks, HANDOFF["n_mels"], 3000), dtype=torch.float16, device="cuda")
@@ -173,6 +201,8 @@ def rooms(sep, n_rooms, seconds, fs, chunk, logmel=False, pcm16=False, rate=None
             print_handoff(streams, fs)
         if nemo:
             print_nemo(streams, fs)   # -> the streaming encoder's next chunk: torch.from_numpy(s.nemo.mel[k])[None]
+        if chunks:
+            nemo_chunks(group, streams, step, buffered)   # -> encoder.cache_aware_stream_step(step[:B]) / asr(buffered[:B]) on the same GPU
         if preview:
             t = time.perf_counter()
             pv = group.preview(handoff=logmel)
@@ -200,6 +230,7 @@ def main():
     ap.add_argument("--rooms", type=int, default=1, help="meetings fed tick by tick through one CssStreamGroup")
     ap.add_argument("--logmel", action="store_true", help="also return Whisper log-mel frames and kept ranges with every tick")
     ap.add_argument("--nemo", action="store_true", help="also return raw NeMo log-mel frames and kept ranges with every tick (not with --logmel)")
+    ap.add_argument("--chunks", action="store_true", help="with --nemo: after each tick, a NeMo consumer's chunks per room and speaker in torch tensors on the GPU")
     ap.add_argument("--pcm16", action="store_true", help="the source delivers int16 samples: push_pcm16 instead of push")
     ap.add_argument("--preview", action="store_true", help="after each tick's push, also fetch the provisional tail (preview)")
     ap.add_argument("--rate", type=int, default=0, help="the source delivers int16 samples at this rate: CssStream(input_rate=HZ)")
@@ -213,12 +244,14 @@ def main():
     a.logmel = a.logmel or a.window
     if a.nemo and a.logmel:
         ap.error("--nemo is a hand-off format of its own: not with --logmel, --window or --present")
+    if a.chunks and not a.nemo:
+        ap.error("--chunks are a NeMo consumer's: with --nemo")
     a.pcm16 = a.pcm16 or bool(a.rate)
     output = dict(rate=a.out_rate or fs, dtype="int16" if a.out_pcm16 else "float32") if a.out_rate or a.out_pcm16 else None
     desc = W.ModelDesc.mc_v1()
     sep = SEP.HipSeparator(W.apply_golden_recipe(W.portable_state_dict(desc, 0)), None, device=0)
     if a.rooms > 1:
-        rooms(sep, a.rooms, a.seconds, fs, fs // 2, a.logmel, a.pcm16, a.rate or None, a.preview, a.window, a.present, output, a.nemo)
+        rooms(sep, a.rooms, a.seconds, fs, fs // 2, a.logmel, a.pcm16, a.rate or None, a.preview, a.window, a.present, output, a.nemo, a.chunks)
         sep.close()
         return
     mix = SYN.synth_meeting(a.seconds, 7, seed=1)[0]
@@ -230,7 +263,10 @@ def main():
     streams = [[] for _ in range(desc.num_spks)]
     mels = [[] for _ in range(desc.num_spks)]
     with STR.CssStream(sep, CSS.CssCfg(), fs=fs, num_channels=7, handoff=HANDOFF if a.logmel else None, input_rate=a.rate or None,
-                       window_history=3000 if a.window else None, output=output, nemo=NEMO if a.nemo else None) as s:
+                       window_history=3000 if a.window else None, output=output, nemo=NEMO if a.nemo else None,
+                       nemo_history=1024 if a.chunks else None) as s:
+        if a.chunks:
+            step, buffered = chunk_batches(desc.num_spks, NEMO["n_mels"])
         if a.window:
             import torch
             batch = torch.empty((desc.num_spks, HANDOFF["n_mels"], 3000), dtype=torch.float16, device="cuda")
@@ -252,6 +288,8 @@ def main():
                 print_nemo([s], fs)
                 for k, m in enumerate(s.nemo.mel):
                     mels[k].append(m)
+            if a.chunks:
+                nemo_chunks(STR.CssStreamGroup([s]), [s], step, buffered)
             if a.preview:
                 try:
                     count = s.preview(handoff=a.logmel)[0].shape[0]

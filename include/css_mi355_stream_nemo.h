@@ -29,8 +29,9 @@
  * three launches for all its NeMo streams (append, ONE product, mel; tables of 16 streams), besides Whisper's three where the
  * round has Whisper streams; css_stream_handoff_stats counts both.
  * Refused with CSS_ERR_STATE and a message, for a NeMo stream: a preview with hand-off (css_mi355_preview_handoff.h; a plain
- * preview, css_mi355_preview.h, works and leaves the NeMo state untouched), a frame history (css_mi355_window.h) and windows up
- * to the present (css_mi355_present_window.h).
+ * preview, css_mi355_preview.h, works and leaves the NeMo state untouched), Whisper's frame history and encoder windows
+ * (css_mi355_window.h) and windows up to the present (css_mi355_present_window.h).  A NeMo stream's own frame history, and chunks
+ * of it written on the device, are css_mi355_nemo_chunk.h's.
  * Out of scope: per-band normalisation over the whole recording (a live consumer cannot have it before the end), float16 frames,
  * other frame geometries.
  */

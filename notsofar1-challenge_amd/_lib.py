@@ -300,6 +300,40 @@ STREAM_NEMO_ARRAYS = {
 }
 
 
+# include/css_mi355_nemo_chunk.h: chunks out of a NeMo stream's frame history
+NEMO_CHUNK_NORMALIZE = {None: 0, "per_feature": 1}   # CSS_NEMO_CHUNK_RAW, CSS_NEMO_CHUNK_PER_FEATURE
+NEMO_CHUNK_MAX_WIDTH = 3000                      # CSS_NEMO_CHUNK_MAX_WIDTH
+NEMO_CHUNK_TABLE = 32                            # CSS_NEMO_CHUNK_TABLE: chunks per launch of css_stream_nemo_chunks
+
+
+class CssStreamNemoChunk(C.Structure):
+    _fields_ = [("id", C.c_int32), ("speaker", C.c_int32), ("first_frame", C.c_int64), ("n_frames", C.c_int32), ("width", C.c_int32),
+                ("dtype", C.c_int32), ("normalize", C.c_int32), ("pad_value", C.c_float), ("reserved", C.c_int32),
+                ("out_dev", C.c_void_p), ("ld", C.c_int64), ("mean_host", C.c_void_p), ("std_host", C.c_void_p)]
+
+
+class CssNemoChunkArray(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("elems", C.c_int64)]
+
+
+class CssNemoChunkJob(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n_mels", "n_frames", "width", "dtype", "normalize")] + [("pad_value", C.c_float)] + \
+               [(n, C.c_int64) for n in ("hist", "end_frame", "first_frame", "ld", "out_offset")] + \
+               [(n, CssNemoChunkArray) for n in ("ring", "out", "mean", "std")]
+
+
+class CssStreamNemoMelHistoryJob(C.Structure):
+    _fields_ = [("n_mels", C.c_int32), ("reserved", C.c_int32)] + [(n, C.c_int64) for n in ("row0", "rows", "mel_ld", "hist")] + \
+               [(n, CssNemoChunkArray) for n in ("n_new", "mel", "ring", "frames_after")]
+
+
+# the arrays of the two kernel entries, as STREAM_NEMO_ARRAYS (out: float32, or float16 words where the job's dtype is 1)
+NEMO_CHUNK_ARRAYS = {
+    "CssNemoChunkJob": ((("ring", np.float32),), (("out", None), ("mean", np.float32), ("std", np.float32))),
+    "CssStreamNemoMelHistoryJob": ((("n_new", np.int32), ("frames_after", np.int64)), (("mel", np.float32), ("ring", np.float32))),
+}
+
+
 class CssSessionScanJob(C.Structure):           # include/css_mi355_handoff_kernels.h
     _fields_ = [(n, C.c_int32) for n in ("S", "pad", "drop", "cap_ranges", "gate_off", "reserved")] + [("TL", C.c_int64)] + \
                [(n, CssKArray) for n in ("gate", "psum", "regs", "offs", "st", "n_new", "n_ranges", "ranges_out", "n_frames_out",
@@ -663,6 +697,14 @@ STREAM_NEMO_ABI = {
     "css_stream_nemo_append_host": (C.c_int, [_P, C.POINTER(CssStreamNemoAppendJob), C.c_int32, _P, C.c_int64]),
     "css_stream_nemo_mel_host": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.c_int64, C.POINTER(CssStreamNemoMelJob), C.c_int32]),
 }
+# include/css_mi355_nemo_chunk.h (a table of its own, as STREAM_NEMO_ABI)
+NEMO_CHUNK_ABI = {
+    "css_stream_nemo_history_open": (C.c_int, [_P, C.c_int32, C.c_int32]),
+    "css_stream_nemo_history_range": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "css_stream_nemo_chunks": (C.c_int, [_P, C.POINTER(CssStreamNemoChunk), C.c_int32, C.POINTER(C.c_int32)]),
+    "css_nemo_chunk_host": (C.c_int, [_P, C.POINTER(CssNemoChunkJob), C.c_int32]),
+    "css_stream_nemo_mel_history_host": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.c_int64, C.POINTER(CssStreamNemoMelHistoryJob), C.c_int32]),
+}
 WINDOW_KERNEL_ITEMS = 64                         # CSS_WINDOW_KERNEL_ITEMS
 ARRAY_MIN_MICS, ARRAY_MAX_MICS = 2, 8            # CSS_ARRAY_MIN_MICS, CSS_ARRAY_MAX_MICS
 SESSION_SCAN_CHUNK = 1024                        # CSS_SESSION_SCAN_CHUNK: the keep-scan kernel's step, in gate frames / sample blocks
@@ -715,7 +757,7 @@ def load() -> C.CDLL:
                               list(ARRAY_SIGNATURES.items()) + list(SESSION_RATE_SIGNATURES.items()) +
                               list(SESSION_WINDOW_BINDINGS.items()) + list(RATE_KERNEL_BINDINGS.items()) +
                               list(STREAM_KERNEL_BINDINGS.items()) + list(HANDOFF_KERNEL_BINDINGS.items()) +
-                              list(NEMO_HANDOFF_ABI.items()) + list(STREAM_NEMO_ABI.items())):
+                              list(NEMO_HANDOFF_ABI.items()) + list(STREAM_NEMO_ABI.items()) + list(NEMO_CHUNK_ABI.items())):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -1628,7 +1670,8 @@ class Handle:
     #      (include/css_mi355_stream_kernels.h; tests/test_hip_stream_kernels.py).  A job is a dict of the descriptor's scalar fields
     #      and its arrays (the WHOLE allocations; None or absent: not passed); the arrays a launch may write are copied first, and
     #      every call returns one dict per job with them as the launch left them.
-    def _stream_kernel_table(self, kind, jobs, arrays=None):
+    def _stream_kernel_table(self, kind, jobs, arrays=None, skip=()):
+        """(``skip``: keys of a job that only say how its arrays are read -- ``f16`` -- and are no field of ``kind``)"""
         ins, outs = (arrays or STREAM_KERNEL_ARRAYS)[kind.__name__]
         tab = (kind * len(jobs))()
         keep, left = [], []
@@ -1648,7 +1691,8 @@ class Handle:
                 if out:
                     got[name] = a
             for k, v in j.items():
-                setattr(d, k, float(v) if k == "activity_th" else int(v))
+                if k not in skip:
+                    setattr(d, k, float(v) if k == "activity_th" else int(v))
             left.append(got)
         return tab, keep, left
 
@@ -1709,6 +1753,24 @@ class Handle:
         spec = np.ascontiguousarray(spec, dtype=np.float32).reshape(-1)
         tab, keep, left = self._stream_kernel_table(CssStreamNemoMelJob, jobs, STREAM_NEMO_ARRAYS)
         return self._rate_left(self.lib.css_stream_nemo_mel_host(self.h, int(S), _np_ptr(spec), spec.size, int(ld), tab, len(jobs)), left)
+
+    # ---- the two kernel entries of include/css_mi355_nemo_chunk.h (tests/test_hip_nemo_chunk_kernels.py); jobs are dicts as above
+    def stream_nemo_mel_history(self, S: int, spec, ld: int, jobs):
+        """launch_nemo_mel_multi with a frame history (css_stream_nemo_mel_history_host): ``stream_nemo_mel``'s jobs with ``hist``,
+        ``ring`` [S, n_mels, hist] and ``frames_after`` [S] (int64: the frame counts after the round) -> [{mel, ring}]"""
+        spec = np.ascontiguousarray(spec, dtype=np.float32).reshape(-1)
+        tab, keep, left = self._stream_kernel_table(CssStreamNemoMelHistoryJob, jobs, NEMO_CHUNK_ARRAYS)
+        return self._rate_left(self.lib.css_stream_nemo_mel_history_host(self.h, int(S), _np_ptr(spec), spec.size, int(ld), tab, len(jobs)), left)
+
+    def nemo_chunk_kernel(self, jobs):
+        """launch_nemo_chunks per 32 jobs (css_nemo_chunk_host) on caller rings [n_mels, hist]: the descriptor's fields, with
+        ``normalize`` and ``dtype`` as numbers; ``out`` is float32, or uint16 words of float16 with ``dtype`` 1 -> [{out, mean, std}]"""
+        jobs = [dict(j) for j in jobs]
+        pads = [float(j.pop("pad_value", 0.0)) for j in jobs]
+        tab, keep, left = self._stream_kernel_table(CssNemoChunkJob, [dict(j, f16=int(int(j["dtype"]) == 1)) for j in jobs], NEMO_CHUNK_ARRAYS, skip=("f16",))
+        for d, p in zip(tab, pads):
+            d.pad_value = p
+        return self._rate_left(self.lib.css_nemo_chunk_host(self.h, tab, len(jobs)), left)
 
     # ---- the window kernels and the queued sessions' hand-off kernels of csrc/handoff.hip on caller data
     #      (include/css_mi355_handoff_kernels.h; tests/test_hip_window_kernels.py).  A job is a dict as above; an array with an

@@ -1,6 +1,6 @@
 // Internal header of the host side of streamed sessions: what api_stream.hip (the window, the rounds, push / finish / preview),
-// api_stream_handoff.hip (hand-off, frame history, encoder windows) and api_stream_io.hip (rate ratio, output format, the ways
-// samples reach the window and leave it) share.  Nothing here is exported.
+// api_stream_handoff.hip (hand-off, frame history, encoder windows), api_nemo_chunk.hip (a NeMo stream's history and chunks) and
+// api_stream_io.hip (rate ratio, output format, the ways samples reach the window and leave it) share.  Nothing here is exported.
 #pragma once
 #include "api_ctx.hpp"
 #include "../../include/css_mi355_rate.h"
@@ -10,6 +10,7 @@
 #include "../../include/css_mi355_present_window.h"
 #include "../../include/css_mi355_stream_out.h"
 #include "../../include/css_mi355_stream_nemo.h"
+#include "../../include/css_mi355_nemo_chunk.h"
 
 #include <climits>
 
@@ -39,7 +40,8 @@ struct HandoffStream {
     int64_t hist_frames = 0;
     // the NeMo format (css_stream_nemo_open, include/css_mi355_stream_nemo.h): everything above but the history serves it as it
     // serves Whisper's (cfg holds n_mels, pad_frames, drop_silence; tail at NEMO_TAIL_LD); the last kept sample per speaker
-    // travels in two generations beside carry and tail
+    // travels in two generations beside carry and tail.  A NeMo stream's history (css_stream_nemo_history_open,
+    // include/css_mi355_nemo_chunk.h; api_nemo_chunk.hip) is `ring` and `hist_frames` above, without the maxima.
     bool nemo = false;
     float preemph = 0.f;
     DevBuf xlast[2];
@@ -56,6 +58,8 @@ struct HandoffCtx {
     // the same for the NeMo streams of a round (their own operand, spectra, results and staging: a round may have both formats)
     DevBuf nemo_operand, nemo_spec, nemo_res;
     std::vector<PinnedBuf> nemo_pinned;
+    // css_stream_nemo_chunks: mean and std [2][n_mels] per chunk of one call, and their staging
+    DevBuf chunk_stats; PinnedBuf chunk_pin;
 };
 
 // Per stream with a rate ratio (css_stream_set_rate; resample.hip).  Nothing here is part of the window: the rebase never touches

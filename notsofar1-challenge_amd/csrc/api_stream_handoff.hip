@@ -3,7 +3,8 @@
 // downloads of a round: three launches for all streams of the round (handoff.hip: append, ONE DFT product, mel), results
 // into page-locked staging under the call's final synchronise, where the host trims them into the caller's buffers.
 // The NeMo format (css_stream_nemo_*; include/css_mi355_stream_nemo.h) is the same step with nemo_stream.hip's kernels and the
-// offline NeMo path's tables: raw ln(mel + 2^-24) frames instead, no running maximum, no previews with hand-off, no history.
+// offline NeMo path's tables: raw ln(mel + 2^-24) frames instead, no running maximum, no previews with hand-off.  Its frame history
+// and the chunks out of it are api_nemo_chunk.hip's (include/css_mi355_nemo_chunk.h); the mel launch below fills that ring too.
 // A hand-off stream with a frame history (css_stream_window_open, include/css_mi355_window.h) also keeps its last raw
 // log-mel frames in a ring on the device: the mel launch of a committed round leaves them there.  css_stream_windows turns spans
 // of them into Whisper encoder inputs in the caller's device memory, css_stream_present_windows spans that end in a preview's
@@ -143,6 +144,7 @@ static int handoff_round_format(css_ctx* h, const std::vector<RoundJob>& all, si
             nap[i] = NemoAppend{ap[i], (const float*)o->xlast[o->cur].p, (float*)o->xlast[1 - o->cur].p, o->preemph, 0};
             nme[i] = NemoMel{ap[i].row0, ap[i].rows, ap[i].n_new, nemo_bank(h, o->cfg.n_mels), (float*)((char*)res.p + mel_off[i]), ap[i].rows,
                              o->cfg.n_mels, 0};
+            if (commit && o->hist_frames) { nme[i].ring = (float*)o->ring.p; nme[i].hist = o->hist_frames; nme[i].st = st; }
             me[i].mel = nme[i].mel;
         } else {
             me[i] = HandoffMel{ap[i].row0, ap[i].rows, ap[i].n_new, st, dftm + HO_DFT_F + (o->cfg.n_mels == 80 ? 0 : HO_MEL80_F), o->cfg.n_mels,
@@ -514,7 +516,7 @@ int css_stream_window_range(css_handle_t h, int32_t id, int64_t* first_frame, in
     if (!h) return CSS_ERR_INVALID_ARG;
     StreamState* s = get_stream(h, id);
     if (!s || !first_frame || !end_frame) return fail(h, CSS_ERR_INVALID_ARG, "no open stream with this id / null argument");
-    if (!s->ho || !s->ho->hist_frames) return fail(h, CSS_ERR_STATE, "this stream has no frame history (css_stream_window_open)");
+    if (!s->ho || !s->ho->hist_frames || s->ho->nemo) return fail(h, CSS_ERR_STATE, "this stream has no frame history (css_stream_window_open)");
     for (int k = 0; k < h->d.num_spks; ++k) {
         const int64_t J = s->ho->m.J[(size_t)k];
         first_frame[k] = std::max<int64_t>(J - s->ho->hist_frames, 0);
@@ -534,7 +536,7 @@ int css_stream_windows(css_handle_t h, CssStreamWindow* items, int32_t n_items, 
         const StreamState* s = get_stream(h, p.id);
         if (!s) return refuse("no open stream with this id");
         const HandoffStream* o = s->ho.get();
-        if (!o || !o->hist_frames) return refuse("the stream has no frame history (css_stream_window_open)");
+        if (!o || !o->hist_frames || o->nemo) return refuse("the stream has no frame history (css_stream_window_open)");
         if (const char* bad = window_refusal(h, o, p, &p.first_frame)) return refuse(bad);
         w[(size_t)i] = history_item(o, p);
         w[(size_t)i].J = p.first_frame + p.n_frames;   // (no provisional frames: the span the kernel resolves is the request's)

@@ -10,6 +10,7 @@
 #include "stitch_common.hpp"   // (OLA_T: the gate kernel's block of frames)
 #include "../../include/css_mi355_stream_kernels.h"
 #include "../../include/css_mi355_stream_nemo.h"
+#include "../../include/css_mi355_nemo_chunk.h"
 
 using namespace css;
 using namespace css::kstage;
@@ -22,6 +23,8 @@ bool pow2(int64_t v) { return v > 0 && (v & (v - 1)) == 0; }
 bool pos_ok(int64_t v) { return v >= 0 && v <= POS_MAX; }
 static_assert(sizeof(CssStreamNemoArray) == sizeof(CssKArray), "the stager's array descriptor");
 CssKArray ka(const CssStreamNemoArray& a) { return CssKArray{a.p, a.elems}; }
+static_assert(sizeof(CssNemoChunkArray) == sizeof(CssKArray), "the stager's array descriptor");
+CssStreamNemoArray na(const CssNemoChunkArray& a) { return CssStreamNemoArray{a.p, a.elems}; }
 
 // Both append entries: job i is job(i); nemo(i), where the call is css_stream_nemo_append_host, its NeMo part (else null).
 template <class Job, class Nemo>
@@ -358,42 +361,80 @@ int css_stream_mel_host(css_handle_t h, int32_t S, const float* spec, int64_t sp
     return download_all(h, sg, base);
 }
 
-int css_stream_nemo_mel_host(css_handle_t h, int32_t S, const float* spec, int64_t spec_elems, int64_t ld, CssStreamNemoMelJob* jobs,
-                             int32_t n_jobs) {
-    CSS_DRAIN(h);
-    if (!h) return CSS_ERR_INVALID_ARG;
-    auto bad = [&](const char* what) { return fail(h, CSS_ERR_INVALID_ARG, std::string("css_stream_nemo_mel_host: ") + what); };
-    if (!jobs || !spec) return bad("null argument");
+// Both NeMo mel entries: job i's mel part is mj(i); hj, where the call is css_stream_nemo_mel_history_host, its jobs (else null: `jobs`).
+static int nemo_mel_host(css_ctx* h, const char* who, int32_t S, const float* spec, int64_t spec_elems, int64_t ld, CssStreamNemoMelJob* jobs,
+                         CssStreamNemoMelHistoryJob* hj, int32_t n_jobs) {
+    auto bad = [&](const char* what) { return fail(h, CSS_ERR_INVALID_ARG, std::string(who) + ": " + what); };
+    auto mj = [&](int i) {
+        if (!hj) return jobs[i];
+        const CssStreamNemoMelHistoryJob& q = hj[i];
+        return CssStreamNemoMelJob{q.n_mels, q.reserved, q.row0, q.rows, q.mel_ld, na(q.n_new), na(q.mel)};
+    };
+    if ((!jobs && !hj) || !spec) return bad("null argument");
     if (n_jobs < 1 || n_jobs > CSS_STREAM_KERNEL_JOBS) return bad("1 .. 64 jobs");
     if (S < 1 || S > 4) return bad("S must be 1 .. 4");
     constexpr int64_t SPEC_ROWS = 2 * NEMO_BINS;
     if (ld < 1 || ld > HOST_CAP / SPEC_ROWS || spec_elems < SPEC_ROWS * ld || spec_elems > HOST_CAP) return bad("spec is shorter than [514][ld]");
     for (int i = 0; i < n_jobs; ++i) {
-        const CssStreamNemoMelJob& j = jobs[i];
+        const CssStreamNemoMelJob j = mj(i);
         if (j.n_mels != 80 && j.n_mels != 128) return bad("n_mels must be 80 or 128");
         if (j.row0 < 0 || j.rows < 1 || j.rows > (1 << 20) || j.row0 + (int64_t)S * j.rows > ld) return bad("row0 + S rows must lie in [0, ld]");
         if (j.mel_ld < j.rows || j.mel_ld > HOST_CAP) return bad("mel_ld must cover rows");
         if (!arr_ok(ka(j.n_new), S) || !arr_ok(ka(j.mel), (int64_t)S * j.n_mels * j.mel_ld) || !j.n_new.p || !j.mel.p) return bad("an array is null or shorter than its description");
         for (int k = 0; k < S; ++k)
             if (((const int32_t*)j.n_new.p)[k] < 0) return bad("n_new must not be negative");
+        if (!hj) continue;
+        const CssStreamNemoMelHistoryJob& q = hj[i];
+        if (q.hist < 1 || q.hist > HOST_CAP / (S * j.n_mels)) return bad("hist must be 1 .. 2^28 / (S n_mels) (the ring is staged whole)");
+        if (!arr_ok(ka(na(q.ring)), (int64_t)S * j.n_mels * q.hist) || !arr_ok(ka(na(q.frames_after)), S) || !q.ring.p || !q.frames_after.p)
+            return bad("an array is null or shorter than its description");
+        for (int k = 0; k < S; ++k) {
+            const int64_t J = ((const int64_t*)q.frames_after.p)[k];
+            if (J < ((const int32_t*)j.n_new.p)[k] || !pos_ok(J)) return bad("a frame count after the round below n_new");
+        }
     }
     int rc;
     HIPCHK(h, hipSetDevice(h->device));
     if ((rc = nemo_ensure_tables(h)) != CSS_OK) return rc;
     Stager sg;
     const size_t spec_at = sg.take_raw((void*)spec, (size_t)spec_elems * 4, false);
-    std::vector<size_t> nn_at((size_t)n_jobs), mel_at((size_t)n_jobs);
-    for (int i = 0; i < n_jobs; ++i) { nn_at[(size_t)i] = sg.take(ka(jobs[i].n_new), 4, false); mel_at[(size_t)i] = sg.take(ka(jobs[i].mel), 4, true); }
+    struct At { size_t nn, mel, ring, st; };
+    std::vector<At> at((size_t)n_jobs);
+    std::vector<std::vector<HandoffState>> st((size_t)n_jobs);   // the state rows the kernel reads the counts from
+    for (int i = 0; i < n_jobs; ++i) {
+        At& a = at[(size_t)i];
+        a = At{sg.take(ka(mj(i).n_new), 4, false), sg.take(ka(mj(i).mel), 4, true), 0, 0};
+        if (!hj) continue;
+        st[(size_t)i].assign((size_t)S, HandoffState{});
+        for (int k = 0; k < S; ++k) st[(size_t)i][(size_t)k].J = ((const int64_t*)hj[i].frames_after.p)[k];
+        a.ring = sg.take(ka(na(hj[i].ring)), 4, true);
+        a.st = sg.take_raw(st[(size_t)i].data(), (size_t)S * sizeof(HandoffState), false);
+    }
     char* base = nullptr;
     if ((rc = stage_and_upload(h, sg, &base)) != CSS_OK) return rc;
     std::vector<NemoMel> me((size_t)n_jobs);
     for (int i = 0; i < n_jobs; ++i) {
-        const CssStreamNemoMelJob& j = jobs[i];
-        me[(size_t)i] = NemoMel{j.row0, j.rows, (const int32_t*)(base + nn_at[(size_t)i]), nemo_bank(h, j.n_mels), (float*)(base + mel_at[(size_t)i]), j.mel_ld,
-                                j.n_mels, 0};
+        const CssStreamNemoMelJob j = mj(i);
+        const At& a = at[(size_t)i];
+        me[(size_t)i] = NemoMel{j.row0, j.rows, (const int32_t*)(base + a.nn), nemo_bank(h, j.n_mels), (float*)(base + a.mel), j.mel_ld, j.n_mels, 0};
+        if (hj) { me[(size_t)i].ring = (float*)(base + a.ring); me[(size_t)i].hist = hj[i].hist; me[(size_t)i].st = (const HandoffState*)(base + a.st); }
     }
     launch_nemo_mel_multi(me.data(), n_jobs, S, (const float*)(base + spec_at), ld, h->stream);
     return download_all(h, sg, base);
+}
+
+int css_stream_nemo_mel_host(css_handle_t h, int32_t S, const float* spec, int64_t spec_elems, int64_t ld, CssStreamNemoMelJob* jobs,
+                             int32_t n_jobs) {
+    CSS_DRAIN(h);
+    if (!h) return CSS_ERR_INVALID_ARG;
+    return nemo_mel_host(h, "css_stream_nemo_mel_host", S, spec, spec_elems, ld, jobs, nullptr, n_jobs);
+}
+
+int css_stream_nemo_mel_history_host(css_handle_t h, int32_t S, const float* spec, int64_t spec_elems, int64_t ld,
+                                     CssStreamNemoMelHistoryJob* jobs, int32_t n_jobs) {
+    CSS_DRAIN(h);
+    if (!h) return CSS_ERR_INVALID_ARG;
+    return nemo_mel_host(h, "css_stream_nemo_mel_history_host", S, spec, spec_elems, ld, nullptr, jobs, n_jobs);
 }
 
 }  // extern "C"

@@ -17,6 +17,7 @@
 #include "kernels.hpp"
 #include "table.hpp"
 #include "wave.hpp"
+#include "window_vec.hpp"
 
 namespace css {
 
@@ -311,23 +312,6 @@ __global__ __launch_bounds__(256) void handoff_mel_multi_kernel(HandoffMelTable 
 
 // ---- encoder windows: a span of the frame history, then a preview's provisional frames where the window reaches the present ----
 struct WindowTable : Table<WindowItem, WINDOW_MULTI_MAX> {};
-
-template <typename T> struct WindowVec;
-template <> struct WindowVec<float> {
-    static constexpr int V = 4;
-    static __device__ __forceinline__ void store(float* p, float v) { *p = v; }
-    static __device__ __forceinline__ void store16(float* p, const float* v) { *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]); }
-};
-template <> struct WindowVec<__half> {
-    static constexpr int V = 8;
-    static __device__ __forceinline__ void store(__half* p, float v) { *p = __float2half_rn(v); }
-    static __device__ __forceinline__ void store16(__half* p, const float* v) {
-        auto two = [&](int i) {
-            return (uint32_t)__half_as_ushort(__float2half_rn(v[i])) | ((uint32_t)__half_as_ushort(__float2half_rn(v[i + 1])) << 16);
-        };
-        *reinterpret_cast<uint4*>(p) = make_uint4(two(0), two(2), two(4), two(6));
-    }
-};
 
 // Frames s .. s + V - 1 of one band's row of `len` floats (the caller has s + V <= len) through 16-byte loads: as they are at a
 // 16-byte boundary; off it, the aligned pieces around them where those lie inside the row (selects on constant positions: no

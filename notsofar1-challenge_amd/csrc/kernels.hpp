@@ -367,9 +367,31 @@ struct NemoMel {
     const float* w;                                     // the bank [n_mels][257]
     float* mel; int64_t mel_ld;                         // out [S][n_mels][mel_ld]: ln(mel + 2^-24)
     int32_t n_mels, pad_;
+    // the frame history (include/css_mi355_nemo_chunk.h), null for an entry without one: [S][n_mels][hist], frame j of speaker k's
+    // concatenation in slot j mod hist.  st[k].J is k's frame count AFTER the round (the append kernel's st_out), so the round's
+    // frame j is frame J - n_new + j; only the round's last `hist` frames are written: frames j and j + hist share a slot.
+    float* ring; int64_t hist; const HandoffState* st;
 };
 void launch_nemo_append_multi(const NemoAppend* e, int n, float* operand, hipStream_t s);   // tables of HANDOFF_MULTI_MAX
 void launch_nemo_mel_multi(const NemoMel* e, int n, int S, const float* spec, int64_t ld, hipStream_t s);
+
+// NeMo chunks out of the frame history (include/css_mi355_nemo_chunk.h; DESIGN.md 7b "NeMo chunks out of the frame history"):
+// frames [first, first + n_frames) of one speaker's ring, raw or normalised per band over the span -- (raw - mean) / (std + 1e-5),
+// nemo_norm_kernel's expression, with the span's own mean and unbiased std -- padded with pad_value to `width` columns, as float32
+// or float16 into the caller's device memory.  The sums are float64 in ONE order: lane l of 64 adds frames l, l + 64, ... in
+// increasing order, then x[l] += x[l + s] for s = 32 .. 1; d * d and the addition of the second pass are rounded apart.  The host
+// has checked max(J - hist, 0) <= first and first + n_frames <= J for the speaker's count J.  A table launch: blockIdx.z = chunk.
+struct NemoChunkItem {
+    const float* ring;                                  // the speaker's rows of the history: [n_mels][hist]
+    void* out; float* mean; float* stdv;                // out [n_mels][ld] of the dtype; the span's statistics [n_mels] each (written with `normalize`)
+    int64_t hist, ld, first;
+    float pad_value;
+    int32_t n_frames, width, n_mels, f16, normalize;
+};
+constexpr int NEMO_CHUNK_MULTI_MAX = 32;                // (CSS_NEMO_CHUNK_TABLE of the header)
+constexpr int NEMO_CHUNK_ROWS = 8;                      // mel bands per block
+constexpr int NEMO_CHUNK_MAX_WIDTH = 3000;              // (CSS_NEMO_CHUNK_MAX_WIDTH; a wave keeps its row's frames in LDS)
+void launch_nemo_chunks(const NemoChunkItem* e, int n, hipStream_t s);   // one launch; n <= NEMO_CHUNK_MULTI_MAX
 
 // ------------------------------------------------------------------------------------------------
 // loss.hip -- validation loss of the training loop (train.py:411 _calc_loss): S x S base-loss sums + the noise term

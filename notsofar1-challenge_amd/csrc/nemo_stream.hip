@@ -1,9 +1,12 @@
 // The NeMo hand-off of STREAMED sessions (include/css_mi355_stream_nemo.h; DESIGN.md 7b "The NeMo hand-off of a stream"): the
 // append kernel and the multi-owner mel kernel of a round (kernels.hpp NemoAppend, NemoMel).  The product between them is
-// launch_gemm on the offline path's [514][512] analysis matrix; the tile is the offline path's (nemo_tile.hpp).
+// launch_gemm on the offline path's [514][512] analysis matrix; the tile is the offline path's (nemo_tile.hpp).  The mel kernel
+// also keeps a stream's frame history, and nemo_chunk_kernel turns spans of it into a consumer's chunks
+// (include/css_mi355_nemo_chunk.h; DESIGN.md 7b "NeMo chunks out of the frame history").
 #include "kernels.hpp"
 #include "nemo_tile.hpp"
 #include "table.hpp"
+#include "window_vec.hpp"
 
 namespace css {
 
@@ -117,6 +120,135 @@ __global__ __launch_bounds__(256) void nemo_mel_multi_kernel(NemoMelTable tab, c
     if (j0 >= nfr) return;
     __shared__ NemoTilePw pw;
     nemo_mel_tile(pw, spec, ld, e.row0 + (int64_t)k * e.rows, j0, nfr, e.w, e.n_mels, e.mel + (int64_t)k * e.n_mels * e.mel_ld, e.mel_ld);
+    if (!e.ring) return;   // (uniform over the block: an entry without a history pays nothing more)
+    // The frame history: the tile's frames are copied out of the rows the block has just written, so the tile itself -- and with it
+    // the offline kernel that shares it -- stays as it is.  The round's frame j is frame J - n_new + j of the concatenation, J the
+    // count after the round; frames j and j + hist share a slot, so only the round's last `hist` frames are written and no two
+    // threads of a launch write one slot.
+    __syncthreads();
+    const int tj = threadIdx.x & (NEMO_TILE_FRAMES - 1), ty = threadIdx.x >> 5;
+    const int64_t j = j0 + tj, n_new = e.n_new[k];
+    if (j >= nfr || j < n_new - e.hist) return;
+    const int64_t slot = (e.st[k].J - n_new + j) % e.hist;
+    const float* __restrict__ mel = e.mel + (int64_t)k * e.n_mels * e.mel_ld + j;
+    float* __restrict__ ring = e.ring + (int64_t)k * e.n_mels * e.hist + slot;
+    for (int m = ty; m < e.n_mels; m += NEMO_TILE_ROWS) ring[(int64_t)m * e.hist] = mel[(int64_t)m * e.mel_ld];
+}
+
+// ---- NeMo chunks out of the frame history (kernels.hpp NemoChunkItem) ---------------------------------------------------------
+struct NemoChunkTable : Table<NemoChunkItem, NEMO_CHUNK_MULTI_MAX> {};
+
+// float64 sum and product that stay ONE rounding each (kernels.hpp css_add_rn: an operation compiled with contraction off cannot
+// become half of an FMA)
+__device__ __forceinline__ double nemo_dadd(double x, double y) {
+#pragma clang fp contract(off)
+    return x + y;
+}
+__device__ __forceinline__ double nemo_dmul(double x, double y) {
+#pragma clang fp contract(off)
+    return x * y;
+}
+// x[l] += x[l + s] for s = 32 .. 1 over the wave's lanes; every lane gets x[0].  (A lane at or above s adds a value the tree does
+// not use: nothing below s reads it.)
+__device__ __forceinline__ double nemo_wave_tree(double x) {
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) x = nemo_dadd(x, __shfl_down(x, s));
+    return __shfl(x, 0);
+}
+
+// `len` floats from src (global) to dst (LDS), consecutive lanes on consecutive floats: scalar loads up to src's first 16-byte
+// boundary, 16-byte loads from there, scalar loads behind the last whole one
+__device__ __forceinline__ void nemo_chunk_load(const float* __restrict__ src, float* dst, int len, int lane) {
+    const int head = min((int)((4 - (((uintptr_t)src >> 2) & 3)) & 3), len);
+    const int nvec = (len - head) / 4, tail = head + nvec * 4;
+    for (int c = lane; c < head; c += 64) dst[c] = src[c];
+    for (int c = tail + lane; c < len; c += 64) dst[c] = src[c];
+    for (int g = lane; g < nvec; g += 64) {
+        const int c = head + g * 4;
+        const float4 q = *reinterpret_cast<const float4*>(src + c);
+        dst[c] = q.x; dst[c + 1] = q.y; dst[c + 2] = q.z; dst[c + 3] = q.w;
+    }
+}
+
+// One row of a chunk out of the wave's LDS copy `rw` of its n frames: column c < n is rw[c], normalised with `norm`; the columns
+// behind them are pad.  Written as handoff.hip's window_row writes a row: scalar stores up to dst's first 16-byte boundary, 16-byte
+// stores from there, scalar stores behind the last whole one.
+template <typename T>
+__device__ __forceinline__ void nemo_chunk_row(const float* rw, int n, int width, bool norm, float mean, float denom, float pad,
+                                               T* __restrict__ dst, int lane) {
+    constexpr int V = WindowVec<T>::V;
+    auto one = [&](int c) {
+        if (c >= n) return pad;
+        const float v = rw[c];
+        return norm ? css_div_rn(css_add_rn(v, -mean), denom) : v;
+    };
+    const int head = min((int)(((16 - ((uintptr_t)dst & 15)) & 15) / sizeof(T)), width);
+    const int nvec = (width - head) / V, tail = head + nvec * V;
+    for (int c = lane; c < head; c += 64) WindowVec<T>::store(dst + c, one(c));
+    for (int c = tail + lane; c < width; c += 64) WindowVec<T>::store(dst + c, one(c));
+    for (int g = lane; g < nvec; g += 64) {
+        const int c = head + g * V;
+        float v[V];
+#pragma unroll
+        for (int i = 0; i < V; ++i) v[i] = one(c + i);
+        WindowVec<T>::store16(dst + c, v);
+    }
+}
+
+// A block has one chunk and NEMO_CHUNK_ROWS bands; a wave has one band row at a time.  The row's span is at most two contiguous
+// pieces of the ring -- slots [slot0, min(slot0 + n, hist)) and, behind a wrap, [0, ...) -- which the wave copies into its LDS
+// row once; both float64 passes and the write pass read the frames from there in span order, so nothing below depends on the slot
+// the span starts in or on a wrap inside it.
+__global__ __launch_bounds__(256) void nemo_chunk_kernel(NemoChunkTable tab) {
+    const NemoChunkItem& e = tab.e[blockIdx.z];
+    const int m0 = blockIdx.x * NEMO_CHUNK_ROWS;
+    if (m0 >= e.n_mels) return;
+    __shared__ float rows[4][NEMO_CHUNK_MAX_WIDTH];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int n = e.n_frames;
+    const int64_t slot0 = e.first % e.hist;
+    const int n_a = (int)(slot0 + n <= e.hist ? n : e.hist - slot0);
+    float* rw = rows[wave];
+    for (int r = 0; r < NEMO_CHUNK_ROWS; r += 4) {
+        const int m = m0 + r + wave;
+        const bool live = m < e.n_mels;
+        if (live) {
+            const float* __restrict__ ring = e.ring + (int64_t)m * e.hist;
+            nemo_chunk_load(ring + slot0, rw, n_a, lane);
+            if (n_a < n) nemo_chunk_load(ring, rw + n_a, n - n_a, lane);
+        }
+        __syncthreads();
+        if (live) {
+            float mean_f = 0.f, denom = 1.f;
+            if (e.normalize) {
+                double s = 0.0;
+                for (int c = lane; c < n; c += 64) s = nemo_dadd(s, (double)rw[c]);
+                const double mean = nemo_wave_tree(s) / (double)n;
+                double q = 0.0;
+                for (int c = lane; c < n; c += 64) {
+                    const double d = nemo_dadd((double)rw[c], -mean);
+                    q = nemo_dadd(q, nemo_dmul(d, d));
+                }
+                const double ss = nemo_wave_tree(q);
+                mean_f = (float)mean;
+                const float std_f = n > 1 ? (float)sqrt(ss / (double)(n - 1)) : 0.f;
+                denom = css_add_rn(std_f, NEMO_STD_EPS);
+                if (lane == 0) { e.mean[m] = mean_f; e.stdv[m] = std_f; }
+            }
+            if (e.f16) nemo_chunk_row<__half>(rw, n, e.width, e.normalize != 0, mean_f, denom, e.pad_value, (__half*)e.out + (int64_t)m * e.ld, lane);
+            else nemo_chunk_row<float>(rw, n, e.width, e.normalize != 0, mean_f, denom, e.pad_value, (float*)e.out + (int64_t)m * e.ld, lane);
+        }
+        __syncthreads();   // (the row is free for the wave's next band)
+    }
+}
+
+void launch_nemo_chunks(const NemoChunkItem* e, int n, hipStream_t s) {
+    // (the caller chunks and counts the launches: more than one table here would be a launch it does not report)
+    for_each_table<NemoChunkTable>(e, std::min(n, NEMO_CHUNK_MULTI_MAX), [&](const NemoChunkTable& tab, int cnt) {
+        const int most = table_max(tab, cnt, 1, [](const NemoChunkItem& w) { return (int)w.n_mels; });
+        hipLaunchKernelGGL(nemo_chunk_kernel, dim3((unsigned)((most + NEMO_CHUNK_ROWS - 1) / NEMO_CHUNK_ROWS), 1, cnt), dim3(256), 0, s, tab);
+        return true;
+    });
 }
 
 void launch_nemo_append_multi(const NemoAppend* e, int n, float* operand, hipStream_t s) {

@@ -26,6 +26,14 @@ rules (``Handoff``; ``raw_max`` is None).  All calls' frames of a finished strea
 ``Handle.handoff_nemo_all(..., normalize=False).mel[k]`` of the whole recording, bit for bit.  A stream has one format:
 ``nemo=`` with ``handoff=`` or ``window_history=`` raises ValueError.
 
+``CssStream(..., nemo={...}, nemo_history=1024)`` (css_stream_nemo_history_open, include/css_mi355_nemo_chunk.h) also keeps the last
+``nemo_history`` raw NeMo frames of every separated stream on the device.  ``nemo_chunk(k)`` and
+``CssStreamGroup.nemo_chunks(requests)`` (css_stream_nemo_chunks) return a NeMo consumer's chunks as torch tensors on the handle's
+device -- a span of those frames, raw (cache-aware streaming FastConformer, ``normalize: NA``) or normalised per band over the span
+(buffered inference: ``(x - mean) / (std + 1e-5)`` with the span's own mean and unbiased std), padded to ``width`` columns with
+``pad_value``, float32 or float16 -- without the frames crossing PCIe again: ``nemo_chunk_features`` of the frames the pushes
+returned, bit for bit.
+
 ``CssStream(..., input_rate=48000)`` takes its pushes at the capture rate (css_stream_set_rate): ``push`` and ``push_pcm16`` move the
 samples to the device as they were captured and the rate conversion to the model's ``fs`` -- ``scipy.signal.resample_poly``'s
 default filter, in float32 -- is part of the ingest kernel.  A finished stream returned ``css_run`` of
@@ -142,6 +150,64 @@ def nemo_features(x: np.ndarray, n_mels: int = 80, preemphasis: float = 0.97, no
     return (raw - mean.astype(np.float32)[:, None]) / (std.astype(np.float32)[:, None] + np.float32(1e-5))
 
 
+def nemo_chunk_stats(raw: np.ndarray):
+    """Per band mean and unbiased std (0 for one frame) of raw NeMo frames [n_mels, n], as css_stream_nemo_chunks computes them:
+    float64 sums in one fixed order -- lane l of 64 adds frames l, l + 64, ... in increasing order, then ``x[l] += x[l + s]`` for
+    s = 32 .. 1 -- with ``d = raw - mean`` squared and added in two roundings, each result rounded to float32 once
+    -> (mean, std) float32 [n_mels]."""
+    raw = np.asarray(raw, dtype=np.float32)
+    if raw.ndim != 2 or raw.shape[1] < 1:
+        raise ValueError(f"expected [n_mels, n >= 1] frames, got {raw.shape}")
+    n_mels, n = raw.shape
+    rounds = -(-n // 64)
+    valid = (np.arange(rounds * 64) < n).reshape(rounds, 64)
+
+    def ordered_sum(x):   # x [n_mels, n] float64
+        lanes = np.zeros((n_mels, rounds * 64))
+        lanes[:, :n] = x
+        lanes = lanes.reshape(n_mels, rounds, 64)
+        acc = np.zeros((n_mels, 64))
+        for r in range(rounds):
+            acc = np.where(valid[r], acc + lanes[:, r], acc)
+        s = 32
+        while s:
+            acc[:, :s] = acc[:, :s] + acc[:, s:2 * s]
+            s //= 2
+        return acc[:, 0]
+
+    x = raw.astype(np.float64)
+    mean = ordered_sum(x) / np.float64(n)
+    d = x - mean[:, None]
+    std = np.sqrt(ordered_sum(d * d) / np.float64(n - 1)) if n > 1 else np.zeros(n_mels)
+    return mean.astype(np.float32), std.astype(np.float32)
+
+
+def nemo_chunk_features(raw: np.ndarray, width: Optional[int] = None, normalize: Optional[str] = "per_feature", dtype="float32",
+                        pad_value: float = 0.0) -> np.ndarray:
+    """The numpy statement of css_stream_nemo_chunks: raw NeMo frames [n_mels, n] of one span -> [n_mels, width] (default n).
+    Columns < n are the raw frames (``normalize=None``) or ``(raw - mean) / (std + 1e-5)`` in float32 with ``nemo_chunk_stats``
+    of the span (``"per_feature"``); the columns behind them hold ``pad_value`` and are never normalised; float16 is ``astype`` of
+    the float32 values.  Bit for bit what the device writes."""
+    raw = np.asarray(raw, dtype=np.float32)
+    dt = np.dtype(dtype)
+    if dt not in (np.dtype(np.float32), np.dtype(np.float16)):
+        raise ValueError(f"chunks are float32 or float16, got {dt}")
+    if normalize not in _lib.NEMO_CHUNK_NORMALIZE:
+        raise ValueError(f"normalize is None or 'per_feature', got {normalize!r}")
+    width = raw.shape[1] if width is None and raw.ndim == 2 else width
+    if raw.ndim != 2 or not 1 <= raw.shape[1] <= int(width) <= _lib.NEMO_CHUNK_MAX_WIDTH:
+        raise ValueError(f"expected [n_mels, 1 .. width <= {_lib.NEMO_CHUNK_MAX_WIDTH}] frames, got {raw.shape} for width {width}")
+    if not np.isfinite(pad_value):
+        raise ValueError("pad_value is finite")
+    out = np.full((raw.shape[0], int(width)), np.float32(pad_value), np.float32)
+    if normalize is None:
+        out[:, :raw.shape[1]] = raw
+    else:
+        mean, std = nemo_chunk_stats(raw)
+        out[:, :raw.shape[1]] = (raw - mean[:, None]) / (std + np.float32(1e-5))[:, None]
+    return out.astype(dt)
+
+
 def whisper_window(raw: np.ndarray, width: int = 3000, dtype="float16") -> np.ndarray:
     """The numpy statement of css_stream_windows: raw log-mel frames [n_mels, n] of one span -> [n_mels, width].  Columns < n are
     ``whisper_normalize(raw)``, clamped at the span's own maximum M; the columns behind them hold what a frame of digital zeros
@@ -248,9 +314,11 @@ class CssStream:
     def __init__(self, separator: HipSeparator, cfg: Optional[CssCfg] = None, fs: int = 16000, num_channels: Optional[int] = None,
                  handoff: Optional[Mapping[str, object]] = None, input_rate: Optional[int] = None,
                  window_history: Optional[int] = None, output: Optional[Mapping[str, object]] = None,
-                 nemo: Optional[Mapping[str, object]] = None):
+                 nemo: Optional[Mapping[str, object]] = None, nemo_history: Optional[int] = None):
         if nemo is not None and (handoff is not None or window_history is not None):
             raise ValueError("nemo= is a hand-off format of its own: not together with handoff= or window_history=")
+        if nemo_history is not None and nemo is None:
+            raise ValueError("nemo_history needs a stream opened with nemo=")
         self.separator = separator
         self.cfg = cfg if cfg is not None else CssCfg()
         desc = separator.desc
@@ -332,6 +400,16 @@ class CssStream:
                 self.close()
                 raise
             self.window_history = int(window_history)
+        self.nemo_history = None
+        self.chunk_mean = None
+        self.chunk_std = None
+        if nemo_history is not None:
+            try:
+                _lib.check(self._h.h, self._h.lib.css_stream_nemo_history_open(self._h.h, self.id, int(nemo_history)))
+            except Exception:
+                self.close()
+                raise
+            self.nemo_history = int(nemo_history)
 
     def _model_samples(self, n_in: int, finished: bool = False) -> int:
         """model-rate samples after ``n_in`` samples as they are pushed (css_stream_rate_samples; without a rate: ``n_in``)"""
@@ -607,6 +685,35 @@ class CssStream:
                                                                _raise_refused=True)
         return got[0] if out is not None or spans[0, 1] > 0 else None
 
+    def nemo_history_range(self):
+        """(first, end): the frames [first[k], end[k]) of separated stream k's concatenation the NeMo history holds
+        (css_stream_nemo_history_range)"""
+        first, end = np.zeros(self.num_spks, np.int64), np.zeros(self.num_spks, np.int64)
+        _lib.check(self._h.h, self._h.lib.css_stream_nemo_history_range(self._h.h, self.id, first.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                                        end.ctypes.data_as(C.POINTER(C.c_int64))))
+        return first, end
+
+    def nemo_chunk(self, k: int, first_frame: Optional[int] = None, n_frames: Optional[int] = None, width: Optional[int] = None,
+                   normalize: Optional[str] = "per_feature", dtype: str = "float32", pad_value: float = 0.0, out=None):
+        """One chunk of separated stream k for a NeMo consumer as a torch tensor [n_mels, width] on the handle's device
+        (css_stream_nemo_chunks): frames [first_frame, first_frame + n_frames) of the history -- by default the last
+        min(end - first, width) retained ones; ``width`` defaults to ``n_frames``, or to everything retained (at most 3000) --
+        raw (``normalize=None``) or normalised per band over the span, padded with ``pad_value``, in ``dtype``.  ``out``: a tensor
+        (or a slice of one) to write into.  ``chunk_mean`` / ``chunk_std`` hold the statistics a normalised chunk used."""
+        if self.nemo_history is None:
+            raise ValueError("nemo_chunk() needs a stream opened with nemo= and nemo_history=")
+        if width is None:
+            if n_frames is not None:
+                width = int(n_frames)
+            elif out is not None:
+                width = int(out.shape[-1])
+            else:
+                first, end = self.nemo_history_range()
+                width = max(min(int(end[k] - first[k]), _lib.NEMO_CHUNK_MAX_WIDTH), 1)
+        got = CssStreamGroup([self]).nemo_chunks([(self, k, first_frame, n_frames)], width, normalize, dtype, pad_value,
+                                                 None if out is None else out[None])
+        return got[0]
+
     def close(self):
         if self.id >= 0 and self._h.h:
             self._h.lib.css_stream_close(self._h.h, self.id)
@@ -757,6 +864,54 @@ class CssStreamGroup:
         self.window_launches = int(launches.value)
         for it, (s, *_) in zip(items, reqs):
             s.window_max = float(it.window_max)
+        return out
+
+    def nemo_chunks(self, requests, width: int, normalize: Optional[str] = "per_feature", dtype: str = "float32", pad_value: float = 0.0,
+                    out=None):
+        """Many chunks for a NeMo consumer in ONE css_stream_nemo_chunks: ``requests`` are (stream, k) or (stream, k, first_frame,
+        n_frames) with the defaults of ``CssStream.nemo_chunk`` -> a torch tensor [W, n_mels, width] on the handle's device
+        (``out``, or a slice of a caller's tensor, if given: ``windows``' rules).  All streams of the requests hand off the same
+        n_mels.  ``window_launches`` holds the kernel launches of the call, and every named stream's ``chunk_mean`` /
+        ``chunk_std`` (float32 [n_mels]; None for a raw chunk) the statistics of its last request."""
+        reqs = [tuple(r) + (None,) * (4 - len(r)) for r in requests]
+        if not reqs:
+            raise ValueError("no chunk requests")
+        for s, *_ in reqs:
+            if s not in self.streams:
+                raise ValueError("a stream that is not in this group")
+            if s.nemo_history is None:
+                raise ValueError("nemo_chunks() needs streams opened with nemo= and nemo_history=")
+        if normalize not in _lib.NEMO_CHUNK_NORMALIZE:
+            raise ValueError(f"normalize is None or 'per_feature', got {normalize!r}")
+        n_mels = int(reqs[0][0]._hcfg.n_mels)
+        if any(int(s._hcfg.n_mels) != n_mels for s, *_ in reqs):
+            raise ValueError("the streams of one nemo_chunks() call hand off the same n_mels")
+        width = int(width)
+        out, ld = _window_out(self._h, len(reqs), n_mels, width, dtype, out)
+        items = (_lib.CssStreamNemoChunk * len(reqs))()
+        stats = np.zeros((len(reqs), 2, n_mels), np.float32)
+        el = out.element_size()
+        for i, (it, (s, k, first_frame, n_frames)) in enumerate(zip(items, reqs)):
+            if first_frame is None or n_frames is None:
+                first, end = s.nemo_history_range()
+                if first_frame is None:
+                    n = min(int(end[k] - first[k]), width) if n_frames is None else int(n_frames)
+                    first_frame = int(end[k]) - n
+                if n_frames is None:
+                    n_frames = min(int(end[k]) - int(first_frame), width)
+                if end[k] == 0:   # (a live caller's first ticks: said here, not as the library's refusal of a span of no frames)
+                    raise ValueError(f"request {i}: no frames retained yet for separated stream {int(k)} (nemo_history_range())")
+            it.id, it.speaker, it.first_frame, it.n_frames, it.width = s.id, int(k), int(first_frame), int(n_frames), width
+            it.dtype, it.normalize, it.pad_value = _lib.WINDOW_DTYPES[dtype], _lib.NEMO_CHUNK_NORMALIZE[normalize], float(pad_value)
+            it.out_dev, it.ld = out.data_ptr() + i * out.stride(0) * el, ld
+            it.mean_host, it.std_host = stats[i, 0].ctypes.data, stats[i, 1].ctypes.data
+        # (as in windows(): what torch has queued for `out` on its own stream is finished first)
+        _torch().cuda.current_stream(out.device).synchronize()
+        launches = C.c_int32(0)
+        _lib.check(self._h.h, self._h.lib.css_stream_nemo_chunks(self._h.h, items, len(reqs), C.byref(launches)))
+        self.window_launches = int(launches.value)
+        for i, (s, *_) in enumerate(reqs):
+            s.chunk_mean, s.chunk_std = (None, None) if normalize is None else (stats[i, 0].copy(), stats[i, 1].copy())
         return out
 
     def present_windows(self, requests, width: int = 3000, dtype: str = "float16", out=None, _raise_refused: bool = False):

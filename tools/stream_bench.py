@@ -58,6 +58,13 @@ With --nemo (with --streams) four arms run, each in a fresh process of its own a
 with the Whisper hand-off, with the NeMo hand-off (CssStream(nemo=...), include/css_mi355_stream_nemo.h), and the host's route --
 the plain tick, then stream.nemo_features of every returned piece on the CPU.  --parent-library PATH adds the plain and the
 Whisper arm on an earlier build of the library, between this one's (profiles/r27_stream_nemo.json).
+
+With --nemo --chunks three arms run the same way: the NeMo tick on the earlier build (--parent-library), on this one without a
+frame history and with one of 3000 frames (CssStream(nemo_history=3000), include/css_mi355_nemo_chunk.h).  Behind its last pass the
+third arm times one CssStreamGroup.nemo_chunks call of 48 per-feature float16 chunks, of 400 frames and of up to 3000, against the
+host's route for the same chunks: numpy's per-feature normalisation of the frames the pushes returned, stacked, cast and uploaded
+with torch.from_numpy(...).cuda(); the device's chunks are first compared with stream.nemo_chunk_features, bit for bit
+(profiles/r28_stream_nemo_chunks.json).  --repeats sets how often every arm runs.
 """
 import argparse
 import json
@@ -351,7 +358,53 @@ NEMO = dict(n_mels=80, pad_frames=8, drop_silence=True, preemphasis=0.97)
 NEMO_ARMS = {"plain": "one css_stream_push_many per tick, no hand-off",
              "whisper": "the same, every stream with the Whisper hand-off (80 bands, pad 8, drop silence)",
              "nemo": "the same, every stream with the NeMo hand-off (80 bands, pad 8, drop silence, p = 0.97)",
-             "host": "the plain tick, then the raw NeMo features of every returned piece on the CPU (numpy float32 on BLAS: host_nemo_features)"}
+             "host": "the plain tick, then the raw NeMo features of every returned piece on the CPU (numpy float32 on BLAS: host_nemo_features)",
+             "history": "the NeMo tick, every stream with a frame history of 3000 frames (nemo_history=3000); behind the last pass, one "
+                        "nemo_chunks call of 48 per-feature float16 chunks against the host's route for the same chunks"}
+CHUNK_HISTORY = 3000
+
+
+def chunk_calls(group, streams, kept, repeats=20):
+    """--nemo --chunks, behind the timed ticks: (b) one CssStreamGroup.nemo_chunks call of 48 per-feature float16 chunks and (c) the
+    host's route for the same chunks -- numpy's per-feature normalisation of the frames the pushes returned (`kept`), stacked and
+    uploaded into a torch tensor -- for spans of 400 frames and of up to 3000; every timed call is first checked bit-identical to
+    stream.nemo_chunk_features.  -> {n_frames: {...}}"""
+    import torch
+    import notsofar1_challenge_amd.stream as STR
+    out = {}
+    # the 48 (stream, speaker) pairs that hold the most frames; a span is as long as the shortest of them allows
+    pairs = sorted(((kept[i][k].shape[1], i, k) for i in range(len(streams)) for k in range(3)), reverse=True)[:48]
+    for want in (400, 3000):
+        n = min(want, pairs[-1][0], CHUNK_HISTORY)
+        if n < 1:
+            continue
+        reqs = [(streams[i], k) for _, i, k in pairs]
+        spans = [kept[streams.index(s)][k][:, -n:] for s, k in reqs]
+        buf = torch.empty((len(reqs), NEMO["n_mels"], n), dtype=torch.float16, device="cuda")
+        got = group.nemo_chunks([(s, k, None, n) for s, k in reqs], n, "per_feature", "float16", 0.0, out=buf).cpu().numpy()
+        same = all(np.array_equal(got[i].view(np.uint16), STR.nemo_chunk_features(spans[i], n, "per_feature", "float16").view(np.uint16))
+                   for i in range(len(reqs)))
+        if not same:   # (no timing of a call that does not give the statement's bits)
+            raise SystemExit(f"nemo_chunks of {n} frames differs from stream.nemo_chunk_features: nothing is timed")
+        dev, host = [], []
+        for _ in range(repeats):
+            t = time.perf_counter()
+            group.nemo_chunks([(s, k, None, n) for s, k in reqs], n, "per_feature", "float16", 0.0, out=buf)
+            dev.append((time.perf_counter() - t) * 1e3)
+            t = time.perf_counter()
+            batch = np.stack(spans)
+            mean = batch.mean(axis=2, dtype=np.float64)
+            std = np.sqrt(((batch - mean[:, :, None]) ** 2).sum(axis=2) / max(n - 1, 1))
+            norm = ((batch - mean.astype(np.float32)[:, :, None]) / (std.astype(np.float32)[:, :, None] + np.float32(1e-5))).astype(np.float16)
+            up = torch.from_numpy(norm).cuda()
+            torch.cuda.synchronize()
+            host.append((time.perf_counter() - t) * 1e3)
+        close = float(np.abs(up.cpu().numpy().astype(np.float32) - got.astype(np.float32)).max())
+        out[str(want)] = {"n_frames": n, "chunks": len(reqs), "launches": group.window_launches, "bit_identical_to_numpy_statement": bool(same),
+                          "device_call_ms_median": round(float(np.median(dev)), 4), "device_call_ms_min": round(min(dev), 4),
+                          "host_route_ms_median": round(float(np.median(host)), 4), "host_route_ms_min": round(min(host), 4),
+                          "host_route_max_abs_difference": close}
+    return out
 
 
 def host_nemo_features(tables, x, p):
@@ -376,7 +429,13 @@ def nemo_arm(arm, n_streams, seconds=60.0, round_s=1.5, passes=2):
     passes of grouped ticks over `n_streams` meetings; prints one JSON line {"arm", "tick_ms": [...], "bit_identical", ...}."""
     import notsofar1_challenge_amd._lib as LIB
     if os.environ.get("CSS_MI355_LIBRARY"):
-        LIB.STREAM_NEMO_ABI.clear()   # (an earlier build of the library: it has no NeMo stream entries, and no arm on it asks for one)
+        # (an earlier build of the library: the entries it does not export yet are taken out of the binding; no arm on it asks for one)
+        import ctypes
+        LIB._share_hip_runtime_with_torch()
+        probe = ctypes.CDLL(LIB.LIB_PATH)
+        for table in (LIB.STREAM_NEMO_ABI, LIB.NEMO_CHUNK_ABI):
+            for name in [n for n in table if not hasattr(probe, n)]:
+                del table[name]
     import notsofar1_challenge_amd.css as CSS
     import notsofar1_challenge_amd.separator as SEP
     import notsofar1_challenge_amd.stream as STR
@@ -391,9 +450,10 @@ def nemo_arm(arm, n_streams, seconds=60.0, round_s=1.5, passes=2):
     refs = [sep.handle.run(x, rc).copy() for x in recs]
     step = int(round_s * FS)
     tables = STR.nemo_tables(NEMO["n_mels"])
-    ms, same, frames = [], True, []
+    ms, same, frames, chunk_res = [], True, [], None
     for p in range(passes + 1):
-        kw = dict(handoff=HANDOFF) if arm == "whisper" else dict(nemo=NEMO) if arm == "nemo" else {}
+        kw = {"whisper": dict(handoff=HANDOFF), "nemo": dict(nemo=NEMO), "history": dict(nemo=NEMO, nemo_history=CHUNK_HISTORY)}.get(arm, {})
+        kept = [[np.zeros((NEMO["n_mels"], 0), np.float32) for _ in range(3)] for _ in recs]   # (the host's own history, for the host's route)
         streams = [STR.CssStream(sep, cfg, **kw) for _ in recs]
         group = STR.CssStreamGroup(streams)
         em = [0] * n_streams
@@ -409,11 +469,15 @@ def nemo_arm(arm, n_streams, seconds=60.0, round_s=1.5, passes=2):
                 if arm == "host":
                     frames.append(sum(f.shape[1] for f in feats))
                 elif arm != "plain":
-                    frames.append(sum(m.shape[1] for s in streams for m in (s.nemo if arm == "nemo" else s.handoff).mel))
+                    frames.append(sum(m.shape[1] for s in streams for m in (s.handoff if arm == "whisper" else s.nemo).mel))
+            if arm == "history" and p == passes:
+                kept = [[np.concatenate([kept[i][k], s.nemo.mel[k]], axis=1)[:, -CHUNK_HISTORY:] for k in range(3)] for i, s in enumerate(streams)]
             for i, got in enumerate(res):
                 got = np.stack(got)
                 same = same and bool(np.array_equal(got, refs[i][:, em[i]:em[i] + got.shape[1]]))
                 em[i] += got.shape[1]
+        if arm == "history" and p == passes:
+            chunk_res = chunk_calls(group, streams, kept)
         for i, s in enumerate(streams):
             got = np.stack(s.finish())
             same = same and bool(np.array_equal(got, refs[i][:, em[i]:])) and em[i] + got.shape[1] == refs[i].shape[1]
@@ -422,14 +486,18 @@ def nemo_arm(arm, n_streams, seconds=60.0, round_s=1.5, passes=2):
     sep.close()
     print("NEMO_ARM " + json.dumps({"arm": arm, "library": os.environ.get("CSS_MI355_LIBRARY") or "this", "tick_ms": [round(v, 4) for v in ms],
                                     "bit_identical": same, "frames_per_tick_median": float(np.median(frames)) if frames else 0.0,
-                                    "launches_products_frames_last_call": stats}))
+                                    "launches_products_frames_last_call": stats, "chunks": chunk_res}))
 
 
-def nemo_bench(n_streams, out_path, parent_library, repeats=3, passes=2):
+def nemo_bench(n_streams, out_path, parent_library, repeats=3, passes=2, chunks=False):
     """--nemo: every arm in a fresh process of its own, one after the other and alternated -- the parent commit's library (plain,
-    Whisper) between this commit's arms -- `repeats` times; per arm the tick's p50 of every repeat, their median [min, max]."""
+    Whisper) between this commit's arms -- `repeats` times; per arm the tick's p50 of every repeat, their median [min, max].
+    chunks (--nemo --chunks): the NeMo tick on the parent's library, on this one without a history and with one, and the chunk calls
+    the `history` arm times behind its last pass (profiles/r28_stream_nemo_chunks.json)."""
     import subprocess
     order = [("plain", True), ("plain", False), ("whisper", True), ("whisper", False), ("nemo", False), ("host", False)]
+    if chunks:
+        order = [("nemo", True), ("nemo", False), ("history", False)]
     if not parent_library:
         order = [o for o in order if not o[1]]
     got = {}
@@ -444,6 +512,7 @@ def nemo_bench(n_streams, out_path, parent_library, repeats=3, passes=2):
             if out.returncode != 0:   # (a child that failed ends the measurement: nothing more is started on the GPU)
                 sys.stderr.write(out.stdout[-2000:] + out.stderr[-4000:])
                 raise SystemExit(f"arm {arm} ({'parent' if parent else 'this'}) ended with {out.returncode}")
+            print(f"repeat {rep}: arm {arm} ({'parent' if parent else 'this'}) done", file=sys.stderr, flush=True)
             line = [l for l in out.stdout.splitlines() if l.startswith("NEMO_ARM ")][-1]
             got.setdefault(("parent " if parent else "this ") + arm, []).append(json.loads(line[len("NEMO_ARM "):]))
     res = {"what": "tools/stream_bench.py --nemo --streams %d: 60 s meetings, mc_v1 (18 blocks, exact float32), 1.5 s grouped ticks, every arm in a "
@@ -456,10 +525,23 @@ def nemo_bench(n_streams, out_path, parent_library, repeats=3, passes=2):
                              "ticks_per_repeat": len(runs[0]["tick_ms"]), "bit_identical": all(r["bit_identical"] for r in runs),
                              "frames_per_tick_median": runs[0]["frames_per_tick_median"],
                              "launches_products_frames_last_call": runs[0]["launches_products_frames_last_call"]}
+        if any(r.get("chunks") for r in runs):
+            res["arms"][name]["chunk_calls_per_repeat"] = [r["chunks"] for r in runs]
     a = res["arms"]
     med = lambda k: a[k]["tick_ms_median"]
-    res["extra_over_plain_ms"] = {k: round(med("this " + k) - med("this plain"), 3) for k in ("whisper", "nemo", "host")}
-    if parent_library:
+    if chunks:
+        res["what"] = res["what"].replace("--nemo ", "--nemo --chunks ")
+        res["history_minus_no_history_ms"] = round(med("this history") - med("this nemo"), 3)
+        if parent_library:
+            pr = a["parent nemo"]
+            spread = pr["tick_ms_max"] - pr["tick_ms_min"]
+            res["parent_nemo_spread_ms"] = round(spread, 3)
+            res["bar_for_history_ms"] = round(pr["tick_ms_median"] + spread + 0.03 * pr["tick_ms_median"], 3)
+            res["history_within_bar"] = bool(med("this history") <= res["bar_for_history_ms"])
+            res["this_minus_parent_nemo_ms"] = round(med("this nemo") - pr["tick_ms_median"], 3)
+    else:
+        res["extra_over_plain_ms"] = {k: round(med("this " + k) - med("this plain"), 3) for k in ("whisper", "nemo", "host")}
+    if parent_library and not chunks:
         for k in ("plain", "whisper"):
             pr = a["parent " + k]
             res["this_minus_parent_" + k + "_ms"] = round(med("this " + k) - med("parent " + k), 3)
@@ -618,14 +700,17 @@ def main():
     ap.add_argument("--passes", type=int, default=2, help="with --streams: timed passes over the recordings")
     ap.add_argument("--nemo", action="store_true", help="with --streams: plain, Whisper hand-off, NeMo hand-off and the host's route, each arm in a process "
                     "of its own, alternated (profiles/r27_stream_nemo.json)")
-    ap.add_argument("--parent-library", default=None, help="with --nemo: an earlier build of the library; its plain and Whisper arms run between this one's")
+    ap.add_argument("--chunks", action="store_true", help="with --nemo: the NeMo tick on the parent's library, without and with a frame history, and one "
+                    "nemo_chunks call of 48 chunks against the host's route (profiles/r28_stream_nemo_chunks.json)")
+    ap.add_argument("--repeats", type=int, default=3, help="with --nemo: how often every arm runs")
+    ap.add_argument("--parent-library", default=None, help="with --nemo: an earlier build of the library; its arms run between this one's")
     ap.add_argument("--nemo-arm", default=None, choices=sorted(NEMO_ARMS), help="one arm of --nemo in this process (what --nemo starts)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.streams and a.nemo_arm:
         return nemo_arm(a.nemo_arm, a.streams, passes=a.passes)
     if a.streams and a.nemo:
-        return nemo_bench(a.streams, a.out, a.parent_library, passes=a.passes)
+        return nemo_bench(a.streams, a.out, a.parent_library, repeats=a.repeats, passes=a.passes, chunks=a.chunks)
     if a.streams and a.out_rate:
         return output_bench(a.streams, a.out, a.rate or FS, a.out_rate, a.out_pcm16, pinned=a.pinned, passes=a.passes)
     if a.streams:
